@@ -130,6 +130,40 @@ def test_bench_fails_loudly_without_a_gpu(z):
     assert '"metric"' not in p.stdout
 
 
+def test_bench_output_dump_stays_in_budget(tmp_path):
+    """bench.py --dump-outputs: status bytes as float32, whole below 64 MB; a batch too large for it is a fixed seeded sample whose
+    index file names the rows, the same from run to run."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    for n, world in ((1 << 20, 1), (1 << 25, 1), (1 << 24, 8)):
+        st = torch.from_numpy((np.arange(n) % 7).astype(np.uint8))
+        for run in ('a', 'b'):
+            d = tmp_path / ('%d_%d_%s' % (n, world, run))
+            for r in range(world):
+                bench.dump_outputs(str(d), [st], r, world)
+            assert sum(f.stat().st_size for f in d.iterdir()) <= bench.DUMP_BYTES
+        sfx = '_rank%d' % (world - 1) if world > 1 else ''
+        a = np.load(d / ('status%s.npy' % sfx))
+        assert a.dtype == np.float32
+        if n * 4 <= bench.DUMP_BYTES // 2 // world:
+            assert (a == np.arange(n) % 7).all()
+        else:
+            i = np.load(d / ('status_index%s.npy' % sfx))
+            assert i.dtype == np.float64 and (a == i % 7).all()
+            assert (np.load(tmp_path / ('%d_%d_a' % (n, world)) / ('status_index%s.npy' % sfx)) == i).all()
+
+
+def test_bench_rejects_zero_steps():
+    """--steps sets the number of timed steps; ms_per_step is the time of one, so a run without a timed step is an error."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and '--steps' in p.stderr
+
+
 def test_offsets_running_backwards_are_rejected(z, real_proofs):
     """Caller-supplied offsets index the blob inside the kernels: non-monotonic offsets are an argument error, not a read."""
     import numpy as np
