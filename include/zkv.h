@@ -266,13 +266,27 @@ int zkv_bn254_pairing_batch_dev(zkv_ctx* ctx, size_t n, size_t k, const uint8_t*
  * Groth16Verifier::verify_proof_with_key(vm_type, &vk, a, b, c, &signals) -> bool (common/groth16.rs:23-49) is generic over the
  * key; this context takes any key.  vk_words: alpha1.x alpha1.y | beta2.x[0] x[1] y[0] y[1] | gamma2 (4) | delta2 (4) |
  * ic[0].x ic[0].y ... ic[n_ic-1] -- 32-byte big-endian words in the layout of `VerificationKey` (common/types.rs:17-23; G2 words
- * are (imaginary, real)), 1 <= n_ic <= 6.  vm_type: ZKV_VM_RISC0 negates A, ZKV_VM_SP1 does not (groth16.rs:96-103).
- * A key holding a point the precompiles would reject makes every proof fail, as in the reference. */
+ * are (imaginary, real)), 1 <= n_ic <= ZKV_GROTH16_MAX_IC (128 per-proof signals); NULL outside that range.  vm_type: ZKV_VM_RISC0
+ * negates A, ZKV_VM_SP1 does not (groth16.rs:96-103).  A key holding a point the precompiles would reject makes every proof fail, as in
+ * the reference.  The context only copies the key; the device is touched at the first compute call.
+ * Long keys (n_ic > 6; the environment knob ZKV_LONG_KEY=1, read at creation, sends keys with 2 <= n_ic <= 6 the same way, for A/B runs)
+ * take their own vk_x tables and kernels ("Long keys"):
+ *   - device memory: 8-bit fixed-base window tables of (n_ic - 1) x 32 x 256 x 64 B (512 KB per signal: 64 MB at 128 signals) on top
+ *     of the key's other tables, plus the staged signals of the proofs in flight, 32 x (n_ic - 1) bytes per proof;
+ *   - chunks: at most 2^29 / (32 (n_ic - 1)) proofs rounded down to a power of two (the staged signals of a chunk stay within 512 MB:
+ *     2^17 proofs at 128 signals), and at most ZKV_CHUNK;
+ *   - zkv_ctx_set_aggregate_check returns ZKV_OK and changes nothing: the chunks run the ordinary per-proof path and
+ *     zkv_ctx_aggregate_counters stays {0, 0} (as for a key with alpha or beta at infinity). */
 #define ZKV_VM_GROTH16 3
+#define ZKV_GROTH16_MAX_IC 129
 zkv_ctx* zkv_groth16_ctx_create(const uint8_t* vk_words, size_t n_ic, int vm_type, int device);
 /* proofs: n x 256 bytes (a.x a.y b.x[0] b.x[1] b.y[0] b.y[1] c.x c.y); signals: n x (n_ic - 1) x 32 bytes big-endian;
  * verified[i] = 1 / 0 is the function's return value (signal >= R, malformed point, pairing product != 1 -> 0). */
 int zkv_groth16_verify_batch(zkv_ctx* ctx, size_t n, const uint8_t* proofs, const uint8_t* signals, uint8_t* verified);
+/* The same with proofs, signals and verdicts resident in HBM (device pointers; any key, short or long), enqueued on `stream` (a hipStream_t;
+ * NULL = the context's stream) without copies or host synchronisation; chunked internally, verdicts turned into 1 / 0 on the device.
+ * zkv_ctx_synchronize or the stream tells when d_verified is written. */
+int zkv_groth16_verify_batch_dev(zkv_ctx* ctx, size_t n, const uint8_t* d_proofs, const uint8_t* d_signals, uint8_t* d_verified, void* stream);
 
 /* ------------------------------------------------------------------ Groth16 core pieces
  * Groth16Verifier::compute_vk_x (common/groth16.rs:51-58) for a batch: vk_x = IC[0] + sum s_i IC[i+1] with the context's

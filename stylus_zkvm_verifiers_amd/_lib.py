@@ -58,6 +58,7 @@ SYMBOLS = {
     'zkv_bn254_pairing_batch_dev': (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     'zkv_groth16_ctx_create': (_vp, [_cp, _sz, _i, _i]),
     'zkv_groth16_verify_batch': (_i, [_vp, _sz, _vp, _vp, _vp]),
+    'zkv_groth16_verify_batch_dev': (_i, [_vp, _sz, _vp, _vp, _vp, _vp]),
     'zkv_ctx_vk_x_batch': (_i, [_vp, _sz, _vp, _vp]),
     'zkv_diag_mulmod_rate': (_i, [_i, _i, _i, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'zkv_diag_issue_rate': (_i, [_i, _i, _i, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

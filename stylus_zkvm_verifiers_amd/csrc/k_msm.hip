@@ -114,6 +114,74 @@ void launch_vk_x(size_t n, const VkTables* d_tab, const Msm16& m16, const InstTa
     hipLaunchKernelGGL(k_vk_x, dim3((unsigned)((n + ZKV_BLOCK - 1) / ZKV_BLOCK)), dim3(ZKV_BLOCK), 0, s, n, d_tab, m16, inst_tab, inst, sig, out);
 }
 
+// Long keys (LongKey, zkv_verify.h): G lanes per proof walk strided shares of the proof's (signal, window) pairs, a butterfly of complete
+// additions folds the G partial sums (log2 G rounds; all lanes of a group share the proof, so a group enters and leaves together), and
+// the group's first lane adds IC[0], normalises and stores.  G = 1 for big chunks, 16 / 64 for small ones (zkv_capi.hip, msm_lanes_long).
+template <uint32_t G> __global__ __launch_bounds__(64) void k_msm_long(size_t n, const VkTables* __restrict__ vk, LongKey lk, Workspace ws) {
+    const uint32_t lane = threadIdx.x % G;
+    const size_t i = (size_t)blockIdx.x * (64 / G) + threadIdx.x / G;
+    if (i >= n) return;
+    uint32_t flags = ws.flags[i];
+    if (!(flags & FL_ALIVE)) return;
+    auto digit = [&](uint32_t b, uint32_t w) { return (lk.sig[(size_t)(8 * b + (w >> 2)) * lk.stride + i] >> ((w & 3) * 8)) & 255u; };
+    G1J acc = long_msm_slice(lk.n_sig, lk.win, lk.tab, digit, lane, G);
+#pragma unroll 1
+    for (uint32_t m = G / 2; m > 0; m >>= 1) acc = g1j_add(acc, g1j_shfl_xor(acc, (int)m));
+    if (lane != 0) return;
+    if (!vk->base_inf) acc = g1j_add_affine(acc, vk->base.x, vk->base.y);
+    PrepOut in;
+    in.ax = ws_ld(ws.prep, ws.cap, 0, i); in.ay = ws_ld(ws.prep, ws.cap, 8, i);
+    in.cx = ws_ld(ws.prep, ws.cap, 16, i); in.cy = ws_ld(ws.prep, ws.cap, 24, i);
+    G1Norm o;
+    msm_normalize_acc(acc, in, flags, o);
+    ws_st(ws.norm, ws.cap, 0, i, o.axs); ws_st(ws.norm, ws.cap, 8, i, o.ays);
+    ws_st(ws.norm, ws.cap, 16, i, o.lxs); ws_st(ws.norm, ws.cap, 24, i, o.lys);
+    ws_st(ws.norm, ws.cap, 32, i, o.cxs); ws_st(ws.norm, ws.cap, 40, i, o.cys);
+    ws.flags[i] = flags;
+}
+void launch_msm_long(size_t n, uint32_t lanes, const VkTables* d_tab, const LongKey& lk, const Workspace& ws, hipStream_t s) {
+    if (!n) return;
+    const dim3 grid((unsigned)((n * lanes + 63) / 64)), block(64);
+    if (lanes == 64) hipLaunchKernelGGL(k_msm_long<64>, grid, block, 0, s, n, d_tab, lk, ws);
+    else if (lanes == 16) hipLaunchKernelGGL(k_msm_long<16>, grid, block, 0, s, n, d_tab, lk, ws);
+    else hipLaunchKernelGGL(k_msm_long<1>, grid, block, 0, s, n, d_tab, lk, ws);
+}
+// compute_vk_x alone for a long key: the same walk, digits read straight from the caller's big-endian signals (byte 31 - w of signal b)
+template <uint32_t G> __global__ __launch_bounds__(64) void k_vk_x_long(size_t n, const VkTables* __restrict__ vk, LongKey lk, const uint8_t* __restrict__ sig,
+                                                                         uint8_t* __restrict__ out) {
+    const uint32_t lane = threadIdx.x % G;
+    const size_t i = (size_t)blockIdx.x * (64 / G) + threadIdx.x / G;
+    if (i >= n) return;
+    const uint8_t* row = sig + (size_t)32 * lk.n_sig * i;
+    auto digit = [&](uint32_t b, uint32_t w) { return (uint32_t)row[32 * b + 31 - w]; };
+    G1J acc = long_msm_slice(lk.n_sig, lk.win, lk.tab, digit, lane, G);
+#pragma unroll 1
+    for (uint32_t m = G / 2; m > 0; m >>= 1) acc = g1j_add(acc, g1j_shfl_xor(acc, (int)m));
+    if (lane != 0) return;
+    if (!vk->base_inf) acc = g1j_add_affine(acc, vk->base.x, vk->base.y);
+    G1A a; uint32_t inf;
+    g1j_to_affine(acc, a, inf);
+    uint32_t r[8];
+    uint8_t* o = out + 64 * i;
+#pragma unroll 1
+    for (int c = 0; c < 2; c++) {
+        fp_to_raw(r, c ? a.y : a.x);
+#pragma unroll 1
+        for (int k = 0; k < 8; k++) {
+            uint32_t v = r[7 - k];
+            o[32 * c + 4 * k] = (uint8_t)(v >> 24); o[32 * c + 4 * k + 1] = (uint8_t)(v >> 16);
+            o[32 * c + 4 * k + 2] = (uint8_t)(v >> 8); o[32 * c + 4 * k + 3] = (uint8_t)v;
+        }
+    }
+}
+void launch_vk_x_long(size_t n, uint32_t lanes, const VkTables* d_tab, const LongKey& lk, const uint8_t* sig, uint8_t* out, hipStream_t s) {
+    if (!n) return;
+    const dim3 grid((unsigned)((n * lanes + 63) / 64)), block(64);
+    if (lanes == 64) hipLaunchKernelGGL(k_vk_x_long<64>, grid, block, 0, s, n, d_tab, lk, sig, out);
+    else if (lanes == 16) hipLaunchKernelGGL(k_vk_x_long<16>, grid, block, 0, s, n, d_tab, lk, sig, out);
+    else hipLaunchKernelGGL(k_vk_x_long<1>, grid, block, 0, s, n, d_tab, lk, sig, out);
+}
+
 void launch_msm(size_t n, const VkTables* d_tab, const Msm16& m16, const InstTab* inst_tab, const Workspace& ws, hipStream_t s) {
     if (!n) return;
     hipLaunchKernelGGL(k_msm, dim3((unsigned)((n + ZKV_BLOCK - 1) / ZKV_BLOCK)), dim3(ZKV_BLOCK), 0, s, n, d_tab, m16, inst_tab, ws);

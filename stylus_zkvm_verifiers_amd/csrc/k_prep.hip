@@ -4,11 +4,14 @@
 
 namespace zkv {
 
-__device__ __forceinline__ void store_prep(const Workspace& ws, size_t i, const PrepOut& o) {
+__device__ __forceinline__ void store_prep_points(const Workspace& ws, size_t i, const PrepOut& o) {
     ws_st(ws.prep, ws.cap, 0, i, o.ax); ws_st(ws.prep, ws.cap, 8, i, o.ay);
     ws_st(ws.prep, ws.cap, 16, i, o.cx); ws_st(ws.prep, ws.cap, 24, i, o.cy);
     ws_st(ws.prep, ws.cap, 32, i, o.bx.c0); ws_st(ws.prep, ws.cap, 40, i, o.bx.c1);
     ws_st(ws.prep, ws.cap, 48, i, o.by.c0); ws_st(ws.prep, ws.cap, 56, i, o.by.c1);
+}
+__device__ __forceinline__ void store_prep(const Workspace& ws, size_t i, const PrepOut& o) {
+    store_prep_points(ws, i, o);
 #pragma unroll
     for (int b = 0; b < MAX_VAR; b++) {
 #pragma unroll
@@ -163,6 +166,50 @@ __global__ __launch_bounds__(ZKV_BLOCK) void k_prep_groth16(PrepArgs a, Workspac
     ws.flags[i] = flags;
     ws.g2bad[i] = 0;
     a.status[i] = ST_VERIFICATION_FAILED;
+}
+
+// The same for a long key: all n_sig signals range-checked (groth16.rs:32) and staged column-major as little-endian limbs for k_msm_long
+// (limb k of signal b at sig[(8 b + k) * stride + i]: a wavefront's reads of one limb are 256 contiguous bytes); the scalar rows of
+// ws.prep (MAX_VAR wide) are not used.
+__global__ __launch_bounds__(ZKV_BLOCK) void k_prep_groth16_long(PrepArgs a, Workspace ws, uint32_t* __restrict__ sig, size_t stride) {
+    size_t i = (size_t)blockIdx.x * ZKV_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    uint32_t flags = 0;
+    if (!a.force_fail) {
+        bool ok = true;
+#pragma unroll 1
+        for (uint32_t b = 0; b < a.n_sig; b++) {
+            uint32_t s[8];
+            load_be256(s, a.in32_a + 32 * ((size_t)a.n_sig * i + b));
+            ok = raw_lt_r(s) && ok;
+#pragma unroll
+            for (int k = 0; k < 8; k++) sig[(size_t)(8 * b + k) * stride + i] = s[k];
+        }
+        if (ok) {
+            PrepOut o;
+            uint32_t w[8][8];
+            const uint8_t* rec = a.blob + 256 * i;
+#pragma unroll 1
+            for (int j = 0; j < 8; j++) load_be256(w[j], rec + 32 * j);
+            if (prep_points(w, a.negate_a != 0, o)) { flags = o.flags; store_prep_points(ws, i, o); }
+        }
+    }
+    ws.flags[i] = flags;
+    ws.g2bad[i] = 0;
+    a.status[i] = ST_VERIFICATION_FAILED;
+}
+void launch_prep_groth16_long(const PrepArgs& a, const Workspace& ws, uint32_t* sig, size_t stride, hipStream_t s) {
+    if (!a.n) return;
+    hipLaunchKernelGGL(k_prep_groth16_long, dim3((unsigned)((a.n + ZKV_BLOCK - 1) / ZKV_BLOCK)), dim3(ZKV_BLOCK), 0, s, a, ws, sig, stride);
+}
+// zkv_groth16_verify_batch_dev: status bytes -> 1 (ZKV_STATUS_OK) / 0, in place
+__global__ __launch_bounds__(ZKV_BLOCK) void k_status_to_bool(size_t n, uint8_t* __restrict__ st) {
+    size_t i = (size_t)blockIdx.x * ZKV_BLOCK + threadIdx.x;
+    if (i < n) st[i] = st[i] == ST_OK ? 1 : 0;
+}
+void launch_status_to_bool(size_t n, uint8_t* status, hipStream_t s) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_status_to_bool, dim3((unsigned)((n + ZKV_BLOCK - 1) / ZKV_BLOCK)), dim3(ZKV_BLOCK), 0, s, n, status);
 }
 
 void launch_prep_groth16(const PrepArgs& a, const Workspace& ws, hipStream_t s) {

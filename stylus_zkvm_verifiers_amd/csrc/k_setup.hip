@@ -56,6 +56,21 @@ void launch_setup_msm16(const VkTables* d_tab, const Msm16& m, G1A* tab, uint32_
     hipLaunchKernelGGL(k_setup_msm16, dim3(rows * 16), dim3(64), 0, s, d_tab, m, tab, rows);
 }
 
+// Long keys (LongKey): precompile validity of IC[1..] -- any invalid point fails every proof -- and their window rows, in an allocation of
+// their own.  ic: n_sig x 16 raw limbs.  Validation: lanes stride over the points; one window row per lane, one block per signal.
+__global__ __launch_bounds__(64) void k_setup_long_validate(const uint32_t* __restrict__ ic, uint32_t n_sig, VkTables* __restrict__ t) {
+    if (!long_ic_valid(ic, blockIdx.x * 64 + threadIdx.x, n_sig, gridDim.x * 64)) atomicAnd(&t->vk_valid, 0u);
+}
+__global__ __launch_bounds__(64) void k_setup_long_rows(const uint32_t* __restrict__ ic, G1A* __restrict__ tab, uint32_t* __restrict__ win) {
+    const uint32_t b = blockIdx.x, w = threadIdx.x;
+    if (w < (uint32_t)MSM_MAX_WINDOWS) setup_long_row((const uint32_t(*)[8])(ic + 16 * (size_t)b), w, tab + ((size_t)b * MSM_MAX_WINDOWS + w) * MSM_DIGITS, win + b);
+}
+void launch_setup_long(const uint32_t* d_ic, uint32_t n_sig, VkTables* d_tab, G1A* tab, uint32_t* win, hipStream_t s) {
+    if (!n_sig) return;
+    hipLaunchKernelGGL(k_setup_long_validate, dim3((n_sig + 63) / 64), dim3(64), 0, s, d_ic, n_sig, d_tab);     // after k_setup_validate (same stream)
+    hipLaunchKernelGGL(k_setup_long_rows, dim3(n_sig), dim3(64), 0, s, d_ic, tab, win);
+}
+
 void launch_setup(const VkRaw* d_raw, VkTables* d_tab, hipStream_t s) {
     hipLaunchKernelGGL(k_setup_validate, dim3(1), dim3(64), 0, s, d_raw, d_tab);
     hipLaunchKernelGGL(k_setup_base, dim3(1), dim3(64), 0, s, d_raw, d_tab);

@@ -38,8 +38,12 @@ struct zkv_ctx {
     std::vector<InstTab> inst_host;          // copy of the device table (selectors derived on the device) for the getters
     InstTab* d_inst = nullptr;
     uint32_t* d_inst_idx = nullptr;
-    uint8_t gvk[448 + 64 * MAX_IC] = {0};    // ZKV_VM_GROTH16: the caller's verification key
+    std::vector<uint8_t> gvk;                // ZKV_VM_GROTH16: the caller's verification key (448 + 64 n_ic bytes)
     uint32_t g_n_ic = 0; bool g_negate = false, vk_invalid = false;
+    // long-key path (n_ic > MAX_IC, or ZKV_LONG_KEY=1 at creation): IC[1..] in tables of their own (LongKey) and the staged signals of a chunk
+    bool long_key = false;
+    G1A* d_ltab = nullptr; uint32_t* d_lwin = nullptr; uint32_t* d_lsig = nullptr;
+    size_t lsig_cap = 0;
     // device side (created lazily on the first compute call)
     bool dev_ready = false;
     hipStream_t stream = nullptr;
@@ -267,12 +271,12 @@ static void ctx_free_device(zkv_ctx* c) {
                      (void**)&c->d_rv_all, (void**)&c->d_inst, (void**)&c->d_inst_idx, (void**)&c->d_pkey, (void**)&c->d_plonk_tab,
                      (void**)&c->d_agg_tab, (void**)&c->d_agg, (void**)&c->ws2.prep, (void**)&c->ws2.norm, (void**)&c->ws2.f, (void**)&c->ws2.fe,
                      (void**)&c->ws2.flags, (void**)&c->ws2.g2bad, (void**)&c->d_status2, (void**)&c->d_agg_cnt, (void**)&c->ws3.prep, (void**)&c->ws3.flags,
-                     (void**)&c->ws3.g2bad, (void**)&c->d_status3, (void**)&c->d_agg_idx};
+                     (void**)&c->ws3.g2bad, (void**)&c->d_status3, (void**)&c->d_agg_idx, (void**)&c->d_ltab, (void**)&c->d_lwin, (void**)&c->d_lsig};
     for (void** p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
     c->ws2.cap = 0; c->ws3 = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0}; c->agg_cap = 0; c->agg_key_ok = false;
     for (int k = 0; k < 6; k++) { if (c->hb[k]) (void)hipFree(c->hb[k]); c->hb[k] = nullptr; c->hb_cap[k] = 0; }
     for (int k = 0; k < 20; k++) { if (c->mx[k]) (void)hipFree(c->mx[k]); c->mx[k] = nullptr; c->mx_cap[k] = 0; }
-    c->ws.cap = 0; c->blob_cap = c->pv_cap = 0; c->cd_cap[0] = c->cd_cap[1] = c->st_all_cap = c->rv_all_cap = 0;
+    c->ws.cap = 0; c->lsig_cap = 0; c->blob_cap = c->pv_cap = 0; c->cd_cap[0] = c->cd_cap[1] = c->st_all_cap = c->rv_all_cap = 0;
     hipEvent_t* evs[] = {&c->ev[0], &c->ev[1], &c->ev[2], &c->ev[3], &c->ev[4], &c->ev[5], &c->ev_wire[0], &c->ev_wire[1], &c->ev_done,
                          &c->ev_copied[0], &c->ev_copied[1], &c->ev_decoded[0], &c->ev_decoded[1], &c->ev_fork, &c->ev_join, &c->ev_seg[0], &c->ev_seg[1]};
     for (hipEvent_t* e : evs) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
@@ -300,7 +304,7 @@ static int ctx_device_setup(zkv_ctx* c) {
     if (c->vm != ZKV_VM_BN254 && c->vm != ZKV_VM_MIXED) {
         VkRaw raw;
         if (c->vm == ZKV_VM_RISC0 || c->vm == ZKV_VM_RISC0_SET) host::fill_vk_risc0(raw, c->control_root_0, c->control_root_1, c->control_id);
-        else if (c->vm == ZKV_VM_GROTH16) host::fill_vk_generic(raw, c->gvk, c->g_n_ic);
+        else if (c->vm == ZKV_VM_GROTH16) host::fill_vk_generic(raw, c->gvk.data(), c->long_key ? 1u : c->g_n_ic);   // long key: IC[0] only here
         else if (c->vm == ZKV_VM_SP1_PLONK) {
             // the pairing of a PLONK proof has two FIXED pairs: the SRS's [1]_2 and [tau]_2 take the line-table slots of gamma and
             // delta; there is no (alpha, beta) pair (alpha = infinity contributes 1) and no IC points
@@ -318,7 +322,26 @@ static int ctx_device_setup(zkv_ctx* c) {
         HIP_TRY(hipMemcpyAsync(d_raw, &raw, sizeof raw, hipMemcpyHostToDevice, c->stream));
         launch_setup(d_raw, c->d_tab, c->stream);
         HIP_TRY(hipGetLastError());
-        const bool agg_vm = c->vm == ZKV_VM_RISC0 || c->vm == ZKV_VM_RISC0_SET || c->vm == ZKV_VM_SP1 || c->vm == ZKV_VM_GROTH16;
+        if (c->long_key) {
+            // IC[1..n_ic-1]: validity (folded into vk_valid) and window rows, 512 KB per signal; the raw points (mx[1]) only until set-up is done
+            const uint32_t n_sig = c->g_n_ic - 1;
+            std::vector<uint32_t> ic((size_t)16 * n_sig);
+            for (uint32_t b = 0; b < n_sig; b++) {
+                host::be_to_limbs(&ic[16 * (size_t)b], c->gvk.data() + 448 + 64 * (size_t)(b + 1));
+                host::be_to_limbs(&ic[16 * (size_t)b + 8], c->gvk.data() + 480 + 64 * (size_t)(b + 1));
+            }
+            const size_t tab_bytes = (size_t)n_sig * LONG_ROW_ENTRIES * sizeof(G1A);
+            HIP_TRY(hipMalloc(&c->mx[1], sizeof(uint32_t) * ic.size()));
+            HIP_TRY(hipMalloc(&c->d_ltab, tab_bytes));
+            HIP_TRY(hipMalloc(&c->d_lwin, sizeof(uint32_t) * n_sig));
+            HIP_TRY(hipMemsetAsync(c->d_ltab, 0, tab_bytes, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->mx[1], ic.data(), sizeof(uint32_t) * ic.size(), hipMemcpyHostToDevice, c->stream));
+            launch_setup_long((const uint32_t*)c->mx[1], n_sig, c->d_tab, c->d_ltab, c->d_lwin, c->stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(c->stream));        // `ic` is a pageable host buffer about to go out of scope
+        }
+        // (a long key takes no aggregate check: its chunks run the ordinary per-proof path)
+        const bool agg_vm = c->vm == ZKV_VM_RISC0 || c->vm == ZKV_VM_RISC0_SET || c->vm == ZKV_VM_SP1 || (c->vm == ZKV_VM_GROTH16 && !c->long_key);
         if (agg_vm && msm_window_bits() == 16) {
             // 16-bit window rows for the vk_x stage of big batches: 4 MB per row, built from the 8-bit rows k_setup_msm has just written
             Msm16 m = {nullptr, {0, 0, 0, 0, 0}};
@@ -642,6 +665,18 @@ static void enqueue_agg_plonk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool
     if (timed) (void)hipEventRecord(c->ev[5], s);
 }
 
+// Long keys (LongKey): the table walk of a chunk of n proofs runs with G lanes per proof -- 64 up to ZKV_MSM_WAVE_BELOW proofs (one proof
+// per wavefront, as k_msm_w), 16 below ZKV_LONG_LANE_BELOW (default 2^18: a chunk of fewer proofs has too few wavefronts with one lane
+// per proof to fill the chip -- 2^18 proofs are four per SIMD -- while 32 (n_ic - 1) / G additions per lane stay far above the 4 of the
+// butterfly), one lane per proof above.  zkv_ctx_set_lanes_per_proof fixes it: 2 -> 1, 16 -> 16, 64 / 128 -> 64.
+static uint32_t msm_lanes_long(const zkv_ctx* c, size_t n) {
+    if (c->lanes) return c->lanes == 2 ? 1u : c->lanes == 16 ? 16u : 64u;
+    if (n <= msm_wave_below()) return 64;
+    const char* e = getenv("ZKV_LONG_LANE_BELOW");
+    return n < (e ? (size_t)strtoull(e, nullptr, 10) : ((size_t)1 << 18)) ? 16u : 1u;
+}
+static LongKey long_key_of(const zkv_ctx* c) { return LongKey{c->d_ltab, c->d_lwin, c->d_lsig, c->lsig_cap, c->g_n_ic - 1}; }
+
 // Enqueues the five stages for one chunk (all pointers device-resident).
 static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool timed) {
     if (timed) (void)hipEventRecord(c->ev[0], s);
@@ -667,6 +702,7 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
         return;
     }
     if (c->vm == ZKV_VM_RISC0 || c->vm == ZKV_VM_RISC0_SET) launch_prep_risc0(a, c->consts, c->ws, s);
+    else if (c->vm == ZKV_VM_GROTH16 && c->long_key) launch_prep_groth16_long(a, c->ws, c->d_lsig, c->lsig_cap, s);
     else if (c->vm == ZKV_VM_GROTH16) launch_prep_groth16(a, c->ws, s);
     else launch_prep_sp1(a, c->ws, s);
     if (timed) (void)hipEventRecord(c->ev[1], s);
@@ -678,7 +714,8 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
         // of the last `tail` through their own small-batch mapping (whose Miller kernels leave the subgroup test of B to k_g2chk2)
         const size_t head = a.n - tail;
         const Workspace wt = ws_from(c->ws, head);
-        launch_msm(a.n, c->d_tab, c->m16, a.inst ? c->d_inst : nullptr, c->ws, s);
+        if (c->long_key) launch_msm_long(a.n, msm_lanes_long(c, a.n), c->d_tab, long_key_of(c), c->ws, s);
+        else launch_msm(a.n, c->d_tab, c->m16, a.inst ? c->d_inst : nullptr, c->ws, s);
         if (timed) (void)hipEventRecord(c->ev[2], s);
         // the tail's kernels on the second stream beside the lane-pair kernels of the others (odd number of layers), or after them
         // (tail_of_chunk); disjoint workspace rows and status bytes either way
@@ -711,7 +748,8 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
         launch_g2chk2(a.n, c->ws, a.status, c->side);
         (void)hipEventRecord(c->ev_join, c->side);
     }
-    if (a.n <= msm_wave_below()) launch_msm_w(a.n, c->d_tab, a.inst ? c->d_inst : nullptr, c->ws, s);     // one proof per wavefront
+    if (c->long_key) launch_msm_long(a.n, msm_lanes_long(c, a.n), c->d_tab, long_key_of(c), c->ws, s);
+    else if (a.n <= msm_wave_below()) launch_msm_w(a.n, c->d_tab, a.inst ? c->d_inst : nullptr, c->ws, s);     // one proof per wavefront
     else launch_msm(a.n, c->d_tab, c->m16, a.inst ? c->d_inst : nullptr, c->ws, s);
     if (timed) (void)hipEventRecord(c->ev[2], s);
     if (wide && !fork) launch_g2chk2(a.n, c->ws, a.status, s);
@@ -1079,7 +1117,7 @@ ZKV_EXPORT zkv_ctx* zkv_ctx_create_sharded(zkv_ctx* const* shards, size_t n_shar
         if (s->vm != ZKV_VM_RISC0 && s->vm != ZKV_VM_SP1 && s->vm != ZKV_VM_MIXED && s->vm != ZKV_VM_GROTH16 && s->vm != ZKV_VM_SP1_PLONK) return nullptr;
         // shards of one verifier: the same parameters everywhere (the host-visible state of shard 0 answers the getters)
         if (!s->initialized || memcmp(s->selector, shards[0]->selector, 4) || memcmp(s->control_id, shards[0]->control_id, 32) ||
-            memcmp(s->gvk, shards[0]->gvk, sizeof s->gvk) || s->g_n_ic != shards[0]->g_n_ic || s->g_negate != shards[0]->g_negate ||
+            s->gvk != shards[0]->gvk || s->g_n_ic != shards[0]->g_n_ic || s->g_negate != shards[0]->g_negate || s->long_key != shards[0]->long_key ||
             memcmp(s->plonk_hash, shards[0]->plonk_hash, 32)) return nullptr;
         if (s->vm == ZKV_VM_SP1_PLONK && (memcmp(&s->pk_raw, &shards[0]->pk_raw, sizeof s->pk_raw) || memcmp(s->pk_g2, shards[0]->pk_g2, sizeof s->pk_g2))) return nullptr;
         if (s->vm == ZKV_VM_MIXED && memcmp(s->kid[0]->selector, shards[0]->kid[0]->selector, 4)) return nullptr;
@@ -1090,7 +1128,7 @@ ZKV_EXPORT zkv_ctx* zkv_ctx_create_sharded(zkv_ctx* const* shards, size_t n_shar
     c->vm = s0->vm; c->device = s0->device; c->initialized = s0->initialized; c->id_ge_r = s0->id_ge_r;
     memcpy(c->control_root_0, s0->control_root_0, 16); memcpy(c->control_root_1, s0->control_root_1, 16);
     memcpy(c->control_id, s0->control_id, 32); memcpy(c->selector, s0->selector, 4);
-    c->consts = s0->consts; c->g_n_ic = s0->g_n_ic; c->g_negate = s0->g_negate; memcpy(c->gvk, s0->gvk, sizeof c->gvk);
+    c->consts = s0->consts; c->g_n_ic = s0->g_n_ic; c->g_negate = s0->g_negate; c->gvk = s0->gvk; c->long_key = s0->long_key;
     memcpy(c->plonk_hash, s0->plonk_hash, 32);
     c->shards.assign(shards, shards + n_shards);
     c->sh.resize(n_shards);
@@ -1846,14 +1884,45 @@ ZKV_EXPORT int zkv_bn254_pairing_batch(zkv_ctx* c, size_t n, size_t k, const uin
 }
 
 // ------------------------------------------------------------------ Groth16 core, arbitrary verification key
+// Long keys stage the signals of a chunk (32 bytes per signal and proof) next to the workspace: the chunk is capped so that they stay within
+// LONG_STAGE_BYTES (2^17 proofs at 128 signals).
+constexpr size_t LONG_STAGE_BYTES = (size_t)512 << 20;
+static size_t long_chunk(const zkv_ctx* c) {
+    const size_t per = 32 * (size_t)(c->g_n_ic - 1), cap = chunk_capacity();
+    size_t lim = 64;
+    while (lim < cap && 2 * lim * per <= LONG_STAGE_BYTES) lim *= 2;
+    return lim < cap ? lim : cap;
+}
+// device set-up and buffers for a generic-key batch of n proofs; returns the proofs per chunk through *chunk
+static int groth16_ready(zkv_ctx* c, size_t n, size_t* chunk) {
+    if (!c->long_key) {
+        const int rc = ctx_ready(c, n);
+        *chunk = c->ws.cap;
+        return rc;
+    }
+    const size_t lc = long_chunk(c);
+    int rc = ctx_ready(c, n < lc ? n : lc);
+    if (rc != ZKV_OK) return rc;
+    const size_t need = c->ws.cap < lc ? c->ws.cap : lc;
+    if (c->lsig_cap < need) {
+        if (c->d_lsig) (void)hipFree(c->d_lsig);
+        c->d_lsig = nullptr; c->lsig_cap = 0;
+        if (hipMalloc(&c->d_lsig, (size_t)32 * (c->g_n_ic - 1) * need) != hipSuccess) { (void)hipGetLastError(); return ZKV_ERR_OOM; }
+        c->lsig_cap = need;
+    }
+    *chunk = need;
+    return ZKV_OK;
+}
 ZKV_EXPORT zkv_ctx* zkv_groth16_ctx_create(const uint8_t* vk_words, size_t n_ic, int vm_type, int device) {
-    if (!vk_words || n_ic < 1 || n_ic > MAX_IC || (vm_type != ZKV_VM_RISC0 && vm_type != ZKV_VM_SP1)) return nullptr;
+    if (!vk_words || n_ic < 1 || n_ic > ZKV_GROTH16_MAX_IC || (vm_type != ZKV_VM_RISC0 && vm_type != ZKV_VM_SP1)) return nullptr;
     zkv_ctx* c = new (std::nothrow) zkv_ctx();
     if (!c) return nullptr;
     c->vm = ZKV_VM_GROTH16; c->device = device; c->initialized = true;
     memset(&c->consts, 0, sizeof c->consts);
-    memcpy(c->gvk, vk_words, 448 + 64 * n_ic);
+    try { c->gvk.assign(vk_words, vk_words + 448 + 64 * n_ic); } catch (const std::bad_alloc&) { delete c; return nullptr; }
     c->g_n_ic = (uint32_t)n_ic; c->g_negate = vm_type == ZKV_VM_RISC0;
+    const char* e = getenv("ZKV_LONG_KEY");                  // A/B knob: keys with n_ic <= MAX_IC through the long-key path as well
+    c->long_key = n_ic > (size_t)MAX_IC || (n_ic >= 2 && e && atoi(e) == 1);
     return c;
 }
 ZKV_EXPORT int zkv_groth16_verify_batch(zkv_ctx* c, size_t n, const uint8_t* proofs, const uint8_t* signals, uint8_t* verified) {
@@ -1865,9 +1934,9 @@ ZKV_EXPORT int zkv_groth16_verify_batch(zkv_ctx* c, size_t n, const uint8_t* pro
         return run_sharded(c, n, [&](zkv_ctx* k, size_t lo, size_t hi) {
             return zkv_groth16_verify_batch(k, hi - lo, proofs + 256 * lo, n_sig ? signals + (size_t)32 * n_sig * lo : signals, verified + lo); });
     std::lock_guard<std::mutex> lk(c->mu);
-    int rc = ctx_ready(c, n);
+    size_t cap = 0;
+    int rc = groth16_ready(c, n, &cap);
     if (rc != ZKV_OK) return rc;
-    const size_t cap = c->ws.cap;
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
     for (size_t base = 0; base < n; base += cap) {
         size_t m = n - base < cap ? n - base : cap;
@@ -1888,6 +1957,35 @@ ZKV_EXPORT int zkv_groth16_verify_batch(zkv_ctx* c, size_t n, const uint8_t* pro
     }
     return ZKV_OK;
 }
+ZKV_EXPORT int zkv_groth16_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_proofs, const uint8_t* d_signals, uint8_t* d_verified, void* stream) {
+    if (!c || c->vm != ZKV_VM_GROTH16) return ZKV_ERR_WRONG_CTX;
+    const uint32_t n_sig = c->g_n_ic - 1;
+    if (n && (!d_proofs || !d_verified || (n_sig && !d_signals))) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (is_sharded(c)) {
+        const DevRow rows[2] = {{d_proofs, 256}, {d_signals, (size_t)32 * n_sig}};
+        return run_sharded_dev(c, n, rows, n_sig ? 2 : 1, d_verified, nullptr, stream, [&](zkv_ctx* k, size_t m, const uint8_t* const* r, uint8_t* st, uint8_t*, hipStream_t s) {
+            return zkv_groth16_verify_batch_dev(k, m, r[0], n_sig ? r[1] : nullptr, st, s); });
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    size_t cap = 0;
+    int rc = groth16_ready(c, n, &cap);
+    if (rc != ZKV_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    for (size_t base = 0; base < n; base += cap) {
+        const size_t m = n - base < cap ? n - base : cap;
+        PrepArgs a;
+        memset(&a, 0, sizeof a);
+        a.n = m; a.blob = d_proofs + 256 * base; a.in32_a = n_sig ? d_signals + (size_t)32 * n_sig * base : nullptr;
+        a.n_sig = n_sig; a.negate_a = c->g_negate ? 1u : 0u; a.force_fail = c->vk_invalid ? 1u : 0u;
+        a.status = d_verified + base; a.recv = nullptr;
+        enqueue_chunk(c, a, s, base + cap >= n);
+        launch_status_to_bool(m, d_verified + base, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return mark_done(c, s);
+}
 
 // ------------------------------------------------------------------ Groth16 core pieces
 ZKV_EXPORT int zkv_ctx_vk_x_batch(zkv_ctx* c, size_t n, const uint8_t* var_signals, uint8_t* out) {
@@ -1899,16 +1997,18 @@ ZKV_EXPORT int zkv_ctx_vk_x_batch(zkv_ctx* c, size_t n, const uint8_t* var_signa
     // per-proof signals: two for the RISC Zero / SP1 keys, all n_ic - 1 for a generic key (k_vk_x reads n_var x 32 bytes per proof)
     const size_t sig = 32 * (size_t)(c->vm == ZKV_VM_GROTH16 ? c->g_n_ic - 1 : 2);
     std::lock_guard<std::mutex> lk(c->mu);
-    int rc = ctx_ready(c, n);
+    size_t cap = 0;
+    int rc = c->vm == ZKV_VM_GROTH16 ? groth16_ready(c, n, &cap) : ctx_ready(c, n);
     if (rc != ZKV_OK) return rc;
-    const size_t cap = c->ws.cap;
+    if (c->vm != ZKV_VM_GROTH16) cap = c->ws.cap;
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
     for (size_t base = 0; base < n; base += cap) {
         size_t m = n - base < cap ? n - base : cap;
         if ((rc = grow(&c->d_blob, &c->blob_cap, m * sig + 8)) != ZKV_OK) return rc;
         if ((rc = grow(&c->d_pv, &c->pv_cap, m * 64 + 8)) != ZKV_OK) return rc;
         if (sig) HIP_TRY(hipMemcpyAsync(c->d_blob, var_signals + sig * base, sig * m, hipMemcpyHostToDevice, c->stream));
-        launch_vk_x(m, c->d_tab, c->m16, nullptr, nullptr, c->d_blob, c->d_pv, c->stream);
+        if (c->long_key) launch_vk_x_long(m, msm_lanes_long(c, m), c->d_tab, long_key_of(c), c->d_blob, c->d_pv, c->stream);
+        else launch_vk_x(m, c->d_tab, c->m16, nullptr, nullptr, c->d_blob, c->d_pv, c->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(out + 64 * base, c->d_pv, 64 * m, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2084,7 +2184,8 @@ ZKV_EXPORT int zkv_ctx_reserve(zkv_ctx* c, size_t n) {
         return ctx_device_init(c);
     }
     std::lock_guard<std::mutex> lk(c->mu);
-    return ctx_ready(c, n);
+    size_t chunk;
+    return c->vm == ZKV_VM_GROTH16 ? groth16_ready(c, n, &chunk) : ctx_ready(c, n);
 }
 ZKV_EXPORT int zkv_ctx_synchronize(zkv_ctx* c) {
     if (!c) return ZKV_ERR_INVALID_ARG;

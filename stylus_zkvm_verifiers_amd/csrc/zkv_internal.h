@@ -80,6 +80,12 @@ void launch_prep_groth16(const PrepArgs& a, const Workspace& ws, hipStream_t s);
 void launch_setup_msm16(const VkTables* d_tab, const Msm16& m, G1A* tab, uint32_t rows, hipStream_t s);
 void launch_msm(size_t n, const VkTables* d_tab, const Msm16& m16, const InstTab* inst_tab, const Workspace& ws, hipStream_t s);
 void launch_msm_w(size_t n, const VkTables* d_tab, const InstTab* inst_tab, const Workspace& ws, hipStream_t s);
+// long keys (n_ic > MAX_IC or ZKV_LONG_KEY=1; LongKey in zkv_verify.h)
+void launch_setup_long(const uint32_t* d_ic, uint32_t n_sig, VkTables* d_tab, G1A* tab, uint32_t* win, hipStream_t s);
+void launch_prep_groth16_long(const PrepArgs& a, const Workspace& ws, uint32_t* sig, size_t stride, hipStream_t s);
+void launch_msm_long(size_t n, uint32_t lanes, const VkTables* d_tab, const LongKey& lk, const Workspace& ws, hipStream_t s);
+void launch_vk_x_long(size_t n, uint32_t lanes, const VkTables* d_tab, const LongKey& lk, const uint8_t* sig, uint8_t* out, hipStream_t s);
+void launch_status_to_bool(size_t n, uint8_t* status, hipStream_t s);
 void launch_setup_instances(const VkRaw* d_raw, const InstConsts& k, const InstRaw* d_in, InstTab* d_out, uint32_t n_inst, hipStream_t s);
 void launch_vk_x(size_t n, const VkTables* d_tab, const Msm16& m16, const InstTab* inst_tab, const uint32_t* inst, const uint8_t* sig, uint8_t* out, hipStream_t s);
 // lane-pair variants (k_pair.hip): one proof per two lanes, two waves per SIMD

@@ -25,7 +25,7 @@ enum : uint32_t { FL_ALIVE = 1u, FL_A_INF = 2u, FL_B_INF = 4u, FL_C_INF = 8u, FL
 constexpr int N_LINES = 88;          // 65 doublings + 21 NAF additions + 2 Frobenius additions
 constexpr int MSM_MAX_WINDOWS = 32;  // 8-bit windows over a 256-bit scalar
 constexpr int MSM_DIGITS = 256;
-constexpr int MAX_IC = 6;
+constexpr int MAX_IC = 6;           // generic keys with more IC points take the long-key path (LongKey below)
 constexpr int MAX_VAR = 5;           // per-proof signals (risc0 and sp1 use 2; a generic key uses all n_ic - 1)
 
 // Raw verification key handed to the set-up kernel: canonical values as 8 x 32-bit little-endian limbs.
@@ -56,6 +56,13 @@ struct VkTables {
 // (setup_msm16_chunk); tab == nullptr: not built (ZKV_MSM_WINDOW_BITS=8, or a generic key with more than MSM16_MAX_ROWS rows).
 constexpr uint32_t MSM16_MAX_ROWS = 32;
 struct Msm16 { const G1A* tab; uint32_t row0[MAX_VAR]; };
+// Long keys' vk_x tables and a chunk's staged signals (see long_msm_slice)
+struct LongKey {
+    const G1A* tab; const uint32_t* win;
+    const uint32_t* sig; size_t stride;      // staged signals: limb k of signal b of proof i at sig[(8 b + k) * stride + i] (k_prep_groth16_long)
+    uint32_t n_sig;
+};
+constexpr uint32_t LONG_ROW_ENTRIES = MSM_MAX_WINDOWS * MSM_DIGITS;     // table entries per signal
 
 // Verifier sets: raw parameters, set-up constants and the per-instance device table (see setup_instance).
 struct InstRaw { uint8_t control_root[32]; uint8_t control_id[32]; };
@@ -227,6 +234,25 @@ ZKV_HD void msm_normalize_acc(const G1J& acc, const PrepOut& in, uint32_t& flags
     out.lys = fp_mul(fp_mul(z2, acc.z), iyl);            // Z^3 / Y
 }
 ZKV_HD void msm_normalize(const VkTables& vk, const PrepOut& in, uint32_t& flags, G1Norm& out) { msm_normalize(vk, in, flags, out, vk.base, vk.base_inf); }
+
+// ---------------------------------------------------------------- stage MSM for long keys (n_ic > MAX_IC, or ZKV_LONG_KEY=1)
+// Their IC[1..n_ic-1] live outside VkTables (which then describes alpha, beta, gamma, delta and IC[0] only): the raw points, one
+// window count per signal and a fixed-base table of 8-bit windows, entry (32 b + w) * 256 + d = d * 256^w * IC[b + 1] (d = 0 unused):
+// 16 KB per window row, 512 KB per signal.  LongKey::win[b] = 32, or 0 when IC[b + 1] is the point at infinity (its rows are never read).
+// The (signal, window) pairs q = 32 b + w of one proof are dealt to G lanes, lane j taking q = j, j + G, j + 2G, ...; the G partial sums
+// are folded by a butterfly (k_msm_long), and IC[0] (VkTables::base) is added last.  digit(b, w) = byte w (least significant first) of
+// signal b.  (LongKey: next to Msm16 above.)
+template <class DIGIT> ZKV_HD G1J long_msm_slice(uint32_t n_sig, const uint32_t* win, const G1A* tab, DIGIT digit, uint32_t lane, uint32_t lanes) {
+    G1J acc = g1j_infinity();
+#pragma unroll 1
+    for (uint32_t q = lane; q < (uint32_t)MSM_MAX_WINDOWS * n_sig; q += lanes) {
+        const uint32_t b = q / MSM_MAX_WINDOWS, w = q % MSM_MAX_WINDOWS;
+        if (w >= win[b]) continue;
+        const uint32_t d = digit(b, w);
+        if (d) { const G1A e = tab[(size_t)q * MSM_DIGITS + d]; acc = g1j_add_affine(acc, e.x, e.y); }
+    }
+    return acc;
+}
 
 #endif  // !ZKV_PAIRED (PREP and MSM run one proof per lane)
 
@@ -723,6 +749,19 @@ ZKV_HD void setup_msm16_chunk(const VkTables& t, G1A* row, uint32_t b, uint32_t 
         out[j].x = x3;
         out[j].y = fp_sub(fp_mul(lam, fp_sub(H.x, x3)), H.y);
     }
+}
+// Long keys: one window row of IC[b + 1] (raw limbs ic[0] = x, ic[1] = y) into row = tab + (32 b + w) * 256; w == 0 also writes win[b].
+ZKV_HD void setup_long_row(const uint32_t ic[2][8], uint32_t w, G1A* row, uint32_t* win) {
+    const bool inf = raw_g1_is_inf(ic);
+    if (w == 0) *win = inf ? 0u : (uint32_t)MSM_MAX_WINDOWS;
+    if (!inf) setup_window_row(fp_from_raw(ic[0]), fp_from_raw(ic[1]), (int)w, row);
+}
+// Long keys: are all n_sig points IC[1..] (16 limbs each) inputs the ecMul / ecAdd precompiles accept?  A loop, not an unrolled chain.
+ZKV_HD bool long_ic_valid(const uint32_t* ic, uint32_t first, uint32_t n_sig, uint32_t step) {
+    bool ok = true;
+#pragma unroll 1
+    for (uint32_t b = first; b < n_sig; b += step) ok = raw_g1_valid((const uint32_t(*)[8])(ic + 16 * (size_t)b)) && ok;
+    return ok;
 }
 // One instance of a RISC Zero verifier set: what `initialize` derives from (control_root, bn254_control_id)
 // (risc0/verifier.rs:58-76) -- the selector (verifier.rs:128-144: tagged SHA-256 over control root, byte-reversed control

@@ -202,6 +202,69 @@ def make_batch(vm, base_seal, n, seed, pool=16, mutate_every=64, classes=MUTATIO
     return seals, mutated, mclass, flip_input
 
 
+GROTH16_MUTATION_CLASSES = ('signal_first', 'signal_middle', 'signal_last', 'signal_eq_r', 'c_off_curve', 'b_out_of_subgroup')
+
+
+def make_groth16_batch(vk_words, vm, base_proof_words, signals, n, seed, pool=16, mutate_every=64, classes=GROTH16_MUTATION_CLASSES):
+    """Synthetic batch for an ARBITRARY key (Groth16Verifier): re-randomisations of one valid proof of `signals` under that key.
+
+    vk_words: the key as zkv_groth16_ctx_create takes it; vm: 'risc0' (A negated in the pairing) or 'sp1'; base_proof_words: 256 bytes
+    (a.x a.y b.x[0] b.x[1] b.y[0] b.y[1] c.x c.y, G2 words (imaginary, real)); signals: the proof's n_ic - 1 public signals (ints or
+    32-byte values).  The re-randomisation A' = r1^-1 A, B' = r1 B + r1 r2 delta', C' = C + r2 A keeps the pairing product when
+    delta' = delta for 'risc0' (e(-A, B) ... e(C, delta)) and delta' = -delta for 'sp1' (e(A, B) ... e(C, delta)).
+    Every `mutate_every`-th proof gets one mutation of `classes` (signal classes are skipped for a key without signals): a signal
+    changed at the first / middle / last index, a signal set to R, C moved off the curve, B moved out of the order-r subgroup.
+    Returns (proofs uint8[n, 256], signals uint8[n, n_ic - 1, 32], mutated bool[n], mutation class index int8[n] (-1 = valid))."""
+    rng = SplitMix64(seed)
+    sig = [int.from_bytes(bytes(x), 'big') if isinstance(x, (bytes, bytearray)) else int(x) for x in signals]
+    k = len(sig)
+    w = [int.from_bytes(base_proof_words[32 * i:32 * i + 32], 'big') for i in range(8)]
+    a0, b0, c0 = (w[0], w[1]), ((w[3], w[2]), (w[5], w[4])), (w[6], w[7])
+    a0 = None if a0 == (0, 0) else a0
+    c0 = None if c0 == (0, 0) else c0
+    dw = [int.from_bytes(vk_words[320 + 32 * i:352 + 32 * i], 'big') for i in range(4)]
+    delta = _delta_point(dw, negate=(vm != 'risc0'))
+    classes = [c for c in classes if k or not c.startswith('signal')]
+    pool = max(1, min(pool, n))
+    state = []
+    for _ in range(pool):
+        r1, r2 = rng.scalar(), rng.scalar()
+        a = g1_mul(a0, pow(r1, -1, R)) if a0 else None
+        b = g2_add(g2_mul(b0, r1), g2_mul(delta, r1 * r2 % R))
+        c = g1_add(c0, g1_mul(a0, r2)) if a0 else c0
+        state.append([a, b, c, g2_mul(delta, r1), a0])
+    base_sig = np.frombuffer(b''.join(int(v).to_bytes(32, 'big') for v in sig), dtype=np.uint8).reshape(k, 32) if k else np.zeros((0, 32), np.uint8)
+    proofs = np.zeros((n, 256), dtype=np.uint8)
+    sigs = np.broadcast_to(base_sig, (n, k, 32)).copy()
+    mutated = np.zeros(n, dtype=bool)
+    mclass = np.full(n, -1, dtype=np.int8)
+    oos = random_twist_point(rng) if 'b_out_of_subgroup' in classes else None
+    be = lambda v: int(v).to_bytes(32, 'big')
+    for i in range(n):
+        st = state[i % pool]
+        a, b, c = st[0], st[1], st[2]
+        a_ = a or (0, 0); c_ = c or (0, 0)
+        words = [a_[0], a_[1]] + ([b[0][1], b[0][0], b[1][1], b[1][0]] if b else [0, 0, 0, 0]) + [c_[0], c_[1]]
+        if mutate_every and classes and i % mutate_every == mutate_every - 1:
+            name = classes[rng.below(len(classes))]
+            mutated[i] = True
+            mclass[i] = GROTH16_MUTATION_CLASSES.index(name)
+            if name.startswith('signal') and name != 'signal_eq_r':
+                j = {'signal_first': 0, 'signal_middle': k // 2, 'signal_last': k - 1}[name]
+                sigs[i, j] = np.frombuffer(be((sig[j] + 1) % R), dtype=np.uint8)
+            elif name == 'signal_eq_r':
+                sigs[i, rng.below(k)] = np.frombuffer(be(R), dtype=np.uint8)
+            elif name == 'c_off_curve':
+                words[7] ^= 1
+            elif name == 'b_out_of_subgroup':
+                words[2:6] = [oos[0][1], oos[0][0], oos[1][1], oos[1][0]]
+        proofs[i] = np.frombuffer(b''.join(be(v) for v in words), dtype=np.uint8)
+        st[1] = g2_add(b, st[3])
+        if st[4] is not None:
+            st[2] = g1_add(c, st[4])
+    return proofs, sigs, mutated, mclass
+
+
 def _lane(args):
     vm, base_seal, n, seed, pool, mutate_every, classes = args
     return make_batch(vm, base_seal, n, seed, pool=pool, mutate_every=mutate_every, classes=classes)
