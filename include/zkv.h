@@ -92,6 +92,11 @@ int zkv_risc0_verify_integrity(zkv_ctx* ctx, const uint8_t* seal, size_t seal_le
  * `stream` is a hipStream_t (NULL = the context's own stream).  Asynchronous: returns after enqueueing. */
 int zkv_risc0_verify_batch_dev(zkv_ctx* ctx, size_t n, const uint8_t* d_seals, const uint8_t* d_image_ids,
                                const uint8_t* d_journal_digests, uint8_t* d_status, uint8_t* d_recv_selector, void* stream);
+/* IRiscZeroVerifier::verify_integrity, everything resident in HBM: d_seals n x 260, d_claim_digests n x 32.  Statuses and received
+ * selectors are those of verify_integrity (risc0/verifier.rs:94-104): the checks of `verify` without the claim-digest chain; an
+ * un-initialised verifier gives INVALID_INITIALIZATION for every proof.  Asynchronous on `stream`; shards like the call above. */
+int zkv_risc0_verify_integrity_batch_dev(zkv_ctx* ctx, size_t n, const uint8_t* d_seals, const uint8_t* d_claim_digests,
+                                         uint8_t* d_status, uint8_t* d_recv_selector, void* stream);
 
 /* ------------------------------------------------------------------ RISC Zero verifier sets
  * Many `RiscZeroVerifier` instances -- one per (control_root, bn254_control_id), i.e. per zkVM release -- resident on one
@@ -112,6 +117,13 @@ int zkv_risc0_set_verify_batch(zkv_ctx* ctx, size_t n, const uint32_t* instance,
 /* fixed-stride 260-byte seals, everything (including the instance indices) resident in HBM; asynchronous on `stream` */
 int zkv_risc0_set_verify_batch_dev(zkv_ctx* ctx, size_t n, const uint32_t* d_instance, const uint8_t* d_seals, const uint8_t* d_image_ids,
                                    const uint8_t* d_journal_digests, uint8_t* d_status, uint8_t* d_recv_selector, void* stream);
+/* IRiscZeroVerifier::verify_integrity over a batch, proof i against instance[i]: claim_digests n x 32 bytes.  An index >= the set
+ * size gives INVALID_INITIALIZATION, as for verify.  Verifier sets are single-device: anything else is ZKV_ERR_WRONG_CTX. */
+int zkv_risc0_set_verify_integrity_batch(zkv_ctx* ctx, size_t n, const uint32_t* instance, const uint8_t* seal_blob, const uint64_t* seal_off,
+                                         const uint8_t* claim_digests, uint8_t* status, uint8_t* recv_selector);
+/* the same, fixed-stride 260-byte seals, everything resident in HBM; asynchronous on `stream` */
+int zkv_risc0_set_verify_integrity_batch_dev(zkv_ctx* ctx, size_t n, const uint32_t* d_instance, const uint8_t* d_seals,
+                                             const uint8_t* d_claim_digests, uint8_t* d_status, uint8_t* d_recv_selector, void* stream);
 /* compute_vk_x (common/groth16.rs:51-58) of (instance[i], claim digest halves i): var_signals n x 2 x 32 bytes, out n x 64 */
 int zkv_risc0_set_vk_x_batch(zkv_ctx* ctx, size_t n, const uint32_t* instance, const uint8_t* var_signals, uint8_t* out);
 
@@ -155,6 +167,23 @@ int zkv_mixed_verify_batch(zkv_ctx* ctx, size_t n, const uint8_t* vm, const uint
  * (the host learns the two sub-batch sizes from the device). */
 int zkv_mixed_verify_batch_dev(zkv_ctx* ctx, size_t n, const uint8_t* d_vm, const uint8_t* d_seals, const uint8_t* d_in_a, const uint8_t* d_in_b,
                                size_t b_stride, size_t pv_len, uint8_t* d_status, uint8_t* d_recv_selector, void* stream);
+/* Mixed batches with a per-proof method: the deployed RISC Zero shell exports verify(uint8[],bytes32,bytes32) and
+ * verifyIntegrity(uint8[],bytes32).  method[i] (NULL = all ZKV_METHOD_VERIFY, which makes these the two calls above):
+ *   vm 0, method 0: IRiscZeroVerifier::verify(seal, in_a = image_id, in_b = journal_digest)
+ *   vm 0, method 1: IRiscZeroVerifier::verify_integrity(seal, in_a = claim_digest) (risc0/verifier.rs:94-104); in_b is not read,
+ *                   and in the host call its slice may have any length, 0 included
+ *   vm 1, method 0: ISp1Verifier::verify_proof, as above
+ *   vm 0 or 1, any other method: ZKV_STATUS_BAD_CALLDATA with a zero received selector (no reference counterpart: the shell's router
+ *                   has no such function to dispatch to; SP1 has no second method)
+ *   any other vm:   ZKV_STATUS_UNKNOWN_VM, whatever the method.
+ * The method travels through the device-side demultiplexer into the RISC Zero sub-batch, so its verify and verify_integrity rows
+ * share one stage pipeline (and the aggregate check, when on).  Shards like the calls above (the method row is one more byte per proof). */
+#define ZKV_METHOD_VERIFY 0
+#define ZKV_METHOD_VERIFY_INTEGRITY 1
+int zkv_mixed_verify_call_batch(zkv_ctx* ctx, size_t n, const uint8_t* vm, const uint8_t* method, const uint8_t* seal_blob, const uint64_t* seal_off,
+                                const uint8_t* in_a, const uint8_t* in_b_blob, const uint64_t* in_b_off, uint8_t* status, uint8_t* recv_selector);
+int zkv_mixed_verify_call_batch_dev(zkv_ctx* ctx, size_t n, const uint8_t* d_vm, const uint8_t* d_method, const uint8_t* d_seals, const uint8_t* d_in_a,
+                                    const uint8_t* d_in_b, size_t b_stride, size_t pv_len, uint8_t* d_status, uint8_t* d_recv_selector, void* stream);
 
 /* ------------------------------------------------------------------ sharded (multi-device) contexts
  * `zkv_risc0_ctx_create(control_root, bn254_control_id, device_mask)` -- one verifier over several GPUs of a node.

@@ -107,7 +107,7 @@ struct zkv_ctx {
     // (zkv_ctx_create_sharded).  sh[] is the per-shard state of device-resident batches: staging rows on the shard's device, a copy
     // stream (the transfer of piece k + 1 runs behind the kernels of piece k), the shard's compute stream and its events.
     struct ShardDev {
-        uint8_t* row[4] = {nullptr, nullptr, nullptr, nullptr}; size_t row_cap[4] = {0, 0, 0, 0};
+        uint8_t* row[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t row_cap[5] = {0, 0, 0, 0, 0};
         uint8_t *st = nullptr, *rv = nullptr; size_t st_cap = 0, rv_cap = 0;
         hipStream_t copy = nullptr, run = nullptr;
         hipEvent_t ev_piece[2] = {nullptr, nullptr}, ev_done = nullptr;
@@ -140,8 +140,8 @@ struct zkv_ctx {
     std::vector<hipEvent_t> ev_in;                       // per source device: "the caller's stream has produced the inputs"
     zkv_ctx* kid[2] = {nullptr, nullptr};
     bool kid_ran[2] = {false, false};        // which sub-batch of the most recent mixed call was non-empty (zkv_ctx_last_stage_ms)
-    uint8_t* mx[20] = {nullptr};
-    size_t mx_cap[20] = {0};
+    uint8_t* mx[22] = {nullptr};
+    size_t mx_cap[22] = {0};
     std::mutex mu;
 };
 
@@ -910,9 +910,9 @@ static int run_dev_batch(zkv_ctx* c, size_t n, const uint8_t* d_blob, const uint
 
 // Stage pipeline over m compact records that a device-side front end produced (fixed 260-byte stride plus the true length,
 // 32-byte inputs, public values as (start, length) into one blob): the output format of the calldata decoder and of the
-// mixed-batch demultiplexer.  Asynchronous on `s`.
+// mixed-batch demultiplexer.  `kind` (RISC Zero, may be null): per-proof method, 1 = verify_integrity.  Asynchronous on `s`.
 static int run_records(zkv_ctx* c, size_t m_total, const uint8_t* seals, const uint32_t* len, const uint8_t* in_a, const uint8_t* in_b,
-                       const uint8_t* pv_blob, const uint64_t* pv_start, const uint32_t* pv_len, uint8_t* st, uint8_t* rv, hipStream_t s) {
+                       const uint8_t* kind, const uint8_t* pv_blob, const uint64_t* pv_start, const uint32_t* pv_len, uint8_t* st, uint8_t* rv, hipStream_t s) {
     if (!m_total) return ZKV_OK;
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_ready(c, m_total);
@@ -929,7 +929,7 @@ static int run_records(zkv_ctx* c, size_t m_total, const uint8_t* seals, const u
             a.pv_blob = pv_blob; a.pv_off = pv_start + base; a.pv_len = pv_len + base;
             a.selector_be = be32_of(host::SP1_VERIFIER_HASH);
         } else {
-            a.in32_b = in_b + 32 * base;
+            a.in32_b = in_b + 32 * base; a.kind = kind ? kind + base : nullptr;
             a.selector_be = be32_of(c->selector);
             a.force_fail = c->id_ge_r ? 1u : 0u;
         }
@@ -1004,10 +1004,11 @@ static int shard_dev_setup(zkv_ctx::ShardDev& d, int device) {
     return ZKV_OK;
 }
 struct DevRow { const uint8_t* p; size_t stride; };
-// child_call(child, m, rows[4] (device pointers on the child's GPU), status, recv (may be null), stream) -> ZKV_*
+// child_call(child, m, rows[n_rows <= 5] (device pointers on the child's GPU), status, recv (may be null), stream) -> ZKV_*
 template <class F>
 static int run_sharded_dev(zkv_ctx* c, size_t n, const DevRow* rows, int n_rows, uint8_t* d_status, uint8_t* d_recv, void* stream, F child_call) {
     if (!n) return ZKV_OK;
+    if (n_rows < 1 || n_rows > 5) return ZKV_ERR_INVALID_ARG;
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, rows[0].p) != hipSuccess) { (void)hipGetLastError(); return ZKV_ERR_INVALID_ARG; }
     const int sdev = at.device;
@@ -1065,7 +1066,7 @@ static int run_sharded_dev(zkv_ctx* c, size_t n, const DevRow* rows, int n_rows,
             }
         }
         for (int q = 0; q < np; q++) {
-            const uint8_t* rp[4] = {nullptr, nullptr, nullptr, nullptr};
+            const uint8_t* rp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
             for (int j = 0; j < n_rows; j++) rp[j] = (staged ? d.row[j] : rows[j].p + lo * rows[j].stride) + pc[q] * rows[j].stride;
             if (staged) HIP_TRY(hipStreamWaitEvent(d.run, d.ev_piece[q], 0));
             uint8_t* st = (staged ? d.st : d_status + lo) + pc[q];
@@ -1175,25 +1176,25 @@ ZKV_EXPORT zkv_ctx* zkv_mixed_ctx_create(const uint8_t control_root[32], const u
 ZKV_EXPORT zkv_ctx* zkv_mixed_ctx_risc0(zkv_ctx* c) { if (is_sharded(c)) c = c->shards[0]; return c && c->vm == ZKV_VM_MIXED ? c->kid[0] : nullptr; }
 ZKV_EXPORT zkv_ctx* zkv_mixed_ctx_sp1(zkv_ctx* c) { if (is_sharded(c)) c = c->shards[0]; return c && c->vm == ZKV_VM_MIXED ? c->kid[1] : nullptr; }
 
-enum { MX_CNT = 0, MX_TOT, MX_POS, MX_IDX, MX_SEALS, MX_LEN, MX_A, MX_B, MX_PVOFF, MX_PVLEN, MX_ST, MX_RV,
-       MX_H_VM, MX_H_SEALS, MX_H_SOFF, MX_H_A, MX_H_B, MX_H_BOFF, MX_H_ST, MX_H_RV };
-// Everything device-resident; `seal_off` / `b_off` select the ragged layout, otherwise fixed strides.  Synchronises `s` once, after
-// the partition, to learn the two sub-batch sizes.
-static int run_mixed(zkv_ctx* c, size_t n, const uint8_t* d_vm, const uint8_t* d_seals, const uint64_t* d_seal_off, uint32_t seal_stride,
+enum { MX_CNT = 0, MX_TOT, MX_POS, MX_IDX, MX_SEALS, MX_LEN, MX_A, MX_B, MX_PVOFF, MX_PVLEN, MX_ST, MX_RV, MX_KIND,
+       MX_H_VM, MX_H_SEALS, MX_H_SOFF, MX_H_A, MX_H_B, MX_H_BOFF, MX_H_ST, MX_H_RV, MX_H_METHOD };
+// Everything device-resident; `seal_off` / `b_off` select the ragged layout, otherwise fixed strides; `d_method` (may be null: all
+// ZKV_METHOD_VERIFY) is the per-proof method.  Synchronises `s` once, after the partition, to learn the two sub-batch sizes.
+static int run_mixed(zkv_ctx* c, size_t n, const uint8_t* d_vm, const uint8_t* d_method, const uint8_t* d_seals, const uint64_t* d_seal_off, uint32_t seal_stride,
                      const uint8_t* d_a, const uint8_t* d_b, const uint64_t* d_b_off, uint32_t b_stride, uint32_t pv_len,
                      uint8_t* d_status, uint8_t* d_recv, hipStream_t s) {
     int rc;
     const size_t blocks = (n + 255) / 256;
-    const size_t need[12] = {8 * blocks, 8, 4 * n, 4 * n, (size_t)ZKV_SEAL_BYTES * n, 4 * n, 32 * n, 32 * n, 8 * n, 4 * n, n, 4 * n};
-    for (int k = 0; k < 12; k++) if ((rc = grow(&c->mx[k], &c->mx_cap[k], need[k])) != ZKV_OK) return rc;
+    const size_t need[13] = {8 * blocks, 8, 4 * n, 4 * n, (size_t)ZKV_SEAL_BYTES * n, 4 * n, 32 * n, 32 * n, 8 * n, 4 * n, n, 4 * n, n};
+    for (int k = 0; k < 13; k++) if ((rc = grow(&c->mx[k], &c->mx_cap[k], need[k])) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     MixedArgs a;
     memset(&a, 0, sizeof a);
-    a.n = n; a.vm = d_vm; a.seals = d_seals; a.seal_off = d_seal_off; a.seal_stride = seal_stride;
+    a.n = n; a.vm = d_vm; a.method = d_method; a.seals = d_seals; a.seal_off = d_seal_off; a.seal_stride = seal_stride;
     a.in_a = d_a; a.in_b = d_b; a.b_off = d_b_off; a.b_stride = b_stride; a.pv_len = pv_len;
     a.cnt = (uint32_t*)c->mx[MX_CNT]; a.totals = (uint32_t*)c->mx[MX_TOT]; a.pos = (uint32_t*)c->mx[MX_POS]; a.idx = (uint32_t*)c->mx[MX_IDX];
     a.c_seals = c->mx[MX_SEALS]; a.c_len = (uint32_t*)c->mx[MX_LEN]; a.c_a = c->mx[MX_A]; a.c_b = c->mx[MX_B];
-    a.c_pvoff = (uint64_t*)c->mx[MX_PVOFF]; a.c_pvlen = (uint32_t*)c->mx[MX_PVLEN];
+    a.c_pvoff = (uint64_t*)c->mx[MX_PVOFF]; a.c_pvlen = (uint32_t*)c->mx[MX_PVLEN]; a.c_kind = c->mx[MX_KIND];
     a.status = d_status; a.recv = d_recv;
     launch_mixed_partition(a, (uint32_t*)c->mx[MX_CNT], (uint32_t*)c->mx[MX_TOT], s);
     HIP_TRY(hipGetLastError());
@@ -1204,65 +1205,79 @@ static int run_mixed(zkv_ctx* c, size_t n, const uint8_t* d_vm, const uint8_t* d
     if (n0 + n1 > n) return ZKV_ERR_HIP;
     c->kid_ran[0] = n0 > 0; c->kid_ran[1] = n1 > 0;
     uint8_t *st = c->mx[MX_ST], *rv = c->mx[MX_RV];
-    if ((rc = run_records(c->kid[0], n0, a.c_seals, a.c_len, a.c_a, a.c_b, nullptr, nullptr, nullptr, st, rv, s)) != ZKV_OK) return rc;
-    if ((rc = run_records(c->kid[1], n1, a.c_seals + ZKV_SEAL_BYTES * n0, a.c_len + n0, a.c_a + 32 * n0, nullptr, d_b, a.c_pvoff + n0, a.c_pvlen + n0,
+    if ((rc = run_records(c->kid[0], n0, a.c_seals, a.c_len, a.c_a, a.c_b, d_method ? a.c_kind : nullptr, nullptr, nullptr, nullptr, st, rv, s)) != ZKV_OK) return rc;
+    if ((rc = run_records(c->kid[1], n1, a.c_seals + ZKV_SEAL_BYTES * n0, a.c_len + n0, a.c_a + 32 * n0, nullptr, nullptr, d_b, a.c_pvoff + n0, a.c_pvlen + n0,
                           st + n0, rv + 4 * n0, s)) != ZKV_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     launch_mixed_return(n0 + n1, a.idx, st, rv, d_status, d_recv, s);
     HIP_TRY(hipGetLastError());
     return mark_done(c, s);
 }
-ZKV_EXPORT int zkv_mixed_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_vm, const uint8_t* d_seals, const uint8_t* d_in_a, const uint8_t* d_in_b,
-                                          size_t b_stride, size_t pv_len, uint8_t* d_status, uint8_t* d_recv, void* stream) {
+ZKV_EXPORT int zkv_mixed_verify_call_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_vm, const uint8_t* d_method, const uint8_t* d_seals,
+                                               const uint8_t* d_in_a, const uint8_t* d_in_b, size_t b_stride, size_t pv_len, uint8_t* d_status,
+                                               uint8_t* d_recv, void* stream) {
     if (!c || c->vm != ZKV_VM_MIXED) return ZKV_ERR_WRONG_CTX;
     if (n && (!d_vm || !d_seals || !d_in_a || !d_in_b || !d_status || b_stride < 32 || pv_len > b_stride || b_stride > 0xFFFFFFFFu)) return ZKV_ERR_INVALID_ARG;
     if (!n) return ZKV_OK;
     if (n > 0xFFFFFFF0u) return ZKV_ERR_INVALID_ARG;
     if (is_sharded(c)) {
-        const DevRow rows[4] = {{d_vm, 1}, {d_seals, ZKV_SEAL_BYTES}, {d_in_a, 32}, {d_in_b, b_stride}};
-        return run_sharded_dev(c, n, rows, 4, d_status, d_recv, stream, [&](zkv_ctx* k, size_t m, const uint8_t* const* r, uint8_t* st, uint8_t* rv, hipStream_t s) {
-            return zkv_mixed_verify_batch_dev(k, m, r[0], r[1], r[2], r[3], b_stride, pv_len, st, rv, s); });
+        // the method row travels with the others (one byte per proof); without one the shards get none either
+        const DevRow rows[5] = {{d_vm, 1}, {d_seals, ZKV_SEAL_BYTES}, {d_in_a, 32}, {d_in_b, b_stride}, {d_method, 1}};
+        return run_sharded_dev(c, n, rows, d_method ? 5 : 4, d_status, d_recv, stream,
+                               [&](zkv_ctx* k, size_t m, const uint8_t* const* r, uint8_t* st, uint8_t* rv, hipStream_t s) {
+            return zkv_mixed_verify_call_batch_dev(k, m, r[0], d_method ? r[4] : nullptr, r[1], r[2], r[3], b_stride, pv_len, st, rv, s); });
     }
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_device_init(c);
     if (rc != ZKV_OK) return rc;
-    return run_mixed(c, n, d_vm, d_seals, nullptr, ZKV_SEAL_BYTES, d_in_a, d_in_b, nullptr, (uint32_t)b_stride, (uint32_t)pv_len, d_status, d_recv,
-                     stream ? (hipStream_t)stream : c->stream);
+    return run_mixed(c, n, d_vm, d_method, d_seals, nullptr, ZKV_SEAL_BYTES, d_in_a, d_in_b, nullptr, (uint32_t)b_stride, (uint32_t)pv_len, d_status,
+                     d_recv, stream ? (hipStream_t)stream : c->stream);
 }
-ZKV_EXPORT int zkv_mixed_verify_batch(zkv_ctx* c, size_t n, const uint8_t* vm, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* in_a,
-                                      const uint8_t* in_b_blob, const uint64_t* in_b_off, uint8_t* status, uint8_t* recv) {
+ZKV_EXPORT int zkv_mixed_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_vm, const uint8_t* d_seals, const uint8_t* d_in_a, const uint8_t* d_in_b,
+                                          size_t b_stride, size_t pv_len, uint8_t* d_status, uint8_t* d_recv, void* stream) {
+    return zkv_mixed_verify_call_batch_dev(c, n, d_vm, nullptr, d_seals, d_in_a, d_in_b, b_stride, pv_len, d_status, d_recv, stream);
+}
+ZKV_EXPORT int zkv_mixed_verify_call_batch(zkv_ctx* c, size_t n, const uint8_t* vm, const uint8_t* method, const uint8_t* seal_blob, const uint64_t* seal_off,
+                                           const uint8_t* in_a, const uint8_t* in_b_blob, const uint64_t* in_b_off, uint8_t* status, uint8_t* recv) {
     if (!c || c->vm != ZKV_VM_MIXED) return ZKV_ERR_WRONG_CTX;
     if (n && (!vm || !seal_blob || !seal_off || !in_a || !in_b_blob || !in_b_off || !status)) return ZKV_ERR_INVALID_ARG;
     if (!n) return ZKV_OK;
     if (n > 0xFFFFFFF0u || !offsets_ok(seal_off, n) || !offsets_ok(in_b_off, n)) return ZKV_ERR_INVALID_ARG;
-    for (size_t i = 0; i < n; i++)                   // journal_digest is a B256 in the reference (risc0/verifier.rs:82)
-        if (vm[i] == ZKV_VM_RISC0 && in_b_off[i + 1] - in_b_off[i] != 32) return ZKV_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n; i++)                   // journal_digest is a B256 in the reference (risc0/verifier.rs:82); verify_integrity has none
+        if (vm[i] == ZKV_VM_RISC0 && (!method || method[i] == ZKV_METHOD_VERIFY) && in_b_off[i + 1] - in_b_off[i] != 32) return ZKV_ERR_INVALID_ARG;
     if (is_sharded(c))
         return run_sharded(c, n, [&](zkv_ctx* k, size_t lo, size_t hi) {
-            return zkv_mixed_verify_batch(k, hi - lo, vm + lo, seal_blob, seal_off + lo, in_a + 32 * lo, in_b_blob, in_b_off + lo, status + lo, recv ? recv + 4 * lo : nullptr); });
+            return zkv_mixed_verify_call_batch(k, hi - lo, vm + lo, method ? method + lo : nullptr, seal_blob, seal_off + lo, in_a + 32 * lo, in_b_blob,
+                                               in_b_off + lo, status + lo, recv ? recv + 4 * lo : nullptr); });
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_device_init(c);
     if (rc != ZKV_OK) return rc;
     const uint64_t s0 = seal_off[0], sbytes = seal_off[n] - s0, b0 = in_b_off[0], bbytes = in_b_off[n] - b0;
     const size_t need[8] = {n, (size_t)sbytes + 8, 8 * (n + 1), 32 * n, (size_t)bbytes + 8, 8 * (n + 1), n, 4 * n};
     for (int k = 0; k < 8; k++) if ((rc = grow(&c->mx[MX_H_VM + k], &c->mx_cap[MX_H_VM + k], need[k])) != ZKV_OK) return rc;
+    if (method && (rc = grow(&c->mx[MX_H_METHOD], &c->mx_cap[MX_H_METHOD], n)) != ZKV_OK) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     std::vector<uint64_t> so(seal_off, seal_off + n + 1), bo(in_b_off, in_b_off + n + 1);
     for (auto& v : so) v -= s0;
     for (auto& v : bo) v -= b0;
     HIP_TRY(hipMemcpyAsync(c->mx[MX_H_VM], vm, n, hipMemcpyHostToDevice, s));
+    if (method) HIP_TRY(hipMemcpyAsync(c->mx[MX_H_METHOD], method, n, hipMemcpyHostToDevice, s));
     if (sbytes) HIP_TRY(hipMemcpyAsync(c->mx[MX_H_SEALS], seal_blob + s0, (size_t)sbytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->mx[MX_H_SOFF], so.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->mx[MX_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
     if (bbytes) HIP_TRY(hipMemcpyAsync(c->mx[MX_H_B], in_b_blob + b0, (size_t)bbytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->mx[MX_H_BOFF], bo.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
-    if ((rc = run_mixed(c, n, c->mx[MX_H_VM], c->mx[MX_H_SEALS], (const uint64_t*)c->mx[MX_H_SOFF], 0, c->mx[MX_H_A], c->mx[MX_H_B],
-                        (const uint64_t*)c->mx[MX_H_BOFF], 0, 0, c->mx[MX_H_ST], c->mx[MX_H_RV], s)) != ZKV_OK) return rc;
+    if ((rc = run_mixed(c, n, c->mx[MX_H_VM], method ? c->mx[MX_H_METHOD] : nullptr, c->mx[MX_H_SEALS], (const uint64_t*)c->mx[MX_H_SOFF], 0, c->mx[MX_H_A],
+                        c->mx[MX_H_B], (const uint64_t*)c->mx[MX_H_BOFF], 0, 0, c->mx[MX_H_ST], c->mx[MX_H_RV], s)) != ZKV_OK) return rc;
     HIP_TRY(hipMemcpyAsync(status, c->mx[MX_H_ST], n, hipMemcpyDeviceToHost, s));
     if (recv) HIP_TRY(hipMemcpyAsync(recv, c->mx[MX_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return ZKV_OK;
+}
+ZKV_EXPORT int zkv_mixed_verify_batch(zkv_ctx* c, size_t n, const uint8_t* vm, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* in_a,
+                                      const uint8_t* in_b_blob, const uint64_t* in_b_off, uint8_t* status, uint8_t* recv) {
+    return zkv_mixed_verify_call_batch(c, n, vm, nullptr, seal_blob, seal_off, in_a, in_b_blob, in_b_off, status, recv);
 }
 
 // ------------------------------------------------------------------ RISC Zero
@@ -1367,6 +1382,19 @@ ZKV_EXPORT int zkv_risc0_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d
     }
     return run_dev_batch(c, n, d_seals, d_image_ids, d_journal_digests, nullptr, 0, d_status, d_recv, stream);
 }
+// no journal digest row: the prep kernel takes in_a as the claim digest (k_prep_risc0, in32_b == nullptr)
+ZKV_EXPORT int zkv_risc0_verify_integrity_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint8_t* d_claim_digests, uint8_t* d_status,
+                                                    uint8_t* d_recv, void* stream) {
+    if (!c || c->vm != ZKV_VM_RISC0) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_seals || !d_claim_digests || !d_status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (is_sharded(c)) {
+        const DevRow rows[2] = {{d_seals, ZKV_SEAL_BYTES}, {d_claim_digests, 32}};
+        return run_sharded_dev(c, n, rows, 2, d_status, d_recv, stream, [&](zkv_ctx* k, size_t m, const uint8_t* const* r, uint8_t* st, uint8_t* rv, hipStream_t s) {
+            return zkv_risc0_verify_integrity_batch_dev(k, m, r[0], r[1], st, rv, s); });
+    }
+    return run_dev_batch(c, n, d_seals, d_claim_digests, nullptr, nullptr, 0, d_status, d_recv, stream);
+}
 
 // ------------------------------------------------------------------ RISC Zero verifier sets (many instances, one VK)
 ZKV_EXPORT zkv_ctx* zkv_risc0_set_create(size_t n_instances, const uint8_t* control_roots, const uint8_t* bn254_control_ids, int device) {
@@ -1393,11 +1421,12 @@ ZKV_EXPORT int zkv_risc0_set_get_selector(zkv_ctx* c, size_t instance, uint8_t o
     out[0] = (uint8_t)(s >> 24); out[1] = (uint8_t)(s >> 16); out[2] = (uint8_t)(s >> 8); out[3] = (uint8_t)s;
     return ZKV_OK;
 }
-// shared driver: host pointers when `dev` is false (one chunk at a time, synchronous), device pointers otherwise (asynchronous)
+// shared driver: host pointers when `dev` is false (one chunk at a time, synchronous), device pointers otherwise (asynchronous).
+// integrity: verify_integrity, `ids` holds the claim digests and `jds` is not read.
 static int run_set_batch(zkv_ctx* c, size_t n, const uint32_t* inst, const uint8_t* blob, const uint64_t* off, const uint8_t* ids, const uint8_t* jds,
-                         uint8_t* status, uint8_t* recv, bool dev, void* stream) {
+                         uint8_t* status, uint8_t* recv, bool dev, void* stream, bool integrity = false) {
     if (!c || c->vm != ZKV_VM_RISC0_SET) return ZKV_ERR_WRONG_CTX;
-    if (n && (!inst || !blob || (!dev && !off) || !ids || !jds || !status)) return ZKV_ERR_INVALID_ARG;
+    if (n && (!inst || !blob || (!dev && !off) || !ids || (!integrity && !jds) || !status)) return ZKV_ERR_INVALID_ARG;
     if (n && !dev && !offsets_ok(off, n)) return ZKV_ERR_INVALID_ARG;
     if (!n) return ZKV_OK;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -1414,7 +1443,7 @@ static int run_set_batch(zkv_ctx* c, size_t n, const uint32_t* inst, const uint8
         a.n = m; a.inst_tab = c->d_inst; a.n_inst = (uint32_t)c->inst_raw.size();
         if (dev) {
             a.blob = blob + base * ZKV_SEAL_BYTES; a.stride = ZKV_SEAL_BYTES; a.inst = inst + base;
-            a.in32_a = ids + 32 * base; a.in32_b = jds + 32 * base; a.status = status + base; a.recv = recv ? recv + 4 * base : nullptr;
+            a.in32_a = ids + 32 * base; a.in32_b = integrity ? nullptr : jds + 32 * base; a.status = status + base; a.recv = recv ? recv + 4 * base : nullptr;
         } else {
             const uint64_t b0 = off[base], bytes = off[base + m] - b0;
             if ((rc = grow(&c->d_blob, &c->blob_cap, (size_t)bytes + 8)) != ZKV_OK) return rc;
@@ -1423,9 +1452,9 @@ static int run_set_batch(zkv_ctx* c, size_t n, const uint32_t* inst, const uint8
             if (bytes) HIP_TRY(hipMemcpyAsync(c->d_blob, blob + b0, (size_t)bytes, hipMemcpyHostToDevice, s));
             HIP_TRY(hipMemcpyAsync(c->d_inst_idx, inst + base, sizeof(uint32_t) * m, hipMemcpyHostToDevice, s));
             HIP_TRY(hipMemcpyAsync(c->d_a, ids + 32 * base, 32 * m, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(c->d_b, jds + 32 * base, 32 * m, hipMemcpyHostToDevice, s));
+            if (!integrity) HIP_TRY(hipMemcpyAsync(c->d_b, jds + 32 * base, 32 * m, hipMemcpyHostToDevice, s));
             HIP_TRY(hipStreamSynchronize(s));               // rel[] is reused by the next chunk
-            a.blob = c->d_blob; a.off = c->d_off; a.inst = c->d_inst_idx; a.in32_a = c->d_a; a.in32_b = c->d_b;
+            a.blob = c->d_blob; a.off = c->d_off; a.inst = c->d_inst_idx; a.in32_a = c->d_a; a.in32_b = integrity ? nullptr : c->d_b;
             a.status = c->d_status; a.recv = c->d_recv;
         }
         enqueue_chunk(c, a, s, base + cap >= n);
@@ -1446,6 +1475,15 @@ ZKV_EXPORT int zkv_risc0_set_verify_batch(zkv_ctx* c, size_t n, const uint32_t* 
 ZKV_EXPORT int zkv_risc0_set_verify_batch_dev(zkv_ctx* c, size_t n, const uint32_t* d_instance, const uint8_t* d_seals, const uint8_t* d_image_ids,
                                               const uint8_t* d_journal_digests, uint8_t* d_status, uint8_t* d_recv, void* stream) {
     return run_set_batch(c, n, d_instance, d_seals, nullptr, d_image_ids, d_journal_digests, d_status, d_recv, true, stream);
+}
+ZKV_EXPORT int zkv_risc0_set_verify_integrity_batch(zkv_ctx* c, size_t n, const uint32_t* instance, const uint8_t* seal_blob, const uint64_t* seal_off,
+                                                    const uint8_t* claim_digests, uint8_t* status, uint8_t* recv) {
+    if (recv && n && c && c->vm == ZKV_VM_RISC0_SET) memset(recv, 0, 4 * n);
+    return run_set_batch(c, n, instance, seal_blob, seal_off, claim_digests, nullptr, status, recv, false, nullptr, true);
+}
+ZKV_EXPORT int zkv_risc0_set_verify_integrity_batch_dev(zkv_ctx* c, size_t n, const uint32_t* d_instance, const uint8_t* d_seals,
+                                                        const uint8_t* d_claim_digests, uint8_t* d_status, uint8_t* d_recv, void* stream) {
+    return run_set_batch(c, n, d_instance, d_seals, nullptr, d_claim_digests, nullptr, d_status, d_recv, true, stream, true);
 }
 // compute_vk_x for (instance, claim halves): the per-instance signals come from the device table
 ZKV_EXPORT int zkv_risc0_set_vk_x_batch(zkv_ctx* c, size_t n, const uint32_t* instance, const uint8_t* var_signals, uint8_t* out) {

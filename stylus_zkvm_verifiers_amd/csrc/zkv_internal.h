@@ -105,12 +105,14 @@ void launch_miller_w64d(size_t n, const VkTables* d_tab, const Workspace& ws, ui
 struct MixedArgs {
     size_t n;
     const uint8_t* vm;
+    const uint8_t* method;                                                     // n x ZKV_METHOD_*, or nullptr: all verify
     const uint8_t* seals; const uint64_t* seal_off; uint32_t seal_stride;     // ragged (off) or fixed stride
     const uint8_t* in_a;                                                       // n x 32
     const uint8_t* in_b; const uint64_t* b_off; uint32_t b_stride, pv_len;     // ragged (off) or fixed stride + fixed SP1 length
     const uint32_t* cnt; const uint32_t* totals;
-    uint32_t* pos; uint32_t* idx;                                              // pos[i] = slot (0xFFFFFFFF: unknown VM); idx[slot] = i
+    uint32_t* pos; uint32_t* idx;                                              // pos[i] = slot (0xFFFFFFFF: unknown VM / method); idx[slot] = i
     uint8_t* c_seals; uint32_t* c_len; uint8_t* c_a; uint8_t* c_b; uint64_t* c_pvoff; uint32_t* c_pvlen;   // compact records
+    uint8_t* c_kind;                                                           // compact RISC Zero method (PrepArgs::kind)
     uint8_t* status; uint8_t* recv;                                            // caller's outputs (unknown-VM proofs are answered here)
 };
 void launch_mixed_partition(const MixedArgs& a, uint32_t* cnt, uint32_t* totals, hipStream_t s);

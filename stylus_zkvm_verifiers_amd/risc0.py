@@ -133,6 +133,11 @@ class RiscZeroVerifier:
         _lib.check(self._L.zkv_risc0_verify_batch_dev(self._h, n, d_seals, d_image_ids, d_journal_digests, d_status,
                                                       d_recv or None, stream or None), 'zkv_risc0_verify_batch_dev')
 
+    def verify_integrity_batch_dev(self, n, d_seals, d_claim_digests, d_status, d_recv=0, stream=0):
+        """verify_integrity over n 260-byte seals and n 32-byte claim digests resident in HBM; asynchronous on `stream`."""
+        _lib.check(self._L.zkv_risc0_verify_integrity_batch_dev(self._h, n, d_seals, d_claim_digests, d_status, d_recv or None, stream or None),
+                   'zkv_risc0_verify_integrity_batch_dev')
+
     def vk_x_batch(self, var_signals):
         """Groth16Verifier::compute_vk_x (common/groth16.rs:51-58) for a batch: var_signals = list of (s_a, s_b) 32-byte pairs
         (the two per-proof signals); returns 64-byte affine points."""
@@ -210,6 +215,21 @@ class RiscZeroVerifierSet:
     def verify_batch_dev(self, n, d_instances, d_seals, d_image_ids, d_journal_digests, d_status, d_recv=0, stream=0):
         _lib.check(self._L.zkv_risc0_set_verify_batch_dev(self._h, n, d_instances, d_seals, d_image_ids, d_journal_digests, d_status,
                                                           d_recv or None, stream or None), 'zkv_risc0_set_verify_batch_dev')
+
+    def verify_integrity_batch(self, instances, seals, claim_digests):
+        """verify_integrity of proof i against instance[i] (an index >= len(self) gives InvalidInitialization)."""
+        n = len(seals)
+        _same_len(n, instances=instances, claim_digests=claim_digests)
+        blob, off = _blob(seals)
+        idx = np.ascontiguousarray(instances, dtype=np.uint32)
+        st = np.zeros(n, dtype=np.uint8); rv = np.zeros((n, 4), dtype=np.uint8)
+        _lib.check(self._L.zkv_risc0_set_verify_integrity_batch(self._h, n, idx.ctypes.data, blob, off.ctypes.data, _cat32(claim_digests, 'claim_digest'),
+                                                                st.ctypes.data, rv.ctypes.data), 'zkv_risc0_set_verify_integrity_batch')
+        return st, rv
+
+    def verify_integrity_batch_dev(self, n, d_instances, d_seals, d_claim_digests, d_status, d_recv=0, stream=0):
+        _lib.check(self._L.zkv_risc0_set_verify_integrity_batch_dev(self._h, n, d_instances, d_seals, d_claim_digests, d_status,
+                                                                    d_recv or None, stream or None), 'zkv_risc0_set_verify_integrity_batch_dev')
 
     def vk_x_batch(self, instances, var_signals):
         n = len(var_signals)

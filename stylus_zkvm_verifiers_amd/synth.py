@@ -202,6 +202,41 @@ def make_batch(vm, base_seal, n, seed, pool=16, mutate_every=64, classes=MUTATIO
     return seals, mutated, mclass, flip_input
 
 
+INTEGRITY_MUTATION_CLASSES = ('flip_claim', 'wrong_selector', 'short_seal')
+
+
+def make_integrity_batch(base_seal, claim_digest, n, seed, pool=16, mutate_every=64, classes=INTEGRITY_MUTATION_CLASSES):
+    """`IRiscZeroVerifier::verify_integrity` batches from one real RISC Zero proof and its claim digest (golden real_proofs.json's
+    `claim_digest`).  Returns (seals uint8[n,260], claim digests uint8[n,32], seal lengths int64[n], mutated bool[n], mutation class
+    index int8[n] into `classes` (-1 = valid)).
+
+    flip_claim: one bit of the claim digest flipped (VerificationFailed); wrong_selector: the seal's first byte flipped
+    (SelectorMismatch); short_seal: the seal is cut to fewer than 260 bytes (InvalidProofData) -- the length array says so, the fixed
+    260-byte row of a device batch cannot, so device batches use classes without it."""
+    rng = SplitMix64(seed ^ 0x1A7E6E17)
+    seals, _, _, _ = make_batch('risc0', base_seal, n, seed, pool=pool, mutate_every=0)
+    claims = np.tile(np.frombuffer(bytes(claim_digest), dtype=np.uint8), (n, 1))
+    lens = np.full(n, 260, dtype=np.int64)
+    mutated = np.zeros(n, dtype=bool)
+    mclass = np.full(n, -1, dtype=np.int8)
+    for i in range(n):
+        if not (mutate_every and classes and i % mutate_every == mutate_every - 1):
+            continue
+        k = rng.below(len(classes))
+        mutated[i] = True
+        mclass[i] = k
+        if classes[k] == 'flip_claim':
+            b = rng.below(256)
+            claims[i, b // 8] ^= 1 << (b % 8)
+        elif classes[k] == 'wrong_selector':
+            seals[i, 0] ^= 0x01
+        elif classes[k] == 'short_seal':
+            lens[i] = 4 + rng.below(256)
+        else:
+            raise ValueError('unknown integrity mutation class %r' % classes[k])
+    return seals, claims, lens, mutated, mclass
+
+
 GROTH16_MUTATION_CLASSES = ('signal_first', 'signal_middle', 'signal_last', 'signal_eq_r', 'c_off_curve', 'b_out_of_subgroup')
 
 
