@@ -308,6 +308,7 @@ int zkv_bn254_pairing_batch_dev(zkv_ctx* ctx, size_t n, size_t k, const uint8_t*
  *     zkv_ctx_aggregate_counters stays {0, 0} (as for a key with alpha or beta at infinity). */
 #define ZKV_VM_GROTH16 3
 #define ZKV_GROTH16_MAX_IC 129
+/* Many keys behind one context, the key chosen per proof (Groth16 key sets): include/zkv_groth16_set.h. */
 zkv_ctx* zkv_groth16_ctx_create(const uint8_t* vk_words, size_t n_ic, int vm_type, int device);
 /* proofs: n x 256 bytes (a.x a.y b.x[0] b.x[1] b.y[0] b.y[1] c.x c.y); signals: n x (n_ic - 1) x 32 bytes big-endian;
  * verified[i] = 1 / 0 is the function's return value (signal >= R, malformed point, pairing product != 1 -> 0). */

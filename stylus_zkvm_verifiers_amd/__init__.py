@@ -9,11 +9,12 @@ from .risc0 import RiscZeroVerifier, RiscZeroVerifierSet
 from .sp1 import Sp1Verifier, Sp1PlonkVerifier
 from .bn254 import Bn254Precompiles
 from .groth16 import Groth16Verifier
+from .groth16_set import Groth16VerifierSet
 from .mixed import MixedVerifier
 from . import wire
 from .sharded import shard, shard_count, shard_devices, shard_peer_access
 
-__all__ = ['host_register', 'host_unregister', 'RiscZeroVerifier', 'RiscZeroVerifierSet', 'Sp1Verifier', 'Sp1PlonkVerifier', 'Bn254Precompiles', 'Groth16Verifier', 'MixedVerifier', 'VerifierError', 'errors', 'wire', 'device_count', 'shard', 'shard_count', 'shard_devices', 'shard_peer_access']
+__all__ = ['host_register', 'host_unregister', 'RiscZeroVerifier', 'RiscZeroVerifierSet', 'Sp1Verifier', 'Sp1PlonkVerifier', 'Bn254Precompiles', 'Groth16Verifier', 'Groth16VerifierSet', 'MixedVerifier', 'VerifierError', 'errors', 'wire', 'device_count', 'shard', 'shard_count', 'shard_devices', 'shard_peer_access']
 
 
 def device_count():

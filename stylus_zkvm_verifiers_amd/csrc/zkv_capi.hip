@@ -17,11 +17,13 @@
 #include <vector>
 
 #include "../../include/zkv.h"
+#include "../../include/zkv_groth16_set.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
 #include "zkv_plonk.h"
 #include "zkv_agg.h"
+#include "zkv_gset_layout.h"
 #include <sys/random.h>
 
 using namespace zkv;
@@ -44,6 +46,12 @@ struct zkv_ctx {
     bool long_key = false;
     G1A* d_ltab = nullptr; uint32_t* d_lwin = nullptr; uint32_t* d_lsig = nullptr;
     size_t lsig_cap = 0;
+    // ZKV_VM_GROTH16_SET (zkv_groth16_set.h): the keys back to back in gvk (gs_off[k]: byte offset of key k), their n_ic and sign
+    // convention.  A set runs the long-key path (long_key = true, g_n_ic = the largest n_ic: d_lsig stages the signals of a chunk); on the
+    // device one VkTables per key, the per-key records, all keys' IC[1..] window rows in one allocation and their window counts.
+    std::vector<size_t> gs_off; std::vector<uint32_t> gs_nic; std::vector<uint8_t> gs_neg;
+    std::vector<uint32_t> gs_totals; std::vector<uint64_t> gs_start;     // per call: proofs per key, slot layout (zkv_gset_layout.h)
+    VkTables* d_gs_tab = nullptr; GsetKey* d_gs_key = nullptr; G1A* d_gs_rows = nullptr; uint32_t* d_gs_win = nullptr;
     // device side (created lazily on the first compute call)
     bool dev_ready = false;
     hipStream_t stream = nullptr;
@@ -271,7 +279,8 @@ static void ctx_free_device(zkv_ctx* c) {
                      (void**)&c->d_rv_all, (void**)&c->d_inst, (void**)&c->d_inst_idx, (void**)&c->d_pkey, (void**)&c->d_plonk_tab,
                      (void**)&c->d_agg_tab, (void**)&c->d_agg, (void**)&c->ws2.prep, (void**)&c->ws2.norm, (void**)&c->ws2.f, (void**)&c->ws2.fe,
                      (void**)&c->ws2.flags, (void**)&c->ws2.g2bad, (void**)&c->d_status2, (void**)&c->d_agg_cnt, (void**)&c->ws3.prep, (void**)&c->ws3.flags,
-                     (void**)&c->ws3.g2bad, (void**)&c->d_status3, (void**)&c->d_agg_idx, (void**)&c->d_ltab, (void**)&c->d_lwin, (void**)&c->d_lsig};
+                     (void**)&c->ws3.g2bad, (void**)&c->d_status3, (void**)&c->d_agg_idx, (void**)&c->d_ltab, (void**)&c->d_lwin, (void**)&c->d_lsig,
+                     (void**)&c->d_gs_tab, (void**)&c->d_gs_key, (void**)&c->d_gs_rows, (void**)&c->d_gs_win};
     for (void** p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
     c->ws2.cap = 0; c->ws3 = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0}; c->agg_cap = 0; c->agg_key_ok = false;
     for (int k = 0; k < 6; k++) { if (c->hb[k]) (void)hipFree(c->hb[k]); c->hb[k] = nullptr; c->hb_cap[k] = 0; }
@@ -286,6 +295,7 @@ static void ctx_free_device(zkv_ctx* c) {
     c->dev_ready = false;
 }
 
+static int gset_device_setup(zkv_ctx* c);
 // Lazily creates the streams, the VK tables (set-up kernels) and the events; the per-chunk workspace comes from ctx_reserve().
 static int ctx_device_setup(zkv_ctx* c) {
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -301,6 +311,7 @@ static int ctx_device_setup(zkv_ctx* c) {
         HIP_TRY(hipEventCreateWithFlags(&c->ev_copied[b], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&c->ev_decoded[b], hipEventDisableTiming));
     }
+    if (c->vm == ZKV_VM_GROTH16_SET) return gset_device_setup(c);
     if (c->vm != ZKV_VM_BN254 && c->vm != ZKV_VM_MIXED) {
         VkRaw raw;
         if (c->vm == ZKV_VM_RISC0 || c->vm == ZKV_VM_RISC0_SET) host::fill_vk_risc0(raw, c->control_root_0, c->control_root_1, c->control_id);
@@ -2025,10 +2036,222 @@ ZKV_EXPORT int zkv_groth16_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_t*
     return mark_done(c, s);
 }
 
+// ------------------------------------------------------------------ Groth16 key sets (zkv_groth16_set.h)
+// Set-up of every key in six launches whatever the number of keys (k_gset.hip): VkTables per key (alpha, beta, gamma, delta and IC[0]:
+// 3.6 MB, most of it the unused short-key rows of the struct) and 512 KB of window rows per signal.
+static int gset_device_setup(zkv_ctx* c) {
+    const uint32_t K = (uint32_t)c->gs_nic.size();
+    std::vector<VkRaw> raw(K);
+    std::vector<GsetKey> keys(K);
+    std::vector<uint32_t> ic, sig_key;
+    uint32_t S = 0;
+    for (uint32_t k = 0; k < K; k++) {
+        const uint8_t* w = c->gvk.data() + c->gs_off[k];
+        host::fill_vk_generic(raw[k], w, 1u);                 // IC[0] only: IC[1..] take the window rows
+        const uint32_t n_sig = c->gs_nic[k] - 1;
+        keys[k] = GsetKey{nullptr, S, n_sig, c->gs_neg[k] ? 1u : 0u, 0u};
+        for (uint32_t b = 0; b < n_sig; b++) {
+            ic.resize(ic.size() + 16);
+            host::be_to_limbs(&ic[ic.size() - 16], w + 448 + 64 * (size_t)(b + 1));
+            host::be_to_limbs(&ic[ic.size() - 8], w + 480 + 64 * (size_t)(b + 1));
+            sig_key.push_back(k);
+        }
+        S += n_sig;
+    }
+    HIP_TRY(hipMalloc(&c->d_gs_tab, sizeof(VkTables) * K));
+    HIP_TRY(hipMemsetAsync(c->d_gs_tab, 0, sizeof(VkTables) * K, c->stream));
+    for (uint32_t k = 0; k < K; k++) keys[k].tab = c->d_gs_tab + k;
+    HIP_TRY(hipMalloc(&c->d_gs_key, sizeof(GsetKey) * K));
+    HIP_TRY(hipMemcpyAsync(c->d_gs_key, keys.data(), sizeof(GsetKey) * K, hipMemcpyHostToDevice, c->stream));
+    // the raw keys and points are only read by the set-up kernels: mx[0..2] until those are done
+    HIP_TRY(hipMalloc(&c->mx[0], sizeof(VkRaw) * K));
+    HIP_TRY(hipMemcpyAsync(c->mx[0], raw.data(), sizeof(VkRaw) * K, hipMemcpyHostToDevice, c->stream));
+    if (S) {
+        const size_t tab_bytes = (size_t)S * LONG_ROW_ENTRIES * sizeof(G1A);
+        HIP_TRY(hipMalloc(&c->d_gs_rows, tab_bytes));
+        HIP_TRY(hipMalloc(&c->d_gs_win, sizeof(uint32_t) * S));
+        HIP_TRY(hipMemsetAsync(c->d_gs_rows, 0, tab_bytes, c->stream));
+        HIP_TRY(hipMalloc(&c->mx[1], sizeof(uint32_t) * ic.size()));
+        HIP_TRY(hipMalloc(&c->mx[2], sizeof(uint32_t) * S));
+        HIP_TRY(hipMemcpyAsync(c->mx[1], ic.data(), sizeof(uint32_t) * ic.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->mx[2], sig_key.data(), sizeof(uint32_t) * S, hipMemcpyHostToDevice, c->stream));
+    }
+    launch_gset_setup(K, (const VkRaw*)c->mx[0], c->d_gs_tab, S, (const uint32_t*)c->mx[1], (const uint32_t*)c->mx[2], c->d_gs_rows, c->d_gs_win, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));                // the host vectors above go out of scope
+    for (int k = 0; k < 3; k++) { if (c->mx[k]) (void)hipFree(c->mx[k]); c->mx[k] = nullptr; }
+    return ZKV_OK;
+}
+ZKV_EXPORT zkv_ctx* zkv_groth16_set_create(size_t n_keys, const uint8_t* const* vk_words, const size_t* n_ic, const int* vm_type, int device) {
+    if (n_keys < 1 || n_keys > ZKV_GROTH16_SET_MAX_KEYS || !vk_words || !n_ic || !vm_type) return nullptr;
+    size_t bytes = 0, max_ic = 1;
+    for (size_t k = 0; k < n_keys; k++) {
+        if (!vk_words[k] || n_ic[k] < 1 || n_ic[k] > ZKV_GROTH16_MAX_IC || (vm_type[k] != ZKV_VM_RISC0 && vm_type[k] != ZKV_VM_SP1)) return nullptr;
+        bytes += 448 + 64 * n_ic[k];
+        if (n_ic[k] > max_ic) max_ic = n_ic[k];
+    }
+    zkv_ctx* c = new (std::nothrow) zkv_ctx();
+    if (!c) return nullptr;
+    c->vm = ZKV_VM_GROTH16_SET; c->device = device; c->initialized = true;
+    memset(&c->consts, 0, sizeof c->consts);
+    try {
+        c->gvk.reserve(bytes);
+        for (size_t k = 0; k < n_keys; k++) {
+            c->gs_off.push_back(c->gvk.size());
+            c->gvk.insert(c->gvk.end(), vk_words[k], vk_words[k] + 448 + 64 * n_ic[k]);
+            c->gs_nic.push_back((uint32_t)n_ic[k]);
+            c->gs_neg.push_back(vm_type[k] == ZKV_VM_RISC0 ? 1 : 0);
+        }
+    } catch (const std::bad_alloc&) { delete c; return nullptr; }
+    c->g_n_ic = (uint32_t)max_ic; c->long_key = true;
+    return c;
+}
+ZKV_EXPORT size_t zkv_groth16_set_size(const zkv_ctx* c) { return c && c->vm == ZKV_VM_GROTH16_SET ? c->gs_nic.size() : 0; }
+ZKV_EXPORT size_t zkv_groth16_set_signal_stride(const zkv_ctx* c) { return c && c->vm == ZKV_VM_GROTH16_SET ? (size_t)32 * (c->g_n_ic - 1) : 0; }
+ZKV_EXPORT int zkv_groth16_set_key_n_ic(const zkv_ctx* c, size_t key) {
+    if (!c || c->vm != ZKV_VM_GROTH16_SET) return ZKV_ERR_WRONG_CTX;
+    return key < c->gs_nic.size() ? (int)c->gs_nic[key] : ZKV_ERR_INVALID_ARG;
+}
+// The Miller-loop mapping the automatic policy picks for a batch of n proofs (as enqueue_chunk does for a chunk), in lanes per proof
+static int gset_auto_lanes(const zkv_ctx* c, size_t n) {
+    if (c->lanes) return c->lanes;
+    if (n <= dual_below()) return 128;
+    if (n <= wave_below()) return 64;
+    if (n <= wide_below()) return 16;
+    return 2;
+}
+// One call of n proofs, every buffer on the device, enqueued on s (c->mu held, device set up).  Partition (count per block; the per-key
+// totals come back to the host, which lays the groups out; place), then the stages chunk by chunk over the slots, then the verdicts back
+// to the caller's order.  Chunks of a set take no tail split (tail_of_chunk): every slot of a chunk runs the one mapping of the call.
+static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* d_proofs, const uint8_t* d_signals, uint8_t* d_verified, hipStream_t s) {
+    const uint32_t K = (uint32_t)c->gs_nic.size();
+    GsetPart p;
+    memset(&p, 0, sizeof p);
+    p.n = n; p.n_keys = K;
+    size_t per = (n + 255) / 256;                            // at most 256 partition blocks of a multiple of 64 proofs
+    per = (per + 63) / 64 * 64;
+    p.per_block = (uint32_t)per; p.blocks = (uint32_t)((n + per - 1) / per);
+    const size_t kb = (size_t)K * p.blocks;
+    int rc;
+    if ((rc = grow(&c->mx[3], &c->mx_cap[3], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[4], &c->mx_cap[4], 4 * (size_t)K)) != ZKV_OK ||
+        (rc = grow(&c->mx[5], &c->mx_cap[5], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[6], &c->mx_cap[6], 4 * n)) != ZKV_OK ||
+        (rc = grow(&c->mx[7], &c->mx_cap[7], 8 * ((size_t)K + 1))) != ZKV_OK) return rc;
+    p.key = d_key; p.cnt = (uint32_t*)c->mx[3]; p.totals = (uint32_t*)c->mx[4]; p.off = (uint32_t*)c->mx[5]; p.pos = (uint32_t*)c->mx[6];
+    HIP_TRY(hipMemsetAsync(p.totals, 0, 4 * (size_t)K, s));
+    launch_gset_count(p, s);
+    HIP_TRY(hipGetLastError());
+    c->gs_totals.resize(K); c->gs_start.resize((size_t)K + 1);
+    HIP_TRY(hipMemcpyAsync(c->gs_totals.data(), p.totals, 4 * (size_t)K, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    size_t placed = 0;
+    for (uint32_t k = 0; k < K; k++) placed += c->gs_totals[k];
+    uint64_t slots = 0;
+    const int lanes = gset_choose(c->gs_totals.data(), K, gset_auto_lanes(c, placed), c->lanes != 0, c->gs_start.data(), &slots);
+    const size_t M = (size_t)slots;
+    size_t cap = 0;
+    if ((rc = groth16_ready(c, M ? M : 1, &cap)) != ZKV_OK) return rc;     // (growing frees buffers, which synchronises the device)
+    if ((rc = grow(&c->mx[8], &c->mx_cap[8], 4 * M + 4)) != ZKV_OK || (rc = grow(&c->mx[9], &c->mx_cap[9], 4 * M + 4)) != ZKV_OK ||
+        (rc = grow(&c->d_st_all, &c->st_all_cap, M + 1)) != ZKV_OK) return rc;
+    p.idx = (uint32_t*)c->mx[8]; p.skey = (uint32_t*)c->mx[9];
+    HIP_TRY(hipMemcpyAsync(c->mx[7], c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(p.idx, 0xFF, 4 * M + 4, s));      // pad slots: GSET_NONE
+    HIP_TRY(hipMemsetAsync(p.skey, 0, 4 * M + 4, s));        // (and key 0: a slot's key is only read for live slots, this keeps any read in the set)
+    launch_gset_place(p, (const uint64_t*)c->mx[7], s);
+    HIP_TRY(hipGetLastError());
+    const int fe = lanes == 2 ? 2 : lanes == 16 ? 16 : 64;
+    for (size_t base = 0; base < M; base += cap) {
+        const size_t m = M - base < cap ? M - base : cap;
+        const bool timed = base + cap >= M;
+        GsetChunk ch;
+        memset(&ch, 0, sizeof ch);
+        ch.m = m; ch.slot0 = base; ch.idx = p.idx; ch.skey = p.skey;
+        ch.keys = c->d_gs_key; ch.rows = c->d_gs_rows; ch.win = c->d_gs_win;
+        ch.proofs = d_proofs; ch.signals = d_signals; ch.sig_stride = 32 * (c->g_n_ic - 1);
+        ch.sig = c->d_lsig; ch.sig_cap = c->lsig_cap; ch.status = c->d_st_all + base;
+        if (timed) (void)hipEventRecord(c->ev[0], s);
+        launch_gset_prep(ch, c->ws, s);
+        if (timed) (void)hipEventRecord(c->ev[1], s);
+        launch_gset_msm(ch, msm_lanes_long(c, m), c->ws, s);
+        if (timed) (void)hipEventRecord(c->ev[2], s);
+        if (lanes != 2) launch_g2chk2(m, c->ws, ch.status, s);       // (the lane-pair Miller loop is the subgroup test itself)
+        if (timed) (void)hipEventRecord(c->ev[3], s);
+        launch_gset_miller(lanes, m, p.skey + base, c->d_gs_key, c->ws, ch.status, s);
+        if (timed) (void)hipEventRecord(c->ev[4], s);
+        if (fe == 2) launch_finalexp2(m, c->ws, ch.status, s);
+        else if (fe == 16) launch_finalexp_w(m, c->ws, ch.status, s);
+        else launch_finalexp_w64(m, c->ws, ch.status, s);
+        if (timed) (void)hipEventRecord(c->ev[5], s);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!M) for (int e = 0; e < 6; e++) (void)hipEventRecord(c->ev[e], s);
+    launch_gset_return(n, p.pos, c->d_st_all, d_verified, s);
+    HIP_TRY(hipGetLastError());
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_groth16_set_verify_batch_dev(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* d_proofs, const uint8_t* d_signals,
+                                                uint8_t* d_verified, void* stream) {
+    if (!c || c->vm != ZKV_VM_GROTH16_SET) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_key || !d_proofs || !d_verified || (c->g_n_ic > 1 && !d_signals))) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    size_t cap = 0;
+    int rc = groth16_ready(c, n, &cap);
+    if (rc != ZKV_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    if ((rc = run_gset(c, n, d_key, d_proofs, d_signals, d_verified, s)) != ZKV_OK) return rc;
+    return mark_done(c, s);
+}
+ZKV_EXPORT int zkv_groth16_set_verify_batch(zkv_ctx* c, size_t n, const uint32_t* key, const uint8_t* proofs, const uint8_t* signals, uint8_t* verified) {
+    if (!c || c->vm != ZKV_VM_GROTH16_SET) return ZKV_ERR_WRONG_CTX;
+    const size_t stride = (size_t)32 * (c->g_n_ic - 1);
+    if (n && (!key || !proofs || !verified || (stride && !signals))) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    size_t cap = 0;
+    int rc = groth16_ready(c, n, &cap);
+    if (rc != ZKV_OK) return rc;
+    if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
+    // the whole batch in HBM: keys, proofs, signals (hb[0..2]) and the verdicts (hb[3])
+    if ((rc = grow(&c->hb[0], &c->hb_cap[0], 4 * n)) != ZKV_OK || (rc = grow(&c->hb[1], &c->hb_cap[1], 256 * n)) != ZKV_OK ||
+        (rc = grow(&c->hb[2], &c->hb_cap[2], stride * n + 8)) != ZKV_OK || (rc = grow(&c->hb[3], &c->hb_cap[3], n)) != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c->hb[0], key, 4 * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->hb[1], proofs, 256 * n, hipMemcpyHostToDevice, c->stream));
+    if (stride) HIP_TRY(hipMemcpyAsync(c->hb[2], signals, stride * n, hipMemcpyHostToDevice, c->stream));
+    if ((rc = run_gset(c, n, (const uint32_t*)c->hb[0], c->hb[1], c->hb[2], c->hb[3], c->stream)) != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(verified, c->hb[3], n, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = mark_done(c, c->stream)) != ZKV_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_groth16_set_vk_x_batch(zkv_ctx* c, size_t n, const uint32_t* key, const uint8_t* signals, uint8_t* out) {
+    if (!c || c->vm != ZKV_VM_GROTH16_SET) return ZKV_ERR_WRONG_CTX;
+    const size_t stride = (size_t)32 * (c->g_n_ic - 1);
+    if (n && (!key || !out || (stride && !signals))) return ZKV_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n; i++) if (key[i] >= c->gs_nic.size()) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    size_t cap = 0;
+    int rc = groth16_ready(c, n, &cap);
+    if (rc != ZKV_OK) return rc;
+    if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
+    if ((rc = grow(&c->hb[0], &c->hb_cap[0], 4 * n)) != ZKV_OK || (rc = grow(&c->hb[2], &c->hb_cap[2], stride * n + 8)) != ZKV_OK ||
+        (rc = grow(&c->hb[4], &c->hb_cap[4], 64 * n)) != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c->hb[0], key, 4 * n, hipMemcpyHostToDevice, c->stream));
+    if (stride) HIP_TRY(hipMemcpyAsync(c->hb[2], signals, stride * n, hipMemcpyHostToDevice, c->stream));
+    launch_gset_vk_x(n, msm_lanes_long(c, n), (const uint32_t*)c->hb[0], c->d_gs_key, c->d_gs_rows, c->d_gs_win, c->hb[2], (uint32_t)stride, c->hb[4], c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, c->hb[4], 64 * n, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = mark_done(c, c->stream)) != ZKV_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ZKV_OK;
+}
+
 // ------------------------------------------------------------------ Groth16 core pieces
 ZKV_EXPORT int zkv_ctx_vk_x_batch(zkv_ctx* c, size_t n, const uint8_t* var_signals, uint8_t* out) {
     if (is_sharded(c)) c = c->shards[0];
-    if (!c || c->vm == ZKV_VM_BN254 || c->vm == ZKV_VM_RISC0_SET || c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_PLONK) return ZKV_ERR_WRONG_CTX;
+    if (!c || c->vm == ZKV_VM_BN254 || c->vm == ZKV_VM_RISC0_SET || c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_PLONK || c->vm == ZKV_VM_GROTH16_SET)
+        return ZKV_ERR_WRONG_CTX;
     if (c->vm == ZKV_VM_RISC0 && !c->initialized) return ZKV_ERR_INVALID_ARG;
     if (n && (!var_signals || !out)) return ZKV_ERR_INVALID_ARG;
     if (!n) return ZKV_OK;
@@ -2114,6 +2337,7 @@ ZKV_EXPORT int zkv_ctx_set_lanes_per_proof(zkv_ctx* c, int lanes) {
 // Aggregate check on / off (zkv_agg.h).  seed32 = nullptr draws the 32 secret bytes from the operating system.
 ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t* seed32) {
     if (!c || (enable != 0 && enable != 1 && enable != 16 && enable != 32 && enable != 64 && enable != 128 && enable != 256)) return ZKV_ERR_INVALID_ARG;
+    if (c->vm == ZKV_VM_GROTH16_SET) return ZKV_OK;     // a key set runs the per-proof path (as a long key does): nothing to switch
     uint8_t seed[32];
     if (enable) {
         if (seed32) memcpy(seed, seed32, 32);
@@ -2187,7 +2411,9 @@ ZKV_EXPORT int zkv_diag_wait_faults(int device, uint64_t* out) {
     HIP_TRY(hipSetDevice(device));
     unsigned long long v = 0;
     if (zkv::read_wait_faults(&v) != 0) return ZKV_ERR_HIP;
-    *out = v;
+    unsigned long long g = 0;                            // the key-set Miller kernel counts its own (k_gset_pair.hip)
+    if (zkv::read_gset_wait_faults(&g) != 0) return ZKV_ERR_HIP;
+    *out = v + g;
     return ZKV_OK;
 }
 ZKV_EXPORT int zkv_ctx_shard_peer_access(zkv_ctx* c, size_t shard) {
@@ -2223,7 +2449,7 @@ ZKV_EXPORT int zkv_ctx_reserve(zkv_ctx* c, size_t n) {
     }
     std::lock_guard<std::mutex> lk(c->mu);
     size_t chunk;
-    return c->vm == ZKV_VM_GROTH16 ? groth16_ready(c, n, &chunk) : ctx_ready(c, n);
+    return c->vm == ZKV_VM_GROTH16 || c->vm == ZKV_VM_GROTH16_SET ? groth16_ready(c, n, &chunk) : ctx_ready(c, n);
 }
 ZKV_EXPORT int zkv_ctx_synchronize(zkv_ctx* c) {
     if (!c) return ZKV_ERR_INVALID_ARG;

@@ -118,6 +118,41 @@ struct MixedArgs {
 void launch_mixed_partition(const MixedArgs& a, uint32_t* cnt, uint32_t* totals, hipStream_t s);
 void launch_mixed_return(size_t m, const uint32_t* idx, const uint8_t* c_status, const uint8_t* c_recv, uint8_t* status, uint8_t* recv, hipStream_t s);
 
+// Groth16 key sets (k_gset.hip, k_gset_pair.hip; zkv_gset_layout.h): per-key device record.  tab: the key's VkTables (alpha, beta, gamma,
+// delta, IC[0]); its IC[1..] window rows are rows [sig0, sig0 + n_sig) of the set's one row allocation (LongKey layout), and win[sig0 ..]
+// their window counts.
+struct GsetKey { const VkTables* tab; uint32_t sig0, n_sig, negate, pad; };
+constexpr uint32_t GSET_NONE = 0xFFFFFFFFu;      // pad slot (idx) / proof with no key (pos)
+struct GsetPart {
+    size_t n; uint32_t n_keys, blocks, per_block;   // per_block: proofs per partition block (a multiple of 64)
+    const uint32_t* key;                            // caller's key per proof
+    uint32_t* cnt;                                  // n_keys x blocks, key-major
+    uint32_t* totals;                               // n_keys
+    uint32_t* off;                                  // n_keys x blocks: first slot of (key, block)
+    uint32_t* idx; uint32_t* skey;                  // per slot: caller index (GSET_NONE: pad) and key
+    uint32_t* pos;                                  // per proof: slot (GSET_NONE: key >= n_keys)
+};
+struct GsetChunk {
+    size_t m, slot0;                                // slots [slot0, slot0 + m) of the call
+    const uint32_t* idx; const uint32_t* skey;      // whole-call slot tables
+    const GsetKey* keys; const G1A* rows; const uint32_t* win;
+    const uint8_t* proofs; const uint8_t* signals; uint32_t sig_stride;   // caller rows: 256 bytes / sig_stride bytes per proof
+    uint32_t* sig; size_t sig_cap;                  // staged signals: limb k of signal b of slot j at sig[(8 b + k) * sig_cap + j]
+    uint8_t* status;                                // m statuses (slot order)
+};
+void launch_gset_setup(uint32_t n_keys, const VkRaw* d_raw, VkTables* d_tabs, uint32_t n_sig_all, const uint32_t* d_ic, const uint32_t* d_sig_key,
+                       G1A* rows, uint32_t* win, hipStream_t s);
+void launch_gset_count(const GsetPart& p, hipStream_t s);
+void launch_gset_place(const GsetPart& p, const uint64_t* d_start, hipStream_t s);
+void launch_gset_prep(const GsetChunk& c, const Workspace& ws, hipStream_t s);
+void launch_gset_msm(const GsetChunk& c, uint32_t lanes, const Workspace& ws, hipStream_t s);
+void launch_gset_vk_x(size_t n, uint32_t lanes, const uint32_t* key, const GsetKey* keys, const G1A* rows, const uint32_t* win, const uint8_t* sig,
+                      uint32_t sig_stride, uint8_t* out, hipStream_t s);
+void launch_gset_return(size_t n, const uint32_t* pos, const uint8_t* status, uint8_t* verified, hipStream_t s);
+// Miller loops with the key of each wavefront's first slot (k_gset_pair.hip): lanes 2 / 16 / 64 / 128 as zkv_ctx_set_lanes_per_proof
+void launch_gset_miller(int lanes, size_t m, const uint32_t* skey, const GsetKey* keys, const Workspace& ws, uint8_t* status, hipStream_t s);
+int read_gset_wait_faults(unsigned long long* out);     // k_gset_miller_w64d's counterpart of read_wait_faults
+
 // SP1 PLONK path (k_plonk.hip, zkv_plonk.h)
 #ifndef ZKV_PLONK_PROOF_BYTES
 #define ZKV_PLONK_PROOF_BYTES 868    /* selector + the 27 words of gnark's MarshalSolidity with one BSB22 commitment */
