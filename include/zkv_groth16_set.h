@@ -6,8 +6,16 @@
  * ZKV_OK / ZKV_ERR_* codes); DESIGN.md section 11 describes the device pipeline.
  *
  *   - A set is immutable and single-device (zkv_ctx_create_sharded refuses it).  zkv_ctx_vm returns ZKV_VM_GROTH16_SET.
- *   - zkv_ctx_destroy / _synchronize / _reserve / _set_lanes_per_proof / _last_stage_ms work as on other contexts;
- *     zkv_ctx_set_aggregate_check returns ZKV_OK and changes nothing (a set runs the per-proof path; the counters stay {0, 0}).
+ *   - zkv_ctx_destroy / _synchronize / _reserve / _set_lanes_per_proof / _last_stage_ms work as on other contexts.
+ *   - zkv_ctx_set_aggregate_check works on a set as on other contexts: enable = 1 automatic size, 16 / 32 / 64 / 128 / 256 a fixed
+ *     size, 0 off; the same secret and rekey rules.  zkv_ctx_aggregate_counters counts the set's sub-batches (checked, and failed then
+ *     verified proof by proof).  The check engages for a call only when the mapping is automatic (lanes 0), the call places at least
+ *     ZKV_AGG_MIN proofs and the aggregate buffers could be allocated; otherwise the call runs the per-proof path unchanged.
+ *     A key is aggregate-capable when it is valid and alpha and beta are finite; all proofs of other keys, and of keys past the set,
+ *     take the per-proof path or answer 0 as without the check.  Every sub-batch holds proofs of one key (the equation uses that key's
+ *     alpha, beta, gamma and delta).  Statuses are the per-proof ones.  The first call with the check on allocates every key's
+ *     aggregate tables: about 0.53 MB per key (0.5 GB for 1,024 keys), plus 224 B of rows per proof in flight and the pseudo-proofs'
+ *     workspace; with the check off (the default) nothing is allocated.
  *   - Proofs are 256 bytes each, as for zkv_groth16_verify_batch.  Signals are rows of zkv_groth16_set_signal_stride bytes:
  *     the first n_ic[k] - 1 32-byte big-endian words of row i are proof i's signals; the words after them are never read.
  */

@@ -52,6 +52,9 @@ struct zkv_ctx {
     std::vector<size_t> gs_off; std::vector<uint32_t> gs_nic; std::vector<uint8_t> gs_neg;
     std::vector<uint32_t> gs_totals; std::vector<uint64_t> gs_start;     // per call: proofs per key, slot layout (zkv_gset_layout.h)
     VkTables* d_gs_tab = nullptr; GsetKey* d_gs_key = nullptr; G1A* d_gs_rows = nullptr; uint32_t* d_gs_win = nullptr;
+    // aggregate check on a set: which keys can take it (d_agg_tab then holds one AggTables per key), and per call the two-region layout
+    // (zkv_gset_layout.h: gset_agg_choose) and every aggregate chunk's pseudo-proof slots (run_gset)
+    std::vector<uint8_t> gs_agg_ok; std::vector<uint32_t> gs_agg_n, gs_rest, gs_nsb, gs_amap; std::vector<uint64_t> gs_map, gs_pst;
     // device side (created lazily on the first compute call)
     bool dev_ready = false;
     hipStream_t stream = nullptr;
@@ -442,7 +445,10 @@ static int agg_reserve(zkv_ctx* c) {
                      (void**)&c->d_agg_idx};
     for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
     c->agg_cap = 0; c->ws2.cap = 0; c->ws3.cap = 0;
-    const size_t cap = c->ws.cap, cap2 = (cap + 15) / 16;      // room for the smallest sub-batch size
+    // room for the smallest sub-batch size; a key set pads its pseudo-proofs per key up to 1.25 times (gset_choose in run_gset) and runs
+    // its second pass in place (k_gset_agg_mark): no dense workspace, no index list
+    const bool set = c->vm == ZKV_VM_GROTH16_SET;
+    const size_t cap = c->ws.cap, cap2 = (cap + 15) / 16 + (set ? (cap + 63) / 64 : 0);
     if (hipMalloc(&c->d_agg, sizeof(uint32_t) * WS_AGG_WORDS * cap) != hipSuccess ||
         hipMalloc(&c->ws2.prep, sizeof(uint32_t) * WS_PREP_WORDS * cap2) != hipSuccess ||
         hipMalloc(&c->ws2.norm, sizeof(uint32_t) * WS_NORM_WORDS * cap2) != hipSuccess ||
@@ -450,15 +456,15 @@ static int agg_reserve(zkv_ctx* c) {
         hipMalloc(&c->ws2.fe, sizeof(uint32_t) * WS_FE_WORDS * cap2) != hipSuccess ||
         hipMalloc(&c->ws2.flags, sizeof(uint32_t) * cap2) != hipSuccess || hipMalloc(&c->ws2.g2bad, sizeof(uint32_t) * cap2) != hipSuccess ||
         hipMalloc(&c->d_status2, cap2) != hipSuccess ||
-        hipMalloc(&c->ws3.prep, sizeof(uint32_t) * WS_PREP_WORDS * cap) != hipSuccess || hipMalloc(&c->ws3.flags, sizeof(uint32_t) * cap) != hipSuccess ||
-        hipMalloc(&c->ws3.g2bad, sizeof(uint32_t) * cap) != hipSuccess || hipMalloc(&c->d_status3, cap) != hipSuccess ||
-        hipMalloc(&c->d_agg_idx, sizeof(uint32_t) * cap) != hipSuccess) {
+        (!set && (hipMalloc(&c->ws3.prep, sizeof(uint32_t) * WS_PREP_WORDS * cap) != hipSuccess || hipMalloc(&c->ws3.flags, sizeof(uint32_t) * cap) != hipSuccess ||
+                  hipMalloc(&c->ws3.g2bad, sizeof(uint32_t) * cap) != hipSuccess || hipMalloc(&c->d_status3, cap) != hipSuccess ||
+                  hipMalloc(&c->d_agg_idx, sizeof(uint32_t) * cap) != hipSuccess))) {
         // no room for the extra 0.9 KB per proof in flight: the chunk takes the ordinary kernels (enqueue_chunk looks at agg_cap)
         (void)hipGetLastError();
         for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
         return ZKV_OK;
     }
-    c->ws3.norm = c->ws.norm; c->ws3.f = c->ws.f; c->ws3.fe = c->ws.fe; c->ws3.cap = cap;
+    if (!set) { c->ws3.norm = c->ws.norm; c->ws3.f = c->ws.f; c->ws3.fe = c->ws.fe; c->ws3.cap = cap; }
     c->ws2.cap = cap2; c->agg_cap = cap;
     return ZKV_OK;
 }
@@ -2120,6 +2126,100 @@ static int gset_auto_lanes(const zkv_ctx* c, size_t n) {
     if (n <= wide_below()) return 16;
     return 2;
 }
+// Aggregate check on a set: every key's AggTables (k_setup_agg's contents, 0.53 MB per key) in d_agg_tab and which keys can take the check,
+// built the first time a call wants the check -- not at set creation, so a set that never uses it does not grow -- and the counters.
+// false: no key can, or no room (the call then runs the per-proof path).
+static bool gset_agg_tables(zkv_ctx* c) {
+    if (c->d_agg_tab) return c->agg_key_ok;
+    const uint32_t K = (uint32_t)c->gs_nic.size();
+    std::vector<VkRaw> raw(K);
+    for (uint32_t k = 0; k < K; k++) host::fill_vk_generic(raw[k], c->gvk.data() + c->gs_off[k], 1u);
+    VkRaw* d_raw = nullptr;
+    if (hipMalloc(&c->d_agg_tab, sizeof(AggTables) * K) != hipSuccess || hipMalloc(&d_raw, sizeof(VkRaw) * K) != hipSuccess ||
+        (!c->d_agg_cnt && (hipMalloc(&c->d_agg_cnt, 3 * sizeof(unsigned long long)) != hipSuccess ||
+                           hipMemset(c->d_agg_cnt, 0, 3 * sizeof(unsigned long long)) != hipSuccess))) {
+        (void)hipGetLastError();
+        if (c->d_agg_tab) (void)hipFree(c->d_agg_tab);
+        if (d_raw) (void)hipFree(d_raw);
+        c->d_agg_tab = nullptr;
+        return false;
+    }
+    std::vector<uint32_t> ok(K);
+    bool good = hipMemcpyAsync(d_raw, raw.data(), sizeof(VkRaw) * K, hipMemcpyHostToDevice, c->stream) == hipSuccess;
+    if (good) {
+        launch_gset_setup_agg(K, d_raw, c->d_gs_tab, c->d_agg_tab, c->stream);
+        good = hipGetLastError() == hipSuccess;
+        for (uint32_t k = 0; k < K && good; k++)
+            good = hipMemcpyAsync(&ok[k], &c->d_agg_tab[k].ok, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        good = good && hipStreamSynchronize(c->stream) == hipSuccess;
+    }
+    (void)hipFree(d_raw);
+    if (!good) { (void)hipGetLastError(); (void)hipFree(c->d_agg_tab); c->d_agg_tab = nullptr; return false; }
+    c->gs_agg_ok.assign(K, 0);
+    c->agg_key_ok = false;
+    for (uint32_t k = 0; k < K; k++) { c->gs_agg_ok[k] = ok[k] ? 1 : 0; c->agg_key_ok = c->agg_key_ok || ok[k]; }
+    return c->agg_key_ok;
+}
+// One aggregate chunk's pseudo-proofs: n2 sub-batches, laid out per key and padded to the proofs per wavefront of the Miller mapping
+// `lanes` (gset_choose over the sub-batch counts, as the proofs themselves), so k_gset_miller* take one key per wavefront.  In gs_amap from
+// word `off`: psl (sub-batch -> slot, n2 words), then the key of every pseudo slot (slots words).
+struct GsetAggChunk { size_t base, m, n2, off; uint64_t slots; int lanes; };
+static GsetAggChunk gset_agg_chunk(zkv_ctx* c, size_t base, size_t m, uint32_t sub) {
+    const uint32_t K = (uint32_t)c->gs_nic.size();
+    GsetAggChunk g{base, m, m / sub, c->gs_amap.size(), 0, 0};
+    c->gs_nsb.assign(K, 0);
+    c->gs_pst.resize((size_t)K + 1);
+    const uint64_t* astart = c->gs_map.data();
+    for (uint32_t k = 0; k < K; k++) {
+        const uint64_t lo = astart[k] > base ? astart[k] : base, hi = astart[k] + c->gs_agg_n[k] < base + m ? astart[k] + c->gs_agg_n[k] : base + m;
+        if (hi > lo) c->gs_nsb[k] = (uint32_t)((hi - lo) / sub);
+    }
+    g.lanes = gset_choose(c->gs_nsb.data(), K, gset_auto_lanes(c, g.n2), 0, c->gs_pst.data(), &g.slots);
+    if (g.slots > c->ws2.cap) g.lanes = gset_choose(c->gs_nsb.data(), K, 64, 1, c->gs_pst.data(), &g.slots);     // (no padding)
+    c->gs_amap.resize(g.off + g.n2 + g.slots, 0);
+    uint32_t* psl = c->gs_amap.data() + g.off;
+    uint32_t* skey2 = psl + g.n2;
+    for (uint32_t k = 0; k < K; k++) {
+        if (!c->gs_nsb[k]) continue;
+        const size_t sb0 = (size_t)((astart[k] > base ? astart[k] : base) - base) / sub;
+        for (uint32_t t = 0; t < c->gs_nsb[k]; t++) psl[sb0 + t] = (uint32_t)(c->gs_pst[k] + t);
+        for (uint64_t q = c->gs_pst[k]; q < c->gs_pst[k + 1]; q++) skey2[q] = k;
+    }
+    return g;
+}
+// The aggregate check of one chunk of a set's aggregate region (zkv_agg.h; k_gset_agg.hip): PREP, the coefficients and r A', r C, the
+// Miller loop of the variable pair, one pseudo-proof per sub-batch with its key's gamma / delta lines and ML(alpha, beta), the product of the
+// proofs' Miller values into it, its final exponentiation, the verdicts, and the per-proof kernels once more over the proofs of the
+// sub-batches that failed (in place: k_gset_agg_mark).
+static void enqueue_gset_agg(zkv_ctx* c, const GsetChunk& ch, const GsetAggChunk& g, const uint32_t* skey, const uint32_t* d_amap, uint32_t sub,
+                             hipStream_t s, bool timed) {
+    const size_t m = ch.m;
+    const uint32_t sub64 = sub < 64 ? sub : 64, grp = agg_group(sub64);
+    const uint32_t* psl = d_amap + g.off;
+    const uint32_t* skey2 = psl + g.n2;
+    if (timed) (void)hipEventRecord(c->ev[0], s);
+    launch_gset_prep(ch, c->ws, s);
+    if (timed) (void)hipEventRecord(c->ev[1], s);
+    agg_next_coefficients(c);
+    launch_agg_g1(m, c->d_gs_tab, nullptr, c->ws, c->d_agg, c->agg_seed, true, s);      // (reads no key: the set's tables have n_var = 0)
+    if (timed) { (void)hipEventRecord(c->ev[2], s); (void)hipEventRecord(c->ev[3], s); }
+    if (grp > 1) launch_gset_agg_miller(m, grp, skey, c->d_gs_key, c->ws, ch.status, s);
+    else launch_gset_miller(2, m, skey, c->d_gs_key, c->ws, ch.status, s);
+    (void)hipMemsetAsync(c->ws2.flags, 0, sizeof(uint32_t) * g.slots, s);     // pad slots of the pseudo-proofs: no proof
+    launch_gset_agg_reduce(ch, sub64, grp, c->ws, c->d_agg, c->d_agg_tab, c->ws2, c->d_status2, psl, sub > 64, s);
+    if (sub > 64) launch_gset_agg_combine(ch, g.n2, sub / 64, c->d_agg_tab, c->ws2, c->d_status2, psl, s);
+    launch_gset_miller(g.lanes, (size_t)g.slots, skey2, c->d_gs_key, c->ws2, c->d_status2, s);
+    if (timed) (void)hipEventRecord(c->ev[4], s);
+    launch_gset_agg_fprod(m, g.n2, sub, grp, c->ws, c->d_agg, c->ws2, psl, s);
+    if (g.lanes == 2) launch_finalexp2((size_t)g.slots, c->ws2, c->d_status2, s);
+    else if (g.lanes == 16) launch_finalexp_w((size_t)g.slots, c->ws2, c->d_status2, s);
+    else launch_finalexp_w64((size_t)g.slots, c->ws2, c->d_status2, s);
+    launch_gset_agg_mark(m, sub, grp, c->ws, c->d_agg, c->d_status2, psl, ch.status, c->d_agg_cnt, s);
+    launch_gset_msm(ch, msm_lanes_long(c, m), c->ws, s);
+    launch_gset_miller(2, m, skey, c->d_gs_key, c->ws, ch.status, s);       // (lane pairs: the subgroup test of B included)
+    launch_finalexp2(m, c->ws, ch.status, s);
+    if (timed) (void)hipEventRecord(c->ev[5], s);
+}
 // One call of n proofs, every buffer on the device, enqueued on s (c->mu held, device set up).  Partition (count per block; the per-key
 // totals come back to the host, which lays the groups out; place), then the stages chunk by chunk over the slots, then the verdicts back
 // to the caller's order.  Chunks of a set take no tail split (tail_of_chunk): every slot of a chunk runs the one mapping of the call.
@@ -2145,21 +2245,65 @@ static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
     HIP_TRY(hipStreamSynchronize(s));
     size_t placed = 0;
     for (uint32_t k = 0; k < K; k++) placed += c->gs_totals[k];
-    uint64_t slots = 0;
-    const int lanes = gset_choose(c->gs_totals.data(), K, gset_auto_lanes(c, placed), c->lanes != 0, c->gs_start.data(), &slots);
-    const size_t M = (size_t)slots;
+    // The aggregate check (a fixed mapping, a small call or no capable key: none): the aggregate region [0, R) and the per-proof region
+    // (zkv_gset_layout.h gset_agg_choose); R = 0 falls back to the one-region layout below.
+    bool agg = c->agg_on && c->lanes == 0 && placed >= agg_min() && gset_agg_tables(c) && agg_wanted(c);
+    const uint32_t sub = c->agg_sub, unit = gset_agg_unit(sub);
+    uint64_t slots = 0, R = 0;
+    int lanes = 0;
     size_t cap = 0;
+    if (agg) {
+        c->gs_agg_n.resize(K); c->gs_rest.resize(K); c->gs_map.assign(3 * ((size_t)K + 1), 0);
+        size_t rest = 0;
+        for (uint32_t k = 0; k < K; k++) rest += c->gs_agg_ok[k] ? c->gs_totals[k] % unit : c->gs_totals[k];
+        lanes = gset_agg_choose(c->gs_totals.data(), c->gs_agg_ok.data(), K, sub, gset_auto_lanes(c, rest), 0, c->gs_agg_n.data(), c->gs_map.data(),
+                                c->gs_rest.data(), c->gs_map.data() + K + 1, &R, &slots);
+        for (uint32_t k = 0; k < K; k++) c->gs_map[2 * ((size_t)K + 1) + k] = c->gs_agg_n[k];
+        if ((rc = groth16_ready(c, (size_t)slots, &cap)) != ZKV_OK) return rc;
+        agg = R > 0 && c->agg_cap >= c->ws.cap && cap >= unit;       // (the aggregate buffers could be allocated)
+    }
+    if (!agg) {
+        R = 0;
+        lanes = gset_choose(c->gs_totals.data(), K, gset_auto_lanes(c, placed), c->lanes != 0, c->gs_start.data(), &slots);
+    }
+    const size_t M = (size_t)slots;
     if ((rc = groth16_ready(c, M ? M : 1, &cap)) != ZKV_OK) return rc;     // (growing frees buffers, which synchronises the device)
     if ((rc = grow(&c->mx[8], &c->mx_cap[8], 4 * M + 4)) != ZKV_OK || (rc = grow(&c->mx[9], &c->mx_cap[9], 4 * M + 4)) != ZKV_OK ||
         (rc = grow(&c->d_st_all, &c->st_all_cap, M + 1)) != ZKV_OK) return rc;
     p.idx = (uint32_t*)c->mx[8]; p.skey = (uint32_t*)c->mx[9];
-    HIP_TRY(hipMemcpyAsync(c->mx[7], c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(p.idx, 0xFF, 4 * M + 4, s));      // pad slots: GSET_NONE
     HIP_TRY(hipMemsetAsync(p.skey, 0, 4 * M + 4, s));        // (and key 0: a slot's key is only read for live slots, this keeps any read in the set)
-    launch_gset_place(p, (const uint64_t*)c->mx[7], s);
+    if (agg) {
+        if ((rc = grow(&c->mx[7], &c->mx_cap[7], 8 * (c->gs_map.size() + K + 1))) != ZKV_OK) return rc;
+        HIP_TRY(hipMemsetAsync(c->mx[7] + 8 * c->gs_map.size(), 0, 8 * ((size_t)K + 1), s));      // zero starts: k_gset_scan gives ranks
+        HIP_TRY(hipMemcpyAsync(c->mx[7], c->gs_map.data(), 8 * c->gs_map.size(), hipMemcpyHostToDevice, s));
+        launch_gset_agg_place(p, (const uint64_t*)c->mx[7] + c->gs_map.size(), (const uint64_t*)c->mx[7], s);
+    } else {
+        HIP_TRY(hipMemcpyAsync(c->mx[7], c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
+        launch_gset_place(p, (const uint64_t*)c->mx[7], s);
+    }
     HIP_TRY(hipGetLastError());
+    if (agg) {
+        // aggregate chunks end on multiples of the unit, so no sub-batch and no 64-proof block straddles two of them
+        const size_t capa = cap / unit * unit;
+        std::vector<GsetAggChunk> plan;
+        c->gs_amap.clear();
+        for (size_t base = 0; base < R; base += capa) plan.push_back(gset_agg_chunk(c, base, R - base < capa ? (size_t)R - base : capa, sub));
+        if ((rc = grow(&c->mx[10], &c->mx_cap[10], 4 * c->gs_amap.size() + 4)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(c->mx[10], c->gs_amap.data(), 4 * c->gs_amap.size(), hipMemcpyHostToDevice, s));
+        for (const GsetAggChunk& g : plan) {
+            GsetChunk ch;
+            memset(&ch, 0, sizeof ch);
+            ch.m = g.m; ch.slot0 = g.base; ch.idx = p.idx; ch.skey = p.skey;
+            ch.keys = c->d_gs_key; ch.rows = c->d_gs_rows; ch.win = c->d_gs_win;
+            ch.proofs = d_proofs; ch.signals = d_signals; ch.sig_stride = 32 * (c->g_n_ic - 1);
+            ch.sig = c->d_lsig; ch.sig_cap = c->lsig_cap; ch.status = c->d_st_all + g.base;
+            enqueue_gset_agg(c, ch, g, p.skey + g.base, (const uint32_t*)c->mx[10], sub, s, M == R && g.base + g.m >= R);
+            HIP_TRY(hipGetLastError());
+        }
+    }
     const int fe = lanes == 2 ? 2 : lanes == 16 ? 16 : 64;
-    for (size_t base = 0; base < M; base += cap) {
+    for (size_t base = R; base < M; base += cap) {
         const size_t m = M - base < cap ? M - base : cap;
         const bool timed = base + cap >= M;
         GsetChunk ch;
@@ -2337,7 +2481,6 @@ ZKV_EXPORT int zkv_ctx_set_lanes_per_proof(zkv_ctx* c, int lanes) {
 // Aggregate check on / off (zkv_agg.h).  seed32 = nullptr draws the 32 secret bytes from the operating system.
 ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t* seed32) {
     if (!c || (enable != 0 && enable != 1 && enable != 16 && enable != 32 && enable != 64 && enable != 128 && enable != 256)) return ZKV_ERR_INVALID_ARG;
-    if (c->vm == ZKV_VM_GROTH16_SET) return ZKV_OK;     // a key set runs the per-proof path (as a long key does): nothing to switch
     uint8_t seed[32];
     if (enable) {
         if (seed32) memcpy(seed, seed32, 32);
@@ -2363,7 +2506,8 @@ ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t
         }
         return ZKV_OK;
     }
-    if (c->vm != ZKV_VM_RISC0 && c->vm != ZKV_VM_RISC0_SET && c->vm != ZKV_VM_SP1 && c->vm != ZKV_VM_GROTH16 && c->vm != ZKV_VM_SP1_PLONK)
+    if (c->vm != ZKV_VM_RISC0 && c->vm != ZKV_VM_RISC0_SET && c->vm != ZKV_VM_SP1 && c->vm != ZKV_VM_GROTH16 && c->vm != ZKV_VM_SP1_PLONK &&
+        c->vm != ZKV_VM_GROTH16_SET)
         return enable ? ZKV_ERR_INVALID_ARG : ZKV_OK;
     {
         std::lock_guard<std::mutex> lk(c->mu);

@@ -38,4 +38,34 @@ inline int gset_choose(const uint32_t* cnt, uint32_t n_keys, int lanes, int fixe
     }
 }
 
+// Aggregate check on a key set (zkv_ctx_set_aggregate_check).  Sub-batches must hold proofs of one key, and the
+// aggregate Miller kernel deals a 64-proof block out to its lane pairs, so the unit of the aggregate region is A = max(64, sub) proofs.
+// A capable key k (valid, alpha and beta finite) puts its first floor(cnt[k] / A) * A proofs, in caller order, into the aggregate region
+// [0, R): the keys back to back, no pad slots.  Its other proofs and every proof of a key that cannot take the check go to the per-proof
+// region [R, slots), laid out by gset_choose.
+inline uint32_t gset_agg_unit(uint32_t sub) { return sub > 64u ? sub : 64u; }
+// agg[k]: proofs of key k in the aggregate region, from slot astart[k]; rest[k]: its others, from slot pstart[k] (absolute; pstart[n_keys] =
+// slots).  Returns the per-proof region's Miller mapping (gset_choose with `lanes`, `fixed`); *agg_slots = R.
+inline int gset_agg_choose(const uint32_t* cnt, const uint8_t* capable, uint32_t n_keys, uint32_t sub, int lanes, int fixed, uint32_t* agg,
+                           uint64_t* astart, uint32_t* rest, uint64_t* pstart, uint64_t* agg_slots, uint64_t* slots) {
+    const uint32_t unit = gset_agg_unit(sub);
+    uint64_t r = 0;
+    for (uint32_t k = 0; k < n_keys; k++) {
+        agg[k] = capable[k] ? cnt[k] / unit * unit : 0u;
+        rest[k] = cnt[k] - agg[k];
+        astart[k] = r;
+        r += agg[k];
+    }
+    astart[n_keys] = r;
+    *agg_slots = r;
+    const int l = gset_choose(rest, n_keys, lanes, fixed, pstart, slots);
+    for (uint32_t k = 0; k <= n_keys; k++) pstart[k] += r;
+    *slots += r;
+    return l;
+}
+// The slot of the proof of rank `rank` (in caller order) among key k's proofs
+inline uint64_t gset_agg_slot(uint32_t k, uint32_t rank, const uint32_t* agg, const uint64_t* astart, const uint64_t* pstart) {
+    return rank < agg[k] ? astart[k] + rank : pstart[k] + (rank - agg[k]);
+}
+
 }  // namespace zkv

@@ -152,6 +152,21 @@ void launch_gset_return(size_t n, const uint32_t* pos, const uint8_t* status, ui
 // Miller loops with the key of each wavefront's first slot (k_gset_pair.hip): lanes 2 / 16 / 64 / 128 as zkv_ctx_set_lanes_per_proof
 void launch_gset_miller(int lanes, size_t m, const uint32_t* skey, const GsetKey* keys, const Workspace& ws, uint8_t* status, hipStream_t s);
 int read_gset_wait_faults(unsigned long long* out);     // k_gset_miller_w64d's counterpart of read_wait_faults
+// Aggregate check on a set (k_gset_agg.hip, k_gset_agg_pair.hip; the layout: zkv_gset_layout.h gset_agg_choose).  psl: pseudo-proof slot per sub-batch.
+struct AggTables;
+void launch_gset_setup_agg(uint32_t n_keys, const VkRaw* d_raw, const VkTables* d_tabs, AggTables* d_agg, hipStream_t s);
+// (k_gset_scan of k_gset.hip with d_zero = K + 1 zero starts, so off[] holds ranks; then k_gset_agg_place with the two-region map)
+__global__ void k_gset_scan(GsetPart p, const uint64_t* __restrict__ start);
+void launch_gset_agg_place(const GsetPart& p, const uint64_t* d_zero, const uint64_t* d_map, hipStream_t s);
+void launch_gset_agg_miller(size_t n, uint32_t g, const uint32_t* skey, const GsetKey* keys, const Workspace& ws, uint8_t* status, hipStream_t s);
+void launch_gset_agg_reduce(const GsetChunk& c, uint32_t sub, uint32_t g, const Workspace& ws, const uint32_t* agg, const AggTables* tabs,
+                            const Workspace& ws2, uint8_t* status2, const uint32_t* psl, bool park, hipStream_t s);
+void launch_gset_agg_combine(const GsetChunk& c, size_t n2, uint32_t wide, const AggTables* tabs, const Workspace& ws2, uint8_t* status2, const uint32_t* psl,
+                             hipStream_t s);
+void launch_gset_agg_fprod(size_t n, size_t n2, uint32_t sub, uint32_t g, const Workspace& ws, const uint32_t* agg, const Workspace& ws2, const uint32_t* psl,
+                           hipStream_t s);
+void launch_gset_agg_mark(size_t n, uint32_t sub, uint32_t g, const Workspace& ws, const uint32_t* agg, const uint8_t* status2, const uint32_t* psl,
+                          uint8_t* status, unsigned long long* counters, hipStream_t s);
 
 // SP1 PLONK path (k_plonk.hip, zkv_plonk.h)
 #ifndef ZKV_PLONK_PROOF_BYTES

@@ -154,6 +154,19 @@ class Groth16VerifierSet:
         """Device set-up (every key's tables) and buffers for batches of up to n proofs, ahead of the first batch (optional)."""
         _lib.check(self._L.zkv_ctx_reserve(self._h, n), 'zkv_ctx_reserve')
 
+    def set_aggregate_check(self, enable=True, seed=None, sub_batch=None):
+        """Opt-in aggregate check (include/zkv_groth16_set.h): proofs of capable keys are checked in key-uniform sub-batches of 16 ... 256
+        (None: chosen by the failure rate seen) when a call places at least ZKV_AGG_MIN proofs; the verdicts stay the per-proof ones."""
+        if sub_batch is not None and sub_batch not in (16, 32, 64, 128, 256):
+            raise ValueError('sub_batch must be None, 16, 32, 64, 128 or 256')
+        from .risc0 import _set_aggregate_check
+        _set_aggregate_check(self._L, self._h, enable, seed, sub_batch)
+
+    def aggregate_counters(self):
+        """(sub-batches checked in aggregate, sub-batches that failed and were verified proof by proof)."""
+        from .risc0 import _aggregate_counters
+        return _aggregate_counters(self._L, self._h)
+
     def set_lanes_per_proof(self, lanes):
         """Miller-loop mapping (0 = automatic, 2, 16, 64, 128), kept even where it pads key groups more than 1.25x.  Same results."""
         _lib.check(self._L.zkv_ctx_set_lanes_per_proof(self._h, lanes), 'zkv_ctx_set_lanes_per_proof')

@@ -45,6 +45,19 @@ public:
         if (rc != ZKV_OK) throw std::runtime_error("zkv_groth16_set_verify_batch failed with ZKV error " + std::to_string(rc));
         return std::vector<bool>(out.begin(), out.begin() + n);
     }
+    // Opt-in aggregate check (zkv_ctx_set_aggregate_check): sub_batch 0 = automatic size, 16 ... 256 fixed; seed32 = nullptr draws the secret
+    // from the operating system.  enable = false switches it off.
+    void set_aggregate_check(bool enable, const uint8_t* seed32 = nullptr, int sub_batch = 0) {
+        const int rc = zkv_ctx_set_aggregate_check(ctx_, enable ? (sub_batch ? sub_batch : 1) : 0, seed32);
+        if (rc != ZKV_OK) throw std::invalid_argument("zkv_ctx_set_aggregate_check failed with ZKV error " + std::to_string(rc));
+    }
+    // {sub-batches checked in aggregate, sub-batches that failed and were verified proof by proof}
+    std::vector<uint64_t> aggregate_counters() const {
+        uint64_t v[2] = {0, 0};
+        const int rc = zkv_ctx_aggregate_counters(ctx_, v);
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_ctx_aggregate_counters failed with ZKV error " + std::to_string(rc));
+        return {v[0], v[1]};
+    }
     zkv_ctx* handle() const { return ctx_; }
 
 private:
