@@ -1,0 +1,168 @@
+// SP1 gateway (include/zkv_sp1_gateway.h): every proof of a batch goes to the route -- the SP1 Groth16 verifier or an SP1 PLONK
+// verifier -- whose 4-byte selector begins it, as SP1's on-chain gateway forwards `verify_proof` by the selector.  No reference
+// counterpart (parity unpinned); the routes' own statuses are their contexts' ones.
+//
+// Same shape as the mixed-batch demultiplexer (k_mixed.hip), with up to 8 route columns and ragged proofs:
+//   k_gateway_count   per 256-proof block: proofs per route, not found, short (wave ballots + popcounts)
+//   k_gateway_scan    exclusive scan of every column over the blocks (one workgroup), totals
+//   (the host reads the totals back once and sizes the compact records: route r holds n_r records of 260 or 868 bytes)
+//   k_gateway_place   stable partition: slot of every routed proof; short and not-found proofs are answered in place
+//   k_gateway_gather  one wavefront per proof: first min(len, record) proof bytes, the 32-byte program vkey; the true length and
+//                     the public-values location were written by place
+// The statuses come back through k_mixed_return.  All of it is byte traffic beside the pairing; no scratch, no LDS beyond the counts.
+#include "zkv_internal.h"
+
+namespace zkv {
+
+constexpr int GW_BLOCK = 256;
+
+// route of proof i (0 .. n_routes - 1), GW_COL_NOT_FOUND or GW_COL_SHORT; *sel = the selector read (0 when short).  Byte loads: a
+// ragged blob has no alignment.
+__device__ __forceinline__ int gw_class(const GatewayArgs& a, size_t i, uint32_t* sel) {
+    *sel = 0;
+    const uint64_t s = a.proof_off[i], e = a.proof_off[i + 1];
+    if (e < s || e > a.proof_bytes || e - s < 4) return GW_COL_SHORT;
+    const uint8_t* p = a.proofs + s;
+    const uint32_t v = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+    *sel = v;
+#pragma unroll
+    for (int r = 0; r < GW_MAX_ROUTES; r++)
+        if ((uint32_t)r < a.n_routes && v == a.sel[r]) return r;
+    return GW_COL_NOT_FOUND;
+}
+
+__global__ __launch_bounds__(GW_BLOCK) void k_gateway_count(GatewayArgs a) {
+    __shared__ uint32_t wc[GW_COLS][GW_BLOCK / 64];
+    const size_t i = (size_t)blockIdx.x * GW_BLOCK + threadIdx.x;
+    uint32_t sel;
+    const int c = i < a.n ? gw_class(a, i, &sel) : -1;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < GW_COLS; k++) {
+        const uint64_t m = __ballot(c == k);
+        if (lane == 0) wc[k][wave] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x < GW_COLS) {
+        uint32_t t = 0;
+        for (int w = 0; w < GW_BLOCK / 64; w++) t += wc[threadIdx.x][w];
+        a.cnt[(size_t)blockIdx.x * GW_COLS + threadIdx.x] = t;
+    }
+}
+
+// cnt[b * GW_COLS + k] -> exclusive prefix sums over b in place, per column k; totals[k].  One workgroup.
+__global__ __launch_bounds__(1024) void k_gateway_scan(uint32_t blocks, uint32_t* __restrict__ cnt, uint32_t* __restrict__ totals) {
+    __shared__ uint32_t part[GW_COLS][1024];
+    const uint32_t t = threadIdx.x, per = (blocks + 1023u) / 1024u, lo = t * per, hi = lo + per < blocks ? lo + per : blocks;
+    uint32_t s[GW_COLS];
+#pragma unroll
+    for (int k = 0; k < GW_COLS; k++) s[k] = 0;
+    for (uint32_t b = lo; b < hi; b++) {
+#pragma unroll
+        for (int k = 0; k < GW_COLS; k++) s[k] += cnt[(size_t)b * GW_COLS + k];
+    }
+#pragma unroll
+    for (int k = 0; k < GW_COLS; k++) part[k][t] = s[k];
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {                       // Hillis-Steele inclusive scan of the 1024 partial sums, every column
+        uint32_t v[GW_COLS];
+#pragma unroll
+        for (int k = 0; k < GW_COLS; k++) v[k] = t >= d ? part[k][t - d] : 0;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < GW_COLS; k++) part[k][t] += v[k];
+        __syncthreads();
+    }
+    uint32_t e[GW_COLS];
+#pragma unroll
+    for (int k = 0; k < GW_COLS; k++) e[k] = part[k][t] - s[k];
+    for (uint32_t b = lo; b < hi; b++) {
+#pragma unroll
+        for (int k = 0; k < GW_COLS; k++) { const uint32_t c = cnt[(size_t)b * GW_COLS + k]; cnt[(size_t)b * GW_COLS + k] = e[k]; e[k] += c; }
+    }
+    if (t == 1023) {
+#pragma unroll
+        for (int k = 0; k < GW_COLS; k++) totals[k] = part[k][1023];
+    }
+}
+
+__global__ __launch_bounds__(GW_BLOCK) void k_gateway_place(GatewayArgs a) {
+    __shared__ uint32_t wc[GW_MAX_ROUTES][GW_BLOCK / 64];
+    const size_t i = (size_t)blockIdx.x * GW_BLOCK + threadIdx.x;
+    uint32_t sel = 0;
+    const int c = i < a.n ? gw_class(a, i, &sel) : -1;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    uint64_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < GW_MAX_ROUTES; k++) {
+        const uint64_t m = __ballot(c == k);
+        if (c == k) mine = m;
+        if (lane == 0) wc[k][wave] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (c < 0) return;
+    if (c >= GW_MAX_ROUTES) {                                       // no verifier to ask: answered here, no slot
+        a.pos[i] = GW_NONE;
+        a.status[i] = c == GW_COL_SHORT ? 4 : 8;                    // ZKV_STATUS_INVALID_PROOF_DATA, ZKV_STATUS_ROUTE_NOT_FOUND
+        if (a.recv) {
+            a.recv[4 * i] = (uint8_t)(sel >> 24); a.recv[4 * i + 1] = (uint8_t)(sel >> 16);
+            a.recv[4 * i + 2] = (uint8_t)(sel >> 8); a.recv[4 * i + 3] = (uint8_t)sel;
+        }
+        return;
+    }
+    uint32_t r = (uint32_t)__popcll(mine & below);
+    for (uint32_t w = 0; w < wave; w++) r += wc[c][w];
+    const uint32_t slot = a.start[c] + a.cnt[(size_t)blockIdx.x * GW_COLS + c] + r;
+    a.pos[i] = slot;
+    a.idx[slot] = (uint32_t)i;
+    const uint64_t len = a.proof_off[i + 1] - a.proof_off[i];
+    a.c_len[slot] = len > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)len;
+    a.c_pvoff[slot] = a.pv_off ? a.pv_off[i] : (uint64_t)i * a.pv_stride;
+    a.c_pvlen[slot] = (uint32_t)(a.pv_off ? a.pv_off[i + 1] - a.pv_off[i] : a.pv_stride);
+}
+
+__device__ __forceinline__ uint32_t gw_ld4(const uint8_t* p, uint64_t avail) {      // up to 4 bytes, zero padded, any alignment
+    if (avail >= 4 && !((uintptr_t)p & 3u)) return *(const uint32_t*)p;
+    uint32_t v = 0;
+    for (int k = 0; k < 4; k++) if ((uint64_t)k < avail) v |= (uint32_t)p[k] << (8 * k);
+    return v;
+}
+// One wavefront per proof (four per workgroup): the route's record stride decides how many words the lanes copy (65 or 217).
+__global__ __launch_bounds__(GW_BLOCK) void k_gateway_gather(GatewayArgs a) {
+    const size_t i = (size_t)blockIdx.x * (GW_BLOCK / 64) + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (i >= a.n) return;
+    const uint32_t slot = a.pos[i];
+    if (slot == GW_NONE) return;
+    // route of the slot: the last route starting at or before it (an empty route starts where the next one does)
+    uint32_t r = 0;
+#pragma unroll
+    for (int k = 1; k < GW_MAX_ROUTES; k++) if ((uint32_t)k < a.n_routes && a.start[k] <= slot) r = (uint32_t)k;
+    const uint32_t rec = a.rec[r];
+    uint32_t* dst = (uint32_t*)(a.c_proofs + a.base[r] + (uint64_t)(slot - a.start[r]) * rec);
+    const uint8_t* src = a.proofs + a.proof_off[i];
+    uint64_t len = a.proof_off[i + 1] - a.proof_off[i];
+    if (len > rec) len = rec;
+    for (uint32_t w = lane; w < rec / 4; w += 64) {
+        const uint64_t at = 4ull * w;
+        dst[w] = at < len ? gw_ld4(src + at, len - at) : 0u;
+    }
+    if (lane < 8) ((uint32_t*)a.c_a)[(size_t)slot * 8 + lane] = gw_ld4(a.vkeys + 32 * i + 4 * lane, 4);
+}
+
+void launch_gateway_count(const GatewayArgs& a, hipStream_t s) {
+    if (!a.n) return;
+    const unsigned blocks = (unsigned)((a.n + GW_BLOCK - 1) / GW_BLOCK);
+    hipLaunchKernelGGL(k_gateway_count, dim3(blocks), dim3(GW_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(k_gateway_scan, dim3(1), dim3(1024), 0, s, blocks, a.cnt, a.totals);
+}
+void launch_gateway_place(const GatewayArgs& a, hipStream_t s) {
+    if (!a.n) return;
+    const unsigned blocks = (unsigned)((a.n + GW_BLOCK - 1) / GW_BLOCK);
+    hipLaunchKernelGGL(k_gateway_place, dim3(blocks), dim3(GW_BLOCK), 0, s, a);
+    const size_t per = GW_BLOCK / 64;
+    hipLaunchKernelGGL(k_gateway_gather, dim3((unsigned)((a.n + per - 1) / per)), dim3(GW_BLOCK), 0, s, a);
+}
+
+}  // namespace zkv

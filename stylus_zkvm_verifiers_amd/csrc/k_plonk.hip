@@ -16,11 +16,15 @@ __global__ __launch_bounds__(64) void k_plonk_setup(const PlonkKeyRaw* __restric
 #ifndef ZKV_PLONK_WAVES
 #define ZKV_PLONK_WAVES 4        /* measured on 2^18 proofs: 198 ms at one wave per SIMD, 150 at two, 143 at three, 141 at four */
 #endif
-__global__ __launch_bounds__(ZKV_BLOCK, ZKV_PLONK_WAVES) void k_plonk_prep(PrepArgs a, const PlonkKey* __restrict__ key, Workspace ws) {
+// RECORDS = true: compact records of a device-side front end (the SP1 gateway's demultiplexer, run_records): fixed stride with the
+// true length in a.len, public values as (a.pv_off start, a.pv_len length).  The batch entry points take the RECORDS = false kernel.
+template <bool RECORDS>
+__device__ __forceinline__ void plonk_prep(const PrepArgs& a, const PlonkKey* __restrict__ key, const Workspace& ws) {
     size_t i = (size_t)blockIdx.x * ZKV_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     const uint8_t* rec; size_t len;
-    if (a.off) { rec = a.blob + a.off[i]; len = (size_t)(a.off[i + 1] - a.off[i]); }
+    if (RECORDS) { rec = a.blob + i * (size_t)a.stride; len = a.len[i]; }
+    else if (a.off) { rec = a.blob + a.off[i]; len = (size_t)(a.off[i + 1] - a.off[i]); }
     else { rec = a.blob + i * (size_t)a.stride; len = a.stride; }
     uint8_t st = ST_VERIFICATION_FAILED;
     uint32_t rv = 0, flags = 0;
@@ -42,7 +46,8 @@ __global__ __launch_bounds__(ZKV_BLOCK, ZKV_PLONK_WAVES) void k_plonk_prep(PrepA
         for (int k = 0; k < 27; k++) load_be256(w[k], rec + 4 + 32 * k);
         load_be256(pub[0], a.in32_a + 32 * i);                                      // U256::from_be_bytes(program_vkey), sp1/types.rs:24
         const uint8_t* pv; size_t pvl;
-        if (a.pv_off) { pv = a.pv_blob + a.pv_off[i]; pvl = (size_t)(a.pv_off[i + 1] - a.pv_off[i]); }
+        if (RECORDS) { pv = a.pv_blob + a.pv_off[i]; pvl = a.pv_len[i]; }
+        else if (a.pv_off) { pv = a.pv_blob + a.pv_off[i]; pvl = (size_t)(a.pv_off[i + 1] - a.pv_off[i]); }
         else { pv = a.pv_blob + i * (size_t)a.pv_stride; pvl = a.pv_stride; }
         uint32_t h[8];
         sha256_bytes(pv, pvl, h);
@@ -68,6 +73,12 @@ __global__ __launch_bounds__(ZKV_BLOCK, ZKV_PLONK_WAVES) void k_plonk_prep(PrepA
     ws.g2bad[i] = 0;
     a.status[i] = st;
 }
+__global__ __launch_bounds__(ZKV_BLOCK, ZKV_PLONK_WAVES) void k_plonk_prep(PrepArgs a, const PlonkKey* __restrict__ key, Workspace ws) {
+    plonk_prep<false>(a, key, ws);
+}
+__global__ __launch_bounds__(ZKV_BLOCK, ZKV_PLONK_WAVES) void k_plonk_prep_rec(PrepArgs a, const PlonkKey* __restrict__ key, Workspace ws) {
+    plonk_prep<true>(a, key, ws);
+}
 
 // the multiples of one point per block (one lane works: the levels of the row are sequential), then one lane per row (point, a) of the
 // joint P / phi(P) tables
@@ -85,7 +96,9 @@ void launch_plonk_setup(const PlonkKeyRaw* d_raw, PlonkKey* d_key, hipStream_t s
 }
 void launch_plonk_prep(const PrepArgs& a, const PlonkKey* d_key, const Workspace& ws, hipStream_t s) {
     if (!a.n) return;
-    hipLaunchKernelGGL(k_plonk_prep, dim3((unsigned)((a.n + ZKV_BLOCK - 1) / ZKV_BLOCK)), dim3(ZKV_BLOCK), 0, s, a, d_key, ws);
+    const dim3 grid((unsigned)((a.n + ZKV_BLOCK - 1) / ZKV_BLOCK));
+    if (a.len) hipLaunchKernelGGL(k_plonk_prep_rec, grid, dim3(ZKV_BLOCK), 0, s, a, d_key, ws);
+    else hipLaunchKernelGGL(k_plonk_prep, grid, dim3(ZKV_BLOCK), 0, s, a, d_key, ws);
 }
 
 }  // namespace zkv

@@ -18,6 +18,7 @@
 
 #include "../../include/zkv.h"
 #include "../../include/zkv_groth16_set.h"
+#include "../../include/zkv_sp1_gateway.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
@@ -153,6 +154,12 @@ struct zkv_ctx {
     bool kid_ran[2] = {false, false};        // which sub-batch of the most recent mixed call was non-empty (zkv_ctx_last_stage_ms)
     uint8_t* mx[22] = {nullptr};
     size_t mx_cap[22] = {0};
+    // ZKV_VM_SP1_GATEWAY (zkv_sp1_gateway.h): the routes' contexts and selectors; which routes ran in the most recent call
+    // (zkv_ctx_last_stage_ms) and its per-column proof counts (routes, not found, short)
+    std::vector<zkv_ctx*> gw_route;
+    std::vector<uint32_t> gw_sel;
+    std::vector<uint8_t> gw_ran;
+    uint64_t gw_counts[GW_COLS] = {0};
     std::mutex mu;
 };
 
@@ -315,7 +322,7 @@ static int ctx_device_setup(zkv_ctx* c) {
         HIP_TRY(hipEventCreateWithFlags(&c->ev_decoded[b], hipEventDisableTiming));
     }
     if (c->vm == ZKV_VM_GROTH16_SET) return gset_device_setup(c);
-    if (c->vm != ZKV_VM_BN254 && c->vm != ZKV_VM_MIXED) {
+    if (c->vm != ZKV_VM_BN254 && c->vm != ZKV_VM_MIXED && c->vm != ZKV_VM_SP1_GATEWAY) {
         VkRaw raw;
         if (c->vm == ZKV_VM_RISC0 || c->vm == ZKV_VM_RISC0_SET) host::fill_vk_risc0(raw, c->control_root_0, c->control_root_1, c->control_id);
         else if (c->vm == ZKV_VM_GROTH16) host::fill_vk_generic(raw, c->gvk.data(), c->long_key ? 1u : c->g_n_ic);   // long key: IC[0] only here
@@ -789,6 +796,7 @@ static bool offsets_ok(const uint64_t* off, size_t n) {
     return true;
 }
 static uint32_t be32_of(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+static void be32_put(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
 
 // Host-pointer batch driver shared by risc0 verify / verify_integrity / sp1 verify_proof.
 //
@@ -925,9 +933,10 @@ static int run_dev_batch(zkv_ctx* c, size_t n, const uint8_t* d_blob, const uint
     return n ? mark_done(c, s) : ZKV_OK;
 }
 
-// Stage pipeline over m compact records that a device-side front end produced (fixed 260-byte stride plus the true length,
-// 32-byte inputs, public values as (start, length) into one blob): the output format of the calldata decoder and of the
-// mixed-batch demultiplexer.  `kind` (RISC Zero, may be null): per-proof method, 1 = verify_integrity.  Asynchronous on `s`.
+// Stage pipeline over m compact records that a device-side front end produced (fixed stride plus the true length, 32-byte inputs,
+// public values as (start, length) into one blob): the output format of the calldata decoder, of the mixed-batch demultiplexer and of
+// the SP1 gateway.  The stride is 260 bytes, 868 for an SP1 PLONK context.  `kind` (RISC Zero, may be null): per-proof method,
+// 1 = verify_integrity.  Asynchronous on `s`.
 static int run_records(zkv_ctx* c, size_t m_total, const uint8_t* seals, const uint32_t* len, const uint8_t* in_a, const uint8_t* in_b,
                        const uint8_t* kind, const uint8_t* pv_blob, const uint64_t* pv_start, const uint32_t* pv_len, uint8_t* st, uint8_t* rv, hipStream_t s) {
     if (!m_total) return ZKV_OK;
@@ -936,15 +945,20 @@ static int run_records(zkv_ctx* c, size_t m_total, const uint8_t* seals, const u
     if (rc != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     const size_t cap = c->ws.cap;
+    const size_t rec = c->vm == ZKV_VM_SP1_PLONK ? (size_t)ZKV_PLONK_PROOF_BYTES : (size_t)ZKV_SEAL_BYTES;
     for (size_t base = 0; base < m_total; base += cap) {
         const size_t m = m_total - base < cap ? m_total - base : cap;
         PrepArgs a;
         memset(&a, 0, sizeof a);
-        a.n = m; a.blob = seals + base * ZKV_SEAL_BYTES; a.stride = ZKV_SEAL_BYTES; a.len = len + base;
+        a.n = m; a.blob = seals + base * rec; a.stride = (uint32_t)rec; a.len = len + base;
         a.in32_a = in_a + 32 * base;
         if (c->vm == ZKV_VM_SP1) {
             a.pv_blob = pv_blob; a.pv_off = pv_start + base; a.pv_len = pv_len + base;
             a.selector_be = be32_of(host::SP1_VERIFIER_HASH);
+        } else if (c->vm == ZKV_VM_SP1_PLONK) {
+            a.pv_blob = pv_blob; a.pv_off = pv_start + base; a.pv_len = pv_len + base;
+            a.selector_be = be32_of(c->plonk_hash);
+            a.force_fail = c->vk_invalid ? 1u : 0u;
         } else {
             a.in32_b = in_b + 32 * base; a.kind = kind ? kind + base : nullptr;
             a.selector_be = be32_of(c->selector);
@@ -1330,6 +1344,8 @@ ZKV_EXPORT void zkv_ctx_destroy(zkv_ctx* c) {
     if (!c) return;
     if (is_sharded(c)) shards_free(c);
     for (auto& k : c->kid) { if (k) zkv_ctx_destroy(k); k = nullptr; }
+    for (auto* k : c->gw_route) zkv_ctx_destroy(k);
+    c->gw_route.clear();
     ctx_free_device(c);
     delete c;
 }
@@ -1625,6 +1641,197 @@ ZKV_EXPORT int zkv_sp1_plonk_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_
             return zkv_sp1_plonk_verify_batch_dev(k, m, r[0], r[1], pv_len, r[2], st, rv, s); });
     }
     return run_dev_batch(c, n, d_proofs, d_vkeys, nullptr, d_pv, pv_len, d_status, d_recv, stream);
+}
+
+// ------------------------------------------------------------------ SP1 gateway (zkv_sp1_gateway.h; no reference counterpart: parity unpinned)
+// Up to ZKV_SP1_GATEWAY_MAX_ROUTES SP1 verifiers behind one context; every proof goes to the route whose selector begins it.  The routes
+// are ordinary SP1 / SP1 PLONK contexts owned by the gateway: the device front end (k_gateway.hip) sorts a batch into their compact
+// records, each non-empty route runs its own stage pipeline on them (run_records), and the statuses go back to the caller's order.
+ZKV_EXPORT zkv_ctx* zkv_sp1_gateway_create(int groth16, size_t n_plonk, const uint8_t* const* plonk_vk, const size_t* plonk_vk_len,
+                                           const uint8_t* plonk_verifier_hash, int device) {
+    if ((groth16 != 0 && groth16 != 1) || n_plonk > ZKV_SP1_GATEWAY_MAX_ROUTES || groth16 + n_plonk == 0 ||
+        groth16 + n_plonk > ZKV_SP1_GATEWAY_MAX_ROUTES) return nullptr;
+    if (n_plonk && (!plonk_vk || !plonk_vk_len || !plonk_verifier_hash)) return nullptr;
+    std::vector<uint32_t> sel;
+    if (groth16) sel.push_back(be32_of(host::SP1_VERIFIER_HASH));
+    for (size_t k = 0; k < n_plonk; k++) {
+        if (!plonk_vk[k]) return nullptr;
+        sel.push_back(be32_of(plonk_verifier_hash + 32 * k));
+    }
+    for (size_t k = 0; k < sel.size(); k++)
+        for (size_t j = 0; j < k; j++) if (sel[j] == sel[k]) return nullptr;       // the gateway could not tell the two routes apart
+    zkv_ctx* c = new (std::nothrow) zkv_ctx();
+    if (!c) return nullptr;
+    c->vm = ZKV_VM_SP1_GATEWAY; c->device = device; c->initialized = true;
+    memset(&c->consts, 0, sizeof c->consts);
+    c->gw_sel = sel;
+    if (groth16) {
+        zkv_ctx* r = zkv_sp1_ctx_create(device);
+        if (!r) { zkv_ctx_destroy(c); return nullptr; }
+        c->gw_route.push_back(r);
+    }
+    for (size_t k = 0; k < n_plonk; k++) {
+        zkv_ctx* r = zkv_sp1_plonk_ctx_create(plonk_vk[k], plonk_vk_len[k], plonk_verifier_hash + 32 * k, device);
+        if (!r) { zkv_ctx_destroy(c); return nullptr; }
+        c->gw_route.push_back(r);
+    }
+    c->gw_ran.assign(c->gw_route.size(), 0);
+    return c;
+}
+ZKV_EXPORT size_t zkv_sp1_gateway_route_count(const zkv_ctx* c) { return c && c->vm == ZKV_VM_SP1_GATEWAY ? c->gw_route.size() : 0; }
+ZKV_EXPORT int zkv_sp1_gateway_route(const zkv_ctx* c, size_t r, uint8_t selector[4], int* vm) {
+    if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
+    if (r >= c->gw_route.size()) return ZKV_ERR_INVALID_ARG;
+    if (selector) be32_put(selector, c->gw_sel[r]);
+    if (vm) *vm = c->gw_route[r]->vm;
+    return ZKV_OK;
+}
+ZKV_EXPORT zkv_ctx* zkv_sp1_gateway_route_ctx(zkv_ctx* c, size_t r) {
+    return c && c->vm == ZKV_VM_SP1_GATEWAY && r < c->gw_route.size() ? c->gw_route[r] : nullptr;
+}
+// route of a proof of `len` bytes starting with p: 0 .. R - 1, GW_COL_NOT_FOUND or GW_COL_SHORT (the kernels' gw_class on the host)
+static int gateway_route_of(const zkv_ctx* c, const uint8_t* p, size_t len) {
+    if (len < 4) return GW_COL_SHORT;
+    const uint32_t sel = be32_of(p);
+    for (size_t k = 0; k < c->gw_sel.size(); k++) if (c->gw_sel[k] == sel) return (int)k;
+    return GW_COL_NOT_FOUND;
+}
+ZKV_EXPORT int zkv_sp1_gateway_verify_proof(zkv_ctx* c, const uint8_t vkey[32], const uint8_t* pv, size_t pv_len, const uint8_t* proof, size_t proof_len,
+                                            uint8_t* status, uint8_t recv[4]) {
+    if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
+    if (!vkey || !status || (!pv && pv_len) || (!proof && proof_len)) return ZKV_ERR_INVALID_ARG;
+    const int col = gateway_route_of(c, proof, proof_len);
+    uint8_t rv[4] = {0, 0, 0, 0};
+    if (col < GW_MAX_ROUTES) {
+        zkv_ctx* k = c->gw_route[col];
+        const int rc = k->vm == ZKV_VM_SP1 ? zkv_sp1_verify_proof(k, vkey, pv, pv_len, proof, proof_len, status, rv)
+                                           : zkv_sp1_plonk_verify_proof(k, vkey, pv, pv_len, proof, proof_len, status, rv);
+        if (rc != ZKV_OK) return rc;
+    } else if (col == GW_COL_NOT_FOUND) {
+        *status = ZKV_STATUS_ROUTE_NOT_FOUND;
+        memcpy(rv, proof, 4);
+    } else *status = ZKV_STATUS_INVALID_PROOF_DATA;                // sp1/verifier.rs:64
+    if (recv) memcpy(recv, rv, 4);
+    std::lock_guard<std::mutex> lk(c->mu);
+    for (auto& v : c->gw_counts) v = 0;
+    c->gw_counts[col] = 1;
+    for (size_t k = 0; k < c->gw_ran.size(); k++) c->gw_ran[k] = (int)k == col;
+    return ZKV_OK;
+}
+
+enum { GW_CNT = 0, GW_TOT, GW_POS, GW_IDX, GW_RECS, GW_LEN, GW_A, GW_PVOFF, GW_PVLEN, GW_ST, GW_RV,
+       GW_H_VK, GW_H_PV, GW_H_PVOFF, GW_H_PROOF, GW_H_POFF, GW_H_ST, GW_H_RV };
+// Everything device-resident: ragged proofs (offsets bounded by proof_bytes on the device); public values ragged (d_pv_off) or at a
+// fixed stride.  Synchronises `s` once, after the count, to size the compact records and learn the routes' sub-batch sizes.
+static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8_t* d_proofs, const uint64_t* d_proof_off, uint64_t proof_bytes,
+                       const uint8_t* d_pv, const uint64_t* d_pv_off, uint64_t pv_stride, uint8_t* d_status, uint8_t* d_recv, hipStream_t s) {
+    int rc;
+    const size_t blocks = (n + 255) / 256, R = c->gw_route.size();
+    const size_t need[11] = {4 * GW_COLS * blocks, 4 * GW_COLS, 4 * n, 4 * n, 0, 4 * n, 32 * n, 8 * n, 4 * n, n, 4 * n};
+    for (int k = 0; k < 11; k++) if (k != GW_RECS && (rc = grow(&c->mx[k], &c->mx_cap[k], need[k])) != ZKV_OK) return rc;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    GatewayArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = n; a.proofs = d_proofs; a.proof_off = d_proof_off; a.proof_bytes = proof_bytes; a.vkeys = d_vkeys; a.pv_off = d_pv_off; a.pv_stride = pv_stride;
+    a.n_routes = (uint32_t)R;
+    for (size_t r = 0; r < R; r++) {
+        a.sel[r] = c->gw_sel[r];
+        a.rec[r] = c->gw_route[r]->vm == ZKV_VM_SP1_PLONK ? ZKV_PLONK_PROOF_BYTES : ZKV_SEAL_BYTES;
+    }
+    a.cnt = (uint32_t*)c->mx[GW_CNT]; a.totals = (uint32_t*)c->mx[GW_TOT]; a.pos = (uint32_t*)c->mx[GW_POS]; a.idx = (uint32_t*)c->mx[GW_IDX];
+    a.c_len = (uint32_t*)c->mx[GW_LEN]; a.c_a = c->mx[GW_A]; a.c_pvoff = (uint64_t*)c->mx[GW_PVOFF]; a.c_pvlen = (uint32_t*)c->mx[GW_PVLEN];
+    a.status = d_status; a.recv = d_recv;
+    launch_gateway_count(a, s);
+    HIP_TRY(hipGetLastError());
+    uint32_t tot[GW_COLS];
+    HIP_TRY(hipMemcpyAsync(tot, c->mx[GW_TOT], sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    size_t routed = 0;
+    uint64_t bytes = 0;
+    for (size_t r = 0; r < R; r++) { a.start[r] = (uint32_t)routed; a.base[r] = bytes; routed += tot[r]; bytes += (uint64_t)tot[r] * a.rec[r]; }
+    if (routed + tot[GW_COL_NOT_FOUND] + tot[GW_COL_SHORT] != n) return ZKV_ERR_HIP;
+    if ((rc = grow(&c->mx[GW_RECS], &c->mx_cap[GW_RECS], (size_t)bytes + 8)) != ZKV_OK) return rc;
+    a.c_proofs = c->mx[GW_RECS];
+    for (size_t r = 0; r < R; r++) { c->gw_counts[r] = tot[r]; c->gw_ran[r] = tot[r] > 0; }
+    for (size_t r = R; r < GW_MAX_ROUTES; r++) c->gw_counts[r] = 0;
+    c->gw_counts[GW_COL_NOT_FOUND] = tot[GW_COL_NOT_FOUND]; c->gw_counts[GW_COL_SHORT] = tot[GW_COL_SHORT];
+    launch_gateway_place(a, s);
+    HIP_TRY(hipGetLastError());
+    uint8_t *st = c->mx[GW_ST], *rv = c->mx[GW_RV];
+    for (size_t r = 0; r < R; r++) {
+        const size_t j = a.start[r];
+        if ((rc = run_records(c->gw_route[r], tot[r], a.c_proofs + a.base[r], a.c_len + j, a.c_a + 32 * j, nullptr, nullptr, d_pv, a.c_pvoff + j,
+                              a.c_pvlen + j, st + j, rv + 4 * j, s)) != ZKV_OK) return rc;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    launch_mixed_return(routed, a.idx, st, rv, d_status, d_recv, s);
+    HIP_TRY(hipGetLastError());
+    return mark_done(c, s);
+}
+ZKV_EXPORT int zkv_sp1_gateway_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8_t* d_pv, size_t pv_len,
+                                                const uint8_t* d_proofs, const uint64_t* d_proof_off, uint64_t proof_bytes,
+                                                uint8_t* d_status, uint8_t* d_recv, void* stream) {
+    if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_vkeys || !d_pv || !d_proofs || !d_proof_off || !d_status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u || pv_len > 0xFFFFFFFFu) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    return run_gateway(c, n, d_vkeys, d_proofs, d_proof_off, proof_bytes, d_pv, nullptr, pv_len, d_status, d_recv, stream ? (hipStream_t)stream : c->stream);
+}
+ZKV_EXPORT int zkv_sp1_gateway_verify_batch(zkv_ctx* c, size_t n, const uint8_t* vkeys, const uint8_t* pv_blob, const uint64_t* pv_off,
+                                            const uint8_t* proof_blob, const uint64_t* proof_off, uint8_t* status, uint8_t* recv) {
+    if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
+    if (n && (!vkeys || !pv_blob || !pv_off || !proof_blob || !proof_off || !status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u || !offsets_ok(proof_off, n) || !offsets_ok(pv_off, n)) return ZKV_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n; i++) if (pv_off[i + 1] - pv_off[i] > 0xFFFFFFFFu) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    const uint64_t s0 = proof_off[0], sbytes = proof_off[n] - s0, v0 = pv_off[0], vbytes = pv_off[n] - v0;
+    const size_t need[7] = {32 * n, (size_t)vbytes + 8, 8 * (n + 1), (size_t)sbytes + 8, 8 * (n + 1), n, 4 * n};
+    for (int k = 0; k < 7; k++) if ((rc = grow(&c->mx[GW_H_VK + k], &c->mx_cap[GW_H_VK + k], need[k])) != ZKV_OK) return rc;
+    hipStream_t s = c->stream;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    std::vector<uint64_t> so(proof_off, proof_off + n + 1), vo(pv_off, pv_off + n + 1);
+    for (auto& v : so) v -= s0;
+    for (auto& v : vo) v -= v0;
+    HIP_TRY(hipMemcpyAsync(c->mx[GW_H_VK], vkeys, 32 * n, hipMemcpyHostToDevice, s));
+    if (vbytes) HIP_TRY(hipMemcpyAsync(c->mx[GW_H_PV], pv_blob + v0, (size_t)vbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->mx[GW_H_PVOFF], vo.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+    if (sbytes) HIP_TRY(hipMemcpyAsync(c->mx[GW_H_PROOF], proof_blob + s0, (size_t)sbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->mx[GW_H_POFF], so.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+    if ((rc = run_gateway(c, n, c->mx[GW_H_VK], c->mx[GW_H_PROOF], (const uint64_t*)c->mx[GW_H_POFF], sbytes, c->mx[GW_H_PV],
+                          (const uint64_t*)c->mx[GW_H_PVOFF], 0, c->mx[GW_H_ST], c->mx[GW_H_RV], s)) != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(status, c->mx[GW_H_ST], n, hipMemcpyDeviceToHost, s));
+    if (recv) HIP_TRY(hipMemcpyAsync(recv, c->mx[GW_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_sp1_gateway_last_route_counts(zkv_ctx* c, uint64_t* out) {
+    if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const size_t R = c->gw_route.size();
+    for (size_t r = 0; r < R; r++) out[r] = c->gw_counts[r];
+    out[R] = c->gw_counts[GW_COL_NOT_FOUND]; out[R + 1] = c->gw_counts[GW_COL_SHORT];
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_sp1_gateway_status_abi_encode(const zkv_ctx* c, uint8_t status, const uint8_t received[4], uint8_t out[68]) {
+    if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    if (status == ZKV_STATUS_ROUTE_NOT_FOUND) {                 // RouteNotFound(bytes4): selector, then the bytes4 left-aligned in a word
+        if (!received) return ZKV_ERR_INVALID_ARG;
+        memset(out, 0, 36);
+        host::fn_selector("RouteNotFound(bytes4)", out);
+        memcpy(out + 4, received, 4);
+        return 36;
+    }
+    uint8_t expected[4];
+    be32_put(expected, c->gw_sel[0]);
+    return zkv_status_abi_encode(ZKV_VM_SP1, status, received, expected, out);
 }
 
 // ------------------------------------------------------------------ on-chain wire layer (eth_call batches)
@@ -2394,7 +2601,8 @@ ZKV_EXPORT int zkv_groth16_set_vk_x_batch(zkv_ctx* c, size_t n, const uint32_t* 
 // ------------------------------------------------------------------ Groth16 core pieces
 ZKV_EXPORT int zkv_ctx_vk_x_batch(zkv_ctx* c, size_t n, const uint8_t* var_signals, uint8_t* out) {
     if (is_sharded(c)) c = c->shards[0];
-    if (!c || c->vm == ZKV_VM_BN254 || c->vm == ZKV_VM_RISC0_SET || c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_PLONK || c->vm == ZKV_VM_GROTH16_SET)
+    if (!c || c->vm == ZKV_VM_BN254 || c->vm == ZKV_VM_RISC0_SET || c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_PLONK || c->vm == ZKV_VM_GROTH16_SET ||
+        c->vm == ZKV_VM_SP1_GATEWAY)
         return ZKV_ERR_WRONG_CTX;
     if (c->vm == ZKV_VM_RISC0 && !c->initialized) return ZKV_ERR_INVALID_ARG;
     if (n && (!var_signals || !out)) return ZKV_ERR_INVALID_ARG;
@@ -2474,6 +2682,7 @@ ZKV_EXPORT int zkv_ctx_set_lanes_per_proof(zkv_ctx* c, int lanes) {
     if (c->vm == ZKV_VM_MIXED) {                         // the two verifiers behind the tag run the stages
         for (auto* k : c->kid) { const int rc = zkv_ctx_set_lanes_per_proof(k, lanes); if (rc != ZKV_OK) return rc; }
     }
+    for (auto* k : c->gw_route) { const int rc = zkv_ctx_set_lanes_per_proof(k, lanes); if (rc != ZKV_OK) return rc; }
     std::lock_guard<std::mutex> lk(c->mu);
     c->lanes = lanes;
     return ZKV_OK;
@@ -2496,11 +2705,12 @@ ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t
         }
         return ZKV_OK;
     }
-    if (c->vm == ZKV_VM_MIXED) {
-        for (int k = 0; k < 2; k++) {
+    if (c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_GATEWAY) {
+        const size_t nk = c->vm == ZKV_VM_MIXED ? 2 : c->gw_route.size();
+        for (size_t k = 0; k < nk; k++) {
             uint8_t sk[32];
             if (enable && seed32) { uint8_t buf[33]; memcpy(buf, seed, 32); buf[32] = (uint8_t)k; host::sha256_host(buf, 33, sk); }
-            const int rc = zkv_ctx_set_aggregate_check(c->kid[k], enable, enable && seed32 ? sk : nullptr);
+            const int rc = zkv_ctx_set_aggregate_check(c->vm == ZKV_VM_MIXED ? c->kid[k] : c->gw_route[k], enable, enable && seed32 ? sk : nullptr);
             { volatile uint8_t* w = sk; for (int i = 0; i < 32; i++) w[i] = 0; }
             if (rc != ZKV_OK) return rc;
         }
@@ -2530,11 +2740,11 @@ ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t
 ZKV_EXPORT int zkv_ctx_aggregate_counters(zkv_ctx* c, uint64_t out[2]) {
     if (!c || !out) return ZKV_ERR_INVALID_ARG;
     out[0] = out[1] = 0;
-    if (is_sharded(c) || c->vm == ZKV_VM_MIXED) {
-        const size_t nk = is_sharded(c) ? c->shards.size() : 2;
+    if (is_sharded(c) || c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_GATEWAY) {
+        const size_t nk = is_sharded(c) ? c->shards.size() : c->vm == ZKV_VM_MIXED ? 2 : c->gw_route.size();
         for (size_t k = 0; k < nk; k++) {
             uint64_t o[2];
-            const int rc = zkv_ctx_aggregate_counters(is_sharded(c) ? c->shards[k] : c->kid[k], o);
+            const int rc = zkv_ctx_aggregate_counters(is_sharded(c) ? c->shards[k] : c->vm == ZKV_VM_MIXED ? c->kid[k] : c->gw_route[k], o);
             if (rc != ZKV_OK) return rc;
             out[0] += o[0]; out[1] += o[1];
         }
@@ -2591,6 +2801,11 @@ ZKV_EXPORT int zkv_ctx_reserve(zkv_ctx* c, size_t n) {
         std::lock_guard<std::mutex> lk(c->mu);
         return ctx_device_init(c);
     }
+    if (c->vm == ZKV_VM_SP1_GATEWAY) {                   // any route may own the whole batch
+        for (auto* k : c->gw_route) { const int rc = zkv_ctx_reserve(k, n); if (rc != ZKV_OK) return rc; }
+        std::lock_guard<std::mutex> lk(c->mu);
+        return ctx_device_init(c);
+    }
     std::lock_guard<std::mutex> lk(c->mu);
     size_t chunk;
     return c->vm == ZKV_VM_GROTH16 || c->vm == ZKV_VM_GROTH16_SET ? groth16_ready(c, n, &chunk) : ctx_ready(c, n);
@@ -2606,7 +2821,8 @@ ZKV_EXPORT int zkv_ctx_synchronize(zkv_ctx* c) {
         return ZKV_OK;
     }
     // a mixed context has work in flight as soon as ANY of its three contexts is set up (an all-SP1 batch never touches the RISC Zero child)
-    const bool any = c->dev_ready || (c->vm == ZKV_VM_MIXED && ((c->kid[0] && c->kid[0]->dev_ready) || (c->kid[1] && c->kid[1]->dev_ready)));
+    bool any = c->dev_ready || (c->vm == ZKV_VM_MIXED && ((c->kid[0] && c->kid[0]->dev_ready) || (c->kid[1] && c->kid[1]->dev_ready)));
+    for (auto* k : c->gw_route) any = any || k->dev_ready;
     if (!any) return ZKV_OK;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -2627,6 +2843,19 @@ ZKV_EXPORT int zkv_ctx_last_stage_ms(zkv_ctx* c, float out_ms[5]) {
             for (int i = 0; i < 5; i++) out_ms[i] += a[i];
         }
         return ZKV_OK;
+    }
+    if (c->vm == ZKV_VM_SP1_GATEWAY) {                   // routes run one after the other, as the mixed context's children
+        bool ran = false;
+        for (int i = 0; i < 5; i++) out_ms[i] = 0.0f;
+        for (size_t k = 0; k < c->gw_route.size(); k++) {
+            if (!c->gw_ran[k]) continue;
+            float a[5];
+            const int rc = zkv_ctx_last_stage_ms(c->gw_route[k], a);
+            if (rc != ZKV_OK) return rc;
+            for (int i = 0; i < 5; i++) out_ms[i] += a[i];
+            ran = true;
+        }
+        return ran ? ZKV_OK : ZKV_ERR_NO_DEVICE;
     }
     if (!c->dev_ready) return ZKV_ERR_NO_DEVICE;
     HIP_TRY(hipSetDevice(c->device));

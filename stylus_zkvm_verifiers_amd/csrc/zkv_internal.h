@@ -118,6 +118,27 @@ struct MixedArgs {
 void launch_mixed_partition(const MixedArgs& a, uint32_t* cnt, uint32_t* totals, hipStream_t s);
 void launch_mixed_return(size_t m, const uint32_t* idx, const uint8_t* c_status, const uint8_t* c_recv, uint8_t* status, uint8_t* recv, hipStream_t s);
 
+// SP1 gateway (k_gateway.hip, include/zkv_sp1_gateway.h): every proof goes to the route whose selector begins it.  Count columns:
+// routes 0 .. GW_MAX_ROUTES - 1, then GW_COL_NOT_FOUND and GW_COL_SHORT (shorter than 4 bytes, or offsets outside the blob).
+constexpr int GW_MAX_ROUTES = 8, GW_COL_NOT_FOUND = 8, GW_COL_SHORT = 9, GW_COLS = 10;
+constexpr uint32_t GW_NONE = 0xFFFFFFFFu;
+struct GatewayArgs {
+    size_t n;
+    const uint8_t* proofs; const uint64_t* proof_off; uint64_t proof_bytes;    // ragged proofs; proof_bytes bounds every read
+    const uint8_t* vkeys;                                                      // n x 32
+    const uint64_t* pv_off; uint64_t pv_stride;                                // public values: n + 1 offsets (ragged) or a fixed stride
+    uint32_t n_routes;
+    uint32_t sel[GW_MAX_ROUTES];                                               // route selectors, big-endian words (kernel arguments: SGPRs)
+    uint32_t rec[GW_MAX_ROUTES];                                               // record bytes per route: ZKV_SEAL_BYTES or ZKV_PLONK_PROOF_BYTES
+    uint32_t start[GW_MAX_ROUTES]; uint64_t base[GW_MAX_ROUTES];               // (place, gather) first slot and record byte offset of each route
+    uint32_t* cnt; uint32_t* totals;                                           // GW_COLS per block (exclusive scan in place), GW_COLS totals
+    uint32_t* pos; uint32_t* idx;                                              // pos[i] = slot (GW_NONE: answered in place); idx[slot] = i
+    uint8_t* c_proofs; uint32_t* c_len; uint8_t* c_a; uint64_t* c_pvoff; uint32_t* c_pvlen;    // compact records
+    uint8_t* status; uint8_t* recv;                                            // caller's outputs (short / not-found proofs answered here)
+};
+void launch_gateway_count(const GatewayArgs& a, hipStream_t s);     // count + scan: totals[GW_COLS]
+void launch_gateway_place(const GatewayArgs& a, hipStream_t s);     // place + gather (start[] / base[] filled from the totals)
+
 // Groth16 key sets (k_gset.hip, k_gset_pair.hip; zkv_gset_layout.h): per-key device record.  tab: the key's VkTables (alpha, beta, gamma,
 // delta, IC[0]); its IC[1..] window rows are rows [sig0, sig0 + n_sig) of the set's one row allocation (LongKey layout), and win[sig0 ..]
 // their window counts.

@@ -1,0 +1,67 @@
+// C++ host wrapper of the SP1 gateway (include/zkv_sp1_gateway.h): `ISp1Verifier::verify_proof` with the verifier chosen per proof by
+// the first 4 bytes of `proof_bytes`, as SP1's on-chain gateway does.  Library/runtime failures throw std::runtime_error; statuses
+// (ZKV_STATUS_*, ZKV_STATUS_ROUTE_NOT_FOUND) are never exceptions.  Parity unpinned: the reference holds no gateway and no PLONK code.
+#pragma once
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/zkv_sp1_gateway.h"
+
+namespace zkv {
+
+struct Sp1PlonkRoute {
+    std::vector<uint8_t> vk;              // zkv_sp1_plonk_ctx_create's layout
+    std::vector<uint8_t> verifier_hash;   // 32 bytes; its first four are the route's selector
+};
+
+class Sp1Gateway {
+public:
+    Sp1Gateway(bool groth16, const std::vector<Sp1PlonkRoute>& plonk, int device = 0) {
+        std::vector<const uint8_t*> vk; std::vector<size_t> len; std::vector<uint8_t> hashes;
+        for (const auto& r : plonk) {
+            if (r.verifier_hash.size() != 32) throw std::invalid_argument("Sp1Gateway: verifier_hash must be 32 bytes");
+            vk.push_back(r.vk.data()); len.push_back(r.vk.size()); hashes.insert(hashes.end(), r.verifier_hash.begin(), r.verifier_hash.end());
+        }
+        ctx_ = zkv_sp1_gateway_create(groth16 ? 1 : 0, plonk.size(), vk.data(), len.data(), hashes.data(), device);
+        if (!ctx_) throw std::invalid_argument("zkv_sp1_gateway_create rejected the routes");
+    }
+    Sp1Gateway(Sp1Gateway&& o) noexcept : ctx_(o.ctx_) { o.ctx_ = nullptr; }
+    Sp1Gateway(const Sp1Gateway&) = delete;
+    Sp1Gateway& operator=(const Sp1Gateway&) = delete;
+    ~Sp1Gateway() { if (ctx_) zkv_ctx_destroy(ctx_); }
+
+    size_t route_count() const { return zkv_sp1_gateway_route_count(ctx_); }
+
+    // status[i] / recv[4 i .. 4 i + 4) of proof i (ragged host buffers, as zkv_sp1_verify_batch)
+    void verify_batch(const std::vector<uint8_t>& vkeys, const std::vector<uint8_t>& pv_blob, const std::vector<uint64_t>& pv_off,
+                      const std::vector<uint8_t>& proof_blob, const std::vector<uint64_t>& proof_off, std::vector<uint8_t>& status,
+                      std::vector<uint8_t>& recv) const {
+        const size_t n = proof_off.empty() ? 0 : proof_off.size() - 1;
+        if (vkeys.size() != 32 * n || pv_off.size() != proof_off.size()) throw std::invalid_argument("Sp1Gateway::verify_batch: buffer sizes");
+        status.assign(n, 0); recv.assign(4 * n, 0);
+        const uint8_t zero = 0;
+        const int rc = zkv_sp1_gateway_verify_batch(ctx_, n, vkeys.data(), pv_blob.empty() ? &zero : pv_blob.data(), pv_off.data(),
+                                                    proof_blob.empty() ? &zero : proof_blob.data(), proof_off.data(), status.data(), recv.data());
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_sp1_gateway_verify_batch failed with ZKV error " + std::to_string(rc));
+    }
+    // {proofs per route..., not found, shorter than 4 bytes} of the most recent call
+    std::vector<uint64_t> last_route_counts() const {
+        std::vector<uint64_t> out(route_count() + 2);
+        const int rc = zkv_sp1_gateway_last_route_counts(ctx_, out.data());
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_sp1_gateway_last_route_counts failed with ZKV error " + std::to_string(rc));
+        return out;
+    }
+    // Opt-in aggregate check on every route (zkv_ctx_set_aggregate_check): sub_batch 0 = automatic size, 16 ... 256 fixed.
+    void set_aggregate_check(bool enable, const uint8_t* seed32 = nullptr, int sub_batch = 0) {
+        const int rc = zkv_ctx_set_aggregate_check(ctx_, enable ? (sub_batch ? sub_batch : 1) : 0, seed32);
+        if (rc != ZKV_OK) throw std::invalid_argument("zkv_ctx_set_aggregate_check failed with ZKV error " + std::to_string(rc));
+    }
+    zkv_ctx* handle() const { return ctx_; }
+
+private:
+    zkv_ctx* ctx_ = nullptr;
+};
+
+}  // namespace zkv

@@ -397,3 +397,49 @@ def calldata_sp1_verify_proof(program_vkeys, public_values, proofs):
     k = _u8_array_words(out, 100, public_values)
     _u8_array_words(out, k, proofs)
     return out
+
+
+def make_sp1_gateway_batch(groth16_pool, plonk_pool, n, groth16_fraction, seed, splice_every=0, splice_selectors=()):
+    """One ragged SP1 batch for the gateway (Sp1Gateway): Groth16 and PLONK proofs interleaved in a seeded random order.
+
+    groth16_pool / plonk_pool: (proofs uint8[k, L], program vkeys uint8[k, 32], public values uint8[k, V]) -- the Groth16 rows typically
+    from make_batch('sp1', <real SP1 proof>, k, seed) with the real proof's vkey and public values, the PLONK rows from a proof pool.
+    Both pools must have the same V (device batches take the public values at a fixed stride).  Proof i is Groth16 with probability
+    groth16_fraction, its row drawn at random from that pool.  Every splice_every-th proof (0: none) gets its first 4 bytes replaced by a
+    selector drawn from splice_selectors (a proof carried to another route, or to none).
+    Returns (proof blob uint8[], offsets uint64[n + 1], vkeys uint8[n, 32], public values uint8[n, V], kind int8[n] (0 Groth16, 1 PLONK),
+    pool row int64[n], spliced bool[n])."""
+    rng = np.random.default_rng(seed)
+    gp, gv, gw = (np.asarray(x, dtype=np.uint8) for x in groth16_pool)
+    pp, pv, pw = (np.asarray(x, dtype=np.uint8) for x in plonk_pool)
+    if gw.shape[1] != pw.shape[1]:
+        raise ValueError('both pools need public values of one length')
+    kind = (rng.random(n) >= groth16_fraction).astype(np.int8)
+    if not len(gp):
+        kind[:] = 1
+    if not len(pp):
+        kind[:] = 0
+    row = np.where(kind == 0, rng.integers(0, max(len(gp), 1), n), rng.integers(0, max(len(pp), 1), n))
+    lens = np.where(kind == 0, gp.shape[1], pp.shape[1]).astype(np.uint64)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(lens, dtype=np.uint64)
+    blob = np.zeros(int(off[-1]), dtype=np.uint8)
+    vkeys = np.zeros((n, 32), dtype=np.uint8)
+    pvs = np.zeros((n, gw.shape[1]), dtype=np.uint8)
+    for k, (P, V, W) in enumerate(((gp, gv, gw), (pp, pv, pw))):
+        idx = np.nonzero(kind == k)[0]
+        if not len(idx):
+            continue
+        L = P.shape[1]
+        for c0 in range(0, len(idx), 8192):                        # (index arrays of bounded size)
+            ic = idx[c0:c0 + 8192]
+            blob[off[ic].astype(np.int64)[:, None] + np.arange(L, dtype=np.int64)[None, :]] = P[row[ic]]
+        vkeys[idx] = V[row[idx]]
+        pvs[idx] = W[row[idx]]
+    spliced = np.zeros(n, dtype=bool)
+    if splice_every and len(splice_selectors):
+        for i in range(splice_every - 1, n, splice_every):
+            s = bytes(splice_selectors[int(rng.integers(0, len(splice_selectors)))])
+            blob[int(off[i]):int(off[i]) + 4] = np.frombuffer(s, dtype=np.uint8)
+            spliced[i] = True
+    return blob, off, vkeys, pvs, kind, row, spliced
