@@ -19,6 +19,7 @@
 #include "../../include/zkv.h"
 #include "../../include/zkv_groth16_set.h"
 #include "../../include/zkv_sp1_gateway.h"
+#include "../../include/zkv_plonk_keys.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
@@ -86,7 +87,8 @@ struct zkv_ctx {
     uint8_t* hb[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // seals, seal offsets, in_a, in_b, public values, pv offsets
     size_t hb_cap[6] = {0, 0, 0, 0, 0, 0};
     hipEvent_t ev_seg[2] = {nullptr, nullptr};
-    // ZKV_VM_SP1_PLONK: parsed verifying key, the SRS's two G2 points (reference word order) and the verifier hash
+    // ZKV_VM_SP1_PLONK and ZKV_VM_PLONK (zkv_plonk_keys.h): parsed verifying key, the SRS's two G2 points (reference word order) and
+    // (SP1) the verifier hash
     PlonkKeyRaw pk_raw; uint8_t pk_g2[256] = {0}, plonk_hash[32] = {0};
     PlonkKey* d_pkey = nullptr;
     uint32_t* d_plonk_tab = nullptr;                           // per-proof window tables of the PLONK stage (PLONK_TAB_WORDS words per proof in flight)
@@ -162,6 +164,9 @@ struct zkv_ctx {
     uint64_t gw_counts[GW_COLS] = {0};
     std::mutex mu;
 };
+
+// the two PLONK kinds share the device path after the public-input step (prep kernel, G2 line tables, MSM tables, aggregate check)
+static inline bool is_plonk(const zkv_ctx* c) { return c->vm == ZKV_VM_SP1_PLONK || c->vm == ZKV_VM_PLONK; }
 
 // Proofs per chunk (= per launch of the stage kernels): ZKV_CHUNK, default 2^20, clamped to [64, 2^26].  The upper clamp is a
 // correctness bound, not a tuning choice: the lane-pair kernels address their workspace rows through ONE 32-bit byte offset per lane
@@ -326,7 +331,7 @@ static int ctx_device_setup(zkv_ctx* c) {
         VkRaw raw;
         if (c->vm == ZKV_VM_RISC0 || c->vm == ZKV_VM_RISC0_SET) host::fill_vk_risc0(raw, c->control_root_0, c->control_root_1, c->control_id);
         else if (c->vm == ZKV_VM_GROTH16) host::fill_vk_generic(raw, c->gvk.data(), c->long_key ? 1u : c->g_n_ic);   // long key: IC[0] only here
-        else if (c->vm == ZKV_VM_SP1_PLONK) {
+        else if (is_plonk(c)) {
             // the pairing of a PLONK proof has two FIXED pairs: the SRS's [1]_2 and [tau]_2 take the line-table slots of gamma and
             // delta; there is no (alpha, beta) pair (alpha = infinity contributes 1) and no IC points
             memset(&raw, 0, sizeof raw);
@@ -382,7 +387,7 @@ static int ctx_device_setup(zkv_ctx* c) {
                 }
             }
         }
-        if (agg_vm || c->vm == ZKV_VM_SP1_PLONK) {
+        if (agg_vm || is_plonk(c)) {
             HIP_TRY(hipMalloc(&c->d_agg_cnt, 3 * sizeof(unsigned long long)));
             HIP_TRY(hipMemsetAsync(c->d_agg_cnt, 0, 3 * sizeof(unsigned long long), c->stream));
         }
@@ -405,11 +410,12 @@ static int ctx_device_setup(zkv_ctx* c) {
             c->inst_host.resize(k);
             HIP_TRY(hipMemcpyAsync(c->inst_host.data(), c->d_inst, sizeof(InstTab) * k, hipMemcpyDeviceToHost, c->stream));
         }
-        if (c->vm == ZKV_VM_SP1_PLONK) {
+        if (is_plonk(c)) {
             HIP_TRY(hipMalloc(&c->mx[1], sizeof(PlonkKeyRaw)));
             HIP_TRY(hipMalloc(&c->d_pkey, sizeof(PlonkKey)));
             HIP_TRY(hipMemcpyAsync(c->mx[1], &c->pk_raw, sizeof(PlonkKeyRaw), hipMemcpyHostToDevice, c->stream));
-            launch_plonk_setup((const PlonkKeyRaw*)c->mx[1], c->d_pkey, c->stream);
+            if (c->vm == ZKV_VM_PLONK) launch_plonk_setup_keys((const PlonkKeyRaw*)c->mx[1], c->d_pkey, c->stream);
+            else launch_plonk_setup((const PlonkKeyRaw*)c->mx[1], c->d_pkey, c->stream);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -422,7 +428,13 @@ static int ctx_device_setup(zkv_ctx* c) {
             HIP_TRY(hipMemcpy(&ok, &c->d_agg_tab->ok, sizeof ok, hipMemcpyDeviceToHost));
             c->agg_key_ok = ok != 0;
         }
-        if (c->vm == ZKV_VM_SP1_PLONK) c->agg_key_ok = !c->vk_invalid;      // (no (alpha, beta) pair: nothing else to tabulate)
+        if (is_plonk(c)) c->agg_key_ok = !c->vk_invalid;      // (no (alpha, beta) pair: nothing else to tabulate)
+        if (c->vm == ZKV_VM_PLONK) {
+            // the key's own validity (points, size_inv / generator / coset_shift < R) was judged by k_plonk_setup
+            uint32_t kv = 0;
+            HIP_TRY(hipMemcpy(&kv, &c->d_pkey->valid, sizeof kv, hipMemcpyDeviceToHost));
+            if (!kv) { c->vk_invalid = true; c->agg_key_ok = false; }
+        }
     }
     return ZKV_OK;
 }
@@ -501,7 +513,7 @@ static int ctx_reserve(zkv_ctx* c, size_t want) {
         hipMalloc(&c->d_len, sizeof(uint32_t) * cap) != hipSuccess || hipMalloc(&c->d_pvlen, sizeof(uint32_t) * cap) != hipSuccess ||
         hipMalloc(&c->d_kind, cap) != hipSuccess || hipMalloc(&c->d_cdoff[0], sizeof(uint64_t) * (cap + 1)) != hipSuccess ||
         hipMalloc(&c->d_cdoff[1], sizeof(uint64_t) * (cap + 1)) != hipSuccess ||
-        (c->vm == ZKV_VM_SP1_PLONK && hipMalloc(&c->d_plonk_tab, sizeof(uint32_t) * PLONK_TAB_WORDS * cap) != hipSuccess)) {
+        (is_plonk(c) && hipMalloc(&c->d_plonk_tab, sizeof(uint32_t) * PLONK_TAB_WORDS * cap) != hipSuccess)) {
         (void)hipGetLastError();
         return ZKV_ERR_OOM;
     }
@@ -704,12 +716,13 @@ static LongKey long_key_of(const zkv_ctx* c) { return LongKey{c->d_ltab, c->d_lw
 // Enqueues the five stages for one chunk (all pointers device-resident).
 static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool timed) {
     if (timed) (void)hipEventRecord(c->ev[0], s);
-    if (c->vm == ZKV_VM_SP1_PLONK) {
+    if (is_plonk(c)) {
         // PLONK: the prep stage does everything up to the two G1 points of the final check (transcript, scalar algebra, MSMs);
         // no per-proof G2 point, so no subgroup check, and no vk_x stage
         PrepArgs ap = a;
         ap.plonk_tab = c->d_plonk_tab;
-        launch_plonk_prep(ap, c->d_pkey, c->ws, s);
+        if (c->vm == ZKV_VM_PLONK) launch_plonk_prep_keys(ap, c->d_pkey, c->ws, s);
+        else launch_plonk_prep(ap, c->d_pkey, c->ws, s);
         if (c->agg_on && c->agg_key_ok && c->agg_cap >= c->ws.cap && c->lanes == 0 && a.n >= agg_min() && agg_wanted(c)) {
             if (timed) (void)hipEventRecord(c->ev[1], s);
             enqueue_agg_plonk(c, a, s, timed);
@@ -1146,12 +1159,13 @@ ZKV_EXPORT zkv_ctx* zkv_ctx_create_sharded(zkv_ctx* const* shards, size_t n_shar
         const zkv_ctx* s = shards[k];
         if (!s || is_sharded(s) || s->vm != shards[0]->vm) return nullptr;
         for (size_t j = 0; j < k; j++) if (shards[j] == s) return nullptr;
-        if (s->vm != ZKV_VM_RISC0 && s->vm != ZKV_VM_SP1 && s->vm != ZKV_VM_MIXED && s->vm != ZKV_VM_GROTH16 && s->vm != ZKV_VM_SP1_PLONK) return nullptr;
+        if (s->vm != ZKV_VM_RISC0 && s->vm != ZKV_VM_SP1 && s->vm != ZKV_VM_MIXED && s->vm != ZKV_VM_GROTH16 && s->vm != ZKV_VM_SP1_PLONK &&
+            s->vm != ZKV_VM_PLONK) return nullptr;
         // shards of one verifier: the same parameters everywhere (the host-visible state of shard 0 answers the getters)
         if (!s->initialized || memcmp(s->selector, shards[0]->selector, 4) || memcmp(s->control_id, shards[0]->control_id, 32) ||
             s->gvk != shards[0]->gvk || s->g_n_ic != shards[0]->g_n_ic || s->g_negate != shards[0]->g_negate || s->long_key != shards[0]->long_key ||
             memcmp(s->plonk_hash, shards[0]->plonk_hash, 32)) return nullptr;
-        if (s->vm == ZKV_VM_SP1_PLONK && (memcmp(&s->pk_raw, &shards[0]->pk_raw, sizeof s->pk_raw) || memcmp(s->pk_g2, shards[0]->pk_g2, sizeof s->pk_g2))) return nullptr;
+        if (is_plonk(s) && (memcmp(&s->pk_raw, &shards[0]->pk_raw, sizeof s->pk_raw) || memcmp(s->pk_g2, shards[0]->pk_g2, sizeof s->pk_g2))) return nullptr;
         if (s->vm == ZKV_VM_MIXED && memcmp(s->kid[0]->selector, shards[0]->kid[0]->selector, 4)) return nullptr;
     }
     zkv_ctx* c = new (std::nothrow) zkv_ctx();
@@ -1162,6 +1176,7 @@ ZKV_EXPORT zkv_ctx* zkv_ctx_create_sharded(zkv_ctx* const* shards, size_t n_shar
     memcpy(c->control_id, s0->control_id, 32); memcpy(c->selector, s0->selector, 4);
     c->consts = s0->consts; c->g_n_ic = s0->g_n_ic; c->g_negate = s0->g_negate; c->gvk = s0->gvk; c->long_key = s0->long_key;
     memcpy(c->plonk_hash, s0->plonk_hash, 32);
+    c->pk_raw = s0->pk_raw; memcpy(c->pk_g2, s0->pk_g2, sizeof c->pk_g2);
     c->shards.assign(shards, shards + n_shards);
     c->sh.resize(n_shards);
     return c;
@@ -2249,6 +2264,117 @@ ZKV_EXPORT int zkv_groth16_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_t*
     return mark_done(c, s);
 }
 
+// ------------------------------------------------------------------ PLONK core, any key (zkv_plonk_keys.h)
+// No reference counterpart: parity unpinned.  The SP1 PLONK context's device path with the public inputs read from a per-proof row.
+static size_t plonk_proof_bytes(const zkv_ctx* c) { return (size_t)32 * (24 + 3 * c->pk_raw.n_c); }
+// Host batches stage the public inputs of a chunk (32 nb_public bytes per proof) next to the proofs: at most LONG_STAGE_BYTES per chunk.
+static size_t plonk_host_chunk(const zkv_ctx* c) {
+    const size_t per = 32 * (size_t)c->pk_raw.nb_public, cap = chunk_capacity();
+    if (!per) return cap;
+    size_t lim = 64;
+    while (lim < cap && 2 * lim * per <= LONG_STAGE_BYTES) lim *= 2;
+    return lim < cap ? lim : cap;
+}
+// device set-up and buffers for a batch of n proofs; the proofs per chunk of a host batch through *chunk
+static int plonk_ready(zkv_ctx* c, size_t n, size_t* chunk) {
+    const size_t hc = plonk_host_chunk(c);
+    const int rc = ctx_ready(c, n < hc ? n : hc);
+    *chunk = c->ws.cap < hc ? c->ws.cap : hc;
+    return rc;
+}
+ZKV_EXPORT zkv_ctx* zkv_plonk_ctx_create(const uint8_t* vk, size_t vk_len, int device) {
+    if (!vk || vk_len < 7 * 32) return nullptr;
+    uint32_t w[7][8];
+    for (int k = 0; k < 7; k++) host::be_to_limbs(w[k], vk + 32 * k);
+    auto below = [](const uint32_t* x, int limbs) { for (int i = limbs; i < 8; i++) if (x[i]) return false; return true; };
+    // size < 2^64; nb_public, n_c and cci one limb each (the SP1 parser reads limb 0 alone; this one checks the others)
+    if (!below(w[0], 2) || !below(w[4], 1) || !below(w[5], 1) || !below(w[6], 1)) return nullptr;
+    if (w[5][0] > 1 || w[4][0] > ZKV_PLONK_MAX_PUBLIC) return nullptr;
+    const size_t n_c = w[5][0];
+    if (vk_len != 7 * 32 + (8 + n_c) * 64 + 256) return nullptr;
+    zkv_ctx* c = new (std::nothrow) zkv_ctx();
+    if (!c) return nullptr;
+    c->vm = ZKV_VM_PLONK; c->device = device; c->initialized = true;
+    memset(&c->consts, 0, sizeof c->consts);
+    memset(&c->pk_raw, 0, sizeof c->pk_raw);
+    memcpy(c->pk_raw.size, w[0], 32); memcpy(c->pk_raw.size_inv, w[1], 32); memcpy(c->pk_raw.gen, w[2], 32); memcpy(c->pk_raw.coset, w[3], 32);
+    c->pk_raw.nb_public = w[4][0]; c->pk_raw.n_c = w[5][0]; c->pk_raw.cci = w[6][0];
+    for (size_t p = 0; p < 8 + n_c; p++) {
+        host::be_to_limbs(c->pk_raw.pts[p][0], vk + 224 + 64 * p); host::be_to_limbs(c->pk_raw.pts[p][1], vk + 256 + 64 * p);
+    }
+    memcpy(c->pk_g2, vk + 224 + 64 * (8 + n_c), 256);
+    return c;
+}
+ZKV_EXPORT int zkv_plonk_key_shape(const zkv_ctx* c, size_t* nb_public, size_t* n_commitments, size_t* proof_bytes) {
+    if (!c || c->vm != ZKV_VM_PLONK) return ZKV_ERR_WRONG_CTX;
+    if (nb_public) *nb_public = c->pk_raw.nb_public;
+    if (n_commitments) *n_commitments = c->pk_raw.n_c;
+    if (proof_bytes) *proof_bytes = plonk_proof_bytes(c);
+    return ZKV_OK;
+}
+static PrepArgs plonk_args(const zkv_ctx* c, size_t m, const uint8_t* proofs, const uint8_t* pub, uint8_t* status) {
+    PrepArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = m; a.blob = proofs; a.stride = (uint32_t)plonk_proof_bytes(c);
+    a.in32_a = pub; a.n_sig = c->pk_raw.nb_public;
+    a.force_fail = c->vk_invalid ? 1u : 0u;
+    a.status = status; a.recv = nullptr;
+    return a;
+}
+ZKV_EXPORT int zkv_plonk_verify_batch(zkv_ctx* c, size_t n, const uint8_t* proofs, const uint8_t* public_inputs, uint8_t* verified) {
+    if (!c || c->vm != ZKV_VM_PLONK) return ZKV_ERR_WRONG_CTX;
+    const size_t pb = plonk_proof_bytes(c), pin = (size_t)32 * c->pk_raw.nb_public;
+    if (n && (!proofs || !verified || (pin && !public_inputs))) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (is_sharded(c))
+        return run_sharded(c, n, [&](zkv_ctx* k, size_t lo, size_t hi) {
+            return zkv_plonk_verify_batch(k, hi - lo, proofs + pb * lo, pin ? public_inputs + pin * lo : public_inputs, verified + lo); });
+    std::lock_guard<std::mutex> lk(c->mu);
+    size_t cap = 0;
+    int rc = plonk_ready(c, n, &cap);
+    if (rc != ZKV_OK) return rc;
+    if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
+    for (size_t base = 0; base < n; base += cap) {
+        const size_t m = n - base < cap ? n - base : cap;
+        if ((rc = grow(&c->d_blob, &c->blob_cap, m * pb + 8)) != ZKV_OK) return rc;
+        if ((rc = grow(&c->d_pv, &c->pv_cap, m * pin + 8)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(c->d_blob, proofs + pb * base, pb * m, hipMemcpyHostToDevice, c->stream));
+        if (pin) HIP_TRY(hipMemcpyAsync(c->d_pv, public_inputs + pin * base, pin * m, hipMemcpyHostToDevice, c->stream));
+        const PrepArgs a = plonk_args(c, m, c->d_blob, c->d_pv, c->d_status);
+        enqueue_chunk(c, a, c->stream, true);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(verified + base, c->d_status, m, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < m; i++) verified[base + i] = verified[base + i] == ZKV_STATUS_OK ? 1 : 0;
+    }
+    return mark_done(c, c->stream);
+}
+ZKV_EXPORT int zkv_plonk_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_proofs, const uint8_t* d_public_inputs, uint8_t* d_verified, void* stream) {
+    if (!c || c->vm != ZKV_VM_PLONK) return ZKV_ERR_WRONG_CTX;
+    const size_t pb = plonk_proof_bytes(c), pin = (size_t)32 * c->pk_raw.nb_public;
+    if (n && (!d_proofs || !d_verified || (pin && !d_public_inputs))) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (is_sharded(c)) {
+        const DevRow rows[2] = {{d_proofs, pb}, {d_public_inputs, pin}};
+        return run_sharded_dev(c, n, rows, pin ? 2 : 1, d_verified, nullptr, stream, [&](zkv_ctx* k, size_t m, const uint8_t* const* r, uint8_t* st, uint8_t*, hipStream_t s) {
+            return zkv_plonk_verify_batch_dev(k, m, r[0], pin ? r[1] : nullptr, st, s); });
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_ready(c, n);
+    if (rc != ZKV_OK) return rc;
+    const size_t cap = c->ws.cap;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    for (size_t base = 0; base < n; base += cap) {
+        const size_t m = n - base < cap ? n - base : cap;
+        const PrepArgs a = plonk_args(c, m, d_proofs + pb * base, pin ? d_public_inputs + pin * base : nullptr, d_verified + base);
+        enqueue_chunk(c, a, s, base + cap >= n);
+        launch_status_to_bool(m, d_verified + base, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return mark_done(c, s);
+}
+
 // ------------------------------------------------------------------ Groth16 key sets (zkv_groth16_set.h)
 // Set-up of every key in six launches whatever the number of keys (k_gset.hip): VkTables per key (alpha, beta, gamma, delta and IC[0]:
 // 3.6 MB, most of it the unused short-key rows of the struct) and 512 KB of window rows per signal.
@@ -2602,7 +2728,7 @@ ZKV_EXPORT int zkv_groth16_set_vk_x_batch(zkv_ctx* c, size_t n, const uint32_t* 
 ZKV_EXPORT int zkv_ctx_vk_x_batch(zkv_ctx* c, size_t n, const uint8_t* var_signals, uint8_t* out) {
     if (is_sharded(c)) c = c->shards[0];
     if (!c || c->vm == ZKV_VM_BN254 || c->vm == ZKV_VM_RISC0_SET || c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_PLONK || c->vm == ZKV_VM_GROTH16_SET ||
-        c->vm == ZKV_VM_SP1_GATEWAY)
+        c->vm == ZKV_VM_SP1_GATEWAY || c->vm == ZKV_VM_PLONK)
         return ZKV_ERR_WRONG_CTX;
     if (c->vm == ZKV_VM_RISC0 && !c->initialized) return ZKV_ERR_INVALID_ARG;
     if (n && (!var_signals || !out)) return ZKV_ERR_INVALID_ARG;
@@ -2717,7 +2843,7 @@ ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t
         return ZKV_OK;
     }
     if (c->vm != ZKV_VM_RISC0 && c->vm != ZKV_VM_RISC0_SET && c->vm != ZKV_VM_SP1 && c->vm != ZKV_VM_GROTH16 && c->vm != ZKV_VM_SP1_PLONK &&
-        c->vm != ZKV_VM_GROTH16_SET)
+        c->vm != ZKV_VM_GROTH16_SET && c->vm != ZKV_VM_PLONK)
         return enable ? ZKV_ERR_INVALID_ARG : ZKV_OK;
     {
         std::lock_guard<std::mutex> lk(c->mu);
@@ -2808,6 +2934,7 @@ ZKV_EXPORT int zkv_ctx_reserve(zkv_ctx* c, size_t n) {
     }
     std::lock_guard<std::mutex> lk(c->mu);
     size_t chunk;
+    if (c->vm == ZKV_VM_PLONK) return plonk_ready(c, n, &chunk);
     return c->vm == ZKV_VM_GROTH16 || c->vm == ZKV_VM_GROTH16_SET ? groth16_ready(c, n, &chunk) : ctx_ready(c, n);
 }
 ZKV_EXPORT int zkv_ctx_synchronize(zkv_ctx* c) {

@@ -195,7 +195,9 @@ void launch_gset_agg_mark(size_t n, uint32_t sub, uint32_t g, const Workspace& w
 #endif
 struct PlonkKeyRaw; struct PlonkKey;
 void launch_plonk_setup(const PlonkKeyRaw* d_raw, PlonkKey* d_key, hipStream_t s);
+void launch_plonk_setup_keys(const PlonkKeyRaw* d_raw, PlonkKey* d_key, hipStream_t s);     // any key (k_plonk_keys.hip): include/zkv_plonk_keys.h key rule
 void launch_plonk_prep(const PrepArgs& a, const PlonkKey* d_key, const Workspace& ws, hipStream_t s);
+void launch_plonk_prep_keys(const PrepArgs& a, const PlonkKey* d_key, const Workspace& ws, hipStream_t s);     // any key, up to 128 public inputs (k_plonk_keys.hip)
 
 // k_wide.hip: consumer wavefronts that timed out waiting for their producer on the current device (always 0 unless a wavefront died)
 int read_wait_faults(unsigned long long* out);

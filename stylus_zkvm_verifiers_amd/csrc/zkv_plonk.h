@@ -77,14 +77,18 @@ ZKV_HD bool plonk_g1(const uint32_t x[8], const uint32_t y[8], G1A& out, uint32_
     out.x = fp_from_raw(x); out.y = fp_from_raw(y); inf = 0;
     return g1_on_curve(out.x, out.y);
 }
-ZKV_HD void plonk_setup_key(const PlonkKeyRaw& r, PlonkKey& k) {
-    bool ok = raw_lt_r(r.size_inv) && raw_lt_r(r.gen) && raw_lt_r(r.coset) && r.n_c <= 1 && r.nb_public == 2;
+// generic = false: an SP1 PLONK key (exactly two public inputs); true: any key of include/zkv_plonk_keys.h (up to PLONK_MAX_PUBLIC public
+// inputs; nb_public + cci may carry into a 33rd bit)
+constexpr uint32_t PLONK_MAX_PUBLIC = 128;
+ZKV_HD void plonk_setup_key(const PlonkKeyRaw& r, PlonkKey& k, bool generic = false) {
+    bool ok = raw_lt_r(r.size_inv) && raw_lt_r(r.gen) && raw_lt_r(r.coset) && r.n_c <= 1 && (generic ? r.nb_public <= PLONK_MAX_PUBLIC : r.nb_public == 2);
     for (int i = 0; i < 8; i++) { k.size[i] = r.size[i]; k.size_p2[i] = r.size[i]; }
     uint32_t c = 2;
     for (int i = 0; i < 8; i++) { uint64_t t = (uint64_t)k.size_p2[i] + c; k.size_p2[i] = (uint32_t)t; c = (uint32_t)(t >> 32); }
     k.size_inv = fr_from_raw(r.size_inv); k.gen = fr_from_raw(r.gen); k.coset = fr_from_raw(r.coset);
     uint32_t e[8] = {r.nb_public + r.cci, 0, 0, 0, 0, 0, 0, 0};
-    k.gen_cci = fr_pow(k.gen, e, 32);
+    if (generic) e[1] = e[0] < r.cci ? 1u : 0u;
+    k.gen_cci = fr_pow(k.gen, e, generic ? 33 : 32);
     k.nb_public = r.nb_public; k.n_c = r.n_c; k.pad = 0;
     for (int p = 0; p < PK_POINTS; p++) {
         for (int j = 0; j < 8; j++) { k.raw[p][0][j] = r.pts[p][0][j]; k.raw[p][1][j] = r.pts[p][1][j]; }
@@ -338,15 +342,34 @@ ZKV_HD Fr plonk_hash_to_field(const uint32_t x[8], const uint32_t y[8]) {
 }
 
 // ---------------------------------------------------------------- the verifier up to the pairing
-// words: the 27 proof words as canonical limbs.  pub: the two public inputs (program vkey unreduced, public-values hash).
+// The public inputs come from one of two sources, the template parameter of plonk_prepare:
+//   uint32_t[2][8]  SP1 PLONK (k_plonk_prep): the two inputs (program vkey unreduced, public-values hash) in registers;
+//   PlonkPubRow     any key (k_plonk_prep_keys, include/zkv_plonk_keys.h): key.nb_public 32-byte big-endian words of the proof's row,
+//                   read where they are used (the transcript, the range check, PI(zeta)) and never held in a private array.
+// Everything else -- transcript, scalar algebra, the four multi-scalar multiplications, the KZG folding -- is one copy for both.
+struct PlonkPubRow { const uint8_t* p; };
+template <class PUB> struct PlonkPubIsRow { static constexpr bool value = false; };
+template <> struct PlonkPubIsRow<PlonkPubRow> { static constexpr bool value = true; };
+
+// words: the 27 proof words as canonical limbs (a key without commitment: words 24..26 zero, never checked).
 // Returns false => VerificationFailed.  On success D and Q are the pairing's G1 inputs (Q already negated), Jacobian, Z = 0 for infinity:
 // what the Miller loop wants of them -- x / y and 1 / y -- takes one inversion for both (k_plonk_prep), affine coordinates would take two more.
 struct PlonkOut { G1J d, q; };
-ZKV_HD_NI bool plonk_prepare(const PlonkKey& key, const uint32_t (&w)[27][8], const uint32_t (&pub)[2][8], PlonkOut& out, const TabRef& tab) {
+template <class PUB>
+ZKV_HD_NI bool plonk_prepare(const PlonkKey& key, const uint32_t (&w)[27][8], const PUB& pub, PlonkOut& out, const TabRef& tab) {
+    constexpr bool ROW = PlonkPubIsRow<PUB>::value;
     if (!key.valid) return false;
-    if (!raw_lt_r(pub[0]) || !raw_lt_r(pub[1])) return false;
-    const int SC[7] = {12, 13, 14, 15, 16, 19, 24};
-    for (int i = 0; i < 7; i++) if (!raw_lt_r(w[SC[i]])) return false;
+    if constexpr (ROW) {
+#pragma unroll 1
+        for (uint32_t i = 0; i < key.nb_public; i++) { uint32_t x[8]; load_be256(x, pub.p + 32 * (size_t)i); if (!raw_lt_r(x)) return false; }
+        const int SC[6] = {12, 13, 14, 15, 16, 19};
+        for (int i = 0; i < 6; i++) if (!raw_lt_r(w[SC[i]])) return false;
+        if (key.n_c && !raw_lt_r(w[24])) return false;
+    } else {
+        if (!raw_lt_r(pub[0]) || !raw_lt_r(pub[1])) return false;
+        const int SC[7] = {12, 13, 14, 15, 16, 19, 24};
+        for (int i = 0; i < 7; i++) if (!raw_lt_r(w[SC[i]])) return false;
+    }
     // proof points: L R O H0 H1 H2 Z Hz Hzw BSB
     const int PT[10] = {0, 2, 4, 6, 8, 10, 17, 20, 22, 25};
     G1A pp[10]; uint32_t pinf[10];
@@ -362,7 +385,10 @@ ZKV_HD_NI bool plonk_prepare(const PlonkKey& key, const uint32_t (&w)[27][8], co
 #pragma unroll 1
     for (int p = 0; p < 8; p++) { s.limbs_be(key.raw[p][0]); s.limbs_be(key.raw[p][1]); }
     if (n_c) { s.limbs_be(key.raw[PK_QCP][0]); s.limbs_be(key.raw[PK_QCP][1]); }
-    s.limbs_be(pub[0]); s.limbs_be(pub[1]);
+    if constexpr (ROW) {
+#pragma unroll 1
+        for (uint32_t i = 0; i < key.nb_public; i++) { uint32_t x[8]; load_be256(x, pub.p + 32 * (size_t)i); s.limbs_be(x); }
+    } else { s.limbs_be(pub[0]); s.limbs_be(pub[1]); }
 #pragma unroll 1
     for (int i = 0; i < 6; i++) s.limbs_be(w[i]);
     s.finish(cg);
@@ -385,12 +411,27 @@ ZKV_HD_NI bool plonk_prepare(const PlonkKey& key, const uint32_t (&w)[27][8], co
     digest_to_limbs(cz, lim); const Fr zeta = fr_from_raw_reduce(lim);
     // ---- public-input polynomial at zeta
     const Fr one = fr_one();
-    const Fr zeta_n = fr_pow(zeta, key.size, 64);
+    const Fr zeta_n = fr_pow(zeta, key.size, 64);        // size < 2^64 (both context kinds check it)
     const Fr zh = fr_sub(zeta_n, one);
     Fr den = fr_sub(zeta, one);
     if (fr_is_zero(den)) return false;
-    // the three denominators zeta - 1, zeta - w, zeta - w^(nb_public + cci) share one inversion
-    const Fr d1 = fr_sub(zeta, key.gen), d2 = fr_sub(zeta, key.gen_cci);
+    // the three denominators zeta - 1, d1, zeta - w^(nb_public + cci) share one inversion.  SP1: d1 = zeta - w.  Any key: the public
+    // inputs' sum  sum_i x_i w^i / (zeta - w^i)  as a running fraction N / d1 (N <- N d_i + x_i w^i d1, d1 <- d1 d_i: four Fr
+    // multiplications per input, plus the next power of w); d1 = 0 exactly when some zeta - w^i vanishes (i = 0: zeta - 1, checked above).
+    Fr d1, pin;
+    if constexpr (ROW) {
+        Fr wi = one;
+        d1 = one; pin = fr_zero();
+#pragma unroll 1
+        for (uint32_t i = 0; i < key.nb_public; i++) {
+            uint32_t x[8]; load_be256(x, pub.p + 32 * (size_t)i);
+            const Fr di = fr_sub(zeta, wi);
+            pin = fr_add(fr_mul(pin, di), fr_mul(fr_mul(fr_from_raw(x), wi), d1));
+            d1 = fr_mul(d1, di);
+            wi = fr_mul(wi, key.gen);
+        }
+    } else d1 = fr_sub(zeta, key.gen);
+    const Fr d2 = fr_sub(zeta, key.gen_cci);
     if (fr_is_zero(d1) || (n_c && fr_is_zero(d2))) return false;
     const Fr d2e = n_c ? d2 : one;
     const Fr p01 = fr_mul(den, d1);
@@ -400,8 +441,12 @@ ZKV_HD_NI bool plonk_prepare(const PlonkKey& key, const uint32_t (&w)[27][8], co
     const Fr i0 = fr_mul(i01, d1), i1 = fr_mul(i01, den);
     const Fr zn = fr_mul(zh, key.size_inv);                // (zeta^n - 1) / n
     const Fr lag0 = fr_mul(zn, i0);
-    Fr pi = fr_mul(lag0, fr_from_raw(pub[0]));
-    pi = fr_add(pi, fr_mul(fr_mul(fr_mul(zn, i1), key.gen), fr_from_raw(pub[1])));
+    Fr pi;
+    if constexpr (ROW) pi = fr_mul(fr_mul(zn, i1), pin);
+    else {
+        pi = fr_mul(lag0, fr_from_raw(pub[0]));
+        pi = fr_add(pi, fr_mul(fr_mul(fr_mul(zn, i1), key.gen), fr_from_raw(pub[1])));
+    }
     if (n_c) pi = fr_add(pi, fr_mul(fr_mul(fr_mul(zn, i2), key.gen_cci), plonk_hash_to_field(w[25], w[26])));
     const Fr l = fr_from_raw(w[12]), r = fr_from_raw(w[13]), o = fr_from_raw(w[14]), s1 = fr_from_raw(w[15]), s2 = fr_from_raw(w[16]);
     const Fr zu = fr_from_raw(w[19]), qcpz = fr_from_raw(w[24]);
@@ -414,7 +459,7 @@ ZKV_HD_NI bool plonk_prepare(const PlonkKey& key, const uint32_t (&w)[27][8], co
     const Fr bz = fr_mul(beta, zeta), bzu = fr_mul(bz, key.coset), bzu2 = fr_mul(bzu, key.coset);
     const Fr _s2 = fr_neg(fr_mul(fr_mul(fr_mul(alpha, fr_add(fr_add(bz, l), gamma)), fr_add(fr_add(bzu, r), gamma)), fr_add(fr_add(bzu2, o), gamma)));
     const Fr coeff_z = fr_add(a2l0, _s2);
-    const Fr zn2 = fr_pow(zeta, key.size_p2, 64);
+    const Fr zn2 = fr_pow(zeta, key.size_p2, ROW ? 65 : 64);      // size + 2 may need a 65th bit (an SP1 key keeps the 64 it always had)
     const Fr k0 = fr_neg(zh), k1 = fr_mul(zn2, k0), k2 = fr_mul(zn2, k1);
     // ---- linearised polynomial digest: qcp Pi2 + l Ql + r Qr + lr Qm + o Qo + Qk + _s1 S3 + coeff_z Z + k0 H0 + k1 H1 + k2 H2
     G1J qk = g1j_infinity();
