@@ -1,0 +1,51 @@
+/*
+ * zkv_diag_primitive.h -- known-answer harness of the arithmetic primitives.  TEST ONLY: no verification path uses it.
+ *
+ * Runs operands the caller chooses through the library's own field, tower and G1 code on the device, in the mappings the verify
+ * kernels use (one value per lane, one case per lane pair, one per 16 lanes, one per wavefront), and returns the raw result words, so
+ * that a test can check a primitive at the edges of its contract.  Companion of zkv.h (same library, same ZKV_OK / ZKV_ERR_* codes);
+ * the case bodies are stylus_zkvm_verifiers_amd/csrc/zkv_selftest.h.
+ */
+#ifndef ZKV_DIAG_PRIMITIVE_H
+#define ZKV_DIAG_PRIMITIVE_H
+#include "zkv.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define ZKV_DIAG_PRIMITIVE_MAX_CASES 65536
+
+/* Synchronous, host buffers: runs n cases (1 <= n <= ZKV_DIAG_PRIMITIVE_MAX_CASES) of one op
+ * through the library's own field, tower and G1 code in the mapping the verify kernels use, and returns the raw result words.
+ * ZKV_ERR_INVALID_ARG for an unknown (mapping, op), n = 0 or n > 65,536, or a NULL buffer (checked before anything is launched);
+ * ZKV_ERR_NO_DEVICE without a gfx950 device.  Words are little-endian uint32; an Fp or Fr is 8 words holding a Montgomery-domain
+ * integer (R = 2^261 for both fields; inputs need not be reduced), an Fp2 is c0 then c1 (16 words), an Fp12 six Fp2 in slot order
+ * g0 g1 g2 h0 h1 h2 = powers 0 2 4 1 3 5 of w (96 words).  in: n x IN words, out: n x OUT words; per op (IN -> OUT):
+ *   mapping 0, one value per lane:
+ *     op 0  a b c (24) -> fp_add(a,b) fp_sub(a,b) fp_neg(a) fp_dbl(a) fp_half(a), fp_add_x2 -> (a+b, c+a), fp_sub_x2 -> (a-b, c-a),
+ *           fp_add_n<3>([a b c], [b c a]), fp_sub_n<3>(same), then fp_is_zero(a), fp_eq(a,b) and six zero words (128)
+ *     op 1  a b c (24) -> fp_mul(a,b) fp_sqr(c) (16)           op 2  x (raw, < p) y (16) -> fp_from_raw(x) fp_to_raw(y) (16)
+ *     op 3  a (8) -> fp_inv(a) (8)                             op 4  a b (Fp2, 32) -> f2_mul(a,b) f2_sqr(a) f2_mul_xi(a) f2_inv(a) (64)
+ *     op 5  a b (Fr) x (raw 256-bit) (24) -> fr_mul(a,b) fr_add(a,b) fr_sub(a,b) fr_inv(a) fr_from_raw_reduce(x) (40)
+ *     op 6  k (raw, 8) -> glv_split: |k1| (5 words) neg1 |k2| (5 words) neg2 (12)
+ *     op 7  P (Jacobian x y z) Q (affine x y) T (Jacobian) (64) -> g1j_dbl(P) g1j_add_affine(P,Q) g1j_add(P,T) (72)
+ *   mapping 1, one case per lane pair (ZKV_PAIRED: the even lane holds c0, the odd lane c1):
+ *     op 0  a b (Fp2, 32) -> f2_mul(a,b) f2_sqr(a) f2_mul_xi(a) f2_add(a,b) f2_sub(a,b) (80)
+ *     op 1  n c k_even[8] k_odd[8] x_even[8][9] x_odd[8][9] (162) -> l9_lincomb of the first n (1..8; otherwise zeros) terms with
+ *           coefficient c, nine 29-bit limbs per lane, even lane first (18)
+ *     op 2  a0 a1 b0 b1, nine limbs each (36) -> l9_mul(a, b), nine limbs per component (18)
+ *     op 3  a b (Fp12) c0 c3 c4 (Fp2) (240) -> eleven Fp12 (1056): f12m_mul(a,b) f12m_mul_conj(a,b) f12m_sqr(a) f12m_inv(a)
+ *           f12m_frob(a,1) (a,2) (a,3) f12m_mul_by_034(a; c0,c3,c4) f12m_mul_by_134(a; c3,c4) f12l9_mul(a,b) f12l9_mul(a,conj b),
+ *           with a and the results in LDS slots (LRef; L9Ref for f12l9_*) and the S operand of f12l9_mul in the input row
+ *     op 4  a (cyclotomic Fp12, 96) -> f12m_cyclo_sqr(a) f12l9_cyclo_sqr(a) (192)
+ *   mapping 2 (one case per 16 lanes, S = 1) and mapping 3 (one case per wavefront, S = 4), zkv_tower_wide.h:
+ *     op 0  a b c0 c3 c4 as for mapping 1 op 3 (240) -> eight Fp12 (768): w12_mul(a,b) w12_mul(a,conj b) w12_sqr(a)
+ *           w12_mul_sparse(a; c0,c3,c4) w12_mul_sparse(a; 1,c3,c4) w12_frob(a,1) (a,2) (a,3)
+ *     op 1  a (cyclotomic Fp12, 96) -> w12_cyclo_sqr(a) (96) */
+int zkv_diag_primitive(int device, int mapping, int op, size_t n, const uint32_t* in, uint32_t* out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* ZKV_DIAG_PRIMITIVE_H */

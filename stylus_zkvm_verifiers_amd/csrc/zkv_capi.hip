@@ -20,12 +20,14 @@
 #include "../../include/zkv_groth16_set.h"
 #include "../../include/zkv_sp1_gateway.h"
 #include "../../include/zkv_plonk_keys.h"
+#include "../../include/zkv_diag_primitive.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
 #include "zkv_plonk.h"
 #include "zkv_agg.h"
 #include "zkv_gset_layout.h"
+#include "zkv_selftest.h"
 #include <sys/random.h>
 
 using namespace zkv;
@@ -2798,6 +2800,32 @@ ZKV_EXPORT int zkv_diag_mulmod_rate(int device, int kind, int waves_per_simd, ui
 ZKV_EXPORT int zkv_diag_issue_rate(int device, int kind, int waves_per_simd, uint32_t iters, double* lane_instr_per_s, double* shader_clock_ghz) {
     if (kind < 0 || kind > 2 || waves_per_simd < 1 || waves_per_simd > 8 || !iters || !lane_instr_per_s) return ZKV_ERR_INVALID_ARG;
     return run_diag(device, true, kind, waves_per_simd, iters, lane_instr_per_s, shader_clock_ghz);
+}
+
+// Known-answer harness of the arithmetic primitives (zkv_selftest.h): every argument is checked here, before anything is allocated or
+// launched; the batch is padded to whole wavefronts (lane pairs, 16-lane groups) with zero operands whose results are discarded.
+ZKV_EXPORT int zkv_diag_primitive(int device, int mapping, int op, size_t n, const uint32_t* in, uint32_t* out) {
+    int iw = 0, ow = 0;
+    if (!selftest_io(mapping, op, &iw, &ow) || n == 0 || n > ZKV_DIAG_PRIMITIVE_MAX_CASES || !in || !out) return ZKV_ERR_INVALID_ARG;
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { (void)hipGetLastError(); return ZKV_ERR_NO_DEVICE; }
+    if (device < 0 || device >= nd || !device_is_gfx950(device)) return ZKV_ERR_NO_DEVICE;
+    HIP_TRY(hipSetDevice(device));
+    const size_t per = (size_t)selftest_cases_per_wave(mapping), waves = (n + per - 1) / per, padded = waves * per;
+    uint32_t *d_in = nullptr, *d_out = nullptr;
+    int rc = ZKV_ERR_HIP;
+    if (hipMalloc(&d_in, padded * (size_t)iw * 4) != hipSuccess || hipMalloc(&d_out, padded * (size_t)ow * 4) != hipSuccess) { rc = ZKV_ERR_OOM; goto done; }
+    if (hipMemset(d_in, 0, padded * (size_t)iw * 4) != hipSuccess || hipMemcpy(d_in, in, n * (size_t)iw * 4, hipMemcpyHostToDevice) != hipSuccess) goto done;
+    if (mapping == 0) launch_selftest_lane(op, (unsigned)waves, d_in, d_out, nullptr);
+    else launch_selftest_pair(mapping, op, (unsigned)waves, d_in, d_out, nullptr);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) goto done;
+    if (hipMemcpy(out, d_out, n * (size_t)ow * 4, hipMemcpyDeviceToHost) != hipSuccess) goto done;
+    rc = ZKV_OK;
+done:
+    if (rc != ZKV_OK) (void)hipGetLastError();
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    return rc;
 }
 
 // ------------------------------------------------------------------ shared

@@ -1,0 +1,219 @@
+// Known-answer harness of the arithmetic primitives (zkv_diag_primitive, include/zkv.h).  TEST ONLY: nothing on a verify path calls it.
+//
+// One case is one set of operands; the case bodies below call the library's own primitives -- nothing is re-implemented here -- in the
+// mapping the verify kernels run them in:
+//   mapping 0  one value per lane (k_selftest.hip, ZKV_PAIRED undefined): k_prep, k_msm, k_plonk, k_precompile, the aggregate check;
+//   mapping 1  one case per lane pair (k_selftest_pair.hip): k_miller2, k_finalexp2, the precompile pairing; Fp12 values in LDS slots
+//              (LRef, and L9Ref for the resident-limb accumulator) with the S operand of f12l9_mul in a global row (SoaRW);
+//   mapping 2  one case per 16 lanes (zkv_tower_wide.h, S = 1), mapping 3  one case per wavefront (S = 4), slots laid out as in k_wide.hip.
+// The bodies are ZKV_HD so that the host emulations (tests/host_sim) run the same code on the same cases.
+// Words: every Fp / Fr is eight little-endian 32-bit words (a Montgomery-domain integer, not necessarily reduced); an Fp2 is c0 then c1;
+// an Fp12 is six Fp2 in slot order g0 g1 g2 h0 h1 h2 (powers 0 2 4 1 3 5 of w), 96 words.  Layouts per op: include/zkv.h.
+#pragma once
+#include <stdint.h>
+
+namespace zkv {
+
+// words per case of (mapping, op): in, out; false for an unknown pair
+inline bool selftest_io(int mapping, int op, int* in_w, int* out_w) {
+    static const int LANE[8][2] = {{24, 128}, {24, 16}, {16, 16}, {8, 8}, {32, 64}, {24, 40}, {8, 12}, {64, 72}};
+    static const int PAIR[5][2] = {{32, 80}, {162, 18}, {36, 18}, {240, 11 * 96}, {96, 2 * 96}};
+    static const int WIDE[2][2] = {{240, 8 * 96}, {96, 96}};
+    const int* w = nullptr;
+    if (mapping == 0 && op >= 0 && op < 8) w = LANE[op];
+    else if (mapping == 1 && op >= 0 && op < 5) w = PAIR[op];
+    else if ((mapping == 2 || mapping == 3) && op >= 0 && op < 2) w = WIDE[op];
+    if (!w) return false;
+    *in_w = w[0]; *out_w = w[1];
+    return true;
+}
+// cases one wavefront holds in each mapping (the host pads a batch to whole wavefronts with zero operands)
+inline int selftest_cases_per_wave(int mapping) { return mapping == 0 ? 64 : mapping == 1 ? 32 : mapping == 2 ? 4 : 1; }
+
+}  // namespace zkv
+
+#if defined(ZKV_SELFTEST_BODIES)
+#if defined(ZKV_PAIRED)
+#include "zkv_tower_wide.h"
+#else
+#include "zkv_verify.h"
+#include "zkv_scalar.h"
+#endif
+
+namespace zkv {
+
+ZKV_HD Fp st_ld(const uint32_t* w) { Fp r; for (int i = 0; i < 8; i++) r.v[i] = w[i]; return r; }
+ZKV_HD void st_st(uint32_t* w, const Fp& a) { for (int i = 0; i < 8; i++) w[i] = a.v[i]; }
+
+#if !defined(ZKV_PAIRED)
+ZKV_HD Fr st_ldr(const uint32_t* w) { Fr r; for (int i = 0; i < 8; i++) r.v[i] = w[i]; return r; }
+ZKV_HD void st_str(uint32_t* w, const Fr& a) { for (int i = 0; i < 8; i++) w[i] = a.v[i]; }
+ZKV_HD void st_stj(uint32_t* w, const G1J& p) { st_st(w, p.x); st_st(w + 8, p.y); st_st(w + 16, p.z); }
+ZKV_HD G1J st_ldj(const uint32_t* w) { G1J p; p.x = st_ld(w); p.y = st_ld(w + 8); p.z = st_ld(w + 16); return p; }
+ZKV_HD Fp2 st_ld2(const uint32_t* w) { Fp2 r; r.c0 = st_ld(w); r.c1 = st_ld(w + 8); return r; }
+ZKV_HD void st_st2(uint32_t* w, const Fp2& a) { st_st(w, a.c0); st_st(w + 8, a.c1); }
+
+// one case, one lane
+ZKV_HD void selftest_lane(int op, const uint32_t* in, uint32_t* out) {
+    switch (op) {
+    case 0: {                // linear ops: in a b c; out add sub neg dbl half (a+b, c+a) (a-b, c-a) add_n sub_n [is_zero(a), eq(a, b)]
+        const Fp a = st_ld(in), b = st_ld(in + 8), c = st_ld(in + 16);
+        st_st(out, fp_add(a, b)); st_st(out + 8, fp_sub(a, b)); st_st(out + 16, fp_neg(a)); st_st(out + 24, fp_dbl(a)); st_st(out + 32, fp_half(a));
+        Fp r0, r1;
+        fp_add_x2(a, b, c, a, r0, r1); st_st(out + 40, r0); st_st(out + 48, r1);
+        fp_sub_x2(a, b, c, a, r0, r1); st_st(out + 56, r0); st_st(out + 64, r1);
+        const Fp x[3] = {a, b, c}, y[3] = {b, c, a};
+        Fp r[3];
+        fp_add_n<3>(x, y, r); for (int k = 0; k < 3; k++) st_st(out + 72 + 8 * k, r[k]);
+        fp_sub_n<3>(x, y, r); for (int k = 0; k < 3; k++) st_st(out + 96 + 8 * k, r[k]);
+        for (int k = 120; k < 128; k++) out[k] = 0;
+        out[120] = fp_is_zero(a) ? 1u : 0u; out[121] = fp_eq(a, b) ? 1u : 0u;
+        break;
+    }
+    case 1: {                // in a b c; out fp_mul(a, b), fp_sqr(c)
+        st_st(out, fp_mul(st_ld(in), st_ld(in + 8))); st_st(out + 8, fp_sqr(st_ld(in + 16)));
+        break;
+    }
+    case 2: {                // in x (canonical raw), y (Montgomery); out fp_from_raw(x), fp_to_raw(y)
+        st_st(out, fp_from_raw(in)); fp_to_raw(out + 8, st_ld(in + 8));
+        break;
+    }
+    case 3: st_st(out, fp_inv(st_ld(in))); break;
+    case 4: {                // in a b (Fp2); out f2_mul(a, b) f2_sqr(a) f2_mul_xi(a) f2_inv(a)
+        const Fp2 a = st_ld2(in), b = st_ld2(in + 16);
+        st_st2(out, f2_mul(a, b)); st_st2(out + 16, f2_sqr(a)); st_st2(out + 32, f2_mul_xi(a)); st_st2(out + 48, f2_inv(a));
+        break;
+    }
+    case 5: {                // in a b (Montgomery Fr), x (any 256-bit word); out fr_mul fr_add fr_sub fr_inv(a) fr_from_raw_reduce(x)
+        const Fr a = st_ldr(in), b = st_ldr(in + 8);
+        st_str(out, fr_mul(a, b)); st_str(out + 8, fr_add(a, b)); st_str(out + 16, fr_sub(a, b)); st_str(out + 24, fr_inv(a));
+        st_str(out + 32, fr_from_raw_reduce(in + 16));
+        break;
+    }
+    case 6: {                // in k (raw scalar); out |k1| (5 words) neg1 |k2| (5 words) neg2
+        uint32_t k[8], m1[5], m2[5], n1, n2;
+        for (int i = 0; i < 8; i++) k[i] = in[i];
+        glv_split(k, m1, n1, m2, n2);
+        for (int i = 0; i < 5; i++) { out[i] = m1[i]; out[6 + i] = m2[i]; }
+        out[5] = n1; out[11] = n2;
+        break;
+    }
+    case 7: {                // in P (Jacobian), Q (affine), R (Jacobian); out g1j_dbl(P), g1j_add_affine(P, Q), g1j_add(P, R)
+        const G1J p = st_ldj(in), r = st_ldj(in + 40);
+        st_stj(out, g1j_dbl(p)); st_stj(out + 24, g1j_add_affine(p, st_ld(in + 24), st_ld(in + 32))); st_stj(out + 48, g1j_add(p, r));
+        break;
+    }
+    default: break;
+    }
+}
+#else   // ---------------------------------------------------------------- lane pairs and wide groups
+
+template <int N> ZKV_HD L9 st_lincomb_n(const uint32_t* xs, const uint32_t* ks, int c) {
+    LTerm t[N];
+    for (int j = 0; j < N; j++) { t[j].x = xs + 9 * j; t[j].k = (int32_t)ks[j]; }
+    return l9_lincomb(t, c);
+}
+ZKV_HD Fp2 st_ldh(const uint32_t* w, uint32_t par) { Fp2 r; r.h = st_ld(w + 8 * par); return r; }
+
+// one case, one lane of its pair.  lds: this lane's column of a (144 + 54) x 64-word LDS block (word k of the column at lds[64 k]).
+ZKV_HD void selftest_pair(int op, const uint32_t* in, uint32_t* out, uint32_t* lds) {
+    const uint32_t par = zkv_parity();
+    switch (op) {
+    case 0: {                // in a0 a1 b0 b1; out (c0, c1) of f2_mul(a, b) f2_sqr(a) f2_mul_xi(a) f2_add(a, b) f2_sub(a, b)
+        const Fp2 a = st_ldh(in, par), b = st_ldh(in + 16, par);
+        const Fp2 r[5] = {f2_mul(a, b), f2_sqr(a), f2_mul_xi(a), f2_add(a, b), f2_sub(a, b)};
+        for (int k = 0; k < 5; k++) st_st(out + 16 * k + 8 * par, r[k].h);
+        break;
+    }
+    case 1: {                // in n c k_even[8] k_odd[8] x_even[8][9] x_odd[8][9]; out this lane's nine limbs (even lane first)
+        const int n = (int)in[0], c = (int)in[1];
+        const uint32_t* ks = in + 2 + 8 * par;
+        const uint32_t* xs = in + 18 + 72 * par;
+        L9 r;
+        switch (n) {
+        case 1: r = st_lincomb_n<1>(xs, ks, c); break;
+        case 2: r = st_lincomb_n<2>(xs, ks, c); break;
+        case 3: r = st_lincomb_n<3>(xs, ks, c); break;
+        case 4: r = st_lincomb_n<4>(xs, ks, c); break;
+        case 5: r = st_lincomb_n<5>(xs, ks, c); break;
+        case 6: r = st_lincomb_n<6>(xs, ks, c); break;
+        case 7: r = st_lincomb_n<7>(xs, ks, c); break;
+        case 8: r = st_lincomb_n<8>(xs, ks, c); break;
+        default: for (int i = 0; i < 9; i++) r.l[i] = 0; break;
+        }
+        for (int i = 0; i < 9; i++) out[9 * par + i] = r.l[i];
+        break;
+    }
+    case 2: {                // in a0 a1 b0 b1 as nine limbs each; out l9_mul(a, b), nine limbs per component
+        L9 a, b;
+        for (int i = 0; i < 9; i++) { a.l[i] = in[9 * par + i]; b.l[i] = in[18 + 9 * par + i]; }
+        const L9 r = l9_mul(a, b);
+        for (int i = 0; i < 9; i++) out[9 * par + i] = r.l[i];
+        break;
+    }
+    case 3: {                // in a b (Fp12) c0 c3 c4 (Fp2); out the eleven results listed in include/zkv.h
+        const LRef A = l_ref(lds), B = l_ref(lds + 48 * 64), D = l_ref(lds + 96 * 64);
+        const L9Ref acc = l9_ref(lds + 144 * 64);
+        const MRef ga = m_ref((uint32_t*)in + 8 * par, 1, 16), gb = m_ref((uint32_t*)in + 96 + 8 * par, 1, 16);
+        const Fp2 c0 = st_ldh(in + 192, par), c3 = st_ldh(in + 208, par), c4 = st_ldh(in + 224, par);
+        f12m_copy(A, ga); f12m_copy(B, gb);
+        f12m_copy(D, A); f12m_mul(D, D, B); f12m_copy(m_ref(out + 8 * par, 1, 16), D);                 // d aliases a, as in the kernels
+        f12m_copy(D, A); f12m_mul_conj(D, D, B); f12m_copy(m_ref(out + 96 + 8 * par, 1, 16), D);
+        f12m_copy(D, A); f12m_sqr(D); f12m_copy(m_ref(out + 192 + 8 * par, 1, 16), D);
+        f12m_inv(D, A); f12m_copy(m_ref(out + 288 + 8 * par, 1, 16), D);
+        for (int k = 1; k <= 3; k++) { f12m_frob(D, A, k); f12m_copy(m_ref(out + 288 + 96 * k + 8 * par, 1, 16), D); }
+        f12m_copy(D, A); f12m_mul_by_034(D, &c0, &c3, &c4); f12m_copy(m_ref(out + 672 + 8 * par, 1, 16), D);
+        f12m_copy(D, A); f12m_mul_by_134(D, &c3, &c4); f12m_copy(m_ref(out + 768 + 8 * par, 1, 16), D);
+        for (int cj = 0; cj < 2; cj++) {
+            SoaRW S; S.p = (uint32_t*)in + 96; S.stride = 1; S.off = 32u * par;
+            f12m_copy(acc, A);
+            f12l9_mul(acc, S, cj != 0);
+            f12m_copy(m_ref(out + 864 + 96 * cj + 8 * par, 1, 16), acc);
+        }
+        break;
+    }
+    case 4: {                // in a (cyclotomic Fp12); out f12m_cyclo_sqr(a), f12l9_cyclo_sqr(a)
+        const LRef D = l_ref(lds + 96 * 64);
+        const L9Ref acc = l9_ref(lds + 144 * 64);
+        const MRef ga = m_ref((uint32_t*)in + 8 * par, 1, 16);
+        f12m_copy(D, ga); f12m_cyclo_sqr(D); f12m_copy(m_ref(out + 8 * par, 1, 16), D);
+        f12m_copy(acc, ga); f12l9_cyclo_sqr(acc); f12m_copy(m_ref(out + 96 + 8 * par, 1, 16), acc);
+        break;
+    }
+    default: break;
+    }
+}
+
+// words of group memory per case of the wide mappings: slots a, b, d and the slices' rows
+constexpr int ST_WIDE_SLOT = 3 * 96 + W_RED_WORDS;
+// one case, one lane of its 16 S-lane group.  g: the group's ST_WIDE_SLOT words (LDS on the device); w: this lane's coefficient and slice.
+template <int S> ZKV_HD void selftest_wide(int op, const uint32_t* in, uint32_t* out, uint32_t* g, WL w) {
+    const uint32_t par = zkv_parity();
+    const int q = w.q;
+    uint32_t* base = g + 8 * par;
+    const MRef A = m_ref(base, 1, 16), B = m_ref(base + 96, 1, 16), D = m_ref(base + 192, 1, 16), red = m_ref(base + 288, 1, 16);
+    const MRef ga = m_ref((uint32_t*)in + 8 * par, 1, 16), gb = m_ref((uint32_t*)in + 96 + 8 * par, 1, 16);
+    auto put = [&](int k) { w12_copy(m_ref(out + 96 * k + 8 * par, 1, 16), D, q); };
+    switch (op) {
+    case 0: {                // in a b (Fp12) c0 c3 c4 (Fp2); out the eight results listed in include/zkv.h
+        const Fp2 c0 = st_ldh(in + 192, par), c3 = st_ldh(in + 208, par), c4 = st_ldh(in + 224, par);
+        w12_copy(A, ga, q); w12_copy(B, gb, q);
+        w12_copy(D, A, q); w12_mul<S>(D, D, B, w, false, red); put(0);          // d aliases a, as in exp_u_w
+        w12_copy(D, A, q); w12_mul<S>(D, D, B, w, true, red); put(1);
+        w12_copy(D, A, q); w12_sqr<S>(D, w, red); put(2);
+        w12_copy(D, A, q); w12_mul_sparse<S>(D, &c0, &c3, &c4, w, false, red); put(3);
+        w12_copy(D, A, q); w12_mul_sparse<S>(D, &c3, &c3, &c4, w, true, red); put(4);        // with `one`, c0 aliases c3 (fixed_lines_mul_w)
+        for (int k = 1; k <= 3; k++) { w12_frob(D, A, k, q); put(4 + k); }
+        break;
+    }
+    case 1: {                // in a (cyclotomic Fp12); out w12_cyclo_sqr(a)
+        w12_copy(D, ga, q); w12_cyclo_sqr<S>(D, w, red); put(0);
+        break;
+    }
+    default: break;
+    }
+}
+#endif  // ZKV_PAIRED
+
+}  // namespace zkv
+#endif  // ZKV_SELFTEST_BODIES

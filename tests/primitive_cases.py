@@ -1,0 +1,567 @@
+"""Case generators, references and runners for the known-answer harness of the arithmetic primitives (zkv_diag_primitive,
+stylus_zkvm_verifiers_amd/csrc/zkv_selftest.h).  Shared by the GPU test (tests/test_device_primitives_gpu.py) and its CPU counterpart
+(tests/test_device_primitives_host.py), which runs the same cases through host builds of the same header (tests/host_sim).
+
+Operands are Montgomery-domain integers (R = 2^261 for Fp and Fr); expectations come from Python integers and, for Fp12 and G1, from
+oracle/spec_model.py.  Every generator puts its edge operands first (lane 0, both lanes of the first pair, the first group), again at the
+end of the first wavefront and the start of the second (lanes 63 / 64, across a pair / group boundary), and fills the rest at random."""
+import ctypes as C
+import os
+import random
+import subprocess
+
+import numpy as np
+
+import spec_model as m
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(HERE, '..', 'stylus_zkvm_verifiers_amd', 'csrc')
+P, RR = m.P, m.R
+RM = 1 << 261
+RI = pow(RM, -1, P)              # Fp: Montgomery value x represents x RI
+RIR = pow(RM, -1, RR)            # Fr
+M29 = (1 << 29) - 1
+WP = [0, 2, 4, 1, 3, 5]          # slot index -> power of w
+
+# (mapping, op) -> (in words, out words): include/zkv.h
+IO = {(0, 0): (24, 128), (0, 1): (24, 16), (0, 2): (16, 16), (0, 3): (8, 8), (0, 4): (32, 64), (0, 5): (24, 40), (0, 6): (8, 12), (0, 7): (64, 72),
+      (1, 0): (32, 80), (1, 1): (162, 18), (1, 2): (36, 18), (1, 3): (240, 11 * 96), (1, 4): (96, 192),
+      (2, 0): (240, 768), (2, 1): (96, 96), (3, 0): (240, 768), (3, 1): (96, 96)}
+PER_WAVE = {0: 64, 1: 32, 2: 4, 3: 1}
+
+
+def words(v, n=8): return [(v >> (32 * i)) & 0xffffffff for i in range(n)]
+def unwords(w): return sum(int(x) << (32 * i) for i, x in enumerate(w))
+def limbs9(v): return [(v >> (29 * i)) & M29 for i in range(8)] + [v >> 232]
+def val9(l): return sum(int(x) << (29 * i) for i, x in enumerate(l))
+def sval9(l): return sum((int(x) - (1 << 32) if int(x) >= (1 << 31) else int(x)) << (29 * i) for i, x in enumerate(l))
+
+
+def place_edges(edges, randoms, n, per_wave=64):
+    """n cases: the edges at the start, again just before and after the first wavefront boundary (when n reaches it), randoms elsewhere."""
+    out = list(edges[:n])
+    while len(out) < n:
+        out.append(next(randoms))
+    b = per_wave
+    if n >= b + len(edges) and len(edges) <= b:
+        out[b - len(edges) // 2:b - len(edges) // 2 + len(edges)] = edges
+    return out[:n]
+
+
+def gen_stream(f):
+    while True:
+        yield f()
+
+
+# ---------------------------------------------------------------- mapping 0: one value per lane
+def edge_fp2(): return [0, 1, 2, P - 1, P, P + 1, 2 * P - 2, 2 * P - 1, (P + 1) // 2, (1 << 253) - 1]
+def edge_fp4(): return edge_fp2() + [2 * P, 2 * P + 1, 3 * P, 3 * P + 1, 4 * P - 1]
+
+
+def lane_cases(op, n, rng):
+    e2, e4 = edge_fp2(), edge_fp4()
+    if op == 0:
+        edges = [[a, b, c] for a in e2 for b in (0, P, 2 * P - 1, a, (a + P) % (2 * P)) for c in (0, 2 * P - 1)]
+        rnd = gen_stream(lambda: [rng.choice(e2) if rng.random() < 0.2 else rng.randrange(2 * P) for _ in range(3)])
+        cs = place_edges(edges, rnd, n)
+        return [words(a) + words(b) + words(c) for a, b, c in cs]
+    if op == 1:
+        any256 = [0, (1 << 256) - 1, 1 << 255, (1 << 232) - 1, int('5' * 64, 16), int('a' * 64, 16)]
+        edges = [[a, b, rng.choice(e4 + any256)] for a in e4 for b in (0, 1, P - 1, 4 * P - 1, 2 * P - 1)] + [[4 * P - 1, 4 * P - 1, c] for c in any256]
+        rnd = gen_stream(lambda: [rng.randrange(4 * P), rng.randrange(4 * P), rng.randrange(1 << 256) if rng.random() < 0.5 else rng.randrange(4 * P)])
+        return [words(a) + words(b) + words(c) for a, b, c in place_edges(edges, rnd, n)]
+    if op == 2:
+        edges = [[x, y] for x in (0, 1, P - 1, P - 2, (1 << 253) - 1) for y in e2]
+        rnd = gen_stream(lambda: [rng.randrange(P), rng.randrange(2 * P)])
+        return [words(x) + words(y) for x, y in place_edges(edges, rnd, n)]
+    if op == 3:
+        edges = [[a] for a in e4 + [(1 << 256) - 1, 1 << 255, (1 << 256) - P, 5 * P, 5 * P + 1, (1 << 30) - 1, 1 << 30, (1 << 60) + 1]]
+        rnd = gen_stream(lambda: [rng.randrange(1 << 256) if rng.random() < 0.3 else rng.randrange(2 * P)])
+        return [words(a) for (a,) in place_edges(edges, rnd, n)]
+    if op == 4:
+        edges = [[a0, a1, b0, b1] for a0 in e2 for a1 in (0, P, 2 * P - 1) for b0, b1 in ((0, 4 * P - 1), (4 * P - 1, 4 * P - 1), (P, 2 * P))]
+        edges += [[a0, a1, 4 * P - 1, 3 * P] for a0 in (3 * P, 4 * P - 1) for a1 in (0, 4 * P - 1)]
+        rnd = gen_stream(lambda: [rng.randrange(2 * P), rng.randrange(2 * P), rng.randrange(4 * P), rng.randrange(4 * P)] if rng.random() < 0.7
+                         else [rng.randrange(4 * P) for _ in range(4)])
+        return [words(a0) + words(a1) + words(b0) + words(b1) for a0, a1, b0, b1 in place_edges(edges, rnd, n)]
+    if op == 5:
+        er = [0, 1, RR - 1, RR - 2, (RR + 1) // 2, (1 << 253) - 1]
+        ex = [0, 1, RR - 1, RR, RR + 1, 2 * RR, 5 * RR - 1, (1 << 256) - 1, (1 << 256) - RR, 1 << 255]
+        edges = [[a, b, x] for a in er for b in er[:4] for x in ex[:3]] + [[rng.randrange(RR), rng.randrange(RR), x] for x in ex]
+        rnd = gen_stream(lambda: [rng.randrange(RR), rng.randrange(RR), rng.randrange(1 << 256)])
+        return [words(a) + words(b) + words(x) for a, b, x in place_edges(edges, rnd, n)]
+    if op == 6:
+        u = m.U
+        nn, a1, b2 = 2 * u + 1, 6 * u * u + 2 * u, 6 * u * u + 4 * u + 1
+        base = [0, 1, RR - 1, RR, RR + 1, (1 << 256) - 1, (1 << 255), (1 << 128) - 1, 1 << 128]
+        for v in (nn, a1, b2, a1 + nn, b2 - nn):
+            for j in (1, 2, 3, 1 << 64, (1 << 126) // v if v < (1 << 126) else 1):
+                for d in (-1, 0, 1):
+                    if 0 <= j * v + d < (1 << 256):
+                        base.append(j * v + d)
+        edges = [[k] for k in base]
+        rnd = gen_stream(lambda: [rng.randrange(1 << 256) if rng.random() < 0.5 else rng.randrange(RR)])
+        return [words(k) for (k,) in place_edges(edges, rnd, n)]
+    if op == 7:
+        return g1_cases(n, rng)
+    raise ValueError(op)
+
+
+def _mont_rep(v, rng, loose=True):
+    x = v * RM % P
+    return x + P if loose and rng.random() < 0.3 else x
+
+
+def _jac(pt, rng):
+    """affine point (or None) -> Jacobian words with a random z; infinity has z = 0 (or p)."""
+    if pt is None:
+        return words(_mont_rep(1, rng)) + words(_mont_rep(1, rng)) + words(rng.choice([0, P]))
+    z = rng.choice([1, rng.randrange(1, P)])
+    x, y = pt[0] * z * z % P, pt[1] * z * z * z % P
+    return words(_mont_rep(x, rng)) + words(_mont_rep(y, rng)) + words(_mont_rep(z, rng))
+
+
+_G1_POOL = None
+
+
+def _g1_pool():
+    global _G1_POOL
+    if _G1_POOL is None:
+        r = random.Random(0x61)
+        g = (1, 2)
+        _G1_POOL = [g, m.g1_neg(g), m.g1_mul(g, 2), m.g1_mul(g, RR - 1)] + [m.g1_mul(g, r.randrange(1, RR)) for _ in range(12)]
+    return _G1_POOL
+
+
+def g1_cases(n, rng):
+    """(P, Q affine, T): P + P, P + (-P), inf + P, P + inf and generic sums, mixed so that lanes of one wavefront take different branches."""
+    pool = _g1_pool()
+
+    def case(kind):
+        p = rng.choice(pool)
+        q = rng.choice(pool)
+        t = rng.choice(pool)
+        if kind == 1: q = t = p                                     # P + P
+        elif kind == 2: q = t = m.g1_neg(p)                         # P + (-P)
+        elif kind == 3: p = None                                    # inf + P
+        elif kind == 4: t = None                                    # P + inf (g1j_add)
+        elif kind == 5: p = None; t = None
+        return (p, q, t)
+    edges = [case(k) for k in (1, 2, 3, 4, 5, 0, 1, 2, 0, 3)]
+    cs = place_edges(edges, gen_stream(lambda: case(rng.choice([0, 0, 1, 2, 3, 4]))), n)
+    out = []
+    for p, q, t in cs:
+        out.append(_jac(p, rng) + words(_mont_rep(q[0], rng)) + words(_mont_rep(q[1], rng)) + _jac(t, rng))
+    return out
+
+
+def _fp_of(w, k): return unwords(w[8 * k:8 * k + 8])
+
+
+def _jac_to_aff(w):
+    x, y, z = (_fp_of(w, k) * RI % P for k in range(3))
+    if z == 0:
+        return None
+    zi = pow(z, -1, P)
+    return (x * zi * zi % P, y * zi * zi * zi % P)
+
+
+def check_lane(op, ins, outs):
+    bad = []
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        try:
+            _check_lane_one(op, wi, wo)
+        except AssertionError as e:
+            bad.append((idx, str(e)))
+            if len(bad) > 5:
+                break
+    assert not bad, 'op %d: %d failing cases, first %s' % (op, len(bad), bad[:3])
+
+
+def _check_lane_one(op, wi, wo):
+    f = lambda k: _fp_of(wi, k)
+    o = lambda k: _fp_of(wo, k)
+    if op == 0:
+        a, b, c = f(0), f(1), f(2)
+        want = [a + b, a - b, -a, 2 * a, a * pow(2, -1, P), a + b, c + a, a - b, c - a, a + b, b + c, c + a, a - b, b - c, c - a]
+        names = ['add', 'sub', 'neg', 'dbl', 'half', 'add_x2.0', 'add_x2.1', 'sub_x2.0', 'sub_x2.1', 'add_n.0', 'add_n.1', 'add_n.2', 'sub_n.0', 'sub_n.1', 'sub_n.2']
+        for k, (w, nm) in enumerate(zip(want, names)):
+            assert o(k) < 2 * P and (o(k) - w) % P == 0, (nm, hex(a), hex(b), hex(c), hex(o(k)))
+        assert wo[120] == (1 if a % P == 0 else 0), ('is_zero', hex(a))
+        assert wo[121] == (1 if (a - b) % P == 0 else 0), ('eq', hex(a), hex(b))
+        assert list(wo[122:128]) == [0] * 6
+    elif op == 1:
+        a, b, c = f(0), f(1), f(2)
+        assert o(0) < 2 * P and (o(0) - a * b * RI) % P == 0, ('mul', hex(a), hex(b), hex(o(0)))
+        assert o(1) < 2 * P and (o(1) - c * c * RI) % P == 0, ('sqr', hex(c), hex(o(1)))
+    elif op == 2:
+        x, y = f(0), f(1)
+        assert o(0) < 2 * P and (o(0) - x * RM) % P == 0, ('from_raw', hex(x), hex(o(0)))
+        assert o(1) == y * RI % P, ('to_raw', hex(y), hex(o(1)))
+    elif op == 3:
+        a = f(0)
+        v = a * RI % P
+        want = pow(v, -1, P) * RM % P if v else 0
+        assert o(0) < 2 * P and (o(0) - want) % P == 0, ('inv', hex(a), hex(o(0)))
+    elif op == 4:
+        a0, a1, b0, b1 = f(0), f(1), f(2), f(3)
+        r = [o(k) for k in range(8)]
+        assert all(x < 2 * P for x in r[:2]), ('f2_mul bound', [hex(x) for x in r[:2]])
+        assert (r[0] - (a0 * b0 - a1 * b1) * RI) % P == 0 and (r[1] - (a0 * b1 + a1 * b0) * RI) % P == 0, ('f2_mul', hex(a0), hex(a1), hex(b0), hex(b1))
+        if max(a0, a1) < 2 * P:
+            assert all(x < 2 * P for x in r[2:8]), ('f2 bound', [hex(x) for x in r[2:8]])
+            assert (r[2] - (a0 * a0 - a1 * a1) * RI) % P == 0 and (r[3] - 2 * a0 * a1 * RI) % P == 0, ('f2_sqr', hex(a0), hex(a1))
+            assert (r[4] - (9 * a0 - a1)) % P == 0 and (r[5] - (9 * a1 + a0)) % P == 0, ('f2_mul_xi', hex(a0), hex(a1))
+            v0, v1 = a0 * RI % P, a1 * RI % P
+            nrm = (v0 * v0 + v1 * v1) % P
+            w0, w1 = (v0 * pow(nrm, -1, P) % P, -v1 * pow(nrm, -1, P) % P) if nrm else (0, 0)
+            assert (r[6] - w0 * RM) % P == 0 and (r[7] - w1 * RM) % P == 0, ('f2_inv', hex(a0), hex(a1))
+    elif op == 5:
+        a, b, x = f(0), f(1), f(2)
+        r = [o(k) for k in range(5)]
+        va = a * RIR % RR
+        want = [a * b * RIR % RR, (a + b) % RR, (a - b) % RR, (pow(va, -1, RR) * RM % RR) if va else 0, (x % RR) * RM % RR]
+        for k, nm in enumerate(['fr_mul', 'fr_add', 'fr_sub', 'fr_inv', 'fr_from_raw_reduce']):
+            assert r[k] == want[k], (nm, hex(a), hex(b), hex(x), hex(r[k]), hex(want[k]))          # canonical, not merely congruent
+    elif op == 6:
+        k = f(0)
+        m1, n1, m2, n2 = unwords(wo[0:5]), wo[5], unwords(wo[6:11]), wo[11]
+        assert n1 in (0, 1) and n2 in (0, 1) and m1 < (1 << 128) and m2 < (1 << 128), ('glv bound', hex(k), hex(m1), hex(m2))
+        k1, k2 = (-m1 if n1 else m1), (-m2 if n2 else m2)
+        assert (k1 + k2 * GLV_LAMBDA - k) % RR == 0, ('glv identity', hex(k))
+    elif op == 7:
+        p = _jac_to_aff(wi[0:24]); q = (_fp_of(wi, 3) * RI % P, _fp_of(wi, 4) * RI % P); t = _jac_to_aff(wi[40:64])
+        assert all(x < 2 * P for x in [o(k) for k in range(9)]), 'g1 bound'
+        assert _jac_to_aff(wo[0:24]) == m.g1_add(p, p), ('g1j_dbl', p)
+        assert _jac_to_aff(wo[24:48]) == m.g1_add(p, q), ('g1j_add_affine', p, q)
+        assert _jac_to_aff(wo[48:72]) == m.g1_add(p, t), ('g1j_add', p, t)
+
+
+GLV_LAMBDA = (6 * m.U * m.U + 2 * m.U) * pow(2 * m.U + 1, -1, RR) % RR       # a1 - n lambda = 0 (mod r): the basis of zkv_scalar.h glv_split
+
+
+# ---------------------------------------------------------------- mapping 1: lane pairs (Fp2, L9)
+def pair_f2_cases(n, rng):
+    e4 = [0, 1, P - 1, P, P + 1, 2 * P - 1, 2 * P, 2 * P + 1, 3 * P, 4 * P - 1]
+    e2 = [v for v in e4 if v < 2 * P]
+    edges = [[a0, a1, b0, b1] for a0 in e4 for a1 in (0, P, 4 * P - 1) for b0, b1 in ((0, 4 * P - 1), (4 * P - 1, 4 * P - 1), (P, 2 * P))]
+    edges += [[a0, a1, b0, b1] for a0 in e2 for a1 in e2[::2] for b0, b1 in ((2 * P - 1, 0), (0, 2 * P - 1))]
+    rnd = gen_stream(lambda: [rng.randrange(4 * P) for _ in range(4)] if rng.random() < 0.5 else [rng.randrange(2 * P) for _ in range(4)])
+    cs = place_edges(edges, rnd, n, 32)
+    return [words(a0) + words(a1) + words(b0) + words(b1) for a0, a1, b0, b1 in cs]
+
+
+def check_pair_f2(ins, outs):
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        a0, a1, b0, b1 = (_fp_of(wi, k) for k in range(4))
+        r = [_fp_of(wo, k) for k in range(10)]
+        ctx = (idx, hex(a0), hex(a1), hex(b0), hex(b1))
+        assert r[0] < 2 * P and r[1] < 2 * P, ('mul bound',) + ctx
+        assert (r[0] - (a0 * b0 - a1 * b1) * RI) % P == 0 and (r[1] - (a0 * b1 + a1 * b0) * RI) % P == 0, ('mul',) + ctx
+        if max(a0, a1, b0, b1) < 2 * P:
+            assert all(x < 2 * P for x in r), ('bound',) + ctx
+            assert (r[2] - (a0 * a0 - a1 * a1) * RI) % P == 0 and (r[3] - 2 * a0 * a1 * RI) % P == 0, ('sqr',) + ctx
+            assert (r[4] - (9 * a0 - a1)) % P == 0 and (r[5] - (9 * a1 + a0)) % P == 0, ('xi',) + ctx
+            assert (r[6] - (a0 + b0)) % P == 0 and (r[7] - (a1 + b1)) % P == 0, ('add',) + ctx
+            assert (r[8] - (a0 - b0)) % P == 0 and (r[9] - (a1 - b1)) % P == 0, ('sub',) + ctx
+
+
+# (coefficients of the even lane, of the odd lane, c, which terms are lazy three-term sums): the call sites of zkv_tower_mem.h /
+# zkv_tower_wide.h, with the per-lane signs (k1 = -1 / +1, k3 = 3 / -3) they use
+LINCOMB_SITES = [((1, 9, -1), (1, 9, 1), 4, ()), ((3, -30, 3, -2), (3, -30, -3, -2), 72, ()), ((6, 2), (6, 2), 1, ()),
+                 ((54, -6, 2), (54, 6, 2), 14, ()), ((1, 9, -1), (1, 9, 1), 48, (1, 2)), ((1, 9, -1), (1, 9, 1), 8, (0,)), ((1,), (1,), 8, (0,)),
+                 ((1, 9, -1, -1), (1, 9, 1, -1), 52, (1, 2)), ((1, 9, -1, -1), (1, 9, 1, -1), 12, (0,)), ((1, -1), (1, -1), 12, (0,)),
+                 ((0, 6, 0, 2), (0, 6, 0, 2), 72, ()), ((0, 54, 6, 2), (0, 54, -6, 2), 72, ()), ((3, -30, 3, -2), (0, 6, 0, 2), 72, ()),
+                 ((1, 1), (1, 1), 1, ()), ((-1,), (-1,), 3, ()), ((1, 9, 1, -1), (1, 9, -1, -1), 12, (0,)),
+                 ((2, 2, 18, 18, -2, 2, 0, 0), (2, 2, 18, 18, 2, -2, 0, 0), 20, ()), ((1, 9, -1, 9, -1), (1, 9, 1, 9, 1), 8, ())]
+
+
+def lincomb_cases(n, rng):
+    edge = [0, 1, P - 1, P, P + 1, 2 * P - 1, (1 << 232) - 1, 2 * P - 2]
+
+    def pick(): return rng.choice(edge) if rng.random() < 0.5 else rng.randrange(2 * P)
+
+    def lazy3():
+        sign = -1 if rng.random() < 0.7 else 1
+        x, y, z = (limbs9(pick()) for _ in range(3))
+        return [(a + sign * (b + c)) & 0xffffffff for a, b, c in zip(x, y, z)]
+
+    def one(site, rep):
+        ke, ko, c, lazy = site
+        w = [len(ke), c] + [k & 0xffffffff for k in ke] + [0] * (8 - len(ke)) + [k & 0xffffffff for k in ko] + [0] * (8 - len(ko))
+        for ks in (ke, ko):
+            terms = []
+            for j, k in enumerate(ks):
+                if j in lazy:
+                    terms += lazy3()
+                else:
+                    terms += limbs9(pick() if rep else (2 * P - 1 if k < 0 else 0))        # rep 0: the most negative combination
+            w += terms + [0] * (72 - len(terms))
+        return w
+    edges = [one(s, 0) for s in LINCOMB_SITES]
+    k = [0]
+
+    def rnd():
+        k[0] += 1
+        return one(LINCOMB_SITES[k[0] % len(LINCOMB_SITES)], k[0])
+    return place_edges(edges, gen_stream(rnd), n, 32)
+
+
+def check_lincomb(ins, outs):
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        nt, c = wi[0], wi[1]
+        for par in (0, 1):
+            ks = [int(np.int32(np.uint32(x))) for x in wi[2 + 8 * par:2 + 8 * par + nt]]
+            total = sum(k * sval9(wi[18 + 72 * par + 9 * j:18 + 72 * par + 9 * j + 9]) for j, k in enumerate(ks))
+            got = [int(x) for x in wo[9 * par:9 * par + 9]]
+            assert all(x <= M29 for x in got[:8]), (idx, par, ks, c, got)
+            v = val9(got)
+            assert v % P == total % P and v < P + (P >> 6), (idx, par, ks, c, hex(v))
+
+
+def l9mul_cases(n, rng):
+    big = [limbs9(2 * P - 1), [M29] * 8 + [(2 * P - 1) >> 232], limbs9(0), limbs9(P)]
+
+    def mcand():
+        x, y = (rng.choice(big) if rng.random() < 0.4 else limbs9(rng.randrange(2 * P)) for _ in range(2))
+        return [a + b for a, b in zip(x, y)]
+
+    def mplier(v=None): return limbs9(v if v is not None else rng.choice([0, P, 2 * P - 1, 4 * P - 1, 7 * P + (P >> 1), rng.randrange(4 * P), rng.randrange(8 * P - P // 10)]))
+    top = [M29 * 2 - 1] * 8 + [((2 * P - 1) >> 232) * 2]
+    edges = [top + top + mplier(7 * P + (P >> 1)) + mplier(7 * P + (P >> 1)), top + top + mplier(0) + mplier(7 * P + (P >> 1)),
+             limbs9(0) * 2 + mplier(0) * 2, top + limbs9(0) + mplier(4 * P - 1) + mplier(0)]
+    return place_edges(edges, gen_stream(lambda: mcand() + mcand() + mplier() + mplier()), n, 32)
+
+
+def check_l9mul(ins, outs):
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        A0, A1, B0, B1 = (val9(wi[9 * k:9 * k + 9]) for k in range(4))
+        r0, r1 = val9(wo[:9]), val9(wo[9:])
+        assert all(int(x) <= M29 for x in list(wo[:8]) + list(wo[9:17])), idx
+        assert r0 % P == (A0 * B0 - A1 * B1) * RI % P and r1 % P == (A0 * B1 + A1 * B0) * RI % P, idx
+        assert r0 < 2 * P and r1 < 2 * P, idx
+
+
+# ---------------------------------------------------------------- Fp12 (mappings 1-3)
+def slots_to_f12(slots):
+    """six Fp2 value-domain pairs in slot order -> spec_model's w-basis (12 Fp coefficients)"""
+    out = [0] * 12
+    for i, c in enumerate(slots):
+        out = [(x + y) % P for x, y in zip(out, m.f2_to_f12(c, WP[i]))]
+    return out
+
+
+def f12_to_slots(t):
+    slots = [None] * 6
+    for i in range(6):
+        k = WP[i]
+        a1 = t[k + 6] % P
+        slots[i] = ((t[k] + 9 * a1) % P, a1)
+    return slots
+
+
+def f12_words(slots_mont):
+    w = []
+    for c0, c1 in slots_mont:
+        w += words(c0) + words(c1)
+    return w
+
+
+def f12_from_words(w):
+    """96 words -> (raw Montgomery integers per component, value-domain w-basis element)"""
+    raw = [(unwords(w[16 * i:16 * i + 8]), unwords(w[16 * i + 8:16 * i + 16])) for i in range(6)]
+    return raw, slots_to_f12([(a * RI % P, b * RI % P) for a, b in raw])
+
+
+def _mont_words_of(t, rng, loose):
+    out = []
+    for c0, c1 in f12_to_slots(t):
+        out.append((_mont_rep(c0, rng, loose), _mont_rep(c1, rng, loose)))
+    return out
+
+
+def f12_conj(t): return [x if k % 2 == 0 else -x % P for k, x in enumerate(t)]
+
+
+_FROB = {}
+
+
+def f12_frob(t, k):
+    """pi^k(a) = a^(p^k): linear over Fp, so sum_j t_j (w^(p^k))^j, with the powers of w computed once by f12pow"""
+    if k not in _FROB:
+        wk = m.f12pow([0, 1] + [0] * 10, P ** k)
+        pw = [m.F12_ONE]
+        for _ in range(11):
+            pw.append(m.f12mul(pw[-1], wk))
+        _FROB[k] = pw
+    out = [0] * 12
+    for j, x in enumerate(t):
+        if x:
+            out = [(o + x * y) % P for o, y in zip(out, _FROB[k][j])]
+    return out
+
+
+def line_f12(c0, c3, c4): return slots_to_f12([c0, (0, 0), (0, 0), c3, c4, (0, 0)])
+
+
+_CYCLO = None
+
+
+def cyclotomic_pool():
+    """a handful of seeded elements of the cyclotomic subgroup, f^((p^6 - 1)(p^2 + 1))"""
+    global _CYCLO
+    if _CYCLO is None:
+        r = random.Random(0xC1C)
+        _CYCLO = []
+        for _ in range(4):
+            f = [r.randrange(P) for _ in range(12)]
+            _CYCLO.append(m.f12pow(f, (P ** 6 - 1) * (P ** 2 + 1)))
+    return _CYCLO
+
+
+def _f12_special(kind, rng):
+    if kind == 0:
+        return m.F12_ONE
+    if kind == 1:
+        return [0] * 12
+    if kind == 2:                                  # zero and one coefficients
+        return slots_to_f12([rng.choice([(0, 0), (1, 0), (0, 1), (P - 1, 0), (rng.randrange(P), rng.randrange(P))]) for _ in range(6)])
+    return [rng.randrange(P) for _ in range(12)]
+
+
+def f12_cases(n, rng):
+    """a b c0 c3 c4: random elements, elements with x + p coefficients, zero and one coefficients"""
+    def case(ka, kb):
+        a, b = _f12_special(ka, rng), _f12_special(kb, rng)
+        loose = rng.random() < 0.5
+        lines = [(_mont_rep(rng.randrange(P), rng, loose), _mont_rep(rng.randrange(P), rng, loose)) for _ in range(3)]
+        if rng.random() < 0.15:
+            lines[0] = (P if loose else 0, 0)
+        w = f12_words(_mont_words_of(a, rng, loose)) + f12_words(_mont_words_of(b, rng, rng.random() < 0.5))
+        for c in lines:
+            w += words(c[0]) + words(c[1])
+        return w
+    edges = [case(ka, kb) for ka, kb in ((0, 3), (3, 0), (2, 3), (3, 2), (2, 2), (1, 3), (3, 3), (0, 0))]
+    return place_edges(edges, gen_stream(lambda: case(3 if rng.random() < 0.7 else 2, 3 if rng.random() < 0.7 else 2)), n, 4)
+
+
+def cyclo_cases(n, rng):
+    pool = cyclotomic_pool()
+
+    def case():
+        a = rng.choice(pool)
+        if rng.random() < 0.3:
+            a = m.f12mul(a, rng.choice(pool))
+        return f12_words(_mont_words_of(a, rng, rng.random() < 0.6))
+    edges = [f12_words(_mont_words_of(m.F12_ONE, rng, False)), f12_words(_mont_words_of(m.F12_ONE, rng, True))] + \
+            [f12_words(_mont_words_of(c, rng, lo)) for c in pool for lo in (False, True)]
+    return place_edges(edges, gen_stream(case), n, 4)
+
+
+def _f12_out(wo, k):
+    raw, v = f12_from_words(wo[96 * k:96 * k + 96])
+    assert all(x < 2 * P for c in raw for x in c), ('bound', k, [hex(x) for c in raw for x in c if x >= 2 * P])
+    return v
+
+
+def f12_inputs(wi):
+    a = f12_from_words(wi[0:96])[1]
+    b = f12_from_words(wi[96:192])[1]
+    cs = [(unwords(wi[192 + 16 * j:200 + 16 * j]) * RI % P, unwords(wi[200 + 16 * j:208 + 16 * j]) * RI % P) for j in range(3)]
+    return a, b, cs
+
+
+def check_pair_f12(ins, outs):
+    names = ['f12m_mul', 'f12m_mul_conj', 'f12m_sqr', 'f12m_inv', 'f12m_frob1', 'f12m_frob2', 'f12m_frob3', 'f12m_mul_by_034', 'f12m_mul_by_134',
+             'f12l9_mul', 'f12l9_mul(conj_b)']
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        a, b, (c0, c3, c4) = f12_inputs(wi)
+        want = [m.f12mul(a, b), m.f12mul(a, f12_conj(b)), m.f12mul(a, a), None, f12_frob(a, 1), f12_frob(a, 2), f12_frob(a, 3),
+                m.f12mul(a, line_f12(c0, c3, c4)), m.f12mul(a, line_f12((1, 0), c3, c4)), m.f12mul(a, b), m.f12mul(a, f12_conj(b))]
+        for k, nm in enumerate(names):
+            got = _f12_out(wo, k)
+            if k == 3:
+                ok = (m.f12mul(got, a) == m.F12_ONE) if any(a) else not any(got)
+                assert ok, (idx, nm)
+            else:
+                assert got == want[k], (idx, nm)
+
+
+def check_cyclo(ins, outs, nout):
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        a = f12_from_words(wi[0:96])[1]
+        want = m.f12mul(a, a)
+        for k in range(nout):
+            assert _f12_out(wo, k) == want, (idx, k)
+
+
+def check_wide_f12(ins, outs):
+    names = ['w12_mul', 'w12_mul(conj_b)', 'w12_sqr', 'w12_mul_sparse', 'w12_mul_sparse(one)', 'w12_frob1', 'w12_frob2', 'w12_frob3']
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        a, b, (c0, c3, c4) = f12_inputs(wi)
+        want = [m.f12mul(a, b), m.f12mul(a, f12_conj(b)), m.f12mul(a, a), m.f12mul(a, line_f12(c0, c3, c4)), m.f12mul(a, line_f12((1, 0), c3, c4)),
+                f12_frob(a, 1), f12_frob(a, 2), f12_frob(a, 3)]
+        for k, nm in enumerate(names):
+            assert _f12_out(wo, k) == want[k], (idx, nm)
+
+
+# ---------------------------------------------------------------- runners
+def as_array(cases, mapping, op):
+    iw = IO[(mapping, op)][0]
+    a = np.array(cases, dtype=np.uint32).reshape(len(cases), iw)
+    return np.ascontiguousarray(a)
+
+
+def _ptr(a): return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def run_device(lib, mapping, op, ins, device=0):
+    ins = as_array(ins, mapping, op)
+    out = np.zeros((len(ins), IO[(mapping, op)][1]), dtype=np.uint32)
+    rc = lib.zkv_diag_primitive(device, mapping, op, len(ins), _ptr(ins), _ptr(out))
+    assert rc == 0, rc
+    return out
+
+
+_HOST = {}
+
+
+def host_lib(paired):
+    """the host build of zkv_selftest.h: tests/host_sim/host_sim_selftest.cpp (mapping 0) or host_sim_selftest_pair.cpp (mappings 1-3)"""
+    name = 'host_sim_selftest_pair' if paired else 'host_sim_selftest'
+    if name not in _HOST:
+        src = os.path.join(HERE, 'host_sim', name + '.cpp')
+        lib = os.path.join(HERE, 'host_sim', 'lib%s.so' % name)
+        deps = [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
+        if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(d) for d in deps):
+            subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-pthread', '-Wno-unknown-pragmas', '-o', lib, src])
+        L = C.CDLL(lib)
+        L.hs_selftest.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        _HOST[name] = L
+    return _HOST[name]
+
+
+def run_host(mapping, op, ins):
+    ins = as_array(ins, mapping, op)
+    out = np.zeros((len(ins), IO[(mapping, op)][1]), dtype=np.uint32)
+    assert host_lib(mapping != 0).hs_selftest(mapping, op, len(ins), _ptr(ins), _ptr(out)) == 0
+    return out
+
+
+def cases_for(mapping, op, n, seed):
+    rng = random.Random(seed * 1000 + mapping * 10 + op)
+    if mapping == 0:
+        return lane_cases(op, n, rng)
+    if mapping == 1:
+        return [pair_f2_cases, lincomb_cases, l9mul_cases, f12_cases, cyclo_cases][op](n, rng)
+    return [f12_cases, cyclo_cases][op](n, rng)
+
+
+def check(mapping, op, ins, outs):
+    ins = [list(map(int, r)) for r in as_array(ins, mapping, op)]
+    outs = [list(map(int, r)) for r in outs]
+    if mapping == 0:
+        return check_lane(op, ins, outs)
+    if mapping == 1:
+        return [check_pair_f2, check_lincomb, check_l9mul, check_pair_f12, lambda i, o: check_cyclo(i, o, 2)][op](ins, outs)
+    return [check_wide_f12, lambda i, o: check_cyclo(i, o, 1)][op](ins, outs)

@@ -1,0 +1,122 @@
+"""Known-answer tests of the field, tower and G1 primitives ON THE DEVICE (zkv_diag_primitive): the code the verify kernels run -- carry
+builtins, the non-inlined f2_mul_ni / l9_mul_ni leaves, the DPP exchange inside a lane pair, Fp12 values in LDS, the wide routines with
+several cases per wavefront -- at the edges of each primitive's contract, against Python integers and oracle/spec_model.py.  Where the
+host build of the same harness (tests/host_sim/host_sim_selftest*.cpp) can be compiled, the device words must also be bit-identical to
+the host build's words for the same cases.  Case generators and references: tests/primitive_cases.py."""
+import functools
+import subprocess
+
+import numpy as np
+import pytest
+
+import primitive_cases as pc
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module')
+def lib():
+    import stylus_zkvm_verifiers_amd as z
+    from stylus_zkvm_verifiers_amd import diag_primitive
+    assert z.device_count() >= 1, 'no gfx950 device'
+    return diag_primitive.lib()
+
+
+@functools.lru_cache(maxsize=None)
+def _host_available(paired):
+    try:
+        pc.host_lib(paired)
+        return True
+    except (OSError, subprocess.CalledProcessError):         # no host compiler: the device results are still checked against Python
+        return False
+
+
+def run(lib, mapping, op, n, same_as_host=None, seed=7):
+    """one call with all n cases of the op; checks the results, and the first `same_as_host` (default all) against the host build"""
+    ins = pc.cases_for(mapping, op, n, seed)
+    out = pc.run_device(lib, mapping, op, ins)
+    pc.check(mapping, op, ins, out)
+    if _host_available(mapping != 0):
+        k = n if same_as_host is None else min(n, same_as_host)
+        host = pc.run_host(mapping, op, ins[:k])
+        diff = np.nonzero((host != out[:k]).any(axis=1))[0]
+        assert len(diff) == 0, 'device and host words differ for cases %s' % list(diff[:8])
+    return out
+
+
+# ---------------------------------------------------------------- one value per lane (k_selftest_lane)
+def test_lane_fp_linear_ops(lib):
+    run(lib, 0, 0, 64 * 64 + 1)
+
+
+def test_lane_fp_mul_and_sqr(lib):
+    run(lib, 0, 1, 64 * 64 + 1)
+
+
+def test_lane_fp_from_raw_to_raw(lib):
+    run(lib, 0, 2, 64 * 16 + 1)
+
+
+def test_lane_fp_inv(lib):
+    run(lib, 0, 3, 64 * 32 + 1)
+
+
+def test_lane_fp2_products_and_inverse(lib):
+    run(lib, 0, 4, 64 * 48 + 1)
+
+
+def test_lane_fr_ops(lib):
+    run(lib, 0, 5, 64 * 32 + 1)
+
+
+def test_lane_glv_split(lib):
+    run(lib, 0, 6, 64 * 48 + 1)
+
+
+def test_lane_g1_jacobian_ops(lib):
+    run(lib, 0, 7, 64 * 16 + 1)
+
+
+def test_small_batches_are_padded(lib):
+    """1 and 31 cases (the rest of the wavefront, pair block or group runs on zero operands and is discarded)"""
+    for mapping, op in ((0, 1), (0, 7), (1, 0), (1, 3), (2, 1), (3, 1)):
+        for n in (1, 31) if mapping < 2 else (1, 5):
+            run(lib, mapping, op, n, seed=n)
+
+
+# ---------------------------------------------------------------- lane pairs (k_selftest_pair)
+def test_pair_fp2_ops_through_the_dpp_exchange(lib):
+    run(lib, 1, 0, 32 * 64 + 1, same_as_host=512)
+
+
+def test_pair_l9_lincomb_at_every_call_site(lib):
+    run(lib, 1, 1, 32 * 32 + 1)
+
+
+def test_pair_l9_mul(lib):
+    run(lib, 1, 2, 32 * 32 + 1, same_as_host=512)
+
+
+def test_pair_fp12_routines_in_lds(lib):
+    run(lib, 1, 3, 32 * 3 + 1)
+
+
+def test_pair_cyclotomic_squarings(lib):
+    run(lib, 1, 4, 32 * 2 + 1)
+
+
+# ---------------------------------------------------------------- wide groups (k_selftest_wide_s1 / _s4)
+def test_wide_sixteen_lanes_fp12_routines(lib):
+    run(lib, 2, 0, 4 * 8 + 1)
+
+
+def test_wide_sixteen_lanes_cyclotomic_squaring(lib):
+    run(lib, 2, 1, 4 * 8 + 1)
+
+
+def test_wide_one_wavefront_fp12_routines(lib):
+    run(lib, 3, 0, 9)
+
+
+def test_wide_one_wavefront_cyclotomic_squaring(lib):
+    run(lib, 3, 1, 9)
