@@ -20,6 +20,7 @@
 #include "../../include/zkv_groth16_set.h"
 #include "../../include/zkv_sp1_gateway.h"
 #include "../../include/zkv_plonk_keys.h"
+#include "../../include/zkv_plonk_set.h"
 #include "../../include/zkv_diag_primitive.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
@@ -94,6 +95,12 @@ struct zkv_ctx {
     PlonkKeyRaw pk_raw; uint8_t pk_g2[256] = {0}, plonk_hash[32] = {0};
     PlonkKey* d_pkey = nullptr;
     uint32_t* d_plonk_tab = nullptr;                           // per-proof window tables of the PLONK stage (PLONK_TAB_WORDS words per proof in flight)
+    // ZKV_VM_PLONK_SET (zkv_plonk_set.h): every key's parsed header and points, its two G2 points (256 bytes per key in ps_g2), and the
+    // largest nb_public and n_c (the row strides).  On the device: the keys' PlonkKey array in d_pkey, one VkTables per key in d_gs_tab
+    // with its GsetKey in d_gs_key (what the Groth16 sets' Miller kernels read), and a validity word per key in d_ps_ok.  A call reuses
+    // the Groth16 sets' partition buffers (gs_totals, gs_start, mx[3..9]).
+    std::vector<PlonkKeyRaw> ps_raw; std::vector<uint8_t> ps_g2; uint32_t ps_nb_max = 0, ps_nc_max = 0;
+    uint32_t* d_ps_ok = nullptr;
     // Aggregate check (zkv_agg.h, zkv_ctx_set_aggregate_check): key tables, per-proof rows, the pseudo-proofs' workspace (one per
     // sub-batch), their statuses and the counters {sub-batches checked, sub-batches failed}
     bool agg_on = false, agg_key_ok = false;
@@ -297,7 +304,7 @@ static void ctx_free_device(zkv_ctx* c) {
                      (void**)&c->d_agg_tab, (void**)&c->d_agg, (void**)&c->ws2.prep, (void**)&c->ws2.norm, (void**)&c->ws2.f, (void**)&c->ws2.fe,
                      (void**)&c->ws2.flags, (void**)&c->ws2.g2bad, (void**)&c->d_status2, (void**)&c->d_agg_cnt, (void**)&c->ws3.prep, (void**)&c->ws3.flags,
                      (void**)&c->ws3.g2bad, (void**)&c->d_status3, (void**)&c->d_agg_idx, (void**)&c->d_ltab, (void**)&c->d_lwin, (void**)&c->d_lsig,
-                     (void**)&c->d_gs_tab, (void**)&c->d_gs_key, (void**)&c->d_gs_rows, (void**)&c->d_gs_win};
+                     (void**)&c->d_gs_tab, (void**)&c->d_gs_key, (void**)&c->d_gs_rows, (void**)&c->d_gs_win, (void**)&c->d_ps_ok};
     for (void** p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
     c->ws2.cap = 0; c->ws3 = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0}; c->agg_cap = 0; c->agg_key_ok = false;
     for (int k = 0; k < 6; k++) { if (c->hb[k]) (void)hipFree(c->hb[k]); c->hb[k] = nullptr; c->hb_cap[k] = 0; }
@@ -313,6 +320,7 @@ static void ctx_free_device(zkv_ctx* c) {
 }
 
 static int gset_device_setup(zkv_ctx* c);
+static int pset_device_setup(zkv_ctx* c);
 // Lazily creates the streams, the VK tables (set-up kernels) and the events; the per-chunk workspace comes from ctx_reserve().
 static int ctx_device_setup(zkv_ctx* c) {
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -329,6 +337,7 @@ static int ctx_device_setup(zkv_ctx* c) {
         HIP_TRY(hipEventCreateWithFlags(&c->ev_decoded[b], hipEventDisableTiming));
     }
     if (c->vm == ZKV_VM_GROTH16_SET) return gset_device_setup(c);
+    if (c->vm == ZKV_VM_PLONK_SET) return pset_device_setup(c);
     if (c->vm != ZKV_VM_BN254 && c->vm != ZKV_VM_MIXED && c->vm != ZKV_VM_SP1_GATEWAY) {
         VkRaw raw;
         if (c->vm == ZKV_VM_RISC0 || c->vm == ZKV_VM_RISC0_SET) host::fill_vk_risc0(raw, c->control_root_0, c->control_root_1, c->control_id);
@@ -515,7 +524,7 @@ static int ctx_reserve(zkv_ctx* c, size_t want) {
         hipMalloc(&c->d_len, sizeof(uint32_t) * cap) != hipSuccess || hipMalloc(&c->d_pvlen, sizeof(uint32_t) * cap) != hipSuccess ||
         hipMalloc(&c->d_kind, cap) != hipSuccess || hipMalloc(&c->d_cdoff[0], sizeof(uint64_t) * (cap + 1)) != hipSuccess ||
         hipMalloc(&c->d_cdoff[1], sizeof(uint64_t) * (cap + 1)) != hipSuccess ||
-        (is_plonk(c) && hipMalloc(&c->d_plonk_tab, sizeof(uint32_t) * PLONK_TAB_WORDS * cap) != hipSuccess)) {
+        ((is_plonk(c) || c->vm == ZKV_VM_PLONK_SET) && hipMalloc(&c->d_plonk_tab, sizeof(uint32_t) * PLONK_TAB_WORDS * cap) != hipSuccess)) {
         (void)hipGetLastError();
         return ZKV_ERR_OOM;
     }
@@ -2284,27 +2293,36 @@ static int plonk_ready(zkv_ctx* c, size_t n, size_t* chunk) {
     *chunk = c->ws.cap < hc ? c->ws.cap : hc;
     return rc;
 }
-ZKV_EXPORT zkv_ctx* zkv_plonk_ctx_create(const uint8_t* vk, size_t vk_len, int device) {
-    if (!vk || vk_len < 7 * 32) return nullptr;
+// A key in zkv_plonk_keys.h's layout: false on its rules (length, n_c > 1, nb_public > MAX, oversized header words)
+static bool plonk_parse_key(const uint8_t* vk, size_t vk_len, PlonkKeyRaw& raw, uint8_t g2[256]) {
+    if (!vk || vk_len < 7 * 32) return false;
     uint32_t w[7][8];
     for (int k = 0; k < 7; k++) host::be_to_limbs(w[k], vk + 32 * k);
     auto below = [](const uint32_t* x, int limbs) { for (int i = limbs; i < 8; i++) if (x[i]) return false; return true; };
     // size < 2^64; nb_public, n_c and cci one limb each (the SP1 parser reads limb 0 alone; this one checks the others)
-    if (!below(w[0], 2) || !below(w[4], 1) || !below(w[5], 1) || !below(w[6], 1)) return nullptr;
-    if (w[5][0] > 1 || w[4][0] > ZKV_PLONK_MAX_PUBLIC) return nullptr;
+    if (!below(w[0], 2) || !below(w[4], 1) || !below(w[5], 1) || !below(w[6], 1)) return false;
+    if (w[5][0] > 1 || w[4][0] > ZKV_PLONK_MAX_PUBLIC) return false;
     const size_t n_c = w[5][0];
-    if (vk_len != 7 * 32 + (8 + n_c) * 64 + 256) return nullptr;
+    if (vk_len != 7 * 32 + (8 + n_c) * 64 + 256) return false;
+    memset(&raw, 0, sizeof raw);
+    memcpy(raw.size, w[0], 32); memcpy(raw.size_inv, w[1], 32); memcpy(raw.gen, w[2], 32); memcpy(raw.coset, w[3], 32);
+    raw.nb_public = w[4][0]; raw.n_c = w[5][0]; raw.cci = w[6][0];
+    for (size_t p = 0; p < 8 + n_c; p++) {
+        host::be_to_limbs(raw.pts[p][0], vk + 224 + 64 * p); host::be_to_limbs(raw.pts[p][1], vk + 256 + 64 * p);
+    }
+    memcpy(g2, vk + 224 + 64 * (8 + n_c), 256);
+    return true;
+}
+ZKV_EXPORT zkv_ctx* zkv_plonk_ctx_create(const uint8_t* vk, size_t vk_len, int device) {
+    PlonkKeyRaw raw;
+    uint8_t g2[256];
+    if (!plonk_parse_key(vk, vk_len, raw, g2)) return nullptr;
     zkv_ctx* c = new (std::nothrow) zkv_ctx();
     if (!c) return nullptr;
     c->vm = ZKV_VM_PLONK; c->device = device; c->initialized = true;
     memset(&c->consts, 0, sizeof c->consts);
-    memset(&c->pk_raw, 0, sizeof c->pk_raw);
-    memcpy(c->pk_raw.size, w[0], 32); memcpy(c->pk_raw.size_inv, w[1], 32); memcpy(c->pk_raw.gen, w[2], 32); memcpy(c->pk_raw.coset, w[3], 32);
-    c->pk_raw.nb_public = w[4][0]; c->pk_raw.n_c = w[5][0]; c->pk_raw.cci = w[6][0];
-    for (size_t p = 0; p < 8 + n_c; p++) {
-        host::be_to_limbs(c->pk_raw.pts[p][0], vk + 224 + 64 * p); host::be_to_limbs(c->pk_raw.pts[p][1], vk + 256 + 64 * p);
-    }
-    memcpy(c->pk_g2, vk + 224 + 64 * (8 + n_c), 256);
+    c->pk_raw = raw;
+    memcpy(c->pk_g2, g2, 256);
     return c;
 }
 ZKV_EXPORT int zkv_plonk_key_shape(const zkv_ctx* c, size_t* nb_public, size_t* n_commitments, size_t* proof_bytes) {
@@ -2726,11 +2744,191 @@ ZKV_EXPORT int zkv_groth16_set_vk_x_batch(zkv_ctx* c, size_t n, const uint32_t* 
     return ZKV_OK;
 }
 
+// ------------------------------------------------------------------ PLONK key sets (zkv_plonk_set.h)
+// No reference counterpart: parity unpinned.  The Groth16 sets' partition by key with 64-slot key groups (zkv_gset_layout.h pset_choose),
+// PREP with the key of each wavefront (k_plonk_set.hip), the Groth16 sets' Miller loops with every key's [1]_2 / [tau]_2 in the gamma /
+// delta slots of its VkTables, the single-key final exponentiation, and the Groth16 sets' return to the caller's order.
+static size_t pset_proof_stride(const zkv_ctx* c) { return (size_t)32 * (24 + 3 * c->ps_nc_max); }
+static size_t pset_input_stride(const zkv_ctx* c) { return (size_t)32 * c->ps_nb_max; }
+// Host batches stage the public inputs of a chunk next to the proofs: at most LONG_STAGE_BYTES, sized by the set's largest nb_public.
+static size_t pset_host_chunk(const zkv_ctx* c) {
+    const size_t per = pset_input_stride(c), cap = chunk_capacity();
+    if (!per) return cap;
+    size_t lim = 64;
+    while (lim < cap && 2 * lim * per <= LONG_STAGE_BYTES) lim *= 2;
+    return lim < cap ? lim : cap;
+}
+// Set-up of every key whatever K is: the VkTables of its two G2 points (k_gset.hip's kernels, grid y = key; the VkRaw the single-key PLONK
+// path builds), then its PlonkKey (24 MB) and validity word (k_plonk_set.hip).
+static int pset_device_setup(zkv_ctx* c) {
+    const uint32_t K = (uint32_t)c->ps_raw.size();
+    std::vector<VkRaw> raw(K);
+    std::vector<GsetKey> keys(K);
+    for (uint32_t k = 0; k < K; k++) {
+        memset(&raw[k], 0, sizeof raw[k]);
+        const uint8_t* g2 = c->ps_g2.data() + 256 * (size_t)k;
+        const int perm[4] = {1, 0, 3, 2};
+        for (int q = 0; q < 4; q++) { host::be_to_limbs(raw[k].gamma[q], g2 + 32 * perm[q]); host::be_to_limbs(raw[k].delta[q], g2 + 128 + 32 * perm[q]); }
+    }
+    HIP_TRY(hipMalloc(&c->d_gs_tab, sizeof(VkTables) * K));
+    HIP_TRY(hipMemsetAsync(c->d_gs_tab, 0, sizeof(VkTables) * K, c->stream));
+    for (uint32_t k = 0; k < K; k++) keys[k] = GsetKey{c->d_gs_tab + k, 0u, 0u, 0u, 0u};
+    HIP_TRY(hipMalloc(&c->d_gs_key, sizeof(GsetKey) * K));
+    HIP_TRY(hipMemcpyAsync(c->d_gs_key, keys.data(), sizeof(GsetKey) * K, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMalloc(&c->d_pkey, sizeof(PlonkKey) * K));
+    HIP_TRY(hipMalloc(&c->d_ps_ok, sizeof(uint32_t) * K));
+    // the raw keys are only read by the set-up kernels: mx[0..1] until those are done
+    HIP_TRY(hipMalloc(&c->mx[0], sizeof(VkRaw) * K));
+    HIP_TRY(hipMalloc(&c->mx[1], sizeof(PlonkKeyRaw) * K));
+    HIP_TRY(hipMemcpyAsync(c->mx[0], raw.data(), sizeof(VkRaw) * K, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->mx[1], c->ps_raw.data(), sizeof(PlonkKeyRaw) * K, hipMemcpyHostToDevice, c->stream));
+    launch_gset_setup(K, (const VkRaw*)c->mx[0], c->d_gs_tab, 0, nullptr, nullptr, nullptr, nullptr, c->stream);
+    launch_pset_setup(K, (const PlonkKeyRaw*)c->mx[1], c->d_pkey, c->d_gs_tab, c->d_ps_ok, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));                // the host vectors above go out of scope
+    for (int k = 0; k < 2; k++) { if (c->mx[k]) (void)hipFree(c->mx[k]); c->mx[k] = nullptr; }
+    return ZKV_OK;
+}
+ZKV_EXPORT zkv_ctx* zkv_plonk_set_create(size_t n_keys, const uint8_t* const* vk_bytes, const size_t* vk_len, int device) {
+    if (n_keys < 1 || n_keys > ZKV_PLONK_SET_MAX_KEYS || !vk_bytes || !vk_len) return nullptr;
+    std::vector<PlonkKeyRaw> raw;
+    std::vector<uint8_t> g2;
+    try {
+        raw.resize(n_keys);
+        g2.resize(256 * n_keys);
+    } catch (const std::bad_alloc&) { return nullptr; }
+    uint32_t nb_max = 0, nc_max = 0;
+    for (size_t k = 0; k < n_keys; k++) {
+        if (!plonk_parse_key(vk_bytes[k], vk_len[k], raw[k], g2.data() + 256 * k)) return nullptr;
+        if (raw[k].nb_public > nb_max) nb_max = raw[k].nb_public;
+        if (raw[k].n_c > nc_max) nc_max = raw[k].n_c;
+    }
+    zkv_ctx* c = new (std::nothrow) zkv_ctx();
+    if (!c) return nullptr;
+    c->vm = ZKV_VM_PLONK_SET; c->device = device; c->initialized = true;
+    memset(&c->consts, 0, sizeof c->consts);
+    c->ps_raw = std::move(raw); c->ps_g2 = std::move(g2);
+    c->ps_nb_max = nb_max; c->ps_nc_max = nc_max;
+    return c;
+}
+ZKV_EXPORT size_t zkv_plonk_set_size(const zkv_ctx* c) { return c && c->vm == ZKV_VM_PLONK_SET ? c->ps_raw.size() : 0; }
+ZKV_EXPORT size_t zkv_plonk_set_proof_stride(const zkv_ctx* c) { return c && c->vm == ZKV_VM_PLONK_SET ? pset_proof_stride(c) : 0; }
+ZKV_EXPORT size_t zkv_plonk_set_input_stride(const zkv_ctx* c) { return c && c->vm == ZKV_VM_PLONK_SET ? pset_input_stride(c) : 0; }
+ZKV_EXPORT int zkv_plonk_set_key_shape(const zkv_ctx* c, size_t key, size_t* nb_public, size_t* n_commitments, size_t* proof_bytes) {
+    if (!c || c->vm != ZKV_VM_PLONK_SET) return ZKV_ERR_WRONG_CTX;
+    if (key >= c->ps_raw.size()) return ZKV_ERR_INVALID_ARG;
+    const PlonkKeyRaw& r = c->ps_raw[key];
+    if (nb_public) *nb_public = r.nb_public;
+    if (n_commitments) *n_commitments = r.n_c;
+    if (proof_bytes) *proof_bytes = (size_t)32 * (24 + 3 * r.n_c);
+    return ZKV_OK;
+}
+// One call of n proofs, every buffer on the device, enqueued on s (c->mu held, device set up).  Partition by key (count; the per-key totals
+// come back to the host, which lays the groups out on 64-slot boundaries and picks the Miller mapping; place), then the stages chunk by
+// chunk over the slots, then the verdicts back to the caller's order.  No G2 subgroup check (a PLONK proof has no G2 point) and no
+// aggregate check.
+static int run_pset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* d_proofs, const uint8_t* d_inputs, uint8_t* d_verified, hipStream_t s) {
+    const uint32_t K = (uint32_t)c->ps_raw.size();
+    GsetPart p;
+    memset(&p, 0, sizeof p);
+    p.n = n; p.n_keys = K;
+    size_t per = (n + 255) / 256;                            // at most 256 partition blocks of a multiple of 64 proofs
+    per = (per + 63) / 64 * 64;
+    p.per_block = (uint32_t)per; p.blocks = (uint32_t)((n + per - 1) / per);
+    const size_t kb = (size_t)K * p.blocks;
+    int rc;
+    if ((rc = grow(&c->mx[3], &c->mx_cap[3], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[4], &c->mx_cap[4], 4 * (size_t)K)) != ZKV_OK ||
+        (rc = grow(&c->mx[5], &c->mx_cap[5], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[6], &c->mx_cap[6], 4 * n)) != ZKV_OK ||
+        (rc = grow(&c->mx[7], &c->mx_cap[7], 8 * ((size_t)K + 1))) != ZKV_OK) return rc;
+    p.key = d_key; p.cnt = (uint32_t*)c->mx[3]; p.totals = (uint32_t*)c->mx[4]; p.off = (uint32_t*)c->mx[5]; p.pos = (uint32_t*)c->mx[6];
+    HIP_TRY(hipMemsetAsync(p.totals, 0, 4 * (size_t)K, s));
+    launch_gset_count(p, s);
+    HIP_TRY(hipGetLastError());
+    c->gs_totals.resize(K); c->gs_start.resize((size_t)K + 1);
+    HIP_TRY(hipMemcpyAsync(c->gs_totals.data(), p.totals, 4 * (size_t)K, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    uint64_t slots = 0;
+    const int lanes = pset_choose(c->gs_totals.data(), K, c->lanes, wave_below(), wide_below(), c->gs_start.data(), &slots);
+    const size_t M = (size_t)slots;
+    if ((rc = ctx_ready(c, M ? M : 1)) != ZKV_OK) return rc;     // (growing frees buffers, which synchronises the device)
+    if ((rc = grow(&c->mx[8], &c->mx_cap[8], 4 * M + 4)) != ZKV_OK || (rc = grow(&c->mx[9], &c->mx_cap[9], 4 * M + 4)) != ZKV_OK ||
+        (rc = grow(&c->d_st_all, &c->st_all_cap, M + 1)) != ZKV_OK) return rc;
+    p.idx = (uint32_t*)c->mx[8]; p.skey = (uint32_t*)c->mx[9];
+    HIP_TRY(hipMemsetAsync(p.idx, 0xFF, 4 * M + 4, s));      // pad slots: GSET_NONE
+    HIP_TRY(hipMemsetAsync(p.skey, 0, 4 * M + 4, s));        // (and key 0: keeps any read of a pad slot's key in the set)
+    HIP_TRY(hipMemcpyAsync(c->mx[7], c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
+    launch_gset_place(p, (const uint64_t*)c->mx[7], s);
+    HIP_TRY(hipGetLastError());
+    const size_t cap = c->ws.cap;                            // (a power of two >= 4,096 or ZKV_CHUNK, a multiple of 64: chunks keep the 64-slot groups)
+    for (size_t base = 0; base < M; base += cap) {
+        const size_t m = M - base < cap ? M - base : cap;
+        const bool timed = base + cap >= M;
+        PsetChunk ch;
+        memset(&ch, 0, sizeof ch);
+        ch.m = m; ch.slot0 = base; ch.idx = p.idx; ch.skey = p.skey;
+        ch.keys = c->d_pkey; ch.ok = c->d_ps_ok;
+        ch.proofs = d_proofs; ch.proof_stride = (uint32_t)pset_proof_stride(c);
+        ch.inputs = d_inputs; ch.input_stride = (uint32_t)pset_input_stride(c);
+        ch.plonk_tab = c->d_plonk_tab; ch.status = c->d_st_all + base;
+        if (timed) (void)hipEventRecord(c->ev[0], s);
+        launch_pset_prep(ch, c->ws, s);
+        if (timed) { (void)hipEventRecord(c->ev[1], s); (void)hipEventRecord(c->ev[2], s); (void)hipEventRecord(c->ev[3], s); }
+        launch_gset_miller(lanes, m, p.skey + base, c->d_gs_key, c->ws, ch.status, s);
+        if (timed) (void)hipEventRecord(c->ev[4], s);
+        if (lanes == 2) launch_finalexp2(m, c->ws, ch.status, s);
+        else if (lanes == 16) launch_finalexp_w(m, c->ws, ch.status, s);
+        else launch_finalexp_w64(m, c->ws, ch.status, s);
+        if (timed) (void)hipEventRecord(c->ev[5], s);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!M) for (int e = 0; e < 6; e++) (void)hipEventRecord(c->ev[e], s);
+    launch_gset_return(n, p.pos, c->d_st_all, d_verified, s);
+    HIP_TRY(hipGetLastError());
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_plonk_set_verify_batch_dev(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* d_proofs, const uint8_t* d_public_inputs,
+                                              uint8_t* d_verified, void* stream) {
+    if (!c || c->vm != ZKV_VM_PLONK_SET) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_key || !d_proofs || !d_verified || (pset_input_stride(c) && !d_public_inputs))) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_ready(c, n);
+    if (rc != ZKV_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    if ((rc = run_pset(c, n, d_key, d_proofs, d_public_inputs, d_verified, s)) != ZKV_OK) return rc;
+    return mark_done(c, s);
+}
+ZKV_EXPORT int zkv_plonk_set_verify_batch(zkv_ctx* c, size_t n, const uint32_t* key, const uint8_t* proofs, const uint8_t* public_inputs, uint8_t* verified) {
+    if (!c || c->vm != ZKV_VM_PLONK_SET) return ZKV_ERR_WRONG_CTX;
+    const size_t ps = pset_proof_stride(c), is = pset_input_stride(c);
+    if (n && (!key || !proofs || !verified || (is && !public_inputs))) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const size_t hc = pset_host_chunk(c);
+    int rc = ctx_ready(c, n < hc ? n : hc);
+    if (rc != ZKV_OK) return rc;
+    if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
+    // chunks of the caller's order staged in HBM: keys, proofs, public inputs (hb[0..2]) and the verdicts (hb[3])
+    for (size_t base = 0; base < n; base += hc) {
+        const size_t m = n - base < hc ? n - base : hc;
+        if ((rc = grow(&c->hb[0], &c->hb_cap[0], 4 * m)) != ZKV_OK || (rc = grow(&c->hb[1], &c->hb_cap[1], ps * m)) != ZKV_OK ||
+            (rc = grow(&c->hb[2], &c->hb_cap[2], is * m + 8)) != ZKV_OK || (rc = grow(&c->hb[3], &c->hb_cap[3], m)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(c->hb[0], key + base, 4 * m, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->hb[1], proofs + ps * base, ps * m, hipMemcpyHostToDevice, c->stream));
+        if (is) HIP_TRY(hipMemcpyAsync(c->hb[2], public_inputs + is * base, is * m, hipMemcpyHostToDevice, c->stream));
+        if ((rc = run_pset(c, m, (const uint32_t*)c->hb[0], c->hb[1], is ? c->hb[2] : nullptr, c->hb[3], c->stream)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(verified + base, c->hb[3], m, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return mark_done(c, c->stream);
+}
+
 // ------------------------------------------------------------------ Groth16 core pieces
 ZKV_EXPORT int zkv_ctx_vk_x_batch(zkv_ctx* c, size_t n, const uint8_t* var_signals, uint8_t* out) {
     if (is_sharded(c)) c = c->shards[0];
     if (!c || c->vm == ZKV_VM_BN254 || c->vm == ZKV_VM_RISC0_SET || c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_PLONK || c->vm == ZKV_VM_GROTH16_SET ||
-        c->vm == ZKV_VM_SP1_GATEWAY || c->vm == ZKV_VM_PLONK)
+        c->vm == ZKV_VM_SP1_GATEWAY || c->vm == ZKV_VM_PLONK || c->vm == ZKV_VM_PLONK_SET)
         return ZKV_ERR_WRONG_CTX;
     if (c->vm == ZKV_VM_RISC0 && !c->initialized) return ZKV_ERR_INVALID_ARG;
     if (n && (!var_signals || !out)) return ZKV_ERR_INVALID_ARG;
@@ -2871,7 +3069,7 @@ ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t
         return ZKV_OK;
     }
     if (c->vm != ZKV_VM_RISC0 && c->vm != ZKV_VM_RISC0_SET && c->vm != ZKV_VM_SP1 && c->vm != ZKV_VM_GROTH16 && c->vm != ZKV_VM_SP1_PLONK &&
-        c->vm != ZKV_VM_GROTH16_SET && c->vm != ZKV_VM_PLONK)
+        c->vm != ZKV_VM_GROTH16_SET && c->vm != ZKV_VM_PLONK && c->vm != ZKV_VM_PLONK_SET)     // (a PLONK set accepts it and runs the per-proof path)
         return enable ? ZKV_ERR_INVALID_ARG : ZKV_OK;
     {
         std::lock_guard<std::mutex> lk(c->mu);

@@ -38,6 +38,21 @@ inline int gset_choose(const uint32_t* cnt, uint32_t n_keys, int lanes, int fixe
     }
 }
 
+// PLONK key sets (zkv_plonk_set_*).  PREP runs one proof per lane, so every key group starts on a multiple of 64
+// slots (one PREP wavefront); every Miller wavefront (32, 4 or 1 proofs) then holds one key as well.  The Miller mapping is the single-key
+// PLONK policy of enqueue_chunk applied to the n placed proofs: one wavefront per proof at or below wave_below or when the caller fixed
+// 64 / 128, 16 lanes at or below wide_below or when fixed to 16, lane pairs otherwise (fixed = 0: automatic).  No two-wavefront
+// kernel (PLONK has no variable pair for a second wavefront to step) and no stepping to finer mappings (they do not reduce 64-slot
+// padding).  Returns the lanes per proof (2, 16 or 64) and fills start[] (gset_layout, align 64).
+inline int pset_choose(const uint32_t* cnt, uint32_t n_keys, int fixed, uint64_t wave_below, uint64_t wide_below, uint64_t* start, uint64_t* slots) {
+    uint64_t n = 0;
+    for (uint32_t k = 0; k < n_keys; k++) n += cnt[k];
+    *slots = gset_layout(cnt, n_keys, 64, start);
+    if (fixed == 64 || fixed == 128 || (!fixed && n <= wave_below)) return 64;
+    if (fixed == 16 || (!fixed && n <= wide_below)) return 16;
+    return 2;
+}
+
 // Aggregate check on a key set (zkv_ctx_set_aggregate_check).  Sub-batches must hold proofs of one key, and the
 // aggregate Miller kernel deals a 64-proof block out to its lane pairs, so the unit of the aggregate region is A = max(64, sub) proofs.
 // A capable key k (valid, alpha and beta finite) puts its first floor(cnt[k] / A) * A proofs, in caller order, into the aggregate region

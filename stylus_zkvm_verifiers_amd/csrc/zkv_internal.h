@@ -198,6 +198,20 @@ void launch_plonk_setup(const PlonkKeyRaw* d_raw, PlonkKey* d_key, hipStream_t s
 void launch_plonk_setup_keys(const PlonkKeyRaw* d_raw, PlonkKey* d_key, hipStream_t s);     // any key (k_plonk_keys.hip): include/zkv_plonk_keys.h key rule
 void launch_plonk_prep(const PrepArgs& a, const PlonkKey* d_key, const Workspace& ws, hipStream_t s);
 void launch_plonk_prep_keys(const PrepArgs& a, const PlonkKey* d_key, const Workspace& ws, hipStream_t s);     // any key, up to 128 public inputs (k_plonk_keys.hip)
+// PLONK key sets (k_plonk_set.hip; include/zkv_plonk_set.h): the PlonkKey of every key (grid y = key) and its validity word (PlonkKey.valid
+// and the key's VkTables.vk_valid, so after launch_gset_setup on the same stream), and PREP with the key of each 64-slot wavefront
+// (zkv_gset_layout.h pset_choose).  Slot j of a chunk is slot slot0 + j of the call; its proof is row idx[] of the caller's rows.
+struct PsetChunk {
+    size_t m, slot0;                                // slots [slot0, slot0 + m) of the call
+    const uint32_t* idx; const uint32_t* skey;      // whole-call slot tables (GsetPart)
+    const PlonkKey* keys; const uint32_t* ok;       // the set's keys and their validity words
+    const uint8_t* proofs; uint32_t proof_stride;   // caller rows: key's 32 (24 + 3 n_c) bytes first
+    const uint8_t* inputs; uint32_t input_stride;   // caller rows: key's nb_public 32-byte words first
+    uint32_t* plonk_tab;                            // PLONK_TAB_WORDS words per slot of the chunk
+    uint8_t* status;                                // m statuses (slot order)
+};
+void launch_pset_setup(uint32_t n_keys, const PlonkKeyRaw* d_raw, PlonkKey* d_keys, const VkTables* d_tabs, uint32_t* d_ok, hipStream_t s);
+void launch_pset_prep(const PsetChunk& c, const Workspace& ws, hipStream_t s);
 
 // k_wide.hip: consumer wavefronts that timed out waiting for their producer on the current device (always 0 unless a wavefront died)
 int read_wait_faults(unsigned long long* out);
