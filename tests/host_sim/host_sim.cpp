@@ -135,6 +135,33 @@ void hs_vk_x16(int vm, const uint8_t* cr, const uint8_t* cid, const uint8_t* s0,
         for (int i = 0; i < 8; i++) for (int k = 0; k < 4; k++) out64[32 * c + 31 - 4 * i - k] = r[i] >> (8 * k);
     }
 }
+// PREP + MSM of verify_proof_with_key for an arbitrary key, exported as hs_prepare does (for the lane-pair and 16-lane emulations): the
+// tables of the last key stay until the next call.  NULL when the key is invalid or the proof is rejected before the pairing.
+const void* hs_prepare_generic(const uint8_t* vk_words, int n_ic, int negate_a, const uint8_t* words, const uint8_t* signals,
+                               uint32_t* flags_out, uint32_t* norm48, uint32_t* b32) {
+    static VkTables* t = (VkTables*)malloc(sizeof(VkTables));
+    VkRaw raw; host::fill_vk_generic(raw, vk_words, (uint32_t)n_ic);
+    memset(t, 0, sizeof *t);
+    setup_validate(raw, *t);
+    if (!t->vk_valid) return nullptr;
+    setup_base(raw, *t);
+    for (uint32_t b = 0; b < raw.n_var; b++) for (uint32_t w = 0; w < raw.var_windows[b]; w++) setup_msm_row(raw, *t, (int)b, (int)w);
+    setup_lines(raw.gamma, t->lines[0]);
+    setup_lines(raw.delta, t->lines[1]);
+    { uint32_t ab[96 + 48]; MRef fm = m_ref(ab, 1), tm = m_ref(ab + 96, 1); setup_alpha_beta(raw, *t, fm, tm); }
+    PrepOut p; memset(&p, 0, sizeof p);
+    for (int b = 0; b + 1 < n_ic; b++) { load_be256(p.s[b], signals + 32 * b); if (!raw_lt_r(p.s[b])) return nullptr; }
+    uint32_t w[8][8];
+    for (int k = 0; k < 8; k++) load_be256(w[k], words + 32 * k);
+    if (!prep_points(w, negate_a != 0, p)) return nullptr;
+    G1Norm n; uint32_t fl = p.flags;
+    msm_normalize(*t, p, fl, n);
+    *flags_out = fl;
+    const Fp* nf[6] = {&n.axs, &n.ays, &n.lxs, &n.lys, &n.cxs, &n.cys};
+    for (int k = 0; k < 6; k++) memcpy(norm48 + 8 * k, nf[k]->v, 32);
+    memcpy(b32, p.bx.c0.v, 32); memcpy(b32 + 8, p.bx.c1.v, 32); memcpy(b32 + 16, p.by.c0.v, 32); memcpy(b32 + 24, p.by.c1.v, 32);
+    return t;
+}
 // verify_proof_with_key for an arbitrary key through the kernel stage functions (tables rebuilt per call: test only)
 int hs_groth16_generic(const uint8_t* vk_words, int n_ic, int negate_a, const uint8_t* words, const uint8_t* signals) {
     static VkTables* t = (VkTables*)malloc(sizeof(VkTables));

@@ -25,8 +25,10 @@ def _pt(k):
     return m.g1_mul(m.G1_GEN, k % R)
 
 
-def make_key(rng, nb_public, n_c, log_n=None, cci=None):
-    """A trapdoor key: dict in plonk_model's layout plus the discrete logs ('dlog') and tau."""
+def make_key(rng, nb_public, n_c, log_n=None, cci=None, over=None):
+    """A trapdoor key: dict in plonk_model's layout plus the discrete logs ('dlog') and tau.  `over` replaces discrete logs after the
+    draws (so a key with overrides shares every other value with the key without): {name: int, or callable(dlog) -> int}; 0 gives the
+    point at infinity, equal or negated discrete logs equal or opposite points."""
     if log_n is None:
         log_n = max(3, (nb_public + 2).bit_length() + 1)
     n = 1 << log_n
@@ -35,6 +37,7 @@ def make_key(rng, nb_public, n_c, log_n=None, cci=None):
     tau = rng.randrange(2, R)
     names = ('s1', 's2', 's3', 'ql', 'qr', 'qm', 'qo', 'qk') + (('qcp',) if n_c else ())
     dlog = {k: rng.randrange(1, R) for k in names}
+    dlog.update(_resolve(over, dlog))
     if cci is None:
         cci = rng.randrange(0, n - nb_public) if n_c else 0
     vk = dict(size=n, size_inv=finv(n), generator=w, coset_shift=5, nb_public=nb_public, cci=[cci] if n_c else [],
@@ -42,6 +45,11 @@ def make_key(rng, nb_public, n_c, log_n=None, cci=None):
               **{k: pm.g1_wire(_pt(dlog[k])) for k in names if k != 'qcp'})
     vk['dlog'], vk['tau'] = dlog, tau
     return vk
+
+
+def _resolve(over, dlog):
+    """Overrides against the drawn discrete logs: every callable sees the values drawn, not other overrides."""
+    return {k: (v(dlog) if callable(v) else v) % R for k, v in (over or {}).items()}
 
 
 def proof_words(vk):
@@ -52,15 +60,38 @@ def pad27(proof):
     return bytes(proof) + bytes(32 * 27 - len(proof))
 
 
-def forge(vk, public_inputs, rng):
-    """Proof bytes (24 + 3 n_c words) that plonk_verify accepts for `public_inputs` (ints < R) under the trapdoor key vk."""
+def forge(vk, public_inputs, rng, over=None, evals=None, solve=None, info=None):
+    """Proof bytes (24 + 3 n_c words) that plonk_verify accepts for `public_inputs` (ints < R) under the trapdoor key vk.
+
+    Degenerate proofs (every override is applied after the same rng draws, so that the plain forgery does not change):
+      over:  discrete logs of L R O H0 H1 H2 Z BSB ({name: int, or callable(drawn dlogs) -> int}; 0 = the point at infinity);
+      evals: claimed evaluations l r o s1 s2 zu qcpz ({name: int});
+      solve: 'hzw' -- H_zeta_omega = O: z(omega zeta) = dlog Z (zu is not hashed before zeta);
+             'hz'  -- H_zeta = O: every claimed evaluation equals its digest's discrete log, and zu solves the affine equation
+                      lin_eval(zu) = f_lin(zu), so that the folded digest equals [folded evaluation] G for every gamma_kzg;
+             'lin' -- linearised digest = O (n_c = 1): qcp(zeta) solves f_lin = 0 (qcp(zeta) is hashed only after the digest).
+      info:  a dict that receives the forger's intermediate values (f_lin, F, fe, hz / hzw discrete logs) for branch assertions.
+    Out of reach, by design: the folded digest F at infinity (every free value is hashed into gamma_kzg, the challenge that
+    multiplies it) and both pairing inputs D and Q at infinity together (the same, through lambda); these states are not forced."""
     n_c = len(vk['qcp'])
     d = vk['dlog']
     ks = ('s1', 's2', 's3', 'ql', 'qr', 'qm', 'qo', 'qk')
     dl = {k: rng.randrange(1, R) for k in ('L', 'R', 'O', 'H0', 'H1', 'H2', 'Z', 'BSB')}
+    dl.update(_resolve(over, dl))
     pt = {k: _pt(v) for k, v in dl.items() if k != 'BSB' or n_c}
     l, r, o, s1, s2, zu = (rng.randrange(R) for _ in range(6))
     qcpz = rng.randrange(R) if n_c else 0
+    ev = dict(l=l, r=r, o=o, s1=s1, s2=s2, zu=zu, qcpz=qcpz)
+    ev.update({k: v % R for k, v in (evals or {}).items()})
+    if solve == 'hzw':
+        ev['zu'] = dl['Z']
+    elif solve == 'hz':
+        ev.update(l=dl['L'], r=dl['R'], o=dl['O'], s1=d['s1'], s2=d['s2'], qcpz=d['qcp'] if n_c else 0)
+    elif solve == 'lin':
+        assert n_c == 1, 'the linearised digest is solved through qcp(zeta)'
+    elif solve is not None:
+        raise ValueError(solve)
+    l, r, o, s1, s2, zu, qcpz = (ev[k] for k in ('l', 'r', 'o', 's1', 's2', 'zu', 'qcpz'))
     # ---- challenges (plonk_verify)
     fs = pm.Transcript('gamma', 'beta', 'alpha', 'zeta')
     for k in ks:
@@ -94,15 +125,26 @@ def forge(vk, public_inputs, rng):
     a2l0 = lagrange0 * alpha % R * alpha % R
     t1 = (l + beta * s1 + gamma) % R
     t2 = (r + beta * s2 + gamma) % R
-    lin_eval = -(pi - a2l0 + alpha * t1 % R * t2 % R * ((o + gamma) % R) % R * zu) % R
-    _s1 = alpha * t1 % R * t2 % R * beta % R * zu % R
     _s2 = -alpha * ((l + beta * zeta + gamma) % R) % R * ((r + beta * u % R * zeta + gamma) % R) % R * ((o + beta * u % R * u % R * zeta + gamma) % R) % R
     coeff_z = (a2l0 + _s2) % R
     zn2 = pow(zeta, n + 2, R)
-    terms = ([(qcpz, dl['BSB'])] if n_c else []) + [
-        (l, d['ql']), (r, d['qr']), (l * r, d['qm']), (o, d['qo']), (1, d['qk']), (_s1, d['s3']), (coeff_z, dl['Z']),
-        (-zh, dl['H0']), (-zn2 * zh, dl['H1']), (-zn2 * zn2 % R * zh, dl['H2'])]
-    f_lin = sum(k * x for k, x in terms) % R
+
+    def linearised(zu, qcpz):                    # (lin_eval, f_lin): both affine in zu and qcpz
+        lin_eval = -(pi - a2l0 + alpha * t1 % R * t2 % R * ((o + gamma) % R) % R * zu) % R
+        _s1 = alpha * t1 % R * t2 % R * beta % R * zu % R
+        terms = ([(qcpz, dl['BSB'])] if n_c else []) + [
+            (l, d['ql']), (r, d['qr']), (l * r, d['qm']), (o, d['qo']), (1, d['qk']), (_s1, d['s3']), (coeff_z, dl['Z']),
+            (-zh, dl['H0']), (-zn2 * zh, dl['H1']), (-zn2 * zn2 % R * zh, dl['H2'])]
+        return lin_eval, sum(k * x for k, x in terms) % R
+
+    if solve == 'hz':                            # lin_eval(zu) - f_lin(zu) = c0 + c1 zu = 0
+        c0 = (linearised(0, qcpz)[0] - linearised(0, qcpz)[1]) % R
+        c1 = (linearised(1, qcpz)[0] - linearised(1, qcpz)[1] - c0) % R
+        zu = -c0 * finv(c1) % R
+    elif solve == 'lin':                         # f_lin(qcpz) = k0 + k1 qcpz = 0
+        k0 = linearised(zu, 0)[1]
+        qcpz = -k0 * finv((linearised(zu, 1)[1] - k0) % R) % R
+    lin_eval, f_lin = linearised(zu, qcpz)
     lin = _pt(f_lin)
     # ---- folding
     dig_dl = [f_lin, dl['L'], dl['R'], dl['O'], d['s1'], d['s2']] + ([d['qcp']] if n_c else [])
@@ -111,7 +153,7 @@ def forge(vk, public_inputs, rng):
     fk = pm.Transcript('gamma')
     fk.add('gamma', be32(zeta))
     for g in digests:
-        fk.add('gamma', g1_bytes(None if tuple(g) == (0, 0) else g))
+        fk.add('gamma', g1_bytes(None if g is None or tuple(g) == (0, 0) else g))
     for v in values:
         fk.add('gamma', be32(v))
     fk.add('gamma', be32(zu))
@@ -123,6 +165,9 @@ def forge(vk, public_inputs, rng):
     tau, zeta_w = vk['tau'], zeta * w % R
     hz = _pt((F - fe) * finv(tau - zeta))
     hzw = _pt((dl['Z'] - zu) * finv(tau - zeta_w))
+    if info is not None:
+        info.update(f_lin=f_lin, F=F, fe=fe, hz=(F - fe) * finv(tau - zeta) % R, hzw=(dl['Z'] - zu) * finv(tau - zeta_w) % R, dlog=dict(dl),
+                    evals=dict(l=l, r=r, o=o, s1=s1, s2=s2, zu=zu, qcpz=qcpz))
     wire = lambda p: be32(p[0]) + be32(p[1]) if p is not None else bytes(64)
     out = b''.join(wire(pt[k]) for k in ('L', 'R', 'O', 'H0', 'H1', 'H2'))
     out += b''.join(be32(v) for v in (l, r, o, s1, s2)) + wire(pt['Z']) + be32(zu) + wire(hz) + wire(hzw)
