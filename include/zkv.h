@@ -15,6 +15,7 @@
  *     therefore executed one after another, also when the *_dev entry points are given different HIP streams (each
  *     call makes its stream wait for the previous call's last kernel).  Use one context per host thread / per
  *     concurrent stream for overlap.
+ * Alignment: byte-typed buffers (uint8_t*), host or device, may have any alignment; uint32_t* / uint64_t* arguments need their natural one.
  */
 #ifndef ZKV_H
 #define ZKV_H

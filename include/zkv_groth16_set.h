@@ -18,6 +18,7 @@
  *     workspace; with the check off (the default) nothing is allocated.
  *   - Proofs are 256 bytes each, as for zkv_groth16_verify_batch.  Signals are rows of zkv_groth16_set_signal_stride bytes:
  *     the first n_ic[k] - 1 32-byte big-endian words of row i are proof i's signals; the words after them are never read.
+ * Alignment: byte-typed buffers (uint8_t*), host or device, may have any alignment; uint32_t* / uint64_t* arguments need their natural one.
  */
 #ifndef ZKV_GROTH16_SET_H
 #define ZKV_GROTH16_SET_H

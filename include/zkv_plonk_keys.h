@@ -31,6 +31,7 @@
  *     flight 3.7 KB of workspace and 3.75 KB of MSM tables (7.5 KB), and for host batches the staged proofs and public inputs
  *     (proof_bytes + 32 nb_public bytes).  Host batches run in chunks of at most 512 MB of staged public inputs (2^17 proofs at 128
  *     inputs); device batches in chunks of the workspace (default up to 2^20 proofs, ZKV_CHUNK).
+ * Alignment: byte-typed buffers (uint8_t*), host or device, may have any alignment; uint32_t* / uint64_t* arguments need their natural one.
  */
 #ifndef ZKV_PLONK_KEYS_H
 #define ZKV_PLONK_KEYS_H

@@ -20,6 +20,7 @@
  *   - Device memory: about 24 MB per key (the key points' window tables: 6.2 GB for 256 keys) and 3.6 MB of line tables per key, set
  *     up lazily on the first batch or zkv_ctx_reserve; per proof in flight 3.7 KB of workspace and 3.75 KB of MSM tables, and per
  *     call the slot tables of the partition by key.
+ * Alignment: byte-typed buffers (uint8_t*), host or device, may have any alignment; uint32_t* / uint64_t* arguments need their natural one.
  */
 #ifndef ZKV_PLONK_SET_H
 #define ZKV_PLONK_SET_H

@@ -28,6 +28,7 @@
  *
  * Device scratch of a batch call, on top of the routes' own workspaces: sum over routes of n_r x record_r (260 bytes per Groth16-route
  * proof, 868 per PLONK-route proof) plus 61 bytes per proof; host-buffer calls also stage the caller's buffers in device memory.
+ * Alignment: byte-typed buffers (uint8_t*), host or device, may have any alignment; uint32_t* / uint64_t* arguments need their natural one.
  */
 #ifndef ZKV_SP1_GATEWAY_H
 #define ZKV_SP1_GATEWAY_H

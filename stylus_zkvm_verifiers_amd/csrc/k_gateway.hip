@@ -11,6 +11,7 @@
 //                     the public-values location were written by place
 // The statuses come back through k_mixed_return.  All of it is byte traffic beside the pairing; no scratch, no LDS beyond the counts.
 #include "zkv_internal.h"
+#include "zkv_bytes.h"
 
 namespace zkv {
 
@@ -122,12 +123,6 @@ __global__ __launch_bounds__(GW_BLOCK) void k_gateway_place(GatewayArgs a) {
     a.c_pvlen[slot] = (uint32_t)(a.pv_off ? a.pv_off[i + 1] - a.pv_off[i] : a.pv_stride);
 }
 
-__device__ __forceinline__ uint32_t gw_ld4(const uint8_t* p, uint64_t avail) {      // up to 4 bytes, zero padded, any alignment
-    if (avail >= 4 && !((uintptr_t)p & 3u)) return *(const uint32_t*)p;
-    uint32_t v = 0;
-    for (int k = 0; k < 4; k++) if ((uint64_t)k < avail) v |= (uint32_t)p[k] << (8 * k);
-    return v;
-}
 // One wavefront per proof (four per workgroup): the route's record stride decides how many words the lanes copy (65 or 217).
 __global__ __launch_bounds__(GW_BLOCK) void k_gateway_gather(GatewayArgs a) {
     const size_t i = (size_t)blockIdx.x * (GW_BLOCK / 64) + (threadIdx.x >> 6);

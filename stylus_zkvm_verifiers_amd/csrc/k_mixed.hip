@@ -16,6 +16,7 @@
 // sub-batch's per-proof `kind` (PrepArgs::kind, as in the wire layer).  A method that the proof's VM does not have gets
 // ZKV_STATUS_BAD_CALLDATA in place, like an unknown tag gets ZKV_STATUS_UNKNOWN_VM: no slot, no verifier.
 #include "zkv_internal.h"
+#include "zkv_bytes.h"
 
 namespace zkv {
 
@@ -93,12 +94,6 @@ __global__ __launch_bounds__(MX_BLOCK) void k_mixed_place(MixedArgs a) {
 
 // One thread per (proof, word): 65 seal words, 8 words of in_a, 8 words of in_b (the RISC Zero journal digest; not for verify_integrity).
 constexpr uint32_t MX_WORDS = 65 + 8 + 8;
-__device__ __forceinline__ uint32_t mx_ld4(const uint8_t* p, size_t avail) {      // up to 4 bytes, zero padded, any alignment
-    if (avail >= 4 && !((uintptr_t)p & 3u)) return *(const uint32_t*)p;
-    uint32_t v = 0;
-    for (int k = 0; k < 4; k++) if ((size_t)k < avail) v |= (uint32_t)p[k] << (8 * k);
-    return v;
-}
 __global__ __launch_bounds__(MX_BLOCK) void k_mixed_gather(MixedArgs a) {
     const size_t t = (size_t)blockIdx.x * MX_BLOCK + threadIdx.x;
     const size_t i = t / MX_WORDS;

@@ -7,29 +7,12 @@
 // loads, checks that it is the canonical ABI encoding (the router decodes with validation: any other byte string is
 // rejected -- unpinned), and compacts the arrays to bytes.
 #include "zkv_internal.h"
+#include "zkv_bytes.h"
 
 namespace zkv {
 
 constexpr int WIRE_BLOCK = 256;                  // four requests per workgroup
 constexpr uint32_t WIRE_BAD = 0xFFFFFFFFu;
-
-// One 32-byte ABI word that must hold a value < 2^32.  `al` (wave-uniform): the word is 4-byte aligned.
-struct WordVal { uint32_t v; bool small; };
-__device__ __forceinline__ WordVal wire_word(const uint8_t* p, bool al) {
-    uint32_t hi = 0, last;
-    if (al) {
-        const uint32_t* q = (const uint32_t*)p;
-        uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3], w4 = q[4], w5 = q[5], w6 = q[6];
-        hi = w0 | w1 | w2 | w3 | w4 | w5 | w6;
-        last = __builtin_bswap32(q[7]);
-    } else {
-#pragma unroll 4
-        for (int k = 0; k < 28; k++) hi |= p[k];
-        last = ((uint32_t)p[28] << 24) | ((uint32_t)p[29] << 16) | ((uint32_t)p[30] << 8) | p[31];
-    }
-    WordVal r; r.v = last; r.small = hi == 0;
-    return r;
-}
 
 // 16 bytes of calldata as four dwords in ABI (big-endian) significance order: w[3] holds the lowest-order bytes.
 template <bool AL, bool NT = false>

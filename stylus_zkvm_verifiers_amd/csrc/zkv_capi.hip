@@ -22,6 +22,7 @@
 #include "../../include/zkv_plonk_keys.h"
 #include "../../include/zkv_plonk_set.h"
 #include "../../include/zkv_diag_primitive.h"
+#include "../../include/zkv_diag_prep.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
@@ -85,6 +86,7 @@ struct zkv_ctx {
     // each call first makes its stream wait for the previous call's last kernel (ev_done), then records ev_done again.
     hipEvent_t ev_done = nullptr;
     bool has_done = false;
+    size_t last_chunk_n = 0;                                 // proofs of the most recent chunk (zkv_diag_prep.h reads their rows back)
     // host-buffer batches (run_host_batch): whole-batch staging in HBM, filled segment by segment on copy_stream while the previous
     // segment is verified
     uint8_t* hb[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // seals, seal offsets, in_a, in_b, public values, pv offsets
@@ -726,6 +728,7 @@ static LongKey long_key_of(const zkv_ctx* c) { return LongKey{c->d_ltab, c->d_lw
 
 // Enqueues the five stages for one chunk (all pointers device-resident).
 static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool timed) {
+    c->last_chunk_n = a.n;
     if (timed) (void)hipEventRecord(c->ev[0], s);
     if (is_plonk(c)) {
         // PLONK: the prep stage does everything up to the two G1 points of the final check (transcript, scalar algebra, MSMs);
@@ -3024,6 +3027,27 @@ done:
     if (d_in) (void)hipFree(d_in);
     if (d_out) (void)hipFree(d_out);
     return rc;
+}
+
+// ------------------------------------------------------------------ zkv_diag_prep.h: what PREP stored for the vk_x stage (TEST ONLY)
+static_assert(ZKV_DIAG_PREP_SIGNALS == MAX_VAR, "zkv_diag_prep.h documents MAX_VAR signal rows");
+ZKV_EXPORT int zkv_diag_prep_signals(zkv_ctx* c, size_t n, uint32_t* signals, uint32_t* flags) {
+    if (!c || !signals || !flags || n == 0) return ZKV_ERR_INVALID_ARG;
+    if (is_sharded(c) || (c->vm != ZKV_VM_RISC0 && c->vm != ZKV_VM_SP1) || c->agg_on) return ZKV_ERR_INVALID_ARG;
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { (void)hipGetLastError(); return ZKV_ERR_NO_DEVICE; }
+    if (c->device < 0 || c->device >= nd || !device_is_gfx950(c->device)) return ZKV_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->dev_ready || !c->ws.prep || n > c->last_chunk_n || n > c->ws.cap) return ZKV_ERR_INVALID_ARG;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());                         // the call may have run on a stream of the caller's
+    const size_t rows = (size_t)8 * MAX_VAR;
+    std::vector<uint32_t> t(rows * n);
+    HIP_TRY(hipMemcpy2D(t.data(), 4 * n, c->ws.prep + (size_t)64 * c->ws.cap, 4 * c->ws.cap, 4 * n, rows, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flags, c->ws.flags, 4 * n, hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < n; j++)
+        for (size_t r = 0; r < rows; r++) signals[j * rows + r] = t[r * n + j];
+    return ZKV_OK;
 }
 
 // ------------------------------------------------------------------ shared
