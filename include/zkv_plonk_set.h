@@ -10,8 +10,8 @@
  *     proof against it answers 0; the other keys' proofs are unaffected.
  *   - A set is immutable and single-device (zkv_ctx_create_sharded refuses it).  zkv_ctx_vm returns ZKV_VM_PLONK_SET.
  *   - zkv_ctx_destroy / _synchronize / _reserve / _set_lanes_per_proof / _last_stage_ms work as on other contexts.
- *   - zkv_ctx_set_aggregate_check returns ZKV_OK on a set, but calls run the per-proof path and zkv_ctx_aggregate_counters stays
- *     {0, 0} (as on long Groth16 keys).
+ *   - zkv_ctx_set_aggregate_check works on a set: sub-batches run across the keys of one SRS (keys with equal [1]_2 | [tau]_2 bytes);
+ *     zkv_plonk_set_agg.h states the contract.  Before the first call that engages it zkv_ctx_aggregate_counters is {0, 0}.
  *   - zkv_ctx_vk_x_batch and every other kind's entry points return ZKV_ERR_WRONG_CTX on a set, and the entry points below return it
  *     on every other kind.
  *   - Proofs are rows of zkv_plonk_set_proof_stride bytes: row i holds key[i]'s 32 (24 + 3 n_c) proof bytes (zkv_plonk_keys.h's layout)

@@ -21,6 +21,7 @@
 #include "../../include/zkv_sp1_gateway.h"
 #include "../../include/zkv_plonk_keys.h"
 #include "../../include/zkv_plonk_set.h"
+#include "../../include/zkv_plonk_set_agg.h"
 #include "../../include/zkv_diag_primitive.h"
 #include "../../include/zkv_diag_prep.h"
 #include "zkv_host_abi.h"
@@ -103,6 +104,9 @@ struct zkv_ctx {
     // the Groth16 sets' partition buffers (gs_totals, gs_start, mx[3..9]).
     std::vector<PlonkKeyRaw> ps_raw; std::vector<uint8_t> ps_g2; uint32_t ps_nb_max = 0, ps_nc_max = 0;
     uint32_t* d_ps_ok = nullptr;
+    // aggregate check on a PLONK set (zkv_plonk_set_agg.h): every key's SRS class and each class's first key (formed at creation), which
+    // classes can take the check (read back the first time a call wants it), and per call every class's region (pset_agg_choose)
+    std::vector<uint32_t> ps_class, ps_cls_rep; std::vector<uint8_t> ps_cls_ok; std::vector<uint64_t> ps_cbeg, ps_cend;
     // Aggregate check (zkv_agg.h, zkv_ctx_set_aggregate_check): key tables, per-proof rows, the pseudo-proofs' workspace (one per
     // sub-batch), their statuses and the counters {sub-batches checked, sub-batches failed}
     bool agg_on = false, agg_key_ok = false;
@@ -479,7 +483,7 @@ static int agg_reserve(zkv_ctx* c) {
     c->agg_cap = 0; c->ws2.cap = 0; c->ws3.cap = 0;
     // room for the smallest sub-batch size; a key set pads its pseudo-proofs per key up to 1.25 times (gset_choose in run_gset) and runs
     // its second pass in place (k_gset_agg_mark): no dense workspace, no index list
-    const bool set = c->vm == ZKV_VM_GROTH16_SET;
+    const bool set = c->vm == ZKV_VM_GROTH16_SET || c->vm == ZKV_VM_PLONK_SET;     // (a PLONK set pads per SRS class: run_pset)
     const size_t cap = c->ws.cap, cap2 = (cap + 15) / 16 + (set ? (cap + 63) / 64 : 0);
     if (hipMalloc(&c->d_agg, sizeof(uint32_t) * WS_AGG_WORDS * cap) != hipSuccess ||
         hipMalloc(&c->ws2.prep, sizeof(uint32_t) * WS_PREP_WORDS * cap2) != hipSuccess ||
@@ -2810,9 +2814,20 @@ ZKV_EXPORT zkv_ctx* zkv_plonk_set_create(size_t n_keys, const uint8_t* const* vk
     if (!c) return nullptr;
     c->vm = ZKV_VM_PLONK_SET; c->device = device; c->initialized = true;
     memset(&c->consts, 0, sizeof c->consts);
+    try {
+        c->ps_class.resize(n_keys); c->ps_cls_rep.resize(n_keys);
+        c->ps_cls_rep.resize(pset_srs_classes(g2.data(), (uint32_t)n_keys, c->ps_class.data(), c->ps_cls_rep.data()));
+    } catch (const std::bad_alloc&) { delete c; return nullptr; }
     c->ps_raw = std::move(raw); c->ps_g2 = std::move(g2);
     c->ps_nb_max = nb_max; c->ps_nc_max = nc_max;
     return c;
+}
+// (zkv_plonk_set_agg.h) host only: the classes were formed at creation
+ZKV_EXPORT int zkv_plonk_set_srs_classes(const zkv_ctx* c, uint32_t* class_of_key, size_t* n_classes) {
+    if (!c || c->vm != ZKV_VM_PLONK_SET) return ZKV_ERR_WRONG_CTX;
+    if (class_of_key) for (size_t k = 0; k < c->ps_class.size(); k++) class_of_key[k] = c->ps_class[k];
+    if (n_classes) *n_classes = c->ps_cls_rep.size();
+    return ZKV_OK;
 }
 ZKV_EXPORT size_t zkv_plonk_set_size(const zkv_ctx* c) { return c && c->vm == ZKV_VM_PLONK_SET ? c->ps_raw.size() : 0; }
 ZKV_EXPORT size_t zkv_plonk_set_proof_stride(const zkv_ctx* c) { return c && c->vm == ZKV_VM_PLONK_SET ? pset_proof_stride(c) : 0; }
@@ -2826,10 +2841,89 @@ ZKV_EXPORT int zkv_plonk_set_key_shape(const zkv_ctx* c, size_t key, size_t* nb_
     if (proof_bytes) *proof_bytes = (size_t)32 * (24 + 3 * r.n_c);
     return ZKV_OK;
 }
+// Aggregate check on a PLONK set (zkv_plonk_set_agg.h).  Which SRS classes can take it -- the VkTables.vk_valid of
+// each class's first key, i.e. its two G2 points passed the set-up validation -- and the counters, the first time a call wants the check: a
+// set that never uses it allocates nothing.  false: no class can, or no room (the call then runs the per-proof path).
+static bool pset_agg_classes(zkv_ctx* c) {
+    if (c->d_agg_cnt) return c->agg_key_ok;
+    const uint32_t n_cls = (uint32_t)c->ps_cls_rep.size();
+    std::vector<uint32_t> ok(n_cls, 0);
+    bool good = true;
+    for (uint32_t q = 0; q < n_cls && good; q++)
+        good = hipMemcpy(&ok[q], &c->d_gs_tab[c->ps_cls_rep[q]].vk_valid, sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess;
+    if (!good || hipMalloc(&c->d_agg_cnt, 3 * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(c->d_agg_cnt, 0, 3 * sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (c->d_agg_cnt) (void)hipFree(c->d_agg_cnt);
+        c->d_agg_cnt = nullptr;
+        return false;
+    }
+    c->ps_cls_ok.assign(n_cls, 0);
+    c->agg_key_ok = false;
+    for (uint32_t q = 0; q < n_cls; q++) { c->ps_cls_ok[q] = ok[q] ? 1 : 0; c->agg_key_ok = c->agg_key_ok || ok[q]; }
+    return c->agg_key_ok;
+}
+// One aggregate chunk's pseudo-proofs (gset_agg_chunk with a class where that has a key): n2 sub-batches, laid out per class and padded to
+// the proofs per wavefront of the Miller mapping `lanes`, so k_gset_miller* take one class per wavefront -- through the class's first key,
+// whose line tables are those of every key of the class.  In gs_amap from word `off`: psl (sub-batch -> slot, n2 words), then the key of every
+// pseudo slot (slots words).
+static GsetAggChunk pset_agg_chunk(zkv_ctx* c, size_t base, size_t m, uint32_t sub) {
+    const uint32_t n_cls = (uint32_t)c->ps_cls_rep.size();
+    GsetAggChunk g{base, m, m / sub, c->gs_amap.size(), 0, 0};
+    c->gs_nsb.assign(n_cls, 0);
+    c->gs_pst.resize((size_t)n_cls + 1);
+    for (uint32_t q = 0; q < n_cls; q++) {
+        if (!c->ps_cls_ok[q]) continue;
+        const uint64_t lo = c->ps_cbeg[q] > base ? c->ps_cbeg[q] : base, hi = c->ps_cend[q] < base + m ? c->ps_cend[q] : base + m;
+        if (hi > lo) c->gs_nsb[q] = (uint32_t)((hi - lo) / sub);
+    }
+    g.lanes = gset_choose(c->gs_nsb.data(), n_cls, gset_auto_lanes(c, g.n2), 0, c->gs_pst.data(), &g.slots);
+    if (g.slots > c->ws2.cap) g.lanes = gset_choose(c->gs_nsb.data(), n_cls, 64, 1, c->gs_pst.data(), &g.slots);     // (no padding)
+    c->gs_amap.resize(g.off + g.n2 + g.slots, 0);
+    uint32_t* psl = c->gs_amap.data() + g.off;
+    uint32_t* skey2 = psl + g.n2;
+    for (uint32_t q = 0; q < n_cls; q++) {
+        if (!c->gs_nsb[q]) continue;
+        const size_t sb0 = (size_t)((c->ps_cbeg[q] > base ? c->ps_cbeg[q] : base) - base) / sub;
+        for (uint32_t t = 0; t < c->gs_nsb[q]; t++) psl[sb0 + t] = (uint32_t)(c->gs_pst[q] + t);
+        for (uint64_t w = c->gs_pst[q]; w < c->gs_pst[q + 1]; w++) skey2[w] = c->ps_cls_rep[q];
+    }
+    return g;
+}
+// The aggregate check of one chunk of a PLONK set's aggregate region: PREP unchanged, the coefficients and r_i D_i, r_i (-Q_i)
+// (k_agg_plonk_g1: no per-proof Miller loop), one pseudo-proof per sub-batch with its class's [1]_2 / [tau]_2 lines, its final
+// exponentiation, the verdicts, and the per-proof kernels once more over the proofs of the sub-batches that failed -- in place, on the
+// proofs' own points (k_agg_plonk_g1 leaves PREP's rows in ws.norm alone), so the verdict is the per-proof one.
+static void enqueue_pset_agg(zkv_ctx* c, const PsetChunk& ch, const GsetAggChunk& g, const uint32_t* skey, const uint32_t* d_amap, uint32_t sub,
+                             hipStream_t s, bool timed) {
+    const size_t m = ch.m;
+    const uint32_t sub64 = sub < 64 ? sub : 64;
+    const uint32_t* psl = d_amap + g.off;
+    const uint32_t* skey2 = psl + g.n2;
+    if (timed) (void)hipEventRecord(c->ev[0], s);
+    launch_pset_prep(ch, c->ws, s);
+    if (timed) (void)hipEventRecord(c->ev[1], s);
+    agg_next_coefficients(c);
+    launch_agg_plonk_g1(m, c->ws, c->d_agg, c->agg_seed, s);
+    if (timed) { (void)hipEventRecord(c->ev[2], s); (void)hipEventRecord(c->ev[3], s); }
+    (void)hipMemsetAsync(c->ws2.flags, 0, sizeof(uint32_t) * g.slots, s);     // pad slots of the pseudo-proofs: no proof
+    launch_pset_agg_reduce(m, sub64, c->ws, c->d_agg, c->ws2, c->d_status2, psl, sub > 64, s);
+    if (sub > 64) launch_pset_agg_combine(g.n2, sub / 64, c->ws2, c->d_status2, psl, s);
+    launch_gset_miller(g.lanes, (size_t)g.slots, skey2, c->d_gs_key, c->ws2, c->d_status2, s);
+    if (timed) (void)hipEventRecord(c->ev[4], s);
+    if (g.lanes == 2) launch_finalexp2((size_t)g.slots, c->ws2, c->d_status2, s);
+    else if (g.lanes == 16) launch_finalexp_w((size_t)g.slots, c->ws2, c->d_status2, s);
+    else launch_finalexp_w64((size_t)g.slots, c->ws2, c->d_status2, s);
+    launch_gset_agg_mark(m, sub, 1, c->ws, c->d_agg, c->d_status2, psl, ch.status, c->d_agg_cnt, s);
+    launch_gset_miller(2, m, skey, c->d_gs_key, c->ws, ch.status, s);
+    launch_finalexp2(m, c->ws, ch.status, s);
+    if (timed) (void)hipEventRecord(c->ev[5], s);
+}
 // One call of n proofs, every buffer on the device, enqueued on s (c->mu held, device set up).  Partition by key (count; the per-key totals
 // come back to the host, which lays the groups out on 64-slot boundaries and picks the Miller mapping; place), then the stages chunk by
-// chunk over the slots, then the verdicts back to the caller's order.  No G2 subgroup check (a PLONK proof has no G2 point) and no
-// aggregate check.
+// chunk over the slots, then the verdicts back to the caller's order.  No G2 subgroup check (a PLONK proof has no G2 point).  With the
+// aggregate check (automatic mapping, at least ZKV_AGG_MIN proofs placed, a capable SRS class) the groups are ordered class by class
+// (pset_agg_choose): slots [0, R) take enqueue_pset_agg, the classes that cannot take the check follow on the per-proof path.
 static int run_pset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* d_proofs, const uint8_t* d_inputs, uint8_t* d_verified, hipStream_t s) {
     const uint32_t K = (uint32_t)c->ps_raw.size();
     GsetPart p;
@@ -2850,8 +2944,21 @@ static int run_pset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
     c->gs_totals.resize(K); c->gs_start.resize((size_t)K + 1);
     HIP_TRY(hipMemcpyAsync(c->gs_totals.data(), p.totals, 4 * (size_t)K, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    uint64_t slots = 0;
-    const int lanes = pset_choose(c->gs_totals.data(), K, c->lanes, wave_below(), wide_below(), c->gs_start.data(), &slots);
+    size_t placed = 0;
+    for (uint32_t k = 0; k < K; k++) placed += c->gs_totals[k];
+    bool agg = c->agg_on && c->lanes == 0 && placed >= agg_min() && pset_agg_classes(c) && agg_wanted(c);
+    const uint32_t sub = c->agg_sub;
+    uint64_t slots = 0, R = 0;
+    int lanes = 0;
+    if (agg) {
+        const uint32_t n_cls = (uint32_t)c->ps_cls_rep.size();
+        c->ps_cbeg.assign(n_cls, 0); c->ps_cend.assign(n_cls, 0);
+        lanes = pset_agg_choose(c->gs_totals.data(), c->ps_class.data(), K, c->ps_cls_ok.data(), n_cls, sub, 0, wave_below(), wide_below(),
+                                c->gs_start.data(), c->ps_cbeg.data(), c->ps_cend.data(), &R, &slots);
+        if ((rc = ctx_ready(c, slots ? (size_t)slots : 1)) != ZKV_OK) return rc;
+        agg = R > 0 && c->agg_cap >= c->ws.cap && pset_agg_chunk_slots(c->ws.cap, sub) > 0;       // (the aggregate buffers could be allocated)
+    }
+    if (!agg) { R = 0; lanes = pset_choose(c->gs_totals.data(), K, c->lanes, wave_below(), wide_below(), c->gs_start.data(), &slots); }
     const size_t M = (size_t)slots;
     if ((rc = ctx_ready(c, M ? M : 1)) != ZKV_OK) return rc;     // (growing frees buffers, which synchronises the device)
     if ((rc = grow(&c->mx[8], &c->mx_cap[8], 4 * M + 4)) != ZKV_OK || (rc = grow(&c->mx[9], &c->mx_cap[9], 4 * M + 4)) != ZKV_OK ||
@@ -2863,7 +2970,27 @@ static int run_pset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
     launch_gset_place(p, (const uint64_t*)c->mx[7], s);
     HIP_TRY(hipGetLastError());
     const size_t cap = c->ws.cap;                            // (a power of two >= 4,096 or ZKV_CHUNK, a multiple of 64: chunks keep the 64-slot groups)
-    for (size_t base = 0; base < M; base += cap) {
+    if (agg) {
+        // aggregate chunks end on multiples of max(64, sub), so no sub-batch straddles two of them
+        const size_t capa = (size_t)pset_agg_chunk_slots(cap, sub);
+        std::vector<GsetAggChunk> plan;
+        c->gs_amap.clear();
+        for (size_t base = 0; base < R; base += capa) plan.push_back(pset_agg_chunk(c, base, R - base < capa ? (size_t)R - base : capa, sub));
+        if ((rc = grow(&c->mx[10], &c->mx_cap[10], 4 * c->gs_amap.size() + 4)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(c->mx[10], c->gs_amap.data(), 4 * c->gs_amap.size(), hipMemcpyHostToDevice, s));
+        for (const GsetAggChunk& g : plan) {
+            PsetChunk ch;
+            memset(&ch, 0, sizeof ch);
+            ch.m = g.m; ch.slot0 = g.base; ch.idx = p.idx; ch.skey = p.skey;
+            ch.keys = c->d_pkey; ch.ok = c->d_ps_ok;
+            ch.proofs = d_proofs; ch.proof_stride = (uint32_t)pset_proof_stride(c);
+            ch.inputs = d_inputs; ch.input_stride = (uint32_t)pset_input_stride(c);
+            ch.plonk_tab = c->d_plonk_tab; ch.status = c->d_st_all + g.base;
+            enqueue_pset_agg(c, ch, g, p.skey + g.base, (const uint32_t*)c->mx[10], sub, s, M == R && g.base + g.m >= R);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    for (size_t base = (size_t)R; base < M; base += cap) {
         const size_t m = M - base < cap ? M - base : cap;
         const bool timed = base + cap >= M;
         PsetChunk ch;
@@ -3093,7 +3220,7 @@ ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t
         return ZKV_OK;
     }
     if (c->vm != ZKV_VM_RISC0 && c->vm != ZKV_VM_RISC0_SET && c->vm != ZKV_VM_SP1 && c->vm != ZKV_VM_GROTH16 && c->vm != ZKV_VM_SP1_PLONK &&
-        c->vm != ZKV_VM_GROTH16_SET && c->vm != ZKV_VM_PLONK && c->vm != ZKV_VM_PLONK_SET)     // (a PLONK set accepts it and runs the per-proof path)
+        c->vm != ZKV_VM_GROTH16_SET && c->vm != ZKV_VM_PLONK && c->vm != ZKV_VM_PLONK_SET)
         return enable ? ZKV_ERR_INVALID_ARG : ZKV_OK;
     {
         std::lock_guard<std::mutex> lk(c->mu);

@@ -83,4 +83,60 @@ inline uint64_t gset_agg_slot(uint32_t k, uint32_t rank, const uint32_t* agg, co
     return rank < agg[k] ? astart[k] + rank : pstart[k] + (rank - agg[k]);
 }
 
+// Aggregate check on a PLONK key set (zkv_plonk_set_agg.h).  A PLONK key gives the pairing check nothing but its two
+// G2 points, so a sub-batch may hold proofs of any keys of one SRS class (keys with the same [1]_2 | [tau]_2 bytes): cls[k] is key k's class,
+// capable[c] whether class c's points passed the set-up validation.  Key groups stay on 64-slot boundaries (PREP wavefronts stay
+// key-uniform) but are ordered class by class, the capable classes first, and every class region starts on a multiple of
+// A = gset_agg_unit(sub) slots: a sub-batch is `sub` consecutive slots of a class region whatever keys they belong to, pad slots included as
+// dead lanes, and no sub-batch spans two classes.  Slots [0, R) are the capable classes' regions (the aggregate region), [R, slots) those of
+// the other classes (per-proof path).  A class without proofs takes no slots.
+// start[k]: first slot of key k's group (NOT monotone in k; start[n_keys] = slots); cbeg[c], cend[c]: class c's region (cend a multiple of A).
+// Returns the per-proof region's Miller mapping (pset_choose's policy applied to its proofs); *agg_slots = R.
+inline int pset_agg_choose(const uint32_t* cnt, const uint32_t* cls, uint32_t n_keys, const uint8_t* capable, uint32_t n_cls, uint32_t sub, int fixed,
+                           uint64_t wave_below, uint64_t wide_below, uint64_t* start, uint64_t* cbeg, uint64_t* cend, uint64_t* agg_slots, uint64_t* slots) {
+    const uint64_t unit = gset_agg_unit(sub);
+    for (uint32_t c = 0; c < n_cls; c++) cend[c] = 0;
+    for (uint32_t k = 0; k < n_keys; k++) cend[cls[k]] += ((uint64_t)cnt[k] + 63) / 64 * 64;       // the class's slots before rounding up to A
+    uint64_t s = 0, rest = 0;
+    for (int pass = 0; pass < 2; pass++) {                      // capable classes, then the others, each in class order
+        for (uint32_t c = 0; c < n_cls; c++) {
+            if ((capable[c] != 0) != (pass == 0)) continue;
+            cbeg[c] = s;
+            s += (cend[c] + unit - 1) / unit * unit;
+        }
+        if (pass == 0) *agg_slots = s;
+    }
+    *slots = s;
+    for (uint32_t c = 0; c < n_cls; c++) cend[c] = cbeg[c];     // running first free slot of the class
+    for (uint32_t k = 0; k < n_keys; k++) {
+        start[k] = cend[cls[k]];
+        cend[cls[k]] += ((uint64_t)cnt[k] + 63) / 64 * 64;
+        if (!capable[cls[k]]) rest += cnt[k];
+    }
+    start[n_keys] = s;
+    for (uint32_t c = 0; c < n_cls; c++) cend[c] = cbeg[c] + (cend[c] - cbeg[c] + unit - 1) / unit * unit;
+    if (fixed == 64 || fixed == 128 || (!fixed && rest <= wave_below)) return 64;
+    if (fixed == 16 || (!fixed && rest <= wide_below)) return 16;
+    return 2;
+}
+// SRS classes of a PLONK set: class_of[k] numbered by first appearance in key order, by byte equality of the 256 G2 bytes (g2: 256 bytes per
+// key); rep[c]: the first key of class c (rep may be null).  Returns the number of classes.
+inline uint32_t pset_srs_classes(const uint8_t* g2, uint32_t n_keys, uint32_t* class_of, uint32_t* rep) {
+    uint32_t n_cls = 0;
+    for (uint32_t k = 0; k < n_keys; k++) {
+        uint32_t c = n_cls;
+        for (uint32_t j = 0; j < k; j++) {
+            bool eq = true;
+            for (uint32_t b = 0; b < 256 && eq; b++) eq = g2[256 * (size_t)j + b] == g2[256 * (size_t)k + b];
+            if (eq) { c = class_of[j]; break; }
+        }
+        class_of[k] = c;
+        if (c == n_cls) { if (rep) rep[n_cls] = k; n_cls++; }
+    }
+    return n_cls;
+}
+// Where aggregate chunks over [0, R) end when the workspace holds `cap` slots: multiples of A, so no sub-batch straddles two chunks
+// (0: the workspace is smaller than one unit and the call takes the per-proof path).
+inline uint64_t pset_agg_chunk_slots(uint64_t cap, uint32_t sub) { return cap / gset_agg_unit(sub) * gset_agg_unit(sub); }
+
 }  // namespace zkv

@@ -212,6 +212,11 @@ struct PsetChunk {
 };
 void launch_pset_setup(uint32_t n_keys, const PlonkKeyRaw* d_raw, PlonkKey* d_keys, const VkTables* d_tabs, uint32_t* d_ok, hipStream_t s);
 void launch_pset_prep(const PsetChunk& c, const Workspace& ws, hipStream_t s);
+// Aggregate check on a PLONK set (k_pset_agg.hip; the layout: zkv_gset_layout.h pset_agg_choose).  psl: pseudo-proof slot per sub-batch of the
+// chunk's m slots (m a multiple of max(64, sub)); sub <= 64 here, sub-batches of 128 / 256 slots park 64-slot sums for the combine step.
+void launch_pset_agg_reduce(size_t m, uint32_t sub, const Workspace& ws, const uint32_t* agg, const Workspace& ws2, uint8_t* status2, const uint32_t* psl,
+                            bool park, hipStream_t s);
+void launch_pset_agg_combine(size_t n2, uint32_t wide, const Workspace& ws2, uint8_t* status2, const uint32_t* psl, hipStream_t s);
 
 // k_wide.hip: consumer wavefronts that timed out waiting for their producer on the current device (always 0 unless a wavefront died)
 int read_wait_faults(unsigned long long* out);

@@ -155,6 +155,25 @@ class PlonkVerifierSet:
         """Device set-up (every key's tables, about 24 MB per key) and buffers for batches of up to n proofs, ahead of the first batch."""
         _lib.check(self._L.zkv_ctx_reserve(self._h, n), 'zkv_ctx_reserve')
 
+    def set_aggregate_check(self, enable=True, seed=None, sub_batch=None):
+        """Opt-in aggregate check (include/zkv_plonk_set_agg.h): the pairing equation is checked per sub-batch of 16 ... 256 slots (None:
+        chosen by the failure rate seen), sub-batches running across the keys of one SRS class, when the mapping is automatic and a call
+        places at least ZKV_AGG_MIN proofs; the verdicts stay the per-proof ones."""
+        if sub_batch is not None and sub_batch not in (16, 32, 64, 128, 256):
+            raise ValueError('sub_batch must be None, 16, 32, 64, 128 or 256')
+        from .risc0 import _set_aggregate_check
+        _set_aggregate_check(self._L, self._h, enable, seed, sub_batch)
+
+    def aggregate_counters(self):
+        """(sub-batches checked in aggregate, sub-batches that failed and were verified proof by proof)."""
+        from .risc0 import _aggregate_counters
+        return _aggregate_counters(self._L, self._h)
+
+    def srs_classes(self):
+        """(class of every key, number of classes): keys with equal [1]_2 | [tau]_2 bytes are one SRS class and share sub-batches."""
+        from . import plonk_set_agg
+        return plonk_set_agg.srs_classes(self._h, self.size())
+
     def set_lanes_per_proof(self, lanes):
         """Miller-loop mapping (0 = automatic, 2, 16, 64; 128 runs as 64: PLONK has no variable pair).  Same results."""
         _lib.check(self._L.zkv_ctx_set_lanes_per_proof(self._h, lanes), 'zkv_ctx_set_lanes_per_proof')
