@@ -279,6 +279,29 @@ static size_t wave_below() {
     const char* e = getenv("ZKV_WAVE_BELOW");
     return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)2048;
 }
+// The mapping policy, in its one place: lanes per proof of the Miller loop of n proofs on context c -- what the caller fixed
+// (zkv_ctx_set_lanes_per_proof), else by the thresholds above: 128 (two wavefronts per proof), 64 (one), 16, or 2 (lane pairs).  Every chunk,
+// tail, pseudo-proof batch and Groth16 key-set layout asks here (DESIGN.md section 11b has the table of call sites).
+static int miller_lanes(const zkv_ctx* c, size_t n) {
+    if (c->lanes) return c->lanes;
+    if (n <= dual_below()) return 128;
+    if (n <= wave_below()) return 64;
+    if (n <= wide_below()) return 16;
+    return 2;
+}
+// The single-key kernels of a mapping (launch_gset_miller is the key-set counterpart).  The final exponentiation has no two-wavefront
+// kernel: 128 takes the one-wavefront one.
+static void launch_miller_lanes(int lanes, size_t n, const VkTables* tab, const Workspace& ws, uint8_t* status, hipStream_t s) {
+    if (lanes == 128) launch_miller_w64d(n, tab, ws, status, s);
+    else if (lanes == 64) launch_miller_w64(n, tab, ws, s);
+    else if (lanes == 16) launch_miller_w(n, tab, ws, s);
+    else launch_miller2(n, tab, ws, status, s);
+}
+static void launch_finalexp_lanes(int lanes, size_t n, const Workspace& ws, uint8_t* status, hipStream_t s) {
+    if (lanes == 2) launch_finalexp2(n, ws, status, s);
+    else if (lanes == 16) launch_finalexp_w(n, ws, status, s);
+    else launch_finalexp_w64(n, ws, status, s);
+}
 
 static bool device_is_gfx950(int dev) {
     hipDeviceProp_t p;
@@ -583,18 +606,6 @@ static uint32_t agg_group(uint32_t sub) {
     while (g > 1 && sub / g < 2) g >>= 1;
     return g;
 }
-// Miller loop / final exponentiation of n proofs in workspace ws with the kernel family the chunk size selects (as enqueue_chunk does)
-static void launch_miller_by_size(zkv_ctx* c, size_t n, const Workspace& ws, uint8_t* status, hipStream_t s) {
-    if (n <= dual_below()) launch_miller_w64d(n, c->d_tab, ws, status, s);
-    else if (n <= wave_below()) launch_miller_w64(n, c->d_tab, ws, s);
-    else if (n <= wide_below()) launch_miller_w(n, c->d_tab, ws, s);
-    else launch_miller2(n, c->d_tab, ws, status, s);
-}
-static void launch_finalexp_by_size(size_t n, const Workspace& ws, uint8_t* status, hipStream_t s) {
-    if (n <= wave_below()) launch_finalexp_w64(n, ws, status, s);
-    else if (n <= wide_below()) launch_finalexp_w(n, ws, status, s);
-    else launch_finalexp2(n, ws, status, s);
-}
 // enable = 1 ("automatic"): before a chunk is enqueued, and only if everything enqueued earlier on this context has finished (no
 // waiting), the counters tell which fraction of the sub-batches checked since the last look failed; from it the rate p of proofs that
 // fail at the pairing, and from p the size for the coming chunks: a failed sub-batch costs its `sub` proofs a second, ordinary
@@ -673,6 +684,7 @@ static void enqueue_agg(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool timed
     const size_t n2 = sub > 64 ? (a.n + sub - 1) / sub : n64 * (64 / sub);      // the last block counted in full (empty sub-batches switch themselves off)
     // proofs per Miller accumulator: ZKV_AGG_GROUP = 1 (k_miller2), 2, 4 or 8 (k_agg_miller); at most the sub-batch's eighth... see agg_group()
     const uint32_t grp = agg_group(sub64);
+    const int lanes2 = miller_lanes(c, n2);                   // the pseudo-proofs' mapping (automatic: the check runs only with c->lanes == 0)
     const InstTab* inst = a.inst ? c->d_inst : nullptr;
     agg_next_coefficients(c);
     // vk_x through summed scalars: one key (no per-proof base) and at most two per-proof signals
@@ -683,10 +695,10 @@ static void enqueue_agg(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool timed
     else launch_miller2(a.n, c->d_tab, c->ws, a.status, s);
     launch_agg_reduce(a.n, sub64, sums, grp, c->d_tab, c->ws, c->d_agg, c->d_agg_tab, c->ws2, c->d_status2, sub > 64, s);
     if (sub > 64) launch_agg_combine(n64, n2, sub / 64, c->d_agg_tab, c->ws2, c->d_status2, s);
-    launch_miller_by_size(c, n2, c->ws2, c->d_status2, s);
+    launch_miller_lanes(lanes2, n2, c->d_tab, c->ws2, c->d_status2, s);
     if (timed) (void)hipEventRecord(c->ev[4], s);
     launch_agg_fprod(a.n, n2, sub, grp, c->ws, c->d_agg, c->ws2, s);
-    launch_finalexp_by_size(n2, c->ws2, c->d_status2, s);
+    launch_finalexp_lanes(lanes2, n2, c->ws2, c->d_status2, s);
     launch_agg_mark(a.n, sub, grp, c->ws, c->d_agg, c->d_status2, a.status, c->d_agg_cnt, c->d_agg_idx, s);
     launch_agg_gather(a.n, c->ws, c->d_agg, c->d_agg_cnt, c->d_agg_idx, c->ws3, c->d_status3, s);
     launch_msm(a.n, c->d_tab, c->m16, inst, c->ws3, s);
@@ -702,14 +714,15 @@ static void enqueue_agg_plonk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool
     const uint32_t sub = c->agg_sub, sub64 = sub < 64 ? sub : 64;
     const size_t n64 = (a.n + 63) / 64;
     const size_t n2 = sub > 64 ? (a.n + sub - 1) / sub : n64 * (64 / sub);
+    const int lanes2 = miller_lanes(c, n2);
     agg_next_coefficients(c);
     launch_agg_plonk_g1(a.n, c->ws, c->d_agg, c->agg_seed, s);
     if (timed) { (void)hipEventRecord(c->ev[2], s); (void)hipEventRecord(c->ev[3], s); }
     launch_agg_reduce(a.n, sub64, false, 1, c->d_tab, c->ws, c->d_agg, nullptr, c->ws2, c->d_status2, sub > 64, s);
     if (sub > 64) launch_agg_combine(n64, n2, sub / 64, nullptr, c->ws2, c->d_status2, s);
-    launch_miller_by_size(c, n2, c->ws2, c->d_status2, s);
+    launch_miller_lanes(lanes2, n2, c->d_tab, c->ws2, c->d_status2, s);
     if (timed) (void)hipEventRecord(c->ev[4], s);
-    launch_finalexp_by_size(n2, c->ws2, c->d_status2, s);
+    launch_finalexp_lanes(lanes2, n2, c->ws2, c->d_status2, s);
     launch_agg_mark(a.n, sub, 1, c->ws, c->d_agg, c->d_status2, a.status, c->d_agg_cnt, c->d_agg_idx, s);
     launch_agg_plonk_norm(a.n, c->ws, c->d_agg, c->d_agg_cnt, c->d_agg_idx, c->ws3, c->d_status3, s);
     launch_miller2(a.n, c->d_tab, c->ws3, c->d_status3, s);
@@ -747,12 +760,11 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
             return;
         }
         if (timed) { (void)hipEventRecord(c->ev[1], s); (void)hipEventRecord(c->ev[2], s); (void)hipEventRecord(c->ev[3], s); }
-        const int pl = c->lanes ? c->lanes : 2;
-        const bool wave_p = pl == 64 || pl == 128 || (c->lanes == 0 && a.n <= wave_below());      // (no variable pair: nothing for a second wavefront to do)
-        const bool wide_p = wave_p || pl == 16 || (c->lanes == 0 && a.n <= wide_below());
-        if (wave_p) launch_miller_w64(a.n, c->d_tab, c->ws, s); else if (wide_p) launch_miller_w(a.n, c->d_tab, c->ws, s); else launch_miller2(a.n, c->d_tab, c->ws, a.status, s);
+        int pl = miller_lanes(c, a.n);
+        if (pl == 128) pl = 64;                              // (no variable pair: nothing for a second wavefront to do)
+        launch_miller_lanes(pl, a.n, c->d_tab, c->ws, a.status, s);
         if (timed) (void)hipEventRecord(c->ev[4], s);
-        if (wave_p) launch_finalexp_w64(a.n, c->ws, a.status, s); else if (wide_p) launch_finalexp_w(a.n, c->ws, a.status, s); else launch_finalexp2(a.n, c->ws, a.status, s);
+        launch_finalexp_lanes(pl, a.n, c->ws, a.status, s);
         if (timed) (void)hipEventRecord(c->ev[5], s);
         return;
     }
@@ -780,18 +792,19 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
         launch_g2chk2(tail, wt, a.status + head, st);
         if (timed) (void)hipEventRecord(c->ev[3], s);
         launch_miller2(head, c->d_tab, c->ws, a.status, s);
-        launch_miller_by_size(c, tail, wt, a.status + head, st);
+        const int tl = miller_lanes(c, tail);                // (automatic: a fixed mapping takes no tail split)
+        launch_miller_lanes(tl, tail, c->d_tab, wt, a.status + head, st);
         if (timed) (void)hipEventRecord(c->ev[4], s);
         launch_finalexp2(head, c->ws, a.status, s);
-        launch_finalexp_by_size(tail, wt, a.status + head, st);
+        launch_finalexp_lanes(tl, tail, wt, a.status + head, st);
         if (beside) { (void)hipEventRecord(c->ev_join, c->side); (void)hipStreamWaitEvent(s, c->ev_join, 0); }
         if (timed) (void)hipEventRecord(c->ev[5], s);
         return;
     }
-    const int lanes = c->lanes ? c->lanes : 2;       // 2 = one proof per lane pair; 16 = one proof per 16 lanes (small chunks); 64 = per wavefront (smallest)
-    const bool dual = lanes == 128 || (c->lanes == 0 && a.n <= dual_below());       // 128 = two wavefronts per proof in the Miller loop
-    const bool wave = dual || lanes == 64 || (c->lanes == 0 && a.n <= wave_below());
-    const bool wide = wave || lanes == 16 || (c->lanes == 0 && a.n <= wide_below());
+    // 2 = one proof per lane pair; 16 = one proof per 16 lanes (small chunks); 64 = per wavefront (smaller); 128 = two wavefronts per proof
+    // in the Miller loop (smallest)
+    const int lanes = miller_lanes(c, a.n);
+    const bool wide = lanes != 2;
     // Lane-pair kernels: the Miller loop itself is the subgroup test of B (miller_loop_p), there is no separate check; stage time
     // [2] is then 0.  16-lane kernels (small chunks, most of the chip idle): the check (k_g2chk2) only needs the PREP output and only
     // its verdict (ws.g2bad; the MSM owns ws.flags) is needed, by the final exponentiation, so it runs on a second stream beside the
@@ -809,15 +822,10 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
     if (timed) (void)hipEventRecord(c->ev[2], s);
     if (wide && !fork) launch_g2chk2(a.n, c->ws, a.status, s);
     if (timed) (void)hipEventRecord(c->ev[3], s);
-    if (dual) launch_miller_w64d(a.n, c->d_tab, c->ws, a.status, s);
-    else if (wave) launch_miller_w64(a.n, c->d_tab, c->ws, s);
-    else if (wide) launch_miller_w(a.n, c->d_tab, c->ws, s);
-    else launch_miller2(a.n, c->d_tab, c->ws, a.status, s);
+    launch_miller_lanes(lanes, a.n, c->d_tab, c->ws, a.status, s);
     if (timed) (void)hipEventRecord(c->ev[4], s);
     if (fork) (void)hipStreamWaitEvent(s, c->ev_join, 0);     // the final exponentiation reads the verdict of the subgroup check
-    if (wave) launch_finalexp_w64(a.n, c->ws, a.status, s);
-    else if (wide) launch_finalexp_w(a.n, c->ws, a.status, s);
-    else launch_finalexp2(a.n, c->ws, a.status, s);
+    launch_finalexp_lanes(lanes, a.n, c->ws, a.status, s);
     if (timed) (void)hipEventRecord(c->ev[5], s);
 }
 
@@ -2478,14 +2486,6 @@ ZKV_EXPORT int zkv_groth16_set_key_n_ic(const zkv_ctx* c, size_t key) {
     if (!c || c->vm != ZKV_VM_GROTH16_SET) return ZKV_ERR_WRONG_CTX;
     return key < c->gs_nic.size() ? (int)c->gs_nic[key] : ZKV_ERR_INVALID_ARG;
 }
-// The Miller-loop mapping the automatic policy picks for a batch of n proofs (as enqueue_chunk does for a chunk), in lanes per proof
-static int gset_auto_lanes(const zkv_ctx* c, size_t n) {
-    if (c->lanes) return c->lanes;
-    if (n <= dual_below()) return 128;
-    if (n <= wave_below()) return 64;
-    if (n <= wide_below()) return 16;
-    return 2;
-}
 // Aggregate check on a set: every key's AggTables (k_setup_agg's contents, 0.53 MB per key) in d_agg_tab and which keys can take the check,
 // built the first time a call wants the check -- not at set creation, so a set that never uses it does not grow -- and the counters.
 // false: no key can, or no room (the call then runs the per-proof path).
@@ -2520,32 +2520,80 @@ static bool gset_agg_tables(zkv_ctx* c) {
     for (uint32_t k = 0; k < K; k++) { c->gs_agg_ok[k] = ok[k] ? 1 : 0; c->agg_key_ok = c->agg_key_ok || ok[k]; }
     return c->agg_key_ok;
 }
-// One aggregate chunk's pseudo-proofs: n2 sub-batches, laid out per key and padded to the proofs per wavefront of the Miller mapping
-// `lanes` (gset_choose over the sub-batch counts, as the proofs themselves), so k_gset_miller* take one key per wavefront.  In gs_amap from
-// word `off`: psl (sub-batch -> slot, n2 words), then the key of every pseudo slot (slots words).
+// ---- The steps of a call that both kinds of key set take (run_gset, run_pset: each keeps its own layout choice, placement and stages).
+// Partition: the proofs counted per key, block by block; the per-key totals come back to the host (gs_totals: the call's one
+// synchronisation) and *placed is their sum.
+static int set_partition(zkv_ctx* c, size_t n, uint32_t K, const uint32_t* d_key, hipStream_t s, GsetPart* p, size_t* placed) {
+    memset(p, 0, sizeof *p);
+    p->n = n; p->n_keys = K;
+    size_t per = (n + 255) / 256;                            // at most 256 partition blocks of a multiple of 64 proofs
+    per = (per + 63) / 64 * 64;
+    p->per_block = (uint32_t)per; p->blocks = (uint32_t)((n + per - 1) / per);
+    const size_t kb = (size_t)K * p->blocks;
+    int rc;
+    if ((rc = grow(&c->mx[3], &c->mx_cap[3], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[4], &c->mx_cap[4], 4 * (size_t)K)) != ZKV_OK ||
+        (rc = grow(&c->mx[5], &c->mx_cap[5], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[6], &c->mx_cap[6], 4 * n)) != ZKV_OK ||
+        (rc = grow(&c->mx[7], &c->mx_cap[7], 8 * ((size_t)K + 1))) != ZKV_OK) return rc;
+    p->key = d_key; p->cnt = (uint32_t*)c->mx[3]; p->totals = (uint32_t*)c->mx[4]; p->off = (uint32_t*)c->mx[5]; p->pos = (uint32_t*)c->mx[6];
+    HIP_TRY(hipMemsetAsync(p->totals, 0, 4 * (size_t)K, s));
+    launch_gset_count(*p, s);
+    HIP_TRY(hipGetLastError());
+    c->gs_totals.resize(K); c->gs_start.resize((size_t)K + 1);
+    HIP_TRY(hipMemcpyAsync(c->gs_totals.data(), p->totals, 4 * (size_t)K, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *placed = 0;
+    for (uint32_t k = 0; k < K; k++) *placed += c->gs_totals[k];
+    return ZKV_OK;
+}
+// Slot buffers of a layout of M slots: the proof of every slot, its key and its status byte.
+static int set_slot_buffers(zkv_ctx* c, size_t M, GsetPart* p, hipStream_t s) {
+    int rc;
+    if ((rc = grow(&c->mx[8], &c->mx_cap[8], 4 * M + 4)) != ZKV_OK || (rc = grow(&c->mx[9], &c->mx_cap[9], 4 * M + 4)) != ZKV_OK ||
+        (rc = grow(&c->d_st_all, &c->st_all_cap, M + 1)) != ZKV_OK) return rc;
+    p->idx = (uint32_t*)c->mx[8]; p->skey = (uint32_t*)c->mx[9];
+    HIP_TRY(hipMemsetAsync(p->idx, 0xFF, 4 * M + 4, s));     // pad slots: GSET_NONE
+    HIP_TRY(hipMemsetAsync(p->skey, 0, 4 * M + 4, s));       // (and key 0: a slot's key is only read for live slots, this keeps any read in the set)
+    return ZKV_OK;
+}
+// The aggregate chunks of the aggregate region [0, R), `capa` slots each, and their pseudo-proof maps (zkv_gset_layout.h
+// gset_agg_chunk_plan, whose regions the caller passes on): chunk g's map is in gs_amap from word g.off -- psl (sub-batch -> pseudo slot, n2
+// words), then the key of every pseudo slot (slots words) -- and all of gs_amap goes to mx[10] in one copy.
 struct GsetAggChunk { size_t base, m, n2, off; uint64_t slots; int lanes; };
-static GsetAggChunk gset_agg_chunk(zkv_ctx* c, size_t base, size_t m, uint32_t sub) {
-    const uint32_t K = (uint32_t)c->gs_nic.size();
-    GsetAggChunk g{base, m, m / sub, c->gs_amap.size(), 0, 0};
-    c->gs_nsb.assign(K, 0);
-    c->gs_pst.resize((size_t)K + 1);
-    const uint64_t* astart = c->gs_map.data();
-    for (uint32_t k = 0; k < K; k++) {
-        const uint64_t lo = astart[k] > base ? astart[k] : base, hi = astart[k] + c->gs_agg_n[k] < base + m ? astart[k] + c->gs_agg_n[k] : base + m;
-        if (hi > lo) c->gs_nsb[k] = (uint32_t)((hi - lo) / sub);
+static int set_agg_plan(zkv_ctx* c, const uint64_t* beg, const uint64_t* end, const uint32_t* rep, uint32_t n_regions, uint64_t R, size_t capa,
+                        uint32_t sub, std::vector<GsetAggChunk>* plan, hipStream_t s) {
+    c->gs_amap.clear();
+    c->gs_nsb.assign(n_regions, 0); c->gs_pst.resize((size_t)n_regions + 1);
+    for (size_t base = 0; base < R; base += capa) {
+        const size_t m = R - base < capa ? (size_t)R - base : capa;
+        GsetAggChunk g{base, m, m / sub, c->gs_amap.size(), 0, 0};
+        c->gs_amap.resize(g.off + 2 * g.n2 + 31 * (size_t)n_regions, 0);      // (the most the padding can take; cut to the slots below)
+        uint32_t* psl = c->gs_amap.data() + g.off;
+        g.lanes = gset_agg_chunk_plan(beg, end, rep, n_regions, base, m, sub, miller_lanes(c, g.n2), c->ws2.cap, c->gs_nsb.data(), c->gs_pst.data(),
+                                      psl, psl + g.n2, &g.slots);
+        c->gs_amap.resize(g.off + g.n2 + g.slots);
+        plan->push_back(g);
     }
-    g.lanes = gset_choose(c->gs_nsb.data(), K, gset_auto_lanes(c, g.n2), 0, c->gs_pst.data(), &g.slots);
-    if (g.slots > c->ws2.cap) g.lanes = gset_choose(c->gs_nsb.data(), K, 64, 1, c->gs_pst.data(), &g.slots);     // (no padding)
-    c->gs_amap.resize(g.off + g.n2 + g.slots, 0);
-    uint32_t* psl = c->gs_amap.data() + g.off;
-    uint32_t* skey2 = psl + g.n2;
-    for (uint32_t k = 0; k < K; k++) {
-        if (!c->gs_nsb[k]) continue;
-        const size_t sb0 = (size_t)((astart[k] > base ? astart[k] : base) - base) / sub;
-        for (uint32_t t = 0; t < c->gs_nsb[k]; t++) psl[sb0 + t] = (uint32_t)(c->gs_pst[k] + t);
-        for (uint64_t q = c->gs_pst[k]; q < c->gs_pst[k + 1]; q++) skey2[q] = k;
-    }
-    return g;
+    const int rc = grow(&c->mx[10], &c->mx_cap[10], 4 * c->gs_amap.size() + 4);
+    if (rc != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c->mx[10], c->gs_amap.data(), 4 * c->gs_amap.size(), hipMemcpyHostToDevice, s));
+    return ZKV_OK;
+}
+// The verdicts back to the caller's order (a call that placed no proof still records the six stage events).
+static int set_return(zkv_ctx* c, size_t n, size_t M, const GsetPart& p, uint8_t* d_verified, hipStream_t s) {
+    if (!M) for (int e = 0; e < 6; e++) (void)hipEventRecord(c->ev[e], s);
+    launch_gset_return(n, p.pos, c->d_st_all, d_verified, s);
+    HIP_TRY(hipGetLastError());
+    return ZKV_OK;
+}
+// Slots [base, base + m) of a Groth16 set's layout as one chunk
+static GsetChunk gset_chunk_of(const zkv_ctx* c, const GsetPart& p, const uint8_t* d_proofs, const uint8_t* d_signals, size_t base, size_t m) {
+    GsetChunk ch;
+    memset(&ch, 0, sizeof ch);
+    ch.m = m; ch.slot0 = base; ch.idx = p.idx; ch.skey = p.skey;
+    ch.keys = c->d_gs_key; ch.rows = c->d_gs_rows; ch.win = c->d_gs_win;
+    ch.proofs = d_proofs; ch.signals = d_signals; ch.sig_stride = 32 * (c->g_n_ic - 1);
+    ch.sig = c->d_lsig; ch.sig_cap = c->lsig_cap; ch.status = c->d_st_all + base;
+    return ch;
 }
 // The aggregate check of one chunk of a set's aggregate region (zkv_agg.h; k_gset_agg.hip): PREP, the coefficients and r A', r C, the
 // Miller loop of the variable pair, one pseudo-proof per sub-batch with its key's gamma / delta lines and ML(alpha, beta), the product of the
@@ -2571,9 +2619,7 @@ static void enqueue_gset_agg(zkv_ctx* c, const GsetChunk& ch, const GsetAggChunk
     launch_gset_miller(g.lanes, (size_t)g.slots, skey2, c->d_gs_key, c->ws2, c->d_status2, s);
     if (timed) (void)hipEventRecord(c->ev[4], s);
     launch_gset_agg_fprod(m, g.n2, sub, grp, c->ws, c->d_agg, c->ws2, psl, s);
-    if (g.lanes == 2) launch_finalexp2((size_t)g.slots, c->ws2, c->d_status2, s);
-    else if (g.lanes == 16) launch_finalexp_w((size_t)g.slots, c->ws2, c->d_status2, s);
-    else launch_finalexp_w64((size_t)g.slots, c->ws2, c->d_status2, s);
+    launch_finalexp_lanes(g.lanes, (size_t)g.slots, c->ws2, c->d_status2, s);
     launch_gset_agg_mark(m, sub, grp, c->ws, c->d_agg, c->d_status2, psl, ch.status, c->d_agg_cnt, s);
     launch_gset_msm(ch, msm_lanes_long(c, m), c->ws, s);
     launch_gset_miller(2, m, skey, c->d_gs_key, c->ws, ch.status, s);       // (lane pairs: the subgroup test of B included)
@@ -2586,25 +2632,9 @@ static void enqueue_gset_agg(zkv_ctx* c, const GsetChunk& ch, const GsetAggChunk
 static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* d_proofs, const uint8_t* d_signals, uint8_t* d_verified, hipStream_t s) {
     const uint32_t K = (uint32_t)c->gs_nic.size();
     GsetPart p;
-    memset(&p, 0, sizeof p);
-    p.n = n; p.n_keys = K;
-    size_t per = (n + 255) / 256;                            // at most 256 partition blocks of a multiple of 64 proofs
-    per = (per + 63) / 64 * 64;
-    p.per_block = (uint32_t)per; p.blocks = (uint32_t)((n + per - 1) / per);
-    const size_t kb = (size_t)K * p.blocks;
-    int rc;
-    if ((rc = grow(&c->mx[3], &c->mx_cap[3], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[4], &c->mx_cap[4], 4 * (size_t)K)) != ZKV_OK ||
-        (rc = grow(&c->mx[5], &c->mx_cap[5], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[6], &c->mx_cap[6], 4 * n)) != ZKV_OK ||
-        (rc = grow(&c->mx[7], &c->mx_cap[7], 8 * ((size_t)K + 1))) != ZKV_OK) return rc;
-    p.key = d_key; p.cnt = (uint32_t*)c->mx[3]; p.totals = (uint32_t*)c->mx[4]; p.off = (uint32_t*)c->mx[5]; p.pos = (uint32_t*)c->mx[6];
-    HIP_TRY(hipMemsetAsync(p.totals, 0, 4 * (size_t)K, s));
-    launch_gset_count(p, s);
-    HIP_TRY(hipGetLastError());
-    c->gs_totals.resize(K); c->gs_start.resize((size_t)K + 1);
-    HIP_TRY(hipMemcpyAsync(c->gs_totals.data(), p.totals, 4 * (size_t)K, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
     size_t placed = 0;
-    for (uint32_t k = 0; k < K; k++) placed += c->gs_totals[k];
+    int rc;
+    if ((rc = set_partition(c, n, K, d_key, s, &p, &placed)) != ZKV_OK) return rc;
     // The aggregate check (a fixed mapping, a small call or no capable key: none): the aggregate region [0, R) and the per-proof region
     // (zkv_gset_layout.h gset_agg_choose); R = 0 falls back to the one-region layout below.
     bool agg = c->agg_on && c->lanes == 0 && placed >= agg_min() && gset_agg_tables(c) && agg_wanted(c);
@@ -2616,7 +2646,7 @@ static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
         c->gs_agg_n.resize(K); c->gs_rest.resize(K); c->gs_map.assign(3 * ((size_t)K + 1), 0);
         size_t rest = 0;
         for (uint32_t k = 0; k < K; k++) rest += c->gs_agg_ok[k] ? c->gs_totals[k] % unit : c->gs_totals[k];
-        lanes = gset_agg_choose(c->gs_totals.data(), c->gs_agg_ok.data(), K, sub, gset_auto_lanes(c, rest), 0, c->gs_agg_n.data(), c->gs_map.data(),
+        lanes = gset_agg_choose(c->gs_totals.data(), c->gs_agg_ok.data(), K, sub, miller_lanes(c, rest), 0, c->gs_agg_n.data(), c->gs_map.data(),
                                 c->gs_rest.data(), c->gs_map.data() + K + 1, &R, &slots);
         for (uint32_t k = 0; k < K; k++) c->gs_map[2 * ((size_t)K + 1) + k] = c->gs_agg_n[k];
         if ((rc = groth16_ready(c, (size_t)slots, &cap)) != ZKV_OK) return rc;
@@ -2624,15 +2654,11 @@ static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
     }
     if (!agg) {
         R = 0;
-        lanes = gset_choose(c->gs_totals.data(), K, gset_auto_lanes(c, placed), c->lanes != 0, c->gs_start.data(), &slots);
+        lanes = gset_choose(c->gs_totals.data(), K, miller_lanes(c, placed), c->lanes != 0, c->gs_start.data(), &slots);
     }
     const size_t M = (size_t)slots;
     if ((rc = groth16_ready(c, M ? M : 1, &cap)) != ZKV_OK) return rc;     // (growing frees buffers, which synchronises the device)
-    if ((rc = grow(&c->mx[8], &c->mx_cap[8], 4 * M + 4)) != ZKV_OK || (rc = grow(&c->mx[9], &c->mx_cap[9], 4 * M + 4)) != ZKV_OK ||
-        (rc = grow(&c->d_st_all, &c->st_all_cap, M + 1)) != ZKV_OK) return rc;
-    p.idx = (uint32_t*)c->mx[8]; p.skey = (uint32_t*)c->mx[9];
-    HIP_TRY(hipMemsetAsync(p.idx, 0xFF, 4 * M + 4, s));      // pad slots: GSET_NONE
-    HIP_TRY(hipMemsetAsync(p.skey, 0, 4 * M + 4, s));        // (and key 0: a slot's key is only read for live slots, this keeps any read in the set)
+    if ((rc = set_slot_buffers(c, M, &p, s)) != ZKV_OK) return rc;
     if (agg) {
         if ((rc = grow(&c->mx[7], &c->mx_cap[7], 8 * (c->gs_map.size() + K + 1))) != ZKV_OK) return rc;
         HIP_TRY(hipMemsetAsync(c->mx[7] + 8 * c->gs_map.size(), 0, 8 * ((size_t)K + 1), s));      // zero starts: k_gset_scan gives ranks
@@ -2644,34 +2670,20 @@ static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
     }
     HIP_TRY(hipGetLastError());
     if (agg) {
-        // aggregate chunks end on multiples of the unit, so no sub-batch and no 64-proof block straddles two of them
-        const size_t capa = cap / unit * unit;
+        // aggregate chunks end on multiples of the unit, so no sub-batch and no 64-proof block straddles two of them; a region per key:
+        // the keys lie back to back (astart[k + 1] = astart[k] + agg[k]) and stand for themselves
         std::vector<GsetAggChunk> plan;
-        c->gs_amap.clear();
-        for (size_t base = 0; base < R; base += capa) plan.push_back(gset_agg_chunk(c, base, R - base < capa ? (size_t)R - base : capa, sub));
-        if ((rc = grow(&c->mx[10], &c->mx_cap[10], 4 * c->gs_amap.size() + 4)) != ZKV_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(c->mx[10], c->gs_amap.data(), 4 * c->gs_amap.size(), hipMemcpyHostToDevice, s));
+        if ((rc = set_agg_plan(c, c->gs_map.data(), c->gs_map.data() + 1, nullptr, K, R, cap / unit * unit, sub, &plan, s)) != ZKV_OK) return rc;
         for (const GsetAggChunk& g : plan) {
-            GsetChunk ch;
-            memset(&ch, 0, sizeof ch);
-            ch.m = g.m; ch.slot0 = g.base; ch.idx = p.idx; ch.skey = p.skey;
-            ch.keys = c->d_gs_key; ch.rows = c->d_gs_rows; ch.win = c->d_gs_win;
-            ch.proofs = d_proofs; ch.signals = d_signals; ch.sig_stride = 32 * (c->g_n_ic - 1);
-            ch.sig = c->d_lsig; ch.sig_cap = c->lsig_cap; ch.status = c->d_st_all + g.base;
-            enqueue_gset_agg(c, ch, g, p.skey + g.base, (const uint32_t*)c->mx[10], sub, s, M == R && g.base + g.m >= R);
+            enqueue_gset_agg(c, gset_chunk_of(c, p, d_proofs, d_signals, g.base, g.m), g, p.skey + g.base, (const uint32_t*)c->mx[10], sub, s,
+                             M == R && g.base + g.m >= R);
             HIP_TRY(hipGetLastError());
         }
     }
-    const int fe = lanes == 2 ? 2 : lanes == 16 ? 16 : 64;
     for (size_t base = R; base < M; base += cap) {
         const size_t m = M - base < cap ? M - base : cap;
         const bool timed = base + cap >= M;
-        GsetChunk ch;
-        memset(&ch, 0, sizeof ch);
-        ch.m = m; ch.slot0 = base; ch.idx = p.idx; ch.skey = p.skey;
-        ch.keys = c->d_gs_key; ch.rows = c->d_gs_rows; ch.win = c->d_gs_win;
-        ch.proofs = d_proofs; ch.signals = d_signals; ch.sig_stride = 32 * (c->g_n_ic - 1);
-        ch.sig = c->d_lsig; ch.sig_cap = c->lsig_cap; ch.status = c->d_st_all + base;
+        const GsetChunk ch = gset_chunk_of(c, p, d_proofs, d_signals, base, m);
         if (timed) (void)hipEventRecord(c->ev[0], s);
         launch_gset_prep(ch, c->ws, s);
         if (timed) (void)hipEventRecord(c->ev[1], s);
@@ -2681,16 +2693,11 @@ static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
         if (timed) (void)hipEventRecord(c->ev[3], s);
         launch_gset_miller(lanes, m, p.skey + base, c->d_gs_key, c->ws, ch.status, s);
         if (timed) (void)hipEventRecord(c->ev[4], s);
-        if (fe == 2) launch_finalexp2(m, c->ws, ch.status, s);
-        else if (fe == 16) launch_finalexp_w(m, c->ws, ch.status, s);
-        else launch_finalexp_w64(m, c->ws, ch.status, s);
+        launch_finalexp_lanes(lanes, m, c->ws, ch.status, s);
         if (timed) (void)hipEventRecord(c->ev[5], s);
         HIP_TRY(hipGetLastError());
     }
-    if (!M) for (int e = 0; e < 6; e++) (void)hipEventRecord(c->ev[e], s);
-    launch_gset_return(n, p.pos, c->d_st_all, d_verified, s);
-    HIP_TRY(hipGetLastError());
-    return ZKV_OK;
+    return set_return(c, n, M, p, d_verified, s);
 }
 ZKV_EXPORT int zkv_groth16_set_verify_batch_dev(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* d_proofs, const uint8_t* d_signals,
                                                 uint8_t* d_verified, void* stream) {
@@ -2863,32 +2870,16 @@ static bool pset_agg_classes(zkv_ctx* c) {
     for (uint32_t q = 0; q < n_cls; q++) { c->ps_cls_ok[q] = ok[q] ? 1 : 0; c->agg_key_ok = c->agg_key_ok || ok[q]; }
     return c->agg_key_ok;
 }
-// One aggregate chunk's pseudo-proofs (gset_agg_chunk with a class where that has a key): n2 sub-batches, laid out per class and padded to
-// the proofs per wavefront of the Miller mapping `lanes`, so k_gset_miller* take one class per wavefront -- through the class's first key,
-// whose line tables are those of every key of the class.  In gs_amap from word `off`: psl (sub-batch -> slot, n2 words), then the key of every
-// pseudo slot (slots words).
-static GsetAggChunk pset_agg_chunk(zkv_ctx* c, size_t base, size_t m, uint32_t sub) {
-    const uint32_t n_cls = (uint32_t)c->ps_cls_rep.size();
-    GsetAggChunk g{base, m, m / sub, c->gs_amap.size(), 0, 0};
-    c->gs_nsb.assign(n_cls, 0);
-    c->gs_pst.resize((size_t)n_cls + 1);
-    for (uint32_t q = 0; q < n_cls; q++) {
-        if (!c->ps_cls_ok[q]) continue;
-        const uint64_t lo = c->ps_cbeg[q] > base ? c->ps_cbeg[q] : base, hi = c->ps_cend[q] < base + m ? c->ps_cend[q] : base + m;
-        if (hi > lo) c->gs_nsb[q] = (uint32_t)((hi - lo) / sub);
-    }
-    g.lanes = gset_choose(c->gs_nsb.data(), n_cls, gset_auto_lanes(c, g.n2), 0, c->gs_pst.data(), &g.slots);
-    if (g.slots > c->ws2.cap) g.lanes = gset_choose(c->gs_nsb.data(), n_cls, 64, 1, c->gs_pst.data(), &g.slots);     // (no padding)
-    c->gs_amap.resize(g.off + g.n2 + g.slots, 0);
-    uint32_t* psl = c->gs_amap.data() + g.off;
-    uint32_t* skey2 = psl + g.n2;
-    for (uint32_t q = 0; q < n_cls; q++) {
-        if (!c->gs_nsb[q]) continue;
-        const size_t sb0 = (size_t)((c->ps_cbeg[q] > base ? c->ps_cbeg[q] : base) - base) / sub;
-        for (uint32_t t = 0; t < c->gs_nsb[q]; t++) psl[sb0 + t] = (uint32_t)(c->gs_pst[q] + t);
-        for (uint64_t w = c->gs_pst[q]; w < c->gs_pst[q + 1]; w++) skey2[w] = c->ps_cls_rep[q];
-    }
-    return g;
+// Slots [base, base + m) of a PLONK set's layout as one chunk
+static PsetChunk pset_chunk_of(const zkv_ctx* c, const GsetPart& p, const uint8_t* d_proofs, const uint8_t* d_inputs, size_t base, size_t m) {
+    PsetChunk ch;
+    memset(&ch, 0, sizeof ch);
+    ch.m = m; ch.slot0 = base; ch.idx = p.idx; ch.skey = p.skey;
+    ch.keys = c->d_pkey; ch.ok = c->d_ps_ok;
+    ch.proofs = d_proofs; ch.proof_stride = (uint32_t)pset_proof_stride(c);
+    ch.inputs = d_inputs; ch.input_stride = (uint32_t)pset_input_stride(c);
+    ch.plonk_tab = c->d_plonk_tab; ch.status = c->d_st_all + base;
+    return ch;
 }
 // The aggregate check of one chunk of a PLONK set's aggregate region: PREP unchanged, the coefficients and r_i D_i, r_i (-Q_i)
 // (k_agg_plonk_g1: no per-proof Miller loop), one pseudo-proof per sub-batch with its class's [1]_2 / [tau]_2 lines, its final
@@ -2911,9 +2902,7 @@ static void enqueue_pset_agg(zkv_ctx* c, const PsetChunk& ch, const GsetAggChunk
     if (sub > 64) launch_pset_agg_combine(g.n2, sub / 64, c->ws2, c->d_status2, psl, s);
     launch_gset_miller(g.lanes, (size_t)g.slots, skey2, c->d_gs_key, c->ws2, c->d_status2, s);
     if (timed) (void)hipEventRecord(c->ev[4], s);
-    if (g.lanes == 2) launch_finalexp2((size_t)g.slots, c->ws2, c->d_status2, s);
-    else if (g.lanes == 16) launch_finalexp_w((size_t)g.slots, c->ws2, c->d_status2, s);
-    else launch_finalexp_w64((size_t)g.slots, c->ws2, c->d_status2, s);
+    launch_finalexp_lanes(g.lanes, (size_t)g.slots, c->ws2, c->d_status2, s);
     launch_gset_agg_mark(m, sub, 1, c->ws, c->d_agg, c->d_status2, psl, ch.status, c->d_agg_cnt, s);
     launch_gset_miller(2, m, skey, c->d_gs_key, c->ws, ch.status, s);
     launch_finalexp2(m, c->ws, ch.status, s);
@@ -2927,31 +2916,14 @@ static void enqueue_pset_agg(zkv_ctx* c, const PsetChunk& ch, const GsetAggChunk
 static int run_pset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* d_proofs, const uint8_t* d_inputs, uint8_t* d_verified, hipStream_t s) {
     const uint32_t K = (uint32_t)c->ps_raw.size();
     GsetPart p;
-    memset(&p, 0, sizeof p);
-    p.n = n; p.n_keys = K;
-    size_t per = (n + 255) / 256;                            // at most 256 partition blocks of a multiple of 64 proofs
-    per = (per + 63) / 64 * 64;
-    p.per_block = (uint32_t)per; p.blocks = (uint32_t)((n + per - 1) / per);
-    const size_t kb = (size_t)K * p.blocks;
-    int rc;
-    if ((rc = grow(&c->mx[3], &c->mx_cap[3], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[4], &c->mx_cap[4], 4 * (size_t)K)) != ZKV_OK ||
-        (rc = grow(&c->mx[5], &c->mx_cap[5], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[6], &c->mx_cap[6], 4 * n)) != ZKV_OK ||
-        (rc = grow(&c->mx[7], &c->mx_cap[7], 8 * ((size_t)K + 1))) != ZKV_OK) return rc;
-    p.key = d_key; p.cnt = (uint32_t*)c->mx[3]; p.totals = (uint32_t*)c->mx[4]; p.off = (uint32_t*)c->mx[5]; p.pos = (uint32_t*)c->mx[6];
-    HIP_TRY(hipMemsetAsync(p.totals, 0, 4 * (size_t)K, s));
-    launch_gset_count(p, s);
-    HIP_TRY(hipGetLastError());
-    c->gs_totals.resize(K); c->gs_start.resize((size_t)K + 1);
-    HIP_TRY(hipMemcpyAsync(c->gs_totals.data(), p.totals, 4 * (size_t)K, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
     size_t placed = 0;
-    for (uint32_t k = 0; k < K; k++) placed += c->gs_totals[k];
+    int rc;
+    if ((rc = set_partition(c, n, K, d_key, s, &p, &placed)) != ZKV_OK) return rc;
     bool agg = c->agg_on && c->lanes == 0 && placed >= agg_min() && pset_agg_classes(c) && agg_wanted(c);
-    const uint32_t sub = c->agg_sub;
+    const uint32_t sub = c->agg_sub, n_cls = (uint32_t)c->ps_cls_rep.size();
     uint64_t slots = 0, R = 0;
     int lanes = 0;
     if (agg) {
-        const uint32_t n_cls = (uint32_t)c->ps_cls_rep.size();
         c->ps_cbeg.assign(n_cls, 0); c->ps_cend.assign(n_cls, 0);
         lanes = pset_agg_choose(c->gs_totals.data(), c->ps_class.data(), K, c->ps_cls_ok.data(), n_cls, sub, 0, wave_below(), wide_below(),
                                 c->gs_start.data(), c->ps_cbeg.data(), c->ps_cend.data(), &R, &slots);
@@ -2961,60 +2933,38 @@ static int run_pset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
     if (!agg) { R = 0; lanes = pset_choose(c->gs_totals.data(), K, c->lanes, wave_below(), wide_below(), c->gs_start.data(), &slots); }
     const size_t M = (size_t)slots;
     if ((rc = ctx_ready(c, M ? M : 1)) != ZKV_OK) return rc;     // (growing frees buffers, which synchronises the device)
-    if ((rc = grow(&c->mx[8], &c->mx_cap[8], 4 * M + 4)) != ZKV_OK || (rc = grow(&c->mx[9], &c->mx_cap[9], 4 * M + 4)) != ZKV_OK ||
-        (rc = grow(&c->d_st_all, &c->st_all_cap, M + 1)) != ZKV_OK) return rc;
-    p.idx = (uint32_t*)c->mx[8]; p.skey = (uint32_t*)c->mx[9];
-    HIP_TRY(hipMemsetAsync(p.idx, 0xFF, 4 * M + 4, s));      // pad slots: GSET_NONE
-    HIP_TRY(hipMemsetAsync(p.skey, 0, 4 * M + 4, s));        // (and key 0: keeps any read of a pad slot's key in the set)
+    if ((rc = set_slot_buffers(c, M, &p, s)) != ZKV_OK) return rc;
     HIP_TRY(hipMemcpyAsync(c->mx[7], c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
     launch_gset_place(p, (const uint64_t*)c->mx[7], s);
     HIP_TRY(hipGetLastError());
     const size_t cap = c->ws.cap;                            // (a power of two >= 4,096 or ZKV_CHUNK, a multiple of 64: chunks keep the 64-slot groups)
     if (agg) {
-        // aggregate chunks end on multiples of max(64, sub), so no sub-batch straddles two of them
-        const size_t capa = (size_t)pset_agg_chunk_slots(cap, sub);
+        // aggregate chunks end on multiples of max(64, sub), so no sub-batch straddles two of them; a region per class, through the
+        // class's first key, whose line tables are those of every key of the class; a class that cannot take the check: no region
+        for (uint32_t q = 0; q < n_cls; q++) if (!c->ps_cls_ok[q]) c->ps_cend[q] = c->ps_cbeg[q];
         std::vector<GsetAggChunk> plan;
-        c->gs_amap.clear();
-        for (size_t base = 0; base < R; base += capa) plan.push_back(pset_agg_chunk(c, base, R - base < capa ? (size_t)R - base : capa, sub));
-        if ((rc = grow(&c->mx[10], &c->mx_cap[10], 4 * c->gs_amap.size() + 4)) != ZKV_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(c->mx[10], c->gs_amap.data(), 4 * c->gs_amap.size(), hipMemcpyHostToDevice, s));
+        if ((rc = set_agg_plan(c, c->ps_cbeg.data(), c->ps_cend.data(), c->ps_cls_rep.data(), n_cls, R, (size_t)pset_agg_chunk_slots(cap, sub), sub,
+                               &plan, s)) != ZKV_OK) return rc;
         for (const GsetAggChunk& g : plan) {
-            PsetChunk ch;
-            memset(&ch, 0, sizeof ch);
-            ch.m = g.m; ch.slot0 = g.base; ch.idx = p.idx; ch.skey = p.skey;
-            ch.keys = c->d_pkey; ch.ok = c->d_ps_ok;
-            ch.proofs = d_proofs; ch.proof_stride = (uint32_t)pset_proof_stride(c);
-            ch.inputs = d_inputs; ch.input_stride = (uint32_t)pset_input_stride(c);
-            ch.plonk_tab = c->d_plonk_tab; ch.status = c->d_st_all + g.base;
-            enqueue_pset_agg(c, ch, g, p.skey + g.base, (const uint32_t*)c->mx[10], sub, s, M == R && g.base + g.m >= R);
+            enqueue_pset_agg(c, pset_chunk_of(c, p, d_proofs, d_inputs, g.base, g.m), g, p.skey + g.base, (const uint32_t*)c->mx[10], sub, s,
+                             M == R && g.base + g.m >= R);
             HIP_TRY(hipGetLastError());
         }
     }
     for (size_t base = (size_t)R; base < M; base += cap) {
         const size_t m = M - base < cap ? M - base : cap;
         const bool timed = base + cap >= M;
-        PsetChunk ch;
-        memset(&ch, 0, sizeof ch);
-        ch.m = m; ch.slot0 = base; ch.idx = p.idx; ch.skey = p.skey;
-        ch.keys = c->d_pkey; ch.ok = c->d_ps_ok;
-        ch.proofs = d_proofs; ch.proof_stride = (uint32_t)pset_proof_stride(c);
-        ch.inputs = d_inputs; ch.input_stride = (uint32_t)pset_input_stride(c);
-        ch.plonk_tab = c->d_plonk_tab; ch.status = c->d_st_all + base;
+        const PsetChunk ch = pset_chunk_of(c, p, d_proofs, d_inputs, base, m);
         if (timed) (void)hipEventRecord(c->ev[0], s);
         launch_pset_prep(ch, c->ws, s);
         if (timed) { (void)hipEventRecord(c->ev[1], s); (void)hipEventRecord(c->ev[2], s); (void)hipEventRecord(c->ev[3], s); }
         launch_gset_miller(lanes, m, p.skey + base, c->d_gs_key, c->ws, ch.status, s);
         if (timed) (void)hipEventRecord(c->ev[4], s);
-        if (lanes == 2) launch_finalexp2(m, c->ws, ch.status, s);
-        else if (lanes == 16) launch_finalexp_w(m, c->ws, ch.status, s);
-        else launch_finalexp_w64(m, c->ws, ch.status, s);
+        launch_finalexp_lanes(lanes, m, c->ws, ch.status, s);
         if (timed) (void)hipEventRecord(c->ev[5], s);
         HIP_TRY(hipGetLastError());
     }
-    if (!M) for (int e = 0; e < 6; e++) (void)hipEventRecord(c->ev[e], s);
-    launch_gset_return(n, p.pos, c->d_st_all, d_verified, s);
-    HIP_TRY(hipGetLastError());
-    return ZKV_OK;
+    return set_return(c, n, M, p, d_verified, s);
 }
 ZKV_EXPORT int zkv_plonk_set_verify_batch_dev(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* d_proofs, const uint8_t* d_public_inputs,
                                               uint8_t* d_verified, void* stream) {

@@ -139,4 +139,31 @@ inline uint32_t pset_srs_classes(const uint8_t* g2, uint32_t n_keys, uint32_t* c
 // (0: the workspace is smaller than one unit and the call takes the per-proof path).
 inline uint64_t pset_agg_chunk_slots(uint64_t cap, uint32_t sub) { return cap / gset_agg_unit(sub) * gset_agg_unit(sub); }
 
+// The pseudo-proofs of one aggregate chunk [base, base + m) of either kind of set: one per sub-batch of `sub` slots, n2 = m / sub of them.
+// Region q is the slots [beg[q], end[q]) whose sub-batches take the line tables of key rep[q] (rep = null: key q): a Groth16 set passes
+// one region per key (astart[k], astart[k] + agg[k]), a PLONK set one per SRS class (cbeg, cend, the class's first key), an incapable
+// class as an empty region.  Regions are disjoint, and begin and end on multiples of `sub` as do the chunks.  The pseudo-proofs are laid out
+// per region and padded to the proofs per wavefront of the Miller mapping, as the proofs themselves: gset_choose over the regions'
+// sub-batch counts, starting from `lanes` (the mapping n2 proofs would take); when the padded slots exceed `cap`, the pseudo-workspace's
+// capacity, one wavefront per pseudo-proof, which pads nothing.
+// Fills nsb[q] (sub-batches of region q in the chunk), pst[0 .. n_regions] (region q's pseudo slots are [pst[q], pst[q + 1])), psl[t] (the
+// slot of the chunk's sub-batch t, for every t of a region; the others are left alone) and skey2[0 .. *slots) (rep of the region of every
+// pseudo slot, pad slots included); skey2 needs room for n2 + 31 * n_regions words.  Returns the lanes per pseudo-proof.
+inline int gset_agg_chunk_plan(const uint64_t* beg, const uint64_t* end, const uint32_t* rep, uint32_t n_regions, uint64_t base, uint64_t m,
+                               uint32_t sub, int lanes, uint64_t cap, uint32_t* nsb, uint64_t* pst, uint32_t* psl, uint32_t* skey2, uint64_t* slots) {
+    for (uint32_t q = 0; q < n_regions; q++) {
+        const uint64_t lo = beg[q] > base ? beg[q] : base, hi = end[q] < base + m ? end[q] : base + m;
+        nsb[q] = hi > lo ? (uint32_t)((hi - lo) / sub) : 0u;
+    }
+    lanes = gset_choose(nsb, n_regions, lanes, 0, pst, slots);
+    if (*slots > cap) lanes = gset_choose(nsb, n_regions, 64, 1, pst, slots);
+    for (uint32_t q = 0; q < n_regions; q++) {
+        if (!nsb[q]) continue;
+        const uint64_t sb0 = ((beg[q] > base ? beg[q] : base) - base) / sub;
+        for (uint32_t t = 0; t < nsb[q]; t++) psl[sb0 + t] = (uint32_t)(pst[q] + t);
+        for (uint64_t w = pst[q]; w < pst[q + 1]; w++) skey2[w] = rep ? rep[q] : q;
+    }
+    return lanes;
+}
+
 }  // namespace zkv

@@ -1,4 +1,4 @@
-// Host build of the key-set aggregate layout (csrc/zkv_gset_layout.h: gset_agg_choose, gset_agg_slot) and of the per-signal share loop
+// Host build of the key-set aggregate layout (csrc/zkv_gset_layout.h: gset_agg_choose, gset_agg_slot, gset_agg_chunk_plan) and of the per-signal share loop
 // of the scalar-sum form (csrc/zkv_gset_agg.h) for tests/test_groth16_key_sets_aggregate_host.py.  TEST ONLY.
 #include <stdint.h>
 #include <string.h>
@@ -14,6 +14,12 @@ extern "C" int hga_choose(const uint32_t* cnt, const uint8_t* capable, uint32_t 
 }
 extern "C" uint64_t hga_slot(uint32_t k, uint32_t rank, const uint32_t* agg, const uint64_t* astart, const uint64_t* pstart) {
     return gset_agg_slot(k, rank, agg, astart, pstart);
+}
+
+// The pseudo-proof plan of one aggregate chunk (gset_agg_chunk_plan), for both kinds of set: rep = null for a Groth16 set's key regions
+extern "C" int hga_chunk_plan(const uint64_t* beg, const uint64_t* end, const uint32_t* rep, uint32_t n_regions, uint64_t base, uint64_t m, uint32_t sub,
+                              int lanes, uint64_t cap, uint32_t* nsb, uint64_t* pst, uint32_t* psl, uint32_t* skey2, uint64_t* slots) {
+    return gset_agg_chunk_plan(beg, end, rep, n_regions, base, m, sub, lanes, cap, nsb, pst, psl, skey2, slots);
 }
 
 // One sub-batch of `sub` proofs under a key with n_sig signals: ic (n_sig + 1 affine points, 16 big-endian words each... as raw limbs:

@@ -32,6 +32,8 @@ def hga():
     h.hga_slot.restype = C.c_uint64
     h.hga_u.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     h.hga_u.restype = C.c_int
+    h.hga_chunk_plan.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint64] + [C.c_void_p] * 5
+    h.hga_chunk_plan.restype = C.c_int
     return h
 
 
@@ -76,6 +78,70 @@ def test_layout_regions(hga, seed):
     assert (owner[:R.value] >= 0).all()                                          # no pad slot in the aggregate region
     for b in range(0, R.value, A):
         assert len(set(owner[b:b + A])) == 1
+
+
+def _regions(rng, shape, A):
+    """Regions of an aggregate region [0, R): a Groth16 set's keys back to back (rep = None: the key itself), or a PLONK set's SRS classes on
+    multiples of A with a class without proofs among them and a class that cannot take the check passed as an empty region behind R."""
+    if shape == 'keys':
+        n = int(rng.choice([1, 2, 5, 16, 300]))
+        size = A * rng.integers(0, int(rng.choice([2, 4, 40])), n)
+        size[rng.integers(0, n)] += A                                            # (R > 0)
+        beg = np.concatenate([[0], np.cumsum(size)])[:-1]
+        return beg.astype(np.uint64), (beg + size).astype(np.uint64), None, int(size.sum())
+    n = int(rng.choice([3, 8, 40]))
+    size = A * rng.integers(1, int(rng.choice([2, 4, 40])), n)
+    size[rng.integers(0, n - 1)] = 0                                             # a class without proofs
+    size[n - 1] = 0                                                              # the class that cannot take the check
+    beg = np.concatenate([[0], np.cumsum(size)])[:-1]
+    rep = np.sort(rng.choice(np.arange(1, 1024), n, replace=False)).astype(np.uint32)
+    return beg.astype(np.uint64), (beg + size).astype(np.uint64), rep, int(size.sum())
+
+
+def test_aggregate_chunk_plan(hga):
+    """gset_agg_chunk_plan (zkv_gset_layout.h): where the pseudo-proof of every sub-batch of an aggregate chunk lives and which key's line
+    tables its slot takes, for both kinds of set, against a model."""
+    NONE = 0xFFFFFFFF
+    stepped = fell_back = chunks = 0
+    for seed in range(60):
+        rng = np.random.default_rng(7000 + seed)
+        sub = int(rng.choice([16, 32, 64, 128, 256]))
+        A = max(64, sub)
+        beg, end, rep, R = _regions(rng, 'keys' if seed % 2 == 0 else 'classes', A)
+        n_reg = len(beg)
+        rep_of = np.arange(n_reg) if rep is None else rep
+        capa = A * int(rng.integers(1, 12))
+        for base in range(0, R, capa):
+            m = min(capa, R - base)
+            n2 = m // sub
+            lanes_in = int(rng.choice([2, 16, 64, 128]))
+            cap = int(rng.choice([n2, n2 + n2 // 8, 1 << 20]))                    # the pseudo-workspace holds the n2 pseudo-proofs at least
+            nsb = np.full(n_reg, NONE, np.uint32); pst = np.zeros(n_reg + 1, np.uint64)
+            psl = np.full(n2, NONE, np.uint32); skey2 = np.full(n2 + 31 * n_reg, NONE, np.uint32)
+            slots = C.c_uint64(0)
+            lanes = hga.hga_chunk_plan(beg.ctypes.data, end.ctypes.data, None if rep is None else rep.ctypes.data, n_reg, base, m, sub, lanes_in,
+                                       cap, nsb.ctypes.data, pst.ctypes.data, psl.ctypes.data, skey2.ctypes.data, C.byref(slots))
+            lo = np.maximum(beg.astype(np.int64), base); hi = np.minimum(end.astype(np.int64), base + m)
+            want_nsb = np.where(hi > lo, (hi - lo) // sub, 0)
+            assert (nsb == want_nsb).all() and int(want_nsb.sum()) == n2         # (the regions tile the chunk)
+            want_lanes, want_pst = _choose_model([int(x) for x in want_nsb], lanes_in)
+            if int(want_pst[-1]) > cap:                                          # no room for the padding: one wavefront per pseudo-proof
+                fell_back += 1
+                want_lanes, want_pst = 64, np.concatenate([[0], np.cumsum(want_nsb)]).astype(np.uint64)
+            elif want_lanes != lanes_in:
+                stepped += 1
+            a = ALIGN[want_lanes]
+            assert lanes == want_lanes and (pst == want_pst).all()
+            assert slots.value == sum((int(x) + a - 1) // a * a for x in want_nsb) == int(want_pst[-1])
+            assert len(set(psl.tolist())) == n2                                  # injective
+            for q in range(n_reg):
+                t0 = (int(lo[q]) - base) // sub
+                assert (psl[t0:t0 + int(want_nsb[q])] == int(pst[q]) + np.arange(int(want_nsb[q]))).all()       # in order, inside [pst[q], pst[q + 1])
+                assert int(pst[q]) + int(want_nsb[q]) <= int(pst[q + 1])
+                assert (skey2[int(pst[q]):int(pst[q + 1])] == rep_of[q]).all()
+            assert (skey2[slots.value:] == NONE).all()                           # nothing written past the slots
+            chunks += 1
+    assert chunks > 100 and stepped > 0 and fell_back > 0                         # the generator reaches the 1.25x step-down and the capacity fall-back
 
 
 def _limbs(v):
