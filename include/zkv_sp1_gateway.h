@@ -7,6 +7,7 @@
  * holds up to ZKV_SP1_GATEWAY_MAX_ROUTES such verifiers ("routes"): optionally the built-in SP1 v5.0.0 Groth16 verifier
  * (zkv_sp1_ctx_create) and any number of SP1 PLONK verifiers (zkv_sp1_plonk_ctx_create, one per key and verifier hash).
  * Companion of zkv.h (same library, same conventions, same ZKV_OK / ZKV_ERR_* codes); DESIGN.md section 12 describes the device path.
+ * zkv_sp1_gateway_wire.h adds eth_call batches (raw `verifyProof` calldata) on a gateway.
  *
  * PARITY UNPINNED: the reference holds no gateway and no PLONK code.  ZKV_STATUS_ROUTE_NOT_FOUND and its ABI encoding, and every
  * PLONK status, have no reference counterpart; a proof routed to the Groth16 route gets exactly the pinned SP1 statuses.

@@ -31,7 +31,7 @@ def _hipcc():
 
 
 def _deps_mtime():
-    files = glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(HERE, '..', 'include', f) for f in ('zkv.h', 'zkv_groth16_set.h', 'zkv_sp1_gateway.h', 'zkv_plonk_keys.h', 'zkv_plonk_set.h', 'zkv_plonk_set_agg.h', 'zkv_diag_primitive.h', 'zkv_diag_prep.h')]
+    files = glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(HERE, '..', 'include', f) for f in ('zkv.h', 'zkv_groth16_set.h', 'zkv_sp1_gateway.h', 'zkv_sp1_gateway_wire.h', 'zkv_plonk_keys.h', 'zkv_plonk_set.h', 'zkv_plonk_set_agg.h', 'zkv_diag_primitive.h', 'zkv_diag_prep.h')]
     return max(os.path.getmtime(f) for f in files)
 
 

@@ -3,12 +3,13 @@
 // counterpart (parity unpinned); the routes' own statuses are their contexts' ones.
 //
 // Same shape as the mixed-batch demultiplexer (k_mixed.hip), with up to 8 route columns and ragged proofs:
-//   k_gateway_count   per 256-proof block: proofs per route, not found, short (wave ballots + popcounts)
+//   k_gateway_count   per 256-proof block: proofs per route, not found, short, bad calldata (wave ballots + popcounts)
 //   k_gateway_scan    exclusive scan of every column over the blocks (one workgroup), totals
 //   (the host reads the totals back once and sizes the compact records: route r holds n_r records of 260 or 868 bytes)
 //   k_gateway_place   stable partition: slot of every routed proof; short and not-found proofs are answered in place
 //   k_gateway_gather  one wavefront per proof: first min(len, record) proof bytes, the 32-byte program vkey; the true length and
 //                     the public-values location were written by place
+// Proofs arrive as n + 1 contiguous offsets or, from the calldata decoder (k_wire_gateway), as (start, length) records with gaps.
 // The statuses come back through k_mixed_return.  All of it is byte traffic beside the pairing; no scratch, no LDS beyond the counts.
 #include "zkv_internal.h"
 #include "zkv_bytes.h"
@@ -17,12 +18,22 @@ namespace zkv {
 
 constexpr int GW_BLOCK = 256;
 
-// route of proof i (0 .. n_routes - 1), GW_COL_NOT_FOUND or GW_COL_SHORT; *sel = the selector read (0 when short).  Byte loads: a
-// ragged blob has no alignment.
+// Proof i as (start, length) from a.proofs: a record (k_wire_gateway has bounded it) or the caller's two offsets; false: the offsets run
+// backwards or past proof_bytes, the proof is never read.
+__device__ __forceinline__ bool gw_span(const GatewayArgs& a, size_t i, uint64_t* start, uint64_t* len) {
+    if (a.rec_proof_at) { *start = a.rec_proof_at[i]; *len = a.rec_proof_len[i]; return true; }
+    const uint64_t s = a.proof_off[i], e = a.proof_off[i + 1];
+    *start = s; *len = e - s;
+    return s <= e && e <= a.proof_bytes;
+}
+
+// route of proof i (0 .. n_routes - 1), GW_COL_NOT_FOUND, GW_COL_SHORT or (records) GW_COL_BAD; *sel = the selector read (0 when short or
+// bad).  Byte loads: a ragged blob has no alignment.
 __device__ __forceinline__ int gw_class(const GatewayArgs& a, size_t i, uint32_t* sel) {
     *sel = 0;
-    const uint64_t s = a.proof_off[i], e = a.proof_off[i + 1];
-    if (e < s || e > a.proof_bytes || e - s < 4) return GW_COL_SHORT;
+    if (a.rec_bad && a.rec_bad[i]) return GW_COL_BAD;
+    uint64_t s, len;
+    if (!gw_span(a, i, &s, &len) || len < 4) return GW_COL_SHORT;
     const uint8_t* p = a.proofs + s;
     const uint32_t v = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
     *sel = v;
@@ -105,7 +116,7 @@ __global__ __launch_bounds__(GW_BLOCK) void k_gateway_place(GatewayArgs a) {
     if (c < 0) return;
     if (c >= GW_MAX_ROUTES) {                                       // no verifier to ask: answered here, no slot
         a.pos[i] = GW_NONE;
-        a.status[i] = c == GW_COL_SHORT ? 4 : 8;                    // ZKV_STATUS_INVALID_PROOF_DATA, ZKV_STATUS_ROUTE_NOT_FOUND
+        a.status[i] = c == GW_COL_SHORT ? 4 : c == GW_COL_BAD ? 6 : 8;      // ZKV_STATUS_INVALID_PROOF_DATA, _BAD_CALLDATA, _ROUTE_NOT_FOUND
         if (a.recv) {
             a.recv[4 * i] = (uint8_t)(sel >> 24); a.recv[4 * i + 1] = (uint8_t)(sel >> 16);
             a.recv[4 * i + 2] = (uint8_t)(sel >> 8); a.recv[4 * i + 3] = (uint8_t)sel;
@@ -117,8 +128,10 @@ __global__ __launch_bounds__(GW_BLOCK) void k_gateway_place(GatewayArgs a) {
     const uint32_t slot = a.start[c] + a.cnt[(size_t)blockIdx.x * GW_COLS + c] + r;
     a.pos[i] = slot;
     a.idx[slot] = (uint32_t)i;
-    const uint64_t len = a.proof_off[i + 1] - a.proof_off[i];
+    uint64_t at, len;
+    gw_span(a, i, &at, &len);
     a.c_len[slot] = len > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)len;
+    if (a.rec_proof_at) { a.c_pvoff[slot] = a.rec_pv_at[i]; a.c_pvlen[slot] = a.rec_pv_len[i]; return; }
     a.c_pvoff[slot] = a.pv_off ? a.pv_off[i] : (uint64_t)i * a.pv_stride;
     a.c_pvlen[slot] = (uint32_t)(a.pv_off ? a.pv_off[i + 1] - a.pv_off[i] : a.pv_stride);
 }
@@ -136,8 +149,9 @@ __global__ __launch_bounds__(GW_BLOCK) void k_gateway_gather(GatewayArgs a) {
     for (int k = 1; k < GW_MAX_ROUTES; k++) if ((uint32_t)k < a.n_routes && a.start[k] <= slot) r = (uint32_t)k;
     const uint32_t rec = a.rec[r];
     uint32_t* dst = (uint32_t*)(a.c_proofs + a.base[r] + (uint64_t)(slot - a.start[r]) * rec);
-    const uint8_t* src = a.proofs + a.proof_off[i];
-    uint64_t len = a.proof_off[i + 1] - a.proof_off[i];
+    uint64_t at, len;
+    gw_span(a, i, &at, &len);
+    const uint8_t* src = a.proofs + at;
     if (len > rec) len = rec;
     for (uint32_t w = lane; w < rec / 4; w += 64) {
         const uint64_t at = 4ull * w;

@@ -8,6 +8,7 @@
 // rejected -- unpinned), and compacts the arrays to bytes.
 #include "zkv_internal.h"
 #include "zkv_bytes.h"
+#include "zkv_wire_gateway.h"
 
 namespace zkv {
 
@@ -131,6 +132,46 @@ __global__ __launch_bounds__(BLOCK) void k_wire_sp1(WireArgs a) {
     if (lane == 0) { a.seal_len[i] = L; a.pv_off[i] = pv_at; a.pv_len[i] = lpv; }
 }
 
+// verifyProof to the SP1 gateway, either calldata form (zkv_wire_gateway.h): the record of request i instead of a fixed slot, since the
+// proof may be an 868-byte PLONK one.  Form U streams both arrays as k_wire_sp1 does, into the arena at off[i] / 32: the decoded bytes of
+// a request are fewer than a 32nd of its calldata, so requests whose calldata does not overlap do not meet there; the proof copy stops at
+// `cap` bytes (the longest record any route reads), the length passed on is the true one.  Form B is already bytes: the wave checks the
+// zero padding of both arguments (at most 31 bytes each, lanes 0-30 and 32-62) and the record points into the blob.
+template <int BLOCK, bool NT>
+__global__ __launch_bounds__(BLOCK) void k_wire_gateway(GwWireArgs a, uint32_t cap) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t i = (size_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+    if (i >= a.n) return;
+    const uint64_t o0 = a.off[i], o1 = a.off[i + 1];
+    const bool in_blob = o0 <= o1 && o1 <= a.cd_bytes;       // offsets come from the caller: never read outside the blob
+    const uint8_t* cd = a.cd + (in_blob ? o0 : 0);
+    const uint64_t len = in_blob ? o1 - o0 : 0;
+    const bool al = (((uintptr_t)cd) & 3u) == 0;
+    const GwCall h = gww_parse(cd, len, al, a.sel_u_be, a.sel_b_be);     // wave-uniform
+    bool ok = h.ok != 0;
+    uint64_t pv_at = 0, proof_at = 0;
+    if (ok && h.form == GWW_FORM_UINT8_ARRAY) {
+        const uint64_t at = o0 / 32;
+        uint8_t* dst = a.arena + at;
+        ok = wire_u8_array<NT>(cd + h.pv_at, h.pv_len, al, dst, h.pv_len, lane);
+        ok = wire_u8_array<NT>(cd + h.proof_at, h.proof_len, al, dst + h.pv_len, cap, lane) && ok;
+        pv_at = a.arena_delta + at; proof_at = pv_at + h.pv_len;
+    } else if (ok) {
+        const uint32_t half = lane >> 5, k = lane & 31u;
+        const uint64_t body = half ? h.proof_at : h.pv_at, used = half ? h.proof_len : h.pv_len;
+        const uint32_t pad = (uint32_t)(-used & 31u);
+        const uint32_t b = k < pad ? cd[body + used + k] : 0u;
+        ok = __all(b == 0) != 0;
+        pv_at = a.cd_delta + o0 + h.pv_at; proof_at = a.cd_delta + o0 + h.proof_at;
+    }
+    if (h.ok) copy32(a.vkeys + 32 * i, cd + 4, lane);
+    if (lane == 0) {
+        a.bad[i] = ok ? 0 : 1;
+        a.pv_at[i] = ok ? pv_at : 0; a.pv_len[i] = ok ? h.pv_len : 0;
+        a.proof_at[i] = ok ? proof_at : 0; a.proof_len[i] = ok ? h.proof_len : 0;
+    }
+}
+
 // One wavefront per request, four requests per workgroup, non-temporal loads (each calldata byte is read exactly once).
 // Measured on 2^16 verify() requests (554 MB): 4.9 TB/s; a persistent grid-stride grid (3.4-4.5 TB/s), 64- or 512-thread
 // workgroups (4.7 TB/s), default-policy loads (4.8 TB/s) and a header-independent slot-streaming form (4.4 TB/s, 98 VGPRs)
@@ -141,6 +182,11 @@ static void wire_dispatch(bool sp1, const WireArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)((a.n + per - 1) / per));
     if (sp1) hipLaunchKernelGGL((k_wire_sp1<WIRE_BLOCK, true>), grid, dim3(WIRE_BLOCK), 0, s, a);
     else hipLaunchKernelGGL((k_wire_risc0<WIRE_BLOCK, true>), grid, dim3(WIRE_BLOCK), 0, s, a);
+}
+void launch_wire_gateway(const GwWireArgs& a, hipStream_t s) {
+    if (!a.n) return;
+    const size_t per = WIRE_BLOCK / 64;
+    hipLaunchKernelGGL((k_wire_gateway<WIRE_BLOCK, true>), dim3((unsigned)((a.n + per - 1) / per)), dim3(WIRE_BLOCK), 0, s, a, (uint32_t)ZKV_PLONK_PROOF_BYTES);
 }
 void launch_wire_risc0(const WireArgs& a, hipStream_t s) { wire_dispatch(false, a, s); }
 void launch_wire_sp1(const WireArgs& a, hipStream_t s) { wire_dispatch(true, a, s); }

@@ -19,6 +19,7 @@
 #include "../../include/zkv.h"
 #include "../../include/zkv_groth16_set.h"
 #include "../../include/zkv_sp1_gateway.h"
+#include "../../include/zkv_sp1_gateway_wire.h"
 #include "../../include/zkv_plonk_keys.h"
 #include "../../include/zkv_plonk_set.h"
 #include "../../include/zkv_plonk_set_agg.h"
@@ -169,10 +170,10 @@ struct zkv_ctx {
     std::vector<hipEvent_t> ev_in;                       // per source device: "the caller's stream has produced the inputs"
     zkv_ctx* kid[2] = {nullptr, nullptr};
     bool kid_ran[2] = {false, false};        // which sub-batch of the most recent mixed call was non-empty (zkv_ctx_last_stage_ms)
-    uint8_t* mx[22] = {nullptr};
-    size_t mx_cap[22] = {0};
+    uint8_t* mx[28] = {nullptr};
+    size_t mx_cap[28] = {0};
     // ZKV_VM_SP1_GATEWAY (zkv_sp1_gateway.h): the routes' contexts and selectors; which routes ran in the most recent call
-    // (zkv_ctx_last_stage_ms) and its per-column proof counts (routes, not found, short)
+    // (zkv_ctx_last_stage_ms) and its per-column proof counts (routes, not found, short, bad calldata)
     std::vector<zkv_ctx*> gw_route;
     std::vector<uint32_t> gw_sel;
     std::vector<uint8_t> gw_ran;
@@ -337,7 +338,7 @@ static void ctx_free_device(zkv_ctx* c) {
     for (void** p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
     c->ws2.cap = 0; c->ws3 = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0}; c->agg_cap = 0; c->agg_key_ok = false;
     for (int k = 0; k < 6; k++) { if (c->hb[k]) (void)hipFree(c->hb[k]); c->hb[k] = nullptr; c->hb_cap[k] = 0; }
-    for (int k = 0; k < 20; k++) { if (c->mx[k]) (void)hipFree(c->mx[k]); c->mx[k] = nullptr; c->mx_cap[k] = 0; }
+    for (size_t k = 0; k < sizeof c->mx / sizeof c->mx[0]; k++) { if (c->mx[k]) (void)hipFree(c->mx[k]); c->mx[k] = nullptr; c->mx_cap[k] = 0; }
     c->ws.cap = 0; c->lsig_cap = 0; c->blob_cap = c->pv_cap = 0; c->cd_cap[0] = c->cd_cap[1] = c->st_all_cap = c->rv_all_cap = 0;
     hipEvent_t* evs[] = {&c->ev[0], &c->ev[1], &c->ev[2], &c->ev[3], &c->ev[4], &c->ev[5], &c->ev_wire[0], &c->ev_wire[1], &c->ev_done,
                          &c->ev_copied[0], &c->ev_copied[1], &c->ev_decoded[0], &c->ev_decoded[1], &c->ev_fork, &c->ev_join, &c->ev_seg[0], &c->ev_seg[1]};
@@ -1761,11 +1762,15 @@ ZKV_EXPORT int zkv_sp1_gateway_verify_proof(zkv_ctx* c, const uint8_t vkey[32], 
 }
 
 enum { GW_CNT = 0, GW_TOT, GW_POS, GW_IDX, GW_RECS, GW_LEN, GW_A, GW_PVOFF, GW_PVLEN, GW_ST, GW_RV,
-       GW_H_VK, GW_H_PV, GW_H_PVOFF, GW_H_PROOF, GW_H_POFF, GW_H_ST, GW_H_RV };
+       GW_H_VK, GW_H_PV, GW_H_PVOFF, GW_H_PROOF, GW_H_POFF, GW_H_ST, GW_H_RV,
+       GWW_VK, GWW_PVAT, GWW_PVLEN, GWW_PAT, GWW_PLEN, GWW_BAD, GWW_ARENA, GWW_H_CD, GWW_H_OFF };      // calldata batches (run_gateway_wire)
 // Everything device-resident: ragged proofs (offsets bounded by proof_bytes on the device); public values ragged (d_pv_off) or at a
-// fixed stride.  Synchronises `s` once, after the count, to size the compact records and learn the routes' sub-batch sizes.
+// fixed stride.  Or, from the calldata decoder, `recs`: (start, length) records of proofs and public values from one base address, which
+// d_proofs and d_pv then both are, and bad-calldata marks.  Synchronises `s` once, after the count, to size the compact records and learn
+// the routes' sub-batch sizes.
 static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8_t* d_proofs, const uint64_t* d_proof_off, uint64_t proof_bytes,
-                       const uint8_t* d_pv, const uint64_t* d_pv_off, uint64_t pv_stride, uint8_t* d_status, uint8_t* d_recv, hipStream_t s) {
+                       const uint8_t* d_pv, const uint64_t* d_pv_off, uint64_t pv_stride, uint8_t* d_status, uint8_t* d_recv, hipStream_t s,
+                       const GwWireArgs* recs = nullptr) {
     int rc;
     const size_t blocks = (n + 255) / 256, R = c->gw_route.size();
     const size_t need[11] = {4 * GW_COLS * blocks, 4 * GW_COLS, 4 * n, 4 * n, 0, 4 * n, 32 * n, 8 * n, 4 * n, n, 4 * n};
@@ -1774,6 +1779,7 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
     GatewayArgs a;
     memset(&a, 0, sizeof a);
     a.n = n; a.proofs = d_proofs; a.proof_off = d_proof_off; a.proof_bytes = proof_bytes; a.vkeys = d_vkeys; a.pv_off = d_pv_off; a.pv_stride = pv_stride;
+    if (recs) { a.rec_proof_at = recs->proof_at; a.rec_proof_len = recs->proof_len; a.rec_pv_at = recs->pv_at; a.rec_pv_len = recs->pv_len; a.rec_bad = recs->bad; }
     a.n_routes = (uint32_t)R;
     for (size_t r = 0; r < R; r++) {
         a.sel[r] = c->gw_sel[r];
@@ -1790,12 +1796,12 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
     size_t routed = 0;
     uint64_t bytes = 0;
     for (size_t r = 0; r < R; r++) { a.start[r] = (uint32_t)routed; a.base[r] = bytes; routed += tot[r]; bytes += (uint64_t)tot[r] * a.rec[r]; }
-    if (routed + tot[GW_COL_NOT_FOUND] + tot[GW_COL_SHORT] != n) return ZKV_ERR_HIP;
+    if (routed + tot[GW_COL_NOT_FOUND] + tot[GW_COL_SHORT] + tot[GW_COL_BAD] != n) return ZKV_ERR_HIP;
     if ((rc = grow(&c->mx[GW_RECS], &c->mx_cap[GW_RECS], (size_t)bytes + 8)) != ZKV_OK) return rc;
     a.c_proofs = c->mx[GW_RECS];
     for (size_t r = 0; r < R; r++) { c->gw_counts[r] = tot[r]; c->gw_ran[r] = tot[r] > 0; }
     for (size_t r = R; r < GW_MAX_ROUTES; r++) c->gw_counts[r] = 0;
-    c->gw_counts[GW_COL_NOT_FOUND] = tot[GW_COL_NOT_FOUND]; c->gw_counts[GW_COL_SHORT] = tot[GW_COL_SHORT];
+    c->gw_counts[GW_COL_NOT_FOUND] = tot[GW_COL_NOT_FOUND]; c->gw_counts[GW_COL_SHORT] = tot[GW_COL_SHORT]; c->gw_counts[GW_COL_BAD] = tot[GW_COL_BAD];
     launch_gateway_place(a, s);
     HIP_TRY(hipGetLastError());
     uint8_t *st = c->mx[GW_ST], *rv = c->mx[GW_RV];
@@ -2116,6 +2122,121 @@ ZKV_EXPORT int zkv_ctx_last_wire_ms(zkv_ctx* c, float* out_ms) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipEventSynchronize(c->ev_wire[1]));
     HIP_TRY(hipEventElapsedTime(out_ms, c->ev_wire[0], c->ev_wire[1]));
+    return ZKV_OK;
+}
+
+// ------------------------------------------------------------------ SP1 gateway: eth_call batches (zkv_sp1_gateway_wire.h; parity unpinned)
+// verifyProof calls to the gateway in either calldata form: k_wire_gateway turns every request into a record, the demultiplexer takes the
+// records instead of offsets, and everything after it is the decoded-input path.
+static const uint8_t* gateway_bytes_selector() {
+    static const struct Sel { uint8_t b[4]; Sel() { host::fn_selector("verifyProof(bytes32,bytes,bytes)", b); } } s;
+    return s.b;
+}
+ZKV_EXPORT size_t zkv_sp1_gateway_encode_verify_proof_call(int form, const uint8_t program_vkey[32], const uint8_t* pv, size_t pv_len, const uint8_t* proof,
+                                                           size_t proof_len, uint8_t* out, size_t cap) {
+    if (form == ZKV_CALLDATA_FORM_UINT8_ARRAY) return zkv_sp1_encode_verify_proof_call(program_vkey, pv, pv_len, proof, proof_len, out, cap);
+    if (form != ZKV_CALLDATA_FORM_BYTES) return 0;
+    const size_t pv_pad = (pv_len + 31) & ~(size_t)31, proof_pad = (proof_len + 31) & ~(size_t)31;
+    const size_t need = 4 + 96 + 32 + pv_pad + 32 + proof_pad;
+    if (!out || cap < need || (pv_len && !pv) || (proof_len && !proof) || !program_vkey) return need;
+    memset(out, 0, need);
+    memcpy(out, gateway_bytes_selector(), 4);
+    memcpy(out + 4, program_vkey, 32); host::abi_word_u32(out + 36, 0x60); host::abi_word_u32(out + 68, 0x80 + (uint64_t)pv_pad);
+    host::abi_word_u32(out + 100, pv_len);
+    if (pv_len) memcpy(out + 132, pv, pv_len);
+    host::abi_word_u32(out + 132 + pv_pad, proof_len);
+    if (proof_len) memcpy(out + 164 + pv_pad, proof, proof_len);
+    return need;
+}
+ZKV_EXPORT int zkv_sp1_gateway_eth_call_returndata(const zkv_ctx* c, uint8_t status, const uint8_t recv_selector[4], uint8_t out[ZKV_RETURNDATA_STRIDE],
+                                                   uint32_t* out_len, uint8_t* reverted) {
+    static const uint8_t zero[4] = {0, 0, 0, 0};
+    if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
+    if (!out || !out_len || !reverted) return ZKV_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (status == ZKV_STATUS_OK) { *reverted = 0; return ZKV_OK; }      // verifyProof returns nothing
+    *reverted = 1;
+    if (status == ZKV_STATUS_BAD_CALLDATA) return ZKV_OK;               // the router could not decode the call: empty revert data
+    const int k = zkv_sp1_gateway_status_abi_encode(c, status, recv_selector ? recv_selector : zero, out);
+    if (k < 0) return k;
+    *out_len = (uint32_t)k;
+    return ZKV_OK;
+}
+// Calldata and its n + 1 offsets on the device.  The decode is enqueued in front of the count, so the call synchronises where run_gateway does.
+static int run_gateway_wire(zkv_ctx* c, size_t n, const uint8_t* d_cd, const uint64_t* d_off, uint64_t cd_bytes, uint8_t* d_status, uint8_t* d_recv, hipStream_t s) {
+    int rc;
+    const size_t need[7] = {32 * n, 8 * n, 4 * n, 8 * n, 4 * n, n, (size_t)(cd_bytes / 32) + 64};
+    for (int k = 0; k < 7; k++) if ((rc = grow(&c->mx[GWW_VK + k], &c->mx_cap[GWW_VK + k], need[k])) != ZKV_OK) return rc;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    GwWireArgs w;
+    memset(&w, 0, sizeof w);
+    w.n = n; w.cd = d_cd; w.off = d_off; w.cd_bytes = cd_bytes;
+    w.sel_u_be = be32_of(host::selectors().sp1[host::SP1_VERIFY_PROOF]); w.sel_b_be = be32_of(gateway_bytes_selector());
+    w.arena = c->mx[GWW_ARENA]; w.vkeys = c->mx[GWW_VK];
+    w.pv_at = (uint64_t*)c->mx[GWW_PVAT]; w.pv_len = (uint32_t*)c->mx[GWW_PVLEN]; w.proof_at = (uint64_t*)c->mx[GWW_PAT]; w.proof_len = (uint32_t*)c->mx[GWW_PLEN];
+    w.bad = c->mx[GWW_BAD];
+    // one base address for the records: the lower of the two buffers, so that every start is a plain non-negative distance
+    const uintptr_t pc = (uintptr_t)d_cd, pa = (uintptr_t)w.arena, base = pc < pa ? pc : pa;
+    w.cd_delta = pc - base; w.arena_delta = pa - base;
+    (void)hipEventRecord(c->ev_wire[0], s);
+    launch_wire_gateway(w, s);
+    (void)hipEventRecord(c->ev_wire[1], s);
+    c->wire_timed = true;
+    HIP_TRY(hipGetLastError());
+    return run_gateway(c, n, w.vkeys, (const uint8_t*)base, nullptr, 0, (const uint8_t*)base, nullptr, 0, d_status, d_recv, s, &w);
+}
+ZKV_EXPORT int zkv_sp1_gateway_eth_call_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_calldata, const uint64_t* d_calldata_off, uint64_t calldata_bytes,
+                                                  uint8_t* d_status, uint8_t* d_recv, void* stream) {
+    if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_calldata || !d_calldata_off || !d_status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    return run_gateway_wire(c, n, d_calldata, d_calldata_off, calldata_bytes, d_status, d_recv, stream ? (hipStream_t)stream : c->stream);
+}
+ZKV_EXPORT int zkv_sp1_gateway_eth_call_batch(zkv_ctx* c, size_t n, const uint8_t* blob, const uint64_t* off, uint8_t* reverted, uint8_t* returndata,
+                                              uint32_t* returndata_len, uint8_t* status) {
+    if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
+    if (n && (!blob || !off || !reverted || !returndata || !returndata_len)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u || !offsets_ok(off, n)) return ZKV_ERR_INVALID_ARG;
+    std::vector<uint8_t> st(n), rv(4 * n);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        int rc = ctx_device_init(c);
+        if (rc != ZKV_OK) return rc;
+        const uint64_t b0 = off[0], bytes = off[n] - b0;
+        const size_t need[4] = {(size_t)bytes + 8, 8 * (n + 1), n, 4 * n};
+        const int slot[4] = {GWW_H_CD, GWW_H_OFF, GW_H_ST, GW_H_RV};
+        for (int k = 0; k < 4; k++) if ((rc = grow(&c->mx[slot[k]], &c->mx_cap[slot[k]], need[k])) != ZKV_OK) return rc;
+        hipStream_t s = c->stream;
+        if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+        std::vector<uint64_t> rel(off, off + n + 1);
+        for (auto& v : rel) v -= b0;
+        if (bytes) HIP_TRY(hipMemcpyAsync(c->mx[GWW_H_CD], blob + b0, (size_t)bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c->mx[GWW_H_OFF], rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));                        // `rel` is a pageable host buffer
+        if ((rc = run_gateway_wire(c, n, c->mx[GWW_H_CD], (const uint64_t*)c->mx[GWW_H_OFF], bytes, c->mx[GW_H_ST], c->mx[GW_H_RV], s)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(st.data(), c->mx[GW_H_ST], n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(rv.data(), c->mx[GW_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (size_t i = 0; i < n; i++) {
+        const int rc = zkv_sp1_gateway_eth_call_returndata(c, st[i], rv.data() + 4 * i, returndata + i * ZKV_RETURNDATA_STRIDE, &returndata_len[i], &reverted[i]);
+        if (rc != ZKV_OK) return rc;
+        if (status) status[i] = st[i];
+    }
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_sp1_gateway_last_call_counts(zkv_ctx* c, uint64_t* out) {
+    if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const size_t R = c->gw_route.size();
+    for (size_t r = 0; r < R; r++) out[r] = c->gw_counts[r];
+    out[R] = c->gw_counts[GW_COL_NOT_FOUND]; out[R + 1] = c->gw_counts[GW_COL_SHORT]; out[R + 2] = c->gw_counts[GW_COL_BAD];
     return ZKV_OK;
 }
 

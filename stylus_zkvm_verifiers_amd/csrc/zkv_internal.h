@@ -72,6 +72,20 @@ struct WireArgs {
 };
 void launch_wire_risc0(const WireArgs& a, hipStream_t s);
 void launch_wire_sp1(const WireArgs& a, hipStream_t s);
+// eth_call calldata of the SP1 gateway (k_wire_gateway in k_wire.hip; zkv_wire_gateway.h has the two forms): one record per request,
+// its public values and proof as (start, true length) from `base`, an address at or below both the calldata blob and the arena.  Form U
+// requests are compacted into the arena (request i at arena[off[i] / 32 ..): public values, then the first min(Lproof, ZKV_PLONK_PROOF_BYTES)
+// proof bytes); form B records point into the blob.  A request that is not a canonical call has bad = 1 and zero starts and lengths.
+struct GwWireArgs {
+    size_t n;
+    const uint8_t* cd; const uint64_t* off; uint64_t cd_bytes;                  // as WireArgs
+    uint32_t sel_u_be, sel_b_be;                                               // verifyProof(bytes32,uint8[],uint8[]) / verifyProof(bytes32,bytes,bytes)
+    uint8_t* arena;                                                            // cd_bytes / 32 + 64 bytes
+    uint64_t cd_delta, arena_delta;                                            // cd - base, arena - base
+    uint8_t* vkeys;                                                            // n x 32
+    uint64_t* pv_at; uint32_t* pv_len; uint64_t* proof_at; uint32_t* proof_len; uint8_t* bad;
+};
+void launch_wire_gateway(const GwWireArgs& a, hipStream_t s);
 
 void launch_setup(const VkRaw* d_raw, VkTables* d_tab, hipStream_t s);
 void launch_prep_risc0(const PrepArgs& a, const Risc0Consts& k, const Workspace& ws, hipStream_t s);
@@ -119,14 +133,18 @@ void launch_mixed_partition(const MixedArgs& a, uint32_t* cnt, uint32_t* totals,
 void launch_mixed_return(size_t m, const uint32_t* idx, const uint8_t* c_status, const uint8_t* c_recv, uint8_t* status, uint8_t* recv, hipStream_t s);
 
 // SP1 gateway (k_gateway.hip, include/zkv_sp1_gateway.h): every proof goes to the route whose selector begins it.  Count columns:
-// routes 0 .. GW_MAX_ROUTES - 1, then GW_COL_NOT_FOUND and GW_COL_SHORT (shorter than 4 bytes, or offsets outside the blob).
-constexpr int GW_MAX_ROUTES = 8, GW_COL_NOT_FOUND = 8, GW_COL_SHORT = 9, GW_COLS = 10;
+// routes 0 .. GW_MAX_ROUTES - 1, then GW_COL_NOT_FOUND, GW_COL_SHORT (shorter than 4 bytes, or offsets outside the blob) and GW_COL_BAD
+// (record input only: the request was not a canonical call, GwWireArgs::bad).
+constexpr int GW_MAX_ROUTES = 8, GW_COL_NOT_FOUND = 8, GW_COL_SHORT = 9, GW_COL_BAD = 10, GW_COLS = 11;
 constexpr uint32_t GW_NONE = 0xFFFFFFFFu;
 struct GatewayArgs {
     size_t n;
     const uint8_t* proofs; const uint64_t* proof_off; uint64_t proof_bytes;    // ragged proofs; proof_bytes bounds every read
     const uint8_t* vkeys;                                                      // n x 32
     const uint64_t* pv_off; uint64_t pv_stride;                                // public values: n + 1 offsets (ragged) or a fixed stride
+    // record input (rec_proof_at set: proof_off, proof_bytes, pv_off and pv_stride are unused): (start, length) per proof, gaps allowed.
+    // The records come from k_wire_gateway, which has bounded them; `proofs` and the public-values blob are then its one `base`.
+    const uint64_t* rec_proof_at; const uint32_t* rec_proof_len; const uint64_t* rec_pv_at; const uint32_t* rec_pv_len; const uint8_t* rec_bad;
     uint32_t n_routes;
     uint32_t sel[GW_MAX_ROUTES];                                               // route selectors, big-endian words (kernel arguments: SGPRs)
     uint32_t rec[GW_MAX_ROUTES];                                               // record bytes per route: ZKV_SEAL_BYTES or ZKV_PLONK_PROOF_BYTES

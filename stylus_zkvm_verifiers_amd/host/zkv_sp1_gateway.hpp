@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/zkv_sp1_gateway.h"
+#include "../../include/zkv_sp1_gateway_wire.h"
 
 namespace zkv {
 
@@ -51,6 +52,33 @@ public:
         std::vector<uint64_t> out(route_count() + 2);
         const int rc = zkv_sp1_gateway_last_route_counts(ctx_, out.data());
         if (rc != ZKV_OK) throw std::runtime_error("zkv_sp1_gateway_last_route_counts failed with ZKV error " + std::to_string(rc));
+        return out;
+    }
+    // eth_call batches (include/zkv_sp1_gateway_wire.h): raw verifyProof calldata, either form, Groth16 and PLONK proofs mixed.
+    // Canonical calldata of one call; form = ZKV_CALLDATA_FORM_UINT8_ARRAY or ZKV_CALLDATA_FORM_BYTES.
+    static std::vector<uint8_t> encode_verify_proof_call(int form, const uint8_t vkey[32], const std::vector<uint8_t>& pv, const std::vector<uint8_t>& proof) {
+        const size_t n = zkv_sp1_gateway_encode_verify_proof_call(form, vkey, pv.data(), pv.size(), proof.data(), proof.size(), nullptr, 0);
+        if (!n) throw std::invalid_argument("Sp1Gateway::encode_verify_proof_call: no such calldata form");
+        std::vector<uint8_t> out(n);
+        zkv_sp1_gateway_encode_verify_proof_call(form, vkey, pv.data(), pv.size(), proof.data(), proof.size(), out.data(), n);
+        return out;
+    }
+    struct EthCallResult { std::vector<uint8_t> reverted, returndata, status; std::vector<uint32_t> returndata_len; };   // returndata: n x ZKV_RETURNDATA_STRIDE
+    EthCallResult eth_call_batch(const std::vector<uint8_t>& calldata_blob, const std::vector<uint64_t>& calldata_off) const {
+        const size_t n = calldata_off.empty() ? 0 : calldata_off.size() - 1;
+        EthCallResult r;
+        r.reverted.assign(n, 0); r.status.assign(n, 0); r.returndata_len.assign(n, 0); r.returndata.assign(n * ZKV_RETURNDATA_STRIDE, 0);
+        const uint8_t zero = 0;
+        const int rc = zkv_sp1_gateway_eth_call_batch(ctx_, n, calldata_blob.empty() ? &zero : calldata_blob.data(), calldata_off.data(), r.reverted.data(),
+                                                      r.returndata.data(), r.returndata_len.data(), r.status.data());
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_sp1_gateway_eth_call_batch failed with ZKV error " + std::to_string(rc));
+        return r;
+    }
+    // {proofs per route..., not found, shorter than 4 bytes, bad calldata} of the most recent call
+    std::vector<uint64_t> last_call_counts() const {
+        std::vector<uint64_t> out(route_count() + 3);
+        const int rc = zkv_sp1_gateway_last_call_counts(ctx_, out.data());
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_sp1_gateway_last_call_counts failed with ZKV error " + std::to_string(rc));
         return out;
     }
     // Opt-in aggregate check on every route (zkv_ctx_set_aggregate_check): sub_batch 0 = automatic size, 16 ... 256 fixed.

@@ -129,6 +129,40 @@ class Sp1Gateway:
         _lib.check(self._L.zkv_sp1_gateway_last_route_counts(self._h, out), 'zkv_sp1_gateway_last_route_counts')
         return list(out)
 
+    def last_call_counts(self):
+        """last_route_counts with one more column: requests of the most recent eth_call batch that were not canonical calldata."""
+        from . import sp1_gateway_wire as w
+        return w.last_call_counts(self._h, self._L.zkv_sp1_gateway_route_count(self._h))
+
+    # eth_call batches (include/zkv_sp1_gateway_wire.h, sp1_gateway_wire.py): raw verifyProof calldata, decoded and routed on the device
+    @staticmethod
+    def encode_verify_proof_call(program_vkey, public_values, proof_bytes, form=1):
+        """Canonical calldata in `form`: 0 = verifyProof(bytes32,uint8[],uint8[]), 1 = verifyProof(bytes32,bytes,bytes)."""
+        from . import sp1_gateway_wire as w
+        return w.encode_verify_proof_call(program_vkey, public_values, proof_bytes, form)
+
+    def eth_call_batch(self, calls):
+        """calls: calldata byte strings, either form, Groth16 and PLONK proofs mixed -> (reverted uint8[n], [return / revert data],
+        status uint8[n]).  Success returns nothing; anything but a canonical verifyProof call is BAD_CALLDATA with empty revert data."""
+        from . import sp1_gateway_wire as w
+        return w.eth_call_batch(self._h, calls)
+
+    def eth_call_batch_dev(self, n, d_calldata, d_calldata_off, calldata_bytes, d_status, d_recv=0, stream=0):
+        """Device-resident calldata blob and its n + 1 uint64 offsets; n status bytes and n x 4 received selectors (0: none) stay on the
+        device (eth_call_returndata turns one into return / revert data)."""
+        from . import sp1_gateway_wire as w
+        w.eth_call_batch_dev(self._h, n, d_calldata, d_calldata_off, calldata_bytes, d_status, d_recv, stream)
+
+    def eth_call_returndata(self, status, received=bytes(4)):
+        from . import sp1_gateway_wire as w
+        return w.eth_call_returndata(self._h, status, received)
+
+    def last_wire_ms(self):
+        """Decode time of the most recent eth_call batch."""
+        out = C.c_float(0)
+        _lib.check(self._L.zkv_ctx_last_wire_ms(self._h, C.byref(out)), 'zkv_ctx_last_wire_ms')
+        return out.value
+
     def status_abi_encode(self, status, received=bytes(4)):
         """Revert data of a gateway status (RouteNotFound(bytes4) for ROUTE_NOT_FOUND; unpinned)."""
         o = C.create_string_buffer(68)
