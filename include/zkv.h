@@ -59,7 +59,15 @@ const char* zkv_version(void);
 /* An un-initialised verifier bound to HIP device `device` (storage with initialized = false).
  * Device memory of a context, allocated at its first compute call: the key's tables (Groth16: 3 MB, plus the 16-bit window rows of the
  * vk_x stage -- 67 MB for RISC Zero, 134 MB for SP1, ZKV_MSM_WINDOW_BITS=8 leaves them out; SP1 PLONK: 24 MB) and a workspace that grows
- * with the largest chunk it has seen (about 4 KB per proof, chunks of at most 2^20 proofs). */
+ * with the largest chunk it has seen (about 4 KB per proof, chunks of at most 2^20 proofs).
+ * GT tables: a RISC Zero or SP1 context whose calls can run lane-pair chunks (more than 12,288 proofs, or zkv_ctx_set_lanes_per_proof 2)
+ * also builds, at the first such call, fixed-base tables of e(IC_i, gamma) for its two per-proof signals -- 2^19 entries of 384 bytes per
+ * signed 20-bit window: 2 x 7 windows = 2.8 GB for RISC Zero, 2 x 13 = 5.2 GB for SP1 (a mixed context: both), built in about 50 ms.
+ * ZKV_GT_WINDOW_BITS=0 leaves them out (20 or unset builds them; any other value makes that call return ZKV_ERR_INVALID_ARG),
+ * ZKV_GT_MAX_BYTES bounds them; a context without them (also: no room on the device) pairs (vk_x, gamma) in the Miller loop as before,
+ * with the same statuses.  The build is tried once per context, by a verifying call (zkv_ctx_vk_x_batch never builds them): a context
+ * that had no room then keeps the Miller path, and tables once built are kept until the context is destroyed -- a workspace that grows
+ * later does not take their memory back, so a context meant for large batches should see one (or zkv_ctx_reserve) first. */
 zkv_ctx* zkv_risc0_ctx_new(int device);
 /* IRiscZeroVerifier::initialize (risc0/verifier.rs:58-76): *status = OK or ALREADY_INITIALIZED. */
 int zkv_risc0_initialize(zkv_ctx* ctx, const uint8_t control_root[32], const uint8_t bn254_control_id[32], uint8_t* status);

@@ -5,16 +5,17 @@
 
 namespace zkv {
 
-__global__ __launch_bounds__(ZKV_BLOCK) void k_msm(size_t n, const VkTables* __restrict__ vk, Msm16 m16, const InstTab* __restrict__ inst_tab, Workspace ws) {
+__global__ __launch_bounds__(ZKV_BLOCK) void k_msm(size_t n, const VkTables* __restrict__ vk, Msm16 m16, const InstTab* __restrict__ inst_tab, Workspace ws, uint32_t skip_vk_x) {
     size_t i = (size_t)blockIdx.x * ZKV_BLOCK + threadIdx.x;
     if (i >= n) return;
     uint32_t flags = ws.flags[i];
     if (!(flags & FL_ALIVE)) return;
     // the scalars' window digits are read from the proof's workspace row as the walk needs them (L1 / L2 hits: 64 bytes per proof)
-    auto word = [&](uint32_t b, uint32_t k) { return ws.prep[(size_t)(64 + 8 * b + k) * ws.cap + i]; };
+    auto word = [&](uint32_t b, uint32_t k) { return ws.prep[(size_t)(64 + 8 * b + k) * ws.cap + i]; };     // read only: k_finalexp2 reads these rows again (GT tables)
     const G1A* base = &vk->base; uint32_t base_inf = vk->base_inf;
     if (inst_tab) { const InstTab& t = inst_tab[flags >> 8]; flags &= 0xFFu; base = &t.base; base_inf = t.base_inf; }     // verifier set: the instance index rides in the upper bits of the flags word
-    const G1J acc = m16.tab ? msm_accumulate_w16(*vk, m16, word, *base, base_inf) : msm_accumulate_w(*vk, word, *base, base_inf);
+    // skip_vk_x: the pairing of vk_x comes from the GT tables (zkv_gt.h); the Miller loop sees "vk_x absent" and only A' and C are normalised
+    const G1J acc = skip_vk_x ? g1j_infinity() : m16.tab ? msm_accumulate_w16(*vk, m16, word, *base, base_inf) : msm_accumulate_w(*vk, word, *base, base_inf);
     PrepOut in;
     in.ax = ws_ld(ws.prep, ws.cap, 0, i); in.ay = ws_ld(ws.prep, ws.cap, 8, i);
     in.cx = ws_ld(ws.prep, ws.cap, 16, i); in.cy = ws_ld(ws.prep, ws.cap, 24, i);
@@ -182,9 +183,9 @@ void launch_vk_x_long(size_t n, uint32_t lanes, const VkTables* d_tab, const Lon
     else hipLaunchKernelGGL(k_vk_x_long<1>, grid, block, 0, s, n, d_tab, lk, sig, out);
 }
 
-void launch_msm(size_t n, const VkTables* d_tab, const Msm16& m16, const InstTab* inst_tab, const Workspace& ws, hipStream_t s) {
+void launch_msm(size_t n, const VkTables* d_tab, const Msm16& m16, const InstTab* inst_tab, const Workspace& ws, hipStream_t s, bool skip_vk_x) {
     if (!n) return;
-    hipLaunchKernelGGL(k_msm, dim3((unsigned)((n + ZKV_BLOCK - 1) / ZKV_BLOCK)), dim3(ZKV_BLOCK), 0, s, n, d_tab, m16, inst_tab, ws);
+    hipLaunchKernelGGL(k_msm, dim3((unsigned)((n + ZKV_BLOCK - 1) / ZKV_BLOCK)), dim3(ZKV_BLOCK), 0, s, n, d_tab, m16, inst_tab, ws, skip_vk_x ? 1u : 0u);
 }
 
 }  // namespace zkv

@@ -56,7 +56,7 @@ __device__ __forceinline__ void zkv_stamp(unsigned kernel, unsigned slot) {
 
 // The Miller loop is also the subgroup test of B (miller_loop_p, check_b): a proof whose B is outside G2 gets the precompile-failure
 // status here and is skipped by k_finalexp2.  (k_g2chk2 remains for the 16-lane kernels of small chunks.)
-__global__ __launch_bounds__(PAIR_BLOCK, 2) void k_miller2(size_t n, const VkTables* __restrict__ vk, Workspace ws, uint8_t* __restrict__ status) {
+__global__ __launch_bounds__(PAIR_BLOCK, 2) void k_miller2(size_t n, const VkTables* __restrict__ vk, const uint32_t* __restrict__ mconst, Workspace ws, uint8_t* __restrict__ status) {
     __shared__ uint32_t lds[(48 + 24) * PAIR_BLOCK];      // per wavefront: f: 6 Fp per lane, T: 3 Fp per lane, lane-interleaved
     ZKV_STAMP(0, 0);
     size_t i = ((size_t)blockIdx.x * PAIR_BLOCK + threadIdx.x) >> 1;
@@ -73,13 +73,15 @@ __global__ __launch_bounds__(PAIR_BLOCK, 2) void k_miller2(size_t n, const VkTab
         if (!par) { ws.g2bad[i] = 1; status[i] = ST_VERIFICATION_FAILED; }
         return;
     }
-    MRef ab = m_ref((uint32_t*)(vk->f_alpha_beta) + 8 * par, 1, 16);
+    // the per-context constant: ML(alpha, beta), times ML(base, gamma) when the (vk_x, gamma) pair is left to the GT tables (zkv_gt.h; k_msm then
+    // marked every vk_x as absent, so the loop above took no trip for it)
+    MRef ab = m_ref((uint32_t*)(mconst ? mconst : vk->f_alpha_beta) + 8 * par, 1, 16);
     MRef out = m_ref(ws.f + (size_t)(8 * par) * ws.cap + i, (uint32_t)ws.cap, 16);
     f12m_mul_body(out, fm, ab, false);
     ZKV_STAMP(0, 1);
 }
 
-__global__ __launch_bounds__(PAIR_BLOCK, 2) void k_finalexp2(size_t n, Workspace ws, uint8_t* __restrict__ status) {
+__global__ __launch_bounds__(PAIR_BLOCK, 2) void k_finalexp2(size_t n, GtTab gt, long long gt_rel, Workspace ws, uint8_t* __restrict__ status) {
     __shared__ uint32_t lds[54 * PAIR_BLOCK];             // the accumulator in resident 29-bit limbs: 6 coefficients x 9 words per lane
     ZKV_STAMP(1, 0);
     size_t i = ((size_t)blockIdx.x * PAIR_BLOCK + threadIdx.x) >> 1;
@@ -89,7 +91,8 @@ __global__ __launch_bounds__(PAIR_BLOCK, 2) void k_finalexp2(size_t n, Workspace
     const uint32_t par = threadIdx.x & 1u;
     uint32_t* wl = lds + (threadIdx.x >> 6) * (54 * ZKV_BLOCK) + (threadIdx.x & 63u);
     L9Ref acc = l9_ref(wl);
-    bool one = final_exp_prog_p(ws.f, ws.fe, ws.cap, (uint32_t)(8 * par * ws.cap + i) * 4u, acc);
+    const GtRef g = {gt.tab != nullptr, (ptrdiff_t)gt_rel, ws.prep + 64 * ws.cap, gt.nw[0], gt.nw[1]};
+    bool one = final_exp_prog_p(ws.f, ws.fe, ws.cap, (uint32_t)(8 * par * ws.cap + i) * 4u, acc, g);
     if (!par) status[i] = one ? ST_OK : ST_VERIFICATION_FAILED;
     ZKV_STAMP(1, 1);
 }
@@ -321,13 +324,28 @@ void launch_g2chk2(size_t n, const Workspace& ws, uint8_t* status, hipStream_t s
     if (!n) return;
     hipLaunchKernelGGL(k_g2chk2, dim3(pair_grid(n)), dim3(ZKV_BLOCK), 0, s, n, ws, status);
 }
-void launch_miller2(size_t n, const VkTables* d_tab, const Workspace& ws, uint8_t* status, hipStream_t s) {
+void launch_miller2(size_t n, const VkTables* d_tab, const Workspace& ws, uint8_t* status, hipStream_t s, const uint32_t* mconst) {
     if (!n) return;
-    hipLaunchKernelGGL(k_miller2, dim3(hot_grid(n)), dim3(PAIR_BLOCK), 0, s, n, d_tab, ws, status);
+    hipLaunchKernelGGL(k_miller2, dim3(hot_grid(n)), dim3(PAIR_BLOCK), 0, s, n, d_tab, mconst, ws, status);
 }
-void launch_finalexp2(size_t n, const Workspace& ws, uint8_t* status, hipStream_t s) {
+void launch_finalexp2(size_t n, const Workspace& ws, uint8_t* status, hipStream_t s, const GtTab& gt) {
     if (!n) return;
-    hipLaunchKernelGGL(k_finalexp2, dim3(hot_grid(n)), dim3(PAIR_BLOCK), 0, s, n, ws, status);
+    // the tables' place in words from the E rows (GtRef::rel); both are device allocations, 4-byte aligned
+    const long long rel = gt.tab ? (long long)(((intptr_t)gt.tab - (intptr_t)ws.fe) / 4) : 0;
+    hipLaunchKernelGGL(k_finalexp2, dim3(hot_grid(n)), dim3(PAIR_BLOCK), 0, s, n, gt, rel, ws, status);
+}
+// TEST ONLY (zkv_diag_gt_product): every proof alive with the Miller value 1.  k_finalexp2 then exponentiates 1 to 1, walks the tables
+// over the scalars the caller put in ws.prep, and its last COPY TMP <- ACC leaves the product M of the walk in the slot TMP.
+__global__ __launch_bounds__(ZKV_BLOCK) void k_gt_diag_seed(size_t n, Workspace ws) {
+    const size_t i = ((size_t)blockIdx.x * ZKV_BLOCK + threadIdx.x) >> 1;
+    if (i >= n) return;
+    const uint32_t par = threadIdx.x & 1u;
+    f12m_set_one(m_ref(ws.f + (size_t)(8 * par) * ws.cap + i, (uint32_t)ws.cap, 16));
+    if (!par) { ws.flags[i] = FL_ALIVE; ws.g2bad[i] = 0; }
+}
+void launch_gt_diag_seed(size_t n, const Workspace& ws, hipStream_t s) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_gt_diag_seed, dim3(pair_grid(n)), dim3(ZKV_BLOCK), 0, s, n, ws);
 }
 
 }  // namespace zkv

@@ -25,6 +25,7 @@
 #include "../../include/zkv_plonk_set_agg.h"
 #include "../../include/zkv_diag_primitive.h"
 #include "../../include/zkv_diag_prep.h"
+#include "../../include/zkv_diag_gt.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
@@ -69,6 +70,12 @@ struct zkv_ctx {
     VkTables* d_tab = nullptr;
     G1A* d_msm16 = nullptr;                                  // the vk_x stage's 16-bit window rows (Msm16; null: 8-bit walk)
     Msm16 m16 = {nullptr, {0, 0, 0, 0, 0}};
+    // fixed-base GT tables of the (vk_x, gamma) pairing (zkv_gt.h): built the first time a call can run lane-pair chunks (gt_maybe_build);
+    // gt.tab == nullptr: none (ZKV_GT_WINDOW_BITS=0, no room, another kind of context) -- the Miller loop takes the pair
+    uint32_t *d_gt = nullptr, *d_gt_const = nullptr;
+    GtTab gt = GT_NONE;
+    bool gt_tried = false;
+    size_t gt_bytes = 0; float gt_build_ms = 0;
     Workspace ws = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     hipStream_t side = nullptr;                              // small chunks: the G2 subgroup check runs beside the MSM
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -326,7 +333,8 @@ static void ctx_free_device(zkv_ctx* c) {
     if (!c->dev_ready && !c->stream) return;
     (void)hipSetDevice(c->device);
     c->m16 = {nullptr, {0, 0, 0, 0, 0}};
-    void** ptrs[] = {(void**)&c->d_tab, (void**)&c->d_msm16, (void**)&c->ws.prep, (void**)&c->ws.norm, (void**)&c->ws.f, (void**)&c->ws.fe, (void**)&c->ws.flags,
+    c->gt = GT_NONE; c->gt_tried = false; c->gt_bytes = 0;
+    void** ptrs[] = {(void**)&c->d_tab, (void**)&c->d_msm16, (void**)&c->d_gt, (void**)&c->d_gt_const, (void**)&c->ws.prep, (void**)&c->ws.norm, (void**)&c->ws.f, (void**)&c->ws.fe, (void**)&c->ws.flags,
                      (void**)&c->ws.g2bad, (void**)&c->d_blob, (void**)&c->d_a, (void**)&c->d_b, (void**)&c->d_pv, (void**)&c->d_status,
                      (void**)&c->d_recv, (void**)&c->d_off, (void**)&c->d_pvoff, (void**)&c->d_cd[0], (void**)&c->d_cd[1], (void**)&c->d_kind,
                      (void**)&c->d_cdoff[0], (void**)&c->d_cdoff[1], (void**)&c->d_len, (void**)&c->d_pvlen, (void**)&c->d_st_all,
@@ -561,10 +569,77 @@ static int ctx_reserve(zkv_ctx* c, size_t want) {
     c->ws.cap = cap;
     return agg_reserve(c);
 }
+// Fixed-base GT tables (zkv_gt.h) for the (vk_x, gamma) pairing of an SP1 or RISC Zero context: 2^19 entries of 384 bytes per signed 20-bit
+// window of each per-proof signal -- SP1 2 x 13 windows = 5.2 GB, RISC Zero 2 x 7 = 2.8 GB per context.  ZKV_GT_WINDOW_BITS=0 switches them
+// off; ZKV_GT_MAX_BYTES bounds what a context may take for them.  A context without them (switched off, over the bound, or no room on the
+// device) keeps the pair in the Miller loop: same statuses.
+// ZKV_GT_WINDOW_BITS: "0" switches the tables off, "20" (the only width built) or unset keeps them; anything else is refused at the first
+// call that would build them (ZKV_ERR_INVALID_ARG) rather than read as one of the two.
+static int gt_window_bits() {
+    const char* e = getenv("ZKV_GT_WINDOW_BITS");
+    if (!e || !strcmp(e, "20")) return (int)GT_WINDOW_BITS;
+    return !strcmp(e, "0") ? 0 : -1;
+}
+static size_t gt_max_bytes() {
+    const char* e = getenv("ZKV_GT_MAX_BYTES");
+    return e ? (size_t)strtoull(e, nullptr, 10) : ~(size_t)0;
+}
+// Built the first time a call of n proofs can run lane-pair chunks (the only kernels that read them), after the workspace: contexts
+// that only ever see small batches never pay for them.
+// One attempt per context (gt_tried): a context that had no room then keeps the Miller path for its life, and tables once built stay
+// until the context is destroyed.
+static int gt_maybe_build(zkv_ctx* c, size_t n) {
+    if (c->gt_tried || (c->vm != ZKV_VM_SP1 && c->vm != ZKV_VM_RISC0) || c->vk_invalid || !c->d_tab) return ZKV_OK;
+    const size_t per = n < chunk_capacity() ? n : chunk_capacity();
+    if (!(c->lanes == 2 || (c->lanes == 0 && per > wide_below()))) return ZKV_OK;
+    const int bits = gt_window_bits();
+    if (bits < 0) return ZKV_ERR_INVALID_ARG;
+    c->gt_tried = true;
+    if (bits == 0) return ZKV_OK;
+    VkRaw raw;
+    if (c->vm == ZKV_VM_RISC0) host::fill_vk_risc0(raw, c->control_root_0, c->control_root_1, c->control_id);
+    else host::fill_vk_sp1(raw);
+    if (raw.n_var != GT_MAX_SIG || !raw.var_windows[0] || !raw.var_windows[1]) return ZKV_OK;
+    const uint32_t nw0 = gt_windows(8 * raw.var_windows[0]), nw1 = gt_windows(8 * raw.var_windows[1]), rows = nw0 + nw1;
+    if (nw0 > GT_MAX_WINDOWS || nw1 > GT_MAX_WINDOWS) return ZKV_OK;
+    const size_t bytes = (size_t)rows * GT_ROW_BYTES;
+    if (bytes > gt_max_bytes()) return ZKV_OK;
+    VkRaw* d_raw = nullptr; uint32_t* d_scr = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool ok = hipMalloc(&c->d_gt, bytes) == hipSuccess && hipMalloc(&c->d_gt_const, sizeof(uint32_t) * GT_ENTRY_WORDS) == hipSuccess &&
+              hipMalloc(&d_raw, sizeof(VkRaw)) == hipSuccess && hipMalloc(&d_scr, sizeof(uint32_t) * GT_SETUP_SCRATCH_WORDS) == hipSuccess &&
+              hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    if (ok) {
+        ok = hipMemcpyAsync(d_raw, &raw, sizeof raw, hipMemcpyHostToDevice, c->stream) == hipSuccess;
+        (void)hipEventRecord(e0, c->stream);
+        launch_gt_bases(d_raw, c->d_tab, c->d_gt, c->d_gt_const, d_scr, nw0, nw1, c->stream);
+        for (uint32_t level = 1; level < GT_WINDOW_BITS; level++) launch_gt_level(c->d_gt, rows, level, c->stream);
+        (void)hipEventRecord(e1, c->stream);
+        ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+        if (ok) (void)hipEventElapsedTime(&c->gt_build_ms, e0, e1);
+    }
+    (void)hipGetLastError();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (d_raw) (void)hipFree(d_raw);
+    if (d_scr) (void)hipFree(d_scr);
+    if (!ok) {                                                // no room (or a failed launch): the Miller path, same results
+        if (c->d_gt) (void)hipFree(c->d_gt);
+        if (c->d_gt_const) (void)hipFree(c->d_gt_const);
+        c->d_gt = c->d_gt_const = nullptr;
+        return ZKV_OK;
+    }
+    c->gt = GtTab{c->d_gt, c->d_gt_const, {nw0, nw1}};
+    c->gt_bytes = bytes;
+    return ZKV_OK;
+}
 // device set-up + buffers for a batch of n
-static int ctx_ready(zkv_ctx* c, size_t n) {
+// verify == false: a call that runs no verification kernels (zkv_ctx_vk_x_batch) -- it never reads the GT tables and does not build them
+static int ctx_ready(zkv_ctx* c, size_t n, bool verify = true) {
     int rc = ctx_device_init(c);
-    return rc != ZKV_OK ? rc : ctx_reserve(c, n ? n : 1);
+    if (rc == ZKV_OK) rc = ctx_reserve(c, n ? n : 1);
+    if (rc == ZKV_OK && verify) rc = gt_maybe_build(c, n ? n : 1);
+    return rc;
 }
 static int grow(uint8_t** p, size_t* cap, size_t need) {
     if (need <= *cap) return ZKV_OK;
@@ -782,7 +857,12 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
         // of the last `tail` through their own small-batch mapping (whose Miller kernels leave the subgroup test of B to k_g2chk2)
         const size_t head = a.n - tail;
         const Workspace wt = ws_from(c->ws, head);
+        const bool gt = c->gt.tab != nullptr;               // the head's (vk_x, gamma) pairing comes from the GT tables: no window walk for it
         if (c->long_key) launch_msm_long(a.n, msm_lanes_long(c, a.n), c->d_tab, long_key_of(c), c->ws, s);
+        else if (gt) {
+            launch_msm(head, c->d_tab, c->m16, nullptr, c->ws, s, true);
+            launch_msm(tail, c->d_tab, c->m16, nullptr, wt, s);
+        }
         else launch_msm(a.n, c->d_tab, c->m16, a.inst ? c->d_inst : nullptr, c->ws, s);
         if (timed) (void)hipEventRecord(c->ev[2], s);
         // the tail's kernels on the second stream beside the lane-pair kernels of the others (odd number of layers), or after them
@@ -792,11 +872,11 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
         if (beside) { (void)hipEventRecord(c->ev_fork, s); (void)hipStreamWaitEvent(c->side, c->ev_fork, 0); }
         launch_g2chk2(tail, wt, a.status + head, st);
         if (timed) (void)hipEventRecord(c->ev[3], s);
-        launch_miller2(head, c->d_tab, c->ws, a.status, s);
+        launch_miller2(head, c->d_tab, c->ws, a.status, s, c->gt.mconst);
         const int tl = miller_lanes(c, tail);                // (automatic: a fixed mapping takes no tail split)
         launch_miller_lanes(tl, tail, c->d_tab, wt, a.status + head, st);
         if (timed) (void)hipEventRecord(c->ev[4], s);
-        launch_finalexp2(head, c->ws, a.status, s);
+        launch_finalexp2(head, c->ws, a.status, s, c->gt);
         launch_finalexp_lanes(tl, tail, wt, a.status + head, st);
         if (beside) { (void)hipEventRecord(c->ev_join, c->side); (void)hipStreamWaitEvent(s, c->ev_join, 0); }
         if (timed) (void)hipEventRecord(c->ev[5], s);
@@ -806,6 +886,7 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
     // in the Miller loop (smallest)
     const int lanes = miller_lanes(c, a.n);
     const bool wide = lanes != 2;
+    const bool gt = !wide && c->gt.tab != nullptr;           // lane pairs with GT tables (zkv_gt.h): no vk_x walk, no (vk_x, gamma) trip in the Miller loop
     // Lane-pair kernels: the Miller loop itself is the subgroup test of B (miller_loop_p), there is no separate check; stage time
     // [2] is then 0.  16-lane kernels (small chunks, most of the chip idle): the check (k_g2chk2) only needs the PREP output and only
     // its verdict (ws.g2bad; the MSM owns ws.flags) is needed, by the final exponentiation, so it runs on a second stream beside the
@@ -818,15 +899,18 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
         (void)hipEventRecord(c->ev_join, c->side);
     }
     if (c->long_key) launch_msm_long(a.n, msm_lanes_long(c, a.n), c->d_tab, long_key_of(c), c->ws, s);
+    else if (gt) launch_msm(a.n, c->d_tab, c->m16, nullptr, c->ws, s, true);
     else if (a.n <= msm_wave_below()) launch_msm_w(a.n, c->d_tab, a.inst ? c->d_inst : nullptr, c->ws, s);     // one proof per wavefront
     else launch_msm(a.n, c->d_tab, c->m16, a.inst ? c->d_inst : nullptr, c->ws, s);
     if (timed) (void)hipEventRecord(c->ev[2], s);
     if (wide && !fork) launch_g2chk2(a.n, c->ws, a.status, s);
     if (timed) (void)hipEventRecord(c->ev[3], s);
-    launch_miller_lanes(lanes, a.n, c->d_tab, c->ws, a.status, s);
+    if (gt) launch_miller2(a.n, c->d_tab, c->ws, a.status, s, c->gt.mconst);
+    else launch_miller_lanes(lanes, a.n, c->d_tab, c->ws, a.status, s);
     if (timed) (void)hipEventRecord(c->ev[4], s);
     if (fork) (void)hipStreamWaitEvent(s, c->ev_join, 0);     // the final exponentiation reads the verdict of the subgroup check
-    launch_finalexp_lanes(lanes, a.n, c->ws, a.status, s);
+    if (gt) launch_finalexp2(a.n, c->ws, a.status, s, c->gt);
+    else launch_finalexp_lanes(lanes, a.n, c->ws, a.status, s);
     if (timed) (void)hipEventRecord(c->ev[5], s);
 }
 
@@ -3138,7 +3222,7 @@ ZKV_EXPORT int zkv_ctx_vk_x_batch(zkv_ctx* c, size_t n, const uint8_t* var_signa
     const size_t sig = 32 * (size_t)(c->vm == ZKV_VM_GROTH16 ? c->g_n_ic - 1 : 2);
     std::lock_guard<std::mutex> lk(c->mu);
     size_t cap = 0;
-    int rc = c->vm == ZKV_VM_GROTH16 ? groth16_ready(c, n, &cap) : ctx_ready(c, n);
+    int rc = c->vm == ZKV_VM_GROTH16 ? groth16_ready(c, n, &cap) : ctx_ready(c, n, false);
     if (rc != ZKV_OK) return rc;
     if (c->vm != ZKV_VM_GROTH16) cap = c->ws.cap;
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
@@ -3259,6 +3343,62 @@ ZKV_EXPORT int zkv_ctx_set_lanes_per_proof(zkv_ctx* c, int lanes) {
     for (auto* k : c->gw_route) { const int rc = zkv_ctx_set_lanes_per_proof(k, lanes); if (rc != ZKV_OK) return rc; }
     std::lock_guard<std::mutex> lk(c->mu);
     c->lanes = lanes;
+    return ZKV_OK;
+}
+// Diagnostics of the GT tables (zkv_gt.h; include/zkv_diag_gt.h).  info: {built, windows of signal 0, of signal 1, table bytes, build time in
+// microseconds, build attempted}.  read: the 96 words of one entry as stored (Montgomery form, R = 2^261, values below 2p; g0 g1 g2 h0 h1 h2,
+// (c0, c1) each) -- signal 0 / 1, window, digit magnitude d = 1 .. 2^19 --, or with signal < 0 the folded Miller constant.
+ZKV_EXPORT int zkv_diag_gt_info(zkv_ctx* c, uint64_t* out6) {
+    if (!c || !out6) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    out6[0] = c->gt.tab ? 1 : 0; out6[1] = c->gt.nw[0]; out6[2] = c->gt.nw[1]; out6[3] = c->gt_bytes;
+    out6[4] = (uint64_t)(c->gt_build_ms * 1000.0f); out6[5] = c->gt_tried ? 1 : 0;
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_diag_gt_read(zkv_ctx* c, int signal, uint32_t window, uint32_t d, uint32_t* out96) {
+    if (!c || !out96) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->gt.tab) return ZKV_ERR_INVALID_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return ZKV_ERR_HIP;
+    const uint32_t* src = c->gt.mconst;
+    if (signal >= 0) {
+        if (signal >= (int)GT_MAX_SIG || window >= c->gt.nw[signal] || d < 1 || d > GT_ROW_ENTRIES) return ZKV_ERR_INVALID_ARG;
+        src = c->gt.tab + gt_row_word((signal ? c->gt.nw[0] : 0u) + window) + gt_entry_offset(d) / 4;
+    }
+    HIP_TRY(hipMemcpy(out96, src, sizeof(uint32_t) * GT_ENTRY_WORDS, hipMemcpyDeviceToHost));
+    return ZKV_OK;
+}
+// product: what k_finalexp2's table walk makes of given scalars.  The n proofs get the Miller value 1 (k_gt_diag_seed), so the kernel's
+// program exponentiates 1 to 1, the walk multiplies the selected rows into ACC, and the program's COPY TMP <- ACC leaves M in the slot TMP
+// (slot 8 of ws.fe), which is read back.  The kernel and its launch are the ones the verify path uses.
+ZKV_EXPORT int zkv_diag_gt_product(zkv_ctx* c, size_t n, const uint32_t* scalars, uint32_t* out) {
+    if (!c || !n || !scalars || !out) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->gt.tab || n > c->ws.cap) return ZKV_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n; i++) for (uint32_t sig = 0; sig < GT_MAX_SIG; sig++) {        // below 2^(20 nw - 1): the top window takes the last carry
+        const uint32_t top = GT_WINDOW_BITS * c->gt.nw[sig] - 1u;
+        for (uint32_t b = top; b < 256; b++) if ((scalars[(i * GT_MAX_SIG + sig) * 8 + (b >> 5)] >> (b & 31u)) & 1u) return ZKV_ERR_INVALID_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZKV_ERR_HIP;
+    int rc = order_after_previous(c, c->stream);
+    if (rc != ZKV_OK) return rc;
+    constexpr size_t SW = 8 * GT_MAX_SIG;
+    std::vector<uint32_t> rows(SW * n), res((size_t)GT_ENTRY_WORDS * n);
+    for (size_t i = 0; i < n; i++) for (size_t k = 0; k < SW; k++) rows[k * n + i] = scalars[i * SW + k];
+    uint8_t* d_st = nullptr;
+    HIP_TRY(hipMalloc(&d_st, n));
+    const size_t cap = c->ws.cap;
+    bool ok = hipMemcpy2DAsync(c->ws.prep + 64 * cap, cap * 4, rows.data(), n * 4, n * 4, SW, hipMemcpyHostToDevice, c->stream) == hipSuccess;
+    if (ok) {
+        launch_gt_diag_seed(n, c->ws, c->stream);
+        launch_finalexp2(n, c->ws, d_st, c->stream, c->gt);
+        ok = hipGetLastError() == hipSuccess &&
+             hipMemcpy2DAsync(res.data(), n * 4, c->ws.fe + (size_t)(96 * 6) * cap, cap * 4, n * 4, GT_ENTRY_WORDS, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+             hipStreamSynchronize(c->stream) == hipSuccess;
+    }
+    (void)hipFree(d_st);
+    if (!ok) { (void)hipGetLastError(); return ZKV_ERR_HIP; }
+    for (size_t i = 0; i < n; i++) for (size_t k = 0; k < GT_ENTRY_WORDS; k++) out[i * GT_ENTRY_WORDS + k] = res[k * n + i];
     return ZKV_OK;
 }
 // Aggregate check on / off (zkv_agg.h).  seed32 = nullptr draws the 32 secret bytes from the operating system.

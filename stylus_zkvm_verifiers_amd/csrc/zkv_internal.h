@@ -8,6 +8,8 @@ namespace zkv {
 // Per-chunk workspace in HBM, struct-of-arrays: word k of proof i lives at base[k * cap + i], so the 64 lanes
 // of a wavefront read/write 256 contiguous bytes per word (coalesced).
 constexpr int WS_PREP_WORDS = 64 + 8 * MAX_VAR;   // ax ay cx cy (4x8) | bx.c0 bx.c1 by.c0 by.c1 (4x8) | per-proof scalars (MAX_VAR x 8)
+// The scalar rows (64 ..) are written by the PREP stage alone and must stay as written until the chunk's last kernel: with GT tables (zkv_gt.h)
+// k_finalexp2 cuts its window digits from rows 64 .. 79.
 constexpr int WS_NORM_WORDS = 48;   // axs ays lxs lys cxs cys
 constexpr int WS_F_WORDS = 96;      // Fp12 Miller value (slot F of the final exponentiation)
 constexpr int WS_FE_WORDS = 7 * 96; // cold Fp12 slots of the final exponentiation: E, Y1, Y3, Y4 and the window slots x^3, x^5, x^7
@@ -92,7 +94,9 @@ void launch_prep_risc0(const PrepArgs& a, const Risc0Consts& k, const Workspace&
 void launch_prep_sp1(const PrepArgs& a, const Workspace& ws, hipStream_t s);
 void launch_prep_groth16(const PrepArgs& a, const Workspace& ws, hipStream_t s);
 void launch_setup_msm16(const VkTables* d_tab, const Msm16& m, G1A* tab, uint32_t rows, hipStream_t s);
-void launch_msm(size_t n, const VkTables* d_tab, const Msm16& m16, const InstTab* inst_tab, const Workspace& ws, hipStream_t s);
+// skip_vk_x: no window walk -- every vk_x is reported absent (FL_L_INF), A' and C are normalised as always (chunks whose (vk_x, gamma) pair goes
+// through the GT tables)
+void launch_msm(size_t n, const VkTables* d_tab, const Msm16& m16, const InstTab* inst_tab, const Workspace& ws, hipStream_t s, bool skip_vk_x = false);
 void launch_msm_w(size_t n, const VkTables* d_tab, const InstTab* inst_tab, const Workspace& ws, hipStream_t s);
 // long keys (n_ic > MAX_IC or ZKV_LONG_KEY=1; LongKey in zkv_verify.h)
 void launch_setup_long(const uint32_t* d_ic, uint32_t n_sig, VkTables* d_tab, G1A* tab, uint32_t* win, hipStream_t s);
@@ -104,8 +108,18 @@ void launch_setup_instances(const VkRaw* d_raw, const InstConsts& k, const InstR
 void launch_vk_x(size_t n, const VkTables* d_tab, const Msm16& m16, const InstTab* inst_tab, const uint32_t* inst, const uint8_t* sig, uint8_t* out, hipStream_t s);
 // lane-pair variants (k_pair.hip): one proof per two lanes, two waves per SIMD
 void launch_g2chk2(size_t n, const Workspace& ws, uint8_t* status, hipStream_t s);
-void launch_miller2(size_t n, const VkTables* d_tab, const Workspace& ws, uint8_t* status, hipStream_t s);
-void launch_finalexp2(size_t n, const Workspace& ws, uint8_t* status, hipStream_t s);
+// mconst / gt: the chunk leaves the (vk_x, gamma) pair to the context's GT tables (zkv_gt.h; its vk_x stage ran with skip_vk_x) -- the
+// Miller loop multiplies the folded constant in, the final exponentiation walks the tables.  Defaults: the Miller path.
+constexpr GtTab GT_NONE = {nullptr, nullptr, {0, 0}};
+void launch_miller2(size_t n, const VkTables* d_tab, const Workspace& ws, uint8_t* status, hipStream_t s, const uint32_t* mconst = nullptr);
+void launch_finalexp2(size_t n, const Workspace& ws, uint8_t* status, hipStream_t s, const GtTab& gt = GT_NONE);
+// set-up of the tables (k_gt.hip): the window bases G_i^(2^(20 j)) and the folded constant (one launch, scratch: GT_SETUP_SCRATCH_WORDS
+// words), then level L = 1 .. 19 fills entries d = 2^L .. 2^(L+1) - 1 (L = 19: d = 2^19) of every row from entries d / 2
+constexpr size_t GT_SETUP_SCRATCH_WORDS = 3 * 12 * 96;
+void launch_gt_bases(const VkRaw* d_raw, const VkTables* d_tab, uint32_t* tab, uint32_t* mconst, uint32_t* scratch, uint32_t nw0, uint32_t nw1, hipStream_t s);
+void launch_gt_level(uint32_t* tab, uint32_t rows, uint32_t level, hipStream_t s);
+// test only (zkv_diag_gt_product): flags alive, Miller value 1 for n lane-pair proofs
+void launch_gt_diag_seed(size_t n, const Workspace& ws, hipStream_t s);
 // coefficient-parallel small-batch variants (k_wide.hip): one proof per 16 lanes
 void launch_miller_w(size_t n, const VkTables* d_tab, const Workspace& ws, hipStream_t s);
 void launch_finalexp_w(size_t n, const Workspace& ws, uint8_t* status, hipStream_t s);

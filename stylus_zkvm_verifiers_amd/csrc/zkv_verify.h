@@ -12,6 +12,7 @@
 #pragma once
 #include "zkv_tower_mem.h"
 #include "zkv_sha256.h"
+#include "zkv_gt.h"
 
 namespace zkv {
 
@@ -558,23 +559,76 @@ ZKV_HD SoaRW fe_slot(int s, uint32_t* fbase, uint32_t* ebase, size_t cap, uint32
     SoaRW r; r.p = s == 1 ? fbase : ebase + (size_t)(96 * (s - 2)) * cap; r.stride = cap; r.off = off;
     return r;
 }
-ZKV_HD bool final_exp_prog_p(uint32_t* fbase, uint32_t* ebase, size_t cap, uint32_t off, L9Ref acc) {
+// Fixed-base GT tables (zkv_gt.h): where this proof's signals and the context's tables are.  on == false (the default): none, the program
+// runs as generated.  Otherwise four entries per window of each signal follow the program's last multiplication:
+//     TMP <- T[|digit|] (1 for a digit of 0);   CONJ ACC;   ACC <- ACC * TMP;   CONJ ACC
+// with the conjugations only in the lanes whose digit is negative (ACC conj(T) = conj(conj(ACC) T) for unitary values).  The multiplication
+// and the conjugation are the bodies every other entry uses (each inlined once, wave-uniform operands as before: with the table row as the
+// multiplication's own operand -- a second stride and a per-lane conjugation flag -- the kernel needed 32 bytes of scratch); the entry is
+// fetched by the small copy in front, 384 contiguous bytes the two lanes of a pair read together.  A window in which no lane of the wavefront
+// has a digit skips all four.  The digit is cut from the proof's scalar words (sc: word 0 of signal 0 of proof 0, ws.prep + 64 cap).
+// rel: where the tables are, in words FROM ebase (computed on the host): the row hangs off the same base pointer as the slots.  (With the
+// tables' own pointer the copy's source was a choice between two kernel arguments, and the compiler's inliner crashed on it.)
+// ebase + rel is a difference of two device allocations carried as an integer: it relies on the flat address space of the device and is
+// formally outside C++ pointer arithmetic.  The crash was seen with AMD clang 22.0.0git (roc-7.2.0, HIP 7.2.26015), -O3 --offload-arch=gfx950;
+// to reproduce, give GtRef a `const uint32_t* tab` (the kernel argument gt.tab) and set T.p = tab + gt_row_word(row) in the op == 8 branch
+// below, then compile k_pair.hip.  Go back to the pointer when a later compiler takes that form.
+// The scalar words are those the PREP stage wrote (rows 64 .. 79 of ws.prep): no stage between PREP and k_finalexp2 may write them (k_msm
+// only reads them), and every window recomputes its digit from two of them (stateless recoding, gt_digit_of) instead of reading a stored one.
+struct GtRef { bool on; ptrdiff_t rel; const uint32_t* sc; uint32_t nw0, nw1; };
+// What the walk assumes of the generated program (gen_constants.py): it ends in COPY TMP <- ACC; ISONE TMP, and TMP is slot 8.
+constexpr uint32_t FE_PROG_TAIL_CHECK[ZKV_FE_PROG_LEN] = ZKV_FE_PROG;
+static_assert(FE_PROG_TAIL_CHECK[ZKV_FE_PROG_LEN - 2] == (0u | 8u << 8 | 0u << 16) && (FE_PROG_TAIL_CHECK[ZKV_FE_PROG_LEN - 1] & 0xffffu) == (7u | 8u << 8),
+              "final_exp_prog_p: the table walk goes in front of the program's last two entries, COPY TMP <- ACC; ISONE TMP, with TMP = slot 8");
+ZKV_HD bool zkv_wave_any(bool v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(v) != 0;
+#else
+    return v;
+#endif
+}
+ZKV_HD bool final_exp_prog_p(uint32_t* fbase, uint32_t* ebase, size_t cap, uint32_t off, L9Ref acc, const GtRef gt = GtRef{false, 0, nullptr, 0, 0}) {
     const uint32_t PROG[ZKV_FE_PROG_LEN] = ZKV_FE_PROG;
+    const uint32_t GT_PROG[4] = {8u, 1u, 3u | 8u << 24, 1u};         // GTLOAD; CONJ ACC; MUL ACC <- ACC * TMP; CONJ ACC
     bool one = false;
     const uint32_t slot = zkv_wave_slot_parity();
+    // the table walk goes in front of the program's last two entries (COPY TMP <- ACC; ISONE TMP)
+    const int n_extra = gt.on ? 4 * (int)(gt.nw0 + gt.nw1) : 0, cut = ZKV_FE_PROG_LEN - 2;
 #pragma unroll 1
-    for (int pc = 0; pc < ZKV_FE_PROG_LEN; pc++) {
-        const uint32_t e = PROG[pc];
+    for (int pc = 0; pc < ZKV_FE_PROG_LEN + n_extra; pc++) {
+        const int q = pc - cut;
+        const bool extra = q >= 0 && q < n_extra;
+        const uint32_t row = extra ? (uint32_t)q >> 2 : 0u;          // window `row - (signal ? nw0 : 0)` of signal 0 / 1
+        const uint32_t e = extra ? GT_PROG[q & 3] : PROG[q < 0 ? pc : pc - n_extra];
         const int op = (int)(e & 255u), d = (int)((e >> 8) & 255u), a = (int)((e >> 16) & 255u), b = (int)(e >> 24);
         if ((pc & 3) == 0) zkv_fair_share(slot);          // the two wavefronts of a SIMD take turns at priority (zkv_field.h)
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("" : "+v"(off));
 #endif
+        int32_t dg = 0;                                    // a table entry: this lane's digit (both lanes of a pair read the same words)
+        if (extra) {
+            const uint32_t sig = row >= gt.nw0 ? 1u : 0u, j = sig ? row - gt.nw0 : row, k = gt_digit_word(j);
+            const uint32_t i4 = off - 32u * zkv_parity() * (uint32_t)cap;
+            const uint32_t lo = *(const uint32_t*)((const char*)(gt.sc + (size_t)(8u * sig + k) * cap) + i4);
+            const uint32_t hi = k + 1 < 8 ? *(const uint32_t*)((const char*)(gt.sc + (size_t)(8u * sig + k + 1) * cap) + i4) : 0u;
+            dg = gt_digit_of(lo, hi, j);
+            if (!zkv_wave_any(dg != 0)) continue;
+        }
         if (op == 6) { ZKV_MARK("begin cyclo"); f12l9_cyclo_sqr(acc); ZKV_MARK("end cyclo"); }
         else if ((op == 3 || op == 4) && d == 0) { ZKV_MARK("begin accmul");  f12l9_mul(acc, fe_slot(b, fbase, ebase, cap, off), op == 4); ZKV_MARK("end accmul"); }
+        else if (op == 8) {
+            const SoaRW D = fe_slot(8, fbase, ebase, cap, off);
+            if (dg == 0) f12m_set_one(D);
+            else {
+                SoaRW T;
+                T.p = ebase + gt.rel + (ptrdiff_t)gt_row_word(row); T.stride = 1;
+                T.off = gt_entry_offset((uint32_t)(dg < 0 ? -dg : dg)) + 32u * zkv_parity();
+                f12m_copy(D, T);
+            }
+        }
         else if (op == 0 && d == 0) f12m_copy(acc, fe_slot(a, fbase, ebase, cap, off));
         else if (op == 0 && a == 0) f12m_copy(fe_slot(d, fbase, ebase, cap, off), acc);
-        else if (op == 1 && d == 0) f12m_conj(acc);
+        else if (op == 1 && d == 0) { if (!extra || dg < 0) f12m_conj(acc); }
         else {
             const SoaRW D = fe_slot(d, fbase, ebase, cap, off), A = fe_slot(a, fbase, ebase, cap, off);
             if (op == 3 || op == 4) { ZKV_MARK("begin genmul"); f12m_mul_body(D, A, fe_slot(b, fbase, ebase, cap, off), op == 4); ZKV_MARK("end genmul"); }
