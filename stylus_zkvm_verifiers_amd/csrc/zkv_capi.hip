@@ -20,6 +20,7 @@
 #include "../../include/zkv_groth16_set.h"
 #include "../../include/zkv_sp1_gateway.h"
 #include "../../include/zkv_sp1_gateway_wire.h"
+#include "../../include/zkv_sp1_gateway_keys.h"
 #include "../../include/zkv_plonk_keys.h"
 #include "../../include/zkv_plonk_set.h"
 #include "../../include/zkv_plonk_set_agg.h"
@@ -181,7 +182,12 @@ struct zkv_ctx {
     size_t mx_cap[28] = {0};
     // ZKV_VM_SP1_GATEWAY (zkv_sp1_gateway.h): the routes' contexts and selectors; which routes ran in the most recent call
     // (zkv_ctx_last_stage_ms) and its per-column proof counts (routes, not found, short, bad calldata)
+    // Keyed Groth16 routes (zkv_sp1_gateway_keys.h) are routes [gw_key0, gw_key0 + gw_nkeys): they have no context of their own
+    // (gw_route[r] = nullptr) and share gw_group, a Groth16 key set of their keys (n_ic = 3, SP1 sign convention).  gw_hash: 32 bytes per route.
     std::vector<zkv_ctx*> gw_route;
+    zkv_ctx* gw_group = nullptr;
+    size_t gw_key0 = 0, gw_nkeys = 0;
+    std::vector<uint8_t> gw_hash;
     std::vector<uint32_t> gw_sel;
     std::vector<uint8_t> gw_ran;
     uint64_t gw_counts[GW_COLS] = {0};
@@ -1472,6 +1478,8 @@ ZKV_EXPORT void zkv_ctx_destroy(zkv_ctx* c) {
     for (auto& k : c->kid) { if (k) zkv_ctx_destroy(k); k = nullptr; }
     for (auto* k : c->gw_route) zkv_ctx_destroy(k);
     c->gw_route.clear();
+    if (c->gw_group) zkv_ctx_destroy(c->gw_group);
+    c->gw_group = nullptr;
     ctx_free_device(c);
     delete c;
 }
@@ -1773,16 +1781,25 @@ ZKV_EXPORT int zkv_sp1_plonk_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_
 // Up to ZKV_SP1_GATEWAY_MAX_ROUTES SP1 verifiers behind one context; every proof goes to the route whose selector begins it.  The routes
 // are ordinary SP1 / SP1 PLONK contexts owned by the gateway: the device front end (k_gateway.hip) sorts a batch into their compact
 // records, each non-empty route runs its own stage pipeline on them (run_records), and the statuses go back to the caller's order.
-ZKV_EXPORT zkv_ctx* zkv_sp1_gateway_create(int groth16, size_t n_plonk, const uint8_t* const* plonk_vk, const size_t* plonk_vk_len,
-                                           const uint8_t* plonk_verifier_hash, int device) {
-    if ((groth16 != 0 && groth16 != 1) || n_plonk > ZKV_SP1_GATEWAY_MAX_ROUTES || groth16 + n_plonk == 0 ||
-        groth16 + n_plonk > ZKV_SP1_GATEWAY_MAX_ROUTES) return nullptr;
+ZKV_EXPORT zkv_ctx* zkv_sp1_gateway_create_keyed(int groth16, size_t n_keys, const uint8_t* const* vk_words, const uint8_t* verifier_hash,
+                                                 size_t n_plonk, const uint8_t* const* plonk_vk, const size_t* plonk_vk_len,
+                                                 const uint8_t* plonk_verifier_hash, int device) {
+    if ((groth16 != 0 && groth16 != 1) || n_plonk > ZKV_SP1_GATEWAY_MAX_ROUTES || n_keys > ZKV_SP1_GATEWAY_MAX_ROUTES ||
+        groth16 + n_keys + n_plonk == 0 || groth16 + n_keys + n_plonk > ZKV_SP1_GATEWAY_MAX_ROUTES) return nullptr;
     if (n_plonk && (!plonk_vk || !plonk_vk_len || !plonk_verifier_hash)) return nullptr;
+    if (n_keys && (!vk_words || !verifier_hash)) return nullptr;
     std::vector<uint32_t> sel;
-    if (groth16) sel.push_back(be32_of(host::SP1_VERIFIER_HASH));
+    std::vector<uint8_t> hash;
+    if (groth16) { sel.push_back(be32_of(host::SP1_VERIFIER_HASH)); hash.insert(hash.end(), host::SP1_VERIFIER_HASH, host::SP1_VERIFIER_HASH + 32); }
+    for (size_t k = 0; k < n_keys; k++) {
+        if (!vk_words[k]) return nullptr;
+        sel.push_back(be32_of(verifier_hash + 32 * k));
+        hash.insert(hash.end(), verifier_hash + 32 * k, verifier_hash + 32 * k + 32);
+    }
     for (size_t k = 0; k < n_plonk; k++) {
         if (!plonk_vk[k]) return nullptr;
         sel.push_back(be32_of(plonk_verifier_hash + 32 * k));
+        hash.insert(hash.end(), plonk_verifier_hash + 32 * k, plonk_verifier_hash + 32 * k + 32);
     }
     for (size_t k = 0; k < sel.size(); k++)
         for (size_t j = 0; j < k; j++) if (sel[j] == sel[k]) return nullptr;       // the gateway could not tell the two routes apart
@@ -1790,11 +1807,19 @@ ZKV_EXPORT zkv_ctx* zkv_sp1_gateway_create(int groth16, size_t n_plonk, const ui
     if (!c) return nullptr;
     c->vm = ZKV_VM_SP1_GATEWAY; c->device = device; c->initialized = true;
     memset(&c->consts, 0, sizeof c->consts);
-    c->gw_sel = sel;
+    c->gw_sel = sel; c->gw_hash = hash;
     if (groth16) {
         zkv_ctx* r = zkv_sp1_ctx_create(device);
         if (!r) { zkv_ctx_destroy(c); return nullptr; }
         c->gw_route.push_back(r);
+    }
+    if (n_keys) {                                                  // one key set for all of them: its points are judged on the device (vk_valid per key)
+        const std::vector<size_t> n_ic(n_keys, 3);
+        const std::vector<int> vm(n_keys, ZKV_VM_SP1);
+        c->gw_group = zkv_groth16_set_create(n_keys, vk_words, n_ic.data(), vm.data(), device);
+        if (!c->gw_group) { zkv_ctx_destroy(c); return nullptr; }
+        c->gw_key0 = c->gw_route.size(); c->gw_nkeys = n_keys;
+        c->gw_route.insert(c->gw_route.end(), n_keys, nullptr);
     }
     for (size_t k = 0; k < n_plonk; k++) {
         zkv_ctx* r = zkv_sp1_plonk_ctx_create(plonk_vk[k], plonk_vk_len[k], plonk_verifier_hash + 32 * k, device);
@@ -1804,12 +1829,24 @@ ZKV_EXPORT zkv_ctx* zkv_sp1_gateway_create(int groth16, size_t n_plonk, const ui
     c->gw_ran.assign(c->gw_route.size(), 0);
     return c;
 }
+ZKV_EXPORT zkv_ctx* zkv_sp1_gateway_create(int groth16, size_t n_plonk, const uint8_t* const* plonk_vk, const size_t* plonk_vk_len,
+                                           const uint8_t* plonk_verifier_hash, int device) {
+    return zkv_sp1_gateway_create_keyed(groth16, 0, nullptr, nullptr, n_plonk, plonk_vk, plonk_vk_len, plonk_verifier_hash, device);
+}
+// a route of the keyed group (no context of its own)
+static inline bool gw_keyed(const zkv_ctx* c, size_t r) { return r >= c->gw_key0 && r < c->gw_key0 + c->gw_nkeys; }
+ZKV_EXPORT int zkv_sp1_gateway_route_verifier_hash(const zkv_ctx* c, size_t r, uint8_t out[32]) {
+    if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
+    if (r >= c->gw_route.size() || !out) return ZKV_ERR_INVALID_ARG;
+    memcpy(out, c->gw_hash.data() + 32 * r, 32);
+    return ZKV_OK;
+}
 ZKV_EXPORT size_t zkv_sp1_gateway_route_count(const zkv_ctx* c) { return c && c->vm == ZKV_VM_SP1_GATEWAY ? c->gw_route.size() : 0; }
 ZKV_EXPORT int zkv_sp1_gateway_route(const zkv_ctx* c, size_t r, uint8_t selector[4], int* vm) {
     if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
     if (r >= c->gw_route.size()) return ZKV_ERR_INVALID_ARG;
     if (selector) be32_put(selector, c->gw_sel[r]);
-    if (vm) *vm = c->gw_route[r]->vm;
+    if (vm) *vm = gw_keyed(c, r) ? ZKV_VM_SP1 : c->gw_route[r]->vm;
     return ZKV_OK;
 }
 ZKV_EXPORT zkv_ctx* zkv_sp1_gateway_route_ctx(zkv_ctx* c, size_t r) {
@@ -1828,6 +1865,11 @@ ZKV_EXPORT int zkv_sp1_gateway_verify_proof(zkv_ctx* c, const uint8_t vkey[32], 
     if (!vkey || !status || (!pv && pv_len) || (!proof && proof_len)) return ZKV_ERR_INVALID_ARG;
     const int col = gateway_route_of(c, proof, proof_len);
     uint8_t rv[4] = {0, 0, 0, 0};
+    if (col < GW_MAX_ROUTES && gw_keyed(c, (size_t)col)) {       // the keyed group has no single-proof path: a batch of one
+        const uint64_t poff[2] = {0, proof_len}, voff[2] = {0, pv_len};
+        const uint8_t zero = 0;
+        return zkv_sp1_gateway_verify_batch(c, 1, vkey, pv ? pv : &zero, voff, proof, poff, status, recv);
+    }
     if (col < GW_MAX_ROUTES) {
         zkv_ctx* k = c->gw_route[col];
         const int rc = k->vm == ZKV_VM_SP1 ? zkv_sp1_verify_proof(k, vkey, pv, pv_len, proof, proof_len, status, rv)
@@ -1847,7 +1889,51 @@ ZKV_EXPORT int zkv_sp1_gateway_verify_proof(zkv_ctx* c, const uint8_t vkey[32], 
 
 enum { GW_CNT = 0, GW_TOT, GW_POS, GW_IDX, GW_RECS, GW_LEN, GW_A, GW_PVOFF, GW_PVLEN, GW_ST, GW_RV,
        GW_H_VK, GW_H_PV, GW_H_PVOFF, GW_H_PROOF, GW_H_POFF, GW_H_ST, GW_H_RV,
-       GWW_VK, GWW_PVAT, GWW_PVLEN, GWW_PAT, GWW_PLEN, GWW_BAD, GWW_ARENA, GWW_H_CD, GWW_H_OFF };      // calldata batches (run_gateway_wire)
+       GWW_VK, GWW_PVAT, GWW_PVLEN, GWW_PAT, GWW_PLEN, GWW_BAD, GWW_ARENA, GWW_H_CD, GWW_H_OFF,        // calldata batches (run_gateway_wire)
+       GW_SKEY };                                                                                     // keyed group: the key of every group slot
+// The keyed group of a gateway (zkv_sp1_gateway_keys.h): the M padded slots the demultiplexer has filled, from slot
+// G0 of the call and byte B0 of the compact records, verified in one pass for all keys -- k_gwset_prep with the slot's key, then the key
+// sets' stages chunk by chunk as run_gset runs them (no tail split, no aggregate check).  g->mu is held by the caller.
+static int groth16_ready(zkv_ctx* c, size_t n, size_t* chunk);
+static int run_gateway_group(zkv_ctx* gw, zkv_ctx* g, size_t M, int lanes, const GatewayArgs& a, size_t G0, uint64_t B0, const uint64_t* gstart,
+                             const uint8_t* d_pv, uint8_t* st, uint8_t* rv, hipStream_t s) {
+    if (!M) return ZKV_OK;
+    size_t cap = 0;
+    int rc = groth16_ready(g, M, &cap);
+    if (rc != ZKV_OK) return rc;
+    if ((rc = order_after_previous(g, s)) != ZKV_OK) return rc;
+    GwsetChunk pc;
+    memset(&pc, 0, sizeof pc);
+    pc.idx = a.idx + G0; pc.skey = (uint32_t*)gw->mx[GW_SKEY];
+    pc.recs = a.c_proofs + B0; pc.len = a.c_len + G0; pc.vkeys = a.c_a + 32 * G0; pc.pvoff = a.c_pvoff + G0; pc.pvlen = a.c_pvlen + G0; pc.pv = d_pv;
+    pc.n_keys = (uint32_t)gw->gw_nkeys;
+    for (size_t k = 0; k < gw->gw_nkeys; k++) pc.start[k] = (uint32_t)gstart[k];
+    pc.keys = g->d_gs_key; pc.sig = g->d_lsig; pc.sig_cap = g->lsig_cap;
+    pc.status = st + G0; pc.recv = (uint32_t*)(rv + 4 * G0);
+    for (size_t base = 0; base < M; base += cap) {
+        const size_t m = M - base < cap ? M - base : cap;
+        const bool timed = base + cap >= M;
+        pc.m = m; pc.slot0 = base;
+        GsetChunk ch;
+        memset(&ch, 0, sizeof ch);
+        ch.m = m; ch.slot0 = base; ch.idx = pc.idx; ch.skey = pc.skey;
+        ch.keys = g->d_gs_key; ch.rows = g->d_gs_rows; ch.win = g->d_gs_win;
+        ch.sig = g->d_lsig; ch.sig_cap = g->lsig_cap; ch.status = st + G0 + base;
+        if (timed) (void)hipEventRecord(g->ev[0], s);
+        launch_gwset_prep(pc, g->ws, s);
+        if (timed) (void)hipEventRecord(g->ev[1], s);
+        launch_gset_msm(ch, msm_lanes_long(g, m), g->ws, s);
+        if (timed) (void)hipEventRecord(g->ev[2], s);
+        if (lanes != 2) launch_g2chk2(m, g->ws, ch.status, s);       // (the lane-pair Miller loop is the subgroup test itself)
+        if (timed) (void)hipEventRecord(g->ev[3], s);
+        launch_gset_miller(lanes, m, pc.skey + base, g->d_gs_key, g->ws, ch.status, s);
+        if (timed) (void)hipEventRecord(g->ev[4], s);
+        launch_finalexp_lanes(lanes, m, g->ws, ch.status, s);
+        if (timed) (void)hipEventRecord(g->ev[5], s);
+        HIP_TRY(hipGetLastError());
+    }
+    return mark_done(g, s);
+}
 // Everything device-resident: ragged proofs (offsets bounded by proof_bytes on the device); public values ragged (d_pv_off) or at a
 // fixed stride.  Or, from the calldata decoder, `recs`: (start, length) records of proofs and public values from one base address, which
 // d_proofs and d_pv then both are, and bad-calldata marks.  Synchronises `s` once, after the count, to size the compact records and learn
@@ -1856,9 +1942,12 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
                        const uint8_t* d_pv, const uint64_t* d_pv_off, uint64_t pv_stride, uint8_t* d_status, uint8_t* d_recv, hipStream_t s,
                        const GwWireArgs* recs = nullptr) {
     int rc;
-    const size_t blocks = (n + 255) / 256, R = c->gw_route.size();
-    const size_t need[11] = {4 * GW_COLS * blocks, 4 * GW_COLS, 4 * n, 4 * n, 0, 4 * n, 32 * n, 8 * n, 4 * n, n, 4 * n};
+    const size_t blocks = (n + 255) / 256, R = c->gw_route.size(), K = c->gw_nkeys, key0 = c->gw_key0;
+    // slots: one per routed proof, and up to 31 pad slots behind every keyed route (its successor starts on a wavefront of the Miller mapping)
+    const size_t ns = n + 32 * K;
+    const size_t need[11] = {4 * GW_COLS * blocks, 4 * GW_COLS, 4 * n, 4 * ns, 0, 4 * ns, 32 * ns, 8 * ns, 4 * ns, ns, 4 * ns};
     for (int k = 0; k < 11; k++) if (k != GW_RECS && (rc = grow(&c->mx[k], &c->mx_cap[k], need[k])) != ZKV_OK) return rc;
+    if (K && (rc = grow(&c->mx[GW_SKEY], &c->mx_cap[GW_SKEY], 4 * ns)) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     GatewayArgs a;
     memset(&a, 0, sizeof a);
@@ -1867,20 +1956,41 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
     a.n_routes = (uint32_t)R;
     for (size_t r = 0; r < R; r++) {
         a.sel[r] = c->gw_sel[r];
-        a.rec[r] = c->gw_route[r]->vm == ZKV_VM_SP1_PLONK ? ZKV_PLONK_PROOF_BYTES : ZKV_SEAL_BYTES;
+        a.rec[r] = c->gw_route[r] && c->gw_route[r]->vm == ZKV_VM_SP1_PLONK ? ZKV_PLONK_PROOF_BYTES : ZKV_SEAL_BYTES;
     }
     a.cnt = (uint32_t*)c->mx[GW_CNT]; a.totals = (uint32_t*)c->mx[GW_TOT]; a.pos = (uint32_t*)c->mx[GW_POS]; a.idx = (uint32_t*)c->mx[GW_IDX];
     a.c_len = (uint32_t*)c->mx[GW_LEN]; a.c_a = c->mx[GW_A]; a.c_pvoff = (uint64_t*)c->mx[GW_PVOFF]; a.c_pvlen = (uint32_t*)c->mx[GW_PVLEN];
     a.status = d_status; a.recv = d_recv;
+    if (K) HIP_TRY(hipMemsetAsync(a.idx, 0xFF, 4 * ns, s));      // pad slots: GW_NONE
     launch_gateway_count(a, s);
     HIP_TRY(hipGetLastError());
     uint32_t tot[GW_COLS];
     HIP_TRY(hipMemcpyAsync(tot, c->mx[GW_TOT], sizeof tot, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    size_t routed = 0;
-    uint64_t bytes = 0;
-    for (size_t r = 0; r < R; r++) { a.start[r] = (uint32_t)routed; a.base[r] = bytes; routed += tot[r]; bytes += (uint64_t)tot[r] * a.rec[r]; }
-    if (routed + tot[GW_COL_NOT_FOUND] + tot[GW_COL_SHORT] + tot[GW_COL_BAD] != n) return ZKV_ERR_HIP;
+    // The layout.  A route with a context of its own takes one slot per proof; the keyed routes take the key sets' layout
+    // (zkv_gset_layout.h gset_choose: the mapping their proofs would take, stepped to a finer one while the padding exceeds 1.25 times).
+    size_t routed = 0, slots = 0, G0 = 0, M = 0;
+    uint64_t bytes = 0, B0 = 0, gstart[GW_MAX_ROUTES + 1] = {0};
+    int lanes = 0;
+    std::unique_lock<std::mutex> glk;
+    for (size_t r = 0; r < R; r++) {
+        routed += tot[r];
+        if (K && r == key0) {
+            glk = std::unique_lock<std::mutex>(c->gw_group->mu);
+            size_t placed = 0;
+            for (size_t k = 0; k < K; k++) placed += tot[key0 + k];
+            uint64_t gslots = 0;
+            lanes = gset_choose(tot + key0, (uint32_t)K, miller_lanes(c->gw_group, placed), c->gw_group->lanes != 0, gstart, &gslots);
+            G0 = slots; B0 = bytes; M = (size_t)gslots;
+        }
+        if (gw_keyed(c, r)) {
+            a.start[r] = (uint32_t)(G0 + gstart[r - key0]); a.base[r] = B0 + (uint64_t)ZKV_SEAL_BYTES * gstart[r - key0];
+            if (r + 1 == key0 + K) { slots = G0 + M; bytes = B0 + (uint64_t)ZKV_SEAL_BYTES * M; }
+            continue;
+        }
+        a.start[r] = (uint32_t)slots; a.base[r] = bytes; slots += tot[r]; bytes += (uint64_t)tot[r] * a.rec[r];
+    }
+    if (routed + tot[GW_COL_NOT_FOUND] + tot[GW_COL_SHORT] + tot[GW_COL_BAD] != n || slots > ns) return ZKV_ERR_HIP;
     if ((rc = grow(&c->mx[GW_RECS], &c->mx_cap[GW_RECS], (size_t)bytes + 8)) != ZKV_OK) return rc;
     a.c_proofs = c->mx[GW_RECS];
     for (size_t r = 0; r < R; r++) { c->gw_counts[r] = tot[r]; c->gw_ran[r] = tot[r] > 0; }
@@ -1890,12 +2000,22 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
     HIP_TRY(hipGetLastError());
     uint8_t *st = c->mx[GW_ST], *rv = c->mx[GW_RV];
     for (size_t r = 0; r < R; r++) {
+        if (gw_keyed(c, r)) continue;
         const size_t j = a.start[r];
         if ((rc = run_records(c->gw_route[r], tot[r], a.c_proofs + a.base[r], a.c_len + j, a.c_a + 32 * j, nullptr, nullptr, d_pv, a.c_pvoff + j,
                               a.c_pvlen + j, st + j, rv + 4 * j, s)) != ZKV_OK) return rc;
     }
+    if (K && (rc = run_gateway_group(c, c->gw_group, M, lanes, a, G0, B0, gstart, d_pv, st, rv, s)) != ZKV_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    launch_mixed_return(routed, a.idx, st, rv, d_status, d_recv, s);
+    // The statuses back to the caller's order, once per run of routes whose proofs lie back to back (a keyed route may end in pad slots;
+    // a gateway without keyed routes is one run).
+    size_t lo = 0, hi = 0;
+    for (size_t r = 0; r <= R; r++) {
+        if (r < R && !tot[r]) continue;
+        if (r < R && a.start[r] == hi) { hi += tot[r]; continue; }
+        launch_mixed_return(hi - lo, a.idx + lo, st + lo, rv + 4 * lo, d_status, d_recv, s);
+        if (r < R) { lo = a.start[r]; hi = lo + tot[r]; }
+    }
     HIP_TRY(hipGetLastError());
     return mark_done(c, s);
 }
@@ -3340,7 +3460,8 @@ ZKV_EXPORT int zkv_ctx_set_lanes_per_proof(zkv_ctx* c, int lanes) {
     if (c->vm == ZKV_VM_MIXED) {                         // the two verifiers behind the tag run the stages
         for (auto* k : c->kid) { const int rc = zkv_ctx_set_lanes_per_proof(k, lanes); if (rc != ZKV_OK) return rc; }
     }
-    for (auto* k : c->gw_route) { const int rc = zkv_ctx_set_lanes_per_proof(k, lanes); if (rc != ZKV_OK) return rc; }
+    for (auto* k : c->gw_route) { if (!k) continue; const int rc = zkv_ctx_set_lanes_per_proof(k, lanes); if (rc != ZKV_OK) return rc; }
+    if (c->gw_group) { const int rc = zkv_ctx_set_lanes_per_proof(c->gw_group, lanes); if (rc != ZKV_OK) return rc; }
     std::lock_guard<std::mutex> lk(c->mu);
     c->lanes = lanes;
     return ZKV_OK;
@@ -3422,6 +3543,7 @@ ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t
     if (c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_GATEWAY) {
         const size_t nk = c->vm == ZKV_VM_MIXED ? 2 : c->gw_route.size();
         for (size_t k = 0; k < nk; k++) {
+            if (c->vm == ZKV_VM_SP1_GATEWAY && !c->gw_route[k]) continue;      // a keyed route: its group keeps the per-proof path
             uint8_t sk[32];
             if (enable && seed32) { uint8_t buf[33]; memcpy(buf, seed, 32); buf[32] = (uint8_t)k; host::sha256_host(buf, 33, sk); }
             const int rc = zkv_ctx_set_aggregate_check(c->vm == ZKV_VM_MIXED ? c->kid[k] : c->gw_route[k], enable, enable && seed32 ? sk : nullptr);
@@ -3457,6 +3579,7 @@ ZKV_EXPORT int zkv_ctx_aggregate_counters(zkv_ctx* c, uint64_t out[2]) {
     if (is_sharded(c) || c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_GATEWAY) {
         const size_t nk = is_sharded(c) ? c->shards.size() : c->vm == ZKV_VM_MIXED ? 2 : c->gw_route.size();
         for (size_t k = 0; k < nk; k++) {
+            if (!is_sharded(c) && c->vm == ZKV_VM_SP1_GATEWAY && !c->gw_route[k]) continue;
             uint64_t o[2];
             const int rc = zkv_ctx_aggregate_counters(is_sharded(c) ? c->shards[k] : c->vm == ZKV_VM_MIXED ? c->kid[k] : c->gw_route[k], o);
             if (rc != ZKV_OK) return rc;
@@ -3516,7 +3639,8 @@ ZKV_EXPORT int zkv_ctx_reserve(zkv_ctx* c, size_t n) {
         return ctx_device_init(c);
     }
     if (c->vm == ZKV_VM_SP1_GATEWAY) {                   // any route may own the whole batch
-        for (auto* k : c->gw_route) { const int rc = zkv_ctx_reserve(k, n); if (rc != ZKV_OK) return rc; }
+        for (auto* k : c->gw_route) { if (!k) continue; const int rc = zkv_ctx_reserve(k, n); if (rc != ZKV_OK) return rc; }
+        if (c->gw_group) { const int rc = zkv_ctx_reserve(c->gw_group, n); if (rc != ZKV_OK) return rc; }
         std::lock_guard<std::mutex> lk(c->mu);
         return ctx_device_init(c);
     }
@@ -3537,7 +3661,8 @@ ZKV_EXPORT int zkv_ctx_synchronize(zkv_ctx* c) {
     }
     // a mixed context has work in flight as soon as ANY of its three contexts is set up (an all-SP1 batch never touches the RISC Zero child)
     bool any = c->dev_ready || (c->vm == ZKV_VM_MIXED && ((c->kid[0] && c->kid[0]->dev_ready) || (c->kid[1] && c->kid[1]->dev_ready)));
-    for (auto* k : c->gw_route) any = any || k->dev_ready;
+    for (auto* k : c->gw_route) any = any || (k && k->dev_ready);
+    any = any || (c->gw_group && c->gw_group->dev_ready);
     if (!any) return ZKV_OK;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -3562,10 +3687,12 @@ ZKV_EXPORT int zkv_ctx_last_stage_ms(zkv_ctx* c, float out_ms[5]) {
     if (c->vm == ZKV_VM_SP1_GATEWAY) {                   // routes run one after the other, as the mixed context's children
         bool ran = false;
         for (int i = 0; i < 5; i++) out_ms[i] = 0.0f;
+        bool group = false;                              // the keyed routes ran as one pass: their group counts once
         for (size_t k = 0; k < c->gw_route.size(); k++) {
-            if (!c->gw_ran[k]) continue;
+            if (!c->gw_ran[k] || (!c->gw_route[k] && group)) continue;
+            if (!c->gw_route[k]) group = true;
             float a[5];
-            const int rc = zkv_ctx_last_stage_ms(c->gw_route[k], a);
+            const int rc = zkv_ctx_last_stage_ms(c->gw_route[k] ? c->gw_route[k] : c->gw_group, a);
             if (rc != ZKV_OK) return rc;
             for (int i = 0; i < 5; i++) out_ms[i] += a[i];
             ran = true;

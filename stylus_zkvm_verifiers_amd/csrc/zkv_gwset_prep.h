@@ -1,0 +1,58 @@
+// SP1 gateway, Groth16 routes with caller-supplied keys (include/zkv_sp1_gateway_keys.h): the SP1 front end of one
+// slot of the keyed group -- sp1/verifier.rs:58-94 after the selector (the demultiplexer has matched it), with the slot's key.  The slot
+// layout of the group is zkv_gset_layout.h's.  __host__ __device__, so that tests/host_cpp/test_gwset_prep.cpp runs the kernel's own body
+// on the CPU (plain and under the sanitizers).
+#pragma once
+#include "zkv_verify.h"
+
+namespace zkv {
+
+// The 65 words of a compact 260-byte record: a row staged in LDS (words still hold big-endian bytes) or the record itself, byte by byte.
+struct GwsetRec {
+    const uint32_t* row;        // non-null: the staged row
+    const uint8_t* rec;         // otherwise: the record
+    ZKV_HD uint32_t word(int k) const { return row ? __builtin_bswap32(row[k]) : load_be32(rec + 4 * k); }
+    ZKV_HD void u256(uint32_t limbs[8], int word0) const {
+#pragma unroll 1
+        for (int j = 0; j < 8; j++) limbs[7 - j] = word(word0 + j);
+    }
+};
+
+// What the slot hands to the later stages.  sig: the two public signals as little-endian limbs (program vkey, masked SHA-256 of the
+// public values); a signal the checks did not reach stays zero.  o: the points, meaningful when flags has FL_ALIVE.
+struct GwsetSlot { uint8_t status; uint32_t flags; uint32_t sig[2][8]; PrepOut o; };
+
+// k_prep_sp1's checks in the order of the reference: strict length (verifier.rs:80-82), then verify_proof_with_key with the route's key
+// -- a key with an invalid point fails here, as the precompiles would reject it --, program_vkey < R (groth16.rs:32), the hash of the
+// public values & (2^253 - 1) (types.rs:34-38; below R, so it has no range check of its own to fail), the point encodings.
+// vkey: the 32 bytes of the program vkey, 4-byte aligned (the gateway's compact copy).
+ZKV_HD void gwset_prep_slot(uint32_t vk_valid, uint32_t len, const uint32_t* vkey, const uint8_t* pv, size_t pv_len, const GwsetRec& rec, GwsetSlot& r) {
+    r.flags = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) { r.sig[0][k] = 0; r.sig[1][k] = 0; }
+    if (len != 260) { r.status = ST_INVALID_PROOF_DATA; return; }
+    r.status = ST_VERIFICATION_FAILED;
+    if (!vk_valid) return;
+#pragma unroll
+    for (int j = 0; j < 8; j++) r.sig[0][7 - j] = __builtin_bswap32(vkey[j]);       // U256::from_be_bytes(program_vkey)
+    if (!raw_lt_r(r.sig[0])) return;
+    uint32_t h[8];
+    sha256_bytes(pv, pv_len, h);
+    h[0] &= 0x1fffffffu;
+#pragma unroll
+    for (int j = 0; j < 8; j++) r.sig[1][7 - j] = h[j];
+    uint32_t w[8][8];
+#pragma unroll 1
+    for (int j = 0; j < 8; j++) rec.u256(w[j], 1 + 8 * j);
+    if (prep_points(w, false, r.o)) r.flags = r.o.flags;
+}
+
+// The key (route of the group) of group slot j: the last key whose group starts at or before it -- an empty key starts where the next
+// one does, and a pad slot belongs to the key whose group it pads.  start: n_keys first slots (zkv_gset_layout.h gset_layout).
+ZKV_HD uint32_t gwset_key_of_slot(const uint32_t* start, uint32_t n_keys, uint32_t j) {
+    uint32_t k = 0;
+    for (uint32_t q = 1; q < n_keys; q++) if (start[q] <= j) k = q;
+    return k;
+}
+
+}  // namespace zkv

@@ -205,6 +205,21 @@ void launch_gset_return(size_t n, const uint32_t* pos, const uint8_t* status, ui
 // Miller loops with the key of each wavefront's first slot (k_gset_pair.hip): lanes 2 / 16 / 64 / 128 as zkv_ctx_set_lanes_per_proof
 void launch_gset_miller(int lanes, size_t m, const uint32_t* skey, const GsetKey* keys, const Workspace& ws, uint8_t* status, hipStream_t s);
 int read_gset_wait_faults(unsigned long long* out);     // k_gset_miller_w64d's counterpart of read_wait_faults
+// SP1 gateway, keyed Groth16 routes (k_gateway_keys.hip; include/zkv_sp1_gateway_keys.h): PREP of slots [slot0, slot0 + m) of the keyed
+// group, the gateway's routes with caller keys as one key set.  Every per-slot table is the group's (index 0 = its first slot): the
+// demultiplexer's compact outputs -- caller index (GW_NONE: pad slot), 260-byte records, true lengths, program vkeys, (offset, length)
+// of the public values in `pv` -- and the outputs: the slot's key (skey, read by k_gset_msm and k_gset_miller), the signals staged as
+// GsetChunk::sig, the status and the (zero) received selector.  start[k]: first group slot of key k (zkv_gset_layout.h).
+struct GwsetChunk {
+    size_t m, slot0;
+    const uint32_t* idx; uint32_t* skey;
+    const uint8_t* recs; const uint32_t* len; const uint8_t* vkeys; const uint64_t* pvoff; const uint32_t* pvlen; const uint8_t* pv;
+    uint32_t n_keys; uint32_t start[GW_MAX_ROUTES];
+    const GsetKey* keys;
+    uint32_t* sig; size_t sig_cap;
+    uint8_t* status; uint32_t* recv;
+};
+void launch_gwset_prep(const GwsetChunk& c, const Workspace& ws, hipStream_t s);
 // Aggregate check on a set (k_gset_agg.hip, k_gset_agg_pair.hip; the layout: zkv_gset_layout.h gset_agg_choose).  psl: pseudo-proof slot per sub-batch.
 struct AggTables;
 void launch_gset_setup_agg(uint32_t n_keys, const VkRaw* d_raw, const VkTables* d_tabs, AggTables* d_agg, hipStream_t s);

@@ -9,6 +9,7 @@
 
 #include "../../include/zkv_sp1_gateway.h"
 #include "../../include/zkv_sp1_gateway_wire.h"
+#include "../../include/zkv_sp1_gateway_keys.h"
 
 namespace zkv {
 
@@ -17,8 +18,29 @@ struct Sp1PlonkRoute {
     std::vector<uint8_t> verifier_hash;   // 32 bytes; its first four are the route's selector
 };
 
+struct Sp1Groth16Route {
+    std::vector<uint8_t> vk_words;        // ZKV_SP1_GROTH16_KEY_BYTES: zkv_groth16_ctx_create's layout with n_ic = 3, SP1's sign convention
+    std::vector<uint8_t> verifier_hash;   // 32 bytes; its first four are the route's selector
+};
+
 class Sp1Gateway {
 public:
+    // Route order: the built-in Groth16 route, the keyed Groth16 routes, the PLONK routes (include/zkv_sp1_gateway_keys.h)
+    Sp1Gateway(bool groth16, const std::vector<Sp1Groth16Route>& groth16_keys, const std::vector<Sp1PlonkRoute>& plonk, int device = 0) {
+        std::vector<const uint8_t*> key, vk; std::vector<size_t> len; std::vector<uint8_t> key_hashes, hashes;
+        for (const auto& r : groth16_keys) {
+            if (r.vk_words.size() != ZKV_SP1_GROTH16_KEY_BYTES) throw std::invalid_argument("Sp1Gateway: a keyed Groth16 route takes a key with n_ic = 3");
+            if (r.verifier_hash.size() != 32) throw std::invalid_argument("Sp1Gateway: verifier_hash must be 32 bytes");
+            key.push_back(r.vk_words.data()); key_hashes.insert(key_hashes.end(), r.verifier_hash.begin(), r.verifier_hash.end());
+        }
+        for (const auto& r : plonk) {
+            if (r.verifier_hash.size() != 32) throw std::invalid_argument("Sp1Gateway: verifier_hash must be 32 bytes");
+            vk.push_back(r.vk.data()); len.push_back(r.vk.size()); hashes.insert(hashes.end(), r.verifier_hash.begin(), r.verifier_hash.end());
+        }
+        ctx_ = zkv_sp1_gateway_create_keyed(groth16 ? 1 : 0, groth16_keys.size(), key.data(), key_hashes.data(), plonk.size(), vk.data(), len.data(),
+                                            hashes.data(), device);
+        if (!ctx_) throw std::invalid_argument("zkv_sp1_gateway_create_keyed rejected the routes");
+    }
     Sp1Gateway(bool groth16, const std::vector<Sp1PlonkRoute>& plonk, int device = 0) {
         std::vector<const uint8_t*> vk; std::vector<size_t> len; std::vector<uint8_t> hashes;
         for (const auto& r : plonk) {
@@ -34,6 +56,11 @@ public:
     ~Sp1Gateway() { if (ctx_) zkv_ctx_destroy(ctx_); }
 
     size_t route_count() const { return zkv_sp1_gateway_route_count(ctx_); }
+    std::vector<uint8_t> route_verifier_hash(size_t r) const {
+        std::vector<uint8_t> out(32);
+        if (zkv_sp1_gateway_route_verifier_hash(ctx_, r, out.data()) != ZKV_OK) throw std::invalid_argument("Sp1Gateway::route_verifier_hash: no such route");
+        return out;
+    }
 
     // status[i] / recv[4 i .. 4 i + 4) of proof i (ragged host buffers, as zkv_sp1_verify_batch)
     void verify_batch(const std::vector<uint8_t>& vkeys, const std::vector<uint8_t>& pv_blob, const std::vector<uint64_t>& pv_off,

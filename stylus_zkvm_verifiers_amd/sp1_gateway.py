@@ -55,11 +55,14 @@ def lib():
 
 class Sp1Gateway:
     """groth16: include the built-in SP1 v5.0.0 Groth16 verifier as route 0; plonk: list of (vk_bytes, verifier_hash) in
-    Sp1PlonkVerifier's layout, one route each, in order.  At most MAX_ROUTES routes, selectors pairwise distinct."""
+    Sp1PlonkVerifier's layout, one route each, in order; groth16_keys: list of (vk_words, verifier_hash), Groth16 keys of other SP1
+    releases in Groth16Verifier's layout with n_ic = 3 and SP1's sign convention (include/zkv_sp1_gateway_keys.h), one route each, in
+    order, between the built-in route and the PLONK routes.  At most MAX_ROUTES routes, selectors pairwise distinct."""
 
-    def __init__(self, groth16=True, plonk=(), device=0):
+    def __init__(self, groth16=True, plonk=(), device=0, groth16_keys=()):
         plonk = [(bytes(vk), bytes(h)) for vk, h in plonk]
-        if not 1 <= int(bool(groth16)) + len(plonk) <= MAX_ROUTES:
+        groth16_keys = [(bytes(vk), bytes(h)) for vk, h in groth16_keys]
+        if not 1 <= int(bool(groth16)) + len(groth16_keys) + len(plonk) <= MAX_ROUTES:
             raise ValueError('a gateway holds 1 .. %d routes' % MAX_ROUTES)
         if any(len(h) != 32 for _, h in plonk):
             raise ValueError('verifier_hash must be 32 bytes')
@@ -69,10 +72,14 @@ class Sp1Gateway:
         vks = (C.c_char_p * max(k, 1))(*self._vk)
         lens = (C.c_size_t * max(k, 1))(*[len(v) for v in self._vk])
         hashes = b''.join(h for _, h in plonk) + b'\0'
-        self._h = self._L.zkv_sp1_gateway_create(1 if groth16 else 0, k, vks, lens, hashes, device)
+        if groth16_keys:
+            from . import sp1_gateway_keys
+            self._h = sp1_gateway_keys.create(groth16, groth16_keys, plonk, device)
+        else:
+            self._h = self._L.zkv_sp1_gateway_create(1 if groth16 else 0, k, vks, lens, hashes, device)
         if not self._h:
             raise ValueError('zkv_sp1_gateway_create rejected the routes (bad PLONK key, or two routes with one selector)')
-        self._hashes = ([self.groth16_verifier_hash()] if groth16 else []) + [h for _, h in plonk]
+        self._hashes = ([self.groth16_verifier_hash()] if groth16 else []) + [h for _, h in groth16_keys] + [h for _, h in plonk]
 
     def close(self):
         if getattr(self, '_h', None):

@@ -1,0 +1,300 @@
+"""SP1 gateway, Groth16 routes with caller-supplied keys (include/zkv_sp1_gateway_keys.h) without a device: the new
+header against the library's exports, the creation rules, the per-slot front end of the keyed group compiled for the host (plain and
+under the sanitizers) against tests/gateway_keys_model.py, and the slot layout.  Parity unpinned except for a route that holds the
+reference's own key and hash."""
+import ctypes as C
+import hashlib
+import json
+import os
+import random
+import re
+import subprocess
+
+import pytest
+
+import gateway_keys_model as gk
+import spec_model as m
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+SRC = os.path.join(HERE, 'host_cpp', 'test_gwset_prep.cpp')
+H = bytes.fromhex
+NEW = ['zkv_sp1_gateway_create_keyed', 'zkv_sp1_gateway_route_verifier_hash']
+GATEWAY = ['zkv_sp1_gateway_create', 'zkv_sp1_gateway_route_count', 'zkv_sp1_gateway_route', 'zkv_sp1_gateway_route_ctx',
+           'zkv_sp1_gateway_verify_proof', 'zkv_sp1_gateway_verify_batch', 'zkv_sp1_gateway_verify_batch_dev',
+           'zkv_sp1_gateway_last_route_counts', 'zkv_sp1_gateway_status_abi_encode']
+WRONG_CTX, INVALID_ARG = -5, -1
+SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all']
+
+
+def _names(path):
+    return set(re.findall(r'\b(zkv_[a-z0-9_]+)\s*\(', re.sub(r'/\*.*?\*/', '', open(path).read(), flags=re.S)))
+
+
+def _hash(prefix):
+    return bytes(prefix) + hashlib.sha256(bytes(prefix)).digest()[:28]
+
+
+@pytest.fixture(scope='module')
+def L():
+    from stylus_zkvm_verifiers_amd import sp1_gateway_keys
+    return sp1_gateway_keys.lib()
+
+
+@pytest.fixture(scope='module')
+def plonk():
+    d = json.load(open(os.path.join(HERE, 'golden', 'plonk_cases.json')))
+    return H(d['vk']), H(d['verifier_hash'])
+
+
+@pytest.fixture(scope='module')
+def key():
+    return gk.Key(0x12D0)
+
+
+def _create(L, groth16, keyed, plonk):
+    k, p = len(keyed), len(plonk)
+    kw = (C.c_char_p * max(k, 1))(*[w for w, _ in keyed])
+    vks = (C.c_char_p * max(p, 1))(*[vk for vk, _ in plonk])
+    lens = (C.c_size_t * max(p, 1))(*[len(vk) for vk, _ in plonk])
+    return L.zkv_sp1_gateway_create_keyed(groth16, k, kw, b''.join(h for _, h in keyed) + b'\0', p, vks, lens, b''.join(h for _, h in plonk) + b'\0', 0)
+
+
+# ---------------------------------------------------------------- symbol sets
+def test_header_declares_exactly_the_new_symbols_and_the_library_exports_them(L):
+    hdr = os.path.join(ROOT, 'include', 'zkv_sp1_gateway_keys.h')
+    assert _names(hdr) == set(NEW)
+    text = open(hdr).read()
+    assert '#include "zkv_sp1_gateway.h"' in text and 'PARITY UNPINNED' in text and '#define ZKV_SP1_GROTH16_KEY_BYTES 640' in text
+    assert 'share one internal context' in text                     # why zkv_sp1_gateway_route_ctx answers NULL for a keyed route
+    from stylus_zkvm_verifiers_amd import _lib, sp1_gateway, sp1_gateway_keys
+    assert set(sp1_gateway_keys.SYMBOLS) == set(NEW)
+    assert not set(NEW) & set(_lib.SYMBOLS) and not set(NEW) & set(sp1_gateway.SYMBOLS)
+    for name in NEW:
+        assert hasattr(L, name), name
+    # the pinned sets of the existing headers
+    assert set(sp1_gateway.SYMBOLS) == set(GATEWAY)
+    assert _names(os.path.join(ROOT, 'include', 'zkv_sp1_gateway.h')) == set(GATEWAY)
+    main = _names(os.path.join(ROOT, 'include', 'zkv.h'))
+    assert len(main) == 82 and not main & set(NEW)
+
+
+def test_cpp_mirror_with_the_keyed_constructor_compiles(tmp_path):
+    src = tmp_path / 'mirror.cpp'
+    src.write_text('#include "%s"\n'
+                   'int main() { std::vector<zkv::Sp1Groth16Route> k; std::vector<zkv::Sp1PlonkRoute> p;\n'
+                   '  try { zkv::Sp1Gateway a(true, p); zkv::Sp1Gateway b(false, k, p); return (int)b.route_verifier_hash(0).size(); }\n'
+                   '  catch (const std::exception&) { return 0; } }\n' % os.path.join(ROOT, 'stylus_zkvm_verifiers_amd', 'host', 'zkv_sp1_gateway.hpp'))
+    subprocess.check_call(['g++', '-std=c++17', '-fsyntax-only', '-Wall', str(src)])
+
+
+# ---------------------------------------------------------------- creation rules
+def test_create_keyed_refuses_bad_route_sets(L, plonk, key):
+    vk, vh = plonk
+    from stylus_zkvm_verifiers_amd import Sp1Gateway
+    sp1_sel = Sp1Gateway.groth16_verifier_hash()[:4]
+    kw = key.words
+    assert len(kw) == 640
+    assert not _create(L, 0, [], [])                                                                   # no route
+    assert not _create(L, 1, [(kw, _hash(bytes([1, 2, 3, k]))) for k in range(8)], [])                 # 9 routes: 1 + 8 + 0
+    assert not _create(L, 0, [(kw, _hash(bytes([1, 2, 3, k]))) for k in range(9)], [])                 # 0 + 9 + 0
+    assert not _create(L, 1, [(kw, _hash(bytes([1, 2, 3, k]))) for k in range(4)], [(vk, _hash(bytes([9, 2, 3, k]))) for k in range(4)])   # 1 + 4 + 4
+    assert not _create(L, 2, [(kw, _hash(b'\x01\x02\x03\x04'))], [])                                   # groth16 must be 0 / 1
+    assert not _create(L, 1, [(kw, _hash(sp1_sel))], [])                                               # keyed against built-in
+    assert not _create(L, 0, [(kw, _hash(b'\x01\x02\x03\x04')), (kw, _hash(b'\x01\x02\x03\x04'))], [])  # keyed against keyed
+    assert not _create(L, 0, [(kw, vh[:4] + bytes(28))], [(vk, vh)])                                   # keyed against PLONK
+    h = _create(L, 1, [(kw, _hash(b'\x01\x02\x03\x04')), (kw, _hash(b'\x01\x02\x03\x05'))], [(vk, vh)])   # equal keys, distinct selectors: fine
+    assert h and L.zkv_sp1_gateway_route_count(h) == 4
+    L.zkv_ctx_destroy(h)
+    # NULL pointers
+    one = (C.c_char_p * 1)(kw); hh = _hash(b'\x01\x02\x03\x04')
+    assert not L.zkv_sp1_gateway_create_keyed(0, 1, None, hh, 0, None, None, None, 0)
+    assert not L.zkv_sp1_gateway_create_keyed(0, 1, one, None, 0, None, None, None, 0)
+    assert not L.zkv_sp1_gateway_create_keyed(0, 2, (C.c_char_p * 2)(kw, None), hh + _hash(b'\x09\x09\x09\x09'), 0, None, None, None, 0)
+    assert not L.zkv_sp1_gateway_create_keyed(0, 1, one, hh, 1, None, (C.c_size_t * 1)(len(vk)), vh, 0)
+    assert not L.zkv_sp1_gateway_create_keyed(0, 1, one, hh, 1, (C.c_char_p * 1)(vk), None, vh, 0)
+    assert not L.zkv_sp1_gateway_create_keyed(0, 1, one, hh, 1, (C.c_char_p * 1)(vk), (C.c_size_t * 1)(len(vk)), None, 0)
+    assert not L.zkv_sp1_gateway_create_keyed(0, 1, one, hh, 1, (C.c_char_p * 1)(vk[:-1]), (C.c_size_t * 1)(len(vk) - 1), vh, 0)    # a PLONK key the PLONK route refuses
+    # the largest gateways
+    for groth16, k, p in ((0, 8, 0), (1, 7, 0), (1, 3, 4), (0, 1, 7)):
+        h = _create(L, groth16, [(kw, _hash(bytes([7, 7, 7, j]))) for j in range(k)], [(vk, _hash(bytes([8, 8, 8, j]))) for j in range(p)])
+        assert h and L.zkv_sp1_gateway_route_count(h) == 8
+        L.zkv_ctx_destroy(h)
+    with pytest.raises(ValueError):
+        Sp1Gateway(False, [], groth16_keys=[(kw[:-1], hh)])
+    with pytest.raises(ValueError):
+        Sp1Gateway(False, [], groth16_keys=[(kw, hh[:31])])
+    with pytest.raises(ValueError):
+        Sp1Gateway(True, [], groth16_keys=[(kw, _hash(sp1_sel))])
+    with pytest.raises(ValueError):
+        Sp1Gateway(True, [(vk, vh)] * 4, groth16_keys=[(kw, hh)] * 4)
+
+
+def test_route_order_getters_and_context_wide_calls_without_a_device(L, plonk, key):
+    vk, vh = plonk
+    from stylus_zkvm_verifiers_amd import Sp1Gateway, _lib
+    raw = _lib.lib()
+    h1, h2 = _hash(b'\x11\x22\x33\x44'), _hash(b'\x11\x22\x33\x45')
+    bad = gk.off_curve_ic(key.words)                                 # an invalid key is accepted: its own route fails its proofs
+    gw = Sp1Gateway(True, [(vk, vh)], groth16_keys=[(key.words, h1), (bad, h2)])
+    sp1_hash = Sp1Gateway.groth16_verifier_hash()
+    assert gw.routes() == [(sp1_hash[:4], 1, sp1_hash), (h1[:4], 1, h1), (h2[:4], 1, h2), (vh[:4], 6, vh)]
+    assert raw.zkv_ctx_vm(gw._h) == 8
+    o = C.create_string_buffer(32)
+    for r, want in enumerate((sp1_hash, h1, h2, vh)):
+        assert L.zkv_sp1_gateway_route_verifier_hash(gw._h, r, o) == 0 and o.raw == want
+    assert L.zkv_sp1_gateway_route_verifier_hash(gw._h, 4, o) == INVALID_ARG
+    assert L.zkv_sp1_gateway_route_verifier_hash(gw._h, 0, None) == INVALID_ARG
+    assert L.zkv_sp1_gateway_route_verifier_hash(None, 0, o) == WRONG_CTX
+    assert raw.zkv_ctx_vm(L.zkv_sp1_gateway_route_ctx(gw._h, 0)) == 1 and raw.zkv_ctx_vm(L.zkv_sp1_gateway_route_ctx(gw._h, 3)) == 6
+    assert not L.zkv_sp1_gateway_route_ctx(gw._h, 1) and not L.zkv_sp1_gateway_route_ctx(gw._h, 2)     # keyed: one shared internal context
+    assert raw.zkv_ctx_set_lanes_per_proof(gw._h, 16) == 0 and raw.zkv_ctx_set_lanes_per_proof(gw._h, 3) == INVALID_ARG
+    assert raw.zkv_ctx_set_lanes_per_proof(gw._h, 0) == 0
+    assert raw.zkv_ctx_set_aggregate_check(gw._h, 64, bytes(32)) == 0
+    assert raw.zkv_ctx_set_aggregate_check(gw._h, 1, None) == 0
+    assert raw.zkv_ctx_set_aggregate_check(gw._h, 0, None) == 0
+    assert gw.aggregate_counters() == (0, 0)
+    assert raw.zkv_ctx_synchronize(gw._h) == 0
+    assert gw.status_abi_encode(4) == H('e3e94326') and gw.status_abi_encode(1) == H('439cc0cd')
+    # proofs that reach no verifier are answered on the host, keyed routes or not
+    from stylus_zkvm_verifiers_amd import VerifierError
+    with pytest.raises(VerifierError) as ei:
+        gw.verify_proof(bytes(32), b'', b'\x11\x22\x33')
+    assert ei.value.status == 4 and gw.last_route_counts() == [0, 0, 0, 0, 0, 1]
+    with pytest.raises(VerifierError) as ei:
+        gw.verify_proof(bytes(32), b'', b'\x11\x22\x33\x46' + bytes(256))
+    assert ei.value.status == 8 and gw.last_route_counts() == [0, 0, 0, 0, 1, 0]
+    gw.close()
+    only = Sp1Gateway(False, groth16_keys=[(key.words, h1)])         # keyed routes alone
+    assert only.routes() == [(h1[:4], 1, h1)]
+    only.close()
+
+
+def test_no_keys_is_the_old_constructor(L, plonk):
+    vk, vh = plonk
+    from stylus_zkvm_verifiers_amd import Sp1Gateway
+    vh2 = _hash(b'\x5e\xc0\x4d\x00')
+    for groth16, pl in ((1, [(vk, vh)]), (0, [(vk, vh), (vk, vh2)]), (1, [])):
+        a = _create(L, groth16, [], pl)
+        vks = (C.c_char_p * max(len(pl), 1))(*[v for v, _ in pl]); lens = (C.c_size_t * max(len(pl), 1))(*[len(v) for v, _ in pl])
+        b = L.zkv_sp1_gateway_create(groth16, len(pl), vks, lens, b''.join(h for _, h in pl) + b'\0', 0)
+        assert a and b and L.zkv_sp1_gateway_route_count(a) == L.zkv_sp1_gateway_route_count(b) == groth16 + len(pl)
+        for r in range(groth16 + len(pl)):
+            got = []
+            for h in (a, b):
+                sel = C.create_string_buffer(4); vm = C.c_int(-1); o = C.create_string_buffer(32)
+                assert L.zkv_sp1_gateway_route(h, r, sel, C.byref(vm)) == 0 and L.zkv_sp1_gateway_route_verifier_hash(h, r, o) == 0
+                assert L.zkv_sp1_gateway_route_ctx(h, r)
+                got.append((sel.raw, vm.value, o.raw))
+            assert got[0] == got[1]
+        # with NULL key arguments as well
+        c = L.zkv_sp1_gateway_create_keyed(groth16, 0, None, None, len(pl), vks, lens, b''.join(h for _, h in pl) + b'\0', 0)
+        assert c and L.zkv_sp1_gateway_route_count(c) == groth16 + len(pl)
+        for h in (a, b, c):
+            L.zkv_ctx_destroy(h)
+    assert not _create(L, 0, [], []) and not L.zkv_sp1_gateway_create(0, 0, None, None, None, 0)
+    gw = Sp1Gateway(True, [(vk, vh)], groth16_keys=())
+    assert [r[1] for r in gw.routes()] == [1, 6]
+    gw.close()
+
+
+# ---------------------------------------------------------------- the per-slot front end, compiled for the host
+def _program(tmp_path, flags, name):
+    exe = str(tmp_path / name)
+    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-Wno-unknown-pragmas'] + flags + ['-o', exe, SRC])
+    return exe
+
+
+def _run(exe, mode, lines):
+    out = subprocess.run([exe, mode], input=''.join(ln + '\n' for ln in lines).encode(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert out.returncode == 0, (out.returncode, out.stderr.decode()[-2000:])
+    assert not out.stderr, out.stderr.decode()[-2000:]
+    got = out.stdout.decode().splitlines()
+    assert len(got) == len(lines)
+    return got
+
+
+def _prep_cases(key):
+    """(vk_valid, true length, program vkey, public values, 260-byte compact record)."""
+    rng = random.Random(0x12D1)
+    pv96 = bytes(rng.randrange(256) for _ in range(96))
+    vkey = int(rng.randrange(m.R)).to_bytes(32, 'big')
+    good = key.prove(vkey, pv96)
+    w = [int.from_bytes(good[4 + 32 * i:36 + 32 * i], 'big') for i in range(8)]
+
+    def rec(words):
+        return key.selector + b''.join(m.be32(x) for x in words)
+    cases = []
+    for ln in (4, 259, 260, 261):                                   # the gatherer copies min(len, 260) bytes and pads with zeros
+        cases.append((1, ln, vkey, pv96, good[:min(ln, 260)].ljust(260, b'\0')))
+    for v in (0, m.R - 1, m.R, (1 << 256) - 1):
+        cases.append((1, 260, m.be32(v), pv96, good))
+    for n in (0, 55, 56, 63, 64, 119, 120):                         # SHA-256 padding edges: one and two tail blocks, one and two full ones
+        cases.append((1, 260, vkey, bytes(rng.randrange(256) for _ in range(n)), good))
+    cases.append((1, 260, vkey, pv96, rec([0, 0] + w[2:])))                      # A = (0, 0)
+    cases.append((1, 260, vkey, pv96, rec(w[:6] + [0, 0])))                      # C = (0, 0)
+    cases.append((1, 260, vkey, pv96, rec(w[:2] + [0, 0, 0, 0] + w[6:])))        # B = (0, 0)
+    for k in range(8):
+        cases.append((1, 260, vkey, pv96, rec(w[:k] + [w[k] + m.P] + w[k + 1:])))    # a coordinate >= Q (w + Q < 2^256)
+    cases.append((1, 260, vkey, pv96, rec(w[:k] + [m.P] + w[k + 1:])))
+    cases.append((1, 260, vkey, pv96, rec([w[0], (w[1] + 1) % m.P] + w[2:])))    # A off the curve
+    cases.append((1, 260, vkey, pv96, rec(w[:6] + [w[6], (w[7] + 1) % m.P])))    # C off the curve
+    cases.append((1, 260, vkey, pv96, rec(w[:2] + [w[2], (w[3] + 1) % m.P] + w[4:])))    # B off the twist
+    cases.append((0, 260, vkey, pv96, good))                                     # a key with an invalid point
+    cases.append((0, 261, vkey, pv96, good))                                     # ... still answers the length first
+    return cases
+
+
+@pytest.mark.parametrize('flags,name', [([], 'plain'), (SANITIZE, 'san')])
+def test_per_slot_front_end_equals_the_model(tmp_path, key, flags, name):
+    exe = _program(tmp_path, flags, name)
+    cases = _prep_cases(key)
+    got = _run(exe, 'prep', ['%d %d %s %s %s' % (v, ln, vk.hex(), pv.hex() or '-', r.hex()) for v, ln, vk, pv, r in cases])
+    seen = set()
+    for (v, ln, vk, pv, r), line in zip(cases, got):
+        st, fl, s0, s1 = gk.prep_slot(v, ln, vk, pv, r)
+        assert line == '%d %d %064x %064x' % (st, fl, s0, s1), (v, ln, vk.hex(), len(pv))
+        seen.add((st, fl))
+    assert {(4, 0), (1, 0), (1, 1), (1, 3), (1, 5), (1, 9)} <= seen
+    # the model's front end agrees with the whole-proof model wherever that one decides before the pairing
+    for v, ln, vk, pv, r in cases:
+        if v and ln == 260:
+            st = gk.sp1_verify_proof(key.words, key.hash, vk, pv, r)[0]
+            fl = gk.prep_slot(v, ln, vk, pv, r)[1]
+            assert st in (0, 1) and (fl & 1 or st == 1)
+
+
+# ---------------------------------------------------------------- slot layout
+@pytest.mark.parametrize('flags,name', [([], 'plain'), (SANITIZE, 'san')])
+def test_slot_layout_of_the_keyed_group(tmp_path, flags, name):
+    exe = _program(tmp_path, flags, name)
+    counts = [(1, 31, 32, 33, 0, 64), (1, 33, 31), (0, 0, 5), (7,), (0,), (64, 64), (1, 1, 1, 1, 1, 1, 1, 1), (3000, 1, 0, 2999), (40000, 1), (0, 33, 0, 0)]
+    lines, meta = [], []
+    for cnt in counts:
+        for lanes in (2, 16, 64, 128):
+            for fixed in (0, 1):
+                lines.append('%d %d %s' % (lanes, fixed, ' '.join(map(str, cnt))))
+                meta.append((cnt, lanes, fixed))
+    got = _run(exe, 'layout', lines)
+    align_of = {2: 32, 16: 4, 64: 1, 128: 1}
+    for (cnt, lanes, fixed), line in zip(meta, got):
+        head, _, tail = line.partition('|')
+        head = [int(x) for x in head.split()]
+        chosen, slots, start = head[0], head[1], head[2:]
+        keys = [int(x) for x in tail.split()]
+        n = sum(cnt)
+        # the 1.25x rule, stated on its own: the first mapping from `lanes` on (pairs -> 16 lanes -> one wavefront) whose padding is within
+        # 1.25 times the proofs, or the finest; a fixed mapping is kept
+        want = lanes
+        while not fixed and align_of[want] > 1 and 4 * sum(-(-c // align_of[want]) * align_of[want] for c in cnt) > 5 * n:
+            want = 16 if want == 2 else 64
+        assert chosen == want, (cnt, lanes, fixed)
+        al = align_of[chosen]
+        assert all(s % al == 0 for s in start) and slots % al == 0                       # every route starts on a multiple of the alignment
+        assert start == [sum(-(-c // al) * al for c in cnt[:k]) for k in range(len(cnt))]
+        assert slots == sum(-(-c // al) * al for c in cnt) and len(keys) == slots
+        assert slots - n <= (al - 1) * len(cnt)                                           # what the gateway sizes its slot tables by
+        for k, c in enumerate(cnt):                                                       # a route's proofs and its pad slots carry its key
+            assert all(keys[j] == k for j in range(start[k], start[k] + c))
+        for wv in range(0, slots, al):                                                    # no two routes share a wavefront
+            assert len(set(keys[wv:wv + al])) == 1
