@@ -335,7 +335,7 @@ void launch_finalexp2(size_t n, const Workspace& ws, uint8_t* status, hipStream_
     hipLaunchKernelGGL(k_finalexp2, dim3(hot_grid(n)), dim3(PAIR_BLOCK), 0, s, n, gt, rel, ws, status);
 }
 // TEST ONLY (zkv_diag_gt_product): every proof alive with the Miller value 1.  k_finalexp2 then exponentiates 1 to 1, walks the tables
-// over the scalars the caller put in ws.prep, and its last COPY TMP <- ACC leaves the product M of the walk in the slot TMP.
+// over the scalars the caller put in ws.prep, and the walk's COPY TMP <- ACC leaves its u (M = u / conj(u), zkv_gt.h) in the slot TMP.
 __global__ __launch_bounds__(ZKV_BLOCK) void k_gt_diag_seed(size_t n, Workspace ws) {
     const size_t i = ((size_t)blockIdx.x * ZKV_BLOCK + threadIdx.x) >> 1;
     if (i >= n) return;

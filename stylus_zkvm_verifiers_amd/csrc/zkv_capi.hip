@@ -620,6 +620,7 @@ static int gt_maybe_build(zkv_ctx* c, size_t n) {
         (void)hipEventRecord(e0, c->stream);
         launch_gt_bases(d_raw, c->d_tab, c->d_gt, c->d_gt_const, d_scr, nw0, nw1, c->stream);
         for (uint32_t level = 1; level < GT_WINDOW_BITS; level++) launch_gt_level(c->d_gt, rows, level, c->stream);
+        launch_gt_torus(c->d_gt, rows, c->stream);               // every entry to its affine torus value: what the walk multiplies by
         (void)hipEventRecord(e1, c->stream);
         ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
         if (ok) (void)hipEventElapsedTime(&c->gt_build_ms, e0, e1);
@@ -3467,8 +3468,9 @@ ZKV_EXPORT int zkv_ctx_set_lanes_per_proof(zkv_ctx* c, int lanes) {
     return ZKV_OK;
 }
 // Diagnostics of the GT tables (zkv_gt.h; include/zkv_diag_gt.h).  info: {built, windows of signal 0, of signal 1, table bytes, build time in
-// microseconds, build attempted}.  read: the 96 words of one entry as stored (Montgomery form, R = 2^261, values below 2p; g0 g1 g2 h0 h1 h2,
-// (c0, c1) each) -- signal 0 / 1, window, digit magnitude d = 1 .. 2^19 --, or with signal < 0 the folded Miller constant.
+// microseconds, build attempted}.  read: the 96 words of one entry in full Fp12 form (Montgomery form, R = 2^261, values below 2p; g0 g1 g2 h0 h1
+// h2, (c0, c1) each; rebuilt from the stored torus value, k_gt_diag_expand) -- signal 0 / 1, window, digit magnitude d = 1 .. 2^19 --, or with
+// signal < 0 the folded Miller constant as stored.
 ZKV_EXPORT int zkv_diag_gt_info(zkv_ctx* c, uint64_t* out6) {
     if (!c || !out6) return ZKV_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -3486,12 +3488,21 @@ ZKV_EXPORT int zkv_diag_gt_read(zkv_ctx* c, int signal, uint32_t window, uint32_
         if (signal >= (int)GT_MAX_SIG || window >= c->gt.nw[signal] || d < 1 || d > GT_ROW_ENTRIES) return ZKV_ERR_INVALID_ARG;
         src = c->gt.tab + gt_row_word((signal ? c->gt.nw[0] : 0u) + window) + gt_entry_offset(d) / 4;
     }
-    HIP_TRY(hipMemcpy(out96, src, sizeof(uint32_t) * GT_ENTRY_WORDS, hipMemcpyDeviceToHost));
+    if (signal < 0) { HIP_TRY(hipMemcpy(out96, src, sizeof(uint32_t) * GT_ENTRY_WORDS, hipMemcpyDeviceToHost)); return ZKV_OK; }
+    // an entry is stored as its affine torus value a (zkv_gt.h): the full Fp12 is reconstructed from it on the device
+    uint32_t* d_out = nullptr;
+    HIP_TRY(hipMalloc(&d_out, sizeof(uint32_t) * GT_ENTRY_WORDS));
+    launch_gt_diag_expand(src, d_out, c->stream);
+    const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess &&
+                    hipMemcpy(out96, d_out, sizeof(uint32_t) * GT_ENTRY_WORDS, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d_out);
+    if (!ok) { (void)hipGetLastError(); return ZKV_ERR_HIP; }
     return ZKV_OK;
 }
 // product: what k_finalexp2's table walk makes of given scalars.  The n proofs get the Miller value 1 (k_gt_diag_seed), so the kernel's
-// program exponentiates 1 to 1, the walk multiplies the selected rows into ACC, and the program's COPY TMP <- ACC leaves M in the slot TMP
-// (slot 8 of ws.fe), which is read back.  The kernel and its launch are the ones the verify path uses.
+// program exponentiates 1 to 1, the walk carries u with M = u / conj(u) over the selected rows and leaves u in the slot TMP (slot 8 of
+// ws.fe); M is formed from it (k_gt_diag_ratio, one inversion per proof) and read back.  The kernel and its launch are the ones the verify
+// path uses.
 ZKV_EXPORT int zkv_diag_gt_product(zkv_ctx* c, size_t n, const uint32_t* scalars, uint32_t* out) {
     if (!c || !n || !scalars || !out) return ZKV_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -3507,17 +3518,20 @@ ZKV_EXPORT int zkv_diag_gt_product(zkv_ctx* c, size_t n, const uint32_t* scalars
     std::vector<uint32_t> rows(SW * n), res((size_t)GT_ENTRY_WORDS * n);
     for (size_t i = 0; i < n; i++) for (size_t k = 0; k < SW; k++) rows[k * n + i] = scalars[i * SW + k];
     uint8_t* d_st = nullptr;
+    uint32_t* d_m = nullptr;                                     // M and the scratch of k_gt_diag_ratio, 96 n words each
     HIP_TRY(hipMalloc(&d_st, n));
+    if (hipMalloc(&d_m, sizeof(uint32_t) * 2 * GT_ENTRY_WORDS * n) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_st); return ZKV_ERR_HIP; }
     const size_t cap = c->ws.cap;
     bool ok = hipMemcpy2DAsync(c->ws.prep + 64 * cap, cap * 4, rows.data(), n * 4, n * 4, SW, hipMemcpyHostToDevice, c->stream) == hipSuccess;
     if (ok) {
         launch_gt_diag_seed(n, c->ws, c->stream);
         launch_finalexp2(n, c->ws, d_st, c->stream, c->gt);
+        launch_gt_diag_ratio(n, c->ws.fe + (size_t)(96 * 6) * cap, cap, d_m, d_m + (size_t)GT_ENTRY_WORDS * n, c->stream);
         ok = hipGetLastError() == hipSuccess &&
-             hipMemcpy2DAsync(res.data(), n * 4, c->ws.fe + (size_t)(96 * 6) * cap, cap * 4, n * 4, GT_ENTRY_WORDS, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+             hipMemcpyAsync(res.data(), d_m, sizeof(uint32_t) * GT_ENTRY_WORDS * n, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
              hipStreamSynchronize(c->stream) == hipSuccess;
     }
-    (void)hipFree(d_st);
+    (void)hipFree(d_st); (void)hipFree(d_m);
     if (!ok) { (void)hipGetLastError(); return ZKV_ERR_HIP; }
     for (size_t i = 0; i < n; i++) for (size_t k = 0; k < GT_ENTRY_WORDS; k++) out[i * GT_ENTRY_WORDS + k] = res[k * n + i];
     return ZKV_OK;

@@ -8,6 +8,18 @@
 // product M of a proof's entries multiplies the exponentiated value of the other pairs: FE(f_AB f_Cdelta m_const) * M == 1.  Entries
 // are unitary (GT is in the cyclotomic subgroup): a negative digit multiplies by the conjugate.
 //
+// TORUS-COMPRESSED ENTRIES.  Fp12 = Fp6[w] / (w^2 - v), an element is g + h w.  A unitary t = g + h w other than +-1 is (a + w) / (a - w) with
+// a = (1 + g) / h in Fp6 (its affine torus value; (a + w)^2 / (a^2 - v) has g = (a^2 + v) / (a^2 - v), h = 2 a / (a^2 - v)), and t^-1 = conj(t) has
+// the value -a.  Every entry is G^(d 2^(20 j)) with G of prime order R and d 2^(20 j) no multiple of R, so no entry is +-1, h is invertible and
+// a is finite and nonzero.  The tables hold a, and the walk carries an ordinary Fp12 value u = N + D w standing for M = u / conj(u):
+//     start u = 1;   one window with digit d and entry a:   u <- u (sigma a + w), sigma = sign(d):   N' = sigma N a + v D,  D' = N + sigma a D
+// -- conj(u') = conj(u)(sigma a - w), so M' = M t^sigma --, two Fp6 products where the full entry took three, and no conjugation for a
+// negative digit.  u never becomes 0 (that would need a^2 = v, and v is no square in Fp6).  The test FE * M == 1 becomes FE * u == conj(u)
+// (conj(u) is invertible: its norm is N^2 - v D^2 != 0): one Fp12 product and a comparison close the walk (final_exp_prog_p, zkv_verify.h).
+// An entry keeps its 384-byte place (the geometry below is what the host tests pin): a0 a1 a2, (c0, c1) each, in the first 192 bytes, which is
+// all the walk fetches; the second 192 bytes are unused after the build's last step (k_gt_torus) -- they still hold h of the full form, which
+// nothing reads.  Halving the tables means changing that geometry and the tests that pin it.
+//
 // This header is plain C++ (the recoding and the table indexing are tested on the host).
 #pragma once
 #include <stdint.h>
@@ -23,7 +35,7 @@ namespace zkv {
 
 constexpr uint32_t GT_WINDOW_BITS = 20;
 constexpr uint32_t GT_ROW_ENTRIES = 1u << (GT_WINDOW_BITS - 1);     // d = 1 .. 2^19 at index d - 1
-constexpr uint32_t GT_ENTRY_WORDS = 96;                             // one Fp12: g0 g1 g2 h0 h1 h2, (c0, c1) each, 384 contiguous bytes
+constexpr uint32_t GT_ENTRY_WORDS = 96;                             // an entry's place, 384 contiguous bytes: one Fp12 while the tables are built, then a0 a1 a2 in the first 192
 constexpr uint32_t GT_MAX_SIG = 2;                                  // RISC Zero and SP1 have two per-proof signals
 constexpr uint32_t GT_MAX_WINDOWS = 13;                             // 13 x 20 = 260 bits
 constexpr size_t GT_ROW_BYTES = (size_t)GT_ROW_ENTRIES * GT_ENTRY_WORDS * 4;     // 201,326,592: below 2^32, a lane addresses its entry by a 32-bit offset

@@ -118,6 +118,11 @@ void launch_finalexp2(size_t n, const Workspace& ws, uint8_t* status, hipStream_
 constexpr size_t GT_SETUP_SCRATCH_WORDS = 3 * 12 * 96;
 void launch_gt_bases(const VkRaw* d_raw, const VkTables* d_tab, uint32_t* tab, uint32_t* mconst, uint32_t* scratch, uint32_t nw0, uint32_t nw1, hipStream_t s);
 void launch_gt_level(uint32_t* tab, uint32_t rows, uint32_t level, hipStream_t s);
+// the build's last step: every entry of `rows` windows to its affine torus value, in place (k_gt_torus)
+void launch_gt_torus(uint32_t* tab, uint32_t rows, hipStream_t s);
+// test only (zkv_diag_gt_read / zkv_diag_gt_product): a stored a back to the full entry; u / conj(u) of the n values in the TMP rows
+void launch_gt_diag_expand(const uint32_t* a48, uint32_t* out96, hipStream_t s);
+void launch_gt_diag_ratio(size_t n, const uint32_t* tmp, size_t cap, uint32_t* out, uint32_t* scr, hipStream_t s);
 // test only (zkv_diag_gt_product): flags alive, Miller value 1 for n lane-pair proofs
 void launch_gt_diag_seed(size_t n, const Workspace& ws, hipStream_t s);
 // coefficient-parallel small-batch variants (k_wide.hip): one proof per 16 lanes

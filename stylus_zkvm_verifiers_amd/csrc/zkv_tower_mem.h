@@ -323,6 +323,75 @@ template <class RB> ZKV_HD void f12l9_mul(L9Ref acc, RB S0, const bool conj_b) {
     }
     l9_st(acc, 3, h0); l9_st(acc, 4, h1); l9_st(acc, 5, h2);
 }
+// ---- ACC <- ACC * (sigma a + w) on resident limbs: one step of the table walk on torus-compressed entries (zkv_gt.h).  ACC = N + D w,
+// a = a0 + a1 v + a2 v^2 packed in the first three Fp2 of the slot S, sigma = -1 where `neg`:
+//     N' = sigma N a + v D,    D' = N + sigma D a,    v D = (xi D2, D0, D1)
+// -- two Fp6 products with the same multiplier instead of the three of f12l9_mul, and each result coefficient leaves ONE combination
+// that reduces the product's lazy sums, applies the sign as its coefficients and adds the other half of ACC.  Only lanes with `keep`
+// store (a lane without a digit in this window keeps its ACC; what it read from S is then never used).
+// Inputs as for f12l9_mul: ACC normalised and below 2p (multiplicands; their pairwise sums stay below 2^30 per limb), a packed and below
+// 2p (multiplier limbs normalised after unpacking, pairwise sums carried).  Every result is normalised and below 1.01 p.
+// The bound c of each combination takes every product below 2p and both signs at once: a product term of coefficient k counts 2 |k| per
+// value it is made of that can enter negatively (wa, wb: two of three for sigma = 1, one for sigma = -1; wc: two either way).
+// l9_pin(a): a is formed where this stands.  Without it the compiler sinks the three combinations of N' below into the conditional store at
+// the end, behind the second product, and every term of theirs stays live across its six calls (24 spilled registers, 112 bytes of scratch).
+ZKV_HD void l9_pin(L9& a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int i = 0; i < 9; i++) asm volatile("" : "+v"(a.l[i]));
+#else
+    (void)a;
+#endif
+}
+template <class RB> ZKV_HD void f12l9_mul_aw(L9Ref acc, RB S0, const bool neg, const bool keep) {
+    const int32_t k1 = zkv_parity() != 0 ? 1 : -1;                                 // xi q, this lane's component: 9 mine -+ the partner's
+    const int32_t sg = neg ? -1 : 1, sg9 = 9 * sg, sgk = k1 * sg;
+    L9F6Raw raw;
+    int32_t pw[9];
+    L9 n0, n1, n2;
+    {
+        const RB S = m_fresh(S0);
+        l9_f6_mul_raw([&](int i) { return l9_ld(acc, i); }, [&](int i) { return l9_from_fp(m_ld_f2(S, i).h); }, raw);
+        l9_partner_i32(raw.wa, pw);
+        const L9 d2 = l9_ld(acc, 5), pd2 = l9_partner(d2);
+        // N'0 = sigma (v0 + xi wa) + xi D2: negative part at most 2 + 9 * 4 + 4 + 2 units of p
+        { const LTerm t[5] = {{raw.v0.l, sg}, {(const uint32_t*)raw.wa, sg9}, {(const uint32_t*)pw, sgk}, {d2.l, 9}, {pd2.l, k1}}; n0 = l9_lincomb(t, 48); }
+        const L9 pv2 = l9_partner(raw.v2), d0 = l9_ld(acc, 3);
+        // N'1 = sigma (wb + xi v2) + D0: 4 + 9 * 2 + 2
+        { const LTerm t[4] = {{(const uint32_t*)raw.wb, sg}, {raw.v2.l, sg9}, {pv2.l, sgk}, {d0.l, 1}}; n1 = l9_lincomb(t, 28); }
+        const L9 d1 = l9_ld(acc, 4);
+        // N'2 = sigma wc + D1: 4
+        { const LTerm t[2] = {{(const uint32_t*)raw.wc, sg}, {d1.l, 1}}; n2 = l9_lincomb(t, 8); }
+    }
+    l9_pin(n0); l9_pin(n1); l9_pin(n2);
+    L9 h0, h1, h2;
+    {
+        const RB S = m_fresh(S0);
+        l9_f6_mul_raw([&](int i) { return l9_ld(acc, 3 + i); }, [&](int i) { return l9_from_fp(m_ld_f2(S, i).h); }, raw);
+        l9_partner_i32(raw.wa, pw);
+        const L9 g0 = l9_ld(acc, 0);
+        // D'0 = N0 + sigma (v0 + xi wa): 2 + 9 * 4 + 4
+        { const LTerm t[4] = {{raw.v0.l, sg}, {(const uint32_t*)raw.wa, sg9}, {(const uint32_t*)pw, sgk}, {g0.l, 1}}; h0 = l9_lincomb(t, 48); }
+        const L9 pv2 = l9_partner(raw.v2), g1 = l9_ld(acc, 1);
+        { const LTerm t[4] = {{(const uint32_t*)raw.wb, sg}, {raw.v2.l, sg9}, {pv2.l, sgk}, {g1.l, 1}}; h1 = l9_lincomb(t, 28); }
+        const L9 g2 = l9_ld(acc, 2);
+        { const LTerm t[2] = {{(const uint32_t*)raw.wc, sg}, {g2.l, 1}}; h2 = l9_lincomb(t, 8); }
+    }
+    if (keep) {
+        l9_st(acc, 0, n0); l9_st(acc, 1, n1); l9_st(acc, 2, n2);
+        l9_st(acc, 3, h0); l9_st(acc, 4, h1); l9_st(acc, 5, h2);
+    }
+}
+// ACC == conj(T)?  Coefficient by coefficient on the packed values, either representative below 2p accepted (as f12m_is_one does).
+template <class RA, class RT> ZKV_HD bool f12m_eq_conj(RA a, RT t) {
+    bool ok = true;
+#pragma unroll 1
+    for (int k = 0; k < 6; k++) {
+        const Fp2 x = m_ld_f2(a, k), y = m_ld_f2(t, k);
+        ok = (k < 3 ? f2_eq(x, y) : f2_is_zero(f2_add(x, y))) && ok;
+    }
+    return ok;
+}
 #endif  // ZKV_PAIRED
 
 // d <- a * b, or a * conj(b) (conj(b) = b^-1 for b in the cyclotomic subgroup); d may alias a or b

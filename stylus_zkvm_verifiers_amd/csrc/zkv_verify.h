@@ -560,13 +560,17 @@ ZKV_HD SoaRW fe_slot(int s, uint32_t* fbase, uint32_t* ebase, size_t cap, uint32
     return r;
 }
 // Fixed-base GT tables (zkv_gt.h): where this proof's signals and the context's tables are.  on == false (the default): none, the program
-// runs as generated.  Otherwise four entries per window of each signal follow the program's last multiplication:
-//     TMP <- T[|digit|] (1 for a digit of 0);   CONJ ACC;   ACC <- ACC * TMP;   CONJ ACC
-// with the conjugations only in the lanes whose digit is negative (ACC conj(T) = conj(conj(ACC) T) for unitary values).  The multiplication
-// and the conjugation are the bodies every other entry uses (each inlined once, wave-uniform operands as before: with the table row as the
-// multiplication's own operand -- a second stride and a per-lane conjugation flag -- the kernel needed 32 bytes of scratch); the entry is
-// fetched by the small copy in front, 384 contiguous bytes the two lanes of a pair read together.  A window in which no lane of the wavefront
-// has a digit skips all four.  The digit is cut from the proof's scalar words (sc: word 0 of signal 0 of proof 0, ws.prep + 64 cap).
+// runs as generated.  Otherwise the walk REPLACES the program's last two entries (COPY TMP <- ACC; ISONE TMP).  ACC then holds FE, the
+// exponentiated value of the other pairs, and the check FE * M == 1 with M = prod T[|digit|]^(sign digit) is made on torus-compressed
+// entries: the walk carries u = N + D w with M = u / conj(u) (zkv_gt.h) and tests FE * u == conj(u):
+//     COPY Y4 <- ACC (Y4 is dead by then);   ACC <- 1;
+//     per window of each signal:   TMP(0..2) <- a of T[|digit|];   ACC <- ACC * (sign(digit) a + w)      (f12l9_mul_aw: two Fp6 products)
+//     COPY TMP <- ACC;   ACC <- ACC * Y4;   EQCONJ: ACC == conj(TMP)
+// A lane whose digit is 0 fetches nothing and keeps its ACC; a window in which no lane of the wavefront has a digit skips both entries.  TMP
+// is left holding u (zkv_diag_gt_product reads it).  The product is a body of its own, inlined once like every other, with wave-uniform
+// operands: the entry is fetched by the small copy in front, 192 contiguous bytes the two lanes of a pair read together (with the table row
+// as the product's own operand -- a second stride -- the full-entry form of this walk needed 32 bytes of scratch).  The digit is cut from
+// the proof's scalar words (sc: word 0 of signal 0 of proof 0, ws.prep + 64 cap).
 // rel: where the tables are, in words FROM ebase (computed on the host): the row hangs off the same base pointer as the slots.  (With the
 // tables' own pointer the copy's source was a choice between two kernel arguments, and the compiler's inliner crashed on it.)
 // ebase + rel is a difference of two device allocations carried as an integer: it relies on the flat address space of the device and is
@@ -579,7 +583,7 @@ struct GtRef { bool on; ptrdiff_t rel; const uint32_t* sc; uint32_t nw0, nw1; };
 // What the walk assumes of the generated program (gen_constants.py): it ends in COPY TMP <- ACC; ISONE TMP, and TMP is slot 8.
 constexpr uint32_t FE_PROG_TAIL_CHECK[ZKV_FE_PROG_LEN] = ZKV_FE_PROG;
 static_assert(FE_PROG_TAIL_CHECK[ZKV_FE_PROG_LEN - 2] == (0u | 8u << 8 | 0u << 16) && (FE_PROG_TAIL_CHECK[ZKV_FE_PROG_LEN - 1] & 0xffffu) == (7u | 8u << 8),
-              "final_exp_prog_p: the table walk goes in front of the program's last two entries, COPY TMP <- ACC; ISONE TMP, with TMP = slot 8");
+              "final_exp_prog_p: the table walk takes the place of the program's last two entries, COPY TMP <- ACC; ISONE TMP, with TMP = slot 8");
 ZKV_HD bool zkv_wave_any(bool v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_ballot_w64(v) != 0;
@@ -589,24 +593,26 @@ ZKV_HD bool zkv_wave_any(bool v) {
 }
 ZKV_HD bool final_exp_prog_p(uint32_t* fbase, uint32_t* ebase, size_t cap, uint32_t off, L9Ref acc, const GtRef gt = GtRef{false, 0, nullptr, 0, 0}) {
     const uint32_t PROG[ZKV_FE_PROG_LEN] = ZKV_FE_PROG;
-    const uint32_t GT_PROG[4] = {8u, 1u, 3u | 8u << 24, 1u};         // GTLOAD; CONJ ACC; MUL ACC <- ACC * TMP; CONJ ACC
+    // the walk's entries: COPY Y4 <- ACC; SETONE ACC | GTLOAD; MULAW | COPY TMP <- ACC; MUL ACC <- ACC * Y4; EQCONJ ACC, TMP
+    const uint32_t GT_PROG[7] = {0u | 5u << 8, 10u, 8u, 9u, 0u | 8u << 8, 3u | 5u << 24, 11u | 8u << 8};
     bool one = false;
     const uint32_t slot = zkv_wave_slot_parity();
-    // the table walk goes in front of the program's last two entries (COPY TMP <- ACC; ISONE TMP)
-    const int n_extra = gt.on ? 4 * (int)(gt.nw0 + gt.nw1) : 0, cut = ZKV_FE_PROG_LEN - 2;
+    // with tables the walk takes the place of the program's last two entries (COPY TMP <- ACC; ISONE TMP)
+    const int cut = ZKV_FE_PROG_LEN - 2, n_win = gt.on ? 2 * (int)(gt.nw0 + gt.nw1) : 0;
+    const int n_prog = gt.on ? cut + 2 + n_win + 3 : ZKV_FE_PROG_LEN;
 #pragma unroll 1
-    for (int pc = 0; pc < ZKV_FE_PROG_LEN + n_extra; pc++) {
-        const int q = pc - cut;
-        const bool extra = q >= 0 && q < n_extra;
-        const uint32_t row = extra ? (uint32_t)q >> 2 : 0u;          // window `row - (signal ? nw0 : 0)` of signal 0 / 1
-        const uint32_t e = extra ? GT_PROG[q & 3] : PROG[q < 0 ? pc : pc - n_extra];
+    for (int pc = 0; pc < n_prog; pc++) {
+        const int q = pc - cut - 2;                                 // position among the window entries
+        const bool extra = gt.on && pc >= cut, win = extra && q >= 0 && q < n_win;
+        const uint32_t row = win ? (uint32_t)q >> 1 : 0u;            // window `row - (signal ? nw0 : 0)` of signal 0 / 1
+        const uint32_t e = !extra ? PROG[pc] : GT_PROG[q < 0 ? q + 2 : win ? 2 + (q & 1) : q - n_win + 4];
         const int op = (int)(e & 255u), d = (int)((e >> 8) & 255u), a = (int)((e >> 16) & 255u), b = (int)(e >> 24);
         if ((pc & 3) == 0) zkv_fair_share(slot);          // the two wavefronts of a SIMD take turns at priority (zkv_field.h)
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("" : "+v"(off));
 #endif
-        int32_t dg = 0;                                    // a table entry: this lane's digit (both lanes of a pair read the same words)
-        if (extra) {
+        int32_t dg = 0;                                    // a window entry: this lane's digit (both lanes of a pair read the same words)
+        if (win) {
             const uint32_t sig = row >= gt.nw0 ? 1u : 0u, j = sig ? row - gt.nw0 : row, k = gt_digit_word(j);
             const uint32_t i4 = off - 32u * zkv_parity() * (uint32_t)cap;
             const uint32_t lo = *(const uint32_t*)((const char*)(gt.sc + (size_t)(8u * sig + k) * cap) + i4);
@@ -616,19 +622,22 @@ ZKV_HD bool final_exp_prog_p(uint32_t* fbase, uint32_t* ebase, size_t cap, uint3
         }
         if (op == 6) { ZKV_MARK("begin cyclo"); f12l9_cyclo_sqr(acc); ZKV_MARK("end cyclo"); }
         else if ((op == 3 || op == 4) && d == 0) { ZKV_MARK("begin accmul");  f12l9_mul(acc, fe_slot(b, fbase, ebase, cap, off), op == 4); ZKV_MARK("end accmul"); }
+        else if (op == 9) { ZKV_MARK("begin awmul"); f12l9_mul_aw(acc, fe_slot(8, fbase, ebase, cap, off), dg < 0, dg != 0); ZKV_MARK("end awmul"); }
         else if (op == 8) {
-            const SoaRW D = fe_slot(8, fbase, ebase, cap, off);
-            if (dg == 0) f12m_set_one(D);
-            else {
+            if (dg != 0) {                                 // a0 a1 a2 of the entry, the first 192 of its 384 bytes
+                const SoaRW D = fe_slot(8, fbase, ebase, cap, off);
                 SoaRW T;
                 T.p = ebase + gt.rel + (ptrdiff_t)gt_row_word(row); T.stride = 1;
                 T.off = gt_entry_offset((uint32_t)(dg < 0 ? -dg : dg)) + 32u * zkv_parity();
-                f12m_copy(D, T);
+#pragma unroll 1
+                for (int k = 0; k < 3; k++) m_st_f2(D, k, m_ld_f2(T, k));
             }
         }
+        else if (op == 10) f12m_set_one(acc);
+        else if (op == 11) one = f12m_eq_conj(acc, fe_slot(d, fbase, ebase, cap, off));
         else if (op == 0 && d == 0) f12m_copy(acc, fe_slot(a, fbase, ebase, cap, off));
         else if (op == 0 && a == 0) f12m_copy(fe_slot(d, fbase, ebase, cap, off), acc);
-        else if (op == 1 && d == 0) { if (!extra || dg < 0) f12m_conj(acc); }
+        else if (op == 1 && d == 0) f12m_conj(acc);
         else {
             const SoaRW D = fe_slot(d, fbase, ebase, cap, off), A = fe_slot(a, fbase, ebase, cap, off);
             if (op == 3 || op == 4) { ZKV_MARK("begin genmul"); f12m_mul_body(D, A, fe_slot(b, fbase, ebase, cap, off), op == 4); ZKV_MARK("end genmul"); }
