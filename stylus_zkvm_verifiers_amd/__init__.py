@@ -6,6 +6,7 @@ Drop-in for the verify path of gnosisguild/stylus-zkvm-verifiers: `RiscZeroVerif
 from . import errors
 from .errors import VerifierError
 from .risc0 import RiscZeroVerifier, RiscZeroVerifierSet
+from .risc0_set_inclusion import RiscZeroSetInclusionVerifier
 from .sp1 import Sp1Verifier, Sp1PlonkVerifier
 from .bn254 import Bn254Precompiles
 from .groth16 import Groth16Verifier
@@ -17,7 +18,7 @@ from .plonk_set import PlonkVerifierSet
 from . import wire
 from .sharded import shard, shard_count, shard_devices, shard_peer_access
 
-__all__ = ['host_register', 'host_unregister', 'RiscZeroVerifier', 'RiscZeroVerifierSet', 'Sp1Verifier', 'Sp1PlonkVerifier', 'Bn254Precompiles', 'Groth16Verifier', 'Groth16VerifierSet', 'MixedVerifier', 'Sp1Gateway', 'PlonkVerifier', 'PlonkVerifierSet', 'VerifierError', 'errors', 'wire', 'device_count', 'shard', 'shard_count', 'shard_devices', 'shard_peer_access']
+__all__ = ['host_register', 'host_unregister', 'RiscZeroVerifier', 'RiscZeroVerifierSet', 'RiscZeroSetInclusionVerifier', 'Sp1Verifier', 'Sp1PlonkVerifier', 'Bn254Precompiles', 'Groth16Verifier', 'Groth16VerifierSet', 'MixedVerifier', 'Sp1Gateway', 'PlonkVerifier', 'PlonkVerifierSet', 'VerifierError', 'errors', 'wire', 'device_count', 'shard', 'shard_count', 'shard_devices', 'shard_peer_access']
 
 
 def device_count():

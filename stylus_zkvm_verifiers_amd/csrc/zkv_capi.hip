@@ -27,6 +27,7 @@
 #include "../../include/zkv_diag_primitive.h"
 #include "../../include/zkv_diag_prep.h"
 #include "../../include/zkv_diag_gt.h"
+#include "../../include/zkv_risc0_set_inclusion.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
@@ -34,6 +35,7 @@
 #include "zkv_agg.h"
 #include "zkv_gset_layout.h"
 #include "zkv_selftest.h"
+#include "zkv_setincl.h"
 #include <sys/random.h>
 
 using namespace zkv;
@@ -191,6 +193,14 @@ struct zkv_ctx {
     std::vector<uint32_t> gw_sel;
     std::vector<uint8_t> gw_ran;
     uint64_t gw_counts[GW_COLS] = {0};
+    // ZKV_VM_RISC0_SETINCL (zkv_risc0_set_inclusion.h): kid[0] is the inner root verifier V -- a RISC Zero context, or (si_keyed) a generic
+    // Groth16 context of the caller's key in the RISC Zero convention, whose parameters then sit in control_root_0 / _1, control_id and
+    // si_root_sel.  si_roots: the submitted roots, 32 bytes each, ascending; their device copy (mx[SI_STORED]) is refreshed by the next
+    // batch call after a submission (si_dirty).  mx[] holds the workspace and the staging of host-buffer calls (enum SI_*).
+    bool si_keyed = false, si_dirty = false;
+    uint8_t si_id[32] = {0}, si_root_sel[4] = {0}, si_set_sel[4] = {0};
+    std::vector<uint8_t> si_roots;
+    uint64_t si_counts[3] = {0, 0, 0};
     std::mutex mu;
 };
 
@@ -382,7 +392,7 @@ static int ctx_device_setup(zkv_ctx* c) {
     }
     if (c->vm == ZKV_VM_GROTH16_SET) return gset_device_setup(c);
     if (c->vm == ZKV_VM_PLONK_SET) return pset_device_setup(c);
-    if (c->vm != ZKV_VM_BN254 && c->vm != ZKV_VM_MIXED && c->vm != ZKV_VM_SP1_GATEWAY) {
+    if (c->vm != ZKV_VM_BN254 && c->vm != ZKV_VM_MIXED && c->vm != ZKV_VM_SP1_GATEWAY && c->vm != ZKV_VM_RISC0_SETINCL) {
         VkRaw raw;
         if (c->vm == ZKV_VM_RISC0 || c->vm == ZKV_VM_RISC0_SET) host::fill_vk_risc0(raw, c->control_root_0, c->control_root_1, c->control_id);
         else if (c->vm == ZKV_VM_GROTH16) host::fill_vk_generic(raw, c->gvk.data(), c->long_key ? 1u : c->g_n_ic);   // long key: IC[0] only here
@@ -3334,7 +3344,7 @@ ZKV_EXPORT int zkv_plonk_set_verify_batch(zkv_ctx* c, size_t n, const uint32_t* 
 ZKV_EXPORT int zkv_ctx_vk_x_batch(zkv_ctx* c, size_t n, const uint8_t* var_signals, uint8_t* out) {
     if (is_sharded(c)) c = c->shards[0];
     if (!c || c->vm == ZKV_VM_BN254 || c->vm == ZKV_VM_RISC0_SET || c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_PLONK || c->vm == ZKV_VM_GROTH16_SET ||
-        c->vm == ZKV_VM_SP1_GATEWAY || c->vm == ZKV_VM_PLONK || c->vm == ZKV_VM_PLONK_SET)
+        c->vm == ZKV_VM_SP1_GATEWAY || c->vm == ZKV_VM_PLONK || c->vm == ZKV_VM_PLONK_SET || c->vm == ZKV_VM_RISC0_SETINCL)
         return ZKV_ERR_WRONG_CTX;
     if (c->vm == ZKV_VM_RISC0 && !c->initialized) return ZKV_ERR_INVALID_ARG;
     if (n && (!var_signals || !out)) return ZKV_ERR_INVALID_ARG;
@@ -3461,6 +3471,7 @@ ZKV_EXPORT int zkv_ctx_set_lanes_per_proof(zkv_ctx* c, int lanes) {
     if (c->vm == ZKV_VM_MIXED) {                         // the two verifiers behind the tag run the stages
         for (auto* k : c->kid) { const int rc = zkv_ctx_set_lanes_per_proof(k, lanes); if (rc != ZKV_OK) return rc; }
     }
+    if (c->vm == ZKV_VM_RISC0_SETINCL) { const int rc = zkv_ctx_set_lanes_per_proof(c->kid[0], lanes); if (rc != ZKV_OK) return rc; }   // the root jobs run there
     for (auto* k : c->gw_route) { if (!k) continue; const int rc = zkv_ctx_set_lanes_per_proof(k, lanes); if (rc != ZKV_OK) return rc; }
     if (c->gw_group) { const int rc = zkv_ctx_set_lanes_per_proof(c->gw_group, lanes); if (rc != ZKV_OK) return rc; }
     std::lock_guard<std::mutex> lk(c->mu);
@@ -3652,6 +3663,12 @@ ZKV_EXPORT int zkv_ctx_reserve(zkv_ctx* c, size_t n) {
         std::lock_guard<std::mutex> lk(c->mu);
         return ctx_device_init(c);
     }
+    if (c->vm == ZKV_VM_RISC0_SETINCL) {                 // the inner verifier for n root jobs; the hash workspace grows with the calls
+        const int rc = zkv_ctx_reserve(c->kid[0], n);
+        if (rc != ZKV_OK) return rc;
+        std::lock_guard<std::mutex> lk(c->mu);
+        return ctx_device_init(c);
+    }
     if (c->vm == ZKV_VM_SP1_GATEWAY) {                   // any route may own the whole batch
         for (auto* k : c->gw_route) { if (!k) continue; const int rc = zkv_ctx_reserve(k, n); if (rc != ZKV_OK) return rc; }
         if (c->gw_group) { const int rc = zkv_ctx_reserve(c->gw_group, n); if (rc != ZKV_OK) return rc; }
@@ -3674,7 +3691,7 @@ ZKV_EXPORT int zkv_ctx_synchronize(zkv_ctx* c) {
         return ZKV_OK;
     }
     // a mixed context has work in flight as soon as ANY of its three contexts is set up (an all-SP1 batch never touches the RISC Zero child)
-    bool any = c->dev_ready || (c->vm == ZKV_VM_MIXED && ((c->kid[0] && c->kid[0]->dev_ready) || (c->kid[1] && c->kid[1]->dev_ready)));
+    bool any = c->dev_ready || ((c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_RISC0_SETINCL) && ((c->kid[0] && c->kid[0]->dev_ready) || (c->kid[1] && c->kid[1]->dev_ready)));
     for (auto* k : c->gw_route) any = any || (k && k->dev_ready);
     any = any || (c->gw_group && c->gw_group->dev_ready);
     if (!any) return ZKV_OK;
@@ -3696,6 +3713,17 @@ ZKV_EXPORT int zkv_ctx_last_stage_ms(zkv_ctx* c, float out_ms[5]) {
             if (rc != ZKV_OK) return rc;
             for (int i = 0; i < 5; i++) out_ms[i] += a[i];
         }
+        return ZKV_OK;
+    }
+    if (c->vm == ZKV_VM_RISC0_SETINCL) {                 // [0]: k_setincl_hash of the last chunk; [1..4]: the inner verifier's stages of the last root jobs
+        std::lock_guard<std::mutex> lk(c->mu);
+        if (!c->dev_ready || !c->si_counts[0]) return ZKV_ERR_NO_DEVICE;
+        float a[5] = {0, 0, 0, 0, 0};
+        if (c->si_counts[1]) { const int rc = zkv_ctx_last_stage_ms(c->kid[0], a); if (rc != ZKV_OK) return rc; }
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipEventSynchronize(c->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&out_ms[0], c->ev[0], c->ev[1]));
+        for (int i = 1; i < 5; i++) out_ms[i] = a[i];
         return ZKV_OK;
     }
     if (c->vm == ZKV_VM_SP1_GATEWAY) {                   // routes run one after the other, as the mixed context's children
@@ -3735,4 +3763,335 @@ ZKV_EXPORT int zkv_status_abi_encode(int vm, uint8_t status, const uint8_t recei
     if (status > ZKV_STATUS_SELECTOR_MISMATCH) return ZKV_ERR_INVALID_ARG;
     memcpy(out, sel[status], 4);
     return 4;
+}
+
+// ------------------------------------------------------------------ RISC Zero set-inclusion receipts (zkv_risc0_set_inclusion.h)
+// No reference counterpart: parity unpinned.  k_setincl.hip hashes the paths and forms the root jobs; the jobs run on the inner context.
+enum { SI_ROOTS = 0, SI_REP, SI_GSLOT, SI_CLAIMJOB, SI_JOBCLAIM, SI_CNT, SI_STORED, SI_ROWS, SI_LENS, SI_IDS, SI_JDS, SI_PROOFS, SI_SIGNALS, SI_PRE,
+       SI_PRERECV, SI_JST, SI_JRV, SI_H_A, SI_H_B, SI_H_PATHS, SI_H_POFF, SI_H_RIDX, SI_H_SEALS, SI_H_SLEN, SI_H_ST, SI_H_RV, SI_DIAG, SI_BUFS };
+static_assert(SI_BUFS <= sizeof(((zkv_ctx*)nullptr)->mx) / sizeof(uint8_t*), "the set-inclusion buffers live in zkv_ctx::mx");
+constexpr size_t SETINCL_CHUNK = (size_t)1 << 20;
+
+static void setincl_set_selector(const uint8_t id[32], uint8_t out[4]) {
+    uint8_t tag[32], d[32];
+    host::sha256_host((const uint8_t*)"risc0.SetInclusionReceiptVerifierParameters", 43, tag);
+    host::tagged_struct(tag, id, 1, d);
+    memcpy(out, d, 4);
+}
+static zkv_ctx* setincl_new(zkv_ctx* inner, const uint8_t control_root[32], const uint8_t control_id[32], const uint8_t id[32], int device) {
+    if (!inner) return nullptr;
+    zkv_ctx* c = new (std::nothrow) zkv_ctx();
+    if (!c) { zkv_ctx_destroy(inner); return nullptr; }
+    c->vm = ZKV_VM_RISC0_SETINCL; c->device = device; c->initialized = true;
+    c->kid[0] = inner;
+    host::risc0_consts(c->consts);
+    host::split_digest(control_root, c->control_root_0, c->control_root_1);
+    memcpy(c->control_id, control_id, 32);
+    memcpy(c->si_id, id, 32);
+    setincl_set_selector(id, c->si_set_sel);
+    return c;
+}
+ZKV_EXPORT zkv_ctx* zkv_risc0_setincl_create(const uint8_t control_root[32], const uint8_t bn254_control_id[32], const uint8_t set_builder_image_id[32],
+                                             int device) {
+    if (!control_root || !bn254_control_id || !set_builder_image_id) return nullptr;
+    zkv_ctx* c = setincl_new(zkv_risc0_ctx_create(control_root, bn254_control_id, device), control_root, bn254_control_id, set_builder_image_id, device);
+    if (c) memcpy(c->si_root_sel, c->kid[0]->selector, 4);
+    return c;
+}
+ZKV_EXPORT zkv_ctx* zkv_risc0_setincl_create_keyed(const uint8_t* vk_words, const uint8_t root_selector[4], const uint8_t control_root[32],
+                                                   const uint8_t bn254_control_id[32], const uint8_t set_builder_image_id[32], int device) {
+    if (!vk_words || !root_selector || !control_root || !bn254_control_id || !set_builder_image_id) return nullptr;
+    zkv_ctx* c = setincl_new(zkv_groth16_ctx_create(vk_words, 6, ZKV_VM_RISC0, device), control_root, bn254_control_id, set_builder_image_id, device);
+    if (c) { c->si_keyed = true; memcpy(c->si_root_sel, root_selector, 4); }
+    return c;
+}
+ZKV_EXPORT int zkv_risc0_setincl_get_selector(const zkv_ctx* c, uint8_t out[4]) {
+    if (!c || c->vm != ZKV_VM_RISC0_SETINCL) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    memcpy(out, c->si_set_sel, 4);
+    return ZKV_OK;
+}
+// position of `root` in the sorted table, *found = it is there
+static size_t setincl_find(const zkv_ctx* c, const uint8_t root[32], bool* found) {
+    size_t lo = 0, hi = c->si_roots.size() / 32;
+    *found = false;
+    while (lo < hi) {
+        const size_t mid = (lo + hi) / 2;
+        const int r = memcmp(root, c->si_roots.data() + 32 * mid, 32);
+        if (r == 0) { *found = true; return mid; }
+        if (r < 0) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+ZKV_EXPORT int zkv_risc0_setincl_has_root(zkv_ctx* c, const uint8_t root[32]) {
+    if (!c || c->vm != ZKV_VM_RISC0_SETINCL) return ZKV_ERR_WRONG_CTX;
+    if (!root) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    bool found;
+    (void)setincl_find(c, root, &found);
+    return found ? 1 : 0;
+}
+// the five signals of V for (ID, sha256(ID || root)) in the keyed mode, 32-byte big-endian words (risc0/verifier.rs:128-144)
+static void setincl_host_signals(const zkv_ctx* c, const uint8_t jd[32], uint8_t sig[160]) {
+    uint32_t h[8];
+    risc0_claim_digest(c->consts, c->si_id, jd, h);
+    uint8_t d[32], lo[16], hi[16];
+    for (int q = 0; q < 8; q++) be32_put(d + 4 * q, h[q]);
+    host::split_digest(d, lo, hi);
+    memset(sig, 0, 160);
+    memcpy(sig + 16, c->control_root_0, 16); memcpy(sig + 48, c->control_root_1, 16);
+    memcpy(sig + 80, lo, 16); memcpy(sig + 112, hi, 16);
+    memcpy(sig + 128, c->control_id, 32);
+}
+ZKV_EXPORT int zkv_risc0_setincl_submit_root(zkv_ctx* c, const uint8_t root[32], const uint8_t* seal, size_t seal_len, uint8_t* status, uint8_t recv[4]) {
+    if (!c || c->vm != ZKV_VM_RISC0_SETINCL) return ZKV_ERR_WRONG_CTX;
+    if (!root || !status || (!seal && seal_len)) return ZKV_ERR_INVALID_ARG;
+    uint8_t msg[64], jd[32], rv[4] = {0, 0, 0, 0}, st = ZKV_STATUS_VERIFICATION_FAILED;
+    memcpy(msg, c->si_id, 32); memcpy(msg + 32, root, 32);
+    host::sha256_host(msg, 64, jd);
+    int rc = ZKV_OK;
+    if (!c->si_keyed) rc = zkv_risc0_verify(c->kid[0], seal, seal_len, c->si_id, jd, &st, rv);
+    else if (seal_len < 4) st = ZKV_STATUS_INVALID_PROOF_DATA;
+    else if (memcmp(seal, c->si_root_sel, 4)) { st = ZKV_STATUS_SELECTOR_MISMATCH; memcpy(rv, seal, 4); }
+    else if (seal_len != ZKV_SEAL_BYTES) st = ZKV_STATUS_INVALID_PROOF_DATA;
+    else {
+        uint8_t sig[160], v = 0;
+        setincl_host_signals(c, jd, sig);
+        rc = zkv_groth16_verify_batch(c->kid[0], 1, seal + 4, sig, &v);
+        st = v ? ZKV_STATUS_OK : ZKV_STATUS_VERIFICATION_FAILED;
+    }
+    if (rc != ZKV_OK) return rc;
+    *status = st;
+    if (recv) memcpy(recv, rv, 4);
+    if (st != ZKV_STATUS_OK) return ZKV_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    bool found;
+    const size_t at = setincl_find(c, root, &found);
+    if (found) return ZKV_OK;
+    if (c->si_roots.size() / 32 >= ZKV_SETINCL_MAX_ROOTS) return ZKV_ERR_INVALID_ARG;
+    try { c->si_roots.insert(c->si_roots.begin() + 32 * at, root, root + 32); } catch (const std::bad_alloc&) { return ZKV_ERR_OOM; }
+    c->si_dirty = true;
+    return ZKV_OK;
+}
+
+// Everything device-resident.  d_b = nullptr: integrity.  d_slen = nullptr: every root seal is 260 bytes.  d_ridx = nullptr with diag: hash only.
+// Synchronises `s` once per chunk (the job count).  The caller holds c->mu and has initialised the device.
+static int run_setincl(zkv_ctx* c, size_t n, const uint8_t* d_a, const uint8_t* d_b, const uint8_t* d_paths, const uint32_t* d_poff, size_t n_sib,
+                       const uint32_t* d_ridx, size_t m, const uint8_t* d_seals, const uint32_t* d_slen, uint8_t* d_status, uint8_t* d_recv, uint8_t* d_diag,
+                       hipStream_t s) {
+    int rc;
+    const size_t cap = n < SETINCL_CHUNK ? n : SETINCL_CHUNK;
+    const size_t need[7] = {32 * cap, 4 * (m + 1), 4 * (m + 1), 4 * cap, 4 * cap, 16, (size_t)32 * ZKV_SETINCL_MAX_ROOTS};
+    for (int k = 0; k < 7; k++) if ((rc = grow(&c->mx[k], &c->mx_cap[k], need[k])) != ZKV_OK) return rc;
+    if (c->si_dirty) {                                   // a root was submitted since the last call: nothing of this context is in flight after the wait
+        HIP_TRY(hipDeviceSynchronize());
+        if (!c->si_roots.empty()) HIP_TRY(hipMemcpy(c->mx[SI_STORED], c->si_roots.data(), c->si_roots.size(), hipMemcpyHostToDevice));
+        c->si_dirty = false;
+    }
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    uint32_t* cnt = (uint32_t*)c->mx[SI_CNT];
+    HIP_TRY(hipMemsetAsync(cnt, 0, 16, s));
+    if (!d_diag) { c->si_counts[0] = n; c->si_counts[1] = 0; c->si_counts[2] = 0; }
+    for (size_t base = 0; base < n; base += cap) {
+        const size_t mc = n - base < cap ? n - base : cap;
+        SetinclChunk ch;
+        memset(&ch, 0, sizeof ch);
+        ch.n = (uint32_t)mc; ch.m = (uint32_t)m; ch.n_siblings = (uint32_t)n_sib; ch.n_stored = (uint32_t)(c->si_roots.size() / 32);
+        ch.in_a = d_a + 32 * base; ch.in_b = d_b ? d_b + 32 * base : nullptr;
+        ch.paths = d_paths; ch.path_off = d_poff + base; ch.root_idx = d_ridx ? d_ridx + base : nullptr;
+        ch.seals = d_seals; ch.seal_len = d_slen; ch.stored = c->mx[SI_STORED];
+        for (int q = 0; q < 8; q++) ch.id_be[q] = be32_of(c->si_id + 4 * q);
+        ch.roots = (uint32_t*)c->mx[SI_ROOTS]; ch.rep = (uint32_t*)c->mx[SI_REP]; ch.gslot = (uint32_t*)c->mx[SI_GSLOT];
+        ch.claim_job = (uint32_t*)c->mx[SI_CLAIMJOB]; ch.job_claim = (uint32_t*)c->mx[SI_JOBCLAIM]; ch.counters = cnt;
+        ch.status = d_status ? d_status + base : nullptr; ch.recv = d_recv ? d_recv + 4 * base : nullptr;
+        ch.diag_roots = d_diag ? d_diag + 32 * base : nullptr;
+        if (d_diag) { launch_setincl_hash(ch, c->consts, s); HIP_TRY(hipGetLastError()); continue; }
+        HIP_TRY(hipMemsetAsync(ch.rep, 0xFF, 4 * (m + 1), s));
+        HIP_TRY(hipMemsetAsync(cnt, 0, 4, s));
+        HIP_TRY(hipEventRecord(c->ev[0], s));                       // zkv_ctx_last_stage_ms [0]: the hash kernel of the last chunk
+        launch_setincl_hash(ch, c->consts, s);
+        HIP_TRY(hipEventRecord(c->ev[1], s));
+        launch_setincl_group(ch, s);
+        HIP_TRY(hipGetLastError());
+        uint32_t nj = 0;
+        HIP_TRY(hipMemcpyAsync(&nj, cnt, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (nj > mc) return ZKV_ERR_HIP;
+        c->si_counts[1] += nj;
+        SetinclJobs jb;
+        memset(&jb, 0, sizeof jb);
+        jb.n_jobs = nj; jb.keyed = c->si_keyed ? 1u : 0u; jb.selector_be = be32_of(c->si_root_sel);
+        if (nj) {
+            // (growing frees the old buffer, which waits for the device: the previous chunk's scatter has read its rows by then)
+            const size_t jneed[10] = {c->si_keyed ? 0 : (size_t)260 * nj, c->si_keyed ? 0 : (size_t)4 * nj, c->si_keyed ? 0 : (size_t)32 * nj,
+                                      c->si_keyed ? 0 : (size_t)32 * nj, c->si_keyed ? (size_t)256 * nj : 0, c->si_keyed ? (size_t)160 * nj : 0,
+                                      c->si_keyed ? (size_t)nj : 0, c->si_keyed ? (size_t)4 * nj : 0, nj, (size_t)4 * nj};
+            for (int k = 0; k < 10; k++) if ((rc = grow(&c->mx[SI_ROWS + k], &c->mx_cap[SI_ROWS + k], jneed[k])) != ZKV_OK) return rc;
+            jb.rows = c->mx[SI_ROWS]; jb.lens = (uint32_t*)c->mx[SI_LENS]; jb.ids = c->mx[SI_IDS]; jb.jds = c->mx[SI_JDS];
+            jb.proofs = c->mx[SI_PROOFS]; jb.signals = c->mx[SI_SIGNALS]; jb.pre = c->mx[SI_PRE]; jb.pre_recv = c->mx[SI_PRERECV];
+            jb.st = c->mx[SI_JST]; jb.rv = c->mx[SI_JRV];
+            memcpy(jb.fixed[0] + 16, c->control_root_0, 16); memcpy(jb.fixed[1] + 16, c->control_root_1, 16); memcpy(jb.fixed[2], c->control_id, 32);
+            launch_setincl_jobs(ch, jb, c->consts, s);
+            HIP_TRY(hipGetLastError());
+            if (c->si_keyed) rc = zkv_groth16_verify_batch_dev(c->kid[0], nj, jb.proofs, jb.signals, c->mx[SI_JST], s);
+            else rc = run_records(c->kid[0], nj, jb.rows, jb.lens, jb.ids, jb.jds, nullptr, nullptr, nullptr, nullptr, c->mx[SI_JST], c->mx[SI_JRV], s);
+            if (rc != ZKV_OK) return rc;
+            HIP_TRY(hipSetDevice(c->device));
+        }
+        launch_setincl_scatter(ch, jb, s);
+        HIP_TRY(hipGetLastError());
+    }
+    return mark_done(c, s);
+}
+static int setincl_dev_call(zkv_ctx* c, size_t n, const uint8_t* d_a, const uint8_t* d_b, const uint8_t* d_paths, const uint32_t* d_poff, size_t n_sib,
+                            const uint32_t* d_ridx, size_t m, const uint8_t* d_seals, uint8_t* d_status, uint8_t* d_recv, void* stream) {
+    if (!c || c->vm != ZKV_VM_RISC0_SETINCL) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_a || !d_poff || !d_ridx || !d_status || (n_sib && !d_paths) || (m && !d_seals))) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u || m > ((size_t)1 << 24) || n_sib > 0xFFFFFFFFu) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    return run_setincl(c, n, d_a, d_b, d_paths, d_poff, n_sib, d_ridx, m, d_seals, nullptr, d_status, d_recv, nullptr, stream ? (hipStream_t)stream : c->stream);
+}
+ZKV_EXPORT int zkv_risc0_setincl_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_image_ids, const uint8_t* d_journal_digests, const uint8_t* d_path_blob,
+                                                  const uint32_t* d_path_off, size_t n_siblings, const uint32_t* d_root_idx, size_t m,
+                                                  const uint8_t* d_root_seals, uint8_t* d_status, uint8_t* d_recv, void* stream) {
+    return setincl_dev_call(c, n, d_image_ids, d_journal_digests, d_path_blob, d_path_off, n_siblings, d_root_idx, m, d_root_seals, d_status, d_recv, stream);
+}
+// Host buffers: staged whole, one device-resident run, statuses copied back.  in_b = nullptr: integrity.  diag_out: hash only (blob_shift
+// places the path blob off its aligned base).
+static int setincl_host_call(zkv_ctx* c, size_t n, const uint8_t* in_a, const uint8_t* in_b, bool integrity, const uint8_t* path_blob, const uint32_t* path_off,
+                             const uint32_t* root_idx, size_t m, const uint8_t* seal_blob, const uint64_t* seal_off, uint8_t* status, uint8_t* recv,
+                             uint8_t* diag_out, size_t blob_shift) {
+    if (!c || c->vm != ZKV_VM_RISC0_SETINCL) return ZKV_ERR_WRONG_CTX;
+    if (n && (!in_a || (!integrity && !in_b) || !path_off || (!diag_out && (!root_idx || !status)) || (m && (!seal_blob || !seal_off)))) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u || m > ((size_t)1 << 24) || blob_shift > 31 || (m && !offsets_ok(seal_off, m))) return ZKV_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n; i++) if (path_off[i + 1] < path_off[i]) return ZKV_ERR_INVALID_ARG;
+    const uint32_t o0 = path_off[0];
+    const size_t n_sib = path_off[n] - o0;
+    if (n_sib && !path_blob) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    std::vector<uint32_t> po, sl;
+    std::vector<uint8_t> rows;
+    try {
+        po.assign(path_off, path_off + n + 1);
+        for (auto& v : po) v -= o0;
+        sl.resize(m + 1); rows.assign((size_t)ZKV_SEAL_BYTES * (m + 1), 0);
+        for (size_t j = 0; j < m; j++) {
+            const uint64_t len = seal_off[j + 1] - seal_off[j];
+            sl[j] = len > 0xFFFFFFFEu ? 0xFFFFFFFEu : (uint32_t)len;
+            memcpy(rows.data() + ZKV_SEAL_BYTES * j, seal_blob + seal_off[j], len < ZKV_SEAL_BYTES ? (size_t)len : (size_t)ZKV_SEAL_BYTES);
+        }
+    } catch (const std::bad_alloc&) { return ZKV_ERR_OOM; }
+    const size_t need[9] = {32 * n, integrity ? 0 : 32 * n, 32 * n_sib + 256 + 32, 4 * (n + 1), 4 * n, rows.size(), 4 * sl.size(), n, 4 * n};
+    for (int k = 0; k < 9; k++) if ((rc = grow(&c->mx[SI_H_A + k], &c->mx_cap[SI_H_A + k], need[k])) != ZKV_OK) return rc;
+    if (diag_out && (rc = grow(&c->mx[SI_DIAG], &c->mx_cap[SI_DIAG], 32 * n)) != ZKV_OK) return rc;
+    hipStream_t s = c->stream;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    uint8_t* d_paths = (uint8_t*)(((uintptr_t)c->mx[SI_H_PATHS] + 255u) & ~(uintptr_t)255u) + blob_shift;
+    HIP_TRY(hipMemcpyAsync(c->mx[SI_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
+    if (!integrity) HIP_TRY(hipMemcpyAsync(c->mx[SI_H_B], in_b, 32 * n, hipMemcpyHostToDevice, s));
+    if (n_sib) HIP_TRY(hipMemcpyAsync(d_paths, path_blob + 32 * (size_t)o0, 32 * n_sib, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->mx[SI_H_POFF], po.data(), 4 * (n + 1), hipMemcpyHostToDevice, s));
+    if (!diag_out) {
+        HIP_TRY(hipMemcpyAsync(c->mx[SI_H_RIDX], root_idx, 4 * n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c->mx[SI_H_SEALS], rows.data(), rows.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c->mx[SI_H_SLEN], sl.data(), 4 * sl.size(), hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));                    // the staging vectors are pageable host memory
+    rc = run_setincl(c, n, c->mx[SI_H_A], integrity ? nullptr : c->mx[SI_H_B], d_paths, (const uint32_t*)c->mx[SI_H_POFF], n_sib,
+                     diag_out ? nullptr : (const uint32_t*)c->mx[SI_H_RIDX], m, c->mx[SI_H_SEALS], (const uint32_t*)c->mx[SI_H_SLEN],
+                     diag_out ? nullptr : c->mx[SI_H_ST], diag_out ? nullptr : c->mx[SI_H_RV], diag_out ? c->mx[SI_DIAG] : nullptr, s);
+    if (rc != ZKV_OK) return rc;
+    if (diag_out) HIP_TRY(hipMemcpyAsync(diag_out, c->mx[SI_DIAG], 32 * n, hipMemcpyDeviceToHost, s));
+    else {
+        HIP_TRY(hipMemcpyAsync(status, c->mx[SI_H_ST], n, hipMemcpyDeviceToHost, s));
+        if (recv) HIP_TRY(hipMemcpyAsync(recv, c->mx[SI_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_risc0_setincl_verify_batch(zkv_ctx* c, size_t n, const uint8_t* image_ids, const uint8_t* journal_digests, const uint8_t* path_blob,
+                                              const uint32_t* path_off, const uint32_t* root_idx, size_t m, const uint8_t* root_seal_blob,
+                                              const uint64_t* root_seal_off, uint8_t* status, uint8_t* recv) {
+    return setincl_host_call(c, n, image_ids, journal_digests, false, path_blob, path_off, root_idx, m, root_seal_blob, root_seal_off, status, recv, nullptr, 0);
+}
+ZKV_EXPORT int zkv_risc0_setincl_verify_integrity_batch(zkv_ctx* c, size_t n, const uint8_t* claim_digests, const uint8_t* path_blob, const uint32_t* path_off,
+                                                        const uint32_t* root_idx, size_t m, const uint8_t* root_seal_blob, const uint64_t* root_seal_off,
+                                                        uint8_t* status, uint8_t* recv) {
+    return setincl_host_call(c, n, claim_digests, nullptr, true, path_blob, path_off, root_idx, m, root_seal_blob, root_seal_off, status, recv, nullptr, 0);
+}
+ZKV_EXPORT int zkv_diag_setincl_roots(zkv_ctx* c, size_t n, const uint8_t* image_ids, const uint8_t* journal_digests, const uint8_t* path_blob,
+                                      const uint32_t* path_off, size_t blob_shift, uint8_t* out_roots) {
+    if (n && !out_roots) return ZKV_ERR_INVALID_ARG;
+    return setincl_host_call(c, n, image_ids, journal_digests, journal_digests == nullptr, path_blob, path_off, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                             out_roots, blob_shift);
+}
+ZKV_EXPORT int zkv_risc0_setincl_last_counts(zkv_ctx* c, uint64_t out[3]) {
+    if (!c || c->vm != ZKV_VM_RISC0_SETINCL) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    out[0] = c->si_counts[0]; out[1] = c->si_counts[1]; out[2] = 0;
+    if (!c->dev_ready || !c->mx[SI_CNT]) return ZKV_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t v[2] = {0, 0};
+    HIP_TRY(hipMemcpy(v, c->mx[SI_CNT], sizeof v, hipMemcpyDeviceToHost));
+    out[2] = v[1];
+    return ZKV_OK;
+}
+
+// The on-chain form: set_selector || abi.encode(Seal{bytes32[] path; bytes rootSeal}).
+ZKV_EXPORT size_t zkv_risc0_setincl_seal_encode(const zkv_ctx* c, const uint8_t* path, size_t path_len, const uint8_t* root_seal, size_t root_seal_len,
+                                                uint8_t* out, size_t cap) {
+    if (!c || c->vm != ZKV_VM_RISC0_SETINCL || (path_len && !path) || (root_seal_len && !root_seal) || path_len > 0xFFFFFFu || root_seal_len > 0xFFFFFFFFu) return 0;
+    const size_t padded = (root_seal_len + 31) / 32 * 32, total = 4 + 32 + 64 + 32 + 32 * path_len + 32 + padded;
+    if (!out || cap < total) return total;
+    memset(out, 0, total);
+    memcpy(out, c->si_set_sel, 4);
+    uint8_t* b = out + 4;
+    host::abi_word_u32(b, 0x20);
+    host::abi_word_u32(b + 32, 0x40);
+    host::abi_word_u32(b + 64, 0x60 + 32 * path_len);
+    host::abi_word_u32(b + 96, path_len);
+    if (path_len) memcpy(b + 128, path, 32 * path_len);
+    uint8_t* r = b + 128 + 32 * path_len;
+    host::abi_word_u32(r, root_seal_len);
+    if (root_seal_len) memcpy(r + 32, root_seal, root_seal_len);
+    return total;
+}
+// a 32-byte big-endian word that fits 32 bits
+static bool setincl_word(const uint8_t* p, uint64_t* v) {
+    for (int k = 0; k < 28; k++) if (p[k]) return false;
+    *v = be32_of(p + 28);
+    return true;
+}
+ZKV_EXPORT int zkv_risc0_setincl_seal_decode(const zkv_ctx* c, const uint8_t* seal, size_t seal_len, uint8_t* status, uint8_t recv[4], size_t* path_at,
+                                             size_t* path_len, size_t* root_seal_at, size_t* root_seal_len) {
+    if (!c || c->vm != ZKV_VM_RISC0_SETINCL) return ZKV_ERR_WRONG_CTX;
+    if (!status || !path_at || !path_len || !root_seal_at || !root_seal_len || (!seal && seal_len)) return ZKV_ERR_INVALID_ARG;
+    *path_at = *path_len = *root_seal_at = *root_seal_len = 0;
+    if (recv) memset(recv, 0, 4);
+    *status = ZKV_STATUS_INVALID_PROOF_DATA;
+    if (seal_len < 4) return ZKV_OK;
+    if (memcmp(seal, c->si_set_sel, 4)) { *status = ZKV_STATUS_SELECTOR_MISMATCH; if (recv) memcpy(recv, seal, 4); return ZKV_OK; }
+    const uint8_t* b = seal + 4;
+    const uint64_t blen = seal_len - 4;
+    uint64_t w0, w1, w2, k, len;
+    if (blen < 160 || blen % 32) return ZKV_OK;                     // the shortest body: 0x20, two offsets, two length words
+    if (!setincl_word(b, &w0) || w0 != 0x20 || !setincl_word(b + 32, &w1) || w1 != 0x40 || !setincl_word(b + 96, &k)) return ZKV_OK;
+    if (k > (blen - 160) / 32) return ZKV_OK;                       // the path must leave room for the root seal's length word
+    if (!setincl_word(b + 64, &w2) || w2 != 0x60 + 32 * k) return ZKV_OK;
+    const uint8_t* r = b + 128 + 32 * k;
+    if (!setincl_word(r, &len)) return ZKV_OK;
+    const uint64_t padded = (len + 31) / 32 * 32;
+    if (blen != 160 + 32 * k + padded) return ZKV_OK;               // nothing missing, nothing trailing
+    for (uint64_t q = len; q < padded; q++) if (r[32 + q]) return ZKV_OK;    // clean padding
+    *status = ZKV_STATUS_OK;
+    *path_at = 4 + 128; *path_len = (size_t)k; *root_seal_at = (size_t)(4 + 128 + 32 * k + 32); *root_seal_len = (size_t)len;
+    return ZKV_OK;
 }
