@@ -65,7 +65,9 @@ const char* zkv_version(void);
  * signed 20-bit window: 2 x 7 windows = 2.8 GB for RISC Zero, 2 x 13 = 5.2 GB for SP1 (a mixed context: both), built in about 50 ms.
  * ZKV_GT_WINDOW_BITS=0 leaves them out (20 or unset builds them; any other value makes that call return ZKV_ERR_INVALID_ARG),
  * ZKV_GT_MAX_BYTES bounds them; a context without them (also: no room on the device) pairs (vk_x, gamma) in the Miller loop as before,
- * with the same statuses.  The build is tried once per context, by a verifying call (zkv_ctx_vk_x_batch never builds them): a context
+ * with the same statuses.  An SP1 context with tables also keeps, on the device, what the table walk makes of the last few program vkeys
+ * that repeated within a batch (2 KB; ZKV_GT_CACHE=0 leaves it out): proofs of a cached program skip that half of the walk, every other
+ * proof walks as before, the statuses are the same.  The build is tried once per context, by a verifying call (zkv_ctx_vk_x_batch never builds them): a context
  * that had no room then keeps the Miller path, and tables once built are kept until the context is destroyed -- a workspace that grows
  * later does not take their memory back, so a context meant for large batches should see one (or zkv_ctx_reserve) first. */
 zkv_ctx* zkv_risc0_ctx_new(int device);

@@ -35,6 +35,12 @@ int zkv_diag_gt_read(zkv_ctx* ctx, int signal, uint32_t window, uint32_t d, uint
  * range, a scalar too large. */
 int zkv_diag_gt_product(zkv_ctx* ctx, size_t n, const uint32_t* scalars, uint32_t* out);
 
+/* The walk-prefix cache of an SP1 context with tables (the u the walk holds after signal 0's windows, kept per program vkey):
+ * out3 = {entries that hold a value, insertions so far, entries the cache can hold}.  All 0 for a context without one (RISC Zero, no
+ * tables, ZKV_GT_CACHE=0).  Waits for the device.  zkv_diag_gt_product runs the cache's stages like a verify call: it may insert, and it
+ * reads back what the cached path computes. */
+int zkv_diag_gt_cache(zkv_ctx* ctx, uint64_t* out3);
+
 #ifdef __cplusplus
 }
 #endif

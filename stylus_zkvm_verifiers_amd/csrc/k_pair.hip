@@ -81,7 +81,7 @@ __global__ __launch_bounds__(PAIR_BLOCK, 2) void k_miller2(size_t n, const VkTab
     ZKV_STAMP(0, 1);
 }
 
-__global__ __launch_bounds__(PAIR_BLOCK, 2) void k_finalexp2(size_t n, GtTab gt, long long gt_rel, Workspace ws, uint8_t* __restrict__ status) {
+__global__ __launch_bounds__(PAIR_BLOCK, 2) void k_finalexp2(size_t n, GtTab gt, long long gt_rel, long long gt_crel, Workspace ws, uint8_t* __restrict__ status) {
     __shared__ uint32_t lds[54 * PAIR_BLOCK];             // the accumulator in resident 29-bit limbs: 6 coefficients x 9 words per lane
     ZKV_STAMP(1, 0);
     size_t i = ((size_t)blockIdx.x * PAIR_BLOCK + threadIdx.x) >> 1;
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(PAIR_BLOCK, 2) void k_finalexp2(size_t n, GtTab gt,
     const uint32_t par = threadIdx.x & 1u;
     uint32_t* wl = lds + (threadIdx.x >> 6) * (54 * ZKV_BLOCK) + (threadIdx.x & 63u);
     L9Ref acc = l9_ref(wl);
-    const GtRef g = {gt.tab != nullptr, (ptrdiff_t)gt_rel, ws.prep + 64 * ws.cap, gt.nw[0], gt.nw[1]};
+    const GtRef g = {gt.tab != nullptr, (ptrdiff_t)gt_rel, ws.prep + 64 * ws.cap, gt.nw[0], gt.nw[1], gt.cache ? ws.gtag : nullptr, (ptrdiff_t)gt_crel};
     bool one = final_exp_prog_p(ws.f, ws.fe, ws.cap, (uint32_t)(8 * par * ws.cap + i) * 4u, acc, g);
     if (!par) status[i] = one ? ST_OK : ST_VERIFICATION_FAILED;
     ZKV_STAMP(1, 1);
@@ -332,7 +332,64 @@ void launch_finalexp2(size_t n, const Workspace& ws, uint8_t* status, hipStream_
     if (!n) return;
     // the tables' place in words from the E rows (GtRef::rel); both are device allocations, 4-byte aligned
     const long long rel = gt.tab ? (long long)(((intptr_t)gt.tab - (intptr_t)ws.fe) / 4) : 0;
-    hipLaunchKernelGGL(k_finalexp2, dim3(hot_grid(n)), dim3(PAIR_BLOCK), 0, s, n, gt, rel, ws, status);
+    const long long crel = gt.cache ? (long long)(((intptr_t)gt.cache->val - (intptr_t)ws.fe) / 4) : 0;        // (an address, not a read: gt.cache is a device pointer)
+    hipLaunchKernelGGL(k_finalexp2, dim3(hot_grid(n)), dim3(PAIR_BLOCK), 0, s, n, gt, rel, crel, ws, status);
+}
+// Walk-prefix cache (zkv_gt.h), fill: ONE wavefront of lane-pair code per chunk.  Pair k takes signal 0 of sample k, the selection
+// (gt_cache_candidate) picks at most one pair, and that pair alone walks signal 0's windows from u = 1 with the window code of
+// final_exp_prog_p -- digit, entry, f12l9_mul_aw, the entry read straight from its table row -- and stores u at the cursor.  No candidate
+// (every sampled vkey distinct or cached already): the wavefront ends after the selection.
+__global__ __launch_bounds__(ZKV_BLOCK) void k_gt_cache_fill(size_t n, GtTab gt, Workspace ws) {
+    __shared__ uint32_t lds[54 * ZKV_BLOCK];
+    __shared__ uint32_t keys[GT_CACHE_SAMPLES * 8];
+    __shared__ uint32_t ok[GT_CACHE_SAMPLES];
+    const uint32_t k = threadIdx.x >> 1, par = threadIdx.x & 1u;
+    const uint32_t m = gt_cache_samples(n);
+    if (!par) {
+        const bool in = k < m;
+        const size_t i = in ? gt_cache_sample_pos(n, k) : 0;
+        ok[k] = in && (ws.flags[i] & FL_ALIVE) ? 1u : 0u;
+        for (int w = 0; w < 8; w++) keys[8 * k + w] = in ? ws.prep[(size_t)(64 + w) * ws.cap + i] : 0u;
+    }
+    __syncthreads();
+    GtCache& c = *gt.cache;
+    const unsigned long long cand = __builtin_amdgcn_ballot_w64(gt_cache_candidate(c, keys, ok, m, k));
+    if (!cand) return;
+    if (k != (uint32_t)__builtin_ctzll(cand) >> 1) return;
+    const uint32_t* key = keys + 8 * k;
+    L9Ref acc = l9_ref(lds + threadIdx.x);
+    f12m_set_one(acc);
+#pragma unroll 1
+    for (uint32_t j = 0; j < gt.nw[0]; j++) {
+        const uint32_t kw = gt_digit_word(j);
+        const int32_t dg = gt_digit_of(key[kw], kw + 1 < 8 ? key[kw + 1] : 0u, j);
+        if (dg == 0) continue;
+        SoaRW T;
+        T.p = (uint32_t*)gt.tab + gt_row_word(j); T.stride = 1;
+        T.off = gt_entry_offset((uint32_t)(dg < 0 ? -dg : dg)) + 32u * par;
+        f12l9_mul_aw(acc, T, dg < 0, true);
+    }
+    const uint32_t slot = c.cursor % GT_CACHE_ENTRIES;             // both lanes read it before the even lane moves it
+    f12m_copy(m_ref(c.val[slot] + 8 * par, 1, 16), acc);
+    if (!par) (void)gt_cache_claim(c, key);
+}
+// Tag: one proof per lane.  A dead proof (its scalar rows may be stale) gets 0.
+__global__ __launch_bounds__(256) void k_gt_cache_tag(size_t n, const GtCache* __restrict__ c, Workspace ws) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t t = 0;
+    if (ws.flags[i] & FL_ALIVE) {
+        uint32_t key[8];
+#pragma unroll
+        for (int w = 0; w < 8; w++) key[w] = ws.prep[(size_t)(64 + w) * ws.cap + i];
+        t = gt_cache_find(*c, key);
+    }
+    ws.gtag[i] = (uint8_t)t;
+}
+void launch_gt_cache(size_t n, const Workspace& ws, hipStream_t s, const GtTab& gt) {
+    if (!n || !gt.cache) return;
+    hipLaunchKernelGGL(k_gt_cache_fill, dim3(1), dim3(ZKV_BLOCK), 0, s, n, gt, ws);
+    hipLaunchKernelGGL(k_gt_cache_tag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, gt.cache, ws);
 }
 // TEST ONLY (zkv_diag_gt_product): every proof alive with the Miller value 1.  k_finalexp2 then exponentiates 1 to 1, walks the tables
 // over the scalars the caller put in ws.prep, and the walk's COPY TMP <- ACC leaves its u (M = u / conj(u), zkv_gt.h) in the slot TMP.

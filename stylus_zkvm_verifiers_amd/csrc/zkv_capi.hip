@@ -76,6 +76,7 @@ struct zkv_ctx {
     // fixed-base GT tables of the (vk_x, gamma) pairing (zkv_gt.h): built the first time a call can run lane-pair chunks (gt_maybe_build);
     // gt.tab == nullptr: none (ZKV_GT_WINDOW_BITS=0, no room, another kind of context) -- the Miller loop takes the pair
     uint32_t *d_gt = nullptr, *d_gt_const = nullptr;
+    GtCache* d_gt_cache = nullptr;                               // walk-prefix cache of an SP1 context with tables (zkv_gt.h); ZKV_GT_CACHE=0: none
     GtTab gt = GT_NONE;
     bool gt_tried = false;
     size_t gt_bytes = 0; float gt_build_ms = 0;
@@ -284,7 +285,7 @@ static size_t tail_of_chunk(size_t n, bool* beside) {
 // base advanced by `off` elements addresses them as proofs 0, 1, ...
 static Workspace ws_from(const Workspace& ws, size_t off) {
     Workspace w = ws;
-    w.prep += off; w.norm += off; w.f += off; w.fe += off; w.flags += off; w.g2bad += off;
+    w.prep += off; w.norm += off; w.f += off; w.fe += off; w.flags += off; w.g2bad += off; if (w.gtag) w.gtag += off;
     return w;
 }
 // Chunks of at most this many proofs run the Miller loop and the final exponentiation with ONE PROOF PER WAVEFRONT (k_miller_w64 /
@@ -350,7 +351,7 @@ static void ctx_free_device(zkv_ctx* c) {
     (void)hipSetDevice(c->device);
     c->m16 = {nullptr, {0, 0, 0, 0, 0}};
     c->gt = GT_NONE; c->gt_tried = false; c->gt_bytes = 0;
-    void** ptrs[] = {(void**)&c->d_tab, (void**)&c->d_msm16, (void**)&c->d_gt, (void**)&c->d_gt_const, (void**)&c->ws.prep, (void**)&c->ws.norm, (void**)&c->ws.f, (void**)&c->ws.fe, (void**)&c->ws.flags,
+    void** ptrs[] = {(void**)&c->d_tab, (void**)&c->d_msm16, (void**)&c->d_gt, (void**)&c->d_gt_const, (void**)&c->d_gt_cache, (void**)&c->ws.gtag, (void**)&c->ws.prep, (void**)&c->ws.norm, (void**)&c->ws.f, (void**)&c->ws.fe, (void**)&c->ws.flags,
                      (void**)&c->ws.g2bad, (void**)&c->d_blob, (void**)&c->d_a, (void**)&c->d_b, (void**)&c->d_pv, (void**)&c->d_status,
                      (void**)&c->d_recv, (void**)&c->d_off, (void**)&c->d_pvoff, (void**)&c->d_cd[0], (void**)&c->d_cd[1], (void**)&c->d_kind,
                      (void**)&c->d_cdoff[0], (void**)&c->d_cdoff[1], (void**)&c->d_len, (void**)&c->d_pvlen, (void**)&c->d_st_all,
@@ -560,7 +561,7 @@ static int ctx_reserve(zkv_ctx* c, size_t want) {
     while (cap < want) cap <<= 1;
     if (cap > limit) cap = limit;
     void** bufs[] = {(void**)&c->ws.prep, (void**)&c->ws.norm, (void**)&c->ws.f, (void**)&c->ws.fe, (void**)&c->ws.flags, (void**)&c->ws.g2bad,
-                     (void**)&c->d_a, (void**)&c->d_b, (void**)&c->d_status, (void**)&c->d_recv, (void**)&c->d_off, (void**)&c->d_pvoff,
+                     (void**)&c->ws.gtag, (void**)&c->d_a, (void**)&c->d_b, (void**)&c->d_status, (void**)&c->d_recv, (void**)&c->d_off, (void**)&c->d_pvoff,
                      (void**)&c->d_inst_idx, (void**)&c->d_len, (void**)&c->d_pvlen, (void**)&c->d_kind, (void**)&c->d_cdoff[0], (void**)&c->d_cdoff[1],
                      (void**)&c->d_plonk_tab};
     for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
@@ -570,6 +571,7 @@ static int ctx_reserve(zkv_ctx* c, size_t want) {
         hipMalloc(&c->ws.f, sizeof(uint32_t) * WS_F_WORDS * cap) != hipSuccess ||
         hipMalloc(&c->ws.fe, sizeof(uint32_t) * WS_FE_WORDS * cap) != hipSuccess ||
         hipMalloc(&c->ws.flags, sizeof(uint32_t) * cap) != hipSuccess || hipMalloc(&c->ws.g2bad, sizeof(uint32_t) * cap) != hipSuccess ||
+        hipMalloc(&c->ws.gtag, cap) != hipSuccess ||
         hipMalloc(&c->d_a, 32 * cap) != hipSuccess || hipMalloc(&c->d_b, 32 * cap) != hipSuccess ||
         hipMalloc(&c->d_status, cap) != hipSuccess || hipMalloc(&c->d_recv, 4 * cap) != hipSuccess ||
         hipMalloc(&c->d_off, sizeof(uint64_t) * (cap + 1)) != hipSuccess ||
@@ -595,6 +597,11 @@ static int gt_window_bits() {
     const char* e = getenv("ZKV_GT_WINDOW_BITS");
     if (!e || !strcmp(e, "20")) return (int)GT_WINDOW_BITS;
     return !strcmp(e, "0") ? 0 : -1;
+}
+// ZKV_GT_CACHE: "0" leaves an SP1 context without the walk-prefix cache (zkv_gt.h), anything else or unset keeps it.
+static bool gt_cache_wanted() {
+    const char* e = getenv("ZKV_GT_CACHE");
+    return !e || strcmp(e, "0") != 0;
 }
 static size_t gt_max_bytes() {
     const char* e = getenv("ZKV_GT_MAX_BYTES");
@@ -646,8 +653,16 @@ static int gt_maybe_build(zkv_ctx* c, size_t n) {
         c->d_gt = c->d_gt_const = nullptr;
         return ZKV_OK;
     }
-    c->gt = GtTab{c->d_gt, c->d_gt_const, {nw0, nw1}};
+    c->gt = GtTab{c->d_gt, c->d_gt_const, {nw0, nw1}, nullptr};
     c->gt_bytes = bytes;
+    // the walk-prefix cache: SP1 only (signal 0 is the program vkey).  No room for its 2 KB: the context walks every window, same results.
+    if (c->vm == ZKV_VM_SP1 && gt_cache_wanted()) {
+        GtCache head = {};
+        head.entries = GT_CACHE_ENTRIES;
+        if (hipMalloc(&c->d_gt_cache, sizeof(GtCache)) == hipSuccess && hipMemset(c->d_gt_cache, 0, sizeof(GtCache)) == hipSuccess &&
+            hipMemcpy(c->d_gt_cache, &head, 4 * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess) c->gt.cache = c->d_gt_cache;
+        else { (void)hipGetLastError(); if (c->d_gt_cache) (void)hipFree(c->d_gt_cache); c->d_gt_cache = nullptr; }
+    }
     return ZKV_OK;
 }
 // device set-up + buffers for a batch of n
@@ -889,6 +904,7 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
         if (beside) { (void)hipEventRecord(c->ev_fork, s); (void)hipStreamWaitEvent(c->side, c->ev_fork, 0); }
         launch_g2chk2(tail, wt, a.status + head, st);
         if (timed) (void)hipEventRecord(c->ev[3], s);
+        if (gt) launch_gt_cache(head, c->ws, s, c->gt);
         launch_miller2(head, c->d_tab, c->ws, a.status, s, c->gt.mconst);
         const int tl = miller_lanes(c, tail);                // (automatic: a fixed mapping takes no tail split)
         launch_miller_lanes(tl, tail, c->d_tab, wt, a.status + head, st);
@@ -922,7 +938,7 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
     if (timed) (void)hipEventRecord(c->ev[2], s);
     if (wide && !fork) launch_g2chk2(a.n, c->ws, a.status, s);
     if (timed) (void)hipEventRecord(c->ev[3], s);
-    if (gt) launch_miller2(a.n, c->d_tab, c->ws, a.status, s, c->gt.mconst);
+    if (gt) { launch_gt_cache(a.n, c->ws, s, c->gt); launch_miller2(a.n, c->d_tab, c->ws, a.status, s, c->gt.mconst); }
     else launch_miller_lanes(lanes, a.n, c->d_tab, c->ws, a.status, s);
     if (timed) (void)hipEventRecord(c->ev[4], s);
     if (fork) (void)hipStreamWaitEvent(s, c->ev_join, 0);     // the final exponentiation reads the verdict of the subgroup check
@@ -3510,6 +3526,19 @@ ZKV_EXPORT int zkv_diag_gt_read(zkv_ctx* c, int signal, uint32_t window, uint32_
     if (!ok) { (void)hipGetLastError(); return ZKV_ERR_HIP; }
     return ZKV_OK;
 }
+// cache: {valid entries, insertions so far, entries the cache holds} of the walk-prefix cache; all 0 for a context without one.
+ZKV_EXPORT int zkv_diag_gt_cache(zkv_ctx* c, uint64_t* out3) {
+    if (!c || !out3) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!c->gt.cache) return ZKV_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return ZKV_ERR_HIP;
+    uint32_t head[4 + GT_CACHE_ENTRIES];
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(head, c->gt.cache, sizeof head, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZKV_ERR_HIP; }
+    for (uint32_t e = 0; e < GT_CACHE_ENTRIES; e++) out3[0] += head[4 + e] ? 1 : 0;
+    out3[1] = head[1]; out3[2] = head[2];
+    return ZKV_OK;
+}
 // product: what k_finalexp2's table walk makes of given scalars.  The n proofs get the Miller value 1 (k_gt_diag_seed), so the kernel's
 // program exponentiates 1 to 1, the walk carries u with M = u / conj(u) over the selected rows and leaves u in the slot TMP (slot 8 of
 // ws.fe); M is formed from it (k_gt_diag_ratio, one inversion per proof) and read back.  The kernel and its launch are the ones the verify
@@ -3536,6 +3565,7 @@ ZKV_EXPORT int zkv_diag_gt_product(zkv_ctx* c, size_t n, const uint32_t* scalars
     bool ok = hipMemcpy2DAsync(c->ws.prep + 64 * cap, cap * 4, rows.data(), n * 4, n * 4, SW, hipMemcpyHostToDevice, c->stream) == hipSuccess;
     if (ok) {
         launch_gt_diag_seed(n, c->ws, c->stream);
+        launch_gt_cache(n, c->ws, c->stream, c->gt);               // the stages of a verify call: the cached path is what is read back
         launch_finalexp2(n, c->ws, d_st, c->stream, c->gt);
         launch_gt_diag_ratio(n, c->ws.fe + (size_t)(96 * 6) * cap, cap, d_m, d_m + (size_t)GT_ENTRY_WORDS * n, c->stream);
         ok = hipGetLastError() == hipSuccess &&

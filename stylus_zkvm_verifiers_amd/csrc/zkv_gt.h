@@ -67,8 +67,62 @@ ZKV_GT_HD uint32_t gt_entry_offset(uint32_t m) { return (m - 1u) * (GT_ENTRY_WOR
 // First word of window `row`'s sub-table (rows: signal 0's windows, then signal 1's).
 ZKV_GT_HD size_t gt_row_word(uint32_t row) { return (size_t)row * GT_ROW_ENTRIES * GT_ENTRY_WORDS; }
 
+// WALK-PREFIX CACHE (SP1 contexts only).  Signal 0 of an SP1 proof is the program vkey, which a deployment repeats from proof to proof, so
+// the u the walk holds after signal 0's windows (starting from u = 1) is the same Fp12 value for every proof of a program.  A context keeps
+// GT_CACHE_ENTRIES of them on the device, keyed by the eight words of signal 0: k_gt_cache_fill inserts at most one per chunk, k_gt_cache_tag
+// writes one byte per proof (0: miss, 1 + slot: hit), and a hit lane of k_finalexp2 starts its walk from the stored u with signal 0's digits
+// taken as 0 (final_exp_prog_p).  Signal 1 (the hash of the public values) differs for every proof in real use and is never cached; RISC
+// Zero's signals are halves of a claim digest, and its contexts have no cache.
+// The selection below is plain C++ and is what the fill kernel runs: up to GT_CACHE_SAMPLES proofs of a chunk are sampled at evenly spread
+// positions; a sample is a candidate if it is usable (its proof alive, i.e. its scalar passed PREP's range check), its key is not cached
+// and the same key occurs in another usable sample; the lowest-indexed candidate is inserted at the round-robin cursor.  A chunk whose
+// vkeys are all distinct inserts nothing.
+constexpr uint32_t GT_CACHE_ENTRIES = 4;                            // a tag byte holds 1 + slot
+constexpr uint32_t GT_CACHE_SAMPLES = 32;                           // one per lane pair of the fill kernel's wavefront
+struct GtCache {
+    uint32_t cursor, fills, entries, pad;                           // next slot to fill, insertions so far, GT_CACHE_ENTRIES
+    uint32_t valid[GT_CACHE_ENTRIES];
+    uint32_t key[GT_CACHE_ENTRIES][8];                              // signal 0, least significant word first
+    uint32_t val[GT_CACHE_ENTRIES][GT_ENTRY_WORDS];                 // u = N + D w in the packed layout of the final exponentiation's slots
+};
+// Samples of a chunk of n proofs and the proof sample k (< gt_cache_samples(n)) looks at: chunks under 32 proofs sample each proof once.
+ZKV_GT_HD uint32_t gt_cache_samples(size_t n) { return n < GT_CACHE_SAMPLES ? (uint32_t)n : GT_CACHE_SAMPLES; }
+ZKV_GT_HD size_t gt_cache_sample_pos(size_t n, uint32_t k) { return (size_t)(((unsigned long long)k * n) / gt_cache_samples(n)); }
+ZKV_GT_HD bool gt_key_eq(const uint32_t* a, const uint32_t* b) {
+    uint32_t d = 0;
+    for (int k = 0; k < 8; k++) d |= a[k] ^ b[k];
+    return d == 0;
+}
+// 1 + the slot that holds `key`, 0 if none does (the tag byte)
+ZKV_GT_HD uint32_t gt_cache_find(const GtCache& c, const uint32_t* key) {
+    uint32_t t = 0;
+    for (uint32_t e = GT_CACHE_ENTRIES; e-- > 0;) if (c.valid[e] && gt_key_eq(c.key[e], key)) t = e + 1u;
+    return t;
+}
+// keys: m x 8 words, ok[k] != 0: sample k is usable
+ZKV_GT_HD bool gt_cache_candidate(const GtCache& c, const uint32_t* keys, const uint32_t* ok, uint32_t m, uint32_t k) {
+    if (k >= m || !ok[k] || gt_cache_find(c, keys + 8 * k)) return false;
+    for (uint32_t o = 0; o < m; o++) if (o != k && ok[o] && gt_key_eq(keys + 8 * k, keys + 8 * o)) return true;
+    return false;
+}
+// the sample to insert, -1: none
+ZKV_GT_HD int gt_cache_select(const GtCache& c, const uint32_t* keys, const uint32_t* ok, uint32_t m) {
+    for (uint32_t k = 0; k < m; k++) if (gt_cache_candidate(c, keys, ok, m, k)) return (int)k;
+    return -1;
+}
+// Takes the slot at the cursor for `key` (evicting what it held) and returns it; the caller stores the value there.
+ZKV_GT_HD uint32_t gt_cache_claim(GtCache& c, const uint32_t* key) {
+    const uint32_t slot = c.cursor % GT_CACHE_ENTRIES;
+    for (int k = 0; k < 8; k++) c.key[slot][k] = key[k];
+    c.valid[slot] = 1u;
+    c.cursor = (slot + 1u) % GT_CACHE_ENTRIES;
+    c.fills += 1u;
+    return slot;
+}
+
 // What the kernels get: the tables (nullptr: none, the Miller loop takes the pair), the folded Miller constant
-// ML(alpha, beta) * ML(base, gamma) (96 words, the layout of VkTables::f_alpha_beta) and the window counts of the two signals.
-struct GtTab { const uint32_t* tab; const uint32_t* mconst; uint32_t nw[GT_MAX_SIG]; };
+// ML(alpha, beta) * ML(base, gamma) (96 words, the layout of VkTables::f_alpha_beta), the window counts of the two signals and the
+// walk-prefix cache (nullptr: none).
+struct GtTab { const uint32_t* tab; const uint32_t* mconst; uint32_t nw[GT_MAX_SIG]; GtCache* cache; };
 
 }  // namespace zkv

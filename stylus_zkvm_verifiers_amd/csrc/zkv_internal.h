@@ -17,6 +17,7 @@ struct Workspace {
     uint32_t* prep; uint32_t* norm; uint32_t* f; uint32_t* fe; uint32_t* flags;
     uint32_t* g2bad;            // 1 = B failed the subgroup check (own word: the check may run beside the MSM, which owns `flags`)
     size_t cap;
+    uint8_t* gtag;              // walk-prefix cache (zkv_gt.h): one tag byte per proof, written by k_gt_cache_tag (nullptr in the secondary workspaces)
 };
 
 constexpr int ZKV_BLOCK = 64;       // one wavefront per workgroup: one proof per lane, no cross-lane traffic
@@ -113,6 +114,9 @@ void launch_g2chk2(size_t n, const Workspace& ws, uint8_t* status, hipStream_t s
 constexpr GtTab GT_NONE = {nullptr, nullptr, {0, 0}};
 void launch_miller2(size_t n, const VkTables* d_tab, const Workspace& ws, uint8_t* status, hipStream_t s, const uint32_t* mconst = nullptr);
 void launch_finalexp2(size_t n, const Workspace& ws, uint8_t* status, hipStream_t s, const GtTab& gt = GT_NONE);
+// walk-prefix cache (zkv_gt.h; gt.cache != nullptr): at most one insertion from the chunk's sampled proofs, then the chunk's tag bytes
+// (ws.gtag).  Both read the scalar rows and flags PREP wrote and come before launch_finalexp2 on the same stream.
+void launch_gt_cache(size_t n, const Workspace& ws, hipStream_t s, const GtTab& gt);
 // set-up of the tables (k_gt.hip): the window bases G_i^(2^(20 j)) and the folded constant (one launch, scratch: GT_SETUP_SCRATCH_WORDS
 // words), then level L = 1 .. 19 fills entries d = 2^L .. 2^(L+1) - 1 (L = 19: d = 2^19) of every row from entries d / 2
 constexpr size_t GT_SETUP_SCRATCH_WORDS = 3 * 12 * 96;

@@ -563,7 +563,7 @@ ZKV_HD SoaRW fe_slot(int s, uint32_t* fbase, uint32_t* ebase, size_t cap, uint32
 // runs as generated.  Otherwise the walk REPLACES the program's last two entries (COPY TMP <- ACC; ISONE TMP).  ACC then holds FE, the
 // exponentiated value of the other pairs, and the check FE * M == 1 with M = prod T[|digit|]^(sign digit) is made on torus-compressed
 // entries: the walk carries u = N + D w with M = u / conj(u) (zkv_gt.h) and tests FE * u == conj(u):
-//     COPY Y4 <- ACC (Y4 is dead by then);   ACC <- 1;
+//     COPY Y4 <- ACC (Y4 is dead by then);   ACC <- 1   (or the cached u of the proof's signal 0, see GtRef::tag);
 //     per window of each signal:   TMP(0..2) <- a of T[|digit|];   ACC <- ACC * (sign(digit) a + w)      (f12l9_mul_aw: two Fp6 products)
 //     COPY TMP <- ACC;   ACC <- ACC * Y4;   EQCONJ: ACC == conj(TMP)
 // A lane whose digit is 0 fetches nothing and keeps its ACC; a window in which no lane of the wavefront has a digit skips both entries.  TMP
@@ -579,7 +579,11 @@ ZKV_HD SoaRW fe_slot(int s, uint32_t* fbase, uint32_t* ebase, size_t cap, uint32
 // below, then compile k_pair.hip.  Go back to the pointer when a later compiler takes that form.
 // The scalar words are those the PREP stage wrote (rows 64 .. 79 of ws.prep): no stage between PREP and k_finalexp2 may write them (k_msm
 // only reads them), and every window recomputes its digit from two of them (stateless recoding, gt_digit_of) instead of reading a stored one.
-struct GtRef { bool on; ptrdiff_t rel; const uint32_t* sc; uint32_t nw0, nw1; };
+// Walk-prefix cache (zkv_gt.h; SP1 contexts): tag != nullptr is the chunk's row of tag bytes (k_gt_cache_tag: 0 miss, 1 + slot hit) and crel
+// the place of GtCache::val, in words from ebase like rel.  ACC <- 1 then becomes ACC <- the slot's u in a hit lane, and a hit lane's digits
+// of signal 0 are 0: it fetches and stores nothing in those windows, and a window in which every lane with a digit is a hit lane is skipped.
+// The stored u is what the lane's own walk over signal 0 would have left (same factors, same order, from u = 1), so the rest runs as before.
+struct GtRef { bool on; ptrdiff_t rel; const uint32_t* sc; uint32_t nw0, nw1; const uint8_t* tag; ptrdiff_t crel; };
 // What the walk assumes of the generated program (gen_constants.py): it ends in COPY TMP <- ACC; ISONE TMP, and TMP is slot 8.
 constexpr uint32_t FE_PROG_TAIL_CHECK[ZKV_FE_PROG_LEN] = ZKV_FE_PROG;
 static_assert(FE_PROG_TAIL_CHECK[ZKV_FE_PROG_LEN - 2] == (0u | 8u << 8 | 0u << 16) && (FE_PROG_TAIL_CHECK[ZKV_FE_PROG_LEN - 1] & 0xffffu) == (7u | 8u << 8),
@@ -591,7 +595,7 @@ ZKV_HD bool zkv_wave_any(bool v) {
     return v;
 #endif
 }
-ZKV_HD bool final_exp_prog_p(uint32_t* fbase, uint32_t* ebase, size_t cap, uint32_t off, L9Ref acc, const GtRef gt = GtRef{false, 0, nullptr, 0, 0}) {
+ZKV_HD bool final_exp_prog_p(uint32_t* fbase, uint32_t* ebase, size_t cap, uint32_t off, L9Ref acc, const GtRef gt = GtRef{false, 0, nullptr, 0, 0, nullptr, 0}) {
     const uint32_t PROG[ZKV_FE_PROG_LEN] = ZKV_FE_PROG;
     // the walk's entries: COPY Y4 <- ACC; SETONE ACC | GTLOAD; MULAW | COPY TMP <- ACC; MUL ACC <- ACC * Y4; EQCONJ ACC, TMP
     const uint32_t GT_PROG[7] = {0u | 5u << 8, 10u, 8u, 9u, 0u | 8u << 8, 3u | 5u << 24, 11u | 8u << 8};
@@ -618,6 +622,7 @@ ZKV_HD bool final_exp_prog_p(uint32_t* fbase, uint32_t* ebase, size_t cap, uint3
             const uint32_t lo = *(const uint32_t*)((const char*)(gt.sc + (size_t)(8u * sig + k) * cap) + i4);
             const uint32_t hi = k + 1 < 8 ? *(const uint32_t*)((const char*)(gt.sc + (size_t)(8u * sig + k + 1) * cap) + i4) : 0u;
             dg = gt_digit_of(lo, hi, j);
+            if (gt.tag && !sig && gt.tag[i4 >> 2]) dg = 0;          // a hit: signal 0's windows are in the u this lane started from
             if (!zkv_wave_any(dg != 0)) continue;
         }
         if (op == 6) { ZKV_MARK("begin cyclo"); f12l9_cyclo_sqr(acc); ZKV_MARK("end cyclo"); }
@@ -633,7 +638,18 @@ ZKV_HD bool final_exp_prog_p(uint32_t* fbase, uint32_t* ebase, size_t cap, uint3
                 for (int k = 0; k < 3; k++) m_st_f2(D, k, m_ld_f2(T, k));
             }
         }
-        else if (op == 10) f12m_set_one(acc);
+        else if (op == 10) {
+            const uint32_t t = gt.tag ? gt.tag[(off - 32u * zkv_parity() * (uint32_t)cap) >> 2] : 0u;
+            if (t) {                                       // this lane's half of the cached u (a slot's 384 bytes, like a table entry's)
+                SoaRW C;
+                C.p = ebase + gt.crel; C.stride = 1;
+                C.off = (t - 1u) * (GT_ENTRY_WORDS * 4u) + 32u * zkv_parity();
+                f12m_copy(acc, C);
+            }
+            else f12m_set_one(acc);
+            // every lane of the wavefront starts from a cached u: no digit is left in signal 0's windows, go on with signal 1's
+            if (gt.tag && !zkv_wave_any(t == 0u)) pc += 2 * (int)gt.nw0;
+        }
         else if (op == 11) one = f12m_eq_conj(acc, fe_slot(d, fbase, ebase, cap, off));
         else if (op == 0 && d == 0) f12m_copy(acc, fe_slot(a, fbase, ebase, cap, off));
         else if (op == 0 && a == 0) f12m_copy(fe_slot(d, fbase, ebase, cap, off), acc);

@@ -14,6 +14,7 @@ SYMBOLS = {
     'zkv_diag_gt_info': (C.c_int, [C.c_void_p, C.c_void_p]),
     'zkv_diag_gt_read': (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]),
     'zkv_diag_gt_product': (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    'zkv_diag_gt_cache': (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _bound = None
@@ -36,6 +37,13 @@ def info(handle):
     out = np.zeros(6, dtype=np.uint64)
     _lib.check(lib().zkv_diag_gt_info(handle, out.ctypes.data), 'zkv_diag_gt_info')
     return dict(built=bool(out[0]), windows=(int(out[1]), int(out[2])), bytes=int(out[3]), build_ms=int(out[4]) / 1000.0, tried=bool(out[5]))
+
+
+def cache(handle):
+    """dict(valid, fills, entries) of the walk-prefix cache of the context `handle`; all 0 for a context without one."""
+    out = np.zeros(3, dtype=np.uint64)
+    _lib.check(lib().zkv_diag_gt_cache(handle, out.ctypes.data), 'zkv_diag_gt_cache')
+    return dict(valid=int(out[0]), fills=int(out[1]), entries=int(out[2]))
 
 
 def _coeffs(w):
