@@ -1,0 +1,200 @@
+// RISC Zero router (include/zkv_risc0_router.h): every seal of a batch goes to the route -- a built-in-key
+// verifier or a verifier with a caller's key -- whose 4-byte selector begins it, as RISC Zero's on-chain router forwards `verify` and
+// `verifyIntegrity`.  No reference counterpart (parity unpinned); the routes' own statuses are their verifiers' ones.
+//
+// Same shape as the SP1 gateway's demultiplexer (k_gateway.hip), with up to 32 selectors and two groups of routes:
+//   k_rzrouter_count   per 256-seal block: seals of the built-in group (all built-in routes together), per keyed route, unknown, short;
+//                      and the seals of every built-in route, added to one counter per route (the call's per-route totals)
+//   k_gateway_scan     (k_gateway.hip, same column count) exclusive scan of every column over the blocks, totals
+//   (the host reads the totals back once and lays the slots out: the built-in group first, then the keyed routes padded as a key set)
+//   k_rzrouter_place   stable partition: slot of every routed seal; short and unknown seals are answered in place.  A seal of the
+//                      built-in group also gets the instance it matched -- the row the verifier-set pipeline takes from its caller
+//   k_rzrouter_gather  one wavefront per seal: first min(len, 260) seal bytes and the two 32-byte inputs to the slot's compact record
+//   k_rzrouter_prep    the keyed group's PREP, one slot per lane (zkv_rzrouter_prep.h), in front of the key sets' stages
+// The built-in group then runs the verifier set's own pipeline on its compact records, the statuses come back through k_mixed_return.
+#include "zkv_internal.h"
+#include "zkv_bytes.h"
+#include "zkv_rzrouter_prep.h"
+
+namespace zkv {
+
+static_assert(RZR_COLS == GW_COLS, "k_gateway_scan scans GW_COLS columns");
+static_assert(RZR_MAX_KEYED == GW_MAX_ROUTES, "RzrChunk::start holds one first slot per keyed route");
+__global__ void k_gateway_scan(uint32_t blocks, uint32_t* __restrict__ cnt, uint32_t* __restrict__ totals);      // k_gateway.hip
+
+constexpr int RZR_BLOCK = 256;
+constexpr int RZR_ROUTED = RZR_COL_KEYED0 + RZR_MAX_KEYED;      // columns that take slots
+
+// Seal i as (start, length); false: the offsets run backwards or past seal_bytes, the seal is never read.
+__device__ __forceinline__ bool rzr_span(const RzrArgs& a, size_t i, uint64_t* start, uint64_t* len) {
+    if (!a.seal_off) { *start = (uint64_t)i * a.stride; *len = a.stride; return true; }
+    const uint64_t s = a.seal_off[i], e = a.seal_off[i + 1];
+    *start = s; *len = e - s;
+    return s <= e && e <= a.seal_bytes;
+}
+// Column of seal i (zkv_rzrouter_prep.h), *sel = the selector read (0 when short), *inst = the built-in route it matched.  The selector is
+// one dword load when every seal starts 4-byte aligned (a wave-uniform test: fixed stride from an aligned base), byte loads otherwise: a
+// ragged blob has no alignment.  Only these 4 bytes of a seal are read here, so the seals are not staged in LDS; the gather and the two
+// PREP kernels read whole seals, coalesced.
+__device__ __forceinline__ int rzr_class(const RzrArgs& a, size_t i, uint32_t* sel, uint32_t* inst) {
+    *sel = 0; *inst = 0;
+    uint64_t s, len;
+    if (!rzr_span(a, i, &s, &len) || len < 4) return RZR_COL_SHORT;
+    const uint8_t* p = a.seals + s;
+    uint32_t v;
+    if (!a.seal_off && !(((uintptr_t)a.seals | a.stride) & 3u)) v = __builtin_bswap32(*(const uint32_t*)p);
+    else v = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+    *sel = v;
+    return rzrouter_column(a.sel, a.n_builtin, a.n_keyed, v, inst);
+}
+
+__global__ __launch_bounds__(RZR_BLOCK) void k_rzrouter_count(RzrArgs a) {
+    __shared__ uint32_t wc[RZR_COLS][RZR_BLOCK / 64];
+    const size_t i = (size_t)blockIdx.x * RZR_BLOCK + threadIdx.x;
+    uint32_t sel = 0, inst = 0;
+    const int c = i < a.n ? rzr_class(a, i, &sel, &inst) : -1;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < RZR_COLS; k++) {
+        const uint64_t m = __ballot(c == k);
+        if (lane == 0) wc[k][wave] = (uint32_t)__popcll(m);
+    }
+    // per built-in route: one atomic per wavefront and route that has seals (the slots do not depend on these, only the reported counts)
+#pragma unroll 1
+    for (uint32_t r = 0; r < a.n_builtin; r++) {
+        const uint64_t m = __ballot(c == RZR_COL_BUILTIN && inst == r);
+        if (lane == 0 && m) atomicAdd(&a.inst_tot[r], (uint32_t)__popcll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x < RZR_COLS) {
+        uint32_t t = 0;
+        for (int w = 0; w < RZR_BLOCK / 64; w++) t += wc[threadIdx.x][w];
+        a.cnt[(size_t)blockIdx.x * RZR_COLS + threadIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(RZR_BLOCK) void k_rzrouter_place(RzrArgs a) {
+    __shared__ uint32_t wc[RZR_ROUTED][RZR_BLOCK / 64];
+    const size_t i = (size_t)blockIdx.x * RZR_BLOCK + threadIdx.x;
+    uint32_t sel = 0, inst = 0;
+    const int c = i < a.n ? rzr_class(a, i, &sel, &inst) : -1;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    uint64_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < RZR_ROUTED; k++) {
+        const uint64_t m = __ballot(c == k);
+        if (c == k) mine = m;
+        if (lane == 0) wc[k][wave] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (c < 0) return;
+    if (c >= RZR_ROUTED) {                                          // no verifier to ask: answered here, no slot
+        a.pos[i] = GW_NONE;
+        a.status[i] = c == RZR_COL_SHORT ? 4 : 8;                   // ZKV_STATUS_INVALID_PROOF_DATA, ZKV_STATUS_ROUTE_NOT_FOUND
+        if (a.recv) {
+            a.recv[4 * i] = (uint8_t)(sel >> 24); a.recv[4 * i + 1] = (uint8_t)(sel >> 16);
+            a.recv[4 * i + 2] = (uint8_t)(sel >> 8); a.recv[4 * i + 3] = (uint8_t)sel;
+        }
+        return;
+    }
+    uint32_t r = (uint32_t)__popcll(mine & below);
+    for (uint32_t w = 0; w < wave; w++) r += wc[c][w];
+    const uint32_t slot = a.start[c] + a.cnt[(size_t)blockIdx.x * RZR_COLS + c] + r;
+    a.pos[i] = slot;
+    a.idx[slot] = (uint32_t)i;
+    uint64_t at, len;
+    rzr_span(a, i, &at, &len);
+    a.c_len[slot] = len > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)len;
+    if (c == RZR_COL_BUILTIN) a.c_inst[slot] = inst;
+}
+
+// One wavefront per seal (four per workgroup): 65 record words, then 8 words of in_a and (verify) 8 of in_b.
+__global__ __launch_bounds__(RZR_BLOCK) void k_rzrouter_gather(RzrArgs a) {
+    const size_t i = (size_t)blockIdx.x * (RZR_BLOCK / 64) + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (i >= a.n) return;
+    const uint32_t slot = a.pos[i];
+    if (slot == GW_NONE) return;
+    uint32_t* dst = (uint32_t*)(a.c_seals + (uint64_t)slot * 260);
+    uint64_t at, len;
+    rzr_span(a, i, &at, &len);
+    const uint8_t* src = a.seals + at;
+    if (len > 260) len = 260;
+    for (uint32_t w = lane; w < 65; w += 64) {
+        const uint64_t o = 4ull * w;
+        dst[w] = o < len ? gw_ld4(src + o, len - o) : 0u;
+    }
+    if (lane < 8) ((uint32_t*)a.c_a)[(size_t)slot * 8 + lane] = gw_ld4(a.in_a + 32 * i + 4 * lane, 4);
+    else if (lane < 16 && a.in_b) ((uint32_t*)a.c_b)[(size_t)slot * 8 + (lane - 8)] = gw_ld4(a.in_b + 32 * i + 4 * (lane - 8), 4);
+}
+
+void launch_rzrouter_count(const RzrArgs& a, hipStream_t s) {
+    if (!a.n) return;
+    const unsigned blocks = (unsigned)((a.n + RZR_BLOCK - 1) / RZR_BLOCK);
+    hipLaunchKernelGGL(k_rzrouter_count, dim3(blocks), dim3(RZR_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(k_gateway_scan, dim3(1), dim3(1024), 0, s, blocks, a.cnt, a.totals);
+}
+void launch_rzrouter_place(const RzrArgs& a, hipStream_t s) {
+    if (!a.n) return;
+    const unsigned blocks = (unsigned)((a.n + RZR_BLOCK - 1) / RZR_BLOCK);
+    hipLaunchKernelGGL(k_rzrouter_place, dim3(blocks), dim3(RZR_BLOCK), 0, s, a);
+    const size_t per = RZR_BLOCK / 64;
+    hipLaunchKernelGGL(k_rzrouter_gather, dim3((unsigned)((a.n + per - 1) / per)), dim3(RZR_BLOCK), 0, s, a);
+}
+
+// Keyed group.  Records are 260-byte rows from a 4-byte aligned base (the router's own allocation; the built-in group's records before
+// the group's are a multiple of 4 bytes), so the 64 rows of a wavefront are 16,640 contiguous bytes: copied to LDS with coalesced dword
+// loads, every lane then reads its own 65 words (row stride 65 dwords: conflict-free), as k_prep_risc0 stages fixed-stride seals.  The
+// address test is wave-uniform; a base that fails it is read byte by byte.
+__global__ __launch_bounds__(ZKV_BLOCK) void k_rzrouter_prep(RzrChunk c, Risc0Consts kc, Workspace ws) {
+    __shared__ uint32_t lds[ZKV_BLOCK * 65];
+    const size_t b0 = (size_t)blockIdx.x * ZKV_BLOCK;
+    const uint8_t* rows = c.recs + (c.slot0 + b0) * 260;
+    const bool staged = !((uintptr_t)c.recs & 3u);
+    if (staged) {
+        const size_t mm = c.m - b0 < ZKV_BLOCK ? c.m - b0 : ZKV_BLOCK;
+        const uint32_t* src = (const uint32_t*)rows;
+        const uint32_t total = (uint32_t)mm * 65u;
+#pragma unroll 1
+        for (uint32_t t = threadIdx.x; t < total; t += ZKV_BLOCK) lds[t] = src[t];
+        __syncthreads();
+    }
+    const size_t j = b0 + threadIdx.x;
+    if (j >= c.m) return;
+    const size_t slot = c.slot0 + j;
+    const uint32_t k = gwset_key_of_slot(c.start, c.n_keys, (uint32_t)slot);
+    c.skey[slot] = k;
+    const uint32_t i = c.idx[slot];
+    uint32_t flags = 0;
+    uint8_t st = ST_VERIFICATION_FAILED;
+    if (i != GW_NONE) {                                             // (a pad slot carries no seal: every stage skips it)
+        GwsetRec rd;
+        rd.row = staged ? lds + threadIdx.x * 65u : nullptr;
+        rd.rec = rows + (size_t)threadIdx.x * 260;
+        RzrSlot r;
+        rzrouter_prep_slot(c.keys[k].tab->vk_valid, c.routes[k], kc, c.len[slot], c.in_a + 32 * slot, c.in_b ? c.in_b + 32 * slot : nullptr, rd, r);
+#pragma unroll
+        for (int b = 0; b < 5; b++) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) c.sig[(size_t)(8 * b + q) * c.sig_cap + j] = r.sig[b][q];
+        }
+        if (r.flags & FL_ALIVE) {
+            ws_st(ws.prep, ws.cap, 0, j, r.o.ax); ws_st(ws.prep, ws.cap, 8, j, r.o.ay);
+            ws_st(ws.prep, ws.cap, 16, j, r.o.cx); ws_st(ws.prep, ws.cap, 24, j, r.o.cy);
+            ws_st(ws.prep, ws.cap, 32, j, r.o.bx.c0); ws_st(ws.prep, ws.cap, 40, j, r.o.bx.c1);
+            ws_st(ws.prep, ws.cap, 48, j, r.o.by.c0); ws_st(ws.prep, ws.cap, 56, j, r.o.by.c1);
+        }
+        flags = r.flags; st = r.status;
+    }
+    ws.flags[j] = flags;
+    ws.g2bad[j] = 0;
+    c.status[slot] = st;
+    c.recv[slot] = 0;                                               // the route has the seal's selector: nothing received to report
+}
+void launch_rzrouter_prep(const RzrChunk& c, const Risc0Consts& k, const Workspace& ws, hipStream_t s) {
+    if (!c.m) return;
+    hipLaunchKernelGGL(k_rzrouter_prep, dim3((unsigned)((c.m + ZKV_BLOCK - 1) / ZKV_BLOCK)), dim3(ZKV_BLOCK), 0, s, c, k, ws);
+}
+
+}  // namespace zkv

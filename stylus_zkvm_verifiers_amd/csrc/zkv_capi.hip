@@ -28,6 +28,7 @@
 #include "../../include/zkv_diag_prep.h"
 #include "../../include/zkv_diag_gt.h"
 #include "../../include/zkv_risc0_set_inclusion.h"
+#include "../../include/zkv_risc0_router.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
@@ -36,6 +37,7 @@
 #include "zkv_gset_layout.h"
 #include "zkv_selftest.h"
 #include "zkv_setincl.h"
+#include "zkv_rzrouter_prep.h"
 #include <sys/random.h>
 
 using namespace zkv;
@@ -202,6 +204,12 @@ struct zkv_ctx {
     uint8_t si_id[32] = {0}, si_root_sel[4] = {0}, si_set_sel[4] = {0};
     std::vector<uint8_t> si_roots;
     uint64_t si_counts[3] = {0, 0, 0};
+    // ZKV_VM_RISC0_ROUTER (zkv_risc0_router.h): routes [0, rz_nb) are the instances of kid[0], a verifier set; the keyed routes behind them
+    // share gw_group, a Groth16 key set of their keys (n_ic = 6, RISC Zero convention), and rz_routes holds their control parameters.
+    // gw_sel / gw_hash: selector and key digest per route; kid_ran: which group ran; rz_counts: seals per route, unknown, short.
+    size_t rz_nb = 0;
+    std::vector<RzrRoute> rz_routes;
+    std::vector<uint64_t> rz_counts;
     std::mutex mu;
 };
 
@@ -393,7 +401,7 @@ static int ctx_device_setup(zkv_ctx* c) {
     }
     if (c->vm == ZKV_VM_GROTH16_SET) return gset_device_setup(c);
     if (c->vm == ZKV_VM_PLONK_SET) return pset_device_setup(c);
-    if (c->vm != ZKV_VM_BN254 && c->vm != ZKV_VM_MIXED && c->vm != ZKV_VM_SP1_GATEWAY && c->vm != ZKV_VM_RISC0_SETINCL) {
+    if (c->vm != ZKV_VM_BN254 && c->vm != ZKV_VM_MIXED && c->vm != ZKV_VM_SP1_GATEWAY && c->vm != ZKV_VM_RISC0_SETINCL && c->vm != ZKV_VM_RISC0_ROUTER) {
         VkRaw raw;
         if (c->vm == ZKV_VM_RISC0 || c->vm == ZKV_VM_RISC0_SET) host::fill_vk_risc0(raw, c->control_root_0, c->control_root_1, c->control_id);
         else if (c->vm == ZKV_VM_GROTH16) host::fill_vk_generic(raw, c->gvk.data(), c->long_key ? 1u : c->g_n_ic);   // long key: IC[0] only here
@@ -2112,6 +2120,316 @@ ZKV_EXPORT int zkv_sp1_gateway_status_abi_encode(const zkv_ctx* c, uint8_t statu
     return zkv_status_abi_encode(ZKV_VM_SP1, status, received, expected, out);
 }
 
+// ------------------------------------------------------------------ RISC Zero router (zkv_risc0_router.h; no reference counterpart: parity unpinned)
+// Up to ZKV_RISC0_ROUTER_MAX_ROUTES RISC Zero Groth16 verifiers behind one context; every seal goes to the route whose selector begins
+// it.  The built-in-key routes are ONE verifier set (kid[0], a ZKV_VM_RISC0_SET context whose instances are the routes), the keyed routes
+// ONE Groth16 key set (gw_group: n_ic = 6, RISC Zero convention).  The device front end (k_risc0_router.hip) sorts a batch into the two
+// groups' compact records; the built-in group runs the verifier set's own stage pipeline with the instance row the front end wrote, the
+// keyed group k_rzrouter_prep and then the key sets' stages, and the statuses go back to the caller's order.
+// gw_sel: every route's selector (built-in routes first); gw_hash: 32 bytes per route, its key's digest; kid_ran: which group ran.
+ZKV_EXPORT zkv_ctx* zkv_risc0_router_create(size_t n_builtin, const uint8_t* control_roots, const uint8_t* bn254_control_ids, size_t n_keyed,
+                                            const uint8_t* const* vk_words, const uint8_t* keyed_control_roots, const uint8_t* keyed_control_ids, int device) {
+    if (n_builtin > ZKV_RISC0_ROUTER_MAX_ROUTES || n_keyed > ZKV_RISC0_ROUTER_MAX_KEYED || n_builtin + n_keyed == 0 ||
+        n_builtin + n_keyed > ZKV_RISC0_ROUTER_MAX_ROUTES) return nullptr;
+    if (n_builtin && (!control_roots || !bn254_control_ids)) return nullptr;
+    if (n_keyed && (!vk_words || !keyed_control_roots || !keyed_control_ids)) return nullptr;
+    std::vector<uint32_t> sel;
+    std::vector<uint8_t> dig;
+    std::vector<RzrRoute> routes(n_keyed);
+    uint8_t d[32], s4[4];
+    host::risc0_vk_digest(d);
+    for (size_t k = 0; k < n_builtin; k++) {
+        host::risc0_selector_with(control_roots + 32 * k, bn254_control_ids + 32 * k, d, s4);
+        sel.push_back(be32_of(s4));
+        dig.insert(dig.end(), d, d + 32);
+    }
+    for (size_t k = 0; k < n_keyed; k++) {
+        if (!vk_words[k]) return nullptr;
+        const uint8_t *root = keyed_control_roots + 32 * k, *id = keyed_control_ids + 32 * k;
+        host::risc0_vk_digest_words(vk_words[k], 6, d);
+        host::risc0_selector_with(root, id, d, s4);
+        sel.push_back(be32_of(s4));
+        dig.insert(dig.end(), d, d + 32);
+        // control_root_0 / _1 as initialize stores them (verifier.rs:64-66), the control id as it is; all as little-endian limbs
+        uint8_t lo[16], hi[16], w[32];
+        host::split_digest(root, lo, hi);
+        RzrRoute& rt = routes[k];
+        memset(&rt, 0, sizeof rt);
+        memset(w, 0, 32); memcpy(w + 16, lo, 16); host::be_to_limbs(rt.cr0, w);
+        memset(w, 0, 32); memcpy(w + 16, hi, 16); host::be_to_limbs(rt.cr1, w);
+        host::be_to_limbs(rt.id, id);
+        rt.id_ge_r = raw_lt_r(rt.id) ? 0u : 1u;
+    }
+    for (size_t k = 0; k < sel.size(); k++)
+        for (size_t j = 0; j < k; j++) if (sel[j] == sel[k]) return nullptr;       // the router could not tell the two routes apart
+    zkv_ctx* c = new (std::nothrow) zkv_ctx();
+    if (!c) return nullptr;
+    c->vm = ZKV_VM_RISC0_ROUTER; c->device = device; c->initialized = true;
+    host::risc0_consts(c->consts);
+    c->gw_sel = sel; c->gw_hash = dig; c->rz_routes = routes; c->rz_nb = n_builtin;
+    c->rz_counts.assign(sel.size() + 2, 0);
+    if (n_builtin) {
+        c->kid[0] = zkv_risc0_set_create(n_builtin, control_roots, bn254_control_ids, device);
+        if (!c->kid[0]) { zkv_ctx_destroy(c); return nullptr; }
+    }
+    if (n_keyed) {                                                 // one key set for all of them: its points are judged on the device (vk_valid per key)
+        const std::vector<size_t> n_ic(n_keyed, 6);
+        const std::vector<int> vm(n_keyed, ZKV_VM_RISC0);
+        c->gw_group = zkv_groth16_set_create(n_keyed, vk_words, n_ic.data(), vm.data(), device);
+        if (!c->gw_group) { zkv_ctx_destroy(c); return nullptr; }
+    }
+    return c;
+}
+ZKV_EXPORT size_t zkv_risc0_router_route_count(const zkv_ctx* c) { return c && c->vm == ZKV_VM_RISC0_ROUTER ? c->gw_sel.size() : 0; }
+ZKV_EXPORT int zkv_risc0_router_route(const zkv_ctx* c, size_t r, uint8_t selector[4], int* keyed) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (r >= c->gw_sel.size()) return ZKV_ERR_INVALID_ARG;
+    if (selector) be32_put(selector, c->gw_sel[r]);
+    if (keyed) *keyed = r >= c->rz_nb ? 1 : 0;
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_risc0_router_route_verifier_key_digest(const zkv_ctx* c, size_t r, uint8_t out[32]) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (r >= c->gw_sel.size() || !out) return ZKV_ERR_INVALID_ARG;
+    memcpy(out, c->gw_hash.data() + 32 * r, 32);
+    return ZKV_OK;
+}
+
+enum { RZ_CNT = 0, RZ_TOT, RZ_ITOT, RZ_POS, RZ_IDX, RZ_RECS, RZ_LEN, RZ_A, RZ_B, RZ_INST, RZ_ST, RZ_RV, RZ_SKEY, RZ_ROUTES,
+       RZ_H_SEALS, RZ_H_OFF, RZ_H_A, RZ_H_B, RZ_H_ST, RZ_H_RV, RZ_BUFS };
+static_assert(RZ_BUFS <= sizeof(((zkv_ctx*)nullptr)->mx) / sizeof(uint8_t*), "the router's buffers live in zkv_ctx::mx");
+// The built-in group: m compact records from the front end through the verifier set's pipeline (run_set_batch's chunks, with the true
+// lengths and the instance row on the device).  in_b == nullptr: verify_integrity.
+static int run_router_builtin(zkv_ctx* c, size_t m_total, const uint8_t* seals, const uint32_t* len, const uint32_t* inst, const uint8_t* in_a,
+                              const uint8_t* in_b, uint8_t* st, uint8_t* rv, hipStream_t s) {
+    if (!m_total) return ZKV_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_ready(c, m_total);
+    if (rc != ZKV_OK) return rc;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    const size_t cap = c->ws.cap;
+    for (size_t base = 0; base < m_total; base += cap) {
+        const size_t m = m_total - base < cap ? m_total - base : cap;
+        PrepArgs a;
+        memset(&a, 0, sizeof a);
+        a.n = m; a.blob = seals + base * ZKV_SEAL_BYTES; a.stride = ZKV_SEAL_BYTES; a.len = len + base;
+        a.inst = inst + base; a.inst_tab = c->d_inst; a.n_inst = (uint32_t)c->inst_raw.size();
+        a.in32_a = in_a + 32 * base; a.in32_b = in_b ? in_b + 32 * base : nullptr;
+        a.status = st + base; a.recv = rv + 4 * base;
+        enqueue_chunk(c, a, s, base + cap >= m_total);
+    }
+    HIP_TRY(hipGetLastError());
+    return mark_done(c, s);
+}
+// The keyed group: the M padded slots the front end has filled, from slot G0 of the call, verified in one pass for
+// all keys -- k_rzrouter_prep with the slot's route, then the key sets' stages chunk by chunk as run_gateway_group runs them (no tail
+// split, no aggregate check).  g->mu is held by the caller.  This is run_gateway_group with another PREP launch and chunk record; the two
+// are kept apart so that the SP1 gateway's unit compiles to what it did -- a change to the stage sequence of one belongs in the other too.
+static int run_router_group(zkv_ctx* rt, zkv_ctx* g, size_t M, int lanes, const RzrArgs& a, size_t G0, const uint64_t* gstart, uint8_t* st, uint8_t* rv,
+                            hipStream_t s) {
+    if (!M) return ZKV_OK;
+    size_t cap = 0;
+    int rc = groth16_ready(g, M, &cap);
+    if (rc != ZKV_OK) return rc;
+    if ((rc = order_after_previous(g, s)) != ZKV_OK) return rc;
+    const size_t K = rt->rz_routes.size();
+    RzrChunk pc;
+    memset(&pc, 0, sizeof pc);
+    pc.idx = a.idx + G0; pc.skey = (uint32_t*)rt->mx[RZ_SKEY];
+    pc.recs = a.c_seals + (size_t)ZKV_SEAL_BYTES * G0; pc.len = a.c_len + G0; pc.in_a = a.c_a + 32 * G0; pc.in_b = a.in_b ? a.c_b + 32 * G0 : nullptr;
+    pc.n_keys = (uint32_t)K;
+    for (size_t k = 0; k < K; k++) pc.start[k] = (uint32_t)gstart[k];
+    pc.keys = g->d_gs_key; pc.routes = (const RzrRoute*)rt->mx[RZ_ROUTES]; pc.sig = g->d_lsig; pc.sig_cap = g->lsig_cap;
+    pc.status = st + G0; pc.recv = (uint32_t*)(rv + 4 * G0);
+    for (size_t base = 0; base < M; base += cap) {
+        const size_t m = M - base < cap ? M - base : cap;
+        const bool timed = base + cap >= M;
+        pc.m = m; pc.slot0 = base;
+        GsetChunk ch;
+        memset(&ch, 0, sizeof ch);
+        ch.m = m; ch.slot0 = base; ch.idx = pc.idx; ch.skey = pc.skey;
+        ch.keys = g->d_gs_key; ch.rows = g->d_gs_rows; ch.win = g->d_gs_win;
+        ch.sig = g->d_lsig; ch.sig_cap = g->lsig_cap; ch.status = st + G0 + base;
+        if (timed) (void)hipEventRecord(g->ev[0], s);
+        launch_rzrouter_prep(pc, rt->consts, g->ws, s);
+        if (timed) (void)hipEventRecord(g->ev[1], s);
+        launch_gset_msm(ch, msm_lanes_long(g, m), g->ws, s);
+        if (timed) (void)hipEventRecord(g->ev[2], s);
+        if (lanes != 2) launch_g2chk2(m, g->ws, ch.status, s);       // (the lane-pair Miller loop is the subgroup test itself)
+        if (timed) (void)hipEventRecord(g->ev[3], s);
+        launch_gset_miller(lanes, m, pc.skey + base, g->d_gs_key, g->ws, ch.status, s);
+        if (timed) (void)hipEventRecord(g->ev[4], s);
+        launch_finalexp_lanes(lanes, m, g->ws, ch.status, s);
+        if (timed) (void)hipEventRecord(g->ev[5], s);
+        HIP_TRY(hipGetLastError());
+    }
+    return mark_done(g, s);
+}
+// Everything device-resident: ragged seals (offsets bounded by seal_bytes on the device) or, d_seal_off == nullptr, a fixed stride of 260.
+// d_b == nullptr: verify_integrity, d_a holds the claim digests.  Synchronises `s` once, after the count, to lay the slots out and learn
+// the groups' sub-batch sizes.
+static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64_t* d_seal_off, uint64_t seal_bytes, const uint8_t* d_a, const uint8_t* d_b,
+                      uint8_t* d_status, uint8_t* d_recv, hipStream_t s) {
+    int rc;
+    const size_t blocks = (n + 255) / 256, R = c->gw_sel.size(), NB = c->rz_nb, K = R - NB;
+    // slots: one per routed seal, and up to 31 pad slots behind every keyed route (its successor starts on a wavefront of the Miller mapping)
+    const size_t ns = n + 32 * K;
+    const size_t need[RZ_ROUTES] = {4 * GW_COLS * blocks, 4 * GW_COLS, 4 * ZKV_RISC0_ROUTER_MAX_ROUTES, 4 * n, 4 * ns, (size_t)ZKV_SEAL_BYTES * ns + 8, 4 * ns,
+                                    32 * ns, 32 * ns, 4 * ns, ns, 4 * ns, 4 * ns};
+    for (int k = 0; k < RZ_ROUTES; k++) if ((rc = grow(&c->mx[k], &c->mx_cap[k], need[k])) != ZKV_OK) return rc;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    if (K && !c->mx[RZ_ROUTES]) {                                  // the keyed routes' constants, once
+        if ((rc = grow(&c->mx[RZ_ROUTES], &c->mx_cap[RZ_ROUTES], sizeof(RzrRoute) * K)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpy(c->mx[RZ_ROUTES], c->rz_routes.data(), sizeof(RzrRoute) * K, hipMemcpyHostToDevice));
+    }
+    RzrArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = n; a.seals = d_seals; a.seal_off = d_seal_off; a.seal_bytes = seal_bytes; a.stride = ZKV_SEAL_BYTES; a.in_a = d_a; a.in_b = d_b;
+    a.n_builtin = (uint32_t)NB; a.n_keyed = (uint32_t)K;
+    for (size_t r = 0; r < R; r++) a.sel[r] = c->gw_sel[r];
+    a.cnt = (uint32_t*)c->mx[RZ_CNT]; a.totals = (uint32_t*)c->mx[RZ_TOT]; a.inst_tot = (uint32_t*)c->mx[RZ_ITOT];
+    a.pos = (uint32_t*)c->mx[RZ_POS]; a.idx = (uint32_t*)c->mx[RZ_IDX];
+    a.c_seals = c->mx[RZ_RECS]; a.c_len = (uint32_t*)c->mx[RZ_LEN]; a.c_a = c->mx[RZ_A]; a.c_b = c->mx[RZ_B]; a.c_inst = (uint32_t*)c->mx[RZ_INST];
+    a.status = d_status; a.recv = d_recv;
+    HIP_TRY(hipMemsetAsync(a.inst_tot, 0, 4 * ZKV_RISC0_ROUTER_MAX_ROUTES, s));
+    if (K) HIP_TRY(hipMemsetAsync(a.idx, 0xFF, 4 * ns, s));       // pad slots: GW_NONE
+    launch_rzrouter_count(a, s);
+    HIP_TRY(hipGetLastError());
+    uint32_t tot[GW_COLS], itot[ZKV_RISC0_ROUTER_MAX_ROUTES];
+    HIP_TRY(hipMemcpyAsync(tot, c->mx[RZ_TOT], sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(itot, c->mx[RZ_ITOT], sizeof itot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // The layout.  The built-in group takes one slot per seal from slot 0; the keyed routes take the key sets' layout behind it
+    // (zkv_gset_layout.h gset_choose: the mapping their seals would take, stepped to a finer one while the padding exceeds 1.25 times).
+    const size_t n0 = tot[RZR_COL_BUILTIN], G0 = n0;
+    size_t routed = n0, M = 0;
+    uint64_t gstart[GW_MAX_ROUTES + 1] = {0};
+    int lanes = 0;
+    std::unique_lock<std::mutex> glk;
+    if (K) {
+        glk = std::unique_lock<std::mutex>(c->gw_group->mu);
+        size_t placed = 0;
+        for (size_t k = 0; k < K; k++) placed += tot[RZR_COL_KEYED0 + k];
+        routed += placed;
+        uint64_t gslots = 0;
+        lanes = gset_choose(tot + RZR_COL_KEYED0, (uint32_t)K, miller_lanes(c->gw_group, placed), c->gw_group->lanes != 0, gstart, &gslots);
+        M = (size_t)gslots;
+        for (size_t k = 0; k < K; k++) a.start[RZR_COL_KEYED0 + k] = (uint32_t)(G0 + gstart[k]);
+    }
+    a.start[RZR_COL_BUILTIN] = 0;
+    uint64_t isum = 0;
+    for (size_t r = 0; r < NB; r++) isum += itot[r];
+    if (routed + tot[RZR_COL_NOT_FOUND] + tot[RZR_COL_SHORT] != n || G0 + M > ns || isum != n0) return ZKV_ERR_HIP;
+    launch_rzrouter_place(a, s);
+    HIP_TRY(hipGetLastError());
+    uint8_t *st = c->mx[RZ_ST], *rv = c->mx[RZ_RV];
+    if (n0 && (rc = run_router_builtin(c->kid[0], n0, a.c_seals, a.c_len, a.c_inst, a.c_a, d_b ? a.c_b : nullptr, st, rv, s)) != ZKV_OK) return rc;
+    if (routed > n0 && (rc = run_router_group(c, c->gw_group, M, lanes, a, G0, gstart, st, rv, s)) != ZKV_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // The statuses back to the caller's order, once per run of slots that lie back to back (a keyed route may end in pad slots).
+    size_t lo = 0, hi = n0;
+    for (size_t k = 0; k <= K; k++) {
+        const size_t cnt = k < K ? tot[RZR_COL_KEYED0 + k] : 0, at = k < K ? G0 + (size_t)gstart[k] : 0;
+        if (k < K && !cnt) continue;
+        if (k < K && at == hi) { hi += cnt; continue; }
+        launch_mixed_return(hi - lo, a.idx + lo, st + lo, rv + 4 * lo, d_status, d_recv, s);
+        if (k < K) { lo = at; hi = at + cnt; }
+    }
+    HIP_TRY(hipGetLastError());
+    if ((rc = mark_done(c, s)) != ZKV_OK) return rc;
+    // the counts of the most recent call: only a call that enqueued everything replaces them
+    for (size_t r = 0; r < NB; r++) c->rz_counts[r] = itot[r];
+    for (size_t k = 0; k < K; k++) c->rz_counts[NB + k] = tot[RZR_COL_KEYED0 + k];
+    c->rz_counts[R] = tot[RZR_COL_NOT_FOUND]; c->rz_counts[R + 1] = tot[RZR_COL_SHORT];
+    c->kid_ran[0] = n0 > 0; c->kid_ran[1] = routed > n0;
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_risc0_router_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint8_t* d_image_ids, const uint8_t* d_journal_digests,
+                                                 uint8_t* d_status, uint8_t* d_recv, void* stream) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_seals || !d_image_ids || !d_status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    return run_router(c, n, d_seals, nullptr, 0, d_image_ids, d_journal_digests, d_status, d_recv, stream ? (hipStream_t)stream : c->stream);
+}
+// host buffers: in_b == nullptr selects verify_integrity
+static int router_host_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* in_a, const uint8_t* in_b,
+                             uint8_t* status, uint8_t* recv) {
+    if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES || !offsets_ok(seal_off, n)) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    const uint64_t s0 = seal_off[0], sbytes = seal_off[n] - s0;
+    const size_t need[6] = {(size_t)sbytes + 8, 8 * (n + 1), 32 * n, 32 * n, n, 4 * n};
+    for (int k = 0; k < 6; k++) if ((rc = grow(&c->mx[RZ_H_SEALS + k], &c->mx_cap[RZ_H_SEALS + k], need[k])) != ZKV_OK) return rc;
+    hipStream_t s = c->stream;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    std::vector<uint64_t> so(seal_off, seal_off + n + 1);
+    for (auto& v : so) v -= s0;
+    if (sbytes) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_SEALS], seal_blob + s0, (size_t)sbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_OFF], so.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
+    if (in_b) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_B], in_b, 32 * n, hipMemcpyHostToDevice, s));
+    if ((rc = run_router(c, n, c->mx[RZ_H_SEALS], (const uint64_t*)c->mx[RZ_H_OFF], sbytes, c->mx[RZ_H_A], in_b ? c->mx[RZ_H_B] : nullptr,
+                         c->mx[RZ_H_ST], c->mx[RZ_H_RV], s)) != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(status, c->mx[RZ_H_ST], n, hipMemcpyDeviceToHost, s));
+    if (recv) HIP_TRY(hipMemcpyAsync(recv, c->mx[RZ_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_risc0_router_verify_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* image_ids,
+                                             const uint8_t* journal_digests, uint8_t* status, uint8_t* recv) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!seal_blob || !seal_off || !image_ids || !journal_digests || !status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    return router_host_batch(c, n, seal_blob, seal_off, image_ids, journal_digests, status, recv);
+}
+ZKV_EXPORT int zkv_risc0_router_verify_integrity_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* claim_digests,
+                                                       uint8_t* status, uint8_t* recv) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!seal_blob || !seal_off || !claim_digests || !status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    return router_host_batch(c, n, seal_blob, seal_off, claim_digests, nullptr, status, recv);
+}
+ZKV_EXPORT int zkv_risc0_router_verify(zkv_ctx* c, const uint8_t* seal, size_t seal_len, const uint8_t image_id[32], const uint8_t journal_digest[32],
+                                       uint8_t* status, uint8_t recv[4]) {
+    const uint64_t off[2] = {0, seal_len};
+    const uint8_t dummy = 0;
+    if (!seal && seal_len) return ZKV_ERR_INVALID_ARG;
+    return zkv_risc0_router_verify_batch(c, 1, seal ? seal : &dummy, off, image_id, journal_digest, status, recv);
+}
+ZKV_EXPORT int zkv_risc0_router_verify_integrity(zkv_ctx* c, const uint8_t* seal, size_t seal_len, const uint8_t claim_digest[32], uint8_t* status,
+                                                 uint8_t recv[4]) {
+    const uint64_t off[2] = {0, seal_len};
+    const uint8_t dummy = 0;
+    if (!seal && seal_len) return ZKV_ERR_INVALID_ARG;
+    return zkv_risc0_router_verify_integrity_batch(c, 1, seal ? seal : &dummy, off, claim_digest, status, recv);
+}
+ZKV_EXPORT int zkv_risc0_router_last_route_counts(zkv_ctx* c, uint64_t* out) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    for (size_t r = 0; r < c->rz_counts.size(); r++) out[r] = c->rz_counts[r];
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_risc0_router_status_abi_encode(const zkv_ctx* c, uint8_t status, const uint8_t received[4], uint8_t out[68]) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    if (status == ZKV_STATUS_ROUTE_NOT_FOUND) {                 // SelectorUnknown(bytes4): selector, then the bytes4 left-aligned in a word
+        if (!received) return ZKV_ERR_INVALID_ARG;
+        memset(out, 0, 36);
+        host::fn_selector("SelectorUnknown(bytes4)", out);
+        memcpy(out + 4, received, 4);
+        return 36;
+    }
+    uint8_t expected[4];
+    be32_put(expected, c->gw_sel[0]);
+    return zkv_status_abi_encode(ZKV_VM_RISC0, status, received, expected, out);
+}
+
 // ------------------------------------------------------------------ on-chain wire layer (eth_call batches)
 ZKV_EXPORT int zkv_abi_function_selector(const char* signature, uint8_t out[4]) {
     if (!signature || !out) return ZKV_ERR_INVALID_ARG;
@@ -3360,7 +3678,7 @@ ZKV_EXPORT int zkv_plonk_set_verify_batch(zkv_ctx* c, size_t n, const uint32_t* 
 ZKV_EXPORT int zkv_ctx_vk_x_batch(zkv_ctx* c, size_t n, const uint8_t* var_signals, uint8_t* out) {
     if (is_sharded(c)) c = c->shards[0];
     if (!c || c->vm == ZKV_VM_BN254 || c->vm == ZKV_VM_RISC0_SET || c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_PLONK || c->vm == ZKV_VM_GROTH16_SET ||
-        c->vm == ZKV_VM_SP1_GATEWAY || c->vm == ZKV_VM_PLONK || c->vm == ZKV_VM_PLONK_SET || c->vm == ZKV_VM_RISC0_SETINCL)
+        c->vm == ZKV_VM_SP1_GATEWAY || c->vm == ZKV_VM_PLONK || c->vm == ZKV_VM_PLONK_SET || c->vm == ZKV_VM_RISC0_SETINCL || c->vm == ZKV_VM_RISC0_ROUTER)
         return ZKV_ERR_WRONG_CTX;
     if (c->vm == ZKV_VM_RISC0 && !c->initialized) return ZKV_ERR_INVALID_ARG;
     if (n && (!var_signals || !out)) return ZKV_ERR_INVALID_ARG;
@@ -3488,6 +3806,7 @@ ZKV_EXPORT int zkv_ctx_set_lanes_per_proof(zkv_ctx* c, int lanes) {
         for (auto* k : c->kid) { const int rc = zkv_ctx_set_lanes_per_proof(k, lanes); if (rc != ZKV_OK) return rc; }
     }
     if (c->vm == ZKV_VM_RISC0_SETINCL) { const int rc = zkv_ctx_set_lanes_per_proof(c->kid[0], lanes); if (rc != ZKV_OK) return rc; }   // the root jobs run there
+    if (c->vm == ZKV_VM_RISC0_ROUTER && c->kid[0]) { const int rc = zkv_ctx_set_lanes_per_proof(c->kid[0], lanes); if (rc != ZKV_OK) return rc; }   // the built-in group
     for (auto* k : c->gw_route) { if (!k) continue; const int rc = zkv_ctx_set_lanes_per_proof(k, lanes); if (rc != ZKV_OK) return rc; }
     if (c->gw_group) { const int rc = zkv_ctx_set_lanes_per_proof(c->gw_group, lanes); if (rc != ZKV_OK) return rc; }
     std::lock_guard<std::mutex> lk(c->mu);
@@ -3607,6 +3926,11 @@ ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t
         }
         return ZKV_OK;
     }
+    if (c->vm == ZKV_VM_RISC0_ROUTER) {                  // the built-in group only: the keyed group keeps the per-proof path
+        const int rc = c->kid[0] ? zkv_ctx_set_aggregate_check(c->kid[0], enable, enable && seed32 ? seed : nullptr) : ZKV_OK;
+        { volatile uint8_t* w = seed; for (int i = 0; i < 32; i++) w[i] = 0; }
+        return rc;
+    }
     if (c->vm != ZKV_VM_RISC0 && c->vm != ZKV_VM_RISC0_SET && c->vm != ZKV_VM_SP1 && c->vm != ZKV_VM_GROTH16 && c->vm != ZKV_VM_SP1_PLONK &&
         c->vm != ZKV_VM_GROTH16_SET && c->vm != ZKV_VM_PLONK && c->vm != ZKV_VM_PLONK_SET)
         return enable ? ZKV_ERR_INVALID_ARG : ZKV_OK;
@@ -3642,6 +3966,7 @@ ZKV_EXPORT int zkv_ctx_aggregate_counters(zkv_ctx* c, uint64_t out[2]) {
         }
         return ZKV_OK;
     }
+    if (c->vm == ZKV_VM_RISC0_ROUTER) return c->kid[0] ? zkv_ctx_aggregate_counters(c->kid[0], out) : ZKV_OK;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->dev_ready || !c->d_agg_cnt) return ZKV_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -3699,6 +4024,12 @@ ZKV_EXPORT int zkv_ctx_reserve(zkv_ctx* c, size_t n) {
         std::lock_guard<std::mutex> lk(c->mu);
         return ctx_device_init(c);
     }
+    if (c->vm == ZKV_VM_RISC0_ROUTER) {                  // either group may own the whole batch
+        if (c->kid[0]) { const int rc = zkv_ctx_reserve(c->kid[0], n); if (rc != ZKV_OK) return rc; }
+        if (c->gw_group) { const int rc = zkv_ctx_reserve(c->gw_group, n); if (rc != ZKV_OK) return rc; }
+        std::lock_guard<std::mutex> lk(c->mu);
+        return ctx_device_init(c);
+    }
     if (c->vm == ZKV_VM_SP1_GATEWAY) {                   // any route may own the whole batch
         for (auto* k : c->gw_route) { if (!k) continue; const int rc = zkv_ctx_reserve(k, n); if (rc != ZKV_OK) return rc; }
         if (c->gw_group) { const int rc = zkv_ctx_reserve(c->gw_group, n); if (rc != ZKV_OK) return rc; }
@@ -3721,7 +4052,7 @@ ZKV_EXPORT int zkv_ctx_synchronize(zkv_ctx* c) {
         return ZKV_OK;
     }
     // a mixed context has work in flight as soon as ANY of its three contexts is set up (an all-SP1 batch never touches the RISC Zero child)
-    bool any = c->dev_ready || ((c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_RISC0_SETINCL) && ((c->kid[0] && c->kid[0]->dev_ready) || (c->kid[1] && c->kid[1]->dev_ready)));
+    bool any = c->dev_ready || ((c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_RISC0_SETINCL || c->vm == ZKV_VM_RISC0_ROUTER) && ((c->kid[0] && c->kid[0]->dev_ready) || (c->kid[1] && c->kid[1]->dev_ready)));
     for (auto* k : c->gw_route) any = any || (k && k->dev_ready);
     any = any || (c->gw_group && c->gw_group->dev_ready);
     if (!any) return ZKV_OK;
@@ -3755,6 +4086,19 @@ ZKV_EXPORT int zkv_ctx_last_stage_ms(zkv_ctx* c, float out_ms[5]) {
         HIP_TRY(hipEventElapsedTime(&out_ms[0], c->ev[0], c->ev[1]));
         for (int i = 1; i < 5; i++) out_ms[i] = a[i];
         return ZKV_OK;
+    }
+    if (c->vm == ZKV_VM_RISC0_ROUTER) {                  // the two groups run one after the other: stage times add up
+        bool ran = false;
+        for (int i = 0; i < 5; i++) out_ms[i] = 0.0f;
+        for (int k = 0; k < 2; k++) {
+            if (!c->kid_ran[k]) continue;
+            float a[5];
+            const int rc = zkv_ctx_last_stage_ms(k == 0 ? c->kid[0] : c->gw_group, a);
+            if (rc != ZKV_OK) return rc;
+            for (int i = 0; i < 5; i++) out_ms[i] += a[i];
+            ran = true;
+        }
+        return ran ? ZKV_OK : ZKV_ERR_NO_DEVICE;
     }
     if (c->vm == ZKV_VM_SP1_GATEWAY) {                   // routes run one after the other, as the mixed context's children
         bool ran = false;

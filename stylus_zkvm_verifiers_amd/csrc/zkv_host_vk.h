@@ -134,33 +134,49 @@ inline void tagged_struct(const uint8_t tag[32], const uint8_t* down, int n, uin
     buf[32 + 32 * n] = (uint8_t)(v >> 8); buf[33 + 32 * n] = (uint8_t)(v & 0xff);
     sha256_host(buf, 34 + 32 * (size_t)n, out);
 }
-inline void risc0_vk_digest(uint8_t out[32]) {
-    const VkHex& vk = RISC0_VK;
-    uint8_t icd[6][32], buf[128], tag[32], down[64], cur[32], parts[5][32];
-    for (int i = 0; i < 6; i++) { hex32(buf, vk.ic[i][0]); hex32(buf + 32, vk.ic[i][1]); sha256_host(buf, 64, icd[i]); }
-    hex32(buf, vk.alpha[0]); hex32(buf + 32, vk.alpha[1]); sha256_host(buf, 64, parts[0]);
-    for (int k = 0; k < 4; k++) hex32(buf + 32 * k, vk.beta[k]);
-    sha256_host(buf, 128, parts[1]);
-    for (int k = 0; k < 4; k++) hex32(buf + 32 * k, vk.gamma[k]);
-    sha256_host(buf, 128, parts[2]);
-    for (int k = 0; k < 4; k++) hex32(buf + 32 * k, vk.delta[k]);
-    sha256_host(buf, 128, parts[3]);
+// compute_verifier_key_digest (crypto.rs:136-195) over key words in fill_vk_generic's layout, which is the reference's word order:
+// alpha (2 words) | beta, gamma, delta (4 each: x[0] x[1] y[0] y[1]) | ic[i] (2 each).
+inline void risc0_vk_digest_words(const uint8_t* words, uint32_t n_ic, uint8_t out[32]) {
+    uint8_t tag[32], down[64], cur[32], icd[32], parts[5][32];
+    sha256_host(words, 64, parts[0]);
+    for (int k = 0; k < 3; k++) sha256_host(words + 64 + 128 * k, 128, parts[1 + k]);
     sha256_host((const uint8_t*)"risc0_groth16.VerifyingKey.IC", 29, tag);
     memset(cur, 0, 32);
-    for (int i = 5; i >= 0; i--) { memcpy(down, icd[i], 32); memcpy(down + 32, cur, 32); tagged_struct(tag, down, 2, cur); }
+    for (uint32_t i = n_ic; i-- > 0;) {
+        sha256_host(words + 448 + 64 * (size_t)i, 64, icd);
+        memcpy(down, icd, 32); memcpy(down + 32, cur, 32); tagged_struct(tag, down, 2, cur);
+    }
     memcpy(parts[4], cur, 32);
     sha256_host((const uint8_t*)"risc0_groth16.VerifyingKey", 26, tag);
     tagged_struct(tag, &parts[0][0], 5, out);
 }
-inline void risc0_selector(const uint8_t control_root[32], const uint8_t control_id[32], uint8_t sel[4]) {
+// the built-in key (crypto.rs:16-89) as key words: 448 + 64 * 6 bytes
+inline void risc0_vk_words(uint8_t words[832]) {
+    const VkHex& vk = RISC0_VK;
+    hex32(words, vk.alpha[0]); hex32(words + 32, vk.alpha[1]);
+    for (int k = 0; k < 4; k++) { hex32(words + 64 + 32 * k, vk.beta[k]); hex32(words + 192 + 32 * k, vk.gamma[k]); hex32(words + 320 + 32 * k, vk.delta[k]); }
+    for (int i = 0; i < 6; i++) { hex32(words + 448 + 64 * i, vk.ic[i][0]); hex32(words + 480 + 64 * i, vk.ic[i][1]); }
+}
+inline void risc0_vk_digest(uint8_t out[32]) {
+    uint8_t words[832];
+    risc0_vk_words(words);
+    risc0_vk_digest_words(words, 6, out);
+}
+// calculate_selector (verifier.rs:128-144) with a given key digest
+inline void risc0_selector_with(const uint8_t control_root[32], const uint8_t control_id[32], const uint8_t vk_digest[32], uint8_t sel[4]) {
     uint8_t buf[130], h[32];
     sha256_host((const uint8_t*)"risc0.Groth16ReceiptVerifierParameters", 38, buf);
     memcpy(buf + 32, control_root, 32);
     for (int i = 0; i < 32; i++) buf[64 + i] = control_id[31 - i];
-    risc0_vk_digest(buf + 96);
+    memcpy(buf + 96, vk_digest, 32);
     buf[128] = 3; buf[129] = 0;
     sha256_host(buf, 130, h);
     memcpy(sel, h, 4);
+}
+inline void risc0_selector(const uint8_t control_root[32], const uint8_t control_id[32], uint8_t sel[4]) {
+    uint8_t d[32];
+    risc0_vk_digest(d);
+    risc0_selector_with(control_root, control_id, d, sel);
 }
 inline void risc0_consts(Risc0Consts& k) {
     uint8_t tag[32], blk[64];

@@ -229,6 +229,37 @@ struct GwsetChunk {
     uint8_t* status; uint32_t* recv;
 };
 void launch_gwset_prep(const GwsetChunk& c, const Workspace& ws, hipStream_t s);
+// RISC Zero router (k_risc0_router.hip, include/zkv_risc0_router.h; zkv_rzrouter_prep.h has the columns): every seal goes to the route
+// whose selector begins it.  The built-in-key routes are ONE column (a verifier set: place writes the instance each seal matched), every
+// keyed route has its own (one key set, group k from slot start[1 + k]).
+struct RzrArgs {
+    size_t n;
+    const uint8_t* seals; const uint64_t* seal_off; uint64_t seal_bytes;       // ragged seals (seal_bytes bounds every read), or seal_off == nullptr:
+    uint32_t stride;                                                           // a fixed stride
+    const uint8_t* in_a; const uint8_t* in_b;                                  // n x 32 each; in_b == nullptr: verify_integrity, in_a holds claim digests
+    uint32_t n_builtin, n_keyed;
+    uint32_t sel[32];                                                          // route selectors, big-endian words (kernel arguments: SGPRs)
+    uint32_t start[9];                                                         // (place) first slot of the built-in group and of every keyed route
+    uint32_t* cnt; uint32_t* totals;                                           // GW_COLS per block (exclusive scan in place), GW_COLS totals
+    uint32_t* inst_tot;                                                        // seals per built-in route (zeroed by the host before the count)
+    uint32_t* pos; uint32_t* idx;                                              // pos[i] = slot (GW_NONE: answered in place); idx[slot] = i
+    uint8_t* c_seals; uint32_t* c_len; uint8_t* c_a; uint8_t* c_b; uint32_t* c_inst;      // compact records; c_inst: built-in slots only
+    uint8_t* status; uint8_t* recv;                                            // caller's outputs (short / unknown seals answered here)
+};
+void launch_rzrouter_count(const RzrArgs& a, hipStream_t s);       // count + scan: totals[GW_COLS], inst_tot[n_builtin]
+void launch_rzrouter_place(const RzrArgs& a, hipStream_t s);       // place + gather (start[] filled from the totals)
+// PREP of slots [slot0, slot0 + m) of the keyed group, as GwsetChunk: every per-slot table is the group's (index 0 = its first slot).
+struct RzrRoute;
+struct RzrChunk {
+    size_t m, slot0;
+    const uint32_t* idx; uint32_t* skey;
+    const uint8_t* recs; const uint32_t* len; const uint8_t* in_a; const uint8_t* in_b;     // in_b == nullptr: verify_integrity
+    uint32_t n_keys; uint32_t start[GW_MAX_ROUTES];
+    const GsetKey* keys; const RzrRoute* routes;
+    uint32_t* sig; size_t sig_cap;
+    uint8_t* status; uint32_t* recv;
+};
+void launch_rzrouter_prep(const RzrChunk& c, const Risc0Consts& k, const Workspace& ws, hipStream_t s);
 // Aggregate check on a set (k_gset_agg.hip, k_gset_agg_pair.hip; the layout: zkv_gset_layout.h gset_agg_choose).  psl: pseudo-proof slot per sub-batch.
 struct AggTables;
 void launch_gset_setup_agg(uint32_t n_keys, const VkRaw* d_raw, const VkTables* d_tabs, AggTables* d_agg, hipStream_t s);
