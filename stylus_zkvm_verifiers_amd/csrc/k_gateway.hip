@@ -2,7 +2,10 @@
 // verifier -- whose 4-byte selector begins it, as SP1's on-chain gateway forwards `verify_proof` by the selector.  No reference
 // counterpart (parity unpinned); the routes' own statuses are their contexts' ones.
 //
-// Same shape as the mixed-batch demultiplexer (k_mixed.hip), with up to 8 route columns and ragged proofs:
+// The shape of the mixed-batch demultiplexer (k_mixed.hip), with up to 8 route columns and ragged proofs.  The column counts, the slot
+// of a proof, the in-place answers and the record copy are the selector routers' shared skeleton (zkv_demux.h, also under
+// k_risc0_router.hip); this unit's own are the spans and the classifier, the public-values locations, the per-route record size and
+// the scan:
 //   k_gateway_count   per 256-proof block: proofs per route, not found, short, bad calldata (wave ballots + popcounts)
 //   k_gateway_scan    exclusive scan of every column over the blocks (one workgroup), totals
 //   (the host reads the totals back once and sizes the compact records: route r holds n_r records of 260 or 868 bytes)
@@ -11,8 +14,7 @@
 //                     the public-values location were written by place
 // Proofs arrive as n + 1 contiguous offsets or, from the calldata decoder (k_wire_gateway), as (start, length) records with gaps.
 // The statuses come back through k_mixed_return.  All of it is byte traffic beside the pairing; no scratch, no LDS beyond the counts.
-#include "zkv_internal.h"
-#include "zkv_bytes.h"
+#include "zkv_demux.h"
 
 namespace zkv {
 
@@ -47,19 +49,9 @@ __global__ __launch_bounds__(GW_BLOCK) void k_gateway_count(GatewayArgs a) {
     __shared__ uint32_t wc[GW_COLS][GW_BLOCK / 64];
     const size_t i = (size_t)blockIdx.x * GW_BLOCK + threadIdx.x;
     uint32_t sel;
-    const int c = i < a.n ? gw_class(a, i, &sel) : -1;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < GW_COLS; k++) {
-        const uint64_t m = __ballot(c == k);
-        if (lane == 0) wc[k][wave] = (uint32_t)__popcll(m);
-    }
+    demux_ballots(i < a.n ? gw_class(a, i, &sel) : -1, wc);
     __syncthreads();
-    if (threadIdx.x < GW_COLS) {
-        uint32_t t = 0;
-        for (int w = 0; w < GW_BLOCK / 64; w++) t += wc[threadIdx.x][w];
-        a.cnt[(size_t)blockIdx.x * GW_COLS + threadIdx.x] = t;
-    }
+    demux_block_counts(wc, a.cnt);
 }
 
 // cnt[b * GW_COLS + k] -> exclusive prefix sums over b in place, per column k; totals[k].  One workgroup.
@@ -103,34 +95,19 @@ __global__ __launch_bounds__(GW_BLOCK) void k_gateway_place(GatewayArgs a) {
     const size_t i = (size_t)blockIdx.x * GW_BLOCK + threadIdx.x;
     uint32_t sel = 0;
     const int c = i < a.n ? gw_class(a, i, &sel) : -1;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    uint64_t mine = 0;
-#pragma unroll
-    for (int k = 0; k < GW_MAX_ROUTES; k++) {
-        const uint64_t m = __ballot(c == k);
-        if (c == k) mine = m;
-        if (lane == 0) wc[k][wave] = (uint32_t)__popcll(m);
-    }
+    const uint64_t mine = demux_ballots(c, wc);
     __syncthreads();
     if (c < 0) return;
-    if (c >= GW_MAX_ROUTES) {                                       // no verifier to ask: answered here, no slot
-        a.pos[i] = GW_NONE;
-        a.status[i] = c == GW_COL_SHORT ? 4 : c == GW_COL_BAD ? 6 : 8;      // ZKV_STATUS_INVALID_PROOF_DATA, _BAD_CALLDATA, _ROUTE_NOT_FOUND
-        if (a.recv) {
-            a.recv[4 * i] = (uint8_t)(sel >> 24); a.recv[4 * i + 1] = (uint8_t)(sel >> 16);
-            a.recv[4 * i + 2] = (uint8_t)(sel >> 8); a.recv[4 * i + 3] = (uint8_t)sel;
-        }
+    if (c >= GW_MAX_ROUTES) {                                       // ZKV_STATUS_INVALID_PROOF_DATA, _BAD_CALLDATA, _ROUTE_NOT_FOUND
+        demux_answer(i, c == GW_COL_SHORT ? 4 : c == GW_COL_BAD ? 6 : 8, sel, a.pos, a.status, a.recv);
         return;
     }
-    uint32_t r = (uint32_t)__popcll(mine & below);
-    for (uint32_t w = 0; w < wave; w++) r += wc[c][w];
-    const uint32_t slot = a.start[c] + a.cnt[(size_t)blockIdx.x * GW_COLS + c] + r;
+    const uint32_t slot = demux_slot<GW_COLS>(c, mine, wc, a.start, a.cnt);
     a.pos[i] = slot;
     a.idx[slot] = (uint32_t)i;
     uint64_t at, len;
     gw_span(a, i, &at, &len);
-    a.c_len[slot] = len > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)len;
+    a.c_len[slot] = demux_len32(len);
     if (a.rec_proof_at) { a.c_pvoff[slot] = a.rec_pv_at[i]; a.c_pvlen[slot] = a.rec_pv_len[i]; return; }
     a.c_pvoff[slot] = a.pv_off ? a.pv_off[i] : (uint64_t)i * a.pv_stride;
     a.c_pvlen[slot] = (uint32_t)(a.pv_off ? a.pv_off[i + 1] - a.pv_off[i] : a.pv_stride);
@@ -151,12 +128,7 @@ __global__ __launch_bounds__(GW_BLOCK) void k_gateway_gather(GatewayArgs a) {
     uint32_t* dst = (uint32_t*)(a.c_proofs + a.base[r] + (uint64_t)(slot - a.start[r]) * rec);
     uint64_t at, len;
     gw_span(a, i, &at, &len);
-    const uint8_t* src = a.proofs + at;
-    if (len > rec) len = rec;
-    for (uint32_t w = lane; w < rec / 4; w += 64) {
-        const uint64_t at = 4ull * w;
-        dst[w] = at < len ? gw_ld4(src + at, len - at) : 0u;
-    }
+    demux_copy_record(dst, a.proofs + at, len, rec, lane);
     if (lane < 8) ((uint32_t*)a.c_a)[(size_t)slot * 8 + lane] = gw_ld4(a.vkeys + 32 * i + 4 * lane, 4);
 }
 

@@ -2,7 +2,10 @@
 // verifier or a verifier with a caller's key -- whose 4-byte selector begins it, as RISC Zero's on-chain router forwards `verify` and
 // `verifyIntegrity`.  No reference counterpart (parity unpinned); the routes' own statuses are their verifiers' ones.
 //
-// Same shape as the SP1 gateway's demultiplexer (k_gateway.hip), with up to 32 selectors and two groups of routes:
+// Up to 32 selectors and two groups of routes.  The column counts, the slot of a seal, the in-place answers and the record copy are the
+// selector routers' shared skeleton (zkv_demux.h, also under k_gateway.hip), the keyed group's PREP kernel is the shared body of
+// zkv_gwset_prep.h around rzrouter_prep_slot; this unit's own are the spans and the classifier, the instance of a built-in seal and
+// the per-built-in-route counters:
 //   k_rzrouter_count   per 256-seal block: seals of the built-in group (all built-in routes together), per keyed route, unknown, short;
 //                      and the seals of every built-in route, added to one counter per route (the call's per-route totals)
 //   k_gateway_scan     (k_gateway.hip, same column count) exclusive scan of every column over the blocks, totals
@@ -12,8 +15,7 @@
 //   k_rzrouter_gather  one wavefront per seal: first min(len, 260) seal bytes and the two 32-byte inputs to the slot's compact record
 //   k_rzrouter_prep    the keyed group's PREP, one slot per lane (zkv_rzrouter_prep.h), in front of the key sets' stages
 // The built-in group then runs the verifier set's own pipeline on its compact records, the statuses come back through k_mixed_return.
-#include "zkv_internal.h"
-#include "zkv_bytes.h"
+#include "zkv_demux.h"
 #include "zkv_rzrouter_prep.h"
 
 namespace zkv {
@@ -53,24 +55,15 @@ __global__ __launch_bounds__(RZR_BLOCK) void k_rzrouter_count(RzrArgs a) {
     const size_t i = (size_t)blockIdx.x * RZR_BLOCK + threadIdx.x;
     uint32_t sel = 0, inst = 0;
     const int c = i < a.n ? rzr_class(a, i, &sel, &inst) : -1;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < RZR_COLS; k++) {
-        const uint64_t m = __ballot(c == k);
-        if (lane == 0) wc[k][wave] = (uint32_t)__popcll(m);
-    }
+    demux_ballots(c, wc);
     // per built-in route: one atomic per wavefront and route that has seals (the slots do not depend on these, only the reported counts)
 #pragma unroll 1
     for (uint32_t r = 0; r < a.n_builtin; r++) {
         const uint64_t m = __ballot(c == RZR_COL_BUILTIN && inst == r);
-        if (lane == 0 && m) atomicAdd(&a.inst_tot[r], (uint32_t)__popcll(m));
+        if ((threadIdx.x & 63u) == 0 && m) atomicAdd(&a.inst_tot[r], (uint32_t)__popcll(m));
     }
     __syncthreads();
-    if (threadIdx.x < RZR_COLS) {
-        uint32_t t = 0;
-        for (int w = 0; w < RZR_BLOCK / 64; w++) t += wc[threadIdx.x][w];
-        a.cnt[(size_t)blockIdx.x * RZR_COLS + threadIdx.x] = t;
-    }
+    demux_block_counts(wc, a.cnt);
 }
 
 __global__ __launch_bounds__(RZR_BLOCK) void k_rzrouter_place(RzrArgs a) {
@@ -78,34 +71,19 @@ __global__ __launch_bounds__(RZR_BLOCK) void k_rzrouter_place(RzrArgs a) {
     const size_t i = (size_t)blockIdx.x * RZR_BLOCK + threadIdx.x;
     uint32_t sel = 0, inst = 0;
     const int c = i < a.n ? rzr_class(a, i, &sel, &inst) : -1;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    uint64_t mine = 0;
-#pragma unroll
-    for (int k = 0; k < RZR_ROUTED; k++) {
-        const uint64_t m = __ballot(c == k);
-        if (c == k) mine = m;
-        if (lane == 0) wc[k][wave] = (uint32_t)__popcll(m);
-    }
+    const uint64_t mine = demux_ballots(c, wc);
     __syncthreads();
     if (c < 0) return;
-    if (c >= RZR_ROUTED) {                                          // no verifier to ask: answered here, no slot
-        a.pos[i] = GW_NONE;
-        a.status[i] = c == RZR_COL_SHORT ? 4 : 8;                   // ZKV_STATUS_INVALID_PROOF_DATA, ZKV_STATUS_ROUTE_NOT_FOUND
-        if (a.recv) {
-            a.recv[4 * i] = (uint8_t)(sel >> 24); a.recv[4 * i + 1] = (uint8_t)(sel >> 16);
-            a.recv[4 * i + 2] = (uint8_t)(sel >> 8); a.recv[4 * i + 3] = (uint8_t)sel;
-        }
+    if (c >= RZR_ROUTED) {                                          // ZKV_STATUS_INVALID_PROOF_DATA, ZKV_STATUS_ROUTE_NOT_FOUND
+        demux_answer(i, c == RZR_COL_SHORT ? 4 : 8, sel, a.pos, a.status, a.recv);
         return;
     }
-    uint32_t r = (uint32_t)__popcll(mine & below);
-    for (uint32_t w = 0; w < wave; w++) r += wc[c][w];
-    const uint32_t slot = a.start[c] + a.cnt[(size_t)blockIdx.x * RZR_COLS + c] + r;
+    const uint32_t slot = demux_slot<RZR_COLS>(c, mine, wc, a.start, a.cnt);
     a.pos[i] = slot;
     a.idx[slot] = (uint32_t)i;
     uint64_t at, len;
     rzr_span(a, i, &at, &len);
-    a.c_len[slot] = len > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)len;
+    a.c_len[slot] = demux_len32(len);
     if (c == RZR_COL_BUILTIN) a.c_inst[slot] = inst;
 }
 
@@ -119,12 +97,7 @@ __global__ __launch_bounds__(RZR_BLOCK) void k_rzrouter_gather(RzrArgs a) {
     uint32_t* dst = (uint32_t*)(a.c_seals + (uint64_t)slot * 260);
     uint64_t at, len;
     rzr_span(a, i, &at, &len);
-    const uint8_t* src = a.seals + at;
-    if (len > 260) len = 260;
-    for (uint32_t w = lane; w < 65; w += 64) {
-        const uint64_t o = 4ull * w;
-        dst[w] = o < len ? gw_ld4(src + o, len - o) : 0u;
-    }
+    demux_copy_record(dst, a.seals + at, len, 260, lane);
     if (lane < 8) ((uint32_t*)a.c_a)[(size_t)slot * 8 + lane] = gw_ld4(a.in_a + 32 * i + 4 * lane, 4);
     else if (lane < 16 && a.in_b) ((uint32_t*)a.c_b)[(size_t)slot * 8 + (lane - 8)] = gw_ld4(a.in_b + 32 * i + 4 * (lane - 8), 4);
 }
@@ -143,54 +116,13 @@ void launch_rzrouter_place(const RzrArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_rzrouter_gather, dim3((unsigned)((a.n + per - 1) / per)), dim3(RZR_BLOCK), 0, s, a);
 }
 
-// Keyed group.  Records are 260-byte rows from a 4-byte aligned base (the router's own allocation; the built-in group's records before
-// the group's are a multiple of 4 bytes), so the 64 rows of a wavefront are 16,640 contiguous bytes: copied to LDS with coalesced dword
-// loads, every lane then reads its own 65 words (row stride 65 dwords: conflict-free), as k_prep_risc0 stages fixed-stride seals.  The
-// address test is wave-uniform; a base that fails it is read byte by byte.
+// Keyed group: the shared PREP body (zkv_gwset_prep.h) around the router's slot function.
 __global__ __launch_bounds__(ZKV_BLOCK) void k_rzrouter_prep(RzrChunk c, Risc0Consts kc, Workspace ws) {
     __shared__ uint32_t lds[ZKV_BLOCK * 65];
-    const size_t b0 = (size_t)blockIdx.x * ZKV_BLOCK;
-    const uint8_t* rows = c.recs + (c.slot0 + b0) * 260;
-    const bool staged = !((uintptr_t)c.recs & 3u);
-    if (staged) {
-        const size_t mm = c.m - b0 < ZKV_BLOCK ? c.m - b0 : ZKV_BLOCK;
-        const uint32_t* src = (const uint32_t*)rows;
-        const uint32_t total = (uint32_t)mm * 65u;
-#pragma unroll 1
-        for (uint32_t t = threadIdx.x; t < total; t += ZKV_BLOCK) lds[t] = src[t];
-        __syncthreads();
-    }
-    const size_t j = b0 + threadIdx.x;
-    if (j >= c.m) return;
-    const size_t slot = c.slot0 + j;
-    const uint32_t k = gwset_key_of_slot(c.start, c.n_keys, (uint32_t)slot);
-    c.skey[slot] = k;
-    const uint32_t i = c.idx[slot];
-    uint32_t flags = 0;
-    uint8_t st = ST_VERIFICATION_FAILED;
-    if (i != GW_NONE) {                                             // (a pad slot carries no seal: every stage skips it)
-        GwsetRec rd;
-        rd.row = staged ? lds + threadIdx.x * 65u : nullptr;
-        rd.rec = rows + (size_t)threadIdx.x * 260;
-        RzrSlot r;
-        rzrouter_prep_slot(c.keys[k].tab->vk_valid, c.routes[k], kc, c.len[slot], c.in_a + 32 * slot, c.in_b ? c.in_b + 32 * slot : nullptr, rd, r);
-#pragma unroll
-        for (int b = 0; b < 5; b++) {
-#pragma unroll
-            for (int q = 0; q < 8; q++) c.sig[(size_t)(8 * b + q) * c.sig_cap + j] = r.sig[b][q];
-        }
-        if (r.flags & FL_ALIVE) {
-            ws_st(ws.prep, ws.cap, 0, j, r.o.ax); ws_st(ws.prep, ws.cap, 8, j, r.o.ay);
-            ws_st(ws.prep, ws.cap, 16, j, r.o.cx); ws_st(ws.prep, ws.cap, 24, j, r.o.cy);
-            ws_st(ws.prep, ws.cap, 32, j, r.o.bx.c0); ws_st(ws.prep, ws.cap, 40, j, r.o.bx.c1);
-            ws_st(ws.prep, ws.cap, 48, j, r.o.by.c0); ws_st(ws.prep, ws.cap, 56, j, r.o.by.c1);
-        }
-        flags = r.flags; st = r.status;
-    }
-    ws.flags[j] = flags;
-    ws.g2bad[j] = 0;
-    c.status[slot] = st;
-    c.recv[slot] = 0;                                               // the route has the seal's selector: nothing received to report
+    // (kc is a kernel argument taken by reference: the lambda must stay always_inline, so that the reference folds away and kc stays in SGPRs)
+    gwset_prep_lane<5, RzrSlot>(c, ws, lds, [&kc](const RzrChunk& ch, uint32_t k, size_t slot, const GwsetRec& rd, RzrSlot& r) __attribute__((always_inline)) {
+        rzrouter_prep_slot(ch.keys[k].tab->vk_valid, ch.routes[k], kc, ch.len[slot], ch.in_a + 32 * slot, ch.in_b ? ch.in_b + 32 * slot : nullptr, rd, r);
+    });
 }
 void launch_rzrouter_prep(const RzrChunk& c, const Risc0Consts& k, const Workspace& ws, hipStream_t s) {
     if (!c.m) return;

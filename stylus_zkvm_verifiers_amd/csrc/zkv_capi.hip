@@ -1812,6 +1812,98 @@ ZKV_EXPORT int zkv_sp1_plonk_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_
     return run_dev_batch(c, n, d_proofs, d_vkeys, nullptr, d_pv, pv_len, d_status, d_recv, stream);
 }
 
+// ------------------------------------------------------------------ selector routers: what the SP1 gateway and the RISC Zero router share
+// Two routes with one selector: the router could not tell them apart.
+static bool selectors_distinct(const std::vector<uint32_t>& sel) {
+    for (size_t k = 0; k < sel.size(); k++)
+        for (size_t j = 0; j < k; j++) if (sel[j] == sel[k]) return false;
+    return true;
+}
+// The revert data of a custom error with one bytes4 argument, `signature` = "Name(bytes4)": its selector, then the bytes4 left-aligned in a word.
+static int abi_encode_error_bytes4(const char* signature, const uint8_t arg[4], uint8_t* out) {
+    memset(out, 0, 36);
+    host::fn_selector(signature, out);
+    memcpy(out + 4, arg, 4);
+    return 36;
+}
+// A ragged host blob of n items to the device: the bytes [off[0], off[n]) to mx[k_blob], the n + 1 offsets rebased to zero to mx[k_off];
+// *bytes = the byte count.  `rebased` holds the offsets until the caller has synchronised `s`.
+static int stage_ragged(zkv_ctx* c, int k_blob, int k_off, const uint8_t* blob, const uint64_t* off, size_t n, std::vector<uint64_t>* rebased, hipStream_t s,
+                        uint64_t* bytes) {
+    const uint64_t o0 = off[0];
+    *bytes = off[n] - o0;
+    int rc;
+    if ((rc = grow(&c->mx[k_blob], &c->mx_cap[k_blob], (size_t)*bytes + 8)) != ZKV_OK ||
+        (rc = grow(&c->mx[k_off], &c->mx_cap[k_off], 8 * (n + 1))) != ZKV_OK) return rc;
+    rebased->assign(off, off + n + 1);
+    for (auto& v : *rebased) v -= o0;
+    if (*bytes) HIP_TRY(hipMemcpyAsync(c->mx[k_blob], blob + o0, (size_t)*bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->mx[k_off], rebased->data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+    return ZKV_OK;
+}
+// The end of a host-buffer call: n statuses and (recv != nullptr) received selectors from mx[k_st] / mx[k_rv], and the call's wait.
+static int return_to_host(zkv_ctx* c, int k_st, int k_rv, size_t n, uint8_t* status, uint8_t* recv, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(status, c->mx[k_st], n, hipMemcpyDeviceToHost, s));
+    if (recv) HIP_TRY(hipMemcpyAsync(recv, c->mx[k_rv], 4 * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return ZKV_OK;
+}
+// The per-proof stages of one chunk of key-set slots (run_gset's per-proof region, the keyed groups of the two routers): `prep` launches
+// the caller's PREP kernel for the chunk, the remaining stages are the key sets'.  The last chunk of a call records the six stage events.
+template <class Prep>
+static int gset_proof_stages(zkv_ctx* g, const GsetChunk& ch, int lanes, bool timed, hipStream_t s, Prep prep) {
+    const size_t m = ch.m;
+    if (timed) (void)hipEventRecord(g->ev[0], s);
+    prep();
+    if (timed) (void)hipEventRecord(g->ev[1], s);
+    launch_gset_msm(ch, msm_lanes_long(g, m), g->ws, s);
+    if (timed) (void)hipEventRecord(g->ev[2], s);
+    if (lanes != 2) launch_g2chk2(m, g->ws, ch.status, s);       // (the lane-pair Miller loop is the subgroup test itself)
+    if (timed) (void)hipEventRecord(g->ev[3], s);
+    launch_gset_miller(lanes, m, ch.skey + ch.slot0, g->d_gs_key, g->ws, ch.status, s);
+    if (timed) (void)hipEventRecord(g->ev[4], s);
+    launch_finalexp_lanes(lanes, m, g->ws, ch.status, s);
+    if (timed) (void)hipEventRecord(g->ev[5], s);
+    HIP_TRY(hipGetLastError());
+    return ZKV_OK;
+}
+// The keyed group of a router (DESIGN.md sections 12d, 17): the M padded slots the demultiplexer has filled, verified in one pass for all
+// keys of the key set g -- prep(ch) fills and launches the caller's PREP record for the chunk, then the key sets' stages, chunk by chunk
+// as run_gset runs them (no tail split, no aggregate check).  idx, skey, st: the group's slot tables (index 0 = its first slot).  The
+// set's own buffers (its keys, staged signals, workspace) are read after groth16_ready, which may have made them: a PREP record takes
+// them from the chunk it is handed (keyed_prep_chunk), never from g before the call.  g->mu is held by the caller.
+static int groth16_ready(zkv_ctx* c, size_t n, size_t* chunk);
+template <class Prep>
+static int run_keyed_group(zkv_ctx* g, size_t M, int lanes, const uint32_t* idx, const uint32_t* skey, uint8_t* st, hipStream_t s, Prep prep) {
+    if (!M) return ZKV_OK;
+    size_t cap = 0;
+    int rc = groth16_ready(g, M, &cap);
+    if (rc != ZKV_OK) return rc;
+    if ((rc = order_after_previous(g, s)) != ZKV_OK) return rc;
+    for (size_t base = 0; base < M; base += cap) {
+        const size_t m = M - base < cap ? M - base : cap;
+        GsetChunk ch;
+        memset(&ch, 0, sizeof ch);
+        ch.m = m; ch.slot0 = base; ch.idx = idx; ch.skey = skey;
+        ch.keys = g->d_gs_key; ch.rows = g->d_gs_rows; ch.win = g->d_gs_win;
+        ch.sig = g->d_lsig; ch.sig_cap = g->lsig_cap; ch.status = st + base;
+        if ((rc = gset_proof_stages(g, ch, lanes, base + cap >= M, s, [&] { prep(ch); })) != ZKV_OK) return rc;
+    }
+    return mark_done(g, s);
+}
+// What a keyed group's PREP record (GwsetChunk, RzrChunk) shares with the chunk's GsetChunk
+template <class Chunk>
+static void keyed_prep_chunk(Chunk* pc, const GsetChunk& ch) {
+    pc->m = ch.m; pc->slot0 = ch.slot0; pc->keys = ch.keys; pc->sig = ch.sig; pc->sig_cap = ch.sig_cap;
+}
+// The statuses of a router call back to the caller's order: one k_mixed_return per run of live slots (zkv_gset_layout.h route_layout).
+static void route_return(const RouteLayout& L, const uint32_t* idx, const uint8_t* st, const uint8_t* rv, uint8_t* d_status, uint8_t* d_recv, hipStream_t s) {
+    for (uint32_t q = 0; q < L.n_runs; q++) {
+        const size_t lo = (size_t)L.run_at[q];
+        launch_mixed_return((size_t)L.run_n[q], idx + lo, st + lo, rv + 4 * lo, d_status, d_recv, s);
+    }
+}
+
 // ------------------------------------------------------------------ SP1 gateway (zkv_sp1_gateway.h; no reference counterpart: parity unpinned)
 // Up to ZKV_SP1_GATEWAY_MAX_ROUTES SP1 verifiers behind one context; every proof goes to the route whose selector begins it.  The routes
 // are ordinary SP1 / SP1 PLONK contexts owned by the gateway: the device front end (k_gateway.hip) sorts a batch into their compact
@@ -1836,8 +1928,7 @@ ZKV_EXPORT zkv_ctx* zkv_sp1_gateway_create_keyed(int groth16, size_t n_keys, con
         sel.push_back(be32_of(plonk_verifier_hash + 32 * k));
         hash.insert(hash.end(), plonk_verifier_hash + 32 * k, plonk_verifier_hash + 32 * k + 32);
     }
-    for (size_t k = 0; k < sel.size(); k++)
-        for (size_t j = 0; j < k; j++) if (sel[j] == sel[k]) return nullptr;       // the gateway could not tell the two routes apart
+    if (!selectors_distinct(sel)) return nullptr;
     zkv_ctx* c = new (std::nothrow) zkv_ctx();
     if (!c) return nullptr;
     c->vm = ZKV_VM_SP1_GATEWAY; c->device = device; c->initialized = true;
@@ -1926,49 +2017,7 @@ enum { GW_CNT = 0, GW_TOT, GW_POS, GW_IDX, GW_RECS, GW_LEN, GW_A, GW_PVOFF, GW_P
        GW_H_VK, GW_H_PV, GW_H_PVOFF, GW_H_PROOF, GW_H_POFF, GW_H_ST, GW_H_RV,
        GWW_VK, GWW_PVAT, GWW_PVLEN, GWW_PAT, GWW_PLEN, GWW_BAD, GWW_ARENA, GWW_H_CD, GWW_H_OFF,        // calldata batches (run_gateway_wire)
        GW_SKEY };                                                                                     // keyed group: the key of every group slot
-// The keyed group of a gateway (zkv_sp1_gateway_keys.h): the M padded slots the demultiplexer has filled, from slot
-// G0 of the call and byte B0 of the compact records, verified in one pass for all keys -- k_gwset_prep with the slot's key, then the key
-// sets' stages chunk by chunk as run_gset runs them (no tail split, no aggregate check).  g->mu is held by the caller.
-static int groth16_ready(zkv_ctx* c, size_t n, size_t* chunk);
-static int run_gateway_group(zkv_ctx* gw, zkv_ctx* g, size_t M, int lanes, const GatewayArgs& a, size_t G0, uint64_t B0, const uint64_t* gstart,
-                             const uint8_t* d_pv, uint8_t* st, uint8_t* rv, hipStream_t s) {
-    if (!M) return ZKV_OK;
-    size_t cap = 0;
-    int rc = groth16_ready(g, M, &cap);
-    if (rc != ZKV_OK) return rc;
-    if ((rc = order_after_previous(g, s)) != ZKV_OK) return rc;
-    GwsetChunk pc;
-    memset(&pc, 0, sizeof pc);
-    pc.idx = a.idx + G0; pc.skey = (uint32_t*)gw->mx[GW_SKEY];
-    pc.recs = a.c_proofs + B0; pc.len = a.c_len + G0; pc.vkeys = a.c_a + 32 * G0; pc.pvoff = a.c_pvoff + G0; pc.pvlen = a.c_pvlen + G0; pc.pv = d_pv;
-    pc.n_keys = (uint32_t)gw->gw_nkeys;
-    for (size_t k = 0; k < gw->gw_nkeys; k++) pc.start[k] = (uint32_t)gstart[k];
-    pc.keys = g->d_gs_key; pc.sig = g->d_lsig; pc.sig_cap = g->lsig_cap;
-    pc.status = st + G0; pc.recv = (uint32_t*)(rv + 4 * G0);
-    for (size_t base = 0; base < M; base += cap) {
-        const size_t m = M - base < cap ? M - base : cap;
-        const bool timed = base + cap >= M;
-        pc.m = m; pc.slot0 = base;
-        GsetChunk ch;
-        memset(&ch, 0, sizeof ch);
-        ch.m = m; ch.slot0 = base; ch.idx = pc.idx; ch.skey = pc.skey;
-        ch.keys = g->d_gs_key; ch.rows = g->d_gs_rows; ch.win = g->d_gs_win;
-        ch.sig = g->d_lsig; ch.sig_cap = g->lsig_cap; ch.status = st + G0 + base;
-        if (timed) (void)hipEventRecord(g->ev[0], s);
-        launch_gwset_prep(pc, g->ws, s);
-        if (timed) (void)hipEventRecord(g->ev[1], s);
-        launch_gset_msm(ch, msm_lanes_long(g, m), g->ws, s);
-        if (timed) (void)hipEventRecord(g->ev[2], s);
-        if (lanes != 2) launch_g2chk2(m, g->ws, ch.status, s);       // (the lane-pair Miller loop is the subgroup test itself)
-        if (timed) (void)hipEventRecord(g->ev[3], s);
-        launch_gset_miller(lanes, m, pc.skey + base, g->d_gs_key, g->ws, ch.status, s);
-        if (timed) (void)hipEventRecord(g->ev[4], s);
-        launch_finalexp_lanes(lanes, m, g->ws, ch.status, s);
-        if (timed) (void)hipEventRecord(g->ev[5], s);
-        HIP_TRY(hipGetLastError());
-    }
-    return mark_done(g, s);
-}
+static_assert(GW_SKEY < sizeof(((zkv_ctx*)nullptr)->mx) / sizeof(uint8_t*), "the gateway's buffers live in zkv_ctx::mx");
 // Everything device-resident: ragged proofs (offsets bounded by proof_bytes on the device); public values ragged (d_pv_off) or at a
 // fixed stride.  Or, from the calldata decoder, `recs`: (start, length) records of proofs and public values from one base address, which
 // d_proofs and d_pv then both are, and bad-calldata marks.  Synchronises `s` once, after the count, to size the compact records and learn
@@ -2002,31 +2051,18 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
     uint32_t tot[GW_COLS];
     HIP_TRY(hipMemcpyAsync(tot, c->mx[GW_TOT], sizeof tot, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    // The layout.  A route with a context of its own takes one slot per proof; the keyed routes take the key sets' layout
-    // (zkv_gset_layout.h gset_choose: the mapping their proofs would take, stepped to a finer one while the padding exceeds 1.25 times).
-    size_t routed = 0, slots = 0, G0 = 0, M = 0;
-    uint64_t bytes = 0, B0 = 0, gstart[GW_MAX_ROUTES + 1] = {0};
-    int lanes = 0;
+    // The layout (zkv_gset_layout.h route_layout).  A route with a context of its own takes one slot per proof; the keyed routes take the
+    // key sets' layout (gset_choose: the mapping their proofs would take, stepped to a finer one while the padding exceeds 1.25 times).
+    size_t routed = 0, placed = 0;
+    for (size_t r = 0; r < R; r++) routed += tot[r];
+    for (size_t k = 0; k < K; k++) placed += tot[key0 + k];
     std::unique_lock<std::mutex> glk;
-    for (size_t r = 0; r < R; r++) {
-        routed += tot[r];
-        if (K && r == key0) {
-            glk = std::unique_lock<std::mutex>(c->gw_group->mu);
-            size_t placed = 0;
-            for (size_t k = 0; k < K; k++) placed += tot[key0 + k];
-            uint64_t gslots = 0;
-            lanes = gset_choose(tot + key0, (uint32_t)K, miller_lanes(c->gw_group, placed), c->gw_group->lanes != 0, gstart, &gslots);
-            G0 = slots; B0 = bytes; M = (size_t)gslots;
-        }
-        if (gw_keyed(c, r)) {
-            a.start[r] = (uint32_t)(G0 + gstart[r - key0]); a.base[r] = B0 + (uint64_t)ZKV_SEAL_BYTES * gstart[r - key0];
-            if (r + 1 == key0 + K) { slots = G0 + M; bytes = B0 + (uint64_t)ZKV_SEAL_BYTES * M; }
-            continue;
-        }
-        a.start[r] = (uint32_t)slots; a.base[r] = bytes; slots += tot[r]; bytes += (uint64_t)tot[r] * a.rec[r];
-    }
-    if (routed + tot[GW_COL_NOT_FOUND] + tot[GW_COL_SHORT] + tot[GW_COL_BAD] != n || slots > ns) return ZKV_ERR_HIP;
-    if ((rc = grow(&c->mx[GW_RECS], &c->mx_cap[GW_RECS], (size_t)bytes + 8)) != ZKV_OK) return rc;
+    if (K) glk = std::unique_lock<std::mutex>(c->gw_group->mu);
+    RouteLayout L;
+    route_layout(tot, (uint32_t)R, (uint32_t)key0, (uint32_t)K, a.rec, K ? miller_lanes(c->gw_group, placed) : 0, K && c->gw_group->lanes != 0, &L);
+    for (size_t r = 0; r < R; r++) { a.start[r] = L.start[r]; a.base[r] = L.base[r]; }
+    if (routed + tot[GW_COL_NOT_FOUND] + tot[GW_COL_SHORT] + tot[GW_COL_BAD] != n || L.slots > ns) return ZKV_ERR_HIP;
+    if ((rc = grow(&c->mx[GW_RECS], &c->mx_cap[GW_RECS], (size_t)L.bytes + 8)) != ZKV_OK) return rc;
     a.c_proofs = c->mx[GW_RECS];
     for (size_t r = 0; r < R; r++) { c->gw_counts[r] = tot[r]; c->gw_ran[r] = tot[r] > 0; }
     for (size_t r = R; r < GW_MAX_ROUTES; r++) c->gw_counts[r] = 0;
@@ -2040,17 +2076,23 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
         if ((rc = run_records(c->gw_route[r], tot[r], a.c_proofs + a.base[r], a.c_len + j, a.c_a + 32 * j, nullptr, nullptr, d_pv, a.c_pvoff + j,
                               a.c_pvlen + j, st + j, rv + 4 * j, s)) != ZKV_OK) return rc;
     }
-    if (K && (rc = run_gateway_group(c, c->gw_group, M, lanes, a, G0, B0, gstart, d_pv, st, rv, s)) != ZKV_OK) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    // The statuses back to the caller's order, once per run of routes whose proofs lie back to back (a keyed route may end in pad slots;
-    // a gateway without keyed routes is one run).
-    size_t lo = 0, hi = 0;
-    for (size_t r = 0; r <= R; r++) {
-        if (r < R && !tot[r]) continue;
-        if (r < R && a.start[r] == hi) { hi += tot[r]; continue; }
-        launch_mixed_return(hi - lo, a.idx + lo, st + lo, rv + 4 * lo, d_status, d_recv, s);
-        if (r < R) { lo = a.start[r]; hi = lo + tot[r]; }
+    if (K) {                                                       // the keyed group: k_gwset_prep with the slot's key, then the key sets' stages
+        const size_t G0 = (size_t)L.g0;
+        zkv_ctx* g = c->gw_group;
+        GwsetChunk pc;
+        memset(&pc, 0, sizeof pc);
+        pc.idx = a.idx + G0; pc.skey = (uint32_t*)c->mx[GW_SKEY];
+        pc.recs = a.c_proofs + L.b0; pc.len = a.c_len + G0; pc.vkeys = a.c_a + 32 * G0; pc.pvoff = a.c_pvoff + G0; pc.pvlen = a.c_pvlen + G0; pc.pv = d_pv;
+        pc.n_keys = (uint32_t)K;
+        for (size_t k = 0; k < K; k++) pc.start[k] = (uint32_t)L.gstart[k];
+        pc.status = st + G0; pc.recv = (uint32_t*)(rv + 4 * G0);
+        if ((rc = run_keyed_group(g, (size_t)L.m, L.lanes, pc.idx, pc.skey, pc.status, s, [&](const GsetChunk& ch) {
+                keyed_prep_chunk(&pc, ch);
+                launch_gwset_prep(pc, g->ws, s); })) != ZKV_OK) return rc;
     }
+    HIP_TRY(hipSetDevice(c->device));
+    // (a keyed route may end in pad slots; a gateway without keyed routes is one run)
+    route_return(L, a.idx, st, rv, d_status, d_recv, s);
     HIP_TRY(hipGetLastError());
     return mark_done(c, s);
 }
@@ -2076,25 +2118,18 @@ ZKV_EXPORT int zkv_sp1_gateway_verify_batch(zkv_ctx* c, size_t n, const uint8_t*
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_device_init(c);
     if (rc != ZKV_OK) return rc;
-    const uint64_t s0 = proof_off[0], sbytes = proof_off[n] - s0, v0 = pv_off[0], vbytes = pv_off[n] - v0;
-    const size_t need[7] = {32 * n, (size_t)vbytes + 8, 8 * (n + 1), (size_t)sbytes + 8, 8 * (n + 1), n, 4 * n};
-    for (int k = 0; k < 7; k++) if ((rc = grow(&c->mx[GW_H_VK + k], &c->mx_cap[GW_H_VK + k], need[k])) != ZKV_OK) return rc;
+    if ((rc = grow(&c->mx[GW_H_VK], &c->mx_cap[GW_H_VK], 32 * n)) != ZKV_OK || (rc = grow(&c->mx[GW_H_ST], &c->mx_cap[GW_H_ST], n)) != ZKV_OK ||
+        (rc = grow(&c->mx[GW_H_RV], &c->mx_cap[GW_H_RV], 4 * n)) != ZKV_OK) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
-    std::vector<uint64_t> so(proof_off, proof_off + n + 1), vo(pv_off, pv_off + n + 1);
-    for (auto& v : so) v -= s0;
-    for (auto& v : vo) v -= v0;
+    std::vector<uint64_t> so, vo;
+    uint64_t sbytes = 0, vbytes = 0;
     HIP_TRY(hipMemcpyAsync(c->mx[GW_H_VK], vkeys, 32 * n, hipMemcpyHostToDevice, s));
-    if (vbytes) HIP_TRY(hipMemcpyAsync(c->mx[GW_H_PV], pv_blob + v0, (size_t)vbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->mx[GW_H_PVOFF], vo.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
-    if (sbytes) HIP_TRY(hipMemcpyAsync(c->mx[GW_H_PROOF], proof_blob + s0, (size_t)sbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->mx[GW_H_POFF], so.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+    if ((rc = stage_ragged(c, GW_H_PV, GW_H_PVOFF, pv_blob, pv_off, n, &vo, s, &vbytes)) != ZKV_OK ||
+        (rc = stage_ragged(c, GW_H_PROOF, GW_H_POFF, proof_blob, proof_off, n, &so, s, &sbytes)) != ZKV_OK) return rc;
     if ((rc = run_gateway(c, n, c->mx[GW_H_VK], c->mx[GW_H_PROOF], (const uint64_t*)c->mx[GW_H_POFF], sbytes, c->mx[GW_H_PV],
                           (const uint64_t*)c->mx[GW_H_PVOFF], 0, c->mx[GW_H_ST], c->mx[GW_H_RV], s)) != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(status, c->mx[GW_H_ST], n, hipMemcpyDeviceToHost, s));
-    if (recv) HIP_TRY(hipMemcpyAsync(recv, c->mx[GW_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return ZKV_OK;
+    return return_to_host(c, GW_H_ST, GW_H_RV, n, status, recv, s);
 }
 ZKV_EXPORT int zkv_sp1_gateway_last_route_counts(zkv_ctx* c, uint64_t* out) {
     if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
@@ -2108,13 +2143,7 @@ ZKV_EXPORT int zkv_sp1_gateway_last_route_counts(zkv_ctx* c, uint64_t* out) {
 ZKV_EXPORT int zkv_sp1_gateway_status_abi_encode(const zkv_ctx* c, uint8_t status, const uint8_t received[4], uint8_t out[68]) {
     if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
     if (!out) return ZKV_ERR_INVALID_ARG;
-    if (status == ZKV_STATUS_ROUTE_NOT_FOUND) {                 // RouteNotFound(bytes4): selector, then the bytes4 left-aligned in a word
-        if (!received) return ZKV_ERR_INVALID_ARG;
-        memset(out, 0, 36);
-        host::fn_selector("RouteNotFound(bytes4)", out);
-        memcpy(out + 4, received, 4);
-        return 36;
-    }
+    if (status == ZKV_STATUS_ROUTE_NOT_FOUND) return received ? abi_encode_error_bytes4("RouteNotFound(bytes4)", received, out) : ZKV_ERR_INVALID_ARG;
     uint8_t expected[4];
     be32_put(expected, c->gw_sel[0]);
     return zkv_status_abi_encode(ZKV_VM_SP1, status, received, expected, out);
@@ -2160,8 +2189,7 @@ ZKV_EXPORT zkv_ctx* zkv_risc0_router_create(size_t n_builtin, const uint8_t* con
         host::be_to_limbs(rt.id, id);
         rt.id_ge_r = raw_lt_r(rt.id) ? 0u : 1u;
     }
-    for (size_t k = 0; k < sel.size(); k++)
-        for (size_t j = 0; j < k; j++) if (sel[j] == sel[k]) return nullptr;       // the router could not tell the two routes apart
+    if (!selectors_distinct(sel)) return nullptr;
     zkv_ctx* c = new (std::nothrow) zkv_ctx();
     if (!c) return nullptr;
     c->vm = ZKV_VM_RISC0_ROUTER; c->device = device; c->initialized = true;
@@ -2221,50 +2249,6 @@ static int run_router_builtin(zkv_ctx* c, size_t m_total, const uint8_t* seals, 
     HIP_TRY(hipGetLastError());
     return mark_done(c, s);
 }
-// The keyed group: the M padded slots the front end has filled, from slot G0 of the call, verified in one pass for
-// all keys -- k_rzrouter_prep with the slot's route, then the key sets' stages chunk by chunk as run_gateway_group runs them (no tail
-// split, no aggregate check).  g->mu is held by the caller.  This is run_gateway_group with another PREP launch and chunk record; the two
-// are kept apart so that the SP1 gateway's unit compiles to what it did -- a change to the stage sequence of one belongs in the other too.
-static int run_router_group(zkv_ctx* rt, zkv_ctx* g, size_t M, int lanes, const RzrArgs& a, size_t G0, const uint64_t* gstart, uint8_t* st, uint8_t* rv,
-                            hipStream_t s) {
-    if (!M) return ZKV_OK;
-    size_t cap = 0;
-    int rc = groth16_ready(g, M, &cap);
-    if (rc != ZKV_OK) return rc;
-    if ((rc = order_after_previous(g, s)) != ZKV_OK) return rc;
-    const size_t K = rt->rz_routes.size();
-    RzrChunk pc;
-    memset(&pc, 0, sizeof pc);
-    pc.idx = a.idx + G0; pc.skey = (uint32_t*)rt->mx[RZ_SKEY];
-    pc.recs = a.c_seals + (size_t)ZKV_SEAL_BYTES * G0; pc.len = a.c_len + G0; pc.in_a = a.c_a + 32 * G0; pc.in_b = a.in_b ? a.c_b + 32 * G0 : nullptr;
-    pc.n_keys = (uint32_t)K;
-    for (size_t k = 0; k < K; k++) pc.start[k] = (uint32_t)gstart[k];
-    pc.keys = g->d_gs_key; pc.routes = (const RzrRoute*)rt->mx[RZ_ROUTES]; pc.sig = g->d_lsig; pc.sig_cap = g->lsig_cap;
-    pc.status = st + G0; pc.recv = (uint32_t*)(rv + 4 * G0);
-    for (size_t base = 0; base < M; base += cap) {
-        const size_t m = M - base < cap ? M - base : cap;
-        const bool timed = base + cap >= M;
-        pc.m = m; pc.slot0 = base;
-        GsetChunk ch;
-        memset(&ch, 0, sizeof ch);
-        ch.m = m; ch.slot0 = base; ch.idx = pc.idx; ch.skey = pc.skey;
-        ch.keys = g->d_gs_key; ch.rows = g->d_gs_rows; ch.win = g->d_gs_win;
-        ch.sig = g->d_lsig; ch.sig_cap = g->lsig_cap; ch.status = st + G0 + base;
-        if (timed) (void)hipEventRecord(g->ev[0], s);
-        launch_rzrouter_prep(pc, rt->consts, g->ws, s);
-        if (timed) (void)hipEventRecord(g->ev[1], s);
-        launch_gset_msm(ch, msm_lanes_long(g, m), g->ws, s);
-        if (timed) (void)hipEventRecord(g->ev[2], s);
-        if (lanes != 2) launch_g2chk2(m, g->ws, ch.status, s);       // (the lane-pair Miller loop is the subgroup test itself)
-        if (timed) (void)hipEventRecord(g->ev[3], s);
-        launch_gset_miller(lanes, m, pc.skey + base, g->d_gs_key, g->ws, ch.status, s);
-        if (timed) (void)hipEventRecord(g->ev[4], s);
-        launch_finalexp_lanes(lanes, m, g->ws, ch.status, s);
-        if (timed) (void)hipEventRecord(g->ev[5], s);
-        HIP_TRY(hipGetLastError());
-    }
-    return mark_done(g, s);
-}
 // Everything device-resident: ragged seals (offsets bounded by seal_bytes on the device) or, d_seal_off == nullptr, a fixed stride of 260.
 // d_b == nullptr: verify_integrity, d_a holds the claim digests.  Synchronises `s` once, after the count, to lay the slots out and learn
 // the groups' sub-batch sizes.
@@ -2299,42 +2283,44 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
     HIP_TRY(hipMemcpyAsync(tot, c->mx[RZ_TOT], sizeof tot, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(itot, c->mx[RZ_ITOT], sizeof itot, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    // The layout.  The built-in group takes one slot per seal from slot 0; the keyed routes take the key sets' layout behind it
-    // (zkv_gset_layout.h gset_choose: the mapping their seals would take, stepped to a finer one while the padding exceeds 1.25 times).
-    const size_t n0 = tot[RZR_COL_BUILTIN], G0 = n0;
-    size_t routed = n0, M = 0;
-    uint64_t gstart[GW_MAX_ROUTES + 1] = {0};
-    int lanes = 0;
+    // The layout (zkv_gset_layout.h route_layout).  The built-in group takes one slot per seal from slot 0; the keyed routes take the key
+    // sets' layout behind it (gset_choose: the mapping their seals would take, stepped to a finer one while the padding exceeds 1.25 times).
+    const size_t n0 = tot[RZR_COL_BUILTIN];
+    size_t placed = 0;
+    for (size_t k = 0; k < K; k++) placed += tot[RZR_COL_KEYED0 + k];
+    const size_t routed = n0 + placed;
     std::unique_lock<std::mutex> glk;
-    if (K) {
-        glk = std::unique_lock<std::mutex>(c->gw_group->mu);
-        size_t placed = 0;
-        for (size_t k = 0; k < K; k++) placed += tot[RZR_COL_KEYED0 + k];
-        routed += placed;
-        uint64_t gslots = 0;
-        lanes = gset_choose(tot + RZR_COL_KEYED0, (uint32_t)K, miller_lanes(c->gw_group, placed), c->gw_group->lanes != 0, gstart, &gslots);
-        M = (size_t)gslots;
-        for (size_t k = 0; k < K; k++) a.start[RZR_COL_KEYED0 + k] = (uint32_t)(G0 + gstart[k]);
-    }
-    a.start[RZR_COL_BUILTIN] = 0;
+    if (K) glk = std::unique_lock<std::mutex>(c->gw_group->mu);
+    uint32_t rec[RZR_COL_KEYED0 + RZR_MAX_KEYED];
+    for (uint32_t& v : rec) v = ZKV_SEAL_BYTES;
+    RouteLayout L;
+    route_layout(tot, (uint32_t)(RZR_COL_KEYED0 + K), RZR_COL_KEYED0, (uint32_t)K, rec, K ? miller_lanes(c->gw_group, placed) : 0,
+                 K && c->gw_group->lanes != 0, &L);
+    for (size_t q = 0; q < RZR_COL_KEYED0 + K; q++) a.start[q] = L.start[q];
     uint64_t isum = 0;
     for (size_t r = 0; r < NB; r++) isum += itot[r];
-    if (routed + tot[RZR_COL_NOT_FOUND] + tot[RZR_COL_SHORT] != n || G0 + M > ns || isum != n0) return ZKV_ERR_HIP;
+    if (routed + tot[RZR_COL_NOT_FOUND] + tot[RZR_COL_SHORT] != n || L.slots > ns || isum != n0) return ZKV_ERR_HIP;
     launch_rzrouter_place(a, s);
     HIP_TRY(hipGetLastError());
     uint8_t *st = c->mx[RZ_ST], *rv = c->mx[RZ_RV];
     if (n0 && (rc = run_router_builtin(c->kid[0], n0, a.c_seals, a.c_len, a.c_inst, a.c_a, d_b ? a.c_b : nullptr, st, rv, s)) != ZKV_OK) return rc;
-    if (routed > n0 && (rc = run_router_group(c, c->gw_group, M, lanes, a, G0, gstart, st, rv, s)) != ZKV_OK) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    // The statuses back to the caller's order, once per run of slots that lie back to back (a keyed route may end in pad slots).
-    size_t lo = 0, hi = n0;
-    for (size_t k = 0; k <= K; k++) {
-        const size_t cnt = k < K ? tot[RZR_COL_KEYED0 + k] : 0, at = k < K ? G0 + (size_t)gstart[k] : 0;
-        if (k < K && !cnt) continue;
-        if (k < K && at == hi) { hi += cnt; continue; }
-        launch_mixed_return(hi - lo, a.idx + lo, st + lo, rv + 4 * lo, d_status, d_recv, s);
-        if (k < K) { lo = at; hi = at + cnt; }
+    if (routed > n0) {                                             // the keyed group: k_rzrouter_prep with the slot's route, then the key sets' stages
+        const size_t G0 = (size_t)L.g0;
+        zkv_ctx* g = c->gw_group;
+        RzrChunk pc;
+        memset(&pc, 0, sizeof pc);
+        pc.idx = a.idx + G0; pc.skey = (uint32_t*)c->mx[RZ_SKEY];
+        pc.recs = a.c_seals + L.b0; pc.len = a.c_len + G0; pc.in_a = a.c_a + 32 * G0; pc.in_b = a.in_b ? a.c_b + 32 * G0 : nullptr;
+        pc.n_keys = (uint32_t)K;
+        for (size_t k = 0; k < K; k++) pc.start[k] = (uint32_t)L.gstart[k];
+        pc.routes = (const RzrRoute*)c->mx[RZ_ROUTES];
+        pc.status = st + G0; pc.recv = (uint32_t*)(rv + 4 * G0);
+        if ((rc = run_keyed_group(g, (size_t)L.m, L.lanes, pc.idx, pc.skey, pc.status, s, [&](const GsetChunk& ch) {
+                keyed_prep_chunk(&pc, ch);
+                launch_rzrouter_prep(pc, c->consts, g->ws, s); })) != ZKV_OK) return rc;
     }
+    HIP_TRY(hipSetDevice(c->device));
+    route_return(L, a.idx, st, rv, d_status, d_recv, s);                 // (a keyed route may end in pad slots)
     HIP_TRY(hipGetLastError());
     if ((rc = mark_done(c, s)) != ZKV_OK) return rc;
     // the counts of the most recent call: only a call that enqueued everything replaces them
@@ -2362,23 +2348,18 @@ static int router_host_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, con
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_device_init(c);
     if (rc != ZKV_OK) return rc;
-    const uint64_t s0 = seal_off[0], sbytes = seal_off[n] - s0;
-    const size_t need[6] = {(size_t)sbytes + 8, 8 * (n + 1), 32 * n, 32 * n, n, 4 * n};
-    for (int k = 0; k < 6; k++) if ((rc = grow(&c->mx[RZ_H_SEALS + k], &c->mx_cap[RZ_H_SEALS + k], need[k])) != ZKV_OK) return rc;
+    const size_t need[4] = {32 * n, 32 * n, n, 4 * n};
+    for (int k = 0; k < 4; k++) if ((rc = grow(&c->mx[RZ_H_A + k], &c->mx_cap[RZ_H_A + k], need[k])) != ZKV_OK) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
-    std::vector<uint64_t> so(seal_off, seal_off + n + 1);
-    for (auto& v : so) v -= s0;
-    if (sbytes) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_SEALS], seal_blob + s0, (size_t)sbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_OFF], so.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+    std::vector<uint64_t> so;
+    uint64_t sbytes = 0;
+    if ((rc = stage_ragged(c, RZ_H_SEALS, RZ_H_OFF, seal_blob, seal_off, n, &so, s, &sbytes)) != ZKV_OK) return rc;
     HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
     if (in_b) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_B], in_b, 32 * n, hipMemcpyHostToDevice, s));
     if ((rc = run_router(c, n, c->mx[RZ_H_SEALS], (const uint64_t*)c->mx[RZ_H_OFF], sbytes, c->mx[RZ_H_A], in_b ? c->mx[RZ_H_B] : nullptr,
                          c->mx[RZ_H_ST], c->mx[RZ_H_RV], s)) != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(status, c->mx[RZ_H_ST], n, hipMemcpyDeviceToHost, s));
-    if (recv) HIP_TRY(hipMemcpyAsync(recv, c->mx[RZ_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return ZKV_OK;
+    return return_to_host(c, RZ_H_ST, RZ_H_RV, n, status, recv, s);
 }
 ZKV_EXPORT int zkv_risc0_router_verify_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* image_ids,
                                              const uint8_t* journal_digests, uint8_t* status, uint8_t* recv) {
@@ -2418,13 +2399,7 @@ ZKV_EXPORT int zkv_risc0_router_last_route_counts(zkv_ctx* c, uint64_t* out) {
 ZKV_EXPORT int zkv_risc0_router_status_abi_encode(const zkv_ctx* c, uint8_t status, const uint8_t received[4], uint8_t out[68]) {
     if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
     if (!out) return ZKV_ERR_INVALID_ARG;
-    if (status == ZKV_STATUS_ROUTE_NOT_FOUND) {                 // SelectorUnknown(bytes4): selector, then the bytes4 left-aligned in a word
-        if (!received) return ZKV_ERR_INVALID_ARG;
-        memset(out, 0, 36);
-        host::fn_selector("SelectorUnknown(bytes4)", out);
-        memcpy(out + 4, received, 4);
-        return 36;
-    }
+    if (status == ZKV_STATUS_ROUTE_NOT_FOUND) return received ? abi_encode_error_bytes4("SelectorUnknown(bytes4)", received, out) : ZKV_ERR_INVALID_ARG;
     uint8_t expected[4];
     be32_put(expected, c->gw_sel[0]);
     return zkv_status_abi_encode(ZKV_VM_RISC0, status, received, expected, out);
@@ -3352,20 +3327,8 @@ static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
     }
     for (size_t base = R; base < M; base += cap) {
         const size_t m = M - base < cap ? M - base : cap;
-        const bool timed = base + cap >= M;
         const GsetChunk ch = gset_chunk_of(c, p, d_proofs, d_signals, base, m);
-        if (timed) (void)hipEventRecord(c->ev[0], s);
-        launch_gset_prep(ch, c->ws, s);
-        if (timed) (void)hipEventRecord(c->ev[1], s);
-        launch_gset_msm(ch, msm_lanes_long(c, m), c->ws, s);
-        if (timed) (void)hipEventRecord(c->ev[2], s);
-        if (lanes != 2) launch_g2chk2(m, c->ws, ch.status, s);       // (the lane-pair Miller loop is the subgroup test itself)
-        if (timed) (void)hipEventRecord(c->ev[3], s);
-        launch_gset_miller(lanes, m, p.skey + base, c->d_gs_key, c->ws, ch.status, s);
-        if (timed) (void)hipEventRecord(c->ev[4], s);
-        launch_finalexp_lanes(lanes, m, c->ws, ch.status, s);
-        if (timed) (void)hipEventRecord(c->ev[5], s);
-        HIP_TRY(hipGetLastError());
+        if ((rc = gset_proof_stages(c, ch, lanes, base + cap >= M, s, [&] { launch_gset_prep(ch, c->ws, s); })) != ZKV_OK) return rc;
     }
     return set_return(c, n, M, p, d_verified, s);
 }

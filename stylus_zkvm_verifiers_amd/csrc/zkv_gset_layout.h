@@ -38,6 +38,45 @@ inline int gset_choose(const uint32_t* cnt, uint32_t n_keys, int lanes, int fixe
     }
 }
 
+// Selector routers (the SP1 gateway and the RISC Zero router; DESIGN.md sections 12d and 17): the slots and compact records of one call.
+// The demultiplexer counts the items of n_cols routed columns, tot[c] each with records of rec[c] bytes.  Columns [key0, key0 + n_keyed)
+// are the keyed routes: together one key set, laid out by gset_choose from the mapping `lanes` their items would take (`fixed`: the
+// caller's own choice, kept), so every keyed column starts on gset_align_of_lanes slots of the group's first slot and may end in pad
+// slots; their records are rec[key0] bytes each, pad slots included.  Every other column takes one slot per item.  Columns lie in
+// column order, slots and bytes back to back.
+constexpr uint32_t ROUTE_MAX_COLS = 16;
+struct RouteLayout {
+    uint32_t start[ROUTE_MAX_COLS];                 // first slot of column c
+    uint64_t base[ROUTE_MAX_COLS];                  // byte offset of its first record
+    uint64_t g0, b0, m, gstart[ROUTE_MAX_COLS + 1]; // keyed group: first slot, byte offset, slots (pads included), first slot of every key in the group
+    int lanes;                                      // ... and its Miller mapping (0 without keyed columns)
+    uint64_t slots, bytes;                          // of the call
+    uint32_t n_runs;                                // runs of live slots that lie back to back, in slot order: [run_at[q], run_at[q] + run_n[q])
+    uint64_t run_at[ROUTE_MAX_COLS], run_n[ROUTE_MAX_COLS];
+};
+inline void route_layout(const uint32_t* tot, uint32_t n_cols, uint32_t key0, uint32_t n_keyed, const uint32_t* rec, int lanes, int fixed, RouteLayout* L) {
+    uint64_t slots = 0, bytes = 0;
+    L->g0 = L->b0 = L->m = 0; L->lanes = 0; L->n_runs = 0;
+    for (uint32_t k = 0; k <= ROUTE_MAX_COLS; k++) L->gstart[k] = 0;
+    for (uint32_t c = 0; c < n_cols; c++) {
+        if (n_keyed && c == key0) {
+            L->lanes = gset_choose(tot + key0, n_keyed, lanes, fixed, L->gstart, &L->m);
+            L->g0 = slots; L->b0 = bytes;
+        }
+        if (c >= key0 && c < key0 + n_keyed) {
+            L->start[c] = (uint32_t)(L->g0 + L->gstart[c - key0]); L->base[c] = L->b0 + (uint64_t)rec[key0] * L->gstart[c - key0];
+            if (c + 1 == key0 + n_keyed) { slots = L->g0 + L->m; bytes = L->b0 + (uint64_t)rec[key0] * L->m; }
+        } else {
+            L->start[c] = (uint32_t)slots; L->base[c] = bytes;
+            slots += tot[c]; bytes += (uint64_t)tot[c] * rec[c];
+        }
+        if (!tot[c]) continue;
+        if (L->n_runs && L->run_at[L->n_runs - 1] + L->run_n[L->n_runs - 1] == L->start[c]) L->run_n[L->n_runs - 1] += tot[c];
+        else { L->run_at[L->n_runs] = L->start[c]; L->run_n[L->n_runs] = tot[c]; L->n_runs++; }
+    }
+    L->slots = slots; L->bytes = bytes;
+}
+
 // PLONK key sets (zkv_plonk_set_*).  PREP runs one proof per lane, so every key group starts on a multiple of 64
 // slots (one PREP wavefront); every Miller wavefront (32, 4 or 1 proofs) then holds one key as well.  The Miller mapping is the single-key
 // PLONK policy of enqueue_chunk applied to the n placed proofs: one wavefront per proof at or below wave_below or when the caller fixed

@@ -4,6 +4,9 @@
 // on the CPU (plain and under the sanitizers).
 #pragma once
 #include "zkv_verify.h"
+#if defined(__HIPCC__)
+#include "zkv_internal.h"
+#endif
 
 namespace zkv {
 
@@ -54,5 +57,61 @@ ZKV_HD uint32_t gwset_key_of_slot(const uint32_t* start, uint32_t n_keys, uint32
     for (uint32_t q = 1; q < n_keys; q++) if (start[q] <= j) k = q;
     return k;
 }
+
+#if defined(__HIPCC__)
+// The PREP kernel of a keyed group (k_gwset_prep, k_rzrouter_prep), one slot per lane: everything around the unit's slot function.
+// Records are 260-byte rows from a 4-byte aligned base (the caller's own allocation; every record before the group's is a multiple of 4
+// bytes), so the 64 rows of a wavefront are 16,640 contiguous bytes: copied to LDS with coalesced dword loads, every lane then reads its
+// own 65 words (row stride 65 dwords: conflict-free), as k_prep_sp1 stages fixed-stride seals.  The address test is wave-uniform; a base
+// that fails it is read byte by byte.  Then the key of the slot (skey, for k_gset_msm / k_gset_miller), and for a live slot
+// slot_fn(chunk, key, slot, record, r) -- the unit's checks, filling a Slot with NSIG signals --, the signals staged as GsetChunk::sig, the
+// points where k_gset_msm reads them, flags, status and the (zero) received selector.  Chunk: GwsetChunk or RzrChunk (zkv_internal.h);
+// lds: ZKV_BLOCK * 65 words of the kernel's.
+template <int NSIG, class Slot, class Chunk, class F>
+__device__ __forceinline__ void gwset_prep_lane(const Chunk& c, const Workspace& ws, uint32_t* lds, F slot_fn) {
+    const size_t b0 = (size_t)blockIdx.x * ZKV_BLOCK;
+    const uint8_t* rows = c.recs + (c.slot0 + b0) * 260;
+    const bool staged = !((uintptr_t)c.recs & 3u);
+    if (staged) {
+        const size_t mm = c.m - b0 < ZKV_BLOCK ? c.m - b0 : ZKV_BLOCK;
+        const uint32_t* src = (const uint32_t*)rows;
+        const uint32_t total = (uint32_t)mm * 65u;
+#pragma unroll 1
+        for (uint32_t t = threadIdx.x; t < total; t += ZKV_BLOCK) lds[t] = src[t];
+        __syncthreads();
+    }
+    const size_t j = b0 + threadIdx.x;
+    if (j >= c.m) return;
+    const size_t slot = c.slot0 + j;
+    const uint32_t k = gwset_key_of_slot(c.start, c.n_keys, (uint32_t)slot);
+    c.skey[slot] = k;
+    const uint32_t i = c.idx[slot];
+    uint32_t flags = 0;
+    uint8_t st = ST_VERIFICATION_FAILED;
+    if (i != GW_NONE) {                                             // (a pad slot carries nothing: every stage skips it)
+        GwsetRec rd;
+        rd.row = staged ? lds + threadIdx.x * 65u : nullptr;
+        rd.rec = rows + (size_t)threadIdx.x * 260;
+        Slot r;
+        slot_fn(c, k, slot, rd, r);
+#pragma unroll
+        for (int b = 0; b < NSIG; b++) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) c.sig[(size_t)(8 * b + q) * c.sig_cap + j] = r.sig[b][q];
+        }
+        if (r.flags & FL_ALIVE) {
+            ws_st(ws.prep, ws.cap, 0, j, r.o.ax); ws_st(ws.prep, ws.cap, 8, j, r.o.ay);
+            ws_st(ws.prep, ws.cap, 16, j, r.o.cx); ws_st(ws.prep, ws.cap, 24, j, r.o.cy);
+            ws_st(ws.prep, ws.cap, 32, j, r.o.bx.c0); ws_st(ws.prep, ws.cap, 40, j, r.o.bx.c1);
+            ws_st(ws.prep, ws.cap, 48, j, r.o.by.c0); ws_st(ws.prep, ws.cap, 56, j, r.o.by.c1);
+        }
+        flags = r.flags; st = r.status;
+    }
+    ws.flags[j] = flags;
+    ws.g2bad[j] = 0;
+    c.status[slot] = st;
+    c.recv[slot] = 0;                                               // the route has the selector: nothing received to report
+}
+#endif
 
 }  // namespace zkv

@@ -251,6 +251,33 @@ def test_several_releases_in_one_call(router, several, lanes):
     router.set_lanes_per_proof(0)
 
 
+@pytest.mark.gpu
+def test_several_count_blocks_and_a_chunked_keyed_group(zkv, router, several, keys, builtin_params, monkeypatch):
+    """The 179 seals four times over under a seeded permutation: 716 seals are three 256-seal count blocks, so a slot is its route's first
+    slot plus the scanned counts of the blocks in front plus the rank in its own block; the keyed groups hold 4, 132 and 128 seals.  Then
+    a router created with 64-slot chunks: the built-in group runs in 7 chunks and the keyed group in 5 or more, on both ends of the
+    mappings (one wavefront per proof pads nothing, lane pairs pad every group to 32)."""
+    model, items, (want_st, want_rv, route) = several
+    perm = list(range(4 * len(items)))
+    random.Random(0x17B8).shuffle(perm)
+    idx = [p % len(items) for p in perm]
+    big = [items[i] for i in idx]
+    want = (want_st[idx], [want_rv[i] for i in idx], route[idx])
+    counts = [4 * c for c in rm.counts(route, 6)]
+    assert len(big) == 716 and counts[:6] == [256, 128, 36, 4, 132, 128] and rm.counts(want[2], 6) == counts
+    _check(router.verify_batch(*_cols(big)), want, 'defaults')
+    assert router.last_route_counts() == counts
+    monkeypatch.setenv('ZKV_CHUNK', '64')
+    rt = zkv.RiscZeroRouter(builtin_params, [k.triple() for k in keys])
+    try:
+        for lanes in (0, 2):
+            rt.set_lanes_per_proof(lanes)
+            _check(rt.verify_batch(*_cols(big)), want, ('64-slot chunks', lanes))
+            assert rt.last_route_counts() == counts
+    finally:
+        rt.close()
+
+
 # ---------------------------------------------------------------- 3. verify_integrity and the device-resident call
 @pytest.fixture(scope='module')
 def several_integrity(real, keys, builtin_params):

@@ -222,6 +222,49 @@ def test_every_kind_of_route_in_one_shuffled_batch(mixed_gateway, mixed_batch, k
     gw.set_lanes_per_proof(0)
 
 
+@pytest.mark.gpu
+def test_several_count_blocks_and_a_chunked_keyed_group(zkv, mixed_gateway, mixed_batch, keys, plonk, monkeypatch):
+    """The mixed batch seven times over under a seeded permutation: 595 proofs are three 256-proof count blocks, so a slot is its route's
+    first slot plus the scanned counts of the blocks in front plus the rank in its own block; the keyed groups hold 7, 231 and 217 proofs.
+    Through the host entry; through the device-resident one, which takes one public-values length per call, on the proofs of the most
+    common length repeated past 512 (three count blocks there too); then on a gateway created with 64-slot chunks, whose keyed group
+    runs in 8 chunks."""
+    gw, sels, (want_st, want_rv, route) = mixed_gateway
+    items = mixed_batch[0]
+    reps = 7
+    perm = list(range(reps * len(items)))
+    random.Random(0x12DF).shuffle(perm)
+    idx = [p % len(items) for p in perm]
+    big = [items[i] for i in idx]
+    big_st, big_rv, big_route = want_st[idx], [want_rv[i] for i in idx], route[idx]
+    counts = [reps * c for c in gm.counts(route, 5)]
+    assert len(big) == 595 > 512 and counts[1:4] == [7, 231, 217] and gm.counts(big_route, 5) == counts
+
+    def check(g, what):
+        st, rv = g.verify_batch([v for v, _, _ in big], [w for _, w, _ in big], [p for _, _, p in big])
+        bad = np.nonzero(st != big_st)[0]
+        assert not len(bad), (what, bad.tolist(), big_route[bad].tolist(), st[bad].tolist(), big_st[bad].tolist())
+        assert [bytes(x) for x in rv] == big_rv, what
+        assert g.last_route_counts() == counts, what
+    check(gw, 'defaults')
+    lens = [len(w) for _, w, _ in items]
+    common = max(sorted(set(lens)), key=lens.count)
+    same = [i for i in range(len(items)) if lens[i] == common]
+    sub = [same[p % len(same)] for p in perm if p < len(same) * (512 // len(same) + 1)]
+    assert len(sub) > 512 and all(c > 0 for c in gm.counts(route[sub], 5)[1:4])     # every keyed route, in more than two count blocks
+    dst, drv = _dev_call(gw, [items[i][0] for i in sub], [items[i][1] for i in sub], [items[i][2] for i in sub])
+    assert dst.tolist() == want_st[sub].tolist()
+    assert [bytes(x) for x in drv] == [want_rv[i] for i in sub]
+    assert gw.last_route_counts() == gm.counts(route[sub], 5)
+    monkeypatch.setenv('ZKV_CHUNK', '64')
+    A, B, Cc = keys
+    g64 = zkv.Sp1Gateway(True, [plonk[1]], groth16_keys=[(k.words, k.hash) for k in (A, B, Cc)])
+    try:
+        check(g64, '64-slot chunks')
+    finally:
+        g64.close()
+
+
 # ---------------------------------------------------------------- 3. an invalid key fails its own route only
 @pytest.mark.gpu
 def test_a_key_with_an_off_curve_ic_point_fails_its_own_route_only(zkv, keys, mixed_batch, mixed_gateway, plonk):
