@@ -22,9 +22,16 @@
 #if defined(ZKV_COUNT_FP_MUL)
 static thread_local unsigned long long zkv_fp_mul_counter = 0;      // per thread: the lane-pair host emulation runs two
 static thread_local unsigned long long zkv_mad_counter = 0;         // 32 x 32 + 64 multiply-adds (v_mad_u64_u32 on the device) issued by the multipliers
-#define ZKV_COUNT_MADS(n) (zkv_mad_counter += (n))
+// ... and every one the build issues, those included that zkv_mad_counter is not charged: the fused variable-line product of the
+// lane-pair Miller loop (f12m_mul_by_034_body, zkv_tower_mem.h) is charged the Karatsuba form it replaced, so that the work figure of
+// the bench line (tests/golden/stage_mul_counts.json) stays what it was; this counter states what k_miller2 really issues, and
+// tests/test_miller_var_line_host.py pins the difference of the two.
+static thread_local unsigned long long zkv_mad_issued_counter = 0;
+#define ZKV_COUNT_MADS(n) (zkv_mad_counter += (n), zkv_mad_issued_counter += (n))
+#define ZKV_COUNT_MADS_ISSUED(n) (zkv_mad_issued_counter += (n))
 #else
 #define ZKV_COUNT_MADS(n) ((void)0)
+#define ZKV_COUNT_MADS_ISSUED(n) ((void)0)
 #endif
 
 // constant tables that are indexed at run time: namespace-scope device constants (a function-local array would be built on the stack)
@@ -220,13 +227,35 @@ ZKV_HD void fp_unpack29(const Fp& a, uint32_t x[9]) {            // 8 x 32 -> 9 
         x[k] = v & 0x1fffffffu;
     }
 }
+// Column updates.  col_add: a non-negative term (a product of two limbs) enters a column; col_carry: the carry out of the column below.
+// Host check builds (-DZKV_SHADOW_COLS, tests/host_sim) form every update again in 128 bits and count the updates whose 64-bit result
+// differs from it: by induction a column then never differs from a 128-bit shadow of itself, which is what the bounds stated at the
+// multipliers promise (zkv_col_shadow_bad stays 0).
+#if defined(ZKV_SHADOW_COLS) && !defined(__HIP_DEVICE_COMPILE__)
+static thread_local unsigned long long zkv_col_shadow_ops = 0, zkv_col_shadow_bad = 0;
+inline void zkv_col_shadow(uint64_t c, uint64_t t) {
+    zkv_col_shadow_ops++;
+    if ((unsigned __int128)c + (unsigned __int128)t != (unsigned __int128)(uint64_t)(c + t)) zkv_col_shadow_bad++;
+}
+inline void zkv_col_shadow(int64_t c, __int128 t) {
+    zkv_col_shadow_ops++;
+    if ((__int128)c + t != (__int128)(int64_t)((uint64_t)c + (uint64_t)(int64_t)t)) zkv_col_shadow_bad++;
+}
+#define ZKV_COL_SHADOW(c, t) zkv_col_shadow(c, t)
+#else
+#define ZKV_COL_SHADOW(c, t) ((void)0)
+#endif
+ZKV_HD uint64_t col_add(uint64_t c, uint64_t t) { ZKV_COL_SHADOW(c, t); return c + t; }
+ZKV_HD int64_t col_add(int64_t c, uint64_t t) { ZKV_COL_SHADOW(c, (__int128)t); return (int64_t)((uint64_t)c + t); }
+ZKV_HD uint64_t col_carry(uint64_t c, uint64_t carry) { ZKV_COL_SHADOW(c, carry); return c + carry; }
+ZKV_HD int64_t col_carry(int64_t c, int64_t carry) { ZKV_COL_SHADOW(c, (__int128)carry); return (int64_t)((uint64_t)c + (uint64_t)carry); }
 template <typename COL>
 ZKV_HD void fp_mac81(COL col[18], const uint32_t x[9], const uint32_t y[9]) {   // col += x * y, 81 independent-column MACs
     ZKV_COUNT_MADS(81);
 #pragma unroll
     for (int i = 0; i < 9; i++) {
 #pragma unroll
-        for (int j = 0; j < 9; j++) col[i + j] = (COL)((uint64_t)col[i + j] + (uint64_t)x[i] * y[j]);
+        for (int j = 0; j < 9; j++) col[i + j] = col_add(col[i + j], (uint64_t)x[i] * y[j]);
     }
 }
 // Montgomery reduction of an 18-column value V >= 0 (V = sum col[k] 2^(29k)): returns V * 2^-261 mod p in the loose range:
@@ -241,13 +270,13 @@ ZKV_HD void fp_reduce_cols_limbs(COL col[18], uint32_t (&r)[9]) {
     for (int i = 0; i < 9; i++) {                 // one 29-bit digit per step
         uint32_t m = ((uint32_t)col[i] * ZKV_FP_INV29) & M29;
 #pragma unroll
-        for (int j = 0; j < 9; j++) col[i + j] = (COL)((uint64_t)col[i + j] + (uint64_t)m * P29[j]);
-        col[i + 1] += col[i] >> 29;               // low 29 bits of col[i] are now zero; arithmetic shift when signed
+        for (int j = 0; j < 9; j++) col[i + j] = col_add(col[i + j], (uint64_t)m * P29[j]);
+        col[i + 1] = col_carry(col[i + 1], (COL)(col[i] >> 29));      // low 29 bits of col[i] are now zero; arithmetic shift when signed
     }
 #pragma unroll
     for (int k = 9; k < 17; k++) {
         r[k - 9] = (uint32_t)col[k] & M29;
-        col[k + 1] += col[k] >> 29;
+        col[k + 1] = col_carry(col[k + 1], (COL)(col[k] >> 29));
     }
     r[8] = (uint32_t)col[17];
 }
@@ -307,9 +336,9 @@ Fp fp_sqr(Fp a) {
     for (int k = 0; k < 18; k++) col[k] = 0;
 #pragma unroll
     for (int i = 0; i < 9; i++) {
-        col[2 * i] += (uint64_t)x[i] * x[i];
+        col[2 * i] = col_add(col[2 * i], (uint64_t)x[i] * x[i]);
 #pragma unroll
-        for (int j = i + 1; j < 9; j++) col[i + j] += (uint64_t)d[i] * x[j];
+        for (int j = i + 1; j < 9; j++) col[i + j] = col_add(col[i + j], (uint64_t)d[i] * x[j]);
     }
     return fp_reduce_cols(col);
 }
@@ -590,6 +619,81 @@ ZKV_HD Fp f2_dot2_limbs(const uint32_t (&ao)[9], const uint32_t (&ap)[9], const 
     for (int k = 0; k < 18; k++) col[k] = 0;
     fp_mac81(col, ao, bU); fp_mac81(col, ap, bV); fp_mac81(col, co, dU); fp_mac81(col, cp, dV);
     return fp_reduce_cols(col);
+}
+// a b + c d + e f with ONE Montgomery reduction per lane: six 81-term column products (the variable-line product of the Miller loop,
+// whose every output is a sum of three products).  All six operands must be reduced values (< 2p: limbs < 2^29 after unpacking).
+// Range, in units of 2^58 per column: an Fp2 product adds at most 9 (own x U) + 18 (partner x V; the 8p - x limbs of the even lane are
+// below 2^30) = 27 on the even lane and 18 on the odd one.  Two products: at most 54, and with the 9 reduction terms a third does not fit
+// the 64 units of a column.  So after the second product one exact carry pass (fp_cols_carry32) moves the high word of every column into
+// the next one: columns 0 .. 16 are then below 2^32 + 54 * 2^29 < 2^36 (column 17, empty after a 9 x 9 product, takes the rest: below
+// 2^35), and the third product (27), the reduction terms (9) and the reduction's carries (below 2^36) fit: 36 * 2^58 + 2^37 < 2^64.
+// The value is at most 3 (4 p^2 + 16 p^2) = 60 p^2 < 169 p^2.
+// The pass works on 32-bit words (2^32 = 8 * 2^29: col[k + 1] += 8 * (col[k] >> 32), col[k] &= 2^32 - 1) rather than on 29-bit digits: the
+// words of a column are its two registers, so no shift or mask is issued, only one multiply-add and one move per column.
+// The sum comes in two halves, f2_dot3_first (two products and the carry pass) and f2_dot3_last (the third product and the reduction),
+// and the caller loads and prepares one operand of the third product BETWEEN them.  That order is what keeps the compiler from undoing
+// the scheme: it re-associates a column's chain of additions by the rank of its terms, and terms whose operands were loaded before the
+// carried column was formed are summed first, from zero, in a second set of 18 columns to which the carried one is added at the end --
+// 36 more live registers, which the callers do not have.  (For the same reason the carried column passes through an empty volatile asm,
+// which gives it its rank by position, and the factor 8 through another, so that the compiler issues ONE multiply-add of its own per
+// column instead of a 64-bit shift, a mask and an add.  Neither asm holds an instruction: every instruction of the pass is the compiler's,
+// with the compiler's own hazard handling.)
+// These devices and the pin and barrier at the end of f2_dot3_last depend on the compiler: after a toolchain change re-read the resource
+// report of the kernels that inline the callers (k_miller2: 232 VGPRs, 0 bytes of scratch, profiles/miller_var_line_ab.txt).
+ZKV_HD void fp_cols_carry32(uint64_t (&col)[18]) {
+    uint32_t eight = 8u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(eight));                          // no instruction: a factor the compiler cannot turn into a 64-bit shift and add
+#endif
+#pragma unroll
+    for (int k = 17; k >= 1; k--) {
+        const uint32_t hi = (uint32_t)(col[k - 1] >> 32);
+        uint64_t keep = k == 17 ? col[17] : (uint64_t)(uint32_t)col[k];
+        ZKV_COUNT_MADS_ISSUED(1);
+        col[k] = col_add(keep, (uint64_t)hi * eight);
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(col[k]));                     // no instruction: the carried column is formed HERE (see above)
+#endif
+    }
+    col[0] = (uint64_t)(uint32_t)col[0];
+}
+// Host check builds assert the operand contract of the two halves as well: multiplicand limbs and U below 2^29 (reduced values), V
+// below 2^30 (8p - x on the even lane); a violation counts like a column that left its 128-bit value.
+#if defined(ZKV_SHADOW_COLS) && !defined(__HIP_DEVICE_COMPILE__)
+inline void zkv_dot3_operands(const uint32_t (&xo)[9], const uint32_t (&xp)[9], const uint32_t (&U)[9], const uint32_t (&V)[9]) {
+    for (int i = 0; i < 9; i++)
+        if ((xo[i] >> 29) || (xp[i] >> 29) || (U[i] >> 29) || (V[i] >> 30)) zkv_col_shadow_bad++;
+}
+#define ZKV_DOT3_OPERANDS(a, b, c, d) zkv_dot3_operands(a, b, c, d)
+#else
+#define ZKV_DOT3_OPERANDS(a, b, c, d) ((void)0)
+#endif
+ZKV_HD void f2_dot3_first(uint64_t (&col)[18], const uint32_t (&ao)[9], const uint32_t (&ap)[9], const uint32_t (&bU)[9], const uint32_t (&bV)[9],
+                          const uint32_t (&co)[9], const uint32_t (&cp)[9], const uint32_t (&dU)[9], const uint32_t (&dV)[9]) {
+#if defined(ZKV_COUNT_FP_MUL)
+    zkv_fp_mul_counter += 4;
+#endif
+    ZKV_DOT3_OPERANDS(ao, ap, bU, bV); ZKV_DOT3_OPERANDS(co, cp, dU, dV);
+#pragma unroll
+    for (int k = 0; k < 18; k++) col[k] = 0;
+    fp_mac81(col, ao, bU); fp_mac81(col, ap, bV); fp_mac81(col, co, dU); fp_mac81(col, cp, dV);
+    fp_cols_carry32(col);
+}
+ZKV_HD Fp f2_dot3_last(uint64_t (&col)[18], const uint32_t (&eo)[9], const uint32_t (&ep)[9], const uint32_t (&fU)[9], const uint32_t (&fV)[9]) {
+#if defined(ZKV_COUNT_FP_MUL)
+    zkv_fp_mul_counter += 2;
+#endif
+    ZKV_DOT3_OPERANDS(eo, ep, fU, fV);
+    fp_mac81(col, eo, fU); fp_mac81(col, ep, fV);
+    Fp r = fp_reduce_cols(col);
+    // Nothing is scheduled across the end of a sum: its reduction is a serial chain, and left alone the scheduler fills it with the
+    // multiply-adds of the caller's NEXT sum -- two sets of 18 columns with their operands, more than the callers' registers hold.
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int k = 0; k < 8; k++) asm volatile("" : "+v"(r.v[k]));
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+    return r;
 }
 // one product from prepared operands (what f2_mul_lane computes; the multiplicand and multiplier may be lazy sums below 4p)
 ZKV_HD Fp f2_mul_limbs(const uint32_t (&ao)[9], const uint32_t (&ap)[9], const uint32_t (&bU)[9], const uint32_t (&bV)[9]) {

@@ -79,6 +79,34 @@ template <class R> ZKV_HD void m_st_f2(R m, int idx, const Fp2& a) { m_st_fp(m, 
 template <class R> ZKV_HD Fp2 m_ld_f2(R m, int idx) { Fp2 r; r.c0 = m_ld_fp(m, 16 * idx); r.c1 = m_ld_fp(m, 16 * idx + 8); return r; }
 template <class R> ZKV_HD void m_st_f2(R m, int idx, const Fp2& a) { m_st_fp(m, 16 * idx, a.c0); m_st_fp(m, 16 * idx + 8, a.c1); }
 #endif
+// m_ld_f2_again(ref, idx): coefficient idx read AGAIN, as a value the compiler cannot tell from new: where a routine unpacks and exchanges a
+// coefficient a second time because the registers do not hold the first copy that long, common-subexpression elimination would otherwise
+// merge the two preparations into one and keep its eighteen limbs live in between (f12m_mul_by_034_body).  No instruction is issued for it.
+// m_again makes the reference itself opaque for LRef only (the slots of the device kernels that inline that body); for every other slot
+// kind it is the identity and only the loaded words are pinned: the result is the same, the registers are not (the load may then be
+// merged with the first one and its eight packed words kept instead of read again).
+#if defined(ZKV_PAIRED)
+template <class R> ZKV_HD R m_again(R r) { return r; }
+ZKV_HD LRef m_again(LRef r) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(r.p));
+#endif
+    return r;
+}
+ZKV_HD void f2_pin(Fp2& a) {                     // a is formed where this stands (no instruction)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int k = 0; k < 8; k++) asm volatile("" : "+v"(a.h.v[k]));
+#else
+    (void)a;
+#endif
+}
+template <class R> ZKV_HD Fp2 m_ld_f2_again(R m, int idx) {
+    Fp2 r = m_ld_f2(m_again(m), idx);
+    f2_pin(r);
+    return r;
+}
+#endif
 template <class R> ZKV_HD Fp6 m_ld_f6(R m, int idx) { Fp6 r; r.c0 = m_ld_f2(m, idx); r.c1 = m_ld_f2(m, idx + 1); r.c2 = m_ld_f2(m, idx + 2); return r; }
 template <class R> ZKV_HD void m_st_f6(R m, int idx, const Fp6& a) { m_st_f2(m, idx, a.c0); m_st_f2(m, idx + 1, a.c1); m_st_f2(m, idx + 2, a.c2); }
 // An Fp12 slot is six Fp2 coefficients g0 g1 g2 h0 h1 h2.
@@ -410,10 +438,68 @@ template <class RD, class RA, class RB> ZKV_HD_NI void f12m_mul(RD d, RA a, RB b
 template <class RD, class RA, class RB> ZKV_HD_NI void f12m_mul_conj(RD d, RA a, RB b) { f12m_mul_body(d, a, b, true); }
 // f <- f * (c0 + (c3 + c4 v) w)
 #if defined(ZKV_PAIRED)
-// Lane pairs: the thirteen Karatsuba products inlined, with the multipliers c0 and c4 (three and four products) and the multiplicands
-// h2 and g2 + h2 (two each) unpacked and exchanged once: k_miller2 112.5 -> 110.7 ms.  (Keeping c3 and c0 + c3 prepared as well needs
-// 36 more registers and spilled: 115.9 ms.)
+// Lane pairs.  With the coefficients of f taken as powers of w (memory order g0 g1 g2 h0 h1 h2 = w^0 w^2 w^4 w^1 w^3 w^5, w^6 = xi) every
+// output of f (c0 + c3 w + c4 w^3) is exactly THREE products, out[w^k] = f[w^k] c0 + f[w^(k-1)] c3 + f[w^(k-3)] c4 with the xi of a
+// wrapped index put on the line coefficient:
+//   h2' = h2 c0 + g2 c3 + g1 c4      h1' = h1 c0 + g1 c3 + g0 c4         g2' = g2 c0 + h1 c3 + h0 c4
+//   h0' = h0 c0 + g0 c3 + g2 (xi c4) g1' = g1 c0 + h0 c3 + h2 (xi c4)    g0' = g0 c0 + h2 (xi c3) + h1 (xi c4)
+// so the six outputs are six fused three-product sums (f2_dot3_first / f2_dot3_last: one reduction each, one carry pass over the
+// columns after the second product) instead of thirteen Karatsuba products: 3,402 multiply-adds per lane against 3,159, but 6 instead of 13 reduce / pack
+// sets, none of Karatsuba's fifteen modular additions (carry chains with their wait states), and operands prepared once where the
+// registers allow.  Taken in the order above only three multiplier forms are live at a time (c0 throughout; c3 until xi c3 replaces it
+// for the last output; c4 for the first three outputs, xi c4 for the last three), against the four of f12m_mul_by_134_body, which
+// leaves room for the multiplicands: at most four of them are live at a time, g2 and h0 are prepared once, g0, g1, h1 and h2 twice.
+// An output is stored as soon as the last reader of the coefficient it replaces has run.  6,537 -> 5,493 instructions a step,
+// k_miller2 91.2 -> 87.0 ms per 2^20 proofs (profiles/miller_var_line_ab.txt).
+// Operands: f, c0, c3, c4 reduced values (< 2p), as f2_dot3_first asks; f2_mul_xi returns reduced values.
 template <class RF> ZKV_HD void f12m_mul_by_034_body(RF f, const Fp2& c0, const Fp2& c3, const Fp2& c4) {
+    uint32_t lU[9], lV[9], aU[9], aV[9], bU[9], bV[9];                  // c0;  c3, then xi c3;  c4, then xi c4
+    f2_limbs_y(c0.h, lU, lV); f2_limbs_y(c3.h, aU, aV); f2_limbs_y(c4.h, bU, bV);
+    uint32_t g0o[9], g0p[9], g1o[9], g1p[9], g2o[9], g2p[9], h0o[9], h0p[9], h1o[9], h1p[9], h2o[9], h2p[9];
+    uint64_t col[18];
+    Fp2 nh1, nh2, o;
+    f2_limbs_x(m_ld_f2(f, 2).h, g2o, g2p); f2_limbs_x(m_ld_f2(f, 1).h, g1o, g1p);
+    f2_dot3_first(col, g2o, g2p, aU, aV, g1o, g1p, bU, bV);
+    f2_limbs_x(m_ld_f2(f, 5).h, h2o, h2p);
+    nh2.h = f2_dot3_last(col, h2o, h2p, lU, lV);
+    f2_limbs_x(m_ld_f2(f, 0).h, g0o, g0p);
+    f2_dot3_first(col, g1o, g1p, aU, aV, g0o, g0p, bU, bV);
+    f2_limbs_x(m_ld_f2(f, 4).h, h1o, h1p);
+    nh1.h = f2_dot3_last(col, h1o, h1p, lU, lV);
+    f2_dot3_first(col, h1o, h1p, aU, aV, g2o, g2p, lU, lV);
+    f2_limbs_x(m_ld_f2(f, 3).h, h0o, h0p);
+    o.h = f2_dot3_last(col, h0o, h0p, bU, bV);                                              // g2', held until h0' has read g2
+    {
+        Fp2 nh0, x4 = f2_mul_xi(c4);
+        f2_dot3_first(col, g0o, g0p, aU, aV, h0o, h0p, lU, lV);
+        f2_pin(x4); f2_limbs_y(x4.h, bU, bV);
+        nh0.h = f2_dot3_last(col, g2o, g2p, bU, bV);
+        m_st_f2(f, 2, o);
+        f2_limbs_x(m_ld_f2_again(f, 5).h, h2o, h2p);
+        m_st_f2(f, 5, nh2);
+        f2_dot3_first(col, h0o, h0p, aU, aV, h2o, h2p, bU, bV);
+        f2_limbs_x(m_ld_f2_again(f, 1).h, g1o, g1p);
+        o.h = f2_dot3_last(col, g1o, g1p, lU, lV);                                          // g1'
+        m_st_f2(f, 3, nh0); m_st_f2(f, 1, o);
+    }
+    { const Fp2 x3 = f2_mul_xi(c3); f2_limbs_y(x3.h, aU, aV); }
+    f2_limbs_x(m_ld_f2_again(f, 4).h, h1o, h1p);
+    m_st_f2(f, 4, nh1);
+    f2_dot3_first(col, h2o, h2p, aU, aV, h1o, h1p, bU, bV);
+    f2_limbs_x(m_ld_f2_again(f, 0).h, g0o, g0p);
+    o.h = f2_dot3_last(col, g0o, g0p, lU, lV);                                              // g0'
+    m_st_f2(f, 0, o);
+#if defined(ZKV_COUNT_FP_MUL)
+    // zkv_fp_mul_counter and zkv_mad_counter feed tests/golden/stage_mul_counts.json, the work figure of the bench's roofline, which this
+    // change leaves as it was: the product is charged the 13 Karatsuba products it replaced (26 lane multiplications, 13 x 243
+    // multiply-adds).  What it really issues -- 243 more per lane, and 17 in each of the six carry passes -- is in zkv_mad_issued_counter
+    // (zkv_field.h); tests/test_miller_var_line_host.py pins the difference, DESIGN section 3 states both figures.
+    zkv_fp_mul_counter -= 10; zkv_mad_counter -= 243;
+#endif
+}
+// The form this body had before, thirteen Karatsuba products with the multipliers c0 and c4 and the multiplicands h2 and g2 + h2
+// prepared once: kept as the independent check of the fused form (tests/host_sim), no kernel calls it.
+template <class RF> ZKV_HD void f12m_mul_by_034_karatsuba_body(RF f, const Fp2& c0, const Fp2& c3, const Fp2& c4) {
     uint32_t c0U[9], c0V[9], c4U[9], c4V[9], tU[9], tV[9], xo[9], xp[9];
     f2_limbs_y(c0.h, c0U, c0V); f2_limbs_y(c4.h, c4U, c4V);
     Fp2 t0c0, t0c1, t0c2, t1c0, t1c1, t1c2;

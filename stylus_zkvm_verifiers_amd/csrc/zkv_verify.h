@@ -396,6 +396,8 @@ ZKV_HD bool miller_loop_p(const VkTables* vkp, uint32_t flags, SoaRef norm, SoaR
             }
             m_st_f2(tm, 0, T.x); m_st_f2(tm, 1, T.y); m_st_f2(tm, 2, T.z);
             if (do_ab) {
+                // the fused form of this product holds the kernel's register peak and relies on compiler-dependent devices to stay under it
+                // (zkv_field.h, f2_dot3_first): after a toolchain change re-read the resource report (232 VGPRs, 0 bytes of scratch)
                 ZKV_MARK("begin mul034");
                 const Fp2 c3 = f2_mul_fp(l1, norm.fp(0)), c4 = f2_mul_fp(l3, norm.fp(8));
                 f12m_mul_by_034_body(fm, l0, c3, c4);
