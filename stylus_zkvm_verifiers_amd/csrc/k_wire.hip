@@ -9,6 +9,7 @@
 #include "zkv_internal.h"
 #include "zkv_bytes.h"
 #include "zkv_wire_gateway.h"
+#include "zkv_wire_rzrouter.h"
 
 namespace zkv {
 
@@ -172,6 +173,53 @@ __global__ __launch_bounds__(BLOCK) void k_wire_gateway(GwWireArgs a, uint32_t c
     }
 }
 
+// verify / verifyIntegrity to the RISC Zero router, the four call shapes of zkv_wire_rzrouter.h: the fixed 260-byte slot of request i
+// (k_wire_risc0's output: no route reads more than 260 bytes, so a longer seal keeps only its true length) with its inputs and method.
+// Form U streams the element words as k_wire_risc0 does.  Form B is already bytes: the wave copies the first min(L, 260) of them -- whole
+// dwords when the request and the slots are 4-byte aligned (the body starts a multiple of 4 behind the request), bytes otherwise -- and
+// checks the zero padding behind the seal's end, at most 31 bytes, one per lane.  Every position is bounded by rzw_parse: it demands the
+// exact total length, and the request itself lies inside the blob.
+template <int BLOCK, bool NT>
+__global__ __launch_bounds__(BLOCK) void k_wire_rzrouter(RzWireArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t i = (size_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+    if (i >= a.n) return;
+    const uint64_t o0 = a.off[i], o1 = a.off[i + 1];
+    const bool in_blob = o0 <= o1 && o1 <= a.cd_bytes;       // offsets come from the caller: never read outside the blob
+    const uint8_t* cd = a.cd + (in_blob ? o0 : 0);
+    const uint64_t len = in_blob ? o1 - o0 : 0;
+    const bool al = (((uintptr_t)cd) & 3u) == 0;
+    const RzwCall h = rzw_parse(cd, len, al, a.sel_be);      // wave-uniform
+    bool ok = h.ok != 0;
+    uint8_t* slot = a.seals + i * 260;
+    if (ok && h.form == GWW_FORM_UINT8_ARRAY) ok = wire_u8_array<NT>(cd + h.seal_at, h.seal_len, al, slot, 260, lane);
+    else if (ok) {
+        const uint8_t* src = cd + h.seal_at;
+        const uint32_t L = h.seal_len, m = L < 260u ? L : 260u;
+        uint32_t k = 0;                                      // bytes the dword path has copied
+        if (al && !((uintptr_t)a.seals & 3u)) {
+            k = m & ~3u;
+            for (uint32_t w = lane; w < k / 4; w += 64) {
+                const uint32_t* q = (const uint32_t*)src + w;
+                ((uint32_t*)slot)[w] = NT ? __builtin_nontemporal_load(q) : *q;
+            }
+        }
+        for (uint32_t t = k + lane; t < m; t += 64) slot[t] = src[t];
+        const uint32_t pad = (uint32_t)(-L & 31u);
+        const uint32_t b = lane < pad ? src[(uint64_t)L + lane] : 0u;
+        ok = __all(b == 0) != 0;
+    }
+    if (h.ok) {
+        copy32(a.in_a + 32 * i, cd + h.a_at, lane);
+        if (!h.method) copy32(a.in_b + 32 * i, cd + h.a_at + 32, lane);
+    }
+    if (lane == 0) {
+        a.seal_len[i] = ok ? h.seal_len : WIRE_BAD;
+        a.method[i] = ok ? (uint8_t)h.method : 0;
+        if (a.call_kind) a.call_kind[i] = ok ? (uint8_t)(2 * h.form + h.method) : (uint8_t)RZW_KIND_BAD;
+    }
+}
+
 // One wavefront per request, four requests per workgroup, non-temporal loads (each calldata byte is read exactly once).
 // Measured on 2^16 verify() requests (554 MB): 4.9 TB/s; a persistent grid-stride grid (3.4-4.5 TB/s), 64- or 512-thread
 // workgroups (4.7 TB/s), default-policy loads (4.8 TB/s) and a header-independent slot-streaming form (4.4 TB/s, 98 VGPRs)
@@ -187,6 +235,11 @@ void launch_wire_gateway(const GwWireArgs& a, hipStream_t s) {
     if (!a.n) return;
     const size_t per = WIRE_BLOCK / 64;
     hipLaunchKernelGGL((k_wire_gateway<WIRE_BLOCK, true>), dim3((unsigned)((a.n + per - 1) / per)), dim3(WIRE_BLOCK), 0, s, a, (uint32_t)ZKV_PLONK_PROOF_BYTES);
+}
+void launch_wire_rzrouter(const RzWireArgs& a, hipStream_t s) {
+    if (!a.n) return;
+    const size_t per = WIRE_BLOCK / 64;
+    hipLaunchKernelGGL((k_wire_rzrouter<WIRE_BLOCK, true>), dim3((unsigned)((a.n + per - 1) / per)), dim3(WIRE_BLOCK), 0, s, a);
 }
 void launch_wire_risc0(const WireArgs& a, hipStream_t s) { wire_dispatch(false, a, s); }
 void launch_wire_sp1(const WireArgs& a, hipStream_t s) { wire_dispatch(true, a, s); }

@@ -29,6 +29,7 @@
 #include "../../include/zkv_diag_gt.h"
 #include "../../include/zkv_risc0_set_inclusion.h"
 #include "../../include/zkv_risc0_router.h"
+#include "../../include/zkv_risc0_router_wire.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
@@ -38,6 +39,7 @@
 #include "zkv_selftest.h"
 #include "zkv_setincl.h"
 #include "zkv_rzrouter_prep.h"
+#include "zkv_wire_rzrouter.h"
 #include <sys/random.h>
 
 using namespace zkv;
@@ -210,6 +212,7 @@ struct zkv_ctx {
     size_t rz_nb = 0;
     std::vector<RzrRoute> rz_routes;
     std::vector<uint64_t> rz_counts;
+    uint64_t rz_bad = 0;                        // bad-calldata seals of the call rz_counts describes (zkv_risc0_router_last_call_counts)
     std::mutex mu;
 };
 
@@ -2224,12 +2227,15 @@ ZKV_EXPORT int zkv_risc0_router_route_verifier_key_digest(const zkv_ctx* c, size
 }
 
 enum { RZ_CNT = 0, RZ_TOT, RZ_ITOT, RZ_POS, RZ_IDX, RZ_RECS, RZ_LEN, RZ_A, RZ_B, RZ_INST, RZ_ST, RZ_RV, RZ_SKEY, RZ_ROUTES,
-       RZ_H_SEALS, RZ_H_OFF, RZ_H_A, RZ_H_B, RZ_H_ST, RZ_H_RV, RZ_BUFS };
+       RZ_H_SEALS, RZ_H_OFF, RZ_H_A, RZ_H_B, RZ_H_ST, RZ_H_RV,
+       RZ_KIND, RZ_H_METHOD,                    // per-seal methods: the compact row and the host call's staging
+       RZW_SEALS, RZW_LEN, RZW_CK,              // calldata batches: the decoded slots, true lengths and call kinds (inputs and methods: RZ_H_A, RZ_H_B, RZ_H_METHOD)
+       RZ_BUFS };
 static_assert(RZ_BUFS <= sizeof(((zkv_ctx*)nullptr)->mx) / sizeof(uint8_t*), "the router's buffers live in zkv_ctx::mx");
 // The built-in group: m compact records from the front end through the verifier set's pipeline (run_set_batch's chunks, with the true
-// lengths and the instance row on the device).  in_b == nullptr: verify_integrity.
+// lengths and the instance row on the device).  kind: the method row, or nullptr: one method, in_b == nullptr being verify_integrity.
 static int run_router_builtin(zkv_ctx* c, size_t m_total, const uint8_t* seals, const uint32_t* len, const uint32_t* inst, const uint8_t* in_a,
-                              const uint8_t* in_b, uint8_t* st, uint8_t* rv, hipStream_t s) {
+                              const uint8_t* in_b, const uint8_t* kind, uint8_t* st, uint8_t* rv, hipStream_t s) {
     if (!m_total) return ZKV_OK;
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_ready(c, m_total);
@@ -2243,6 +2249,7 @@ static int run_router_builtin(zkv_ctx* c, size_t m_total, const uint8_t* seals, 
         a.n = m; a.blob = seals + base * ZKV_SEAL_BYTES; a.stride = ZKV_SEAL_BYTES; a.len = len + base;
         a.inst = inst + base; a.inst_tab = c->d_inst; a.n_inst = (uint32_t)c->inst_raw.size();
         a.in32_a = in_a + 32 * base; a.in32_b = in_b ? in_b + 32 * base : nullptr;
+        a.kind = kind ? kind + base : nullptr;
         a.status = st + base; a.recv = rv + 4 * base;
         enqueue_chunk(c, a, s, base + cap >= m_total);
     }
@@ -2250,17 +2257,19 @@ static int run_router_builtin(zkv_ctx* c, size_t m_total, const uint8_t* seals, 
     return mark_done(c, s);
 }
 // Everything device-resident: ragged seals (offsets bounded by seal_bytes on the device) or, d_seal_off == nullptr, a fixed stride of 260.
-// d_b == nullptr: verify_integrity, d_a holds the claim digests.  Synchronises `s` once, after the count, to lay the slots out and learn
-// the groups' sub-batch sizes.
+// d_b == nullptr: verify_integrity, d_a holds the claim digests.  d_method: the per-seal method row (d_b is then set), or nullptr.
+// d_wire_len (fixed stride only): the true lengths of decoded calldata.  Synchronises `s` once, after the count, to lay the slots out and
+// learn the groups' sub-batch sizes.
 static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64_t* d_seal_off, uint64_t seal_bytes, const uint8_t* d_a, const uint8_t* d_b,
-                      uint8_t* d_status, uint8_t* d_recv, hipStream_t s) {
+                      uint8_t* d_status, uint8_t* d_recv, hipStream_t s, const uint8_t* d_method = nullptr, const uint32_t* d_wire_len = nullptr) {
     int rc;
     const size_t blocks = (n + 255) / 256, R = c->gw_sel.size(), NB = c->rz_nb, K = R - NB;
     // slots: one per routed seal, and up to 31 pad slots behind every keyed route (its successor starts on a wavefront of the Miller mapping)
     const size_t ns = n + 32 * K;
-    const size_t need[RZ_ROUTES] = {4 * GW_COLS * blocks, 4 * GW_COLS, 4 * ZKV_RISC0_ROUTER_MAX_ROUTES, 4 * n, 4 * ns, (size_t)ZKV_SEAL_BYTES * ns + 8, 4 * ns,
+    const size_t need[RZ_ROUTES] = {4 * GW_COLS * blocks, 4 * GW_COLS, 4 * (RZR_BAD_WORD + 1), 4 * n, 4 * ns, (size_t)ZKV_SEAL_BYTES * ns + 8, 4 * ns,
                                     32 * ns, 32 * ns, 4 * ns, ns, 4 * ns, 4 * ns};
     for (int k = 0; k < RZ_ROUTES; k++) if ((rc = grow(&c->mx[k], &c->mx_cap[k], need[k])) != ZKV_OK) return rc;
+    if (d_method && (rc = grow(&c->mx[RZ_KIND], &c->mx_cap[RZ_KIND], ns)) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     if (K && !c->mx[RZ_ROUTES]) {                                  // the keyed routes' constants, once
         if ((rc = grow(&c->mx[RZ_ROUTES], &c->mx_cap[RZ_ROUTES], sizeof(RzrRoute) * K)) != ZKV_OK) return rc;
@@ -2269,17 +2278,18 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
     RzrArgs a;
     memset(&a, 0, sizeof a);
     a.n = n; a.seals = d_seals; a.seal_off = d_seal_off; a.seal_bytes = seal_bytes; a.stride = ZKV_SEAL_BYTES; a.in_a = d_a; a.in_b = d_b;
+    a.method = d_method; a.wire_len = d_wire_len; a.c_kind = d_method ? c->mx[RZ_KIND] : nullptr;
     a.n_builtin = (uint32_t)NB; a.n_keyed = (uint32_t)K;
     for (size_t r = 0; r < R; r++) a.sel[r] = c->gw_sel[r];
     a.cnt = (uint32_t*)c->mx[RZ_CNT]; a.totals = (uint32_t*)c->mx[RZ_TOT]; a.inst_tot = (uint32_t*)c->mx[RZ_ITOT];
     a.pos = (uint32_t*)c->mx[RZ_POS]; a.idx = (uint32_t*)c->mx[RZ_IDX];
     a.c_seals = c->mx[RZ_RECS]; a.c_len = (uint32_t*)c->mx[RZ_LEN]; a.c_a = c->mx[RZ_A]; a.c_b = c->mx[RZ_B]; a.c_inst = (uint32_t*)c->mx[RZ_INST];
     a.status = d_status; a.recv = d_recv;
-    HIP_TRY(hipMemsetAsync(a.inst_tot, 0, 4 * ZKV_RISC0_ROUTER_MAX_ROUTES, s));
+    HIP_TRY(hipMemsetAsync(a.inst_tot, 0, 4 * (RZR_BAD_WORD + 1), s));
     if (K) HIP_TRY(hipMemsetAsync(a.idx, 0xFF, 4 * ns, s));       // pad slots: GW_NONE
     launch_rzrouter_count(a, s);
     HIP_TRY(hipGetLastError());
-    uint32_t tot[GW_COLS], itot[ZKV_RISC0_ROUTER_MAX_ROUTES];
+    uint32_t tot[GW_COLS], itot[RZR_BAD_WORD + 1];                 // (the routes' words, then the bad-calldata word)
     HIP_TRY(hipMemcpyAsync(tot, c->mx[RZ_TOT], sizeof tot, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(itot, c->mx[RZ_ITOT], sizeof itot, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -2299,11 +2309,12 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
     for (size_t q = 0; q < RZR_COL_KEYED0 + K; q++) a.start[q] = L.start[q];
     uint64_t isum = 0;
     for (size_t r = 0; r < NB; r++) isum += itot[r];
-    if (routed + tot[RZR_COL_NOT_FOUND] + tot[RZR_COL_SHORT] != n || L.slots > ns || isum != n0) return ZKV_ERR_HIP;
+    const uint32_t n_bad = itot[RZR_BAD_WORD];                     // in the short column
+    if (routed + tot[RZR_COL_NOT_FOUND] + tot[RZR_COL_SHORT] != n || L.slots > ns || isum != n0 || n_bad > tot[RZR_COL_SHORT]) return ZKV_ERR_HIP;
     launch_rzrouter_place(a, s);
     HIP_TRY(hipGetLastError());
     uint8_t *st = c->mx[RZ_ST], *rv = c->mx[RZ_RV];
-    if (n0 && (rc = run_router_builtin(c->kid[0], n0, a.c_seals, a.c_len, a.c_inst, a.c_a, d_b ? a.c_b : nullptr, st, rv, s)) != ZKV_OK) return rc;
+    if (n0 && (rc = run_router_builtin(c->kid[0], n0, a.c_seals, a.c_len, a.c_inst, a.c_a, d_b ? a.c_b : nullptr, a.c_kind, st, rv, s)) != ZKV_OK) return rc;
     if (routed > n0) {                                             // the keyed group: k_rzrouter_prep with the slot's route, then the key sets' stages
         const size_t G0 = (size_t)L.g0;
         zkv_ctx* g = c->gw_group;
@@ -2311,6 +2322,7 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
         memset(&pc, 0, sizeof pc);
         pc.idx = a.idx + G0; pc.skey = (uint32_t*)c->mx[RZ_SKEY];
         pc.recs = a.c_seals + L.b0; pc.len = a.c_len + G0; pc.in_a = a.c_a + 32 * G0; pc.in_b = a.in_b ? a.c_b + 32 * G0 : nullptr;
+        pc.kind = a.c_kind ? a.c_kind + G0 : nullptr;
         pc.n_keys = (uint32_t)K;
         for (size_t k = 0; k < K; k++) pc.start[k] = (uint32_t)L.gstart[k];
         pc.routes = (const RzrRoute*)c->mx[RZ_ROUTES];
@@ -2326,7 +2338,7 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
     // the counts of the most recent call: only a call that enqueued everything replaces them
     for (size_t r = 0; r < NB; r++) c->rz_counts[r] = itot[r];
     for (size_t k = 0; k < K; k++) c->rz_counts[NB + k] = tot[RZR_COL_KEYED0 + k];
-    c->rz_counts[R] = tot[RZR_COL_NOT_FOUND]; c->rz_counts[R + 1] = tot[RZR_COL_SHORT];
+    c->rz_counts[R] = tot[RZR_COL_NOT_FOUND]; c->rz_counts[R + 1] = tot[RZR_COL_SHORT] - n_bad; c->rz_bad = n_bad;
     c->kid_ran[0] = n0 > 0; c->kid_ran[1] = routed > n0;
     return ZKV_OK;
 }
@@ -2341,15 +2353,16 @@ ZKV_EXPORT int zkv_risc0_router_verify_batch_dev(zkv_ctx* c, size_t n, const uin
     if (rc != ZKV_OK) return rc;
     return run_router(c, n, d_seals, nullptr, 0, d_image_ids, d_journal_digests, d_status, d_recv, stream ? (hipStream_t)stream : c->stream);
 }
-// host buffers: in_b == nullptr selects verify_integrity
+// host buffers: in_b == nullptr selects verify_integrity; method: the per-seal method row (in_b is then set), or nullptr
 static int router_host_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* in_a, const uint8_t* in_b,
-                             uint8_t* status, uint8_t* recv) {
+                             uint8_t* status, uint8_t* recv, const uint8_t* method = nullptr) {
     if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES || !offsets_ok(seal_off, n)) return ZKV_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_device_init(c);
     if (rc != ZKV_OK) return rc;
     const size_t need[4] = {32 * n, 32 * n, n, 4 * n};
     for (int k = 0; k < 4; k++) if ((rc = grow(&c->mx[RZ_H_A + k], &c->mx_cap[RZ_H_A + k], need[k])) != ZKV_OK) return rc;
+    if (method && (rc = grow(&c->mx[RZ_H_METHOD], &c->mx_cap[RZ_H_METHOD], n)) != ZKV_OK) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     std::vector<uint64_t> so;
@@ -2357,8 +2370,9 @@ static int router_host_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, con
     if ((rc = stage_ragged(c, RZ_H_SEALS, RZ_H_OFF, seal_blob, seal_off, n, &so, s, &sbytes)) != ZKV_OK) return rc;
     HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
     if (in_b) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_B], in_b, 32 * n, hipMemcpyHostToDevice, s));
+    if (method) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_METHOD], method, n, hipMemcpyHostToDevice, s));
     if ((rc = run_router(c, n, c->mx[RZ_H_SEALS], (const uint64_t*)c->mx[RZ_H_OFF], sbytes, c->mx[RZ_H_A], in_b ? c->mx[RZ_H_B] : nullptr,
-                         c->mx[RZ_H_ST], c->mx[RZ_H_RV], s)) != ZKV_OK) return rc;
+                         c->mx[RZ_H_ST], c->mx[RZ_H_RV], s, method ? c->mx[RZ_H_METHOD] : nullptr)) != ZKV_OK) return rc;
     return return_to_host(c, RZ_H_ST, RZ_H_RV, n, status, recv, s);
 }
 ZKV_EXPORT int zkv_risc0_router_verify_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* image_ids,
@@ -2761,6 +2775,155 @@ ZKV_EXPORT int zkv_sp1_gateway_last_call_counts(zkv_ctx* c, uint64_t* out) {
     const size_t R = c->gw_route.size();
     for (size_t r = 0; r < R; r++) out[r] = c->gw_counts[r];
     out[R] = c->gw_counts[GW_COL_NOT_FOUND]; out[R + 1] = c->gw_counts[GW_COL_SHORT]; out[R + 2] = c->gw_counts[GW_COL_BAD];
+    return ZKV_OK;
+}
+
+// ------------------------------------------------------------------ RISC Zero router: per-seal methods and eth_call batches (zkv_risc0_router_wire.h; parity unpinned)
+// verify / verifyIntegrity calls to the router in either calldata form: k_wire_rzrouter turns every request into a fixed 260-byte slot, its
+// true length, its inputs and its method; the router takes the slots as a fixed-stride batch with a true-length row and a method row, and
+// everything after the count is the decoded-input path.
+ZKV_EXPORT int zkv_risc0_router_verify_call_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_method, const uint8_t* d_seals, const uint8_t* d_in_a,
+                                                      const uint8_t* d_in_b, uint8_t* d_status, uint8_t* d_recv, void* stream) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_seals || !d_in_a || !d_in_b || !d_status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    return run_router(c, n, d_seals, nullptr, 0, d_in_a, d_in_b, d_status, d_recv, stream ? (hipStream_t)stream : c->stream, d_method);
+}
+ZKV_EXPORT int zkv_risc0_router_verify_call_batch(zkv_ctx* c, size_t n, const uint8_t* method, const uint8_t* seal_blob, const uint64_t* seal_off,
+                                                  const uint8_t* in_a, const uint8_t* in_b, uint8_t* status, uint8_t* recv) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!seal_blob || !seal_off || !in_a || !in_b || !status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    return router_host_batch(c, n, seal_blob, seal_off, in_a, in_b, status, recv, method);
+}
+
+// The four selectors, index 2 form + method (zkv_wire_rzrouter.h): the Stylus shell's uint8[] signatures, then IRiscZeroVerifier's.
+static const uint8_t* router_call_selector(int kind) {
+    static const struct Sels { uint8_t b[RZW_KINDS][4]; Sels() {
+        host::fn_selector("verify(uint8[],bytes32,bytes32)", b[0]); host::fn_selector("verifyIntegrity(uint8[],bytes32)", b[1]);
+        host::fn_selector("verify(bytes,bytes32,bytes32)", b[2]); host::fn_selector("verifyIntegrity((bytes,bytes32))", b[3]); } } s;
+    return s.b[kind];
+}
+// sel | head words | L | the seal packed and zero padded: form B of either method (kind 2 or 3)
+static size_t router_encode_bytes(int kind, const uint8_t* seal, size_t seal_len, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t cap) {
+    const size_t pad = (seal_len + 31) & ~(size_t)31, need = 4 + 96 + 32 + pad;
+    if (!out || cap < need || (seal_len && !seal) || !a || (kind == 2 && !b)) return need;
+    memset(out, 0, need);
+    memcpy(out, router_call_selector(kind), 4);
+    if (kind == 2) { host::abi_word_u32(out + 4, 0x60); memcpy(out + 36, a, 32); memcpy(out + 68, b, 32); }
+    else { host::abi_word_u32(out + 4, 0x20); host::abi_word_u32(out + 36, 0x40); memcpy(out + 68, a, 32); }
+    host::abi_word_u32(out + 100, seal_len);
+    if (seal_len) memcpy(out + 132, seal, seal_len);
+    return need;
+}
+ZKV_EXPORT size_t zkv_risc0_router_encode_verify_call(int form, const uint8_t* seal, size_t seal_len, const uint8_t image_id[32],
+                                                      const uint8_t journal_digest[32], uint8_t* out, size_t cap) {
+    if (form == ZKV_CALLDATA_FORM_UINT8_ARRAY) return zkv_risc0_encode_verify_call(seal, seal_len, image_id, journal_digest, out, cap);
+    if (form != ZKV_CALLDATA_FORM_BYTES) return 0;
+    return router_encode_bytes(2, seal, seal_len, image_id, journal_digest, out, cap);
+}
+ZKV_EXPORT size_t zkv_risc0_router_encode_verify_integrity_call(int form, const uint8_t* seal, size_t seal_len, const uint8_t claim_digest[32], uint8_t* out,
+                                                                size_t cap) {
+    if (form == ZKV_CALLDATA_FORM_UINT8_ARRAY) return zkv_risc0_encode_verify_integrity_call(seal, seal_len, claim_digest, out, cap);
+    if (form != ZKV_CALLDATA_FORM_BYTES) return 0;
+    return router_encode_bytes(3, seal, seal_len, claim_digest, nullptr, out, cap);
+}
+ZKV_EXPORT int zkv_risc0_router_eth_call_returndata(const zkv_ctx* c, uint8_t status, const uint8_t recv_selector[4], uint8_t call_kind,
+                                                    uint8_t out[ZKV_RETURNDATA_STRIDE], uint32_t* out_len, uint8_t* reverted) {
+    static const uint8_t zero[4] = {0, 0, 0, 0};
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (!out || !out_len || !reverted) return ZKV_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (status == ZKV_STATUS_BAD_CALLDATA) { *reverted = 1; return ZKV_OK; }      // the router could not decode the call: empty revert data
+    if (call_kind >= RZW_KINDS) return ZKV_ERR_INVALID_ARG;                       // every other status belongs to a decoded call
+    if (status == ZKV_STATUS_OK) {                                               // the Stylus shells return `true`, Solidity's verify nothing
+        *reverted = 0;
+        if (call_kind < 2) { host::abi_word_u32(out, 1); *out_len = 32; }
+        return ZKV_OK;
+    }
+    *reverted = 1;
+    const int k = zkv_risc0_router_status_abi_encode(c, status, recv_selector ? recv_selector : zero, out);
+    if (k < 0) return k;
+    *out_len = (uint32_t)k;
+    return ZKV_OK;
+}
+// Calldata and its n + 1 offsets on the device.  The decode is enqueued in front of the count, so the call synchronises where run_router does.
+// d_ck: the caller's call-kind row, or nullptr.
+static int run_router_wire(zkv_ctx* c, size_t n, const uint8_t* d_cd, const uint64_t* d_off, uint64_t cd_bytes, uint8_t* d_status, uint8_t* d_recv,
+                           uint8_t* d_ck, hipStream_t s) {
+    int rc;
+    const int slot[5] = {RZW_SEALS, RZW_LEN, RZ_H_A, RZ_H_B, RZ_H_METHOD};
+    const size_t need[5] = {(size_t)ZKV_SEAL_BYTES * n + 8, 4 * n, 32 * n, 32 * n, n};
+    for (int k = 0; k < 5; k++) if ((rc = grow(&c->mx[slot[k]], &c->mx_cap[slot[k]], need[k])) != ZKV_OK) return rc;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    RzWireArgs w;
+    memset(&w, 0, sizeof w);
+    w.n = n; w.cd = d_cd; w.off = d_off; w.cd_bytes = cd_bytes;
+    for (int k = 0; k < RZW_KINDS; k++) w.sel_be[k] = be32_of(router_call_selector(k));
+    w.seals = c->mx[RZW_SEALS]; w.seal_len = (uint32_t*)c->mx[RZW_LEN]; w.in_a = c->mx[RZ_H_A]; w.in_b = c->mx[RZ_H_B]; w.method = c->mx[RZ_H_METHOD];
+    w.call_kind = d_ck;
+    (void)hipEventRecord(c->ev_wire[0], s);
+    launch_wire_rzrouter(w, s);
+    (void)hipEventRecord(c->ev_wire[1], s);
+    c->wire_timed = true;
+    HIP_TRY(hipGetLastError());
+    return run_router(c, n, w.seals, nullptr, 0, w.in_a, w.in_b, d_status, d_recv, s, w.method, w.seal_len);
+}
+ZKV_EXPORT int zkv_risc0_router_eth_call_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_calldata, const uint64_t* d_calldata_off, uint64_t calldata_bytes,
+                                                   uint8_t* d_status, uint8_t* d_recv, uint8_t* d_call_kind, void* stream) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_calldata || !d_calldata_off || !d_status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    return run_router_wire(c, n, d_calldata, d_calldata_off, calldata_bytes, d_status, d_recv, d_call_kind, stream ? (hipStream_t)stream : c->stream);
+}
+ZKV_EXPORT int zkv_risc0_router_eth_call_batch(zkv_ctx* c, size_t n, const uint8_t* blob, const uint64_t* off, uint8_t* reverted, uint8_t* returndata,
+                                               uint32_t* returndata_len, uint8_t* status) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!blob || !off || !reverted || !returndata || !returndata_len)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES || !offsets_ok(off, n)) return ZKV_ERR_INVALID_ARG;
+    std::vector<uint8_t> st(n), rv(4 * n), ck(n);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        int rc = ctx_device_init(c);
+        if (rc != ZKV_OK) return rc;
+        const size_t need[3] = {n, 4 * n, n};
+        const int slot[3] = {RZ_H_ST, RZ_H_RV, RZW_CK};
+        for (int k = 0; k < 3; k++) if ((rc = grow(&c->mx[slot[k]], &c->mx_cap[slot[k]], need[k])) != ZKV_OK) return rc;
+        hipStream_t s = c->stream;
+        if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+        std::vector<uint64_t> rel;
+        uint64_t bytes = 0;
+        if ((rc = stage_ragged(c, RZ_H_SEALS, RZ_H_OFF, blob, off, n, &rel, s, &bytes)) != ZKV_OK) return rc;
+        if ((rc = run_router_wire(c, n, c->mx[RZ_H_SEALS], (const uint64_t*)c->mx[RZ_H_OFF], bytes, c->mx[RZ_H_ST], c->mx[RZ_H_RV], c->mx[RZW_CK], s)) != ZKV_OK)
+            return rc;
+        HIP_TRY(hipMemcpyAsync(st.data(), c->mx[RZ_H_ST], n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(rv.data(), c->mx[RZ_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ck.data(), c->mx[RZW_CK], n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (size_t i = 0; i < n; i++) {
+        const int rc = zkv_risc0_router_eth_call_returndata(c, st[i], rv.data() + 4 * i, ck[i], returndata + i * ZKV_RETURNDATA_STRIDE, &returndata_len[i], &reverted[i]);
+        if (rc != ZKV_OK) return rc;
+        if (status) status[i] = st[i];
+    }
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_risc0_router_last_call_counts(zkv_ctx* c, uint64_t* out) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const size_t R = c->rz_counts.size();
+    for (size_t r = 0; r < R; r++) out[r] = c->rz_counts[r];
+    out[R] = c->rz_bad;
     return ZKV_OK;
 }
 

@@ -89,6 +89,19 @@ struct GwWireArgs {
     uint64_t* pv_at; uint32_t* pv_len; uint64_t* proof_at; uint32_t* proof_len; uint8_t* bad;
 };
 void launch_wire_gateway(const GwWireArgs& a, hipStream_t s);
+// eth_call calldata of the RISC Zero router (k_wire_rzrouter in k_wire.hip; zkv_wire_rzrouter.h has the four call shapes): request i to a
+// fixed 260-byte slot with the first min(L, 260) seal bytes, the true L (0xFFFFFFFF: not a canonical call), its two 32-byte inputs and
+// its method -- the router's fixed-stride input with a true-length row (RzrArgs::wire_len).
+struct RzWireArgs {
+    size_t n;
+    const uint8_t* cd; const uint64_t* off; uint64_t cd_bytes;                  // as WireArgs
+    uint32_t sel_be[4];                                                        // selector of call kind 2 form + method
+    uint8_t* seals; uint32_t* seal_len;                                        // n x 260 (4-byte aligned), n
+    uint8_t* in_a; uint8_t* in_b;                                              // n x 32 each; in_b is written for verify calls only
+    uint8_t* method;                                                           // n: ZKV_METHOD_* (0 for a bad request)
+    uint8_t* call_kind;                                                        // n or nullptr: 2 form + method, 255 for a bad request
+};
+void launch_wire_rzrouter(const RzWireArgs& a, hipStream_t s);
 
 void launch_setup(const VkRaw* d_raw, VkTables* d_tab, hipStream_t s);
 void launch_prep_risc0(const PrepArgs& a, const Risc0Consts& k, const Workspace& ws, hipStream_t s);
@@ -232,18 +245,24 @@ void launch_gwset_prep(const GwsetChunk& c, const Workspace& ws, hipStream_t s);
 // RISC Zero router (k_risc0_router.hip, include/zkv_risc0_router.h; zkv_rzrouter_prep.h has the columns): every seal goes to the route
 // whose selector begins it.  The built-in-key routes are ONE column (a verifier set: place writes the instance each seal matched), every
 // keyed route has its own (one key set, group k from slot start[1 + k]).
+constexpr int RZR_BAD_WORD = 32;                                               // inst_tot[RZR_BAD_WORD]: behind the ZKV_RISC0_ROUTER_MAX_ROUTES route words
 struct RzrArgs {
     size_t n;
     const uint8_t* seals; const uint64_t* seal_off; uint64_t seal_bytes;       // ragged seals (seal_bytes bounds every read), or seal_off == nullptr:
     uint32_t stride;                                                           // a fixed stride
+    const uint32_t* wire_len;                                                  // fixed stride only, or nullptr: true length of seal i, of which the slot
+                                                                               // holds the first min(length, stride) bytes; 0xFFFFFFFF: bad calldata
     const uint8_t* in_a; const uint8_t* in_b;                                  // n x 32 each; in_b == nullptr: verify_integrity, in_a holds claim digests
+    const uint8_t* method;                                                     // n x ZKV_METHOD_* (a byte above 1: bad calldata), or nullptr: in_b decides
     uint32_t n_builtin, n_keyed;
     uint32_t sel[32];                                                          // route selectors, big-endian words (kernel arguments: SGPRs)
     uint32_t start[9];                                                         // (place) first slot of the built-in group and of every keyed route
     uint32_t* cnt; uint32_t* totals;                                           // GW_COLS per block (exclusive scan in place), GW_COLS totals
-    uint32_t* inst_tot;                                                        // seals per built-in route (zeroed by the host before the count)
+    uint32_t* inst_tot;                                                        // seals per built-in route, then (word RZR_BAD_WORD) the bad-calldata
+                                                                               // seals, which the short column counts too (zeroed by the host)
     uint32_t* pos; uint32_t* idx;                                              // pos[i] = slot (GW_NONE: answered in place); idx[slot] = i
     uint8_t* c_seals; uint32_t* c_len; uint8_t* c_a; uint8_t* c_b; uint32_t* c_inst;      // compact records; c_inst: built-in slots only
+    uint8_t* c_kind;                                                           // compact method row (method != nullptr only)
     uint8_t* status; uint8_t* recv;                                            // caller's outputs (short / unknown seals answered here)
 };
 void launch_rzrouter_count(const RzrArgs& a, hipStream_t s);       // count + scan: totals[GW_COLS], inst_tot[n_builtin]
@@ -254,6 +273,7 @@ struct RzrChunk {
     size_t m, slot0;
     const uint32_t* idx; uint32_t* skey;
     const uint8_t* recs; const uint32_t* len; const uint8_t* in_a; const uint8_t* in_b;     // in_b == nullptr: verify_integrity
+    const uint8_t* kind;                                                                    // per-slot ZKV_METHOD_*, or nullptr: in_b decides
     uint32_t n_keys; uint32_t start[GW_MAX_ROUTES];
     const GsetKey* keys; const RzrRoute* routes;
     uint32_t* sig; size_t sig_cap;

@@ -45,6 +45,13 @@ ZKV_HD void rzrouter_prep_slot(uint32_t vk_valid, const RzrRoute& rt, const Risc
     if (prep_points(w, true, r.o)) r.flags = r.o.flags;
 }
 
+// The in_b of group slot `slot` as rzrouter_prep_slot takes it, chosen per slot: kind is the group's method row (ZKV_METHOD_*), or
+// nullptr when the whole call has one method, which in_b then tells (nullptr: verify_integrity).
+ZKV_HD const uint8_t* rzrouter_slot_in_b(const uint8_t* kind, const uint8_t* in_b, size_t slot) {
+    if (!in_b || (kind && kind[slot] != 0)) return nullptr;
+    return in_b + 32 * slot;
+}
+
 // Router classifier (k_risc0_router.hip) on the host as well: the column of a seal whose first four bytes are `sel` (big-endian word).
 // Columns: 0 = the built-in group (all built-in routes; *inst = which), 1 + k = keyed route k, then not found.  sel[]: the built-in
 // routes' selectors, then the keyed routes'.

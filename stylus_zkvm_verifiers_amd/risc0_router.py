@@ -153,6 +153,57 @@ class RiscZeroRouter:
         _lib.check(self._L.zkv_risc0_router_last_route_counts(self._h, out), 'zkv_risc0_router_last_route_counts')
         return list(out)
 
+    # ---- a method per seal, and eth_call batches (include/zkv_risc0_router_wire.h, risc0_router_wire.py)
+    def verify_call_batch(self, methods, seals, in_a, in_b):
+        """methods[i]: 0 = verify (in_a image id, in_b journal digest), 1 = verifyIntegrity (in_a claim digest, in_b not read); None: all
+        verify.  Any other method byte is BAD_CALLDATA.  -> (status uint8[n], received selector uint8[n, 4])."""
+        from . import risc0_router_wire as w
+        return w.verify_call_batch(self._h, methods, seals, in_a, in_b)
+
+    def verify_call_batch_dev(self, n, d_method, d_seals, d_in_a, d_in_b, d_status, d_recv=0, stream=0):
+        """verify_batch_dev with n method bytes on the device (0: all verify); d_in_b is always a row of n x 32 bytes."""
+        from . import risc0_router_wire as w
+        w.verify_call_batch_dev(self._h, n, d_method, d_seals, d_in_a, d_in_b, d_status, d_recv, stream)
+
+    @staticmethod
+    def encode_verify_call(seal, image_id, journal_digest, form=1):
+        """Canonical calldata in `form`: 0 = verify(uint8[],bytes32,bytes32), 1 = verify(bytes,bytes32,bytes32)."""
+        from . import risc0_router_wire as w
+        return w.encode_verify_call(seal, image_id, journal_digest, form)
+
+    @staticmethod
+    def encode_verify_integrity_call(seal, claim_digest, form=1):
+        """Canonical calldata in `form`: 0 = verifyIntegrity(uint8[],bytes32), 1 = verifyIntegrity((bytes,bytes32))."""
+        from . import risc0_router_wire as w
+        return w.encode_verify_integrity_call(seal, claim_digest, form)
+
+    def eth_call_batch(self, calls):
+        """calls: calldata byte strings, both methods, both forms and seals of every route mixed -> (reverted uint8[n], [return / revert
+        data], status uint8[n]).  Anything but a canonical verify / verifyIntegrity call is BAD_CALLDATA with empty revert data."""
+        from . import risc0_router_wire as w
+        return w.eth_call_batch(self._h, calls)
+
+    def eth_call_batch_dev(self, n, d_calldata, d_calldata_off, calldata_bytes, d_status, d_recv=0, d_call_kind=0, stream=0):
+        """Device-resident calldata blob and its n + 1 uint64 offsets; n status bytes, n x 4 received selectors (0: none) and n call kinds
+        (0: none) stay on the device (eth_call_returndata turns one into return / revert data)."""
+        from . import risc0_router_wire as w
+        w.eth_call_batch_dev(self._h, n, d_calldata, d_calldata_off, calldata_bytes, d_status, d_recv, d_call_kind, stream)
+
+    def eth_call_returndata(self, status, received=bytes(4), call_kind=255):
+        from . import risc0_router_wire as w
+        return w.eth_call_returndata(self._h, status, received, call_kind)
+
+    def last_call_counts(self):
+        """last_route_counts with one more column: seals of the most recent call that were bad calldata."""
+        from . import risc0_router_wire as w
+        return w.last_call_counts(self._h, self._L.zkv_risc0_router_route_count(self._h))
+
+    def last_wire_ms(self):
+        """Decode time of the most recent eth_call batch."""
+        out = C.c_float(0)
+        _lib.check(self._L.zkv_ctx_last_wire_ms(self._h, C.byref(out)), 'zkv_ctx_last_wire_ms')
+        return out.value
+
     def status_revert(self, status, received=bytes(4)):
         """Revert data of a router status (SelectorUnknown(bytes4) for ROUTE_NOT_FOUND; unpinned)."""
         o = C.create_string_buffer(68)
