@@ -398,6 +398,10 @@ int zkv_ctx_reserve(zkv_ctx* ctx, size_t n);
  * closed: the proof / call is reported as failing, never as accepted.  So that such an event is not mistaken for a verdict, it is counted per device
  * since the library was loaded; out = that count (0 in every run so far; the tests assert it).  Synchronise first. */
 int zkv_diag_wait_faults(int device, uint64_t* out);
+/* Device memory the library holds in this process, over all contexts and devices: out = {live allocations, live bytes} (bytes as asked
+ * of the runtime, before its rounding).  Every allocation belongs to a context or to a call in progress, so the figures return to what
+ * they were once a context is destroyed; unlike a free-memory reading they do not move with other processes' work.  Needs no device. */
+int zkv_diag_device_memory(uint64_t out[2]);
 /* Sharded context, device-resident batches: how shard `shard` reaches the GPU that held the rows of the last batch it staged --
  * 1: peer access granted (hipDeviceEnablePeerAccess: the range travels as direct xGMI copies), 0: refused (the runtime bounces the
  * copies through the host), 2: not applicable so far (the shard sits on the source GPU, or it has staged nothing yet).

@@ -33,6 +33,7 @@
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
+#include "zkv_devmem.h"
 #include "zkv_plonk.h"
 #include "zkv_agg.h"
 #include "zkv_gset_layout.h"
@@ -46,7 +47,84 @@ using namespace zkv;
 
 #define ZKV_EXPORT extern "C" __attribute__((visibility("default")))
 
-struct zkv_ctx {
+// ---- Device state of a context.  OWNERSHIP: every device allocation, event and stream of a context is a DevBuf / DevEvent / DevStream
+// (zkv_devmem.h) in one of the three structs below, which hold nothing but such owners, the plain views kernels take by value
+// (Workspace, GtTab, Msm16: filled from the owners beside them) and the sizes and flags that describe them, all with default member
+// initialisers.  Releasing a group is assigning it a default-constructed value; a field added here needs no other edit to be released.
+//
+// Per-chunk buffers, sized by ctx_reserve() for ws.cap proofs in flight.
+struct ChunkMem {
+    DevBuf<uint32_t> ws_prep, ws_norm, ws_f, ws_fe, ws_flags, ws_g2bad;
+    DevBuf<uint8_t> ws_gtag;
+    Workspace ws = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};      // view of the seven rows above
+    DevBuf<uint8_t> d_a, d_b, d_status, d_recv;
+    DevBuf<uint64_t> d_off, d_pvoff;
+    DevBuf<uint32_t> d_inst_idx;
+    // wire layer (eth_call batches): decoded lengths / methods, the calldata offsets of both buffers
+    DevBuf<uint32_t> d_len, d_pvlen;
+    DevBuf<uint8_t> d_kind;
+    DevBuf<uint64_t> d_cdoff[2];
+    DevBuf<uint32_t> d_plonk_tab;                              // per-proof window tables of the PLONK stage (PLONK_TAB_WORDS words per proof in flight)
+};
+// Buffers of the aggregate check (zkv_agg.h), sized by agg_reserve() with the workspace: per-proof rows, the pseudo-proofs' workspace
+// (one per sub-batch) and their statuses; and, for the proofs of failed sub-batches gathered into a dense workspace for the ordinary
+// kernels, own PREP rows, flags and statuses (the scratch rows norm, f, fe of ws3 are the chunk workspace's)
+struct AggMem {
+    DevBuf<uint32_t> d_agg;
+    DevBuf<uint32_t> ws2_prep, ws2_norm, ws2_f, ws2_fe, ws2_flags, ws2_g2bad;
+    DevBuf<uint8_t> d_status2;
+    DevBuf<uint32_t> ws3_prep, ws3_flags, ws3_g2bad;
+    DevBuf<uint8_t> d_status3;
+    DevBuf<uint32_t> d_agg_idx;
+    Workspace ws2 = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    Workspace ws3 = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    size_t agg_cap = 0;                                        // proofs the buffers above have room for (0: none, the chunk takes the ordinary kernels)
+};
+// Everything created lazily for the device (on the first compute call).  ctx_free_device() resets it as a whole.  Buffers come first,
+// then events, then streams: the order in which a reset lets them go.
+struct CtxDevice : ChunkMem, AggMem {
+    bool dev_ready = false;
+    DevBuf<VkTables> d_tab;
+    DevBuf<G1A> d_msm16;                                       // the vk_x stage's 16-bit window rows (Msm16; empty: 8-bit walk)
+    Msm16 m16 = {nullptr, {0, 0, 0, 0, 0}};
+    // fixed-base GT tables of the (vk_x, gamma) pairing (zkv_gt.h): built the first time a call can run lane-pair chunks (gt_maybe_build);
+    // gt.tab == nullptr: none (ZKV_GT_WINDOW_BITS=0, no room, another kind of context) -- the Miller loop takes the pair
+    DevBuf<uint32_t> d_gt, d_gt_const;
+    DevBuf<GtCache> d_gt_cache;                                // walk-prefix cache of an SP1 context with tables (zkv_gt.h); ZKV_GT_CACHE=0: none
+    GtTab gt = GT_NONE;
+    bool gt_tried = false;
+    size_t gt_bytes = 0;
+    DevBuf<InstTab> d_inst;                                    // ZKV_VM_RISC0_SET: the instances' table
+    DevBuf<G1A> d_ltab; DevBuf<uint32_t> d_lwin, d_lsig;       // long key: IC[1..] window rows, their window counts, a chunk's staged signals
+    // key sets: one VkTables per key, the per-key records, all keys' IC[1..] window rows in one allocation and their window counts
+    DevBuf<VkTables> d_gs_tab; DevBuf<GsetKey> d_gs_key; DevBuf<G1A> d_gs_rows; DevBuf<uint32_t> d_gs_win;
+    DevBuf<PlonkKey> d_pkey;
+    DevBuf<uint32_t> d_ps_ok;                                  // PLONK set: a validity word per key
+    // aggregate check: key tables (one AggTables per key on a set), the counters {sub-batches checked, sub-batches failed}, whether a key can take it
+    DevBuf<AggTables> d_agg_tab;
+    DevBuf<unsigned long long> d_agg_cnt;
+    bool agg_key_ok = false;
+    // staging: proofs and public values of a chunk; calldata blobs of the wire layer; whole-batch statuses and receive words
+    DevBuf<> d_blob, d_pv, d_cd[2], d_st_all, d_rv_all;
+    // host-buffer batches (run_host_batch): whole-batch staging in HBM, filled segment by segment on copy_stream while the previous
+    // segment is verified: seals, seal offsets, in_a, in_b, public values, pv offsets
+    DevBuf<> hb[6];
+    // demultiplexing, routing and set-inclusion buffers (enums MX_*, GW_*, GWW_*, RZ_*, RZW_*, KS_*, SI_*)
+    static constexpr size_t MX_SLOTS = 28;
+    DevBuf<> mx[MX_SLOTS];
+    DevEvent ev_fork, ev_join;                                 // small chunks: the G2 subgroup check runs beside the MSM (stream `side`)
+    DevEvent ev_copied[2], ev_decoded[2];                      // wire layer: H2D of calldata chunk k+1 overlaps the kernels of chunk k
+    DevEvent ev[6], ev_wire[2];
+    bool wire_timed = false;
+    // The workspace is shared by every call on this context, and the *_dev entry points run on caller-chosen streams:
+    // each call first makes its stream wait for the previous call's last kernel (ev_done), then records ev_done again.
+    DevEvent ev_done;
+    bool has_done = false;
+    DevEvent ev_seg[2];
+    DevStream copy_stream, side, stream;
+};
+
+struct zkv_ctx : CtxDevice {
     int vm = 0, device = 0, lanes = 0;       // lanes: 0 = library default, 1 or 2 = lanes per proof for the Fp2-heavy stages
     bool initialized = false, id_ge_r = false;
     uint8_t control_root_0[16] = {0}, control_root_1[16] = {0}, control_id[32] = {0}, selector[4] = {0};
@@ -54,78 +132,33 @@ struct zkv_ctx {
     // ZKV_VM_RISC0_SET: n_inst verifier instances sharing the VK tables and the workspace
     std::vector<InstRaw> inst_raw;
     std::vector<InstTab> inst_host;          // copy of the device table (selectors derived on the device) for the getters
-    InstTab* d_inst = nullptr;
-    uint32_t* d_inst_idx = nullptr;
     std::vector<uint8_t> gvk;                // ZKV_VM_GROTH16: the caller's verification key (448 + 64 n_ic bytes)
     uint32_t g_n_ic = 0; bool g_negate = false, vk_invalid = false;
     // long-key path (n_ic > MAX_IC, or ZKV_LONG_KEY=1 at creation): IC[1..] in tables of their own (LongKey) and the staged signals of a chunk
     bool long_key = false;
-    G1A* d_ltab = nullptr; uint32_t* d_lwin = nullptr; uint32_t* d_lsig = nullptr;
-    size_t lsig_cap = 0;
     // ZKV_VM_GROTH16_SET (zkv_groth16_set.h): the keys back to back in gvk (gs_off[k]: byte offset of key k), their n_ic and sign
     // convention.  A set runs the long-key path (long_key = true, g_n_ic = the largest n_ic: d_lsig stages the signals of a chunk); on the
     // device one VkTables per key, the per-key records, all keys' IC[1..] window rows in one allocation and their window counts.
     std::vector<size_t> gs_off; std::vector<uint32_t> gs_nic; std::vector<uint8_t> gs_neg;
     std::vector<uint32_t> gs_totals; std::vector<uint64_t> gs_start;     // per call: proofs per key, slot layout (zkv_gset_layout.h)
-    VkTables* d_gs_tab = nullptr; GsetKey* d_gs_key = nullptr; G1A* d_gs_rows = nullptr; uint32_t* d_gs_win = nullptr;
     // aggregate check on a set: which keys can take it (d_agg_tab then holds one AggTables per key), and per call the two-region layout
     // (zkv_gset_layout.h: gset_agg_choose) and every aggregate chunk's pseudo-proof slots (run_gset)
     std::vector<uint8_t> gs_agg_ok; std::vector<uint32_t> gs_agg_n, gs_rest, gs_nsb, gs_amap; std::vector<uint64_t> gs_map, gs_pst;
-    // device side (created lazily on the first compute call)
-    bool dev_ready = false;
-    hipStream_t stream = nullptr;
-    VkTables* d_tab = nullptr;
-    G1A* d_msm16 = nullptr;                                  // the vk_x stage's 16-bit window rows (Msm16; null: 8-bit walk)
-    Msm16 m16 = {nullptr, {0, 0, 0, 0, 0}};
-    // fixed-base GT tables of the (vk_x, gamma) pairing (zkv_gt.h): built the first time a call can run lane-pair chunks (gt_maybe_build);
-    // gt.tab == nullptr: none (ZKV_GT_WINDOW_BITS=0, no room, another kind of context) -- the Miller loop takes the pair
-    uint32_t *d_gt = nullptr, *d_gt_const = nullptr;
-    GtCache* d_gt_cache = nullptr;                               // walk-prefix cache of an SP1 context with tables (zkv_gt.h); ZKV_GT_CACHE=0: none
-    GtTab gt = GT_NONE;
-    bool gt_tried = false;
-    size_t gt_bytes = 0; float gt_build_ms = 0;
-    Workspace ws = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    hipStream_t side = nullptr;                              // small chunks: the G2 subgroup check runs beside the MSM
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    uint8_t *d_blob = nullptr, *d_a = nullptr, *d_b = nullptr, *d_pv = nullptr, *d_status = nullptr, *d_recv = nullptr;
-    uint64_t *d_off = nullptr, *d_pvoff = nullptr;
-    size_t blob_cap = 0, pv_cap = 0;
-    // wire layer (eth_call batches): calldata blob, its offsets, decoded lengths / methods
-    uint8_t *d_cd[2] = {nullptr, nullptr}, *d_kind = nullptr, *d_st_all = nullptr, *d_rv_all = nullptr;
-    uint64_t* d_cdoff[2] = {nullptr, nullptr};
-    uint32_t *d_len = nullptr, *d_pvlen = nullptr;
-    size_t cd_cap[2] = {0, 0}, st_all_cap = 0, rv_all_cap = 0;
-    hipStream_t copy_stream = nullptr;                       // H2D of calldata chunk k+1 overlaps the kernels of chunk k
-    hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_decoded[2] = {nullptr, nullptr};
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, ev_wire[2] = {nullptr, nullptr};
-    bool wire_timed = false;
-    // The workspace is shared by every call on this context, and the *_dev entry points run on caller-chosen streams:
-    // each call first makes its stream wait for the previous call's last kernel (ev_done), then records ev_done again.
-    hipEvent_t ev_done = nullptr;
-    bool has_done = false;
+    float gt_build_ms = 0;
     size_t last_chunk_n = 0;                                 // proofs of the most recent chunk (zkv_diag_prep.h reads their rows back)
-    // host-buffer batches (run_host_batch): whole-batch staging in HBM, filled segment by segment on copy_stream while the previous
-    // segment is verified
-    uint8_t* hb[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // seals, seal offsets, in_a, in_b, public values, pv offsets
-    size_t hb_cap[6] = {0, 0, 0, 0, 0, 0};
-    hipEvent_t ev_seg[2] = {nullptr, nullptr};
     // ZKV_VM_SP1_PLONK and ZKV_VM_PLONK (zkv_plonk_keys.h): parsed verifying key, the SRS's two G2 points (reference word order) and
     // (SP1) the verifier hash
     PlonkKeyRaw pk_raw; uint8_t pk_g2[256] = {0}, plonk_hash[32] = {0};
-    PlonkKey* d_pkey = nullptr;
-    uint32_t* d_plonk_tab = nullptr;                           // per-proof window tables of the PLONK stage (PLONK_TAB_WORDS words per proof in flight)
     // ZKV_VM_PLONK_SET (zkv_plonk_set.h): every key's parsed header and points, its two G2 points (256 bytes per key in ps_g2), and the
     // largest nb_public and n_c (the row strides).  On the device: the keys' PlonkKey array in d_pkey, one VkTables per key in d_gs_tab
     // with its GsetKey in d_gs_key (what the Groth16 sets' Miller kernels read), and a validity word per key in d_ps_ok.  A call reuses
-    // the Groth16 sets' partition buffers (gs_totals, gs_start, mx[3..9]).
+    // the Groth16 sets' partition buffers (gs_totals, gs_start, mx[KS_CNT..KS_SKEY]).
     std::vector<PlonkKeyRaw> ps_raw; std::vector<uint8_t> ps_g2; uint32_t ps_nb_max = 0, ps_nc_max = 0;
-    uint32_t* d_ps_ok = nullptr;
     // aggregate check on a PLONK set (zkv_plonk_set_agg.h): every key's SRS class and each class's first key (formed at creation), which
     // classes can take the check (read back the first time a call wants it), and per call every class's region (pset_agg_choose)
     std::vector<uint32_t> ps_class, ps_cls_rep; std::vector<uint8_t> ps_cls_ok; std::vector<uint64_t> ps_cbeg, ps_cend;
-    // Aggregate check (zkv_agg.h, zkv_ctx_set_aggregate_check): key tables, per-proof rows, the pseudo-proofs' workspace (one per
-    // sub-batch), their statuses and the counters {sub-batches checked, sub-batches failed}
-    bool agg_on = false, agg_key_ok = false;
+    // Aggregate check (zkv_agg.h, zkv_ctx_set_aggregate_check): the switch and its policy state (the buffers: AggMem, CtxDevice)
+    bool agg_on = false;
     uint32_t agg_sub = 32;                                     // proofs per sub-batch: 16, 32, 64, 128 or 256
     bool agg_auto = false;                                     // enable = 1: the size follows the failure rate seen so far (agg_adapt)
     unsigned long long agg_seen[2] = {0, 0};                   // counters at the last adaptation
@@ -135,27 +168,15 @@ struct zkv_ctx {
     uint32_t agg_pause = 0, agg_pause_len = 0;                 // automatic mode: chunks still to run WITHOUT the check (too many sub-batches fail), and the length of that pause
     bool agg_os_seed = false;                                  // the secret came from the operating system: it is drawn afresh every AGG_REKEY_CHUNKS chunks
     uint32_t agg_key_age = 0;
-    AggTables* d_agg_tab = nullptr;
-    uint32_t* d_agg = nullptr;
-    Workspace ws2 = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    uint8_t* d_status2 = nullptr;
-    // proofs of failed sub-batches, gathered into a dense workspace for the ordinary kernels: own PREP rows, flags and statuses; the
-    // scratch rows (norm, f, fe) are the chunk workspace's
-    Workspace ws3 = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    uint8_t* d_status3 = nullptr;
-    uint32_t* d_agg_idx = nullptr;
-    unsigned long long* d_agg_cnt = nullptr;
-    size_t agg_cap = 0;
     AggSeed agg_seed = {{0, 0, 0, 0, 0, 0, 0, 0}, 0};
-    // ZKV_VM_MIXED: one RISC Zero and one SP1 verifier behind a per-proof VM tag; mx[] are the demultiplexing buffers
+    // ZKV_VM_MIXED: one RISC Zero and one SP1 verifier (kid[]) behind a per-proof VM tag
     // Sharded (multi-device) context: `shards` single-device contexts of one verifier behind the ordinary batch entry points
     // (zkv_ctx_create_sharded).  sh[] is the per-shard state of device-resident batches: staging rows on the shard's device, a copy
     // stream (the transfer of piece k + 1 runs behind the kernels of piece k), the shard's compute stream and its events.
     struct ShardDev {
-        uint8_t* row[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t row_cap[5] = {0, 0, 0, 0, 0};
-        uint8_t *st = nullptr, *rv = nullptr; size_t st_cap = 0, rv_cap = 0;
-        hipStream_t copy = nullptr, run = nullptr;
-        hipEvent_t ev_piece[2] = {nullptr, nullptr}, ev_done = nullptr;
+        DevBuf<> row[5], st, rv;
+        DevEvent ev_piece[2], ev_done;
+        DevStream copy, run;
         bool has_done = false;                                 // ev_done has been recorded: the next call's copies into row[] wait for it
         int peer = 2;                                          // peer access to the source GPU of the last staged batch: 1 granted (direct xGMI copies), 0 refused
                                                                // (the runtime bounces the copies), 2 never needed (same device, or nothing staged yet)
@@ -182,11 +203,9 @@ struct zkv_ctx {
     std::mutex pool_mu;                                        // one batch call at a time hands work to the pool
     std::vector<zkv_ctx*> shards;
     std::vector<ShardDev> sh;
-    std::vector<hipEvent_t> ev_in;                       // per source device: "the caller's stream has produced the inputs"
+    std::vector<DevEvent> ev_in;                         // per source device: "the caller's stream has produced the inputs"
     zkv_ctx* kid[2] = {nullptr, nullptr};
     bool kid_ran[2] = {false, false};        // which sub-batch of the most recent mixed call was non-empty (zkv_ctx_last_stage_ms)
-    uint8_t* mx[28] = {nullptr};
-    size_t mx_cap[28] = {0};
     // ZKV_VM_SP1_GATEWAY (zkv_sp1_gateway.h): the routes' contexts and selectors; which routes ran in the most recent call
     // (zkv_ctx_last_stage_ms) and its per-column proof counts (routes, not found, short, bad calldata)
     // Keyed Groth16 routes (zkv_sp1_gateway_keys.h) are routes [gw_key0, gw_key0 + gw_nkeys): they have no context of their own
@@ -354,53 +373,32 @@ ZKV_EXPORT int zkv_device_count(void) {
 }
 ZKV_EXPORT const char* zkv_version(void) { return "zkv-mi355x 0.1 (gfx950)"; }
 
-#define HIP_TRY(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return ZKV_ERR_HIP; } } while (0)
+// (x: a HIP call, or an owner's alloc() / create() -- any status other than 0 = hipSuccess = ZKV_OK)
+#define HIP_TRY(x) do { if ((x) != 0) { (void)hipGetLastError(); return ZKV_ERR_HIP; } } while (0)
 
 // Releases every device resource of the context and returns it to the "not set up" state (safe on a partially set-up context).
 static void ctx_free_device(zkv_ctx* c) {
     if (!c->dev_ready && !c->stream) return;
     (void)hipSetDevice(c->device);
-    c->m16 = {nullptr, {0, 0, 0, 0, 0}};
-    c->gt = GT_NONE; c->gt_tried = false; c->gt_bytes = 0;
-    void** ptrs[] = {(void**)&c->d_tab, (void**)&c->d_msm16, (void**)&c->d_gt, (void**)&c->d_gt_const, (void**)&c->d_gt_cache, (void**)&c->ws.gtag, (void**)&c->ws.prep, (void**)&c->ws.norm, (void**)&c->ws.f, (void**)&c->ws.fe, (void**)&c->ws.flags,
-                     (void**)&c->ws.g2bad, (void**)&c->d_blob, (void**)&c->d_a, (void**)&c->d_b, (void**)&c->d_pv, (void**)&c->d_status,
-                     (void**)&c->d_recv, (void**)&c->d_off, (void**)&c->d_pvoff, (void**)&c->d_cd[0], (void**)&c->d_cd[1], (void**)&c->d_kind,
-                     (void**)&c->d_cdoff[0], (void**)&c->d_cdoff[1], (void**)&c->d_len, (void**)&c->d_pvlen, (void**)&c->d_st_all,
-                     (void**)&c->d_rv_all, (void**)&c->d_inst, (void**)&c->d_inst_idx, (void**)&c->d_pkey, (void**)&c->d_plonk_tab,
-                     (void**)&c->d_agg_tab, (void**)&c->d_agg, (void**)&c->ws2.prep, (void**)&c->ws2.norm, (void**)&c->ws2.f, (void**)&c->ws2.fe,
-                     (void**)&c->ws2.flags, (void**)&c->ws2.g2bad, (void**)&c->d_status2, (void**)&c->d_agg_cnt, (void**)&c->ws3.prep, (void**)&c->ws3.flags,
-                     (void**)&c->ws3.g2bad, (void**)&c->d_status3, (void**)&c->d_agg_idx, (void**)&c->d_ltab, (void**)&c->d_lwin, (void**)&c->d_lsig,
-                     (void**)&c->d_gs_tab, (void**)&c->d_gs_key, (void**)&c->d_gs_rows, (void**)&c->d_gs_win, (void**)&c->d_ps_ok};
-    for (void** p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    c->ws2.cap = 0; c->ws3 = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0}; c->agg_cap = 0; c->agg_key_ok = false;
-    for (int k = 0; k < 6; k++) { if (c->hb[k]) (void)hipFree(c->hb[k]); c->hb[k] = nullptr; c->hb_cap[k] = 0; }
-    for (size_t k = 0; k < sizeof c->mx / sizeof c->mx[0]; k++) { if (c->mx[k]) (void)hipFree(c->mx[k]); c->mx[k] = nullptr; c->mx_cap[k] = 0; }
-    c->ws.cap = 0; c->lsig_cap = 0; c->blob_cap = c->pv_cap = 0; c->cd_cap[0] = c->cd_cap[1] = c->st_all_cap = c->rv_all_cap = 0;
-    hipEvent_t* evs[] = {&c->ev[0], &c->ev[1], &c->ev[2], &c->ev[3], &c->ev[4], &c->ev[5], &c->ev_wire[0], &c->ev_wire[1], &c->ev_done,
-                         &c->ev_copied[0], &c->ev_copied[1], &c->ev_decoded[0], &c->ev_decoded[1], &c->ev_fork, &c->ev_join, &c->ev_seg[0], &c->ev_seg[1]};
-    for (hipEvent_t* e : evs) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-    c->has_done = false; c->wire_timed = false;
-    hipStream_t* streams[] = {&c->copy_stream, &c->side, &c->stream};
-    for (hipStream_t* st : streams) { if (*st) (void)hipStreamDestroy(*st); *st = nullptr; }
-    c->dev_ready = false;
+    static_cast<CtxDevice&>(*c) = CtxDevice();
 }
 
 static int gset_device_setup(zkv_ctx* c);
 static int pset_device_setup(zkv_ctx* c);
 // Lazily creates the streams, the VK tables (set-up kernels) and the events; the per-chunk workspace comes from ctx_reserve().
 static int ctx_device_setup(zkv_ctx* c) {
-    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    for (auto& e : c->ev) HIP_TRY(hipEventCreate(&e));
-    for (auto& e : c->ev_wire) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
-    HIP_TRY(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    for (auto& e : c->ev_seg) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(c->stream.create());
+    for (auto& e : c->ev) HIP_TRY(e.create());
+    for (auto& e : c->ev_wire) HIP_TRY(e.create());
+    HIP_TRY(c->ev_done.create(hipEventDisableTiming));
+    HIP_TRY(c->side.create());
+    HIP_TRY(c->copy_stream.create());
+    HIP_TRY(c->ev_fork.create(hipEventDisableTiming));
+    HIP_TRY(c->ev_join.create(hipEventDisableTiming));
+    for (auto& e : c->ev_seg) HIP_TRY(e.create(hipEventDisableTiming));
     for (int b = 0; b < 2; b++) {
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_copied[b], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_decoded[b], hipEventDisableTiming));
+        HIP_TRY(c->ev_copied[b].create(hipEventDisableTiming));
+        HIP_TRY(c->ev_decoded[b].create(hipEventDisableTiming));
     }
     if (c->vm == ZKV_VM_GROTH16_SET) return gset_device_setup(c);
     if (c->vm == ZKV_VM_PLONK_SET) return pset_device_setup(c);
@@ -417,16 +415,17 @@ static int ctx_device_setup(zkv_ctx* c) {
         }
         else host::fill_vk_sp1(raw);
         if (c->id_ge_r) memset(raw.fixed_scalar[5], 0, 32);      // never used: every proof fails the range check first
-        // the raw key and the instance parameters are only read by the set-up kernels; mx[0] / mx[1] hold them until those are done
-        HIP_TRY(hipMalloc(&c->mx[0], sizeof(VkRaw)));
-        VkRaw* d_raw = (VkRaw*)c->mx[0];
-        HIP_TRY(hipMalloc(&c->d_tab, sizeof(VkTables)));
+        // the raw key and the instance parameters are only read by the set-up kernels: scoped, released once those are done
+        DevBuf<VkRaw> d_raw;
+        DevBuf<> d_par;
+        HIP_TRY(d_raw.alloc(sizeof(VkRaw)));
+        HIP_TRY(c->d_tab.alloc(sizeof(VkTables)));
         HIP_TRY(hipMemsetAsync(c->d_tab, 0, sizeof(VkTables), c->stream));
         HIP_TRY(hipMemcpyAsync(d_raw, &raw, sizeof raw, hipMemcpyHostToDevice, c->stream));
         launch_setup(d_raw, c->d_tab, c->stream);
         HIP_TRY(hipGetLastError());
         if (c->long_key) {
-            // IC[1..n_ic-1]: validity (folded into vk_valid) and window rows, 512 KB per signal; the raw points (mx[1]) only until set-up is done
+            // IC[1..n_ic-1]: validity (folded into vk_valid) and window rows, 512 KB per signal; the raw points (d_par) only until set-up is done
             const uint32_t n_sig = c->g_n_ic - 1;
             std::vector<uint32_t> ic((size_t)16 * n_sig);
             for (uint32_t b = 0; b < n_sig; b++) {
@@ -434,12 +433,12 @@ static int ctx_device_setup(zkv_ctx* c) {
                 host::be_to_limbs(&ic[16 * (size_t)b + 8], c->gvk.data() + 480 + 64 * (size_t)(b + 1));
             }
             const size_t tab_bytes = (size_t)n_sig * LONG_ROW_ENTRIES * sizeof(G1A);
-            HIP_TRY(hipMalloc(&c->mx[1], sizeof(uint32_t) * ic.size()));
-            HIP_TRY(hipMalloc(&c->d_ltab, tab_bytes));
-            HIP_TRY(hipMalloc(&c->d_lwin, sizeof(uint32_t) * n_sig));
+            HIP_TRY(d_par.alloc(sizeof(uint32_t) * ic.size()));
+            HIP_TRY(c->d_ltab.alloc(tab_bytes));
+            HIP_TRY(c->d_lwin.alloc(sizeof(uint32_t) * n_sig));
             HIP_TRY(hipMemsetAsync(c->d_ltab, 0, tab_bytes, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->mx[1], ic.data(), sizeof(uint32_t) * ic.size(), hipMemcpyHostToDevice, c->stream));
-            launch_setup_long((const uint32_t*)c->mx[1], n_sig, c->d_tab, c->d_ltab, c->d_lwin, c->stream);
+            HIP_TRY(hipMemcpyAsync(d_par, ic.data(), sizeof(uint32_t) * ic.size(), hipMemcpyHostToDevice, c->stream));
+            launch_setup_long(d_par.as<const uint32_t>(), n_sig, c->d_tab, c->d_ltab, c->d_lwin, c->stream);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(c->stream));        // `ic` is a pageable host buffer about to go out of scope
         }
@@ -452,24 +451,21 @@ static int ctx_device_setup(zkv_ctx* c) {
             for (uint32_t b = 0; b < raw.n_var && b < (uint32_t)MAX_VAR; b++) { m.row0[b] = rows; rows += (raw.var_windows[b] + 1) / 2; }
             if (rows && rows <= MSM16_MAX_ROWS) {
                 const size_t bytes = (size_t)rows * 65536 * sizeof(G1A);
-                if (hipMalloc(&c->d_msm16, bytes) == hipSuccess) {
+                if (c->d_msm16.alloc(bytes) == ZKV_OK) {
                     HIP_TRY(hipMemsetAsync(c->d_msm16, 0, bytes, c->stream));
                     launch_setup_msm16(c->d_tab, m, c->d_msm16, rows, c->stream);
                     HIP_TRY(hipGetLastError());
                     m.tab = c->d_msm16;
                     c->m16 = m;
-                } else {                                         // no room for the rows (many contexts on one device): the 8-bit walk, same results
-                    (void)hipGetLastError();
-                    c->d_msm16 = nullptr;
-                }
+                }                                                // else no room for the rows (many contexts on one device): the 8-bit walk, same results
             }
         }
         if (agg_vm || is_plonk(c)) {
-            HIP_TRY(hipMalloc(&c->d_agg_cnt, 3 * sizeof(unsigned long long)));
+            HIP_TRY(c->d_agg_cnt.alloc(3 * sizeof(unsigned long long)));
             HIP_TRY(hipMemsetAsync(c->d_agg_cnt, 0, 3 * sizeof(unsigned long long), c->stream));
         }
         if (agg_vm) {
-            HIP_TRY(hipMalloc(&c->d_agg_tab, sizeof(AggTables)));
+            HIP_TRY(c->d_agg_tab.alloc(sizeof(AggTables)));
             launch_setup_agg(d_raw, c->d_tab, c->d_agg_tab, c->stream);
             HIP_TRY(hipGetLastError());
         }
@@ -478,9 +474,9 @@ static int ctx_device_setup(zkv_ctx* c) {
             InstConsts ic;
             host::sha256_host((const uint8_t*)"risc0.Groth16ReceiptVerifierParameters", 38, ic.tag);
             host::risc0_vk_digest(ic.vk_digest);
-            HIP_TRY(hipMalloc(&c->mx[1], sizeof(InstRaw) * k));
-            InstRaw* d_in = (InstRaw*)c->mx[1];
-            HIP_TRY(hipMalloc(&c->d_inst, sizeof(InstTab) * k));
+            HIP_TRY(d_par.alloc(sizeof(InstRaw) * k));
+            InstRaw* d_in = d_par.as<InstRaw>();
+            HIP_TRY(c->d_inst.alloc(sizeof(InstTab) * k));
             HIP_TRY(hipMemcpyAsync(d_in, c->inst_raw.data(), sizeof(InstRaw) * k, hipMemcpyHostToDevice, c->stream));
             launch_setup_instances(d_raw, ic, d_in, c->d_inst, (uint32_t)k, c->stream);
             HIP_TRY(hipGetLastError());
@@ -488,15 +484,15 @@ static int ctx_device_setup(zkv_ctx* c) {
             HIP_TRY(hipMemcpyAsync(c->inst_host.data(), c->d_inst, sizeof(InstTab) * k, hipMemcpyDeviceToHost, c->stream));
         }
         if (is_plonk(c)) {
-            HIP_TRY(hipMalloc(&c->mx[1], sizeof(PlonkKeyRaw)));
-            HIP_TRY(hipMalloc(&c->d_pkey, sizeof(PlonkKey)));
-            HIP_TRY(hipMemcpyAsync(c->mx[1], &c->pk_raw, sizeof(PlonkKeyRaw), hipMemcpyHostToDevice, c->stream));
-            if (c->vm == ZKV_VM_PLONK) launch_plonk_setup_keys((const PlonkKeyRaw*)c->mx[1], c->d_pkey, c->stream);
-            else launch_plonk_setup((const PlonkKeyRaw*)c->mx[1], c->d_pkey, c->stream);
+            HIP_TRY(d_par.alloc(sizeof(PlonkKeyRaw)));
+            HIP_TRY(c->d_pkey.alloc(sizeof(PlonkKey)));
+            HIP_TRY(hipMemcpyAsync(d_par, &c->pk_raw, sizeof(PlonkKeyRaw), hipMemcpyHostToDevice, c->stream));
+            if (c->vm == ZKV_VM_PLONK) launch_plonk_setup_keys(d_par.as<const PlonkKeyRaw>(), c->d_pkey, c->stream);
+            else launch_plonk_setup(d_par.as<const PlonkKeyRaw>(), c->d_pkey, c->stream);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
-        for (int k = 0; k < 2; k++) { if (c->mx[k]) (void)hipFree(c->mx[k]); c->mx[k] = nullptr; }
+        d_raw.release(); d_par.release();
         uint32_t valid = 0;
         HIP_TRY(hipMemcpy(&valid, &c->d_tab->vk_valid, sizeof valid, hipMemcpyDeviceToHost));
         c->vk_invalid = valid == 0;
@@ -536,32 +532,25 @@ static int ctx_device_init(zkv_ctx* c) {
 // pseudo-proof workspace per 16 proofs (the smallest sub-batch), and the dense workspace of the second pass (own PREP rows, flags, statuses, index list).
 static int agg_reserve(zkv_ctx* c) {
     if (!c->agg_on || !c->agg_key_ok || c->agg_cap >= c->ws.cap) return ZKV_OK;
-    void** bufs[] = {(void**)&c->d_agg, (void**)&c->ws2.prep, (void**)&c->ws2.norm, (void**)&c->ws2.f, (void**)&c->ws2.fe, (void**)&c->ws2.flags,
-                     (void**)&c->ws2.g2bad, (void**)&c->d_status2, (void**)&c->ws3.prep, (void**)&c->ws3.flags, (void**)&c->ws3.g2bad, (void**)&c->d_status3,
-                     (void**)&c->d_agg_idx};
-    for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
-    c->agg_cap = 0; c->ws2.cap = 0; c->ws3.cap = 0;
+    AggMem& g = *c;
+    g = AggMem();
     // room for the smallest sub-batch size; a key set pads its pseudo-proofs per key up to 1.25 times (gset_choose in run_gset) and runs
     // its second pass in place (k_gset_agg_mark): no dense workspace, no index list
     const bool set = c->vm == ZKV_VM_GROTH16_SET || c->vm == ZKV_VM_PLONK_SET;     // (a PLONK set pads per SRS class: run_pset)
     const size_t cap = c->ws.cap, cap2 = (cap + 15) / 16 + (set ? (cap + 63) / 64 : 0);
-    if (hipMalloc(&c->d_agg, sizeof(uint32_t) * WS_AGG_WORDS * cap) != hipSuccess ||
-        hipMalloc(&c->ws2.prep, sizeof(uint32_t) * WS_PREP_WORDS * cap2) != hipSuccess ||
-        hipMalloc(&c->ws2.norm, sizeof(uint32_t) * WS_NORM_WORDS * cap2) != hipSuccess ||
-        hipMalloc(&c->ws2.f, sizeof(uint32_t) * WS_F_WORDS * cap2) != hipSuccess ||
-        hipMalloc(&c->ws2.fe, sizeof(uint32_t) * WS_FE_WORDS * cap2) != hipSuccess ||
-        hipMalloc(&c->ws2.flags, sizeof(uint32_t) * cap2) != hipSuccess || hipMalloc(&c->ws2.g2bad, sizeof(uint32_t) * cap2) != hipSuccess ||
-        hipMalloc(&c->d_status2, cap2) != hipSuccess ||
-        (!set && (hipMalloc(&c->ws3.prep, sizeof(uint32_t) * WS_PREP_WORDS * cap) != hipSuccess || hipMalloc(&c->ws3.flags, sizeof(uint32_t) * cap) != hipSuccess ||
-                  hipMalloc(&c->ws3.g2bad, sizeof(uint32_t) * cap) != hipSuccess || hipMalloc(&c->d_status3, cap) != hipSuccess ||
-                  hipMalloc(&c->d_agg_idx, sizeof(uint32_t) * cap) != hipSuccess))) {
+    if (g.d_agg.alloc(sizeof(uint32_t) * WS_AGG_WORDS * cap) || g.ws2_prep.alloc(sizeof(uint32_t) * WS_PREP_WORDS * cap2) ||
+        g.ws2_norm.alloc(sizeof(uint32_t) * WS_NORM_WORDS * cap2) || g.ws2_f.alloc(sizeof(uint32_t) * WS_F_WORDS * cap2) ||
+        g.ws2_fe.alloc(sizeof(uint32_t) * WS_FE_WORDS * cap2) || g.ws2_flags.alloc(sizeof(uint32_t) * cap2) ||
+        g.ws2_g2bad.alloc(sizeof(uint32_t) * cap2) || g.d_status2.alloc(cap2) ||
+        (!set && (g.ws3_prep.alloc(sizeof(uint32_t) * WS_PREP_WORDS * cap) || g.ws3_flags.alloc(sizeof(uint32_t) * cap) ||
+                  g.ws3_g2bad.alloc(sizeof(uint32_t) * cap) || g.d_status3.alloc(cap) || g.d_agg_idx.alloc(sizeof(uint32_t) * cap)))) {
         // no room for the extra 0.9 KB per proof in flight: the chunk takes the ordinary kernels (enqueue_chunk looks at agg_cap)
-        (void)hipGetLastError();
-        for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+        g = AggMem();
         return ZKV_OK;
     }
-    if (!set) { c->ws3.norm = c->ws.norm; c->ws3.f = c->ws.f; c->ws3.fe = c->ws.fe; c->ws3.cap = cap; }
-    c->ws2.cap = cap2; c->agg_cap = cap;
+    g.ws2 = Workspace{g.ws2_prep, g.ws2_norm, g.ws2_f, g.ws2_fe, g.ws2_flags, g.ws2_g2bad, cap2};
+    if (!set) g.ws3 = Workspace{g.ws3_prep, c->ws.norm, c->ws.f, c->ws.fe, g.ws3_flags, g.ws3_g2bad, cap};
+    g.agg_cap = cap;
     return ZKV_OK;
 }
 static int ctx_reserve(zkv_ctx* c, size_t want) {
@@ -571,31 +560,20 @@ static int ctx_reserve(zkv_ctx* c, size_t want) {
     size_t cap = 4096;
     while (cap < want) cap <<= 1;
     if (cap > limit) cap = limit;
-    void** bufs[] = {(void**)&c->ws.prep, (void**)&c->ws.norm, (void**)&c->ws.f, (void**)&c->ws.fe, (void**)&c->ws.flags, (void**)&c->ws.g2bad,
-                     (void**)&c->ws.gtag, (void**)&c->d_a, (void**)&c->d_b, (void**)&c->d_status, (void**)&c->d_recv, (void**)&c->d_off, (void**)&c->d_pvoff,
-                     (void**)&c->d_inst_idx, (void**)&c->d_len, (void**)&c->d_pvlen, (void**)&c->d_kind, (void**)&c->d_cdoff[0], (void**)&c->d_cdoff[1],
-                     (void**)&c->d_plonk_tab};
-    for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
-    c->ws.cap = 0;
-    if (hipMalloc(&c->ws.prep, sizeof(uint32_t) * WS_PREP_WORDS * cap) != hipSuccess ||
-        hipMalloc(&c->ws.norm, sizeof(uint32_t) * WS_NORM_WORDS * cap) != hipSuccess ||
-        hipMalloc(&c->ws.f, sizeof(uint32_t) * WS_F_WORDS * cap) != hipSuccess ||
-        hipMalloc(&c->ws.fe, sizeof(uint32_t) * WS_FE_WORDS * cap) != hipSuccess ||
-        hipMalloc(&c->ws.flags, sizeof(uint32_t) * cap) != hipSuccess || hipMalloc(&c->ws.g2bad, sizeof(uint32_t) * cap) != hipSuccess ||
-        hipMalloc(&c->ws.gtag, cap) != hipSuccess ||
-        hipMalloc(&c->d_a, 32 * cap) != hipSuccess || hipMalloc(&c->d_b, 32 * cap) != hipSuccess ||
-        hipMalloc(&c->d_status, cap) != hipSuccess || hipMalloc(&c->d_recv, 4 * cap) != hipSuccess ||
-        hipMalloc(&c->d_off, sizeof(uint64_t) * (cap + 1)) != hipSuccess ||
-        hipMalloc(&c->d_pvoff, sizeof(uint64_t) * (cap + 1)) != hipSuccess ||
-        hipMalloc(&c->d_inst_idx, sizeof(uint32_t) * cap) != hipSuccess ||
-        hipMalloc(&c->d_len, sizeof(uint32_t) * cap) != hipSuccess || hipMalloc(&c->d_pvlen, sizeof(uint32_t) * cap) != hipSuccess ||
-        hipMalloc(&c->d_kind, cap) != hipSuccess || hipMalloc(&c->d_cdoff[0], sizeof(uint64_t) * (cap + 1)) != hipSuccess ||
-        hipMalloc(&c->d_cdoff[1], sizeof(uint64_t) * (cap + 1)) != hipSuccess ||
-        ((is_plonk(c) || c->vm == ZKV_VM_PLONK_SET) && hipMalloc(&c->d_plonk_tab, sizeof(uint32_t) * PLONK_TAB_WORDS * cap) != hipSuccess)) {
-        (void)hipGetLastError();
+    ChunkMem& m = *c;
+    m = ChunkMem();
+    if (m.ws_prep.alloc(sizeof(uint32_t) * WS_PREP_WORDS * cap) || m.ws_norm.alloc(sizeof(uint32_t) * WS_NORM_WORDS * cap) ||
+        m.ws_f.alloc(sizeof(uint32_t) * WS_F_WORDS * cap) || m.ws_fe.alloc(sizeof(uint32_t) * WS_FE_WORDS * cap) ||
+        m.ws_flags.alloc(sizeof(uint32_t) * cap) || m.ws_g2bad.alloc(sizeof(uint32_t) * cap) || m.ws_gtag.alloc(cap) ||
+        m.d_a.alloc(32 * cap) || m.d_b.alloc(32 * cap) || m.d_status.alloc(cap) || m.d_recv.alloc(4 * cap) ||
+        m.d_off.alloc(sizeof(uint64_t) * (cap + 1)) || m.d_pvoff.alloc(sizeof(uint64_t) * (cap + 1)) ||
+        m.d_inst_idx.alloc(sizeof(uint32_t) * cap) || m.d_len.alloc(sizeof(uint32_t) * cap) || m.d_pvlen.alloc(sizeof(uint32_t) * cap) ||
+        m.d_kind.alloc(cap) || m.d_cdoff[0].alloc(sizeof(uint64_t) * (cap + 1)) || m.d_cdoff[1].alloc(sizeof(uint64_t) * (cap + 1)) ||
+        ((is_plonk(c) || c->vm == ZKV_VM_PLONK_SET) && m.d_plonk_tab.alloc(sizeof(uint32_t) * PLONK_TAB_WORDS * cap))) {
+        m = ChunkMem();                                      // (at once: the survivors of a failed reserve are of no use to anyone)
         return ZKV_ERR_OOM;
     }
-    c->ws.cap = cap;
+    m.ws = Workspace{m.ws_prep, m.ws_norm, m.ws_f, m.ws_fe, m.ws_flags, m.ws_g2bad, cap, m.ws_gtag};
     return agg_reserve(c);
 }
 // Fixed-base GT tables (zkv_gt.h) for the (vk_x, gamma) pairing of an SP1 or RISC Zero context: 2^19 entries of 384 bytes per signed 20-bit
@@ -638,11 +616,11 @@ static int gt_maybe_build(zkv_ctx* c, size_t n) {
     if (nw0 > GT_MAX_WINDOWS || nw1 > GT_MAX_WINDOWS) return ZKV_OK;
     const size_t bytes = (size_t)rows * GT_ROW_BYTES;
     if (bytes > gt_max_bytes()) return ZKV_OK;
-    VkRaw* d_raw = nullptr; uint32_t* d_scr = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool ok = hipMalloc(&c->d_gt, bytes) == hipSuccess && hipMalloc(&c->d_gt_const, sizeof(uint32_t) * GT_ENTRY_WORDS) == hipSuccess &&
-              hipMalloc(&d_raw, sizeof(VkRaw)) == hipSuccess && hipMalloc(&d_scr, sizeof(uint32_t) * GT_SETUP_SCRATCH_WORDS) == hipSuccess &&
-              hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    DevBuf<VkRaw> d_raw; DevBuf<uint32_t> d_scr;
+    DevEvent e0, e1;
+    bool ok = c->d_gt.alloc(bytes) == ZKV_OK && c->d_gt_const.alloc(sizeof(uint32_t) * GT_ENTRY_WORDS) == ZKV_OK &&
+              d_raw.alloc(sizeof(VkRaw)) == ZKV_OK && d_scr.alloc(sizeof(uint32_t) * GT_SETUP_SCRATCH_WORDS) == ZKV_OK &&
+              e0.create() == ZKV_OK && e1.create() == ZKV_OK;
     if (ok) {
         ok = hipMemcpyAsync(d_raw, &raw, sizeof raw, hipMemcpyHostToDevice, c->stream) == hipSuccess;
         (void)hipEventRecord(e0, c->stream);
@@ -654,14 +632,9 @@ static int gt_maybe_build(zkv_ctx* c, size_t n) {
         if (ok) (void)hipEventElapsedTime(&c->gt_build_ms, e0, e1);
     }
     (void)hipGetLastError();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (d_raw) (void)hipFree(d_raw);
-    if (d_scr) (void)hipFree(d_scr);
+    d_raw.release(); d_scr.release();
     if (!ok) {                                                // no room (or a failed launch): the Miller path, same results
-        if (c->d_gt) (void)hipFree(c->d_gt);
-        if (c->d_gt_const) (void)hipFree(c->d_gt_const);
-        c->d_gt = c->d_gt_const = nullptr;
+        c->d_gt.release(); c->d_gt_const.release();
         return ZKV_OK;
     }
     c->gt = GtTab{c->d_gt, c->d_gt_const, {nw0, nw1}, nullptr};
@@ -670,9 +643,9 @@ static int gt_maybe_build(zkv_ctx* c, size_t n) {
     if (c->vm == ZKV_VM_SP1 && gt_cache_wanted()) {
         GtCache head = {};
         head.entries = GT_CACHE_ENTRIES;
-        if (hipMalloc(&c->d_gt_cache, sizeof(GtCache)) == hipSuccess && hipMemset(c->d_gt_cache, 0, sizeof(GtCache)) == hipSuccess &&
+        if (c->d_gt_cache.alloc(sizeof(GtCache)) == ZKV_OK && hipMemset(c->d_gt_cache, 0, sizeof(GtCache)) == hipSuccess &&
             hipMemcpy(c->d_gt_cache, &head, 4 * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess) c->gt.cache = c->d_gt_cache;
-        else { (void)hipGetLastError(); if (c->d_gt_cache) (void)hipFree(c->d_gt_cache); c->d_gt_cache = nullptr; }
+        else { (void)hipGetLastError(); c->d_gt_cache.release(); }
     }
     return ZKV_OK;
 }
@@ -683,15 +656,6 @@ static int ctx_ready(zkv_ctx* c, size_t n, bool verify = true) {
     if (rc == ZKV_OK) rc = ctx_reserve(c, n ? n : 1);
     if (rc == ZKV_OK && verify) rc = gt_maybe_build(c, n ? n : 1);
     return rc;
-}
-static int grow(uint8_t** p, size_t* cap, size_t need) {
-    if (need <= *cap) return ZKV_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    size_t want = need + need / 4 + 4096;
-    if (hipMalloc(p, want) != hipSuccess) { (void)hipGetLastError(); return ZKV_ERR_OOM; }
-    *cap = want;
-    return ZKV_OK;
 }
 
 // Cross-stream ordering of consecutive calls on one context (see zkv_ctx::ev_done).
@@ -860,7 +824,9 @@ static uint32_t msm_lanes_long(const zkv_ctx* c, size_t n) {
     const char* e = getenv("ZKV_LONG_LANE_BELOW");
     return n < (e ? (size_t)strtoull(e, nullptr, 10) : ((size_t)1 << 18)) ? 16u : 1u;
 }
-static LongKey long_key_of(const zkv_ctx* c) { return LongKey{c->d_ltab, c->d_lwin, c->d_lsig, c->lsig_cap, c->g_n_ic - 1}; }
+// proofs the staged-signal rows of a long key or a key set have room for (= their row stride): d_lsig holds 32 bytes per signal and proof
+static size_t lsig_stride(const zkv_ctx* c) { return c->g_n_ic > 1 ? c->d_lsig.cap() / ((size_t)32 * (c->g_n_ic - 1)) : 0; }
+static LongKey long_key_of(const zkv_ctx* c) { return LongKey{c->d_ltab, c->d_lwin, c->d_lsig, lsig_stride(c), c->g_n_ic - 1}; }
 
 // Enqueues the five stages for one chunk (all pointers device-resident).
 static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool timed) {
@@ -888,7 +854,7 @@ static void enqueue_chunk(zkv_ctx* c, const PrepArgs& a, hipStream_t s, bool tim
         return;
     }
     if (c->vm == ZKV_VM_RISC0 || c->vm == ZKV_VM_RISC0_SET) launch_prep_risc0(a, c->consts, c->ws, s);
-    else if (c->vm == ZKV_VM_GROTH16 && c->long_key) launch_prep_groth16_long(a, c->ws, c->d_lsig, c->lsig_cap, s);
+    else if (c->vm == ZKV_VM_GROTH16 && c->long_key) launch_prep_groth16_long(a, c->ws, c->d_lsig, lsig_stride(c), s);
     else if (c->vm == ZKV_VM_GROTH16) launch_prep_groth16(a, c->ws, s);
     else launch_prep_sp1(a, c->ws, s);
     if (timed) (void)hipEventRecord(c->ev[1], s);
@@ -1002,10 +968,10 @@ static int run_host_batch(zkv_ctx* c, size_t n, const uint8_t* blob, const uint6
         const uint64_t s0 = off[p0], sbytes = off[p0 + pn] - s0;
         const uint64_t v0 = sp1 ? pv_off[p0] : 0, vbytes = sp1 ? pv_off[p0 + pn] - v0 : 0;
         // growing a buffer frees the old one, which synchronises the device: everything is sized before the first copy
-        if ((rc = grow(&c->hb[0], &c->hb_cap[0], (size_t)sbytes + 8)) != ZKV_OK || (rc = grow(&c->hb[1], &c->hb_cap[1], 8 * (pn + 1))) != ZKV_OK ||
-            (rc = grow(&c->hb[2], &c->hb_cap[2], 32 * pn)) != ZKV_OK || (in_b && (rc = grow(&c->hb[3], &c->hb_cap[3], 32 * pn)) != ZKV_OK) ||
-            (sp1 && ((rc = grow(&c->hb[4], &c->hb_cap[4], (size_t)vbytes + 8)) != ZKV_OK || (rc = grow(&c->hb[5], &c->hb_cap[5], 8 * (pn + 1))) != ZKV_OK)) ||
-            (rc = grow(&c->d_st_all, &c->st_all_cap, pn)) != ZKV_OK || (rc = grow(&c->d_rv_all, &c->rv_all_cap, 4 * pn)) != ZKV_OK) return rc;
+        if ((rc = c->hb[0].grow((size_t)sbytes + 8)) != ZKV_OK || (rc = c->hb[1].grow(8 * (pn + 1))) != ZKV_OK ||
+            (rc = c->hb[2].grow(32 * pn)) != ZKV_OK || (in_b && (rc = c->hb[3].grow(32 * pn)) != ZKV_OK) ||
+            (sp1 && ((rc = c->hb[4].grow((size_t)vbytes + 8)) != ZKV_OK || (rc = c->hb[5].grow(8 * (pn + 1))) != ZKV_OK)) ||
+            (rc = c->d_st_all.grow(pn)) != ZKV_OK || (rc = c->d_rv_all.grow(4 * pn)) != ZKV_OK) return rc;
         // offsets relative to the pass (the caller's array is used as it is when the pass starts at offset 0)
         const uint64_t* o = off + p0; const uint64_t* po = sp1 ? pv_off + p0 : nullptr;
         if (s0) { rel.resize(pn + 1); for (size_t i = 0; i <= pn; i++) rel[i] = off[p0 + i] - s0; o = rel.data(); }
@@ -1013,8 +979,8 @@ static int run_host_batch(zkv_ctx* c, size_t n, const uint8_t* blob, const uint6
         const size_t first = host_first_segment(pn, cap);
         // ZKV_HOST_TRACE=1 (diagnostic): events around the segments' copies and kernels, printed to stderr after the pass
         const bool trace = getenv("ZKV_HOST_TRACE") != nullptr;
-        std::vector<hipEvent_t> tev;
-        auto mark = [&](hipStream_t st) { if (!trace) return; hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, st); tev.push_back(e); } };
+        std::vector<DevEvent> tev;
+        auto mark = [&](hipStream_t st) { if (!trace) return; DevEvent e; if (e.create() == ZKV_OK) { (void)hipEventRecord(e, st); tev.push_back(std::move(e)); } };
         mark(c->stream);
         for (size_t base = 0, k = 0; base < pn; k++) {
             // (a third, intermediate segment of 2 * first was measured and dropped: 202.6 against 200.7 ms per 2^20 SP1 proofs,
@@ -1034,10 +1000,10 @@ static int run_host_batch(zkv_ctx* c, size_t n, const uint8_t* blob, const uint6
             HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_seg[k & 1], 0));
             PrepArgs a;
             memset(&a, 0, sizeof a);
-            a.n = m; a.blob = c->hb[0]; a.off = (const uint64_t*)c->hb[1] + base; a.stride = 0;
+            a.n = m; a.blob = c->hb[0]; a.off = c->hb[1].as<const uint64_t>() + base; a.stride = 0;
             a.in32_a = c->hb[2] + 32 * base; a.in32_b = in_b ? c->hb[3] + 32 * base : nullptr;
             if (sp1) {
-                a.pv_blob = c->hb[4]; a.pv_off = (const uint64_t*)c->hb[5] + base;
+                a.pv_blob = c->hb[4]; a.pv_off = c->hb[5].as<const uint64_t>() + base;
                 a.selector_be = be32_of(c->vm == ZKV_VM_SP1_PLONK ? c->plonk_hash : host::SP1_VERIFIER_HASH);
                 a.force_fail = c->vm == ZKV_VM_SP1_PLONK && c->vk_invalid ? 1u : 0u;
             } else {
@@ -1059,7 +1025,6 @@ static int run_host_batch(zkv_ctx* c, size_t n, const uint8_t* blob, const uint6
             for (size_t i = 1; i < tev.size(); i++) { float ms = 0; (void)hipEventElapsedTime(&ms, tev[0], tev[i]); fprintf(stderr, " %.2f", ms); }
             fprintf(stderr, "\n");
         }
-        for (auto e : tev) (void)hipEventDestroy(e);
     }
     return ZKV_OK;
 }
@@ -1196,10 +1161,10 @@ template <class F> static int run_sharded(zkv_ctx* c, size_t n, F per_shard) {
 static int shard_dev_setup(zkv_ctx::ShardDev& d, int device) {
     if (d.run) return ZKV_OK;
     HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipStreamCreateWithFlags(&d.run, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&d.copy, hipStreamNonBlocking));
-    for (auto& e : d.ev_piece) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&d.ev_done, hipEventDisableTiming));
+    HIP_TRY(d.run.create());
+    HIP_TRY(d.copy.create());
+    for (auto& e : d.ev_piece) HIP_TRY(e.create(hipEventDisableTiming));
+    HIP_TRY(d.ev_done.create(hipEventDisableTiming));
     return ZKV_OK;
 }
 struct DevRow { const uint8_t* p; size_t stride; };
@@ -1215,11 +1180,11 @@ static int run_sharded_dev(zkv_ctx* c, size_t n, const DevRow* rows, int n_rows,
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (sdev < 0 || sdev >= ndev) return ZKV_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->ev_in.size() < (size_t)ndev) c->ev_in.resize(ndev, nullptr);
+    if (c->ev_in.size() < (size_t)ndev) c->ev_in.resize(ndev);
     hipStream_t caller = (hipStream_t)stream;
     if (caller) {                                     // the shards' streams start after what the caller's stream has enqueued so far
         HIP_TRY(hipSetDevice(sdev));
-        if (!c->ev_in[sdev]) HIP_TRY(hipEventCreateWithFlags(&c->ev_in[sdev], hipEventDisableTiming));
+        if (!c->ev_in[sdev]) HIP_TRY(c->ev_in[sdev].create(hipEventDisableTiming));
         HIP_TRY(hipEventRecord(c->ev_in[sdev], caller));
     }
     const size_t used = shards_used(c, n);
@@ -1248,8 +1213,8 @@ static int run_sharded_dev(zkv_ctx* c, size_t n, const DevRow* rows, int n_rows,
             // the staging rows are about to be overwritten: not before the previous call's kernels on this shard have read them (that call may
             // have been enqueued on another caller stream, or with none, and still be running)
             if (d.has_done) HIP_TRY(hipStreamWaitEvent(d.copy, d.ev_done, 0));
-            for (int j = 0; j < n_rows; j++) if ((r = grow(&d.row[j], &d.row_cap[j], m * rows[j].stride + 8)) != ZKV_OK) return r;
-            if ((r = grow(&d.st, &d.st_cap, m)) != ZKV_OK || (d_recv && (r = grow(&d.rv, &d.rv_cap, 4 * m)) != ZKV_OK)) return r;
+            for (int j = 0; j < n_rows; j++) if ((r = d.row[j].grow(m * rows[j].stride + 8)) != ZKV_OK) return r;
+            if ((r = d.st.grow(m)) != ZKV_OK || (d_recv && (r = d.rv.grow(4 * m)) != ZKV_OK)) return r;
         }
         // two pieces: the first (at most `first` proofs) is what the kernels wait for, the rest travels behind its kernels
         size_t pc[3] = {0, m, m};
@@ -1296,15 +1261,9 @@ static void shards_free(zkv_ctx* c) {
         if (!d.run) continue;
         (void)hipSetDevice(c->shards[k]->device);
         (void)hipStreamSynchronize(d.run); (void)hipStreamSynchronize(d.copy);
-        for (auto& r : d.row) { if (r) (void)hipFree(r); r = nullptr; }
-        if (d.st) (void)hipFree(d.st);
-        if (d.rv) (void)hipFree(d.rv);
-        for (auto& e : d.ev_piece) if (e) (void)hipEventDestroy(e);
-        if (d.ev_done) (void)hipEventDestroy(d.ev_done);
-        (void)hipStreamDestroy(d.copy); (void)hipStreamDestroy(d.run);
         d = zkv_ctx::ShardDev();
     }
-    for (auto& e : c->ev_in) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    c->ev_in.clear();
     for (auto& k : c->shards) { if (k) zkv_ctx_destroy(k); k = nullptr; }
     c->shards.clear(); c->sh.clear();
 }
@@ -1387,17 +1346,17 @@ static int run_mixed(zkv_ctx* c, size_t n, const uint8_t* d_vm, const uint8_t* d
     int rc;
     const size_t blocks = (n + 255) / 256;
     const size_t need[13] = {8 * blocks, 8, 4 * n, 4 * n, (size_t)ZKV_SEAL_BYTES * n, 4 * n, 32 * n, 32 * n, 8 * n, 4 * n, n, 4 * n, n};
-    for (int k = 0; k < 13; k++) if ((rc = grow(&c->mx[k], &c->mx_cap[k], need[k])) != ZKV_OK) return rc;
+    for (int k = 0; k < 13; k++) if ((rc = c->mx[k].grow(need[k])) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     MixedArgs a;
     memset(&a, 0, sizeof a);
     a.n = n; a.vm = d_vm; a.method = d_method; a.seals = d_seals; a.seal_off = d_seal_off; a.seal_stride = seal_stride;
     a.in_a = d_a; a.in_b = d_b; a.b_off = d_b_off; a.b_stride = b_stride; a.pv_len = pv_len;
-    a.cnt = (uint32_t*)c->mx[MX_CNT]; a.totals = (uint32_t*)c->mx[MX_TOT]; a.pos = (uint32_t*)c->mx[MX_POS]; a.idx = (uint32_t*)c->mx[MX_IDX];
-    a.c_seals = c->mx[MX_SEALS]; a.c_len = (uint32_t*)c->mx[MX_LEN]; a.c_a = c->mx[MX_A]; a.c_b = c->mx[MX_B];
-    a.c_pvoff = (uint64_t*)c->mx[MX_PVOFF]; a.c_pvlen = (uint32_t*)c->mx[MX_PVLEN]; a.c_kind = c->mx[MX_KIND];
+    a.cnt = c->mx[MX_CNT].as<uint32_t>(); a.totals = c->mx[MX_TOT].as<uint32_t>(); a.pos = c->mx[MX_POS].as<uint32_t>(); a.idx = c->mx[MX_IDX].as<uint32_t>();
+    a.c_seals = c->mx[MX_SEALS]; a.c_len = c->mx[MX_LEN].as<uint32_t>(); a.c_a = c->mx[MX_A]; a.c_b = c->mx[MX_B];
+    a.c_pvoff = c->mx[MX_PVOFF].as<uint64_t>(); a.c_pvlen = c->mx[MX_PVLEN].as<uint32_t>(); a.c_kind = c->mx[MX_KIND];
     a.status = d_status; a.recv = d_recv;
-    launch_mixed_partition(a, (uint32_t*)c->mx[MX_CNT], (uint32_t*)c->mx[MX_TOT], s);
+    launch_mixed_partition(a, c->mx[MX_CNT].as<uint32_t>(), c->mx[MX_TOT].as<uint32_t>(), s);
     HIP_TRY(hipGetLastError());
     uint32_t tot[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(tot, c->mx[MX_TOT], sizeof tot, hipMemcpyDeviceToHost, s));
@@ -1455,8 +1414,8 @@ ZKV_EXPORT int zkv_mixed_verify_call_batch(zkv_ctx* c, size_t n, const uint8_t* 
     if (rc != ZKV_OK) return rc;
     const uint64_t s0 = seal_off[0], sbytes = seal_off[n] - s0, b0 = in_b_off[0], bbytes = in_b_off[n] - b0;
     const size_t need[8] = {n, (size_t)sbytes + 8, 8 * (n + 1), 32 * n, (size_t)bbytes + 8, 8 * (n + 1), n, 4 * n};
-    for (int k = 0; k < 8; k++) if ((rc = grow(&c->mx[MX_H_VM + k], &c->mx_cap[MX_H_VM + k], need[k])) != ZKV_OK) return rc;
-    if (method && (rc = grow(&c->mx[MX_H_METHOD], &c->mx_cap[MX_H_METHOD], n)) != ZKV_OK) return rc;
+    for (int k = 0; k < 8; k++) if ((rc = c->mx[MX_H_VM + k].grow(need[k])) != ZKV_OK) return rc;
+    if (method && (rc = c->mx[MX_H_METHOD].grow(n)) != ZKV_OK) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     std::vector<uint64_t> so(seal_off, seal_off + n + 1), bo(in_b_off, in_b_off + n + 1);
@@ -1469,8 +1428,8 @@ ZKV_EXPORT int zkv_mixed_verify_call_batch(zkv_ctx* c, size_t n, const uint8_t* 
     HIP_TRY(hipMemcpyAsync(c->mx[MX_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
     if (bbytes) HIP_TRY(hipMemcpyAsync(c->mx[MX_H_B], in_b_blob + b0, (size_t)bbytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->mx[MX_H_BOFF], bo.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
-    if ((rc = run_mixed(c, n, c->mx[MX_H_VM], method ? c->mx[MX_H_METHOD] : nullptr, c->mx[MX_H_SEALS], (const uint64_t*)c->mx[MX_H_SOFF], 0, c->mx[MX_H_A],
-                        c->mx[MX_H_B], (const uint64_t*)c->mx[MX_H_BOFF], 0, 0, c->mx[MX_H_ST], c->mx[MX_H_RV], s)) != ZKV_OK) return rc;
+    if ((rc = run_mixed(c, n, c->mx[MX_H_VM], method ? c->mx[MX_H_METHOD] : nullptr, c->mx[MX_H_SEALS], c->mx[MX_H_SOFF].as<const uint64_t>(), 0, c->mx[MX_H_A],
+                        c->mx[MX_H_B], c->mx[MX_H_BOFF].as<const uint64_t>(), 0, 0, c->mx[MX_H_ST], c->mx[MX_H_RV], s)) != ZKV_OK) return rc;
     HIP_TRY(hipMemcpyAsync(status, c->mx[MX_H_ST], n, hipMemcpyDeviceToHost, s));
     if (recv) HIP_TRY(hipMemcpyAsync(recv, c->mx[MX_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1651,7 +1610,7 @@ static int run_set_batch(zkv_ctx* c, size_t n, const uint32_t* inst, const uint8
             a.in32_a = ids + 32 * base; a.in32_b = integrity ? nullptr : jds + 32 * base; a.status = status + base; a.recv = recv ? recv + 4 * base : nullptr;
         } else {
             const uint64_t b0 = off[base], bytes = off[base + m] - b0;
-            if ((rc = grow(&c->d_blob, &c->blob_cap, (size_t)bytes + 8)) != ZKV_OK) return rc;
+            if ((rc = c->d_blob.grow((size_t)bytes + 8)) != ZKV_OK) return rc;
             for (size_t i = 0; i <= m; i++) rel[i] = off[base + i] - b0;
             HIP_TRY(hipMemcpyAsync(c->d_off, rel.data(), sizeof(uint64_t) * (m + 1), hipMemcpyHostToDevice, s));
             if (bytes) HIP_TRY(hipMemcpyAsync(c->d_blob, blob + b0, (size_t)bytes, hipMemcpyHostToDevice, s));
@@ -1703,8 +1662,8 @@ ZKV_EXPORT int zkv_risc0_set_vk_x_batch(zkv_ctx* c, size_t n, const uint32_t* in
     const size_t cap = c->ws.cap;
     for (size_t base = 0; base < n; base += cap) {
         size_t m = n - base < cap ? n - base : cap;
-        if ((rc = grow(&c->d_blob, &c->blob_cap, m * 64 + 8)) != ZKV_OK) return rc;
-        if ((rc = grow(&c->d_pv, &c->pv_cap, m * 64 + 8)) != ZKV_OK) return rc;
+        if ((rc = c->d_blob.grow(m * 64 + 8)) != ZKV_OK) return rc;
+        if ((rc = c->d_pv.grow(m * 64 + 8)) != ZKV_OK) return rc;
         HIP_TRY(hipMemcpyAsync(c->d_blob, var_signals + 64 * base, 64 * m, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->d_inst_idx, instance + base, sizeof(uint32_t) * m, hipMemcpyHostToDevice, c->stream));
         launch_vk_x(m, c->d_tab, c->m16, c->d_inst, c->d_inst_idx, c->d_blob, c->d_pv, c->stream);
@@ -1836,8 +1795,8 @@ static int stage_ragged(zkv_ctx* c, int k_blob, int k_off, const uint8_t* blob, 
     const uint64_t o0 = off[0];
     *bytes = off[n] - o0;
     int rc;
-    if ((rc = grow(&c->mx[k_blob], &c->mx_cap[k_blob], (size_t)*bytes + 8)) != ZKV_OK ||
-        (rc = grow(&c->mx[k_off], &c->mx_cap[k_off], 8 * (n + 1))) != ZKV_OK) return rc;
+    if ((rc = c->mx[k_blob].grow((size_t)*bytes + 8)) != ZKV_OK ||
+        (rc = c->mx[k_off].grow(8 * (n + 1))) != ZKV_OK) return rc;
     rebased->assign(off, off + n + 1);
     for (auto& v : *rebased) v -= o0;
     if (*bytes) HIP_TRY(hipMemcpyAsync(c->mx[k_blob], blob + o0, (size_t)*bytes, hipMemcpyHostToDevice, s));
@@ -1889,7 +1848,7 @@ static int run_keyed_group(zkv_ctx* g, size_t M, int lanes, const uint32_t* idx,
         memset(&ch, 0, sizeof ch);
         ch.m = m; ch.slot0 = base; ch.idx = idx; ch.skey = skey;
         ch.keys = g->d_gs_key; ch.rows = g->d_gs_rows; ch.win = g->d_gs_win;
-        ch.sig = g->d_lsig; ch.sig_cap = g->lsig_cap; ch.status = st + base;
+        ch.sig = g->d_lsig; ch.sig_cap = lsig_stride(g); ch.status = st + base;
         if ((rc = gset_proof_stages(g, ch, lanes, base + cap >= M, s, [&] { prep(ch); })) != ZKV_OK) return rc;
     }
     return mark_done(g, s);
@@ -2020,7 +1979,7 @@ enum { GW_CNT = 0, GW_TOT, GW_POS, GW_IDX, GW_RECS, GW_LEN, GW_A, GW_PVOFF, GW_P
        GW_H_VK, GW_H_PV, GW_H_PVOFF, GW_H_PROOF, GW_H_POFF, GW_H_ST, GW_H_RV,
        GWW_VK, GWW_PVAT, GWW_PVLEN, GWW_PAT, GWW_PLEN, GWW_BAD, GWW_ARENA, GWW_H_CD, GWW_H_OFF,        // calldata batches (run_gateway_wire)
        GW_SKEY };                                                                                     // keyed group: the key of every group slot
-static_assert(GW_SKEY < sizeof(((zkv_ctx*)nullptr)->mx) / sizeof(uint8_t*), "the gateway's buffers live in zkv_ctx::mx");
+static_assert(GW_SKEY < CtxDevice::MX_SLOTS, "the gateway's buffers live in zkv_ctx::mx");
 // Everything device-resident: ragged proofs (offsets bounded by proof_bytes on the device); public values ragged (d_pv_off) or at a
 // fixed stride.  Or, from the calldata decoder, `recs`: (start, length) records of proofs and public values from one base address, which
 // d_proofs and d_pv then both are, and bad-calldata marks.  Synchronises `s` once, after the count, to size the compact records and learn
@@ -2033,8 +1992,8 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
     // slots: one per routed proof, and up to 31 pad slots behind every keyed route (its successor starts on a wavefront of the Miller mapping)
     const size_t ns = n + 32 * K;
     const size_t need[11] = {4 * GW_COLS * blocks, 4 * GW_COLS, 4 * n, 4 * ns, 0, 4 * ns, 32 * ns, 8 * ns, 4 * ns, ns, 4 * ns};
-    for (int k = 0; k < 11; k++) if (k != GW_RECS && (rc = grow(&c->mx[k], &c->mx_cap[k], need[k])) != ZKV_OK) return rc;
-    if (K && (rc = grow(&c->mx[GW_SKEY], &c->mx_cap[GW_SKEY], 4 * ns)) != ZKV_OK) return rc;
+    for (int k = 0; k < 11; k++) if (k != GW_RECS && (rc = c->mx[k].grow(need[k])) != ZKV_OK) return rc;
+    if (K && (rc = c->mx[GW_SKEY].grow(4 * ns)) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     GatewayArgs a;
     memset(&a, 0, sizeof a);
@@ -2045,8 +2004,8 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
         a.sel[r] = c->gw_sel[r];
         a.rec[r] = c->gw_route[r] && c->gw_route[r]->vm == ZKV_VM_SP1_PLONK ? ZKV_PLONK_PROOF_BYTES : ZKV_SEAL_BYTES;
     }
-    a.cnt = (uint32_t*)c->mx[GW_CNT]; a.totals = (uint32_t*)c->mx[GW_TOT]; a.pos = (uint32_t*)c->mx[GW_POS]; a.idx = (uint32_t*)c->mx[GW_IDX];
-    a.c_len = (uint32_t*)c->mx[GW_LEN]; a.c_a = c->mx[GW_A]; a.c_pvoff = (uint64_t*)c->mx[GW_PVOFF]; a.c_pvlen = (uint32_t*)c->mx[GW_PVLEN];
+    a.cnt = c->mx[GW_CNT].as<uint32_t>(); a.totals = c->mx[GW_TOT].as<uint32_t>(); a.pos = c->mx[GW_POS].as<uint32_t>(); a.idx = c->mx[GW_IDX].as<uint32_t>();
+    a.c_len = c->mx[GW_LEN].as<uint32_t>(); a.c_a = c->mx[GW_A]; a.c_pvoff = c->mx[GW_PVOFF].as<uint64_t>(); a.c_pvlen = c->mx[GW_PVLEN].as<uint32_t>();
     a.status = d_status; a.recv = d_recv;
     if (K) HIP_TRY(hipMemsetAsync(a.idx, 0xFF, 4 * ns, s));      // pad slots: GW_NONE
     launch_gateway_count(a, s);
@@ -2065,7 +2024,7 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
     route_layout(tot, (uint32_t)R, (uint32_t)key0, (uint32_t)K, a.rec, K ? miller_lanes(c->gw_group, placed) : 0, K && c->gw_group->lanes != 0, &L);
     for (size_t r = 0; r < R; r++) { a.start[r] = L.start[r]; a.base[r] = L.base[r]; }
     if (routed + tot[GW_COL_NOT_FOUND] + tot[GW_COL_SHORT] + tot[GW_COL_BAD] != n || L.slots > ns) return ZKV_ERR_HIP;
-    if ((rc = grow(&c->mx[GW_RECS], &c->mx_cap[GW_RECS], (size_t)L.bytes + 8)) != ZKV_OK) return rc;
+    if ((rc = c->mx[GW_RECS].grow((size_t)L.bytes + 8)) != ZKV_OK) return rc;
     a.c_proofs = c->mx[GW_RECS];
     for (size_t r = 0; r < R; r++) { c->gw_counts[r] = tot[r]; c->gw_ran[r] = tot[r] > 0; }
     for (size_t r = R; r < GW_MAX_ROUTES; r++) c->gw_counts[r] = 0;
@@ -2084,7 +2043,7 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
         zkv_ctx* g = c->gw_group;
         GwsetChunk pc;
         memset(&pc, 0, sizeof pc);
-        pc.idx = a.idx + G0; pc.skey = (uint32_t*)c->mx[GW_SKEY];
+        pc.idx = a.idx + G0; pc.skey = c->mx[GW_SKEY].as<uint32_t>();
         pc.recs = a.c_proofs + L.b0; pc.len = a.c_len + G0; pc.vkeys = a.c_a + 32 * G0; pc.pvoff = a.c_pvoff + G0; pc.pvlen = a.c_pvlen + G0; pc.pv = d_pv;
         pc.n_keys = (uint32_t)K;
         for (size_t k = 0; k < K; k++) pc.start[k] = (uint32_t)L.gstart[k];
@@ -2121,8 +2080,8 @@ ZKV_EXPORT int zkv_sp1_gateway_verify_batch(zkv_ctx* c, size_t n, const uint8_t*
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_device_init(c);
     if (rc != ZKV_OK) return rc;
-    if ((rc = grow(&c->mx[GW_H_VK], &c->mx_cap[GW_H_VK], 32 * n)) != ZKV_OK || (rc = grow(&c->mx[GW_H_ST], &c->mx_cap[GW_H_ST], n)) != ZKV_OK ||
-        (rc = grow(&c->mx[GW_H_RV], &c->mx_cap[GW_H_RV], 4 * n)) != ZKV_OK) return rc;
+    if ((rc = c->mx[GW_H_VK].grow(32 * n)) != ZKV_OK || (rc = c->mx[GW_H_ST].grow(n)) != ZKV_OK ||
+        (rc = c->mx[GW_H_RV].grow(4 * n)) != ZKV_OK) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     std::vector<uint64_t> so, vo;
@@ -2130,8 +2089,8 @@ ZKV_EXPORT int zkv_sp1_gateway_verify_batch(zkv_ctx* c, size_t n, const uint8_t*
     HIP_TRY(hipMemcpyAsync(c->mx[GW_H_VK], vkeys, 32 * n, hipMemcpyHostToDevice, s));
     if ((rc = stage_ragged(c, GW_H_PV, GW_H_PVOFF, pv_blob, pv_off, n, &vo, s, &vbytes)) != ZKV_OK ||
         (rc = stage_ragged(c, GW_H_PROOF, GW_H_POFF, proof_blob, proof_off, n, &so, s, &sbytes)) != ZKV_OK) return rc;
-    if ((rc = run_gateway(c, n, c->mx[GW_H_VK], c->mx[GW_H_PROOF], (const uint64_t*)c->mx[GW_H_POFF], sbytes, c->mx[GW_H_PV],
-                          (const uint64_t*)c->mx[GW_H_PVOFF], 0, c->mx[GW_H_ST], c->mx[GW_H_RV], s)) != ZKV_OK) return rc;
+    if ((rc = run_gateway(c, n, c->mx[GW_H_VK], c->mx[GW_H_PROOF], c->mx[GW_H_POFF].as<const uint64_t>(), sbytes, c->mx[GW_H_PV],
+                          c->mx[GW_H_PVOFF].as<const uint64_t>(), 0, c->mx[GW_H_ST], c->mx[GW_H_RV], s)) != ZKV_OK) return rc;
     return return_to_host(c, GW_H_ST, GW_H_RV, n, status, recv, s);
 }
 ZKV_EXPORT int zkv_sp1_gateway_last_route_counts(zkv_ctx* c, uint64_t* out) {
@@ -2231,7 +2190,7 @@ enum { RZ_CNT = 0, RZ_TOT, RZ_ITOT, RZ_POS, RZ_IDX, RZ_RECS, RZ_LEN, RZ_A, RZ_B,
        RZ_KIND, RZ_H_METHOD,                    // per-seal methods: the compact row and the host call's staging
        RZW_SEALS, RZW_LEN, RZW_CK,              // calldata batches: the decoded slots, true lengths and call kinds (inputs and methods: RZ_H_A, RZ_H_B, RZ_H_METHOD)
        RZ_BUFS };
-static_assert(RZ_BUFS <= sizeof(((zkv_ctx*)nullptr)->mx) / sizeof(uint8_t*), "the router's buffers live in zkv_ctx::mx");
+static_assert(RZ_BUFS <= CtxDevice::MX_SLOTS, "the router's buffers live in zkv_ctx::mx");
 // The built-in group: m compact records from the front end through the verifier set's pipeline (run_set_batch's chunks, with the true
 // lengths and the instance row on the device).  kind: the method row, or nullptr: one method, in_b == nullptr being verify_integrity.
 static int run_router_builtin(zkv_ctx* c, size_t m_total, const uint8_t* seals, const uint32_t* len, const uint32_t* inst, const uint8_t* in_a,
@@ -2268,11 +2227,11 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
     const size_t ns = n + 32 * K;
     const size_t need[RZ_ROUTES] = {4 * GW_COLS * blocks, 4 * GW_COLS, 4 * (RZR_BAD_WORD + 1), 4 * n, 4 * ns, (size_t)ZKV_SEAL_BYTES * ns + 8, 4 * ns,
                                     32 * ns, 32 * ns, 4 * ns, ns, 4 * ns, 4 * ns};
-    for (int k = 0; k < RZ_ROUTES; k++) if ((rc = grow(&c->mx[k], &c->mx_cap[k], need[k])) != ZKV_OK) return rc;
-    if (d_method && (rc = grow(&c->mx[RZ_KIND], &c->mx_cap[RZ_KIND], ns)) != ZKV_OK) return rc;
+    for (int k = 0; k < RZ_ROUTES; k++) if ((rc = c->mx[k].grow(need[k])) != ZKV_OK) return rc;
+    if (d_method && (rc = c->mx[RZ_KIND].grow(ns)) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     if (K && !c->mx[RZ_ROUTES]) {                                  // the keyed routes' constants, once
-        if ((rc = grow(&c->mx[RZ_ROUTES], &c->mx_cap[RZ_ROUTES], sizeof(RzrRoute) * K)) != ZKV_OK) return rc;
+        if ((rc = c->mx[RZ_ROUTES].grow(sizeof(RzrRoute) * K)) != ZKV_OK) return rc;
         HIP_TRY(hipMemcpy(c->mx[RZ_ROUTES], c->rz_routes.data(), sizeof(RzrRoute) * K, hipMemcpyHostToDevice));
     }
     RzrArgs a;
@@ -2281,9 +2240,9 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
     a.method = d_method; a.wire_len = d_wire_len; a.c_kind = d_method ? c->mx[RZ_KIND] : nullptr;
     a.n_builtin = (uint32_t)NB; a.n_keyed = (uint32_t)K;
     for (size_t r = 0; r < R; r++) a.sel[r] = c->gw_sel[r];
-    a.cnt = (uint32_t*)c->mx[RZ_CNT]; a.totals = (uint32_t*)c->mx[RZ_TOT]; a.inst_tot = (uint32_t*)c->mx[RZ_ITOT];
-    a.pos = (uint32_t*)c->mx[RZ_POS]; a.idx = (uint32_t*)c->mx[RZ_IDX];
-    a.c_seals = c->mx[RZ_RECS]; a.c_len = (uint32_t*)c->mx[RZ_LEN]; a.c_a = c->mx[RZ_A]; a.c_b = c->mx[RZ_B]; a.c_inst = (uint32_t*)c->mx[RZ_INST];
+    a.cnt = c->mx[RZ_CNT].as<uint32_t>(); a.totals = c->mx[RZ_TOT].as<uint32_t>(); a.inst_tot = c->mx[RZ_ITOT].as<uint32_t>();
+    a.pos = c->mx[RZ_POS].as<uint32_t>(); a.idx = c->mx[RZ_IDX].as<uint32_t>();
+    a.c_seals = c->mx[RZ_RECS]; a.c_len = c->mx[RZ_LEN].as<uint32_t>(); a.c_a = c->mx[RZ_A]; a.c_b = c->mx[RZ_B]; a.c_inst = c->mx[RZ_INST].as<uint32_t>();
     a.status = d_status; a.recv = d_recv;
     HIP_TRY(hipMemsetAsync(a.inst_tot, 0, 4 * (RZR_BAD_WORD + 1), s));
     if (K) HIP_TRY(hipMemsetAsync(a.idx, 0xFF, 4 * ns, s));       // pad slots: GW_NONE
@@ -2320,12 +2279,12 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
         zkv_ctx* g = c->gw_group;
         RzrChunk pc;
         memset(&pc, 0, sizeof pc);
-        pc.idx = a.idx + G0; pc.skey = (uint32_t*)c->mx[RZ_SKEY];
+        pc.idx = a.idx + G0; pc.skey = c->mx[RZ_SKEY].as<uint32_t>();
         pc.recs = a.c_seals + L.b0; pc.len = a.c_len + G0; pc.in_a = a.c_a + 32 * G0; pc.in_b = a.in_b ? a.c_b + 32 * G0 : nullptr;
         pc.kind = a.c_kind ? a.c_kind + G0 : nullptr;
         pc.n_keys = (uint32_t)K;
         for (size_t k = 0; k < K; k++) pc.start[k] = (uint32_t)L.gstart[k];
-        pc.routes = (const RzrRoute*)c->mx[RZ_ROUTES];
+        pc.routes = c->mx[RZ_ROUTES].as<const RzrRoute>();
         pc.status = st + G0; pc.recv = (uint32_t*)(rv + 4 * G0);
         if ((rc = run_keyed_group(g, (size_t)L.m, L.lanes, pc.idx, pc.skey, pc.status, s, [&](const GsetChunk& ch) {
                 keyed_prep_chunk(&pc, ch);
@@ -2361,8 +2320,8 @@ static int router_host_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, con
     int rc = ctx_device_init(c);
     if (rc != ZKV_OK) return rc;
     const size_t need[4] = {32 * n, 32 * n, n, 4 * n};
-    for (int k = 0; k < 4; k++) if ((rc = grow(&c->mx[RZ_H_A + k], &c->mx_cap[RZ_H_A + k], need[k])) != ZKV_OK) return rc;
-    if (method && (rc = grow(&c->mx[RZ_H_METHOD], &c->mx_cap[RZ_H_METHOD], n)) != ZKV_OK) return rc;
+    for (int k = 0; k < 4; k++) if ((rc = c->mx[RZ_H_A + k].grow(need[k])) != ZKV_OK) return rc;
+    if (method && (rc = c->mx[RZ_H_METHOD].grow(n)) != ZKV_OK) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     std::vector<uint64_t> so;
@@ -2371,7 +2330,7 @@ static int router_host_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, con
     HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
     if (in_b) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_B], in_b, 32 * n, hipMemcpyHostToDevice, s));
     if (method) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_METHOD], method, n, hipMemcpyHostToDevice, s));
-    if ((rc = run_router(c, n, c->mx[RZ_H_SEALS], (const uint64_t*)c->mx[RZ_H_OFF], sbytes, c->mx[RZ_H_A], in_b ? c->mx[RZ_H_B] : nullptr,
+    if ((rc = run_router(c, n, c->mx[RZ_H_SEALS], c->mx[RZ_H_OFF].as<const uint64_t>(), sbytes, c->mx[RZ_H_A], in_b ? c->mx[RZ_H_B] : nullptr,
                          c->mx[RZ_H_ST], c->mx[RZ_H_RV], s, method ? c->mx[RZ_H_METHOD] : nullptr)) != ZKV_OK) return rc;
     return return_to_host(c, RZ_H_ST, RZ_H_RV, n, status, recv, s);
 }
@@ -2503,8 +2462,8 @@ static void host_method(const zkv_ctx* c, const uint8_t* cd, size_t len, uint8_t
 static int enqueue_wire_chunk(zkv_ctx* c, size_t m, const uint8_t* d_cd, const uint64_t* d_cdoff, uint64_t cd_bytes, uint8_t* d_status, uint8_t* d_recv,
                               hipStream_t s, bool timed, hipEvent_t decoded = nullptr) {
     int rc;
-    if ((rc = grow(&c->d_blob, &c->blob_cap, m * ZKV_SEAL_BYTES + 8)) != ZKV_OK) return rc;
-    if (c->vm == ZKV_VM_SP1 && (rc = grow(&c->d_pv, &c->pv_cap, (size_t)(cd_bytes / 32) + 64)) != ZKV_OK) return rc;
+    if ((rc = c->d_blob.grow(m * ZKV_SEAL_BYTES + 8)) != ZKV_OK) return rc;
+    if (c->vm == ZKV_VM_SP1 && (rc = c->d_pv.grow((size_t)(cd_bytes / 32) + 64)) != ZKV_OK) return rc;
     const host::Selectors& S = host::selectors();
     WireArgs w;
     memset(&w, 0, sizeof w);
@@ -2538,7 +2497,6 @@ static int enqueue_wire_chunk(zkv_ctx* c, size_t m, const uint8_t* d_cd, const u
     enqueue_chunk(c, a, s, timed);
     return ZKV_OK;
 }
-static int wire_buffers(zkv_ctx*) { return ZKV_OK; }          // the copy stream and its events are created with the context
 
 // Host calldata: 8-12 KB per proof cross PCIe, as much time as the verification itself.  Chunks of at most 2^16 requests
 // (enough lanes to fill the chip) are double-buffered: the H2D copy of chunk k+1 runs on its own stream while chunk k is
@@ -2557,10 +2515,9 @@ static int run_eth_call_batch(zkv_ctx* c, size_t n, const uint8_t* blob, const u
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_ready(c, n);
     if (rc != ZKV_OK) return rc;
-    if ((rc = wire_buffers(c)) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
     const size_t chunk = wire_host_chunk(c->ws.cap);
-    if ((rc = grow(&c->d_st_all, &c->st_all_cap, n)) != ZKV_OK || (rc = grow(&c->d_rv_all, &c->rv_all_cap, 4 * n)) != ZKV_OK) return rc;
+    if ((rc = c->d_st_all.grow(n)) != ZKV_OK || (rc = c->d_rv_all.grow(4 * n)) != ZKV_OK) return rc;
     uint64_t max_bytes = 0;
     for (size_t base = 0; base < n; base += chunk) {
         size_t m = n - base < chunk ? n - base : chunk;
@@ -2569,9 +2526,9 @@ static int run_eth_call_batch(zkv_ctx* c, size_t n, const uint8_t* blob, const u
     }
     // all device buffers are sized before the loop: growing one frees it, which synchronises the device
     for (int b = 0; b < 2; b++)
-        if ((n > chunk || b == 0) && (rc = grow(&c->d_cd[b], &c->cd_cap[b], (size_t)max_bytes + 8)) != ZKV_OK) return rc;
-    if ((rc = grow(&c->d_blob, &c->blob_cap, chunk * ZKV_SEAL_BYTES + 8)) != ZKV_OK) return rc;
-    if (c->vm == ZKV_VM_SP1 && (rc = grow(&c->d_pv, &c->pv_cap, (size_t)(max_bytes / 32) + 64)) != ZKV_OK) return rc;
+        if ((n > chunk || b == 0) && (rc = c->d_cd[b].grow((size_t)max_bytes + 8)) != ZKV_OK) return rc;
+    if ((rc = c->d_blob.grow(chunk * ZKV_SEAL_BYTES + 8)) != ZKV_OK) return rc;
+    if (c->vm == ZKV_VM_SP1 && (rc = c->d_pv.grow((size_t)(max_bytes / 32) + 64)) != ZKV_OK) return rc;
     std::vector<uint64_t> rel[2];
     size_t k = 0;
     for (size_t base = 0; base < n; base += chunk, k++) {
@@ -2633,7 +2590,6 @@ ZKV_EXPORT int zkv_eth_call_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_cal
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_ready(c, n);
     if (rc != ZKV_OK) return rc;
-    if ((rc = wire_buffers(c)) != ZKV_OK) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const size_t cap = c->ws.cap;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
@@ -2704,14 +2660,14 @@ ZKV_EXPORT int zkv_sp1_gateway_eth_call_returndata(const zkv_ctx* c, uint8_t sta
 static int run_gateway_wire(zkv_ctx* c, size_t n, const uint8_t* d_cd, const uint64_t* d_off, uint64_t cd_bytes, uint8_t* d_status, uint8_t* d_recv, hipStream_t s) {
     int rc;
     const size_t need[7] = {32 * n, 8 * n, 4 * n, 8 * n, 4 * n, n, (size_t)(cd_bytes / 32) + 64};
-    for (int k = 0; k < 7; k++) if ((rc = grow(&c->mx[GWW_VK + k], &c->mx_cap[GWW_VK + k], need[k])) != ZKV_OK) return rc;
+    for (int k = 0; k < 7; k++) if ((rc = c->mx[GWW_VK + k].grow(need[k])) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     GwWireArgs w;
     memset(&w, 0, sizeof w);
     w.n = n; w.cd = d_cd; w.off = d_off; w.cd_bytes = cd_bytes;
     w.sel_u_be = be32_of(host::selectors().sp1[host::SP1_VERIFY_PROOF]); w.sel_b_be = be32_of(gateway_bytes_selector());
     w.arena = c->mx[GWW_ARENA]; w.vkeys = c->mx[GWW_VK];
-    w.pv_at = (uint64_t*)c->mx[GWW_PVAT]; w.pv_len = (uint32_t*)c->mx[GWW_PVLEN]; w.proof_at = (uint64_t*)c->mx[GWW_PAT]; w.proof_len = (uint32_t*)c->mx[GWW_PLEN];
+    w.pv_at = c->mx[GWW_PVAT].as<uint64_t>(); w.pv_len = c->mx[GWW_PVLEN].as<uint32_t>(); w.proof_at = c->mx[GWW_PAT].as<uint64_t>(); w.proof_len = c->mx[GWW_PLEN].as<uint32_t>();
     w.bad = c->mx[GWW_BAD];
     // one base address for the records: the lower of the two buffers, so that every start is a plain non-negative distance
     const uintptr_t pc = (uintptr_t)d_cd, pa = (uintptr_t)w.arena, base = pc < pa ? pc : pa;
@@ -2748,7 +2704,7 @@ ZKV_EXPORT int zkv_sp1_gateway_eth_call_batch(zkv_ctx* c, size_t n, const uint8_
         const uint64_t b0 = off[0], bytes = off[n] - b0;
         const size_t need[4] = {(size_t)bytes + 8, 8 * (n + 1), n, 4 * n};
         const int slot[4] = {GWW_H_CD, GWW_H_OFF, GW_H_ST, GW_H_RV};
-        for (int k = 0; k < 4; k++) if ((rc = grow(&c->mx[slot[k]], &c->mx_cap[slot[k]], need[k])) != ZKV_OK) return rc;
+        for (int k = 0; k < 4; k++) if ((rc = c->mx[slot[k]].grow(need[k])) != ZKV_OK) return rc;
         hipStream_t s = c->stream;
         if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
         std::vector<uint64_t> rel(off, off + n + 1);
@@ -2756,7 +2712,7 @@ ZKV_EXPORT int zkv_sp1_gateway_eth_call_batch(zkv_ctx* c, size_t n, const uint8_
         if (bytes) HIP_TRY(hipMemcpyAsync(c->mx[GWW_H_CD], blob + b0, (size_t)bytes, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(c->mx[GWW_H_OFF], rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));                        // `rel` is a pageable host buffer
-        if ((rc = run_gateway_wire(c, n, c->mx[GWW_H_CD], (const uint64_t*)c->mx[GWW_H_OFF], bytes, c->mx[GW_H_ST], c->mx[GW_H_RV], s)) != ZKV_OK) return rc;
+        if ((rc = run_gateway_wire(c, n, c->mx[GWW_H_CD], c->mx[GWW_H_OFF].as<const uint64_t>(), bytes, c->mx[GW_H_ST], c->mx[GW_H_RV], s)) != ZKV_OK) return rc;
         HIP_TRY(hipMemcpyAsync(st.data(), c->mx[GW_H_ST], n, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(rv.data(), c->mx[GW_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -2858,13 +2814,13 @@ static int run_router_wire(zkv_ctx* c, size_t n, const uint8_t* d_cd, const uint
     int rc;
     const int slot[5] = {RZW_SEALS, RZW_LEN, RZ_H_A, RZ_H_B, RZ_H_METHOD};
     const size_t need[5] = {(size_t)ZKV_SEAL_BYTES * n + 8, 4 * n, 32 * n, 32 * n, n};
-    for (int k = 0; k < 5; k++) if ((rc = grow(&c->mx[slot[k]], &c->mx_cap[slot[k]], need[k])) != ZKV_OK) return rc;
+    for (int k = 0; k < 5; k++) if ((rc = c->mx[slot[k]].grow(need[k])) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     RzWireArgs w;
     memset(&w, 0, sizeof w);
     w.n = n; w.cd = d_cd; w.off = d_off; w.cd_bytes = cd_bytes;
     for (int k = 0; k < RZW_KINDS; k++) w.sel_be[k] = be32_of(router_call_selector(k));
-    w.seals = c->mx[RZW_SEALS]; w.seal_len = (uint32_t*)c->mx[RZW_LEN]; w.in_a = c->mx[RZ_H_A]; w.in_b = c->mx[RZ_H_B]; w.method = c->mx[RZ_H_METHOD];
+    w.seals = c->mx[RZW_SEALS]; w.seal_len = c->mx[RZW_LEN].as<uint32_t>(); w.in_a = c->mx[RZ_H_A]; w.in_b = c->mx[RZ_H_B]; w.method = c->mx[RZ_H_METHOD];
     w.call_kind = d_ck;
     (void)hipEventRecord(c->ev_wire[0], s);
     launch_wire_rzrouter(w, s);
@@ -2897,13 +2853,13 @@ ZKV_EXPORT int zkv_risc0_router_eth_call_batch(zkv_ctx* c, size_t n, const uint8
         if (rc != ZKV_OK) return rc;
         const size_t need[3] = {n, 4 * n, n};
         const int slot[3] = {RZ_H_ST, RZ_H_RV, RZW_CK};
-        for (int k = 0; k < 3; k++) if ((rc = grow(&c->mx[slot[k]], &c->mx_cap[slot[k]], need[k])) != ZKV_OK) return rc;
+        for (int k = 0; k < 3; k++) if ((rc = c->mx[slot[k]].grow(need[k])) != ZKV_OK) return rc;
         hipStream_t s = c->stream;
         if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
         std::vector<uint64_t> rel;
         uint64_t bytes = 0;
         if ((rc = stage_ragged(c, RZ_H_SEALS, RZ_H_OFF, blob, off, n, &rel, s, &bytes)) != ZKV_OK) return rc;
-        if ((rc = run_router_wire(c, n, c->mx[RZ_H_SEALS], (const uint64_t*)c->mx[RZ_H_OFF], bytes, c->mx[RZ_H_ST], c->mx[RZ_H_RV], c->mx[RZW_CK], s)) != ZKV_OK)
+        if ((rc = run_router_wire(c, n, c->mx[RZ_H_SEALS], c->mx[RZ_H_OFF].as<const uint64_t>(), bytes, c->mx[RZ_H_ST], c->mx[RZ_H_RV], c->mx[RZW_CK], s)) != ZKV_OK)
             return rc;
         HIP_TRY(hipMemcpyAsync(st.data(), c->mx[RZ_H_ST], n, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(rv.data(), c->mx[RZ_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
@@ -2950,8 +2906,8 @@ static int run_precompile(zkv_ctx* c, int kind, size_t n, size_t k, const uint8_
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
     for (size_t base = 0; base < n; base += cap) {
         size_t m = n - base < cap ? n - base : cap;
-        if ((rc = grow(&c->d_blob, &c->blob_cap, m * in_sz + 8)) != ZKV_OK) return rc;
-        if ((rc = grow(&c->d_pv, &c->pv_cap, m * out_sz + 8)) != ZKV_OK) return rc;
+        if ((rc = c->d_blob.grow(m * in_sz + 8)) != ZKV_OK) return rc;
+        if ((rc = c->d_pv.grow(m * out_sz + 8)) != ZKV_OK) return rc;
         if (in_sz) HIP_TRY(hipMemcpyAsync(c->d_blob, in + base * in_sz, m * in_sz, hipMemcpyHostToDevice, c->stream));
         if (kind == 0) launch_ecadd(m, c->d_blob, c->d_pv, c->d_status, c->stream);
         else if (kind == 1) launch_ecmul(m, c->d_blob, c->d_pv, c->d_status, c->stream);
@@ -3015,12 +2971,7 @@ static int groth16_ready(zkv_ctx* c, size_t n, size_t* chunk) {
     int rc = ctx_ready(c, n < lc ? n : lc);
     if (rc != ZKV_OK) return rc;
     const size_t need = c->ws.cap < lc ? c->ws.cap : lc;
-    if (c->lsig_cap < need) {
-        if (c->d_lsig) (void)hipFree(c->d_lsig);
-        c->d_lsig = nullptr; c->lsig_cap = 0;
-        if (hipMalloc(&c->d_lsig, (size_t)32 * (c->g_n_ic - 1) * need) != hipSuccess) { (void)hipGetLastError(); return ZKV_ERR_OOM; }
-        c->lsig_cap = need;
-    }
+    if (lsig_stride(c) < need && (rc = c->d_lsig.alloc((size_t)32 * (c->g_n_ic - 1) * need)) != ZKV_OK) return rc;
     *chunk = need;
     return ZKV_OK;
 }
@@ -3051,8 +3002,8 @@ ZKV_EXPORT int zkv_groth16_verify_batch(zkv_ctx* c, size_t n, const uint8_t* pro
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
     for (size_t base = 0; base < n; base += cap) {
         size_t m = n - base < cap ? n - base : cap;
-        if ((rc = grow(&c->d_blob, &c->blob_cap, m * 256 + 8)) != ZKV_OK) return rc;
-        if ((rc = grow(&c->d_pv, &c->pv_cap, m * 32 * n_sig + 8)) != ZKV_OK) return rc;
+        if ((rc = c->d_blob.grow(m * 256 + 8)) != ZKV_OK) return rc;
+        if ((rc = c->d_pv.grow(m * 32 * n_sig + 8)) != ZKV_OK) return rc;
         HIP_TRY(hipMemcpyAsync(c->d_blob, proofs + 256 * base, 256 * m, hipMemcpyHostToDevice, c->stream));
         if (n_sig) HIP_TRY(hipMemcpyAsync(c->d_pv, signals + (size_t)32 * n_sig * base, (size_t)32 * n_sig * m, hipMemcpyHostToDevice, c->stream));
         PrepArgs a;
@@ -3179,8 +3130,8 @@ ZKV_EXPORT int zkv_plonk_verify_batch(zkv_ctx* c, size_t n, const uint8_t* proof
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
     for (size_t base = 0; base < n; base += cap) {
         const size_t m = n - base < cap ? n - base : cap;
-        if ((rc = grow(&c->d_blob, &c->blob_cap, m * pb + 8)) != ZKV_OK) return rc;
-        if ((rc = grow(&c->d_pv, &c->pv_cap, m * pin + 8)) != ZKV_OK) return rc;
+        if ((rc = c->d_blob.grow(m * pb + 8)) != ZKV_OK) return rc;
+        if ((rc = c->d_pv.grow(m * pin + 8)) != ZKV_OK) return rc;
         HIP_TRY(hipMemcpyAsync(c->d_blob, proofs + pb * base, pb * m, hipMemcpyHostToDevice, c->stream));
         if (pin) HIP_TRY(hipMemcpyAsync(c->d_pv, public_inputs + pin * base, pin * m, hipMemcpyHostToDevice, c->stream));
         const PrepArgs a = plonk_args(c, m, c->d_blob, c->d_pv, c->d_status);
@@ -3240,28 +3191,29 @@ static int gset_device_setup(zkv_ctx* c) {
         }
         S += n_sig;
     }
-    HIP_TRY(hipMalloc(&c->d_gs_tab, sizeof(VkTables) * K));
+    HIP_TRY(c->d_gs_tab.alloc(sizeof(VkTables) * K));
     HIP_TRY(hipMemsetAsync(c->d_gs_tab, 0, sizeof(VkTables) * K, c->stream));
     for (uint32_t k = 0; k < K; k++) keys[k].tab = c->d_gs_tab + k;
-    HIP_TRY(hipMalloc(&c->d_gs_key, sizeof(GsetKey) * K));
+    HIP_TRY(c->d_gs_key.alloc(sizeof(GsetKey) * K));
     HIP_TRY(hipMemcpyAsync(c->d_gs_key, keys.data(), sizeof(GsetKey) * K, hipMemcpyHostToDevice, c->stream));
-    // the raw keys and points are only read by the set-up kernels: mx[0..2] until those are done
-    HIP_TRY(hipMalloc(&c->mx[0], sizeof(VkRaw) * K));
-    HIP_TRY(hipMemcpyAsync(c->mx[0], raw.data(), sizeof(VkRaw) * K, hipMemcpyHostToDevice, c->stream));
+    // the raw keys and points are only read by the set-up kernels: scoped, released after the synchronisation below
+    DevBuf<VkRaw> d_raw;
+    DevBuf<uint32_t> d_ic, d_sig_key;
+    HIP_TRY(d_raw.alloc(sizeof(VkRaw) * K));
+    HIP_TRY(hipMemcpyAsync(d_raw, raw.data(), sizeof(VkRaw) * K, hipMemcpyHostToDevice, c->stream));
     if (S) {
         const size_t tab_bytes = (size_t)S * LONG_ROW_ENTRIES * sizeof(G1A);
-        HIP_TRY(hipMalloc(&c->d_gs_rows, tab_bytes));
-        HIP_TRY(hipMalloc(&c->d_gs_win, sizeof(uint32_t) * S));
+        HIP_TRY(c->d_gs_rows.alloc(tab_bytes));
+        HIP_TRY(c->d_gs_win.alloc(sizeof(uint32_t) * S));
         HIP_TRY(hipMemsetAsync(c->d_gs_rows, 0, tab_bytes, c->stream));
-        HIP_TRY(hipMalloc(&c->mx[1], sizeof(uint32_t) * ic.size()));
-        HIP_TRY(hipMalloc(&c->mx[2], sizeof(uint32_t) * S));
-        HIP_TRY(hipMemcpyAsync(c->mx[1], ic.data(), sizeof(uint32_t) * ic.size(), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->mx[2], sig_key.data(), sizeof(uint32_t) * S, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(d_ic.alloc(sizeof(uint32_t) * ic.size()));
+        HIP_TRY(d_sig_key.alloc(sizeof(uint32_t) * S));
+        HIP_TRY(hipMemcpyAsync(d_ic, ic.data(), sizeof(uint32_t) * ic.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_sig_key, sig_key.data(), sizeof(uint32_t) * S, hipMemcpyHostToDevice, c->stream));
     }
-    launch_gset_setup(K, (const VkRaw*)c->mx[0], c->d_gs_tab, S, (const uint32_t*)c->mx[1], (const uint32_t*)c->mx[2], c->d_gs_rows, c->d_gs_win, c->stream);
+    launch_gset_setup(K, d_raw, c->d_gs_tab, S, d_ic, d_sig_key, c->d_gs_rows, c->d_gs_win, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));                // the host vectors above go out of scope
-    for (int k = 0; k < 3; k++) { if (c->mx[k]) (void)hipFree(c->mx[k]); c->mx[k] = nullptr; }
     return ZKV_OK;
 }
 ZKV_EXPORT zkv_ctx* zkv_groth16_set_create(size_t n_keys, const uint8_t* const* vk_words, const size_t* n_ic, const int* vm_type, int device) {
@@ -3302,14 +3254,12 @@ static bool gset_agg_tables(zkv_ctx* c) {
     const uint32_t K = (uint32_t)c->gs_nic.size();
     std::vector<VkRaw> raw(K);
     for (uint32_t k = 0; k < K; k++) host::fill_vk_generic(raw[k], c->gvk.data() + c->gs_off[k], 1u);
-    VkRaw* d_raw = nullptr;
-    if (hipMalloc(&c->d_agg_tab, sizeof(AggTables) * K) != hipSuccess || hipMalloc(&d_raw, sizeof(VkRaw) * K) != hipSuccess ||
-        (!c->d_agg_cnt && (hipMalloc(&c->d_agg_cnt, 3 * sizeof(unsigned long long)) != hipSuccess ||
+    DevBuf<VkRaw> d_raw;
+    if (c->d_agg_tab.alloc(sizeof(AggTables) * K) || d_raw.alloc(sizeof(VkRaw) * K) ||
+        (!c->d_agg_cnt && (c->d_agg_cnt.alloc(3 * sizeof(unsigned long long)) ||
                            hipMemset(c->d_agg_cnt, 0, 3 * sizeof(unsigned long long)) != hipSuccess))) {
         (void)hipGetLastError();
-        if (c->d_agg_tab) (void)hipFree(c->d_agg_tab);
-        if (d_raw) (void)hipFree(d_raw);
-        c->d_agg_tab = nullptr;
+        c->d_agg_tab.release();
         return false;
     }
     std::vector<uint32_t> ok(K);
@@ -3321,8 +3271,7 @@ static bool gset_agg_tables(zkv_ctx* c) {
             good = hipMemcpyAsync(&ok[k], &c->d_agg_tab[k].ok, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) == hipSuccess;
         good = good && hipStreamSynchronize(c->stream) == hipSuccess;
     }
-    (void)hipFree(d_raw);
-    if (!good) { (void)hipGetLastError(); (void)hipFree(c->d_agg_tab); c->d_agg_tab = nullptr; return false; }
+    if (!good) { (void)hipGetLastError(); c->d_agg_tab.release(); return false; }
     c->gs_agg_ok.assign(K, 0);
     c->agg_key_ok = false;
     for (uint32_t k = 0; k < K; k++) { c->gs_agg_ok[k] = ok[k] ? 1 : 0; c->agg_key_ok = c->agg_key_ok || ok[k]; }
@@ -3331,6 +3280,9 @@ static bool gset_agg_tables(zkv_ctx* c) {
 // ---- The steps of a call that both kinds of key set take (run_gset, run_pset: each keeps its own layout choice, placement and stages).
 // Partition: the proofs counted per key, block by block; the per-key totals come back to the host (gs_totals: the call's one
 // synchronisation) and *placed is their sum.
+// mx[] slots of a key-set call (0 .. 2 are not used): per-block counts, per-key totals, block offsets, every proof's position, the keys' slot
+// starts (behind the aggregate layout's map when there is one), the proof and key of every slot, the aggregate chunks' pseudo-proof maps
+enum { KS_CNT = 3, KS_TOT, KS_OFF, KS_POS, KS_START, KS_IDX, KS_SKEY, KS_AMAP };
 static int set_partition(zkv_ctx* c, size_t n, uint32_t K, const uint32_t* d_key, hipStream_t s, GsetPart* p, size_t* placed) {
     memset(p, 0, sizeof *p);
     p->n = n; p->n_keys = K;
@@ -3339,10 +3291,10 @@ static int set_partition(zkv_ctx* c, size_t n, uint32_t K, const uint32_t* d_key
     p->per_block = (uint32_t)per; p->blocks = (uint32_t)((n + per - 1) / per);
     const size_t kb = (size_t)K * p->blocks;
     int rc;
-    if ((rc = grow(&c->mx[3], &c->mx_cap[3], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[4], &c->mx_cap[4], 4 * (size_t)K)) != ZKV_OK ||
-        (rc = grow(&c->mx[5], &c->mx_cap[5], 4 * kb)) != ZKV_OK || (rc = grow(&c->mx[6], &c->mx_cap[6], 4 * n)) != ZKV_OK ||
-        (rc = grow(&c->mx[7], &c->mx_cap[7], 8 * ((size_t)K + 1))) != ZKV_OK) return rc;
-    p->key = d_key; p->cnt = (uint32_t*)c->mx[3]; p->totals = (uint32_t*)c->mx[4]; p->off = (uint32_t*)c->mx[5]; p->pos = (uint32_t*)c->mx[6];
+    if ((rc = c->mx[KS_CNT].grow(4 * kb)) != ZKV_OK || (rc = c->mx[KS_TOT].grow(4 * (size_t)K)) != ZKV_OK ||
+        (rc = c->mx[KS_OFF].grow(4 * kb)) != ZKV_OK || (rc = c->mx[KS_POS].grow(4 * n)) != ZKV_OK ||
+        (rc = c->mx[KS_START].grow(8 * ((size_t)K + 1))) != ZKV_OK) return rc;
+    p->key = d_key; p->cnt = c->mx[KS_CNT].as<uint32_t>(); p->totals = c->mx[KS_TOT].as<uint32_t>(); p->off = c->mx[KS_OFF].as<uint32_t>(); p->pos = c->mx[KS_POS].as<uint32_t>();
     HIP_TRY(hipMemsetAsync(p->totals, 0, 4 * (size_t)K, s));
     launch_gset_count(*p, s);
     HIP_TRY(hipGetLastError());
@@ -3356,16 +3308,16 @@ static int set_partition(zkv_ctx* c, size_t n, uint32_t K, const uint32_t* d_key
 // Slot buffers of a layout of M slots: the proof of every slot, its key and its status byte.
 static int set_slot_buffers(zkv_ctx* c, size_t M, GsetPart* p, hipStream_t s) {
     int rc;
-    if ((rc = grow(&c->mx[8], &c->mx_cap[8], 4 * M + 4)) != ZKV_OK || (rc = grow(&c->mx[9], &c->mx_cap[9], 4 * M + 4)) != ZKV_OK ||
-        (rc = grow(&c->d_st_all, &c->st_all_cap, M + 1)) != ZKV_OK) return rc;
-    p->idx = (uint32_t*)c->mx[8]; p->skey = (uint32_t*)c->mx[9];
+    if ((rc = c->mx[KS_IDX].grow(4 * M + 4)) != ZKV_OK || (rc = c->mx[KS_SKEY].grow(4 * M + 4)) != ZKV_OK ||
+        (rc = c->d_st_all.grow(M + 1)) != ZKV_OK) return rc;
+    p->idx = c->mx[KS_IDX].as<uint32_t>(); p->skey = c->mx[KS_SKEY].as<uint32_t>();
     HIP_TRY(hipMemsetAsync(p->idx, 0xFF, 4 * M + 4, s));     // pad slots: GSET_NONE
     HIP_TRY(hipMemsetAsync(p->skey, 0, 4 * M + 4, s));       // (and key 0: a slot's key is only read for live slots, this keeps any read in the set)
     return ZKV_OK;
 }
 // The aggregate chunks of the aggregate region [0, R), `capa` slots each, and their pseudo-proof maps (zkv_gset_layout.h
 // gset_agg_chunk_plan, whose regions the caller passes on): chunk g's map is in gs_amap from word g.off -- psl (sub-batch -> pseudo slot, n2
-// words), then the key of every pseudo slot (slots words) -- and all of gs_amap goes to mx[10] in one copy.
+// words), then the key of every pseudo slot (slots words) -- and all of gs_amap goes to mx[KS_AMAP] in one copy.
 struct GsetAggChunk { size_t base, m, n2, off; uint64_t slots; int lanes; };
 static int set_agg_plan(zkv_ctx* c, const uint64_t* beg, const uint64_t* end, const uint32_t* rep, uint32_t n_regions, uint64_t R, size_t capa,
                         uint32_t sub, std::vector<GsetAggChunk>* plan, hipStream_t s) {
@@ -3381,9 +3333,9 @@ static int set_agg_plan(zkv_ctx* c, const uint64_t* beg, const uint64_t* end, co
         c->gs_amap.resize(g.off + g.n2 + g.slots);
         plan->push_back(g);
     }
-    const int rc = grow(&c->mx[10], &c->mx_cap[10], 4 * c->gs_amap.size() + 4);
+    const int rc = c->mx[KS_AMAP].grow(4 * c->gs_amap.size() + 4);
     if (rc != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->mx[10], c->gs_amap.data(), 4 * c->gs_amap.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->mx[KS_AMAP], c->gs_amap.data(), 4 * c->gs_amap.size(), hipMemcpyHostToDevice, s));
     return ZKV_OK;
 }
 // The verdicts back to the caller's order (a call that placed no proof still records the six stage events).
@@ -3400,7 +3352,7 @@ static GsetChunk gset_chunk_of(const zkv_ctx* c, const GsetPart& p, const uint8_
     ch.m = m; ch.slot0 = base; ch.idx = p.idx; ch.skey = p.skey;
     ch.keys = c->d_gs_key; ch.rows = c->d_gs_rows; ch.win = c->d_gs_win;
     ch.proofs = d_proofs; ch.signals = d_signals; ch.sig_stride = 32 * (c->g_n_ic - 1);
-    ch.sig = c->d_lsig; ch.sig_cap = c->lsig_cap; ch.status = c->d_st_all + base;
+    ch.sig = c->d_lsig; ch.sig_cap = lsig_stride(c); ch.status = c->d_st_all + base;
     return ch;
 }
 // The aggregate check of one chunk of a set's aggregate region (zkv_agg.h; k_gset_agg.hip): PREP, the coefficients and r A', r C, the
@@ -3468,13 +3420,13 @@ static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
     if ((rc = groth16_ready(c, M ? M : 1, &cap)) != ZKV_OK) return rc;     // (growing frees buffers, which synchronises the device)
     if ((rc = set_slot_buffers(c, M, &p, s)) != ZKV_OK) return rc;
     if (agg) {
-        if ((rc = grow(&c->mx[7], &c->mx_cap[7], 8 * (c->gs_map.size() + K + 1))) != ZKV_OK) return rc;
-        HIP_TRY(hipMemsetAsync(c->mx[7] + 8 * c->gs_map.size(), 0, 8 * ((size_t)K + 1), s));      // zero starts: k_gset_scan gives ranks
-        HIP_TRY(hipMemcpyAsync(c->mx[7], c->gs_map.data(), 8 * c->gs_map.size(), hipMemcpyHostToDevice, s));
-        launch_gset_agg_place(p, (const uint64_t*)c->mx[7] + c->gs_map.size(), (const uint64_t*)c->mx[7], s);
+        if ((rc = c->mx[KS_START].grow(8 * (c->gs_map.size() + K + 1))) != ZKV_OK) return rc;
+        HIP_TRY(hipMemsetAsync(c->mx[KS_START] + 8 * c->gs_map.size(), 0, 8 * ((size_t)K + 1), s));      // zero starts: k_gset_scan gives ranks
+        HIP_TRY(hipMemcpyAsync(c->mx[KS_START], c->gs_map.data(), 8 * c->gs_map.size(), hipMemcpyHostToDevice, s));
+        launch_gset_agg_place(p, c->mx[KS_START].as<const uint64_t>() + c->gs_map.size(), c->mx[KS_START].as<const uint64_t>(), s);
     } else {
-        HIP_TRY(hipMemcpyAsync(c->mx[7], c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
-        launch_gset_place(p, (const uint64_t*)c->mx[7], s);
+        HIP_TRY(hipMemcpyAsync(c->mx[KS_START], c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
+        launch_gset_place(p, c->mx[KS_START].as<const uint64_t>(), s);
     }
     HIP_TRY(hipGetLastError());
     if (agg) {
@@ -3483,7 +3435,7 @@ static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
         std::vector<GsetAggChunk> plan;
         if ((rc = set_agg_plan(c, c->gs_map.data(), c->gs_map.data() + 1, nullptr, K, R, cap / unit * unit, sub, &plan, s)) != ZKV_OK) return rc;
         for (const GsetAggChunk& g : plan) {
-            enqueue_gset_agg(c, gset_chunk_of(c, p, d_proofs, d_signals, g.base, g.m), g, p.skey + g.base, (const uint32_t*)c->mx[10], sub, s,
+            enqueue_gset_agg(c, gset_chunk_of(c, p, d_proofs, d_signals, g.base, g.m), g, p.skey + g.base, c->mx[KS_AMAP].as<const uint32_t>(), sub, s,
                              M == R && g.base + g.m >= R);
             HIP_TRY(hipGetLastError());
         }
@@ -3520,12 +3472,12 @@ ZKV_EXPORT int zkv_groth16_set_verify_batch(zkv_ctx* c, size_t n, const uint32_t
     if (rc != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
     // the whole batch in HBM: keys, proofs, signals (hb[0..2]) and the verdicts (hb[3])
-    if ((rc = grow(&c->hb[0], &c->hb_cap[0], 4 * n)) != ZKV_OK || (rc = grow(&c->hb[1], &c->hb_cap[1], 256 * n)) != ZKV_OK ||
-        (rc = grow(&c->hb[2], &c->hb_cap[2], stride * n + 8)) != ZKV_OK || (rc = grow(&c->hb[3], &c->hb_cap[3], n)) != ZKV_OK) return rc;
+    if ((rc = c->hb[0].grow(4 * n)) != ZKV_OK || (rc = c->hb[1].grow(256 * n)) != ZKV_OK ||
+        (rc = c->hb[2].grow(stride * n + 8)) != ZKV_OK || (rc = c->hb[3].grow(n)) != ZKV_OK) return rc;
     HIP_TRY(hipMemcpyAsync(c->hb[0], key, 4 * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->hb[1], proofs, 256 * n, hipMemcpyHostToDevice, c->stream));
     if (stride) HIP_TRY(hipMemcpyAsync(c->hb[2], signals, stride * n, hipMemcpyHostToDevice, c->stream));
-    if ((rc = run_gset(c, n, (const uint32_t*)c->hb[0], c->hb[1], c->hb[2], c->hb[3], c->stream)) != ZKV_OK) return rc;
+    if ((rc = run_gset(c, n, c->hb[0].as<const uint32_t>(), c->hb[1], c->hb[2], c->hb[3], c->stream)) != ZKV_OK) return rc;
     HIP_TRY(hipMemcpyAsync(verified, c->hb[3], n, hipMemcpyDeviceToHost, c->stream));
     if ((rc = mark_done(c, c->stream)) != ZKV_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3542,11 +3494,11 @@ ZKV_EXPORT int zkv_groth16_set_vk_x_batch(zkv_ctx* c, size_t n, const uint32_t* 
     int rc = groth16_ready(c, n, &cap);
     if (rc != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
-    if ((rc = grow(&c->hb[0], &c->hb_cap[0], 4 * n)) != ZKV_OK || (rc = grow(&c->hb[2], &c->hb_cap[2], stride * n + 8)) != ZKV_OK ||
-        (rc = grow(&c->hb[4], &c->hb_cap[4], 64 * n)) != ZKV_OK) return rc;
+    if ((rc = c->hb[0].grow(4 * n)) != ZKV_OK || (rc = c->hb[2].grow(stride * n + 8)) != ZKV_OK ||
+        (rc = c->hb[4].grow(64 * n)) != ZKV_OK) return rc;
     HIP_TRY(hipMemcpyAsync(c->hb[0], key, 4 * n, hipMemcpyHostToDevice, c->stream));
     if (stride) HIP_TRY(hipMemcpyAsync(c->hb[2], signals, stride * n, hipMemcpyHostToDevice, c->stream));
-    launch_gset_vk_x(n, msm_lanes_long(c, n), (const uint32_t*)c->hb[0], c->d_gs_key, c->d_gs_rows, c->d_gs_win, c->hb[2], (uint32_t)stride, c->hb[4], c->stream);
+    launch_gset_vk_x(n, msm_lanes_long(c, n), c->hb[0].as<const uint32_t>(), c->d_gs_key, c->d_gs_rows, c->d_gs_win, c->hb[2], (uint32_t)stride, c->hb[4], c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, c->hb[4], 64 * n, hipMemcpyDeviceToHost, c->stream));
     if ((rc = mark_done(c, c->stream)) != ZKV_OK) return rc;
@@ -3580,23 +3532,24 @@ static int pset_device_setup(zkv_ctx* c) {
         const int perm[4] = {1, 0, 3, 2};
         for (int q = 0; q < 4; q++) { host::be_to_limbs(raw[k].gamma[q], g2 + 32 * perm[q]); host::be_to_limbs(raw[k].delta[q], g2 + 128 + 32 * perm[q]); }
     }
-    HIP_TRY(hipMalloc(&c->d_gs_tab, sizeof(VkTables) * K));
+    HIP_TRY(c->d_gs_tab.alloc(sizeof(VkTables) * K));
     HIP_TRY(hipMemsetAsync(c->d_gs_tab, 0, sizeof(VkTables) * K, c->stream));
     for (uint32_t k = 0; k < K; k++) keys[k] = GsetKey{c->d_gs_tab + k, 0u, 0u, 0u, 0u};
-    HIP_TRY(hipMalloc(&c->d_gs_key, sizeof(GsetKey) * K));
+    HIP_TRY(c->d_gs_key.alloc(sizeof(GsetKey) * K));
     HIP_TRY(hipMemcpyAsync(c->d_gs_key, keys.data(), sizeof(GsetKey) * K, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMalloc(&c->d_pkey, sizeof(PlonkKey) * K));
-    HIP_TRY(hipMalloc(&c->d_ps_ok, sizeof(uint32_t) * K));
-    // the raw keys are only read by the set-up kernels: mx[0..1] until those are done
-    HIP_TRY(hipMalloc(&c->mx[0], sizeof(VkRaw) * K));
-    HIP_TRY(hipMalloc(&c->mx[1], sizeof(PlonkKeyRaw) * K));
-    HIP_TRY(hipMemcpyAsync(c->mx[0], raw.data(), sizeof(VkRaw) * K, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->mx[1], c->ps_raw.data(), sizeof(PlonkKeyRaw) * K, hipMemcpyHostToDevice, c->stream));
-    launch_gset_setup(K, (const VkRaw*)c->mx[0], c->d_gs_tab, 0, nullptr, nullptr, nullptr, nullptr, c->stream);
-    launch_pset_setup(K, (const PlonkKeyRaw*)c->mx[1], c->d_pkey, c->d_gs_tab, c->d_ps_ok, c->stream);
+    HIP_TRY(c->d_pkey.alloc(sizeof(PlonkKey) * K));
+    HIP_TRY(c->d_ps_ok.alloc(sizeof(uint32_t) * K));
+    // the raw keys are only read by the set-up kernels: scoped, released after the synchronisation below
+    DevBuf<VkRaw> d_raw;
+    DevBuf<PlonkKeyRaw> d_pk;
+    HIP_TRY(d_raw.alloc(sizeof(VkRaw) * K));
+    HIP_TRY(d_pk.alloc(sizeof(PlonkKeyRaw) * K));
+    HIP_TRY(hipMemcpyAsync(d_raw, raw.data(), sizeof(VkRaw) * K, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_pk, c->ps_raw.data(), sizeof(PlonkKeyRaw) * K, hipMemcpyHostToDevice, c->stream));
+    launch_gset_setup(K, d_raw, c->d_gs_tab, 0, nullptr, nullptr, nullptr, nullptr, c->stream);
+    launch_pset_setup(K, d_pk, c->d_pkey, c->d_gs_tab, c->d_ps_ok, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));                // the host vectors above go out of scope
-    for (int k = 0; k < 2; k++) { if (c->mx[k]) (void)hipFree(c->mx[k]); c->mx[k] = nullptr; }
     return ZKV_OK;
 }
 ZKV_EXPORT zkv_ctx* zkv_plonk_set_create(size_t n_keys, const uint8_t* const* vk_bytes, const size_t* vk_len, int device) {
@@ -3654,11 +3607,10 @@ static bool pset_agg_classes(zkv_ctx* c) {
     bool good = true;
     for (uint32_t q = 0; q < n_cls && good; q++)
         good = hipMemcpy(&ok[q], &c->d_gs_tab[c->ps_cls_rep[q]].vk_valid, sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess;
-    if (!good || hipMalloc(&c->d_agg_cnt, 3 * sizeof(unsigned long long)) != hipSuccess ||
+    if (!good || c->d_agg_cnt.alloc(3 * sizeof(unsigned long long)) ||
         hipMemset(c->d_agg_cnt, 0, 3 * sizeof(unsigned long long)) != hipSuccess) {
         (void)hipGetLastError();
-        if (c->d_agg_cnt) (void)hipFree(c->d_agg_cnt);
-        c->d_agg_cnt = nullptr;
+        c->d_agg_cnt.release();
         return false;
     }
     c->ps_cls_ok.assign(n_cls, 0);
@@ -3730,8 +3682,8 @@ static int run_pset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
     const size_t M = (size_t)slots;
     if ((rc = ctx_ready(c, M ? M : 1)) != ZKV_OK) return rc;     // (growing frees buffers, which synchronises the device)
     if ((rc = set_slot_buffers(c, M, &p, s)) != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->mx[7], c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
-    launch_gset_place(p, (const uint64_t*)c->mx[7], s);
+    HIP_TRY(hipMemcpyAsync(c->mx[KS_START], c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
+    launch_gset_place(p, c->mx[KS_START].as<const uint64_t>(), s);
     HIP_TRY(hipGetLastError());
     const size_t cap = c->ws.cap;                            // (a power of two >= 4,096 or ZKV_CHUNK, a multiple of 64: chunks keep the 64-slot groups)
     if (agg) {
@@ -3742,7 +3694,7 @@ static int run_pset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
         if ((rc = set_agg_plan(c, c->ps_cbeg.data(), c->ps_cend.data(), c->ps_cls_rep.data(), n_cls, R, (size_t)pset_agg_chunk_slots(cap, sub), sub,
                                &plan, s)) != ZKV_OK) return rc;
         for (const GsetAggChunk& g : plan) {
-            enqueue_pset_agg(c, pset_chunk_of(c, p, d_proofs, d_inputs, g.base, g.m), g, p.skey + g.base, (const uint32_t*)c->mx[10], sub, s,
+            enqueue_pset_agg(c, pset_chunk_of(c, p, d_proofs, d_inputs, g.base, g.m), g, p.skey + g.base, c->mx[KS_AMAP].as<const uint32_t>(), sub, s,
                              M == R && g.base + g.m >= R);
             HIP_TRY(hipGetLastError());
         }
@@ -3788,12 +3740,12 @@ ZKV_EXPORT int zkv_plonk_set_verify_batch(zkv_ctx* c, size_t n, const uint32_t* 
     // chunks of the caller's order staged in HBM: keys, proofs, public inputs (hb[0..2]) and the verdicts (hb[3])
     for (size_t base = 0; base < n; base += hc) {
         const size_t m = n - base < hc ? n - base : hc;
-        if ((rc = grow(&c->hb[0], &c->hb_cap[0], 4 * m)) != ZKV_OK || (rc = grow(&c->hb[1], &c->hb_cap[1], ps * m)) != ZKV_OK ||
-            (rc = grow(&c->hb[2], &c->hb_cap[2], is * m + 8)) != ZKV_OK || (rc = grow(&c->hb[3], &c->hb_cap[3], m)) != ZKV_OK) return rc;
+        if ((rc = c->hb[0].grow(4 * m)) != ZKV_OK || (rc = c->hb[1].grow(ps * m)) != ZKV_OK ||
+            (rc = c->hb[2].grow(is * m + 8)) != ZKV_OK || (rc = c->hb[3].grow(m)) != ZKV_OK) return rc;
         HIP_TRY(hipMemcpyAsync(c->hb[0], key + base, 4 * m, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->hb[1], proofs + ps * base, ps * m, hipMemcpyHostToDevice, c->stream));
         if (is) HIP_TRY(hipMemcpyAsync(c->hb[2], public_inputs + is * base, is * m, hipMemcpyHostToDevice, c->stream));
-        if ((rc = run_pset(c, m, (const uint32_t*)c->hb[0], c->hb[1], is ? c->hb[2] : nullptr, c->hb[3], c->stream)) != ZKV_OK) return rc;
+        if ((rc = run_pset(c, m, c->hb[0].as<const uint32_t>(), c->hb[1], is ? c->hb[2] : nullptr, c->hb[3], c->stream)) != ZKV_OK) return rc;
         HIP_TRY(hipMemcpyAsync(verified + base, c->hb[3], m, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -3819,8 +3771,8 @@ ZKV_EXPORT int zkv_ctx_vk_x_batch(zkv_ctx* c, size_t n, const uint8_t* var_signa
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
     for (size_t base = 0; base < n; base += cap) {
         size_t m = n - base < cap ? n - base : cap;
-        if ((rc = grow(&c->d_blob, &c->blob_cap, m * sig + 8)) != ZKV_OK) return rc;
-        if ((rc = grow(&c->d_pv, &c->pv_cap, m * 64 + 8)) != ZKV_OK) return rc;
+        if ((rc = c->d_blob.grow(m * sig + 8)) != ZKV_OK) return rc;
+        if ((rc = c->d_pv.grow(m * 64 + 8)) != ZKV_OK) return rc;
         if (sig) HIP_TRY(hipMemcpyAsync(c->d_blob, var_signals + sig * base, sig * m, hipMemcpyHostToDevice, c->stream));
         if (c->long_key) launch_vk_x_long(m, msm_lanes_long(c, m), c->d_tab, long_key_of(c), c->d_blob, c->d_pv, c->stream);
         else launch_vk_x(m, c->d_tab, c->m16, nullptr, nullptr, c->d_blob, c->d_pv, c->stream);
@@ -3842,30 +3794,23 @@ static int run_diag(int device, bool issue, int kind, int waves_per_simd, uint32
     hipDeviceProp_t p;
     HIP_TRY(hipGetDeviceProperties(&p, device));
     const unsigned blocks = (unsigned)p.multiProcessorCount * 4u * (unsigned)waves_per_simd;      // one 64-lane workgroup per wave slot
-    uint32_t* d_out = nullptr; unsigned long long* d_clk = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = ZKV_ERR_HIP;
+    DevBuf<uint32_t> d_out; DevBuf<unsigned long long> d_clk;
+    DevEvent e0, e1;
     float ms = 0;
     unsigned long long clk[2] = {0, 0};
     auto launch = [&](uint32_t it) { if (issue) launch_diag_issue(kind, blocks, it, d_out, d_clk, nullptr); else launch_diag_mulmod(kind, blocks, it, d_out, d_clk, nullptr); };
-    if (hipMalloc(&d_out, (size_t)blocks * 64 * 4) != hipSuccess || hipMalloc(&d_clk, 16) != hipSuccess) goto done;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) goto done;
-    launch(iters / 8 + 1);                                                                 // warm-up (code fetch, clocks)
-    if (hipDeviceSynchronize() != hipSuccess) goto done;
-    if (hipEventRecord(e0, nullptr) != hipSuccess) goto done;
-    launch(iters);
-    if (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) goto done;
-    if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess || hipMemcpy(clk, d_clk, 16, hipMemcpyDeviceToHost) != hipSuccess) goto done;
+    auto measure = [&]() -> bool {
+        if (d_out.alloc((size_t)blocks * 64 * 4) || d_clk.alloc(16) || e0.create() || e1.create()) return false;
+        launch(iters / 8 + 1);                                                             // warm-up (code fetch, clocks)
+        if (hipDeviceSynchronize() != hipSuccess || hipEventRecord(e0, nullptr) != hipSuccess) return false;
+        launch(iters);
+        return hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
+               hipEventElapsedTime(&ms, e0, e1) == hipSuccess && hipMemcpy(clk, d_clk, 16, hipMemcpyDeviceToHost) == hipSuccess;
+    };
+    if (!measure()) { (void)hipGetLastError(); return ZKV_ERR_HIP; }
     *per_s = (double)blocks * 64.0 * (issue ? 64.0 : 4.0 * (kind == 1 ? 2.0 : 1.0)) * (double)iters / ((double)ms * 1e-3);
     if (shader_clock_ghz) *shader_clock_ghz = clk[1] ? 0.1 * (double)clk[0] / (double)clk[1] : 0.0;     // s_memrealtime ticks at 100 MHz
-    rc = ZKV_OK;
-done:
-    if (rc != ZKV_OK) (void)hipGetLastError();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (d_out) (void)hipFree(d_out);
-    if (d_clk) (void)hipFree(d_clk);
-    return rc;
+    return ZKV_OK;
 }
 ZKV_EXPORT int zkv_diag_mulmod_rate(int device, int kind, int waves_per_simd, uint32_t iters, double* mulmods_per_s, double* shader_clock_ghz) {
     if (kind < 0 || kind > 4 || waves_per_simd < 1 || waves_per_simd > 8 || !iters || !mulmods_per_s) return ZKV_ERR_INVALID_ARG;
@@ -3886,20 +3831,17 @@ ZKV_EXPORT int zkv_diag_primitive(int device, int mapping, int op, size_t n, con
     if (device < 0 || device >= nd || !device_is_gfx950(device)) return ZKV_ERR_NO_DEVICE;
     HIP_TRY(hipSetDevice(device));
     const size_t per = (size_t)selftest_cases_per_wave(mapping), waves = (n + per - 1) / per, padded = waves * per;
-    uint32_t *d_in = nullptr, *d_out = nullptr;
-    int rc = ZKV_ERR_HIP;
-    if (hipMalloc(&d_in, padded * (size_t)iw * 4) != hipSuccess || hipMalloc(&d_out, padded * (size_t)ow * 4) != hipSuccess) { rc = ZKV_ERR_OOM; goto done; }
-    if (hipMemset(d_in, 0, padded * (size_t)iw * 4) != hipSuccess || hipMemcpy(d_in, in, n * (size_t)iw * 4, hipMemcpyHostToDevice) != hipSuccess) goto done;
-    if (mapping == 0) launch_selftest_lane(op, (unsigned)waves, d_in, d_out, nullptr);
-    else launch_selftest_pair(mapping, op, (unsigned)waves, d_in, d_out, nullptr);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) goto done;
-    if (hipMemcpy(out, d_out, n * (size_t)ow * 4, hipMemcpyDeviceToHost) != hipSuccess) goto done;
-    rc = ZKV_OK;
-done:
-    if (rc != ZKV_OK) (void)hipGetLastError();
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    DevBuf<uint32_t> d_in, d_out;
+    if (d_in.alloc(padded * (size_t)iw * 4) || d_out.alloc(padded * (size_t)ow * 4)) return ZKV_ERR_OOM;
+    bool ok = hipMemset(d_in, 0, padded * (size_t)iw * 4) == hipSuccess && hipMemcpy(d_in, in, n * (size_t)iw * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        if (mapping == 0) launch_selftest_lane(op, (unsigned)waves, d_in, d_out, nullptr);
+        else launch_selftest_pair(mapping, op, (unsigned)waves, d_in, d_out, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(out, d_out, n * (size_t)ow * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); return ZKV_ERR_HIP; }
+    return ZKV_OK;
 }
 
 // ------------------------------------------------------------------ zkv_diag_prep.h: what PREP stored for the vk_x stage (TEST ONLY)
@@ -3962,12 +3904,11 @@ ZKV_EXPORT int zkv_diag_gt_read(zkv_ctx* c, int signal, uint32_t window, uint32_
     }
     if (signal < 0) { HIP_TRY(hipMemcpy(out96, src, sizeof(uint32_t) * GT_ENTRY_WORDS, hipMemcpyDeviceToHost)); return ZKV_OK; }
     // an entry is stored as its affine torus value a (zkv_gt.h): the full Fp12 is reconstructed from it on the device
-    uint32_t* d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_out, sizeof(uint32_t) * GT_ENTRY_WORDS));
+    DevBuf<uint32_t> d_out;
+    HIP_TRY(d_out.alloc(sizeof(uint32_t) * GT_ENTRY_WORDS));
     launch_gt_diag_expand(src, d_out, c->stream);
     const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess &&
                     hipMemcpy(out96, d_out, sizeof(uint32_t) * GT_ENTRY_WORDS, hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(d_out);
     if (!ok) { (void)hipGetLastError(); return ZKV_ERR_HIP; }
     return ZKV_OK;
 }
@@ -4002,10 +3943,10 @@ ZKV_EXPORT int zkv_diag_gt_product(zkv_ctx* c, size_t n, const uint32_t* scalars
     constexpr size_t SW = 8 * GT_MAX_SIG;
     std::vector<uint32_t> rows(SW * n), res((size_t)GT_ENTRY_WORDS * n);
     for (size_t i = 0; i < n; i++) for (size_t k = 0; k < SW; k++) rows[k * n + i] = scalars[i * SW + k];
-    uint8_t* d_st = nullptr;
-    uint32_t* d_m = nullptr;                                     // M and the scratch of k_gt_diag_ratio, 96 n words each
-    HIP_TRY(hipMalloc(&d_st, n));
-    if (hipMalloc(&d_m, sizeof(uint32_t) * 2 * GT_ENTRY_WORDS * n) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_st); return ZKV_ERR_HIP; }
+    DevBuf<uint8_t> d_st;
+    DevBuf<uint32_t> d_m;                                        // M and the scratch of k_gt_diag_ratio, 96 n words each
+    HIP_TRY(d_st.alloc(n));
+    HIP_TRY(d_m.alloc(sizeof(uint32_t) * 2 * GT_ENTRY_WORDS * n));
     const size_t cap = c->ws.cap;
     bool ok = hipMemcpy2DAsync(c->ws.prep + 64 * cap, cap * 4, rows.data(), n * 4, n * 4, SW, hipMemcpyHostToDevice, c->stream) == hipSuccess;
     if (ok) {
@@ -4017,7 +3958,6 @@ ZKV_EXPORT int zkv_diag_gt_product(zkv_ctx* c, size_t n, const uint32_t* scalars
              hipMemcpyAsync(res.data(), d_m, sizeof(uint32_t) * GT_ENTRY_WORDS * n, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
              hipStreamSynchronize(c->stream) == hipSuccess;
     }
-    (void)hipFree(d_st); (void)hipFree(d_m);
     if (!ok) { (void)hipGetLastError(); return ZKV_ERR_HIP; }
     for (size_t i = 0; i < n; i++) for (size_t k = 0; k < GT_ENTRY_WORDS; k++) out[i * GT_ENTRY_WORDS + k] = res[k * n + i];
     return ZKV_OK;
@@ -4099,6 +4039,11 @@ ZKV_EXPORT int zkv_ctx_aggregate_counters(zkv_ctx* c, uint64_t out[2]) {
     unsigned long long v[2];
     HIP_TRY(hipMemcpy(v, c->d_agg_cnt, sizeof v, hipMemcpyDeviceToHost));
     out[0] = v[0]; out[1] = v[1];
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_diag_device_memory(uint64_t out[2]) {
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    out[0] = g_dev_live_allocs.load(std::memory_order_relaxed); out[1] = g_dev_live_bytes.load(std::memory_order_relaxed);
     return ZKV_OK;
 }
 ZKV_EXPORT int zkv_diag_wait_faults(int device, uint64_t* out) {
@@ -4269,7 +4214,7 @@ ZKV_EXPORT int zkv_status_abi_encode(int vm, uint8_t status, const uint8_t recei
 // No reference counterpart: parity unpinned.  k_setincl.hip hashes the paths and forms the root jobs; the jobs run on the inner context.
 enum { SI_ROOTS = 0, SI_REP, SI_GSLOT, SI_CLAIMJOB, SI_JOBCLAIM, SI_CNT, SI_STORED, SI_ROWS, SI_LENS, SI_IDS, SI_JDS, SI_PROOFS, SI_SIGNALS, SI_PRE,
        SI_PRERECV, SI_JST, SI_JRV, SI_H_A, SI_H_B, SI_H_PATHS, SI_H_POFF, SI_H_RIDX, SI_H_SEALS, SI_H_SLEN, SI_H_ST, SI_H_RV, SI_DIAG, SI_BUFS };
-static_assert(SI_BUFS <= sizeof(((zkv_ctx*)nullptr)->mx) / sizeof(uint8_t*), "the set-inclusion buffers live in zkv_ctx::mx");
+static_assert(SI_BUFS <= CtxDevice::MX_SLOTS, "the set-inclusion buffers live in zkv_ctx::mx");
 constexpr size_t SETINCL_CHUNK = (size_t)1 << 20;
 
 static void setincl_set_selector(const uint8_t id[32], uint8_t out[4]) {
@@ -4382,14 +4327,14 @@ static int run_setincl(zkv_ctx* c, size_t n, const uint8_t* d_a, const uint8_t* 
     int rc;
     const size_t cap = n < SETINCL_CHUNK ? n : SETINCL_CHUNK;
     const size_t need[7] = {32 * cap, 4 * (m + 1), 4 * (m + 1), 4 * cap, 4 * cap, 16, (size_t)32 * ZKV_SETINCL_MAX_ROOTS};
-    for (int k = 0; k < 7; k++) if ((rc = grow(&c->mx[k], &c->mx_cap[k], need[k])) != ZKV_OK) return rc;
+    for (int k = 0; k < 7; k++) if ((rc = c->mx[k].grow(need[k])) != ZKV_OK) return rc;
     if (c->si_dirty) {                                   // a root was submitted since the last call: nothing of this context is in flight after the wait
         HIP_TRY(hipDeviceSynchronize());
         if (!c->si_roots.empty()) HIP_TRY(hipMemcpy(c->mx[SI_STORED], c->si_roots.data(), c->si_roots.size(), hipMemcpyHostToDevice));
         c->si_dirty = false;
     }
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
-    uint32_t* cnt = (uint32_t*)c->mx[SI_CNT];
+    uint32_t* cnt = c->mx[SI_CNT].as<uint32_t>();
     HIP_TRY(hipMemsetAsync(cnt, 0, 16, s));
     if (!d_diag) { c->si_counts[0] = n; c->si_counts[1] = 0; c->si_counts[2] = 0; }
     for (size_t base = 0; base < n; base += cap) {
@@ -4401,8 +4346,8 @@ static int run_setincl(zkv_ctx* c, size_t n, const uint8_t* d_a, const uint8_t* 
         ch.paths = d_paths; ch.path_off = d_poff + base; ch.root_idx = d_ridx ? d_ridx + base : nullptr;
         ch.seals = d_seals; ch.seal_len = d_slen; ch.stored = c->mx[SI_STORED];
         for (int q = 0; q < 8; q++) ch.id_be[q] = be32_of(c->si_id + 4 * q);
-        ch.roots = (uint32_t*)c->mx[SI_ROOTS]; ch.rep = (uint32_t*)c->mx[SI_REP]; ch.gslot = (uint32_t*)c->mx[SI_GSLOT];
-        ch.claim_job = (uint32_t*)c->mx[SI_CLAIMJOB]; ch.job_claim = (uint32_t*)c->mx[SI_JOBCLAIM]; ch.counters = cnt;
+        ch.roots = c->mx[SI_ROOTS].as<uint32_t>(); ch.rep = c->mx[SI_REP].as<uint32_t>(); ch.gslot = c->mx[SI_GSLOT].as<uint32_t>();
+        ch.claim_job = c->mx[SI_CLAIMJOB].as<uint32_t>(); ch.job_claim = c->mx[SI_JOBCLAIM].as<uint32_t>(); ch.counters = cnt;
         ch.status = d_status ? d_status + base : nullptr; ch.recv = d_recv ? d_recv + 4 * base : nullptr;
         ch.diag_roots = d_diag ? d_diag + 32 * base : nullptr;
         if (d_diag) { launch_setincl_hash(ch, c->consts, s); HIP_TRY(hipGetLastError()); continue; }
@@ -4426,8 +4371,8 @@ static int run_setincl(zkv_ctx* c, size_t n, const uint8_t* d_a, const uint8_t* 
             const size_t jneed[10] = {c->si_keyed ? 0 : (size_t)260 * nj, c->si_keyed ? 0 : (size_t)4 * nj, c->si_keyed ? 0 : (size_t)32 * nj,
                                       c->si_keyed ? 0 : (size_t)32 * nj, c->si_keyed ? (size_t)256 * nj : 0, c->si_keyed ? (size_t)160 * nj : 0,
                                       c->si_keyed ? (size_t)nj : 0, c->si_keyed ? (size_t)4 * nj : 0, nj, (size_t)4 * nj};
-            for (int k = 0; k < 10; k++) if ((rc = grow(&c->mx[SI_ROWS + k], &c->mx_cap[SI_ROWS + k], jneed[k])) != ZKV_OK) return rc;
-            jb.rows = c->mx[SI_ROWS]; jb.lens = (uint32_t*)c->mx[SI_LENS]; jb.ids = c->mx[SI_IDS]; jb.jds = c->mx[SI_JDS];
+            for (int k = 0; k < 10; k++) if ((rc = c->mx[SI_ROWS + k].grow(jneed[k])) != ZKV_OK) return rc;
+            jb.rows = c->mx[SI_ROWS]; jb.lens = c->mx[SI_LENS].as<uint32_t>(); jb.ids = c->mx[SI_IDS]; jb.jds = c->mx[SI_JDS];
             jb.proofs = c->mx[SI_PROOFS]; jb.signals = c->mx[SI_SIGNALS]; jb.pre = c->mx[SI_PRE]; jb.pre_recv = c->mx[SI_PRERECV];
             jb.st = c->mx[SI_JST]; jb.rv = c->mx[SI_JRV];
             memcpy(jb.fixed[0] + 16, c->control_root_0, 16); memcpy(jb.fixed[1] + 16, c->control_root_1, 16); memcpy(jb.fixed[2], c->control_id, 32);
@@ -4488,11 +4433,11 @@ static int setincl_host_call(zkv_ctx* c, size_t n, const uint8_t* in_a, const ui
         }
     } catch (const std::bad_alloc&) { return ZKV_ERR_OOM; }
     const size_t need[9] = {32 * n, integrity ? 0 : 32 * n, 32 * n_sib + 256 + 32, 4 * (n + 1), 4 * n, rows.size(), 4 * sl.size(), n, 4 * n};
-    for (int k = 0; k < 9; k++) if ((rc = grow(&c->mx[SI_H_A + k], &c->mx_cap[SI_H_A + k], need[k])) != ZKV_OK) return rc;
-    if (diag_out && (rc = grow(&c->mx[SI_DIAG], &c->mx_cap[SI_DIAG], 32 * n)) != ZKV_OK) return rc;
+    for (int k = 0; k < 9; k++) if ((rc = c->mx[SI_H_A + k].grow(need[k])) != ZKV_OK) return rc;
+    if (diag_out && (rc = c->mx[SI_DIAG].grow(32 * n)) != ZKV_OK) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
-    uint8_t* d_paths = (uint8_t*)(((uintptr_t)c->mx[SI_H_PATHS] + 255u) & ~(uintptr_t)255u) + blob_shift;
+    uint8_t* d_paths = (uint8_t*)(((uintptr_t)c->mx[SI_H_PATHS].as<uint8_t>() + 255u) & ~(uintptr_t)255u) + blob_shift;
     HIP_TRY(hipMemcpyAsync(c->mx[SI_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
     if (!integrity) HIP_TRY(hipMemcpyAsync(c->mx[SI_H_B], in_b, 32 * n, hipMemcpyHostToDevice, s));
     if (n_sib) HIP_TRY(hipMemcpyAsync(d_paths, path_blob + 32 * (size_t)o0, 32 * n_sib, hipMemcpyHostToDevice, s));
@@ -4503,8 +4448,8 @@ static int setincl_host_call(zkv_ctx* c, size_t n, const uint8_t* in_a, const ui
         HIP_TRY(hipMemcpyAsync(c->mx[SI_H_SLEN], sl.data(), 4 * sl.size(), hipMemcpyHostToDevice, s));
     }
     HIP_TRY(hipStreamSynchronize(s));                    // the staging vectors are pageable host memory
-    rc = run_setincl(c, n, c->mx[SI_H_A], integrity ? nullptr : c->mx[SI_H_B], d_paths, (const uint32_t*)c->mx[SI_H_POFF], n_sib,
-                     diag_out ? nullptr : (const uint32_t*)c->mx[SI_H_RIDX], m, c->mx[SI_H_SEALS], (const uint32_t*)c->mx[SI_H_SLEN],
+    rc = run_setincl(c, n, c->mx[SI_H_A], integrity ? nullptr : c->mx[SI_H_B], d_paths, c->mx[SI_H_POFF].as<const uint32_t>(), n_sib,
+                     diag_out ? nullptr : c->mx[SI_H_RIDX].as<const uint32_t>(), m, c->mx[SI_H_SEALS], c->mx[SI_H_SLEN].as<const uint32_t>(),
                      diag_out ? nullptr : c->mx[SI_H_ST], diag_out ? nullptr : c->mx[SI_H_RV], diag_out ? c->mx[SI_DIAG] : nullptr, s);
     if (rc != ZKV_OK) return rc;
     if (diag_out) HIP_TRY(hipMemcpyAsync(diag_out, c->mx[SI_DIAG], 32 * n, hipMemcpyDeviceToHost, s));

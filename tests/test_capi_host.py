@@ -278,3 +278,28 @@ def test_aggregate_check_switch_host_side(z, real_proofs):
         v.set_aggregate_check(True, seed=b'short')
     for ctx in (v, sp, mx, pc):
         ctx.close()
+
+
+def test_device_memory_count_without_a_device(z, real_proofs):
+    """zkv_diag_device_memory needs no device: {0 allocations, 0 bytes} before and after one context of every kind this module creates has
+    been created, asked to compute (refused: no device) and destroyed."""
+    if z.device_count() > 0:
+        pytest.skip('a gfx950 device is present: tests/test_device_memory_gpu.py counts there')
+    from stylus_zkvm_verifiers_amd import _lib
+    L = _lib.lib()
+
+    def live():
+        out = (C.c_uint64 * 2)(7, 7)
+        assert L.zkv_diag_device_memory(out) == _lib.OK
+        return out[0], out[1]
+    assert L.zkv_diag_device_memory(None) == _lib.ERR_INVALID_ARG
+    assert live() == (0, 0)
+    r = real_proofs['risc0']
+    v = z.RiscZeroVerifier(); v.initialize(H(r['control_root']), H(r['bn254_control_id']))
+    ctxs = [v, z.Sp1Verifier(), z.MixedVerifier(H(r['control_root']), H(r['bn254_control_id'])), z.Bn254Precompiles()]
+    for ctx in ctxs:
+        assert L.zkv_ctx_reserve(ctx._h, 64) == _lib.ERR_NO_DEVICE
+    assert live() == (0, 0)
+    for ctx in ctxs:
+        ctx.close()
+    assert live() == (0, 0)

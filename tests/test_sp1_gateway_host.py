@@ -60,7 +60,7 @@ def test_header_declares_exactly_the_new_symbols_and_the_library_exports_them(L)
     for name in NEW:
         assert hasattr(L, name), name
     main = _names(os.path.join(ROOT, 'include', 'zkv.h'))
-    assert len(main) == 82 and not main & set(NEW)
+    assert len(main) == 83 and not main & set(NEW)
 
 
 def test_create_refuses_bad_route_sets(L, plonk):

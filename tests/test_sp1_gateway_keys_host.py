@@ -76,7 +76,7 @@ def test_header_declares_exactly_the_new_symbols_and_the_library_exports_them(L)
     assert set(sp1_gateway.SYMBOLS) == set(GATEWAY)
     assert _names(os.path.join(ROOT, 'include', 'zkv_sp1_gateway.h')) == set(GATEWAY)
     main = _names(os.path.join(ROOT, 'include', 'zkv.h'))
-    assert len(main) == 82 and not main & set(NEW)
+    assert len(main) == 83 and not main & set(NEW)
 
 
 def test_cpp_mirror_with_the_keyed_constructor_compiles(tmp_path):
