@@ -26,11 +26,16 @@ __global__ __launch_bounds__(64) void k_gt_bases(const VkRaw* __restrict__ raw, 
     n.lxs = n.lys = n.cxs = n.cys = fp_zero();
     if (b == 2) {
         MRef out = m_ref(mconst, 1), ab = m_ref(const_cast<uint32_t*>(t->f_alpha_beta), 1);
-        if (t->base_inf) { f12m_copy(out, ab); return; }
-        const Fp iy = fp_inv(t->base.y);
-        n.axs = fp_mul(t->base.x, iy); n.ays = iy;
-        miller_loop_m((const VkTables*)nullptr, 0, n, gx, gy, fm, tm);
-        f12m_mul(out, fm, ab);
+        if (t->base_inf) f12m_copy(out, ab);
+        else {
+            const Fp iy = fp_inv(t->base.y);
+            n.axs = fp_mul(t->base.x, iy); n.ays = iy;
+            miller_loop_m((const VkTables*)nullptr, 0, n, gx, gy, fm, tm);
+            f12m_mul(out, fm, ab);
+        }
+        // ... and behind it the start value of the lane-pair loop, FE(constant)^e (miller_start_value, zkv_verify.h)
+        f12m_copy(fm, out);
+        miller_start_value(m_ref(mconst + 96, 1), fm, E, Y1, Y3, Y4, W, acc);
         return;
     }
     const uint32_t nw = b ? nw1 : nw0, row0 = b ? nw0 : 0u;

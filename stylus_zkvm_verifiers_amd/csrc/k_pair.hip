@@ -69,15 +69,21 @@ __global__ __launch_bounds__(PAIR_BLOCK, 2) void k_miller2(size_t n, const VkTab
     LRef tm = l_ref(wl + 48 * ZKV_BLOCK);
     SoaRef norm = {ws.norm, ws.cap, (uint32_t)i * 4u};                                               // Fp values: both lanes of the pair read them
     SoaRef bsrc = {ws.prep + 32 * ws.cap, ws.cap, (uint32_t)(8 * par * ws.cap + i) * 4u};             // this lane's component of B.x (B.y 16 words on)
-    if (!miller_loop_p(vk, flags, norm, bsrc, fm, tm, true)) {
+    // the per-context constant: ML(alpha, beta), times ML(base, gamma) when the (vk_x, gamma) pair is left to the GT tables (zkv_gt.h; k_msm then
+    // marked every vk_x as absent, so the loop takes no trip for it).  With the tables the constant comes as the loop's START VALUE, the 96
+    // words behind mconst (miller_start_value, zkv_verify.h: the final exponentiation of what the loop then delivers is that of loop value
+    // times constant), and the loop's value goes straight to ws.f; without them the loop starts from 1 and closes with the product.
+    const uint32_t* start = mconst ? mconst + 96 : nullptr;
+    if (!miller_loop_p(vk, flags, norm, bsrc, fm, tm, true, start)) {
         if (!par) { ws.g2bad[i] = 1; status[i] = ST_VERIFICATION_FAILED; }
         return;
     }
-    // the per-context constant: ML(alpha, beta), times ML(base, gamma) when the (vk_x, gamma) pair is left to the GT tables (zkv_gt.h; k_msm then
-    // marked every vk_x as absent, so the loop above took no trip for it)
-    MRef ab = m_ref((uint32_t*)(mconst ? mconst : vk->f_alpha_beta) + 8 * par, 1, 16);
     MRef out = m_ref(ws.f + (size_t)(8 * par) * ws.cap + i, (uint32_t)ws.cap, 16);
-    f12m_mul_body(out, fm, ab, false);
+    if (start) f12m_copy(out, fm);
+    else {
+        MRef ab = m_ref((uint32_t*)vk->f_alpha_beta + 8 * par, 1, 16);
+        f12m_mul_body(out, fm, ab, false);
+    }
     ZKV_STAMP(0, 1);
 }
 

@@ -618,7 +618,8 @@ static int gt_maybe_build(zkv_ctx* c, size_t n) {
     if (bytes > gt_max_bytes()) return ZKV_OK;
     DevBuf<VkRaw> d_raw; DevBuf<uint32_t> d_scr;
     DevEvent e0, e1;
-    bool ok = c->d_gt.alloc(bytes) == ZKV_OK && c->d_gt_const.alloc(sizeof(uint32_t) * GT_ENTRY_WORDS) == ZKV_OK &&
+    bool ok = c->d_gt.alloc(bytes) == ZKV_OK && c->d_gt_const.alloc(sizeof(uint32_t) * 2 * GT_ENTRY_WORDS) == ZKV_OK &&      // the folded constant, and the loop's start value made of it
+              miller_start_exponent_ok() &&                                            // 2^64 h invertible mod r, e its inverse (zkv_verify.h)
               d_raw.alloc(sizeof(VkRaw)) == ZKV_OK && d_scr.alloc(sizeof(uint32_t) * GT_SETUP_SCRATCH_WORDS) == ZKV_OK &&
               e0.create() == ZKV_OK && e1.create() == ZKV_OK;
     if (ok) {

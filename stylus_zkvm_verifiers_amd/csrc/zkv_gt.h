@@ -121,7 +121,8 @@ ZKV_GT_HD uint32_t gt_cache_claim(GtCache& c, const uint32_t* key) {
 }
 
 // What the kernels get: the tables (nullptr: none, the Miller loop takes the pair), the folded Miller constant
-// ML(alpha, beta) * ML(base, gamma) (96 words, the layout of VkTables::f_alpha_beta), the window counts of the two signals and the
+// ML(alpha, beta) * ML(base, gamma) (96 words, the layout of VkTables::f_alpha_beta; the 96 words behind it hold the start value of the
+// lane-pair Miller loop made of it, miller_start_value in zkv_verify.h), the window counts of the two signals and the
 // walk-prefix cache (nullptr: none).
 struct GtTab { const uint32_t* tab; const uint32_t* mconst; uint32_t nw[GT_MAX_SIG]; GtCache* cache; };
 

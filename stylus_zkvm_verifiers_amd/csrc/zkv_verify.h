@@ -364,13 +364,16 @@ struct SoaRef {                         // word k of this proof's (this lane's) 
 // every partial scalar) never meets one and ends with Z != 0.  With check_b the point is stepped for A = infinity too (the precompile
 // validates B whether or not the pair contributes); only the line products are skipped then.
 template <class RF, class RT>
-ZKV_HD bool miller_loop_p(const VkTables* vkp, uint32_t flags, SoaRef norm, SoaRef bsrc, RF fm, RT tm, bool check_b = false) {
+ZKV_HD bool miller_loop_p(const VkTables* vkp, uint32_t flags, SoaRef norm, SoaRef bsrc, RF fm, RT tm, bool check_b = false, const uint32_t* start = nullptr) {
     const uint8_t KIND[ZKV_MILLER_STEPS] = ZKV_MILLER_STEP_KIND;
     const bool with_fixed = vkp != nullptr;
     const bool do_ab = !(flags & (FL_A_INF | FL_B_INF));
     const bool do_t = do_ab || (check_b && !(flags & FL_B_INF));
     const bool do_l = with_fixed && !(flags & FL_L_INF) && !vkp->skip_fixed[0], do_c = with_fixed && !(flags & FL_C_INF) && !vkp->skip_fixed[1];
-    f12m_set_one(fm);
+    // start: the accumulator's first value, 96 words in the layout of VkTables::f_alpha_beta (miller_start_value; the loop then delivers
+    // start^(2^64) times its value); nullptr: 1
+    if (start) f12m_copy(fm, m_ref(const_cast<uint32_t*>(start) + 8 * zkv_parity(), 1, 16));
+    else f12m_set_one(fm);
     { Fp2 bx, by; bx.h = bsrc.fp(0); by.h = bsrc.fp(16); m_st_f2(tm, 0, bx); m_st_f2(tm, 1, by); m_st_f2(tm, 2, f2_one()); }
     const uint32_t slot = zkv_wave_slot_parity();
 #pragma unroll 1
@@ -542,6 +545,54 @@ template <class RA> ZKV_HD bool final_exp_is_one_m(MRef F, MRef E, MRef Y1, MRef
     f12m_frob(E, E, 3);                     // y15
     f12m_mul(acc, E, acc);
     return f12m_is_one(acc);
+}
+// The per-context Miller constant as the START VALUE of the lane-pair loop.  k_miller2 used to close with a dense product by the constant
+// m (ML(alpha, beta), times ML(base, gamma) with the GT tables).  Starting the accumulator from c instead of 1 makes the loop deliver
+// c^(2^64) times its value (64 squarings follow step 0), and with
+//     c = FE(m)^e,   e = (2^64 h)^-1 mod r,   h = k (p^12 - 1) / r  the exponent FE applies (final_exp_is_one_m),
+// FE(c^(2^64)) = FE(m)^(h e 2^64) = FE(m) exactly, because FE(m) has order dividing r: every accept / reject stays what it was.
+// ZKV_MILLER_START_HR = h mod r and ZKV_MILLER_START_E = e, little-endian words (tests/test_miller_sqr_host.py derives both again from p,
+// r and u; miller_start_exponent_ok is the host's assertion that 2^64 h is invertible mod r and that e is its inverse).
+#define ZKV_MILLER_START_HR {0xd636f235u, 0x1c2edc10u, 0xd3290123u, 0x194998a4u, 0x59a7280au, 0xdddc0ef8u, 0xe131a018u, 0x30644e72u}
+#define ZKV_MILLER_START_E {0x0093e79bu, 0xed92c00du, 0x46b3b592u, 0xa24730bau, 0xea466f56u, 0x04db5c66u, 0x47869ae3u, 0x02b6f45eu}
+#define ZKV_MILLER_START_E_BITS 250
+// out <- FE(m)^e.  M holds m on entry (clobbered); E, Y1, Y3, Y4, the three slots at W and acc are the scratch of final_exp_is_one_m;
+// out is a slot of its own.  FE(m) lies in the cyclotomic subgroup, so the ladder squares with f12m_cyclo_sqr.
+ZKV_HD void miller_start_value(MRef out, MRef M, MRef E, MRef Y1, MRef Y3, MRef Y4, MRef W, MRef acc) {
+    const uint32_t EX[8] = ZKV_MILLER_START_E;
+    (void)final_exp_is_one_m(M, E, Y1, Y3, Y4, W, acc);
+    f12m_copy(out, acc);                                         // the top bit
+#pragma unroll 1
+    for (int i = ZKV_MILLER_START_E_BITS - 2; i >= 0; i--) {
+        f12m_cyclo_sqr(out);
+        if ((EX[i >> 5] >> (i & 31)) & 1u) f12m_mul(out, out, acc);
+    }
+}
+// e * 2^64 * (h mod r) == 1 mod r, in plain 256-bit integer arithmetic (shift-and-add; host code: run when a context builds its tables)
+inline bool miller_start_exponent_ok() {
+    const uint32_t RR[8] = ZKV_FR_R_LIMBS, HR[8] = ZKV_MILLER_START_HR, EX[8] = ZKV_MILLER_START_E;
+    auto geq = [&](const uint32_t* a) { for (int i = 8; i >= 0; i--) { const uint32_t m = i < 8 ? RR[i] : 0u; if (a[i] != m) return a[i] > m; } return true; };
+    auto dbl_mod = [&](uint32_t* a) {                           // a < r (nine words, the ninth for the doubled value) -> 2 a mod r
+        for (int i = 8; i > 0; i--) a[i] = (a[i] << 1) | (a[i - 1] >> 31);
+        a[0] <<= 1;
+        if (geq(a)) { uint64_t br = 0; for (int i = 0; i < 9; i++) { const uint64_t d = (uint64_t)a[i] - (i < 8 ? RR[i] : 0u) - br; a[i] = (uint32_t)d; br = (d >> 32) & 1u; } }
+    };
+    auto add_mod = [&](uint32_t* a, const uint32_t* b) {
+        uint64_t c = 0; for (int i = 0; i < 9; i++) { c += (uint64_t)a[i] + b[i]; a[i] = (uint32_t)c; c >>= 32; }
+        if (geq(a)) { uint64_t br = 0; for (int i = 0; i < 9; i++) { const uint64_t d = (uint64_t)a[i] - (i < 8 ? RR[i] : 0u) - br; a[i] = (uint32_t)d; br = (d >> 32) & 1u; } }
+    };
+    uint32_t x[9] = {0}, acc[9] = {0};
+    for (int i = 0; i < 8; i++) x[i] = HR[i];
+    if (geq(x)) return false;
+    for (int i = 0; i < 64; i++) dbl_mod(x);                    // 2^64 h mod r
+    bool zero = true; for (int i = 0; i < 9; i++) zero = zero && x[i] == 0;
+    if (zero) return false;                                     // r divides 2^64 h: not invertible
+    for (int i = 255; i >= 0; i--) {                            // acc = e * x mod r
+        dbl_mod(acc);
+        if ((EX[i >> 5] >> (i & 31)) & 1u) add_mod(acc, x);
+    }
+    bool one = acc[0] == 1u; for (int i = 1; i < 9; i++) one = one && acc[i] == 0;
+    return one;
 }
 
 #if defined(ZKV_PAIRED)
