@@ -30,6 +30,7 @@
 #include "../../include/zkv_risc0_set_inclusion.h"
 #include "../../include/zkv_risc0_router.h"
 #include "../../include/zkv_risc0_router_wire.h"
+#include "../../include/zkv_risc0_router_set.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
@@ -41,6 +42,7 @@
 #include "zkv_setincl.h"
 #include "zkv_rzrouter_prep.h"
 #include "zkv_wire_rzrouter.h"
+#include "zkv_rzrouter_set.h"
 #include <sys/random.h>
 
 using namespace zkv;
@@ -109,8 +111,8 @@ struct CtxDevice : ChunkMem, AggMem {
     // host-buffer batches (run_host_batch): whole-batch staging in HBM, filled segment by segment on copy_stream while the previous
     // segment is verified: seals, seal offsets, in_a, in_b, public values, pv offsets
     DevBuf<> hb[6];
-    // demultiplexing, routing and set-inclusion buffers (enums MX_*, GW_*, GWW_*, RZ_*, RZW_*, KS_*, SI_*)
-    static constexpr size_t MX_SLOTS = 28;
+    // demultiplexing, routing and set-inclusion buffers (enums MX_*, GW_*, GWW_*, RZ_*, RZW_*, RZS_*, KS_*, SI_*)
+    static constexpr size_t MX_SLOTS = 48;
     DevBuf<> mx[MX_SLOTS];
     DevEvent ev_fork, ev_join;                                 // small chunks: the G2 subgroup check runs beside the MSM (stream `side`)
     DevEvent ev_copied[2], ev_decoded[2];                      // wire layer: H2D of calldata chunk k+1 overlaps the kernels of chunk k
@@ -232,6 +234,12 @@ struct zkv_ctx : CtxDevice {
     std::vector<RzrRoute> rz_routes;
     std::vector<uint64_t> rz_counts;
     uint64_t rz_bad = 0;                        // bad-calldata seals of the call rz_counts describes (zkv_risc0_router_last_call_counts)
+    // A router with a set route (zkv_risc0_router_set.h): the set route is the last route and is not in gw_sel -- the partition knows the
+    // Groth16 routes only.  si_id, si_set_sel, si_roots and si_dirty are the set route's as they are a set-inclusion context's.
+    // rzs_counts: seals per route (the set route included), unknown, short; rzs_last: zkv_risc0_router_set_last_counts.
+    bool rz_set = false;
+    std::vector<uint64_t> rzs_counts;
+    uint64_t rzs_last[4] = {0, 0, 0, 0};
     std::mutex mu;
 };
 
@@ -2171,9 +2179,14 @@ ZKV_EXPORT zkv_ctx* zkv_risc0_router_create(size_t n_builtin, const uint8_t* con
     }
     return c;
 }
-ZKV_EXPORT size_t zkv_risc0_router_route_count(const zkv_ctx* c) { return c && c->vm == ZKV_VM_RISC0_ROUTER ? c->gw_sel.size() : 0; }
+ZKV_EXPORT size_t zkv_risc0_router_route_count(const zkv_ctx* c) { return c && c->vm == ZKV_VM_RISC0_ROUTER ? c->gw_sel.size() + (c->rz_set ? 1 : 0) : 0; }
 ZKV_EXPORT int zkv_risc0_router_route(const zkv_ctx* c, size_t r, uint8_t selector[4], int* keyed) {
     if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (c->rz_set && r == c->gw_sel.size()) {                     // the set route (zkv_risc0_router_set.h): the last one
+        if (selector) memcpy(selector, c->si_set_sel, 4);
+        if (keyed) *keyed = 2;
+        return ZKV_OK;
+    }
     if (r >= c->gw_sel.size()) return ZKV_ERR_INVALID_ARG;
     if (selector) be32_put(selector, c->gw_sel[r]);
     if (keyed) *keyed = r >= c->rz_nb ? 1 : 0;
@@ -2190,6 +2203,9 @@ enum { RZ_CNT = 0, RZ_TOT, RZ_ITOT, RZ_POS, RZ_IDX, RZ_RECS, RZ_LEN, RZ_A, RZ_B,
        RZ_H_SEALS, RZ_H_OFF, RZ_H_A, RZ_H_B, RZ_H_ST, RZ_H_RV,
        RZ_KIND, RZ_H_METHOD,                    // per-seal methods: the compact row and the host call's staging
        RZW_SEALS, RZW_LEN, RZW_CK,              // calldata batches: the decoded slots, true lengths and call kinds (inputs and methods: RZ_H_A, RZ_H_B, RZ_H_METHOD)
+       // the set route (zkv_risc0_router_set.h): claim records, the root-seal table, section 16's per-claim and per-slot rows, the job rows
+       RZS_REC, RZS_OWNER, RZS_RIDX, RZS_REP, RZS_GSLOT, RZS_CJOB, RZS_JCLAIM, RZS_ANS, RZS_CNT, RZS_ROOTS, RZS_STORED,
+       RZS_ROWS, RZS_LENS, RZS_IDS, RZS_JDS, RZS_JST, RZS_JRV, RZS_DIAG,
        RZ_BUFS };
 static_assert(RZ_BUFS <= CtxDevice::MX_SLOTS, "the router's buffers live in zkv_ctx::mx");
 // The built-in group: m compact records from the front end through the verifier set's pipeline (run_set_batch's chunks, with the true
@@ -2304,7 +2320,7 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
 }
 ZKV_EXPORT int zkv_risc0_router_verify_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint8_t* d_image_ids, const uint8_t* d_journal_digests,
                                                  uint8_t* d_status, uint8_t* d_recv, void* stream) {
-    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER || c->rz_set) return ZKV_ERR_WRONG_CTX;      // (a set seal has no fixed stride: zkv_risc0_router_verify_ragged_dev)
     if (n && (!d_seals || !d_image_ids || !d_status)) return ZKV_ERR_INVALID_ARG;
     if (!n) return ZKV_OK;
     if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES) return ZKV_ERR_INVALID_ARG;
@@ -2314,6 +2330,8 @@ ZKV_EXPORT int zkv_risc0_router_verify_batch_dev(zkv_ctx* c, size_t n, const uin
     return run_router(c, n, d_seals, nullptr, 0, d_image_ids, d_journal_digests, d_status, d_recv, stream ? (hipStream_t)stream : c->stream);
 }
 // host buffers: in_b == nullptr selects verify_integrity; method: the per-seal method row (in_b is then set), or nullptr
+static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64_t* d_seal_off, uint64_t seal_bytes, const uint8_t* d_a, const uint8_t* d_b,
+                          uint8_t* d_status, uint8_t* d_recv, hipStream_t s, uint32_t fp_mask, uint32_t* d_diag);
 static int router_host_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* in_a, const uint8_t* in_b,
                              uint8_t* status, uint8_t* recv, const uint8_t* method = nullptr) {
     if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES || !offsets_ok(seal_off, n)) return ZKV_ERR_INVALID_ARG;
@@ -2331,8 +2349,11 @@ static int router_host_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, con
     HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
     if (in_b) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_B], in_b, 32 * n, hipMemcpyHostToDevice, s));
     if (method) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_METHOD], method, n, hipMemcpyHostToDevice, s));
-    if ((rc = run_router(c, n, c->mx[RZ_H_SEALS], c->mx[RZ_H_OFF].as<const uint64_t>(), sbytes, c->mx[RZ_H_A], in_b ? c->mx[RZ_H_B] : nullptr,
-                         c->mx[RZ_H_ST], c->mx[RZ_H_RV], s, method ? c->mx[RZ_H_METHOD] : nullptr)) != ZKV_OK) return rc;
+    if (c->rz_set) rc = run_router_set(c, n, c->mx[RZ_H_SEALS], c->mx[RZ_H_OFF].as<const uint64_t>(), sbytes, c->mx[RZ_H_A], in_b ? c->mx[RZ_H_B] : nullptr,
+                                       c->mx[RZ_H_ST], c->mx[RZ_H_RV], s, 0xFFFFFFFFu, nullptr);
+    else rc = run_router(c, n, c->mx[RZ_H_SEALS], c->mx[RZ_H_OFF].as<const uint64_t>(), sbytes, c->mx[RZ_H_A], in_b ? c->mx[RZ_H_B] : nullptr,
+                         c->mx[RZ_H_ST], c->mx[RZ_H_RV], s, method ? c->mx[RZ_H_METHOD] : nullptr);
+    if (rc != ZKV_OK) return rc;
     return return_to_host(c, RZ_H_ST, RZ_H_RV, n, status, recv, s);
 }
 ZKV_EXPORT int zkv_risc0_router_verify_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* image_ids,
@@ -2367,7 +2388,8 @@ ZKV_EXPORT int zkv_risc0_router_last_route_counts(zkv_ctx* c, uint64_t* out) {
     if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
     if (!out) return ZKV_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    for (size_t r = 0; r < c->rz_counts.size(); r++) out[r] = c->rz_counts[r];
+    const std::vector<uint64_t>& v = c->rz_set ? c->rzs_counts : c->rz_counts;
+    for (size_t r = 0; r < v.size(); r++) out[r] = v[r];
     return ZKV_OK;
 }
 ZKV_EXPORT int zkv_risc0_router_status_abi_encode(const zkv_ctx* c, uint8_t status, const uint8_t received[4], uint8_t out[68]) {
@@ -2741,7 +2763,7 @@ ZKV_EXPORT int zkv_sp1_gateway_last_call_counts(zkv_ctx* c, uint64_t* out) {
 // everything after the count is the decoded-input path.
 ZKV_EXPORT int zkv_risc0_router_verify_call_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_method, const uint8_t* d_seals, const uint8_t* d_in_a,
                                                       const uint8_t* d_in_b, uint8_t* d_status, uint8_t* d_recv, void* stream) {
-    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER || c->rz_set) return ZKV_ERR_WRONG_CTX;
     if (n && (!d_seals || !d_in_a || !d_in_b || !d_status)) return ZKV_ERR_INVALID_ARG;
     if (!n) return ZKV_OK;
     if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES) return ZKV_ERR_INVALID_ARG;
@@ -2752,7 +2774,7 @@ ZKV_EXPORT int zkv_risc0_router_verify_call_batch_dev(zkv_ctx* c, size_t n, cons
 }
 ZKV_EXPORT int zkv_risc0_router_verify_call_batch(zkv_ctx* c, size_t n, const uint8_t* method, const uint8_t* seal_blob, const uint64_t* seal_off,
                                                   const uint8_t* in_a, const uint8_t* in_b, uint8_t* status, uint8_t* recv) {
-    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER || c->rz_set) return ZKV_ERR_WRONG_CTX;
     if (n && (!seal_blob || !seal_off || !in_a || !in_b || !status)) return ZKV_ERR_INVALID_ARG;
     if (!n) return ZKV_OK;
     return router_host_batch(c, n, seal_blob, seal_off, in_a, in_b, status, recv, method);
@@ -2832,7 +2854,7 @@ static int run_router_wire(zkv_ctx* c, size_t n, const uint8_t* d_cd, const uint
 }
 ZKV_EXPORT int zkv_risc0_router_eth_call_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_calldata, const uint64_t* d_calldata_off, uint64_t calldata_bytes,
                                                    uint8_t* d_status, uint8_t* d_recv, uint8_t* d_call_kind, void* stream) {
-    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER || c->rz_set) return ZKV_ERR_WRONG_CTX;
     if (n && (!d_calldata || !d_calldata_off || !d_status)) return ZKV_ERR_INVALID_ARG;
     if (!n) return ZKV_OK;
     if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES) return ZKV_ERR_INVALID_ARG;
@@ -2843,7 +2865,7 @@ ZKV_EXPORT int zkv_risc0_router_eth_call_batch_dev(zkv_ctx* c, size_t n, const u
 }
 ZKV_EXPORT int zkv_risc0_router_eth_call_batch(zkv_ctx* c, size_t n, const uint8_t* blob, const uint64_t* off, uint8_t* reverted, uint8_t* returndata,
                                                uint32_t* returndata_len, uint8_t* status) {
-    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER || c->rz_set) return ZKV_ERR_WRONG_CTX;
     if (n && (!blob || !off || !reverted || !returndata || !returndata_len)) return ZKV_ERR_INVALID_ARG;
     if (!n) return ZKV_OK;
     if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES || !offsets_ok(off, n)) return ZKV_ERR_INVALID_ARG;
@@ -2875,7 +2897,7 @@ ZKV_EXPORT int zkv_risc0_router_eth_call_batch(zkv_ctx* c, size_t n, const uint8
     return ZKV_OK;
 }
 ZKV_EXPORT int zkv_risc0_router_last_call_counts(zkv_ctx* c, uint64_t* out) {
-    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER || c->rz_set) return ZKV_ERR_WRONG_CTX;
     if (!out) return ZKV_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     const size_t R = c->rz_counts.size();
@@ -4539,5 +4561,198 @@ ZKV_EXPORT int zkv_risc0_setincl_seal_decode(const zkv_ctx* c, const uint8_t* se
     for (uint64_t q = len; q < padded; q++) if (r[32 + q]) return ZKV_OK;    // clean padding
     *status = ZKV_STATUS_OK;
     *path_at = 4 + 128; *path_len = (size_t)k; *root_seal_at = (size_t)(4 + 128 + 32 * k + 32); *root_seal_len = (size_t)len;
+    return ZKV_OK;
+}
+
+// ------------------------------------------------------------------ RISC Zero router with a set route (zkv_risc0_router_set.h)
+// No reference counterpart: parity unpinned.  A set-inclusion seal is decoded on the device (k_rzrouter_set.hip), its root seal is
+// verified by the router itself: the root jobs are 260-byte rows that go through run_router as a batch of their own.
+ZKV_EXPORT zkv_ctx* zkv_risc0_router_create_with_set(size_t n_builtin, const uint8_t* control_roots, const uint8_t* bn254_control_ids, size_t n_keyed,
+                                                     const uint8_t* const* vk_words, const uint8_t* keyed_control_roots, const uint8_t* keyed_control_ids,
+                                                     const uint8_t set_builder_image_id[32], int device) {
+    if (!set_builder_image_id || n_builtin > ZKV_RISC0_ROUTER_MAX_ROUTES || n_keyed > ZKV_RISC0_ROUTER_MAX_ROUTES ||
+        n_builtin + n_keyed + 1 > ZKV_RISC0_ROUTER_MAX_ROUTES) return nullptr;      // the set route counts
+    zkv_ctx* c = zkv_risc0_router_create(n_builtin, control_roots, bn254_control_ids, n_keyed, vk_words, keyed_control_roots, keyed_control_ids, device);
+    if (!c) return nullptr;
+    memcpy(c->si_id, set_builder_image_id, 32);
+    setincl_set_selector(set_builder_image_id, c->si_set_sel);
+    for (const uint32_t v : c->gw_sel) if (v == be32_of(c->si_set_sel)) { zkv_ctx_destroy(c); return nullptr; }
+    c->rz_set = true;
+    c->rzs_counts.assign(c->gw_sel.size() + 3, 0);
+    return c;
+}
+ZKV_EXPORT int zkv_risc0_router_set_selector(const zkv_ctx* c, uint8_t out[4]) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER || !c->rz_set) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    memcpy(out, c->si_set_sel, 4);
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_risc0_router_set_has_root(zkv_ctx* c, const uint8_t root[32]) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER || !c->rz_set) return ZKV_ERR_WRONG_CTX;
+    if (!root) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    bool found;
+    (void)setincl_find(c, root, &found);
+    return found ? 1 : 0;
+}
+ZKV_EXPORT int zkv_risc0_router_set_submit_root(zkv_ctx* c, const uint8_t root[32], const uint8_t* seal, size_t seal_len, uint8_t* status, uint8_t recv[4]) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER || !c->rz_set) return ZKV_ERR_WRONG_CTX;
+    if (!root || !status || (!seal && seal_len)) return ZKV_ERR_INVALID_ARG;
+    uint8_t msg[64], jd[32], rv[4] = {0, 0, 0, 0}, st = ZKV_STATUS_VERIFICATION_FAILED;
+    memcpy(msg, c->si_id, 32); memcpy(msg + 32, root, 32);
+    host::sha256_host(msg, 64, jd);
+    const int rc = zkv_risc0_router_verify(c, seal, seal_len, c->si_id, jd, &st, rv);      // V is the router
+    if (rc != ZKV_OK) return rc;
+    *status = st;
+    if (recv) memcpy(recv, rv, 4);
+    if (st != ZKV_STATUS_OK) return ZKV_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    bool found;
+    const size_t at = setincl_find(c, root, &found);
+    if (found) return ZKV_OK;
+    if (c->si_roots.size() / 32 >= ZKV_SETINCL_MAX_ROOTS) return ZKV_ERR_INVALID_ARG;
+    try { c->si_roots.insert(c->si_roots.begin() + 32 * at, root, root + 32); } catch (const std::bad_alloc&) { return ZKV_ERR_OOM; }
+    c->si_dirty = true;
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_risc0_router_set_last_counts(zkv_ctx* c, uint64_t out[4]) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER || !c->rz_set) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    for (int k = 0; k < 4; k++) out[k] = c->rzs_last[k];
+    return ZKV_OK;
+}
+
+// Everything device-resident, ragged seals; the caller holds c->mu and has initialised the device.  Per chunk of 2^20 seals: the front
+// and identity kernels, the hash and section 16's grouping; the chunk's four counters come back with the next synchronisation -- for the
+// first chunk that is run_router's own (the caller's seals are partitioned once, for the whole call; a set seal is a seal of an unknown
+// selector there and is answered again by the scatter, behind it in the stream), for a later chunk one of its own.  The root jobs then
+// run through run_router as a batch of 260-byte rows with true lengths.  Two synchronisations for a call of one chunk that has root
+// jobs: the direct seals' route counts (with the job count), the jobs' route counts.
+// d_diag (diagnostic): stop behind the identity kernel of the one chunk and write every claim's representative.
+static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64_t* d_seal_off, uint64_t seal_bytes, const uint8_t* d_a, const uint8_t* d_b,
+                          uint8_t* d_status, uint8_t* d_recv, hipStream_t s, uint32_t fp_mask, uint32_t* d_diag) {
+    int rc;
+    const size_t cap = n < SETINCL_CHUNK ? n : SETINCL_CHUNK, R = c->gw_sel.size();
+    size_t table = 64;
+    while (table < 2 * cap) table <<= 1;
+    const size_t need[RZS_STORED - RZS_REC + 1] = {sizeof(RzsRec) * cap, 4 * table, 4 * cap, 4 * table, 4 * table, 4 * cap, 4 * cap, cap, 16, 32 * cap,
+                                                   (size_t)32 * ZKV_SETINCL_MAX_ROOTS};
+    for (int k = 0; k <= RZS_STORED - RZS_REC; k++) if ((rc = c->mx[RZS_REC + k].grow(need[k])) != ZKV_OK) return rc;
+    if (c->si_dirty) {                                   // a root was submitted since the last call: nothing of this context is in flight after the wait
+        HIP_TRY(hipDeviceSynchronize());
+        if (!c->si_roots.empty()) HIP_TRY(hipMemcpy(c->mx[RZS_STORED], c->si_roots.data(), c->si_roots.size(), hipMemcpyHostToDevice));
+        c->si_dirty = false;
+    }
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    uint32_t* cnt = c->mx[RZS_CNT].as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(cnt, 0, 16, s));
+    uint32_t seen[4] = {0, 0, 0, 0};
+    uint64_t jobs = 0;
+    std::vector<uint64_t> direct;
+    for (size_t base = 0; base < n; base += cap) {
+        const size_t mc = n - base < cap ? n - base : cap;
+        SetinclChunk ch;
+        memset(&ch, 0, sizeof ch);
+        ch.n = (uint32_t)mc; ch.m = (uint32_t)table; ch.n_stored = (uint32_t)(c->si_roots.size() / 32);
+        ch.in_a = d_a + 32 * base; ch.in_b = d_b ? d_b + 32 * base : nullptr;
+        ch.root_idx = c->mx[RZS_RIDX].as<const uint32_t>(); ch.stored = c->mx[RZS_STORED];
+        for (int q = 0; q < 8; q++) ch.id_be[q] = be32_of(c->si_id + 4 * q);
+        ch.roots = c->mx[RZS_ROOTS].as<uint32_t>(); ch.rep = c->mx[RZS_REP].as<uint32_t>(); ch.gslot = c->mx[RZS_GSLOT].as<uint32_t>();
+        ch.claim_job = c->mx[RZS_CJOB].as<uint32_t>(); ch.job_claim = c->mx[RZS_JCLAIM].as<uint32_t>(); ch.counters = cnt;
+        ch.status = d_status ? d_status + base : nullptr; ch.recv = d_recv ? d_recv + 4 * base : nullptr;
+        RzsArgs a;
+        memset(&a, 0, sizeof a);
+        a.seals = d_seals; a.seal_off = d_seal_off + base; a.seal_bytes = seal_bytes;
+        a.set_sel = be32_of(c->si_set_sel); a.table = (uint32_t)table; a.fp_mask = fp_mask;
+        a.rec = c->mx[RZS_REC].as<RzsRec>(); a.owner = c->mx[RZS_OWNER].as<uint32_t>(); a.root_idx = c->mx[RZS_RIDX].as<uint32_t>(); a.ans = c->mx[RZS_ANS];
+        HIP_TRY(hipMemsetAsync(a.owner, 0xFF, 4 * table, s));
+        HIP_TRY(hipMemsetAsync(ch.rep, 0xFF, 4 * table, s));
+        HIP_TRY(hipMemsetAsync(cnt, 0, 4, s));
+        launch_rzset_front(ch, a, s);
+        if (d_diag) {
+            launch_rzset_reps(ch, a, d_diag, s);
+            HIP_TRY(hipGetLastError());
+            return mark_done(c, s);
+        }
+        launch_rzset_hash(ch, a, c->consts, s);
+        launch_setincl_group(ch, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(seen, cnt, sizeof seen, hipMemcpyDeviceToHost, s));
+        if (base == 0) {
+            rc = run_router(c, n, d_seals, d_seal_off, seal_bytes, d_a, d_b, d_status, d_recv, s);
+            if (rc != ZKV_OK) { (void)hipStreamSynchronize(s); return rc; }      // (the copy into `seen` may still be in flight)
+            direct = c->rz_counts;
+        } else HIP_TRY(hipStreamSynchronize(s));
+        const uint32_t nj = seen[0];
+        if (nj > mc) return ZKV_ERR_HIP;
+        jobs += nj;
+        SetinclJobs jb;
+        memset(&jb, 0, sizeof jb);
+        jb.n_jobs = nj;
+        if (nj) {
+            // (growing frees the old buffer, which waits for the device: the previous chunk's scatter has read its rows by then)
+            const size_t jneed[6] = {(size_t)260 * nj, (size_t)4 * nj, (size_t)32 * nj, (size_t)32 * nj, nj, (size_t)4 * nj};
+            for (int k = 0; k < 6; k++) if ((rc = c->mx[RZS_ROWS + k].grow(jneed[k])) != ZKV_OK) return rc;
+            jb.rows = c->mx[RZS_ROWS]; jb.lens = c->mx[RZS_LENS].as<uint32_t>(); jb.ids = c->mx[RZS_IDS]; jb.jds = c->mx[RZS_JDS];
+            jb.st = c->mx[RZS_JST]; jb.rv = c->mx[RZS_JRV];
+            launch_rzset_jobs(ch, a, jb, s);
+            HIP_TRY(hipGetLastError());
+            // root jobs are `verify` calls of the router on (S, ID, sha256(ID || root)): the rows enter its partition with their true lengths
+            if ((rc = run_router(c, nj, jb.rows, nullptr, 0, jb.ids, jb.jds, c->mx[RZS_JST], c->mx[RZS_JRV], s, nullptr, jb.lens)) != ZKV_OK) return rc;
+        }
+        launch_rzset_scatter(ch, a, jb, s);
+        HIP_TRY(hipGetLastError());
+    }
+    if ((rc = mark_done(c, s)) != ZKV_OK) return rc;
+    // the counts of the call: the Groth16 routes' are the caller's direct seals (not the root jobs); the set seals were seals of an
+    // unknown selector to the partition
+    if (direct.size() != R + 2 || direct[R] < seen[2]) return ZKV_ERR_HIP;
+    c->rz_counts = direct;
+    for (size_t r = 0; r < R; r++) c->rzs_counts[r] = direct[r];
+    c->rzs_counts[R] = seen[2]; c->rzs_counts[R + 1] = direct[R] - seen[2]; c->rzs_counts[R + 2] = direct[R + 1];
+    c->rzs_last[0] = seen[2]; c->rzs_last[1] = seen[3]; c->rzs_last[2] = jobs; c->rzs_last[3] = seen[1];
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_risc0_router_verify_ragged_dev(zkv_ctx* c, size_t n, const uint8_t* d_seal_blob, const uint64_t* d_seal_off, uint64_t blob_bytes,
+                                                  const uint8_t* d_image_ids, const uint8_t* d_journal_digests, uint8_t* d_status, uint8_t* d_recv, void* stream) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_seal_off || !d_image_ids || !d_status || (blob_bytes && !d_seal_blob))) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->rz_set) return run_router_set(c, n, d_seal_blob, d_seal_off, blob_bytes, d_image_ids, d_journal_digests, d_status, d_recv, s, 0xFFFFFFFFu, nullptr);
+    return run_router(c, n, d_seal_blob, d_seal_off, blob_bytes, d_image_ids, d_journal_digests, d_status, d_recv, s);
+}
+// Test only: the front and identity kernels alone on host buffers, the fingerprint ANDed with fp_mask (0: every claim starts at slot 0
+// and probes linearly).  out_rep[i]: the representative of claim i's root seal, 0xFFFFFFFF for a seal that names none.
+ZKV_EXPORT int zkv_diag_rzset_groups(zkv_ctx* c, size_t n, const uint8_t* seal_blob, const uint64_t* seal_off, size_t blob_shift, uint32_t fp_mask,
+                                     uint32_t* out_rep) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER || !c->rz_set) return ZKV_ERR_WRONG_CTX;
+    if (n && (!seal_blob || !seal_off || !out_rep)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > SETINCL_CHUNK || blob_shift > 31 || !offsets_ok(seal_off, n)) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    const uint64_t o0 = seal_off[0], bytes = seal_off[n] - o0;
+    std::vector<uint64_t> so;
+    try { so.assign(seal_off, seal_off + n + 1); } catch (const std::bad_alloc&) { return ZKV_ERR_OOM; }
+    for (auto& v : so) v -= o0;
+    if ((rc = c->mx[RZ_H_SEALS].grow((size_t)bytes + 256 + 32)) != ZKV_OK || (rc = c->mx[RZ_H_OFF].grow(8 * (n + 1))) != ZKV_OK ||
+        (rc = c->mx[RZS_DIAG].grow(4 * n)) != ZKV_OK) return rc;
+    hipStream_t s = c->stream;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    uint8_t* d_blob = (uint8_t*)(((uintptr_t)c->mx[RZ_H_SEALS].as<uint8_t>() + 255u) & ~(uintptr_t)255u) + blob_shift;
+    if (bytes) HIP_TRY(hipMemcpyAsync(d_blob, seal_blob + o0, (size_t)bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_OFF], so.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));                    // the staging vector is pageable host memory
+    if ((rc = run_router_set(c, n, d_blob, c->mx[RZ_H_OFF].as<const uint64_t>(), bytes, nullptr, nullptr, nullptr, nullptr, s, fp_mask,
+                             c->mx[RZS_DIAG].as<uint32_t>())) != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out_rep, c->mx[RZS_DIAG], 4 * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return ZKV_OK;
 }

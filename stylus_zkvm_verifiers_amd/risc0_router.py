@@ -146,6 +146,12 @@ class RiscZeroRouter:
         _lib.check(self._L.zkv_risc0_router_verify_batch_dev(self._h, n, d_seals, d_image_ids, d_journal_digests or None, d_status,
                                                              d_recv or None, stream or None), 'zkv_risc0_router_verify_batch_dev')
 
+    def verify_ragged_dev(self, n, d_seal_blob, d_seal_off, blob_bytes, d_image_ids, d_journal_digests, d_status, d_recv=0, stream=0):
+        """verify_batch_dev on seals of any length: a device blob (any alignment) and its n + 1 uint64 offsets, none followed beyond
+        blob_bytes (include/zkv_risc0_router_set.h, risc0_router_set.py)."""
+        from . import risc0_router_set as rs
+        rs.verify_ragged_dev(self._h, n, d_seal_blob, d_seal_off, blob_bytes, d_image_ids, d_journal_digests, d_status, d_recv, stream)
+
     def last_route_counts(self):
         """Seals of the most recent call per route, then selector unknown, then shorter than 4 bytes."""
         k = self._L.zkv_risc0_router_route_count(self._h)
