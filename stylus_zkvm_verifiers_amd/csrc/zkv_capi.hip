@@ -50,9 +50,11 @@ using namespace zkv;
 #define ZKV_EXPORT extern "C" __attribute__((visibility("default")))
 
 // ---- Device state of a context.  OWNERSHIP: every device allocation, event and stream of a context is a DevBuf / DevEvent / DevStream
-// (zkv_devmem.h) in one of the three structs below, which hold nothing but such owners, the plain views kernels take by value
+// (zkv_devmem.h) in one of the structs below, which hold nothing but such owners, the plain views kernels take by value
 // (Workspace, GtTab, Msm16: filled from the owners beside them) and the sizes and flags that describe them, all with default member
 // initialisers.  Releasing a group is assigning it a default-constructed value; a field added here needs no other edit to be released.
+// ChunkMem and AggMem are sized as a whole.  The families' structs behind them (one member of CtxDevice each; DESIGN.md "Growth": which
+// kind of context uses which) are staging: a call grows what it is about to use, each size beside its buffer's name (grow_all).
 //
 // Per-chunk buffers, sized by ctx_reserve() for ws.cap proofs in flight.
 struct ChunkMem {
@@ -82,6 +84,52 @@ struct AggMem {
     Workspace ws3 = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     size_t agg_cap = 0;                                        // proofs the buffers above have room for (0: none, the chunk takes the ordinary kernels)
 };
+// What the three demultiplexers (mixed batches, SP1 gateway, RISC Zero router) all keep: per-block counts, per-column totals, every
+// proof's position, the proof of every slot; the compact records, their lengths and first inputs; the slots' statuses and receive words.
+struct DemuxMem { DevBuf<uint32_t> cnt, totals, pos, idx, len; DevBuf<uint8_t> recs, a, st, rv; };
+// Mixed batches (run_mixed): the compact second inputs, public-value records and method row; h_*: the host call's staging.
+struct MixedMem : DemuxMem {
+    DevBuf<uint8_t> b, kind; DevBuf<uint64_t> pvoff; DevBuf<uint32_t> pvlen;
+    DevBuf<uint8_t> h_vm, h_seals, h_a, h_b, h_st, h_rv, h_method; DevBuf<uint64_t> h_soff, h_boff;
+};
+// SP1 gateway (run_gateway): the compact public-value records and, for the keyed group, the key of every group slot; h_*: the host
+// calls' staging (h_cd, h_cdoff: calldata); w_*: the rows the calldata decoder writes (run_gateway_wire).
+struct GatewayMem : DemuxMem {
+    DevBuf<uint64_t> pvoff; DevBuf<uint32_t> pvlen, skey;
+    DevBuf<uint8_t> h_vk, h_pv, h_proof, h_st, h_rv, h_cd; DevBuf<uint64_t> h_pvoff, h_poff, h_cdoff;
+    DevBuf<uint8_t> w_vk, w_bad, w_arena; DevBuf<uint64_t> w_pvat, w_pat; DevBuf<uint32_t> w_pvlen, w_plen;
+};
+// Section 16's grouping rows, of a set-inclusion context and of a router's set route alike: per claim the root, per root seal its
+// representative and job slot, the claim <-> job maps, the four counters, the submitted roots; then the root jobs' rows (records with
+// their lengths and inputs, or (keyed inner verifier) proofs and signals with the verdicts known beforehand) and their statuses.
+struct SetGroupMem {
+    DevBuf<uint32_t> roots, rep, gslot, claim_job, job_claim, cnt; DevBuf<uint8_t> stored;
+    DevBuf<uint8_t> rows, ids, jds, proofs, signals, pre, pre_recv, jst, jrv; DevBuf<uint32_t> lens;
+};
+// RISC Zero router (run_router): per-instance totals, the compact second inputs, instance and method rows, every group slot's key, the
+// keyed routes' constants; h_*: the host calls' staging (a calldata batch is decoded into h_a, h_b, h_method); w_*: a calldata batch's
+// decoded slots, true lengths and call kinds; s_*, grp: the set route -- claim records, root-seal table, root indices, answers, section 16.
+struct RouterMem : DemuxMem {
+    DevBuf<uint32_t> itot, inst, skey; DevBuf<uint8_t> b, kind; DevBuf<RzrRoute> routes;
+    DevBuf<uint8_t> h_seals, h_a, h_b, h_st, h_rv, h_method; DevBuf<uint64_t> h_off;
+    DevBuf<uint8_t> w_seals, w_ck; DevBuf<uint32_t> w_len;
+    DevBuf<RzsRec> s_rec; DevBuf<uint32_t> s_owner, s_ridx, s_diag; DevBuf<uint8_t> s_ans; SetGroupMem grp;
+};
+// Key sets, Groth16 and PLONK (set_partition .. set_agg_plan): per-block counts, per-key totals, block offsets, every proof's position,
+// the proof and key of every slot, the aggregate chunks' pseudo-proof maps; the keys' slot starts (behind the aggregate layout's map).
+struct KeySetMem { DevBuf<uint32_t> cnt, totals, off, pos, idx, skey, amap; DevBuf<uint64_t> start; };
+// Set-inclusion contexts (run_setincl): section 16's rows; h_*: the host call's staging; diag: zkv_diag_setincl_roots.
+struct SetInclMem : SetGroupMem { DevBuf<uint8_t> h_a, h_b, h_paths, h_seals, h_st, h_rv, diag; DevBuf<uint32_t> h_poff, h_ridx, h_slen; };
+// Host-buffer batches (run_host_batch): whole-batch staging in HBM, filled by segments on copy_stream while the previous one is verified.
+struct HostBatchMem { DevBuf<uint8_t> seals, in_a, in_b, pv; DevBuf<uint64_t> off, pv_off; };
+// Host-buffer calls on a key set: the caller's keys, proofs and signal / public-input rows, the verdicts; the vk_x call's points.
+struct KeySetHostMem { DevBuf<uint32_t> key; DevBuf<uint8_t> proofs, rows, verdicts, vk_x; };
+// Grows each buffer to the byte count behind it, in the order given; the first failure ends it.
+static int grow_all() { return ZKV_OK; }
+template <class T, class... Rest> static int grow_all(DevBuf<T>& buf, size_t bytes, Rest&&... rest) {
+    const int rc = buf.grow(bytes);
+    return rc != ZKV_OK ? rc : grow_all(rest...);
+}
 // Everything created lazily for the device (on the first compute call).  ctx_free_device() resets it as a whole.  Buffers come first,
 // then events, then streams: the order in which a reset lets them go.
 struct CtxDevice : ChunkMem, AggMem {
@@ -108,12 +156,9 @@ struct CtxDevice : ChunkMem, AggMem {
     bool agg_key_ok = false;
     // staging: proofs and public values of a chunk; calldata blobs of the wire layer; whole-batch statuses and receive words
     DevBuf<> d_blob, d_pv, d_cd[2], d_st_all, d_rv_all;
-    // host-buffer batches (run_host_batch): whole-batch staging in HBM, filled segment by segment on copy_stream while the previous
-    // segment is verified: seals, seal offsets, in_a, in_b, public values, pv offsets
-    DevBuf<> hb[6];
-    // demultiplexing, routing and set-inclusion buffers (enums MX_*, GW_*, GWW_*, RZ_*, RZW_*, RZS_*, KS_*, SI_*)
-    static constexpr size_t MX_SLOTS = 48;
-    DevBuf<> mx[MX_SLOTS];
+    // the families' staging: host-buffer batches, key-set host calls; demultiplexing, routing, key-set and set-inclusion buffers
+    HostBatchMem m_host; KeySetHostMem m_kshost;
+    MixedMem m_mixed; GatewayMem m_gw; RouterMem m_rz; KeySetMem m_ks; SetInclMem m_si;
     DevEvent ev_fork, ev_join;                                 // small chunks: the G2 subgroup check runs beside the MSM (stream `side`)
     DevEvent ev_copied[2], ev_decoded[2];                      // wire layer: H2D of calldata chunk k+1 overlaps the kernels of chunk k
     DevEvent ev[6], ev_wire[2];
@@ -154,7 +199,7 @@ struct zkv_ctx : CtxDevice {
     // ZKV_VM_PLONK_SET (zkv_plonk_set.h): every key's parsed header and points, its two G2 points (256 bytes per key in ps_g2), and the
     // largest nb_public and n_c (the row strides).  On the device: the keys' PlonkKey array in d_pkey, one VkTables per key in d_gs_tab
     // with its GsetKey in d_gs_key (what the Groth16 sets' Miller kernels read), and a validity word per key in d_ps_ok.  A call reuses
-    // the Groth16 sets' partition buffers (gs_totals, gs_start, mx[KS_CNT..KS_SKEY]).
+    // the Groth16 sets' partition buffers (gs_totals, gs_start, m_ks).
     std::vector<PlonkKeyRaw> ps_raw; std::vector<uint8_t> ps_g2; uint32_t ps_nb_max = 0, ps_nc_max = 0;
     // aggregate check on a PLONK set (zkv_plonk_set_agg.h): every key's SRS class and each class's first key (formed at creation), which
     // classes can take the check (read back the first time a call wants it), and per call every class's region (pset_agg_choose)
@@ -221,8 +266,8 @@ struct zkv_ctx : CtxDevice {
     uint64_t gw_counts[GW_COLS] = {0};
     // ZKV_VM_RISC0_SETINCL (zkv_risc0_set_inclusion.h): kid[0] is the inner root verifier V -- a RISC Zero context, or (si_keyed) a generic
     // Groth16 context of the caller's key in the RISC Zero convention, whose parameters then sit in control_root_0 / _1, control_id and
-    // si_root_sel.  si_roots: the submitted roots, 32 bytes each, ascending; their device copy (mx[SI_STORED]) is refreshed by the next
-    // batch call after a submission (si_dirty).  mx[] holds the workspace and the staging of host-buffer calls (enum SI_*).
+    // si_root_sel.  si_roots: the submitted roots, 32 bytes each, ascending; their device copy (m_si.stored) is refreshed by the next
+    // batch call after a submission (si_dirty).  m_si holds the workspace and the staging of host-buffer calls.
     bool si_keyed = false, si_dirty = false;
     uint8_t si_id[32] = {0}, si_root_sel[4] = {0}, si_set_sel[4] = {0};
     std::vector<uint8_t> si_roots;
@@ -977,10 +1022,11 @@ static int run_host_batch(zkv_ctx* c, size_t n, const uint8_t* blob, const uint6
         const uint64_t s0 = off[p0], sbytes = off[p0 + pn] - s0;
         const uint64_t v0 = sp1 ? pv_off[p0] : 0, vbytes = sp1 ? pv_off[p0 + pn] - v0 : 0;
         // growing a buffer frees the old one, which synchronises the device: everything is sized before the first copy
-        if ((rc = c->hb[0].grow((size_t)sbytes + 8)) != ZKV_OK || (rc = c->hb[1].grow(8 * (pn + 1))) != ZKV_OK ||
-            (rc = c->hb[2].grow(32 * pn)) != ZKV_OK || (in_b && (rc = c->hb[3].grow(32 * pn)) != ZKV_OK) ||
-            (sp1 && ((rc = c->hb[4].grow((size_t)vbytes + 8)) != ZKV_OK || (rc = c->hb[5].grow(8 * (pn + 1))) != ZKV_OK)) ||
-            (rc = c->d_st_all.grow(pn)) != ZKV_OK || (rc = c->d_rv_all.grow(4 * pn)) != ZKV_OK) return rc;
+        HostBatchMem& hb = c->m_host;
+        if ((rc = grow_all(hb.seals, (size_t)sbytes + 8, hb.off, 8 * (pn + 1), hb.in_a, 32 * pn)) != ZKV_OK ||
+            (in_b && (rc = hb.in_b.grow(32 * pn)) != ZKV_OK) ||
+            (sp1 && (rc = grow_all(hb.pv, (size_t)vbytes + 8, hb.pv_off, 8 * (pn + 1))) != ZKV_OK) ||
+            (rc = grow_all(c->d_st_all, pn, c->d_rv_all, 4 * pn)) != ZKV_OK) return rc;
         // offsets relative to the pass (the caller's array is used as it is when the pass starts at offset 0)
         const uint64_t* o = off + p0; const uint64_t* po = sp1 ? pv_off + p0 : nullptr;
         if (s0) { rel.resize(pn + 1); for (size_t i = 0; i <= pn; i++) rel[i] = off[p0 + i] - s0; o = rel.data(); }
@@ -996,23 +1042,23 @@ static int run_host_batch(zkv_ctx* c, size_t n, const uint8_t* blob, const uint6
             // alternating runs on one box)
             const size_t m = k == 0 ? first : (pn - base < cap ? pn - base : cap);
             hipStream_t cs = c->copy_stream;
-            HIP_TRY(hipMemcpyAsync(c->hb[1] + 8 * base, o + base, 8 * (m + 1), hipMemcpyHostToDevice, cs));
-            if (o[base + m] > o[base]) HIP_TRY(hipMemcpyAsync(c->hb[0] + o[base], blob + s0 + o[base], (size_t)(o[base + m] - o[base]), hipMemcpyHostToDevice, cs));
-            HIP_TRY(hipMemcpyAsync(c->hb[2] + 32 * base, in_a + 32 * (p0 + base), 32 * m, hipMemcpyHostToDevice, cs));
-            if (in_b) HIP_TRY(hipMemcpyAsync(c->hb[3] + 32 * base, in_b + 32 * (p0 + base), 32 * m, hipMemcpyHostToDevice, cs));
+            HIP_TRY(hipMemcpyAsync(hb.off + base, o + base, 8 * (m + 1), hipMemcpyHostToDevice, cs));
+            if (o[base + m] > o[base]) HIP_TRY(hipMemcpyAsync(hb.seals + o[base], blob + s0 + o[base], (size_t)(o[base + m] - o[base]), hipMemcpyHostToDevice, cs));
+            HIP_TRY(hipMemcpyAsync(hb.in_a + 32 * base, in_a + 32 * (p0 + base), 32 * m, hipMemcpyHostToDevice, cs));
+            if (in_b) HIP_TRY(hipMemcpyAsync(hb.in_b + 32 * base, in_b + 32 * (p0 + base), 32 * m, hipMemcpyHostToDevice, cs));
             if (sp1) {
-                HIP_TRY(hipMemcpyAsync(c->hb[5] + 8 * base, po + base, 8 * (m + 1), hipMemcpyHostToDevice, cs));
-                if (po[base + m] > po[base]) HIP_TRY(hipMemcpyAsync(c->hb[4] + po[base], pv_blob + v0 + po[base], (size_t)(po[base + m] - po[base]), hipMemcpyHostToDevice, cs));
+                HIP_TRY(hipMemcpyAsync(hb.pv_off + base, po + base, 8 * (m + 1), hipMemcpyHostToDevice, cs));
+                if (po[base + m] > po[base]) HIP_TRY(hipMemcpyAsync(hb.pv + po[base], pv_blob + v0 + po[base], (size_t)(po[base + m] - po[base]), hipMemcpyHostToDevice, cs));
             }
             HIP_TRY(hipEventRecord(c->ev_seg[k & 1], cs));
             mark(cs);
             HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_seg[k & 1], 0));
             PrepArgs a;
             memset(&a, 0, sizeof a);
-            a.n = m; a.blob = c->hb[0]; a.off = c->hb[1].as<const uint64_t>() + base; a.stride = 0;
-            a.in32_a = c->hb[2] + 32 * base; a.in32_b = in_b ? c->hb[3] + 32 * base : nullptr;
+            a.n = m; a.blob = hb.seals; a.off = hb.off + base; a.stride = 0;
+            a.in32_a = hb.in_a + 32 * base; a.in32_b = in_b ? hb.in_b + 32 * base : nullptr;
             if (sp1) {
-                a.pv_blob = c->hb[4]; a.pv_off = c->hb[5].as<const uint64_t>() + base;
+                a.pv_blob = hb.pv; a.pv_off = hb.pv_off + base;
                 a.selector_be = be32_of(c->vm == ZKV_VM_SP1_PLONK ? c->plonk_hash : host::SP1_VERIFIER_HASH);
                 a.force_fail = c->vm == ZKV_VM_SP1_PLONK && c->vk_invalid ? 1u : 0u;
             } else {
@@ -1329,6 +1375,13 @@ ZKV_EXPORT zkv_ctx* zkv_mixed_ctx_create_multi(const uint8_t control_root[32], c
     if (!control_root || !bn254_control_id) return nullptr;
     return create_multi(device_mask, [&](int d) { return zkv_mixed_ctx_create(control_root, bn254_control_id, d); });
 }
+// The end of a host-buffer call: n statuses and (recv != nullptr) received selectors from d_st / d_rv, and the call's wait.
+static int return_to_host(const DevBuf<uint8_t>& d_st, const DevBuf<uint8_t>& d_rv, size_t n, uint8_t* status, uint8_t* recv, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, s));
+    if (recv) HIP_TRY(hipMemcpyAsync(recv, d_rv, 4 * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return ZKV_OK;
+}
 
 // ------------------------------------------------------------------ mixed batches: per-proof VMType (common/types.rs:24-26)
 ZKV_EXPORT zkv_ctx* zkv_mixed_ctx_create(const uint8_t control_root[32], const uint8_t bn254_control_id[32], int device) {
@@ -1345,8 +1398,6 @@ ZKV_EXPORT zkv_ctx* zkv_mixed_ctx_create(const uint8_t control_root[32], const u
 ZKV_EXPORT zkv_ctx* zkv_mixed_ctx_risc0(zkv_ctx* c) { if (is_sharded(c)) c = c->shards[0]; return c && c->vm == ZKV_VM_MIXED ? c->kid[0] : nullptr; }
 ZKV_EXPORT zkv_ctx* zkv_mixed_ctx_sp1(zkv_ctx* c) { if (is_sharded(c)) c = c->shards[0]; return c && c->vm == ZKV_VM_MIXED ? c->kid[1] : nullptr; }
 
-enum { MX_CNT = 0, MX_TOT, MX_POS, MX_IDX, MX_SEALS, MX_LEN, MX_A, MX_B, MX_PVOFF, MX_PVLEN, MX_ST, MX_RV, MX_KIND,
-       MX_H_VM, MX_H_SEALS, MX_H_SOFF, MX_H_A, MX_H_B, MX_H_BOFF, MX_H_ST, MX_H_RV, MX_H_METHOD };
 // Everything device-resident; `seal_off` / `b_off` select the ragged layout, otherwise fixed strides; `d_method` (may be null: all
 // ZKV_METHOD_VERIFY) is the per-proof method.  Synchronises `s` once, after the partition, to learn the two sub-batch sizes.
 static int run_mixed(zkv_ctx* c, size_t n, const uint8_t* d_vm, const uint8_t* d_method, const uint8_t* d_seals, const uint64_t* d_seal_off, uint32_t seal_stride,
@@ -1354,26 +1405,26 @@ static int run_mixed(zkv_ctx* c, size_t n, const uint8_t* d_vm, const uint8_t* d
                      uint8_t* d_status, uint8_t* d_recv, hipStream_t s) {
     int rc;
     const size_t blocks = (n + 255) / 256;
-    const size_t need[13] = {8 * blocks, 8, 4 * n, 4 * n, (size_t)ZKV_SEAL_BYTES * n, 4 * n, 32 * n, 32 * n, 8 * n, 4 * n, n, 4 * n, n};
-    for (int k = 0; k < 13; k++) if ((rc = c->mx[k].grow(need[k])) != ZKV_OK) return rc;
+    MixedMem& mm = c->m_mixed;
+    if ((rc = grow_all(mm.cnt, 8 * blocks, mm.totals, 8, mm.pos, 4 * n, mm.idx, 4 * n, mm.recs, (size_t)ZKV_SEAL_BYTES * n, mm.len, 4 * n, mm.a, 32 * n,
+                       mm.b, 32 * n, mm.pvoff, 8 * n, mm.pvlen, 4 * n, mm.st, n, mm.rv, 4 * n, mm.kind, n)) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     MixedArgs a;
     memset(&a, 0, sizeof a);
     a.n = n; a.vm = d_vm; a.method = d_method; a.seals = d_seals; a.seal_off = d_seal_off; a.seal_stride = seal_stride;
     a.in_a = d_a; a.in_b = d_b; a.b_off = d_b_off; a.b_stride = b_stride; a.pv_len = pv_len;
-    a.cnt = c->mx[MX_CNT].as<uint32_t>(); a.totals = c->mx[MX_TOT].as<uint32_t>(); a.pos = c->mx[MX_POS].as<uint32_t>(); a.idx = c->mx[MX_IDX].as<uint32_t>();
-    a.c_seals = c->mx[MX_SEALS]; a.c_len = c->mx[MX_LEN].as<uint32_t>(); a.c_a = c->mx[MX_A]; a.c_b = c->mx[MX_B];
-    a.c_pvoff = c->mx[MX_PVOFF].as<uint64_t>(); a.c_pvlen = c->mx[MX_PVLEN].as<uint32_t>(); a.c_kind = c->mx[MX_KIND];
+    a.cnt = mm.cnt; a.totals = mm.totals; a.pos = mm.pos; a.idx = mm.idx; a.c_seals = mm.recs; a.c_len = mm.len; a.c_a = mm.a; a.c_b = mm.b;
+    a.c_pvoff = mm.pvoff; a.c_pvlen = mm.pvlen; a.c_kind = mm.kind;
     a.status = d_status; a.recv = d_recv;
-    launch_mixed_partition(a, c->mx[MX_CNT].as<uint32_t>(), c->mx[MX_TOT].as<uint32_t>(), s);
+    launch_mixed_partition(a, mm.cnt, mm.totals, s);
     HIP_TRY(hipGetLastError());
     uint32_t tot[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(tot, c->mx[MX_TOT], sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(tot, mm.totals, sizeof tot, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const size_t n0 = tot[0], n1 = tot[1];
     if (n0 + n1 > n) return ZKV_ERR_HIP;
     c->kid_ran[0] = n0 > 0; c->kid_ran[1] = n1 > 0;
-    uint8_t *st = c->mx[MX_ST], *rv = c->mx[MX_RV];
+    uint8_t *st = mm.st, *rv = mm.rv;
     if ((rc = run_records(c->kid[0], n0, a.c_seals, a.c_len, a.c_a, a.c_b, d_method ? a.c_kind : nullptr, nullptr, nullptr, nullptr, st, rv, s)) != ZKV_OK) return rc;
     if ((rc = run_records(c->kid[1], n1, a.c_seals + ZKV_SEAL_BYTES * n0, a.c_len + n0, a.c_a + 32 * n0, nullptr, nullptr, d_b, a.c_pvoff + n0, a.c_pvlen + n0,
                           st + n0, rv + 4 * n0, s)) != ZKV_OK) return rc;
@@ -1422,27 +1473,24 @@ ZKV_EXPORT int zkv_mixed_verify_call_batch(zkv_ctx* c, size_t n, const uint8_t* 
     int rc = ctx_device_init(c);
     if (rc != ZKV_OK) return rc;
     const uint64_t s0 = seal_off[0], sbytes = seal_off[n] - s0, b0 = in_b_off[0], bbytes = in_b_off[n] - b0;
-    const size_t need[8] = {n, (size_t)sbytes + 8, 8 * (n + 1), 32 * n, (size_t)bbytes + 8, 8 * (n + 1), n, 4 * n};
-    for (int k = 0; k < 8; k++) if ((rc = c->mx[MX_H_VM + k].grow(need[k])) != ZKV_OK) return rc;
-    if (method && (rc = c->mx[MX_H_METHOD].grow(n)) != ZKV_OK) return rc;
+    MixedMem& mm = c->m_mixed;
+    if ((rc = grow_all(mm.h_vm, n, mm.h_seals, (size_t)sbytes + 8, mm.h_soff, 8 * (n + 1), mm.h_a, 32 * n, mm.h_b, (size_t)bbytes + 8,
+                       mm.h_boff, 8 * (n + 1), mm.h_st, n, mm.h_rv, 4 * n)) != ZKV_OK || (method && (rc = mm.h_method.grow(n)) != ZKV_OK)) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     std::vector<uint64_t> so(seal_off, seal_off + n + 1), bo(in_b_off, in_b_off + n + 1);
     for (auto& v : so) v -= s0;
     for (auto& v : bo) v -= b0;
-    HIP_TRY(hipMemcpyAsync(c->mx[MX_H_VM], vm, n, hipMemcpyHostToDevice, s));
-    if (method) HIP_TRY(hipMemcpyAsync(c->mx[MX_H_METHOD], method, n, hipMemcpyHostToDevice, s));
-    if (sbytes) HIP_TRY(hipMemcpyAsync(c->mx[MX_H_SEALS], seal_blob + s0, (size_t)sbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->mx[MX_H_SOFF], so.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->mx[MX_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
-    if (bbytes) HIP_TRY(hipMemcpyAsync(c->mx[MX_H_B], in_b_blob + b0, (size_t)bbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->mx[MX_H_BOFF], bo.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
-    if ((rc = run_mixed(c, n, c->mx[MX_H_VM], method ? c->mx[MX_H_METHOD] : nullptr, c->mx[MX_H_SEALS], c->mx[MX_H_SOFF].as<const uint64_t>(), 0, c->mx[MX_H_A],
-                        c->mx[MX_H_B], c->mx[MX_H_BOFF].as<const uint64_t>(), 0, 0, c->mx[MX_H_ST], c->mx[MX_H_RV], s)) != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(status, c->mx[MX_H_ST], n, hipMemcpyDeviceToHost, s));
-    if (recv) HIP_TRY(hipMemcpyAsync(recv, c->mx[MX_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return ZKV_OK;
+    HIP_TRY(hipMemcpyAsync(mm.h_vm, vm, n, hipMemcpyHostToDevice, s));
+    if (method) HIP_TRY(hipMemcpyAsync(mm.h_method, method, n, hipMemcpyHostToDevice, s));
+    if (sbytes) HIP_TRY(hipMemcpyAsync(mm.h_seals, seal_blob + s0, (size_t)sbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(mm.h_soff, so.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(mm.h_a, in_a, 32 * n, hipMemcpyHostToDevice, s));
+    if (bbytes) HIP_TRY(hipMemcpyAsync(mm.h_b, in_b_blob + b0, (size_t)bbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(mm.h_boff, bo.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+    if ((rc = run_mixed(c, n, mm.h_vm, method ? mm.h_method : nullptr, mm.h_seals, mm.h_soff, 0, mm.h_a, mm.h_b, mm.h_boff, 0, 0, mm.h_st, mm.h_rv, s)) != ZKV_OK)
+        return rc;
+    return return_to_host(mm.h_st, mm.h_rv, n, status, recv, s);
 }
 ZKV_EXPORT int zkv_mixed_verify_batch(zkv_ctx* c, size_t n, const uint8_t* vm, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* in_a,
                                       const uint8_t* in_b_blob, const uint64_t* in_b_off, uint8_t* status, uint8_t* recv) {
@@ -1797,26 +1845,18 @@ static int abi_encode_error_bytes4(const char* signature, const uint8_t arg[4], 
     memcpy(out + 4, arg, 4);
     return 36;
 }
-// A ragged host blob of n items to the device: the bytes [off[0], off[n]) to mx[k_blob], the n + 1 offsets rebased to zero to mx[k_off];
+// A ragged host blob of n items to the device: the bytes [off[0], off[n]) to d_blob, the n + 1 offsets rebased to zero to d_off;
 // *bytes = the byte count.  `rebased` holds the offsets until the caller has synchronised `s`.
-static int stage_ragged(zkv_ctx* c, int k_blob, int k_off, const uint8_t* blob, const uint64_t* off, size_t n, std::vector<uint64_t>* rebased, hipStream_t s,
-                        uint64_t* bytes) {
+static int stage_ragged(DevBuf<uint8_t>& d_blob, DevBuf<uint64_t>& d_off, const uint8_t* blob, const uint64_t* off, size_t n, std::vector<uint64_t>* rebased,
+                        hipStream_t s, uint64_t* bytes) {
     const uint64_t o0 = off[0];
     *bytes = off[n] - o0;
-    int rc;
-    if ((rc = c->mx[k_blob].grow((size_t)*bytes + 8)) != ZKV_OK ||
-        (rc = c->mx[k_off].grow(8 * (n + 1))) != ZKV_OK) return rc;
+    const int rc = grow_all(d_blob, (size_t)*bytes + 8, d_off, 8 * (n + 1));
+    if (rc != ZKV_OK) return rc;
     rebased->assign(off, off + n + 1);
     for (auto& v : *rebased) v -= o0;
-    if (*bytes) HIP_TRY(hipMemcpyAsync(c->mx[k_blob], blob + o0, (size_t)*bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->mx[k_off], rebased->data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
-    return ZKV_OK;
-}
-// The end of a host-buffer call: n statuses and (recv != nullptr) received selectors from mx[k_st] / mx[k_rv], and the call's wait.
-static int return_to_host(zkv_ctx* c, int k_st, int k_rv, size_t n, uint8_t* status, uint8_t* recv, hipStream_t s) {
-    HIP_TRY(hipMemcpyAsync(status, c->mx[k_st], n, hipMemcpyDeviceToHost, s));
-    if (recv) HIP_TRY(hipMemcpyAsync(recv, c->mx[k_rv], 4 * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if (*bytes) HIP_TRY(hipMemcpyAsync(d_blob, blob + o0, (size_t)*bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_off, rebased->data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
     return ZKV_OK;
 }
 // The per-proof stages of one chunk of key-set slots (run_gset's per-proof region, the keyed groups of the two routers): `prep` launches
@@ -1984,11 +2024,6 @@ ZKV_EXPORT int zkv_sp1_gateway_verify_proof(zkv_ctx* c, const uint8_t vkey[32], 
     return ZKV_OK;
 }
 
-enum { GW_CNT = 0, GW_TOT, GW_POS, GW_IDX, GW_RECS, GW_LEN, GW_A, GW_PVOFF, GW_PVLEN, GW_ST, GW_RV,
-       GW_H_VK, GW_H_PV, GW_H_PVOFF, GW_H_PROOF, GW_H_POFF, GW_H_ST, GW_H_RV,
-       GWW_VK, GWW_PVAT, GWW_PVLEN, GWW_PAT, GWW_PLEN, GWW_BAD, GWW_ARENA, GWW_H_CD, GWW_H_OFF,        // calldata batches (run_gateway_wire)
-       GW_SKEY };                                                                                     // keyed group: the key of every group slot
-static_assert(GW_SKEY < CtxDevice::MX_SLOTS, "the gateway's buffers live in zkv_ctx::mx");
 // Everything device-resident: ragged proofs (offsets bounded by proof_bytes on the device); public values ragged (d_pv_off) or at a
 // fixed stride.  Or, from the calldata decoder, `recs`: (start, length) records of proofs and public values from one base address, which
 // d_proofs and d_pv then both are, and bad-calldata marks.  Synchronises `s` once, after the count, to size the compact records and learn
@@ -2000,9 +2035,9 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
     const size_t blocks = (n + 255) / 256, R = c->gw_route.size(), K = c->gw_nkeys, key0 = c->gw_key0;
     // slots: one per routed proof, and up to 31 pad slots behind every keyed route (its successor starts on a wavefront of the Miller mapping)
     const size_t ns = n + 32 * K;
-    const size_t need[11] = {4 * GW_COLS * blocks, 4 * GW_COLS, 4 * n, 4 * ns, 0, 4 * ns, 32 * ns, 8 * ns, 4 * ns, ns, 4 * ns};
-    for (int k = 0; k < 11; k++) if (k != GW_RECS && (rc = c->mx[k].grow(need[k])) != ZKV_OK) return rc;
-    if (K && (rc = c->mx[GW_SKEY].grow(4 * ns)) != ZKV_OK) return rc;
+    GatewayMem& gm = c->m_gw;                                     // (the compact records are sized behind the count)
+    if ((rc = grow_all(gm.cnt, 4 * GW_COLS * blocks, gm.totals, 4 * GW_COLS, gm.pos, 4 * n, gm.idx, 4 * ns, gm.len, 4 * ns, gm.a, 32 * ns,
+                       gm.pvoff, 8 * ns, gm.pvlen, 4 * ns, gm.st, ns, gm.rv, 4 * ns)) != ZKV_OK || (K && (rc = gm.skey.grow(4 * ns)) != ZKV_OK)) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     GatewayArgs a;
     memset(&a, 0, sizeof a);
@@ -2013,14 +2048,13 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
         a.sel[r] = c->gw_sel[r];
         a.rec[r] = c->gw_route[r] && c->gw_route[r]->vm == ZKV_VM_SP1_PLONK ? ZKV_PLONK_PROOF_BYTES : ZKV_SEAL_BYTES;
     }
-    a.cnt = c->mx[GW_CNT].as<uint32_t>(); a.totals = c->mx[GW_TOT].as<uint32_t>(); a.pos = c->mx[GW_POS].as<uint32_t>(); a.idx = c->mx[GW_IDX].as<uint32_t>();
-    a.c_len = c->mx[GW_LEN].as<uint32_t>(); a.c_a = c->mx[GW_A]; a.c_pvoff = c->mx[GW_PVOFF].as<uint64_t>(); a.c_pvlen = c->mx[GW_PVLEN].as<uint32_t>();
+    a.cnt = gm.cnt; a.totals = gm.totals; a.pos = gm.pos; a.idx = gm.idx; a.c_len = gm.len; a.c_a = gm.a; a.c_pvoff = gm.pvoff; a.c_pvlen = gm.pvlen;
     a.status = d_status; a.recv = d_recv;
     if (K) HIP_TRY(hipMemsetAsync(a.idx, 0xFF, 4 * ns, s));      // pad slots: GW_NONE
     launch_gateway_count(a, s);
     HIP_TRY(hipGetLastError());
     uint32_t tot[GW_COLS];
-    HIP_TRY(hipMemcpyAsync(tot, c->mx[GW_TOT], sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(tot, gm.totals, sizeof tot, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     // The layout (zkv_gset_layout.h route_layout).  A route with a context of its own takes one slot per proof; the keyed routes take the
     // key sets' layout (gset_choose: the mapping their proofs would take, stepped to a finer one while the padding exceeds 1.25 times).
@@ -2033,14 +2067,14 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
     route_layout(tot, (uint32_t)R, (uint32_t)key0, (uint32_t)K, a.rec, K ? miller_lanes(c->gw_group, placed) : 0, K && c->gw_group->lanes != 0, &L);
     for (size_t r = 0; r < R; r++) { a.start[r] = L.start[r]; a.base[r] = L.base[r]; }
     if (routed + tot[GW_COL_NOT_FOUND] + tot[GW_COL_SHORT] + tot[GW_COL_BAD] != n || L.slots > ns) return ZKV_ERR_HIP;
-    if ((rc = c->mx[GW_RECS].grow((size_t)L.bytes + 8)) != ZKV_OK) return rc;
-    a.c_proofs = c->mx[GW_RECS];
+    if ((rc = gm.recs.grow((size_t)L.bytes + 8)) != ZKV_OK) return rc;
+    a.c_proofs = gm.recs;
     for (size_t r = 0; r < R; r++) { c->gw_counts[r] = tot[r]; c->gw_ran[r] = tot[r] > 0; }
     for (size_t r = R; r < GW_MAX_ROUTES; r++) c->gw_counts[r] = 0;
     c->gw_counts[GW_COL_NOT_FOUND] = tot[GW_COL_NOT_FOUND]; c->gw_counts[GW_COL_SHORT] = tot[GW_COL_SHORT]; c->gw_counts[GW_COL_BAD] = tot[GW_COL_BAD];
     launch_gateway_place(a, s);
     HIP_TRY(hipGetLastError());
-    uint8_t *st = c->mx[GW_ST], *rv = c->mx[GW_RV];
+    uint8_t *st = gm.st, *rv = gm.rv;
     for (size_t r = 0; r < R; r++) {
         if (gw_keyed(c, r)) continue;
         const size_t j = a.start[r];
@@ -2052,7 +2086,7 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
         zkv_ctx* g = c->gw_group;
         GwsetChunk pc;
         memset(&pc, 0, sizeof pc);
-        pc.idx = a.idx + G0; pc.skey = c->mx[GW_SKEY].as<uint32_t>();
+        pc.idx = a.idx + G0; pc.skey = gm.skey;
         pc.recs = a.c_proofs + L.b0; pc.len = a.c_len + G0; pc.vkeys = a.c_a + 32 * G0; pc.pvoff = a.c_pvoff + G0; pc.pvlen = a.c_pvlen + G0; pc.pv = d_pv;
         pc.n_keys = (uint32_t)K;
         for (size_t k = 0; k < K; k++) pc.start[k] = (uint32_t)L.gstart[k];
@@ -2089,18 +2123,17 @@ ZKV_EXPORT int zkv_sp1_gateway_verify_batch(zkv_ctx* c, size_t n, const uint8_t*
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_device_init(c);
     if (rc != ZKV_OK) return rc;
-    if ((rc = c->mx[GW_H_VK].grow(32 * n)) != ZKV_OK || (rc = c->mx[GW_H_ST].grow(n)) != ZKV_OK ||
-        (rc = c->mx[GW_H_RV].grow(4 * n)) != ZKV_OK) return rc;
+    GatewayMem& gm = c->m_gw;
+    if ((rc = grow_all(gm.h_vk, 32 * n, gm.h_st, n, gm.h_rv, 4 * n)) != ZKV_OK) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     std::vector<uint64_t> so, vo;
     uint64_t sbytes = 0, vbytes = 0;
-    HIP_TRY(hipMemcpyAsync(c->mx[GW_H_VK], vkeys, 32 * n, hipMemcpyHostToDevice, s));
-    if ((rc = stage_ragged(c, GW_H_PV, GW_H_PVOFF, pv_blob, pv_off, n, &vo, s, &vbytes)) != ZKV_OK ||
-        (rc = stage_ragged(c, GW_H_PROOF, GW_H_POFF, proof_blob, proof_off, n, &so, s, &sbytes)) != ZKV_OK) return rc;
-    if ((rc = run_gateway(c, n, c->mx[GW_H_VK], c->mx[GW_H_PROOF], c->mx[GW_H_POFF].as<const uint64_t>(), sbytes, c->mx[GW_H_PV],
-                          c->mx[GW_H_PVOFF].as<const uint64_t>(), 0, c->mx[GW_H_ST], c->mx[GW_H_RV], s)) != ZKV_OK) return rc;
-    return return_to_host(c, GW_H_ST, GW_H_RV, n, status, recv, s);
+    HIP_TRY(hipMemcpyAsync(gm.h_vk, vkeys, 32 * n, hipMemcpyHostToDevice, s));
+    if ((rc = stage_ragged(gm.h_pv, gm.h_pvoff, pv_blob, pv_off, n, &vo, s, &vbytes)) != ZKV_OK ||
+        (rc = stage_ragged(gm.h_proof, gm.h_poff, proof_blob, proof_off, n, &so, s, &sbytes)) != ZKV_OK) return rc;
+    if ((rc = run_gateway(c, n, gm.h_vk, gm.h_proof, gm.h_poff, sbytes, gm.h_pv, gm.h_pvoff, 0, gm.h_st, gm.h_rv, s)) != ZKV_OK) return rc;
+    return return_to_host(gm.h_st, gm.h_rv, n, status, recv, s);
 }
 ZKV_EXPORT int zkv_sp1_gateway_last_route_counts(zkv_ctx* c, uint64_t* out) {
     if (!c || c->vm != ZKV_VM_SP1_GATEWAY) return ZKV_ERR_WRONG_CTX;
@@ -2199,15 +2232,6 @@ ZKV_EXPORT int zkv_risc0_router_route_verifier_key_digest(const zkv_ctx* c, size
     return ZKV_OK;
 }
 
-enum { RZ_CNT = 0, RZ_TOT, RZ_ITOT, RZ_POS, RZ_IDX, RZ_RECS, RZ_LEN, RZ_A, RZ_B, RZ_INST, RZ_ST, RZ_RV, RZ_SKEY, RZ_ROUTES,
-       RZ_H_SEALS, RZ_H_OFF, RZ_H_A, RZ_H_B, RZ_H_ST, RZ_H_RV,
-       RZ_KIND, RZ_H_METHOD,                    // per-seal methods: the compact row and the host call's staging
-       RZW_SEALS, RZW_LEN, RZW_CK,              // calldata batches: the decoded slots, true lengths and call kinds (inputs and methods: RZ_H_A, RZ_H_B, RZ_H_METHOD)
-       // the set route (zkv_risc0_router_set.h): claim records, the root-seal table, section 16's per-claim and per-slot rows, the job rows
-       RZS_REC, RZS_OWNER, RZS_RIDX, RZS_REP, RZS_GSLOT, RZS_CJOB, RZS_JCLAIM, RZS_ANS, RZS_CNT, RZS_ROOTS, RZS_STORED,
-       RZS_ROWS, RZS_LENS, RZS_IDS, RZS_JDS, RZS_JST, RZS_JRV, RZS_DIAG,
-       RZ_BUFS };
-static_assert(RZ_BUFS <= CtxDevice::MX_SLOTS, "the router's buffers live in zkv_ctx::mx");
 // The built-in group: m compact records from the front end through the verifier set's pipeline (run_set_batch's chunks, with the true
 // lengths and the instance row on the device).  kind: the method row, or nullptr: one method, in_b == nullptr being verify_integrity.
 static int run_router_builtin(zkv_ctx* c, size_t m_total, const uint8_t* seals, const uint32_t* len, const uint32_t* inst, const uint8_t* in_a,
@@ -2242,32 +2266,31 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
     const size_t blocks = (n + 255) / 256, R = c->gw_sel.size(), NB = c->rz_nb, K = R - NB;
     // slots: one per routed seal, and up to 31 pad slots behind every keyed route (its successor starts on a wavefront of the Miller mapping)
     const size_t ns = n + 32 * K;
-    const size_t need[RZ_ROUTES] = {4 * GW_COLS * blocks, 4 * GW_COLS, 4 * (RZR_BAD_WORD + 1), 4 * n, 4 * ns, (size_t)ZKV_SEAL_BYTES * ns + 8, 4 * ns,
-                                    32 * ns, 32 * ns, 4 * ns, ns, 4 * ns, 4 * ns};
-    for (int k = 0; k < RZ_ROUTES; k++) if ((rc = c->mx[k].grow(need[k])) != ZKV_OK) return rc;
-    if (d_method && (rc = c->mx[RZ_KIND].grow(ns)) != ZKV_OK) return rc;
+    RouterMem& rm = c->m_rz;
+    if ((rc = grow_all(rm.cnt, 4 * GW_COLS * blocks, rm.totals, 4 * GW_COLS, rm.itot, 4 * (RZR_BAD_WORD + 1), rm.pos, 4 * n, rm.idx, 4 * ns,
+                       rm.recs, (size_t)ZKV_SEAL_BYTES * ns + 8, rm.len, 4 * ns, rm.a, 32 * ns, rm.b, 32 * ns, rm.inst, 4 * ns, rm.st, ns, rm.rv, 4 * ns,
+                       rm.skey, 4 * ns)) != ZKV_OK || (d_method && (rc = rm.kind.grow(ns)) != ZKV_OK)) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
-    if (K && !c->mx[RZ_ROUTES]) {                                  // the keyed routes' constants, once
-        if ((rc = c->mx[RZ_ROUTES].grow(sizeof(RzrRoute) * K)) != ZKV_OK) return rc;
-        HIP_TRY(hipMemcpy(c->mx[RZ_ROUTES], c->rz_routes.data(), sizeof(RzrRoute) * K, hipMemcpyHostToDevice));
+    if (K && !rm.routes) {                                         // the keyed routes' constants, once
+        if ((rc = rm.routes.grow(sizeof(RzrRoute) * K)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpy(rm.routes, c->rz_routes.data(), sizeof(RzrRoute) * K, hipMemcpyHostToDevice));
     }
     RzrArgs a;
     memset(&a, 0, sizeof a);
     a.n = n; a.seals = d_seals; a.seal_off = d_seal_off; a.seal_bytes = seal_bytes; a.stride = ZKV_SEAL_BYTES; a.in_a = d_a; a.in_b = d_b;
-    a.method = d_method; a.wire_len = d_wire_len; a.c_kind = d_method ? c->mx[RZ_KIND] : nullptr;
+    a.method = d_method; a.wire_len = d_wire_len; a.c_kind = d_method ? rm.kind : nullptr;
     a.n_builtin = (uint32_t)NB; a.n_keyed = (uint32_t)K;
     for (size_t r = 0; r < R; r++) a.sel[r] = c->gw_sel[r];
-    a.cnt = c->mx[RZ_CNT].as<uint32_t>(); a.totals = c->mx[RZ_TOT].as<uint32_t>(); a.inst_tot = c->mx[RZ_ITOT].as<uint32_t>();
-    a.pos = c->mx[RZ_POS].as<uint32_t>(); a.idx = c->mx[RZ_IDX].as<uint32_t>();
-    a.c_seals = c->mx[RZ_RECS]; a.c_len = c->mx[RZ_LEN].as<uint32_t>(); a.c_a = c->mx[RZ_A]; a.c_b = c->mx[RZ_B]; a.c_inst = c->mx[RZ_INST].as<uint32_t>();
+    a.cnt = rm.cnt; a.totals = rm.totals; a.inst_tot = rm.itot; a.pos = rm.pos; a.idx = rm.idx;
+    a.c_seals = rm.recs; a.c_len = rm.len; a.c_a = rm.a; a.c_b = rm.b; a.c_inst = rm.inst;
     a.status = d_status; a.recv = d_recv;
     HIP_TRY(hipMemsetAsync(a.inst_tot, 0, 4 * (RZR_BAD_WORD + 1), s));
     if (K) HIP_TRY(hipMemsetAsync(a.idx, 0xFF, 4 * ns, s));       // pad slots: GW_NONE
     launch_rzrouter_count(a, s);
     HIP_TRY(hipGetLastError());
     uint32_t tot[GW_COLS], itot[RZR_BAD_WORD + 1];                 // (the routes' words, then the bad-calldata word)
-    HIP_TRY(hipMemcpyAsync(tot, c->mx[RZ_TOT], sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(itot, c->mx[RZ_ITOT], sizeof itot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(tot, rm.totals, sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(itot, rm.itot, sizeof itot, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     // The layout (zkv_gset_layout.h route_layout).  The built-in group takes one slot per seal from slot 0; the keyed routes take the key
     // sets' layout behind it (gset_choose: the mapping their seals would take, stepped to a finer one while the padding exceeds 1.25 times).
@@ -2289,19 +2312,19 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
     if (routed + tot[RZR_COL_NOT_FOUND] + tot[RZR_COL_SHORT] != n || L.slots > ns || isum != n0 || n_bad > tot[RZR_COL_SHORT]) return ZKV_ERR_HIP;
     launch_rzrouter_place(a, s);
     HIP_TRY(hipGetLastError());
-    uint8_t *st = c->mx[RZ_ST], *rv = c->mx[RZ_RV];
+    uint8_t *st = rm.st, *rv = rm.rv;
     if (n0 && (rc = run_router_builtin(c->kid[0], n0, a.c_seals, a.c_len, a.c_inst, a.c_a, d_b ? a.c_b : nullptr, a.c_kind, st, rv, s)) != ZKV_OK) return rc;
     if (routed > n0) {                                             // the keyed group: k_rzrouter_prep with the slot's route, then the key sets' stages
         const size_t G0 = (size_t)L.g0;
         zkv_ctx* g = c->gw_group;
         RzrChunk pc;
         memset(&pc, 0, sizeof pc);
-        pc.idx = a.idx + G0; pc.skey = c->mx[RZ_SKEY].as<uint32_t>();
+        pc.idx = a.idx + G0; pc.skey = rm.skey;
         pc.recs = a.c_seals + L.b0; pc.len = a.c_len + G0; pc.in_a = a.c_a + 32 * G0; pc.in_b = a.in_b ? a.c_b + 32 * G0 : nullptr;
         pc.kind = a.c_kind ? a.c_kind + G0 : nullptr;
         pc.n_keys = (uint32_t)K;
         for (size_t k = 0; k < K; k++) pc.start[k] = (uint32_t)L.gstart[k];
-        pc.routes = c->mx[RZ_ROUTES].as<const RzrRoute>();
+        pc.routes = rm.routes;
         pc.status = st + G0; pc.recv = (uint32_t*)(rv + 4 * G0);
         if ((rc = run_keyed_group(g, (size_t)L.m, L.lanes, pc.idx, pc.skey, pc.status, s, [&](const GsetChunk& ch) {
                 keyed_prep_chunk(&pc, ch);
@@ -2338,23 +2361,20 @@ static int router_host_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, con
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_device_init(c);
     if (rc != ZKV_OK) return rc;
-    const size_t need[4] = {32 * n, 32 * n, n, 4 * n};
-    for (int k = 0; k < 4; k++) if ((rc = c->mx[RZ_H_A + k].grow(need[k])) != ZKV_OK) return rc;
-    if (method && (rc = c->mx[RZ_H_METHOD].grow(n)) != ZKV_OK) return rc;
+    RouterMem& rm = c->m_rz;
+    if ((rc = grow_all(rm.h_a, 32 * n, rm.h_b, 32 * n, rm.h_st, n, rm.h_rv, 4 * n)) != ZKV_OK || (method && (rc = rm.h_method.grow(n)) != ZKV_OK)) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     std::vector<uint64_t> so;
     uint64_t sbytes = 0;
-    if ((rc = stage_ragged(c, RZ_H_SEALS, RZ_H_OFF, seal_blob, seal_off, n, &so, s, &sbytes)) != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
-    if (in_b) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_B], in_b, 32 * n, hipMemcpyHostToDevice, s));
-    if (method) HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_METHOD], method, n, hipMemcpyHostToDevice, s));
-    if (c->rz_set) rc = run_router_set(c, n, c->mx[RZ_H_SEALS], c->mx[RZ_H_OFF].as<const uint64_t>(), sbytes, c->mx[RZ_H_A], in_b ? c->mx[RZ_H_B] : nullptr,
-                                       c->mx[RZ_H_ST], c->mx[RZ_H_RV], s, 0xFFFFFFFFu, nullptr);
-    else rc = run_router(c, n, c->mx[RZ_H_SEALS], c->mx[RZ_H_OFF].as<const uint64_t>(), sbytes, c->mx[RZ_H_A], in_b ? c->mx[RZ_H_B] : nullptr,
-                         c->mx[RZ_H_ST], c->mx[RZ_H_RV], s, method ? c->mx[RZ_H_METHOD] : nullptr);
+    if ((rc = stage_ragged(rm.h_seals, rm.h_off, seal_blob, seal_off, n, &so, s, &sbytes)) != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(rm.h_a, in_a, 32 * n, hipMemcpyHostToDevice, s));
+    if (in_b) HIP_TRY(hipMemcpyAsync(rm.h_b, in_b, 32 * n, hipMemcpyHostToDevice, s));
+    if (method) HIP_TRY(hipMemcpyAsync(rm.h_method, method, n, hipMemcpyHostToDevice, s));
+    if (c->rz_set) rc = run_router_set(c, n, rm.h_seals, rm.h_off, sbytes, rm.h_a, in_b ? rm.h_b : nullptr, rm.h_st, rm.h_rv, s, 0xFFFFFFFFu, nullptr);
+    else rc = run_router(c, n, rm.h_seals, rm.h_off, sbytes, rm.h_a, in_b ? rm.h_b : nullptr, rm.h_st, rm.h_rv, s, method ? rm.h_method : nullptr);
     if (rc != ZKV_OK) return rc;
-    return return_to_host(c, RZ_H_ST, RZ_H_RV, n, status, recv, s);
+    return return_to_host(rm.h_st, rm.h_rv, n, status, recv, s);
 }
 ZKV_EXPORT int zkv_risc0_router_verify_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* image_ids,
                                              const uint8_t* journal_digests, uint8_t* status, uint8_t* recv) {
@@ -2682,16 +2702,15 @@ ZKV_EXPORT int zkv_sp1_gateway_eth_call_returndata(const zkv_ctx* c, uint8_t sta
 // Calldata and its n + 1 offsets on the device.  The decode is enqueued in front of the count, so the call synchronises where run_gateway does.
 static int run_gateway_wire(zkv_ctx* c, size_t n, const uint8_t* d_cd, const uint64_t* d_off, uint64_t cd_bytes, uint8_t* d_status, uint8_t* d_recv, hipStream_t s) {
     int rc;
-    const size_t need[7] = {32 * n, 8 * n, 4 * n, 8 * n, 4 * n, n, (size_t)(cd_bytes / 32) + 64};
-    for (int k = 0; k < 7; k++) if ((rc = c->mx[GWW_VK + k].grow(need[k])) != ZKV_OK) return rc;
+    GatewayMem& gm = c->m_gw;
+    if ((rc = grow_all(gm.w_vk, 32 * n, gm.w_pvat, 8 * n, gm.w_pvlen, 4 * n, gm.w_pat, 8 * n, gm.w_plen, 4 * n, gm.w_bad, n,
+                       gm.w_arena, (size_t)(cd_bytes / 32) + 64)) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     GwWireArgs w;
     memset(&w, 0, sizeof w);
     w.n = n; w.cd = d_cd; w.off = d_off; w.cd_bytes = cd_bytes;
     w.sel_u_be = be32_of(host::selectors().sp1[host::SP1_VERIFY_PROOF]); w.sel_b_be = be32_of(gateway_bytes_selector());
-    w.arena = c->mx[GWW_ARENA]; w.vkeys = c->mx[GWW_VK];
-    w.pv_at = c->mx[GWW_PVAT].as<uint64_t>(); w.pv_len = c->mx[GWW_PVLEN].as<uint32_t>(); w.proof_at = c->mx[GWW_PAT].as<uint64_t>(); w.proof_len = c->mx[GWW_PLEN].as<uint32_t>();
-    w.bad = c->mx[GWW_BAD];
+    w.arena = gm.w_arena; w.vkeys = gm.w_vk; w.pv_at = gm.w_pvat; w.pv_len = gm.w_pvlen; w.proof_at = gm.w_pat; w.proof_len = gm.w_plen; w.bad = gm.w_bad;
     // one base address for the records: the lower of the two buffers, so that every start is a plain non-negative distance
     const uintptr_t pc = (uintptr_t)d_cd, pa = (uintptr_t)w.arena, base = pc < pa ? pc : pa;
     w.cd_delta = pc - base; w.arena_delta = pa - base;
@@ -2725,20 +2744,17 @@ ZKV_EXPORT int zkv_sp1_gateway_eth_call_batch(zkv_ctx* c, size_t n, const uint8_
         int rc = ctx_device_init(c);
         if (rc != ZKV_OK) return rc;
         const uint64_t b0 = off[0], bytes = off[n] - b0;
-        const size_t need[4] = {(size_t)bytes + 8, 8 * (n + 1), n, 4 * n};
-        const int slot[4] = {GWW_H_CD, GWW_H_OFF, GW_H_ST, GW_H_RV};
-        for (int k = 0; k < 4; k++) if ((rc = c->mx[slot[k]].grow(need[k])) != ZKV_OK) return rc;
+        GatewayMem& gm = c->m_gw;
+        if ((rc = grow_all(gm.h_cd, (size_t)bytes + 8, gm.h_cdoff, 8 * (n + 1), gm.h_st, n, gm.h_rv, 4 * n)) != ZKV_OK) return rc;
         hipStream_t s = c->stream;
         if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
         std::vector<uint64_t> rel(off, off + n + 1);
         for (auto& v : rel) v -= b0;
-        if (bytes) HIP_TRY(hipMemcpyAsync(c->mx[GWW_H_CD], blob + b0, (size_t)bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c->mx[GWW_H_OFF], rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+        if (bytes) HIP_TRY(hipMemcpyAsync(gm.h_cd, blob + b0, (size_t)bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(gm.h_cdoff, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));                        // `rel` is a pageable host buffer
-        if ((rc = run_gateway_wire(c, n, c->mx[GWW_H_CD], c->mx[GWW_H_OFF].as<const uint64_t>(), bytes, c->mx[GW_H_ST], c->mx[GW_H_RV], s)) != ZKV_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(st.data(), c->mx[GW_H_ST], n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(rv.data(), c->mx[GW_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        if ((rc = run_gateway_wire(c, n, gm.h_cd, gm.h_cdoff, bytes, gm.h_st, gm.h_rv, s)) != ZKV_OK ||
+            (rc = return_to_host(gm.h_st, gm.h_rv, n, st.data(), rv.data(), s)) != ZKV_OK) return rc;
     }
     for (size_t i = 0; i < n; i++) {
         const int rc = zkv_sp1_gateway_eth_call_returndata(c, st[i], rv.data() + 4 * i, returndata + i * ZKV_RETURNDATA_STRIDE, &returndata_len[i], &reverted[i]);
@@ -2835,15 +2851,14 @@ ZKV_EXPORT int zkv_risc0_router_eth_call_returndata(const zkv_ctx* c, uint8_t st
 static int run_router_wire(zkv_ctx* c, size_t n, const uint8_t* d_cd, const uint64_t* d_off, uint64_t cd_bytes, uint8_t* d_status, uint8_t* d_recv,
                            uint8_t* d_ck, hipStream_t s) {
     int rc;
-    const int slot[5] = {RZW_SEALS, RZW_LEN, RZ_H_A, RZ_H_B, RZ_H_METHOD};
-    const size_t need[5] = {(size_t)ZKV_SEAL_BYTES * n + 8, 4 * n, 32 * n, 32 * n, n};
-    for (int k = 0; k < 5; k++) if ((rc = c->mx[slot[k]].grow(need[k])) != ZKV_OK) return rc;
+    RouterMem& rm = c->m_rz;
+    if ((rc = grow_all(rm.w_seals, (size_t)ZKV_SEAL_BYTES * n + 8, rm.w_len, 4 * n, rm.h_a, 32 * n, rm.h_b, 32 * n, rm.h_method, n)) != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     RzWireArgs w;
     memset(&w, 0, sizeof w);
     w.n = n; w.cd = d_cd; w.off = d_off; w.cd_bytes = cd_bytes;
     for (int k = 0; k < RZW_KINDS; k++) w.sel_be[k] = be32_of(router_call_selector(k));
-    w.seals = c->mx[RZW_SEALS]; w.seal_len = c->mx[RZW_LEN].as<uint32_t>(); w.in_a = c->mx[RZ_H_A]; w.in_b = c->mx[RZ_H_B]; w.method = c->mx[RZ_H_METHOD];
+    w.seals = rm.w_seals; w.seal_len = rm.w_len; w.in_a = rm.h_a; w.in_b = rm.h_b; w.method = rm.h_method;
     w.call_kind = d_ck;
     (void)hipEventRecord(c->ev_wire[0], s);
     launch_wire_rzrouter(w, s);
@@ -2874,20 +2889,16 @@ ZKV_EXPORT int zkv_risc0_router_eth_call_batch(zkv_ctx* c, size_t n, const uint8
         std::lock_guard<std::mutex> lk(c->mu);
         int rc = ctx_device_init(c);
         if (rc != ZKV_OK) return rc;
-        const size_t need[3] = {n, 4 * n, n};
-        const int slot[3] = {RZ_H_ST, RZ_H_RV, RZW_CK};
-        for (int k = 0; k < 3; k++) if ((rc = c->mx[slot[k]].grow(need[k])) != ZKV_OK) return rc;
+        RouterMem& rm = c->m_rz;
+        if ((rc = grow_all(rm.h_st, n, rm.h_rv, 4 * n, rm.w_ck, n)) != ZKV_OK) return rc;
         hipStream_t s = c->stream;
         if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
         std::vector<uint64_t> rel;
         uint64_t bytes = 0;
-        if ((rc = stage_ragged(c, RZ_H_SEALS, RZ_H_OFF, blob, off, n, &rel, s, &bytes)) != ZKV_OK) return rc;
-        if ((rc = run_router_wire(c, n, c->mx[RZ_H_SEALS], c->mx[RZ_H_OFF].as<const uint64_t>(), bytes, c->mx[RZ_H_ST], c->mx[RZ_H_RV], c->mx[RZW_CK], s)) != ZKV_OK)
-            return rc;
-        HIP_TRY(hipMemcpyAsync(st.data(), c->mx[RZ_H_ST], n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(rv.data(), c->mx[RZ_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(ck.data(), c->mx[RZW_CK], n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        if ((rc = stage_ragged(rm.h_seals, rm.h_off, blob, off, n, &rel, s, &bytes)) != ZKV_OK) return rc;
+        if ((rc = run_router_wire(c, n, rm.h_seals, rm.h_off, bytes, rm.h_st, rm.h_rv, rm.w_ck, s)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(ck.data(), rm.w_ck, n, hipMemcpyDeviceToHost, s));
+        if ((rc = return_to_host(rm.h_st, rm.h_rv, n, st.data(), rv.data(), s)) != ZKV_OK) return rc;
     }
     for (size_t i = 0; i < n; i++) {
         const int rc = zkv_risc0_router_eth_call_returndata(c, st[i], rv.data() + 4 * i, ck[i], returndata + i * ZKV_RETURNDATA_STRIDE, &returndata_len[i], &reverted[i]);
@@ -3302,10 +3313,7 @@ static bool gset_agg_tables(zkv_ctx* c) {
 }
 // ---- The steps of a call that both kinds of key set take (run_gset, run_pset: each keeps its own layout choice, placement and stages).
 // Partition: the proofs counted per key, block by block; the per-key totals come back to the host (gs_totals: the call's one
-// synchronisation) and *placed is their sum.
-// mx[] slots of a key-set call (0 .. 2 are not used): per-block counts, per-key totals, block offsets, every proof's position, the keys' slot
-// starts (behind the aggregate layout's map when there is one), the proof and key of every slot, the aggregate chunks' pseudo-proof maps
-enum { KS_CNT = 3, KS_TOT, KS_OFF, KS_POS, KS_START, KS_IDX, KS_SKEY, KS_AMAP };
+// synchronisation) and *placed is their sum.  The buffers: KeySetMem.
 static int set_partition(zkv_ctx* c, size_t n, uint32_t K, const uint32_t* d_key, hipStream_t s, GsetPart* p, size_t* placed) {
     memset(p, 0, sizeof *p);
     p->n = n; p->n_keys = K;
@@ -3313,11 +3321,10 @@ static int set_partition(zkv_ctx* c, size_t n, uint32_t K, const uint32_t* d_key
     per = (per + 63) / 64 * 64;
     p->per_block = (uint32_t)per; p->blocks = (uint32_t)((n + per - 1) / per);
     const size_t kb = (size_t)K * p->blocks;
-    int rc;
-    if ((rc = c->mx[KS_CNT].grow(4 * kb)) != ZKV_OK || (rc = c->mx[KS_TOT].grow(4 * (size_t)K)) != ZKV_OK ||
-        (rc = c->mx[KS_OFF].grow(4 * kb)) != ZKV_OK || (rc = c->mx[KS_POS].grow(4 * n)) != ZKV_OK ||
-        (rc = c->mx[KS_START].grow(8 * ((size_t)K + 1))) != ZKV_OK) return rc;
-    p->key = d_key; p->cnt = c->mx[KS_CNT].as<uint32_t>(); p->totals = c->mx[KS_TOT].as<uint32_t>(); p->off = c->mx[KS_OFF].as<uint32_t>(); p->pos = c->mx[KS_POS].as<uint32_t>();
+    KeySetMem& ks = c->m_ks;
+    const int rc = grow_all(ks.cnt, 4 * kb, ks.totals, 4 * (size_t)K, ks.off, 4 * kb, ks.pos, 4 * n, ks.start, 8 * ((size_t)K + 1));
+    if (rc != ZKV_OK) return rc;
+    p->key = d_key; p->cnt = ks.cnt; p->totals = ks.totals; p->off = ks.off; p->pos = ks.pos;
     HIP_TRY(hipMemsetAsync(p->totals, 0, 4 * (size_t)K, s));
     launch_gset_count(*p, s);
     HIP_TRY(hipGetLastError());
@@ -3330,17 +3337,16 @@ static int set_partition(zkv_ctx* c, size_t n, uint32_t K, const uint32_t* d_key
 }
 // Slot buffers of a layout of M slots: the proof of every slot, its key and its status byte.
 static int set_slot_buffers(zkv_ctx* c, size_t M, GsetPart* p, hipStream_t s) {
-    int rc;
-    if ((rc = c->mx[KS_IDX].grow(4 * M + 4)) != ZKV_OK || (rc = c->mx[KS_SKEY].grow(4 * M + 4)) != ZKV_OK ||
-        (rc = c->d_st_all.grow(M + 1)) != ZKV_OK) return rc;
-    p->idx = c->mx[KS_IDX].as<uint32_t>(); p->skey = c->mx[KS_SKEY].as<uint32_t>();
+    const int rc = grow_all(c->m_ks.idx, 4 * M + 4, c->m_ks.skey, 4 * M + 4, c->d_st_all, M + 1);
+    if (rc != ZKV_OK) return rc;
+    p->idx = c->m_ks.idx; p->skey = c->m_ks.skey;
     HIP_TRY(hipMemsetAsync(p->idx, 0xFF, 4 * M + 4, s));     // pad slots: GSET_NONE
     HIP_TRY(hipMemsetAsync(p->skey, 0, 4 * M + 4, s));       // (and key 0: a slot's key is only read for live slots, this keeps any read in the set)
     return ZKV_OK;
 }
 // The aggregate chunks of the aggregate region [0, R), `capa` slots each, and their pseudo-proof maps (zkv_gset_layout.h
 // gset_agg_chunk_plan, whose regions the caller passes on): chunk g's map is in gs_amap from word g.off -- psl (sub-batch -> pseudo slot, n2
-// words), then the key of every pseudo slot (slots words) -- and all of gs_amap goes to mx[KS_AMAP] in one copy.
+// words), then the key of every pseudo slot (slots words) -- and all of gs_amap goes to m_ks.amap in one copy.
 struct GsetAggChunk { size_t base, m, n2, off; uint64_t slots; int lanes; };
 static int set_agg_plan(zkv_ctx* c, const uint64_t* beg, const uint64_t* end, const uint32_t* rep, uint32_t n_regions, uint64_t R, size_t capa,
                         uint32_t sub, std::vector<GsetAggChunk>* plan, hipStream_t s) {
@@ -3356,9 +3362,9 @@ static int set_agg_plan(zkv_ctx* c, const uint64_t* beg, const uint64_t* end, co
         c->gs_amap.resize(g.off + g.n2 + g.slots);
         plan->push_back(g);
     }
-    const int rc = c->mx[KS_AMAP].grow(4 * c->gs_amap.size() + 4);
+    const int rc = c->m_ks.amap.grow(4 * c->gs_amap.size() + 4);
     if (rc != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->mx[KS_AMAP], c->gs_amap.data(), 4 * c->gs_amap.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->m_ks.amap, c->gs_amap.data(), 4 * c->gs_amap.size(), hipMemcpyHostToDevice, s));
     return ZKV_OK;
 }
 // The verdicts back to the caller's order (a call that placed no proof still records the six stage events).
@@ -3443,13 +3449,13 @@ static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
     if ((rc = groth16_ready(c, M ? M : 1, &cap)) != ZKV_OK) return rc;     // (growing frees buffers, which synchronises the device)
     if ((rc = set_slot_buffers(c, M, &p, s)) != ZKV_OK) return rc;
     if (agg) {
-        if ((rc = c->mx[KS_START].grow(8 * (c->gs_map.size() + K + 1))) != ZKV_OK) return rc;
-        HIP_TRY(hipMemsetAsync(c->mx[KS_START] + 8 * c->gs_map.size(), 0, 8 * ((size_t)K + 1), s));      // zero starts: k_gset_scan gives ranks
-        HIP_TRY(hipMemcpyAsync(c->mx[KS_START], c->gs_map.data(), 8 * c->gs_map.size(), hipMemcpyHostToDevice, s));
-        launch_gset_agg_place(p, c->mx[KS_START].as<const uint64_t>() + c->gs_map.size(), c->mx[KS_START].as<const uint64_t>(), s);
+        if ((rc = c->m_ks.start.grow(8 * (c->gs_map.size() + K + 1))) != ZKV_OK) return rc;
+        HIP_TRY(hipMemsetAsync(c->m_ks.start + c->gs_map.size(), 0, 8 * ((size_t)K + 1), s));      // zero starts: k_gset_scan gives ranks
+        HIP_TRY(hipMemcpyAsync(c->m_ks.start, c->gs_map.data(), 8 * c->gs_map.size(), hipMemcpyHostToDevice, s));
+        launch_gset_agg_place(p, c->m_ks.start + c->gs_map.size(), c->m_ks.start, s);
     } else {
-        HIP_TRY(hipMemcpyAsync(c->mx[KS_START], c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
-        launch_gset_place(p, c->mx[KS_START].as<const uint64_t>(), s);
+        HIP_TRY(hipMemcpyAsync(c->m_ks.start, c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
+        launch_gset_place(p, c->m_ks.start, s);
     }
     HIP_TRY(hipGetLastError());
     if (agg) {
@@ -3458,7 +3464,7 @@ static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
         std::vector<GsetAggChunk> plan;
         if ((rc = set_agg_plan(c, c->gs_map.data(), c->gs_map.data() + 1, nullptr, K, R, cap / unit * unit, sub, &plan, s)) != ZKV_OK) return rc;
         for (const GsetAggChunk& g : plan) {
-            enqueue_gset_agg(c, gset_chunk_of(c, p, d_proofs, d_signals, g.base, g.m), g, p.skey + g.base, c->mx[KS_AMAP].as<const uint32_t>(), sub, s,
+            enqueue_gset_agg(c, gset_chunk_of(c, p, d_proofs, d_signals, g.base, g.m), g, p.skey + g.base, c->m_ks.amap, sub, s,
                              M == R && g.base + g.m >= R);
             HIP_TRY(hipGetLastError());
         }
@@ -3494,14 +3500,13 @@ ZKV_EXPORT int zkv_groth16_set_verify_batch(zkv_ctx* c, size_t n, const uint32_t
     int rc = groth16_ready(c, n, &cap);
     if (rc != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
-    // the whole batch in HBM: keys, proofs, signals (hb[0..2]) and the verdicts (hb[3])
-    if ((rc = c->hb[0].grow(4 * n)) != ZKV_OK || (rc = c->hb[1].grow(256 * n)) != ZKV_OK ||
-        (rc = c->hb[2].grow(stride * n + 8)) != ZKV_OK || (rc = c->hb[3].grow(n)) != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->hb[0], key, 4 * n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->hb[1], proofs, 256 * n, hipMemcpyHostToDevice, c->stream));
-    if (stride) HIP_TRY(hipMemcpyAsync(c->hb[2], signals, stride * n, hipMemcpyHostToDevice, c->stream));
-    if ((rc = run_gset(c, n, c->hb[0].as<const uint32_t>(), c->hb[1], c->hb[2], c->hb[3], c->stream)) != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(verified, c->hb[3], n, hipMemcpyDeviceToHost, c->stream));
+    KeySetHostMem& hb = c->m_kshost;                           // the whole batch in HBM: keys, proofs, signals and the verdicts
+    if ((rc = grow_all(hb.key, 4 * n, hb.proofs, 256 * n, hb.rows, stride * n + 8, hb.verdicts, n)) != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(hb.key, key, 4 * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(hb.proofs, proofs, 256 * n, hipMemcpyHostToDevice, c->stream));
+    if (stride) HIP_TRY(hipMemcpyAsync(hb.rows, signals, stride * n, hipMemcpyHostToDevice, c->stream));
+    if ((rc = run_gset(c, n, hb.key, hb.proofs, hb.rows, hb.verdicts, c->stream)) != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(verified, hb.verdicts, n, hipMemcpyDeviceToHost, c->stream));
     if ((rc = mark_done(c, c->stream)) != ZKV_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return ZKV_OK;
@@ -3517,13 +3522,13 @@ ZKV_EXPORT int zkv_groth16_set_vk_x_batch(zkv_ctx* c, size_t n, const uint32_t* 
     int rc = groth16_ready(c, n, &cap);
     if (rc != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
-    if ((rc = c->hb[0].grow(4 * n)) != ZKV_OK || (rc = c->hb[2].grow(stride * n + 8)) != ZKV_OK ||
-        (rc = c->hb[4].grow(64 * n)) != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->hb[0], key, 4 * n, hipMemcpyHostToDevice, c->stream));
-    if (stride) HIP_TRY(hipMemcpyAsync(c->hb[2], signals, stride * n, hipMemcpyHostToDevice, c->stream));
-    launch_gset_vk_x(n, msm_lanes_long(c, n), c->hb[0].as<const uint32_t>(), c->d_gs_key, c->d_gs_rows, c->d_gs_win, c->hb[2], (uint32_t)stride, c->hb[4], c->stream);
+    KeySetHostMem& hb = c->m_kshost;
+    if ((rc = grow_all(hb.key, 4 * n, hb.rows, stride * n + 8, hb.vk_x, 64 * n)) != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(hb.key, key, 4 * n, hipMemcpyHostToDevice, c->stream));
+    if (stride) HIP_TRY(hipMemcpyAsync(hb.rows, signals, stride * n, hipMemcpyHostToDevice, c->stream));
+    launch_gset_vk_x(n, msm_lanes_long(c, n), hb.key, c->d_gs_key, c->d_gs_rows, c->d_gs_win, hb.rows, (uint32_t)stride, hb.vk_x, c->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, c->hb[4], 64 * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, hb.vk_x, 64 * n, hipMemcpyDeviceToHost, c->stream));
     if ((rc = mark_done(c, c->stream)) != ZKV_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return ZKV_OK;
@@ -3705,8 +3710,8 @@ static int run_pset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
     const size_t M = (size_t)slots;
     if ((rc = ctx_ready(c, M ? M : 1)) != ZKV_OK) return rc;     // (growing frees buffers, which synchronises the device)
     if ((rc = set_slot_buffers(c, M, &p, s)) != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->mx[KS_START], c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
-    launch_gset_place(p, c->mx[KS_START].as<const uint64_t>(), s);
+    HIP_TRY(hipMemcpyAsync(c->m_ks.start, c->gs_start.data(), 8 * ((size_t)K + 1), hipMemcpyHostToDevice, s));
+    launch_gset_place(p, c->m_ks.start, s);
     HIP_TRY(hipGetLastError());
     const size_t cap = c->ws.cap;                            // (a power of two >= 4,096 or ZKV_CHUNK, a multiple of 64: chunks keep the 64-slot groups)
     if (agg) {
@@ -3717,7 +3722,7 @@ static int run_pset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
         if ((rc = set_agg_plan(c, c->ps_cbeg.data(), c->ps_cend.data(), c->ps_cls_rep.data(), n_cls, R, (size_t)pset_agg_chunk_slots(cap, sub), sub,
                                &plan, s)) != ZKV_OK) return rc;
         for (const GsetAggChunk& g : plan) {
-            enqueue_pset_agg(c, pset_chunk_of(c, p, d_proofs, d_inputs, g.base, g.m), g, p.skey + g.base, c->mx[KS_AMAP].as<const uint32_t>(), sub, s,
+            enqueue_pset_agg(c, pset_chunk_of(c, p, d_proofs, d_inputs, g.base, g.m), g, p.skey + g.base, c->m_ks.amap, sub, s,
                              M == R && g.base + g.m >= R);
             HIP_TRY(hipGetLastError());
         }
@@ -3760,16 +3765,15 @@ ZKV_EXPORT int zkv_plonk_set_verify_batch(zkv_ctx* c, size_t n, const uint32_t* 
     int rc = ctx_ready(c, n < hc ? n : hc);
     if (rc != ZKV_OK) return rc;
     if ((rc = order_after_previous(c, c->stream)) != ZKV_OK) return rc;
-    // chunks of the caller's order staged in HBM: keys, proofs, public inputs (hb[0..2]) and the verdicts (hb[3])
+    KeySetHostMem& hb = c->m_kshost;                           // chunks of the caller's order staged in HBM: keys, proofs, public inputs and the verdicts
     for (size_t base = 0; base < n; base += hc) {
         const size_t m = n - base < hc ? n - base : hc;
-        if ((rc = c->hb[0].grow(4 * m)) != ZKV_OK || (rc = c->hb[1].grow(ps * m)) != ZKV_OK ||
-            (rc = c->hb[2].grow(is * m + 8)) != ZKV_OK || (rc = c->hb[3].grow(m)) != ZKV_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(c->hb[0], key + base, 4 * m, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->hb[1], proofs + ps * base, ps * m, hipMemcpyHostToDevice, c->stream));
-        if (is) HIP_TRY(hipMemcpyAsync(c->hb[2], public_inputs + is * base, is * m, hipMemcpyHostToDevice, c->stream));
-        if ((rc = run_pset(c, m, c->hb[0].as<const uint32_t>(), c->hb[1], is ? c->hb[2] : nullptr, c->hb[3], c->stream)) != ZKV_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(verified + base, c->hb[3], m, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = grow_all(hb.key, 4 * m, hb.proofs, ps * m, hb.rows, is * m + 8, hb.verdicts, m)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(hb.key, key + base, 4 * m, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(hb.proofs, proofs + ps * base, ps * m, hipMemcpyHostToDevice, c->stream));
+        if (is) HIP_TRY(hipMemcpyAsync(hb.rows, public_inputs + is * base, is * m, hipMemcpyHostToDevice, c->stream));
+        if ((rc = run_pset(c, m, hb.key, hb.proofs, is ? hb.rows : nullptr, hb.verdicts, c->stream)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(verified + base, hb.verdicts, m, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return mark_done(c, c->stream);
@@ -4235,10 +4239,23 @@ ZKV_EXPORT int zkv_status_abi_encode(int vm, uint8_t status, const uint8_t recei
 
 // ------------------------------------------------------------------ RISC Zero set-inclusion receipts (zkv_risc0_set_inclusion.h)
 // No reference counterpart: parity unpinned.  k_setincl.hip hashes the paths and forms the root jobs; the jobs run on the inner context.
-enum { SI_ROOTS = 0, SI_REP, SI_GSLOT, SI_CLAIMJOB, SI_JOBCLAIM, SI_CNT, SI_STORED, SI_ROWS, SI_LENS, SI_IDS, SI_JDS, SI_PROOFS, SI_SIGNALS, SI_PRE,
-       SI_PRERECV, SI_JST, SI_JRV, SI_H_A, SI_H_B, SI_H_PATHS, SI_H_POFF, SI_H_RIDX, SI_H_SEALS, SI_H_SLEN, SI_H_ST, SI_H_RV, SI_DIAG, SI_BUFS };
-static_assert(SI_BUFS <= CtxDevice::MX_SLOTS, "the set-inclusion buffers live in zkv_ctx::mx");
 constexpr size_t SETINCL_CHUNK = (size_t)1 << 20;
+// Section 16's grouping rows in a chunk's record, as they are now (after their grows).
+static void setgroup_chunk_view(const SetGroupMem& g, SetinclChunk* ch) {
+    ch->stored = g.stored; ch->roots = g.roots; ch->rep = g.rep; ch->gslot = g.gslot; ch->claim_job = g.claim_job; ch->job_claim = g.job_claim;
+    ch->counters = g.cnt;
+}
+// The rows of nj root jobs, grown, in a job record: records with lengths and inputs or, for a keyed inner verifier, proofs and signals.
+// (Growing frees the old buffer, which waits for the device: the previous chunk's scatter has read its rows by then.)
+static int setgroup_job_rows(SetGroupMem& g, size_t nj, bool keyed, SetinclJobs* jb) {
+    const size_t rec = keyed ? 0 : nj, key = keyed ? nj : 0;
+    const int rc = grow_all(g.rows, 260 * rec, g.lens, 4 * rec, g.ids, 32 * rec, g.jds, 32 * rec, g.proofs, 256 * key, g.signals, 160 * key, g.pre, key,
+                            g.pre_recv, 4 * key, g.jst, nj, g.jrv, 4 * nj);
+    if (rc != ZKV_OK) return rc;
+    jb->rows = g.rows; jb->lens = g.lens; jb->ids = g.ids; jb->jds = g.jds; jb->st = g.jst; jb->rv = g.jrv;
+    jb->proofs = g.proofs; jb->signals = g.signals; jb->pre = g.pre; jb->pre_recv = g.pre_recv;
+    return ZKV_OK;
+}
 
 static void setincl_set_selector(const uint8_t id[32], uint8_t out[4]) {
     uint8_t tag[32], d[32];
@@ -4349,16 +4366,16 @@ static int run_setincl(zkv_ctx* c, size_t n, const uint8_t* d_a, const uint8_t* 
                        hipStream_t s) {
     int rc;
     const size_t cap = n < SETINCL_CHUNK ? n : SETINCL_CHUNK;
-    const size_t need[7] = {32 * cap, 4 * (m + 1), 4 * (m + 1), 4 * cap, 4 * cap, 16, (size_t)32 * ZKV_SETINCL_MAX_ROOTS};
-    for (int k = 0; k < 7; k++) if ((rc = c->mx[k].grow(need[k])) != ZKV_OK) return rc;
+    SetGroupMem& g = c->m_si;
+    if ((rc = grow_all(g.roots, 32 * cap, g.rep, 4 * (m + 1), g.gslot, 4 * (m + 1), g.claim_job, 4 * cap, g.job_claim, 4 * cap, g.cnt, 16,
+                       g.stored, (size_t)32 * ZKV_SETINCL_MAX_ROOTS)) != ZKV_OK) return rc;
     if (c->si_dirty) {                                   // a root was submitted since the last call: nothing of this context is in flight after the wait
         HIP_TRY(hipDeviceSynchronize());
-        if (!c->si_roots.empty()) HIP_TRY(hipMemcpy(c->mx[SI_STORED], c->si_roots.data(), c->si_roots.size(), hipMemcpyHostToDevice));
+        if (!c->si_roots.empty()) HIP_TRY(hipMemcpy(g.stored, c->si_roots.data(), c->si_roots.size(), hipMemcpyHostToDevice));
         c->si_dirty = false;
     }
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
-    uint32_t* cnt = c->mx[SI_CNT].as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(cnt, 0, 16, s));
+    HIP_TRY(hipMemsetAsync(g.cnt, 0, 16, s));
     if (!d_diag) { c->si_counts[0] = n; c->si_counts[1] = 0; c->si_counts[2] = 0; }
     for (size_t base = 0; base < n; base += cap) {
         const size_t mc = n - base < cap ? n - base : cap;
@@ -4367,22 +4384,21 @@ static int run_setincl(zkv_ctx* c, size_t n, const uint8_t* d_a, const uint8_t* 
         ch.n = (uint32_t)mc; ch.m = (uint32_t)m; ch.n_siblings = (uint32_t)n_sib; ch.n_stored = (uint32_t)(c->si_roots.size() / 32);
         ch.in_a = d_a + 32 * base; ch.in_b = d_b ? d_b + 32 * base : nullptr;
         ch.paths = d_paths; ch.path_off = d_poff + base; ch.root_idx = d_ridx ? d_ridx + base : nullptr;
-        ch.seals = d_seals; ch.seal_len = d_slen; ch.stored = c->mx[SI_STORED];
+        ch.seals = d_seals; ch.seal_len = d_slen;
         for (int q = 0; q < 8; q++) ch.id_be[q] = be32_of(c->si_id + 4 * q);
-        ch.roots = c->mx[SI_ROOTS].as<uint32_t>(); ch.rep = c->mx[SI_REP].as<uint32_t>(); ch.gslot = c->mx[SI_GSLOT].as<uint32_t>();
-        ch.claim_job = c->mx[SI_CLAIMJOB].as<uint32_t>(); ch.job_claim = c->mx[SI_JOBCLAIM].as<uint32_t>(); ch.counters = cnt;
+        setgroup_chunk_view(g, &ch);
         ch.status = d_status ? d_status + base : nullptr; ch.recv = d_recv ? d_recv + 4 * base : nullptr;
         ch.diag_roots = d_diag ? d_diag + 32 * base : nullptr;
         if (d_diag) { launch_setincl_hash(ch, c->consts, s); HIP_TRY(hipGetLastError()); continue; }
         HIP_TRY(hipMemsetAsync(ch.rep, 0xFF, 4 * (m + 1), s));
-        HIP_TRY(hipMemsetAsync(cnt, 0, 4, s));
+        HIP_TRY(hipMemsetAsync(g.cnt, 0, 4, s));
         HIP_TRY(hipEventRecord(c->ev[0], s));                       // zkv_ctx_last_stage_ms [0]: the hash kernel of the last chunk
         launch_setincl_hash(ch, c->consts, s);
         HIP_TRY(hipEventRecord(c->ev[1], s));
         launch_setincl_group(ch, s);
         HIP_TRY(hipGetLastError());
         uint32_t nj = 0;
-        HIP_TRY(hipMemcpyAsync(&nj, cnt, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&nj, g.cnt, 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (nj > mc) return ZKV_ERR_HIP;
         c->si_counts[1] += nj;
@@ -4390,19 +4406,12 @@ static int run_setincl(zkv_ctx* c, size_t n, const uint8_t* d_a, const uint8_t* 
         memset(&jb, 0, sizeof jb);
         jb.n_jobs = nj; jb.keyed = c->si_keyed ? 1u : 0u; jb.selector_be = be32_of(c->si_root_sel);
         if (nj) {
-            // (growing frees the old buffer, which waits for the device: the previous chunk's scatter has read its rows by then)
-            const size_t jneed[10] = {c->si_keyed ? 0 : (size_t)260 * nj, c->si_keyed ? 0 : (size_t)4 * nj, c->si_keyed ? 0 : (size_t)32 * nj,
-                                      c->si_keyed ? 0 : (size_t)32 * nj, c->si_keyed ? (size_t)256 * nj : 0, c->si_keyed ? (size_t)160 * nj : 0,
-                                      c->si_keyed ? (size_t)nj : 0, c->si_keyed ? (size_t)4 * nj : 0, nj, (size_t)4 * nj};
-            for (int k = 0; k < 10; k++) if ((rc = c->mx[SI_ROWS + k].grow(jneed[k])) != ZKV_OK) return rc;
-            jb.rows = c->mx[SI_ROWS]; jb.lens = c->mx[SI_LENS].as<uint32_t>(); jb.ids = c->mx[SI_IDS]; jb.jds = c->mx[SI_JDS];
-            jb.proofs = c->mx[SI_PROOFS]; jb.signals = c->mx[SI_SIGNALS]; jb.pre = c->mx[SI_PRE]; jb.pre_recv = c->mx[SI_PRERECV];
-            jb.st = c->mx[SI_JST]; jb.rv = c->mx[SI_JRV];
+            if ((rc = setgroup_job_rows(g, nj, c->si_keyed, &jb)) != ZKV_OK) return rc;
             memcpy(jb.fixed[0] + 16, c->control_root_0, 16); memcpy(jb.fixed[1] + 16, c->control_root_1, 16); memcpy(jb.fixed[2], c->control_id, 32);
             launch_setincl_jobs(ch, jb, c->consts, s);
             HIP_TRY(hipGetLastError());
-            if (c->si_keyed) rc = zkv_groth16_verify_batch_dev(c->kid[0], nj, jb.proofs, jb.signals, c->mx[SI_JST], s);
-            else rc = run_records(c->kid[0], nj, jb.rows, jb.lens, jb.ids, jb.jds, nullptr, nullptr, nullptr, nullptr, c->mx[SI_JST], c->mx[SI_JRV], s);
+            if (c->si_keyed) rc = zkv_groth16_verify_batch_dev(c->kid[0], nj, jb.proofs, jb.signals, g.jst, s);
+            else rc = run_records(c->kid[0], nj, jb.rows, jb.lens, jb.ids, jb.jds, nullptr, nullptr, nullptr, nullptr, g.jst, g.jrv, s);
             if (rc != ZKV_OK) return rc;
             HIP_TRY(hipSetDevice(c->device));
         }
@@ -4455,31 +4464,27 @@ static int setincl_host_call(zkv_ctx* c, size_t n, const uint8_t* in_a, const ui
             memcpy(rows.data() + ZKV_SEAL_BYTES * j, seal_blob + seal_off[j], len < ZKV_SEAL_BYTES ? (size_t)len : (size_t)ZKV_SEAL_BYTES);
         }
     } catch (const std::bad_alloc&) { return ZKV_ERR_OOM; }
-    const size_t need[9] = {32 * n, integrity ? 0 : 32 * n, 32 * n_sib + 256 + 32, 4 * (n + 1), 4 * n, rows.size(), 4 * sl.size(), n, 4 * n};
-    for (int k = 0; k < 9; k++) if ((rc = c->mx[SI_H_A + k].grow(need[k])) != ZKV_OK) return rc;
-    if (diag_out && (rc = c->mx[SI_DIAG].grow(32 * n)) != ZKV_OK) return rc;
+    SetInclMem& si = c->m_si;
+    if ((rc = grow_all(si.h_a, 32 * n, si.h_b, integrity ? 0 : 32 * n, si.h_paths, 32 * n_sib + 256 + 32, si.h_poff, 4 * (n + 1), si.h_ridx, 4 * n,
+                       si.h_seals, rows.size(), si.h_slen, 4 * sl.size(), si.h_st, n, si.h_rv, 4 * n)) != ZKV_OK || (diag_out && (rc = si.diag.grow(32 * n)) != ZKV_OK)) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
-    uint8_t* d_paths = (uint8_t*)(((uintptr_t)c->mx[SI_H_PATHS].as<uint8_t>() + 255u) & ~(uintptr_t)255u) + blob_shift;
-    HIP_TRY(hipMemcpyAsync(c->mx[SI_H_A], in_a, 32 * n, hipMemcpyHostToDevice, s));
-    if (!integrity) HIP_TRY(hipMemcpyAsync(c->mx[SI_H_B], in_b, 32 * n, hipMemcpyHostToDevice, s));
+    uint8_t* d_paths = (uint8_t*)(((uintptr_t)si.h_paths.as<uint8_t>() + 255u) & ~(uintptr_t)255u) + blob_shift;
+    HIP_TRY(hipMemcpyAsync(si.h_a, in_a, 32 * n, hipMemcpyHostToDevice, s));
+    if (!integrity) HIP_TRY(hipMemcpyAsync(si.h_b, in_b, 32 * n, hipMemcpyHostToDevice, s));
     if (n_sib) HIP_TRY(hipMemcpyAsync(d_paths, path_blob + 32 * (size_t)o0, 32 * n_sib, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->mx[SI_H_POFF], po.data(), 4 * (n + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(si.h_poff, po.data(), 4 * (n + 1), hipMemcpyHostToDevice, s));
     if (!diag_out) {
-        HIP_TRY(hipMemcpyAsync(c->mx[SI_H_RIDX], root_idx, 4 * n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c->mx[SI_H_SEALS], rows.data(), rows.size(), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c->mx[SI_H_SLEN], sl.data(), 4 * sl.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(si.h_ridx, root_idx, 4 * n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(si.h_seals, rows.data(), rows.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(si.h_slen, sl.data(), 4 * sl.size(), hipMemcpyHostToDevice, s));
     }
     HIP_TRY(hipStreamSynchronize(s));                    // the staging vectors are pageable host memory
-    rc = run_setincl(c, n, c->mx[SI_H_A], integrity ? nullptr : c->mx[SI_H_B], d_paths, c->mx[SI_H_POFF].as<const uint32_t>(), n_sib,
-                     diag_out ? nullptr : c->mx[SI_H_RIDX].as<const uint32_t>(), m, c->mx[SI_H_SEALS], c->mx[SI_H_SLEN].as<const uint32_t>(),
-                     diag_out ? nullptr : c->mx[SI_H_ST], diag_out ? nullptr : c->mx[SI_H_RV], diag_out ? c->mx[SI_DIAG] : nullptr, s);
+    rc = run_setincl(c, n, si.h_a, integrity ? nullptr : si.h_b, d_paths, si.h_poff, n_sib, diag_out ? nullptr : si.h_ridx, m, si.h_seals, si.h_slen,
+                     diag_out ? nullptr : si.h_st, diag_out ? nullptr : si.h_rv, diag_out ? si.diag : nullptr, s);
     if (rc != ZKV_OK) return rc;
-    if (diag_out) HIP_TRY(hipMemcpyAsync(diag_out, c->mx[SI_DIAG], 32 * n, hipMemcpyDeviceToHost, s));
-    else {
-        HIP_TRY(hipMemcpyAsync(status, c->mx[SI_H_ST], n, hipMemcpyDeviceToHost, s));
-        if (recv) HIP_TRY(hipMemcpyAsync(recv, c->mx[SI_H_RV], 4 * n, hipMemcpyDeviceToHost, s));
-    }
+    if (!diag_out) return return_to_host(si.h_st, si.h_rv, n, status, recv, s);
+    HIP_TRY(hipMemcpyAsync(diag_out, si.diag, 32 * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return ZKV_OK;
 }
@@ -4504,11 +4509,11 @@ ZKV_EXPORT int zkv_risc0_setincl_last_counts(zkv_ctx* c, uint64_t out[3]) {
     if (!out) return ZKV_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     out[0] = c->si_counts[0]; out[1] = c->si_counts[1]; out[2] = 0;
-    if (!c->dev_ready || !c->mx[SI_CNT]) return ZKV_OK;
+    if (!c->dev_ready || !c->m_si.cnt) return ZKV_OK;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
     uint32_t v[2] = {0, 0};
-    HIP_TRY(hipMemcpy(v, c->mx[SI_CNT], sizeof v, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(v, c->m_si.cnt, sizeof v, hipMemcpyDeviceToHost));
     out[2] = v[1];
     return ZKV_OK;
 }
@@ -4636,17 +4641,16 @@ static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const ui
     const size_t cap = n < SETINCL_CHUNK ? n : SETINCL_CHUNK, R = c->gw_sel.size();
     size_t table = 64;
     while (table < 2 * cap) table <<= 1;
-    const size_t need[RZS_STORED - RZS_REC + 1] = {sizeof(RzsRec) * cap, 4 * table, 4 * cap, 4 * table, 4 * table, 4 * cap, 4 * cap, cap, 16, 32 * cap,
-                                                   (size_t)32 * ZKV_SETINCL_MAX_ROOTS};
-    for (int k = 0; k <= RZS_STORED - RZS_REC; k++) if ((rc = c->mx[RZS_REC + k].grow(need[k])) != ZKV_OK) return rc;
+    RouterMem& rm = c->m_rz; SetGroupMem& g = rm.grp;
+    if ((rc = grow_all(rm.s_rec, sizeof(RzsRec) * cap, rm.s_owner, 4 * table, rm.s_ridx, 4 * cap, g.rep, 4 * table, g.gslot, 4 * table, g.claim_job, 4 * cap,
+                       g.job_claim, 4 * cap, rm.s_ans, cap, g.cnt, 16, g.roots, 32 * cap, g.stored, (size_t)32 * ZKV_SETINCL_MAX_ROOTS)) != ZKV_OK) return rc;
     if (c->si_dirty) {                                   // a root was submitted since the last call: nothing of this context is in flight after the wait
         HIP_TRY(hipDeviceSynchronize());
-        if (!c->si_roots.empty()) HIP_TRY(hipMemcpy(c->mx[RZS_STORED], c->si_roots.data(), c->si_roots.size(), hipMemcpyHostToDevice));
+        if (!c->si_roots.empty()) HIP_TRY(hipMemcpy(g.stored, c->si_roots.data(), c->si_roots.size(), hipMemcpyHostToDevice));
         c->si_dirty = false;
     }
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
-    uint32_t* cnt = c->mx[RZS_CNT].as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(cnt, 0, 16, s));
+    HIP_TRY(hipMemsetAsync(g.cnt, 0, 16, s));
     uint32_t seen[4] = {0, 0, 0, 0};
     uint64_t jobs = 0;
     std::vector<uint64_t> direct;
@@ -4656,19 +4660,18 @@ static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const ui
         memset(&ch, 0, sizeof ch);
         ch.n = (uint32_t)mc; ch.m = (uint32_t)table; ch.n_stored = (uint32_t)(c->si_roots.size() / 32);
         ch.in_a = d_a + 32 * base; ch.in_b = d_b ? d_b + 32 * base : nullptr;
-        ch.root_idx = c->mx[RZS_RIDX].as<const uint32_t>(); ch.stored = c->mx[RZS_STORED];
+        ch.root_idx = rm.s_ridx;
         for (int q = 0; q < 8; q++) ch.id_be[q] = be32_of(c->si_id + 4 * q);
-        ch.roots = c->mx[RZS_ROOTS].as<uint32_t>(); ch.rep = c->mx[RZS_REP].as<uint32_t>(); ch.gslot = c->mx[RZS_GSLOT].as<uint32_t>();
-        ch.claim_job = c->mx[RZS_CJOB].as<uint32_t>(); ch.job_claim = c->mx[RZS_JCLAIM].as<uint32_t>(); ch.counters = cnt;
+        setgroup_chunk_view(g, &ch);
         ch.status = d_status ? d_status + base : nullptr; ch.recv = d_recv ? d_recv + 4 * base : nullptr;
         RzsArgs a;
         memset(&a, 0, sizeof a);
         a.seals = d_seals; a.seal_off = d_seal_off + base; a.seal_bytes = seal_bytes;
         a.set_sel = be32_of(c->si_set_sel); a.table = (uint32_t)table; a.fp_mask = fp_mask;
-        a.rec = c->mx[RZS_REC].as<RzsRec>(); a.owner = c->mx[RZS_OWNER].as<uint32_t>(); a.root_idx = c->mx[RZS_RIDX].as<uint32_t>(); a.ans = c->mx[RZS_ANS];
+        a.rec = rm.s_rec; a.owner = rm.s_owner; a.root_idx = rm.s_ridx; a.ans = rm.s_ans;
         HIP_TRY(hipMemsetAsync(a.owner, 0xFF, 4 * table, s));
         HIP_TRY(hipMemsetAsync(ch.rep, 0xFF, 4 * table, s));
-        HIP_TRY(hipMemsetAsync(cnt, 0, 4, s));
+        HIP_TRY(hipMemsetAsync(g.cnt, 0, 4, s));
         launch_rzset_front(ch, a, s);
         if (d_diag) {
             launch_rzset_reps(ch, a, d_diag, s);
@@ -4678,7 +4681,7 @@ static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const ui
         launch_rzset_hash(ch, a, c->consts, s);
         launch_setincl_group(ch, s);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(seen, cnt, sizeof seen, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(seen, g.cnt, sizeof seen, hipMemcpyDeviceToHost, s));
         if (base == 0) {
             rc = run_router(c, n, d_seals, d_seal_off, seal_bytes, d_a, d_b, d_status, d_recv, s);
             if (rc != ZKV_OK) { (void)hipStreamSynchronize(s); return rc; }      // (the copy into `seen` may still be in flight)
@@ -4691,15 +4694,11 @@ static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const ui
         memset(&jb, 0, sizeof jb);
         jb.n_jobs = nj;
         if (nj) {
-            // (growing frees the old buffer, which waits for the device: the previous chunk's scatter has read its rows by then)
-            const size_t jneed[6] = {(size_t)260 * nj, (size_t)4 * nj, (size_t)32 * nj, (size_t)32 * nj, nj, (size_t)4 * nj};
-            for (int k = 0; k < 6; k++) if ((rc = c->mx[RZS_ROWS + k].grow(jneed[k])) != ZKV_OK) return rc;
-            jb.rows = c->mx[RZS_ROWS]; jb.lens = c->mx[RZS_LENS].as<uint32_t>(); jb.ids = c->mx[RZS_IDS]; jb.jds = c->mx[RZS_JDS];
-            jb.st = c->mx[RZS_JST]; jb.rv = c->mx[RZS_JRV];
+            if ((rc = setgroup_job_rows(g, nj, false, &jb)) != ZKV_OK) return rc;
             launch_rzset_jobs(ch, a, jb, s);
             HIP_TRY(hipGetLastError());
             // root jobs are `verify` calls of the router on (S, ID, sha256(ID || root)): the rows enter its partition with their true lengths
-            if ((rc = run_router(c, nj, jb.rows, nullptr, 0, jb.ids, jb.jds, c->mx[RZS_JST], c->mx[RZS_JRV], s, nullptr, jb.lens)) != ZKV_OK) return rc;
+            if ((rc = run_router(c, nj, jb.rows, nullptr, 0, jb.ids, jb.jds, g.jst, g.jrv, s, nullptr, jb.lens)) != ZKV_OK) return rc;
         }
         launch_rzset_scatter(ch, a, jb, s);
         HIP_TRY(hipGetLastError());
@@ -4742,17 +4741,16 @@ ZKV_EXPORT int zkv_diag_rzset_groups(zkv_ctx* c, size_t n, const uint8_t* seal_b
     std::vector<uint64_t> so;
     try { so.assign(seal_off, seal_off + n + 1); } catch (const std::bad_alloc&) { return ZKV_ERR_OOM; }
     for (auto& v : so) v -= o0;
-    if ((rc = c->mx[RZ_H_SEALS].grow((size_t)bytes + 256 + 32)) != ZKV_OK || (rc = c->mx[RZ_H_OFF].grow(8 * (n + 1))) != ZKV_OK ||
-        (rc = c->mx[RZS_DIAG].grow(4 * n)) != ZKV_OK) return rc;
+    RouterMem& rm = c->m_rz;
+    if ((rc = grow_all(rm.h_seals, (size_t)bytes + 256 + 32, rm.h_off, 8 * (n + 1), rm.s_diag, 4 * n)) != ZKV_OK) return rc;
     hipStream_t s = c->stream;
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
-    uint8_t* d_blob = (uint8_t*)(((uintptr_t)c->mx[RZ_H_SEALS].as<uint8_t>() + 255u) & ~(uintptr_t)255u) + blob_shift;
+    uint8_t* d_blob = (uint8_t*)(((uintptr_t)rm.h_seals.as<uint8_t>() + 255u) & ~(uintptr_t)255u) + blob_shift;
     if (bytes) HIP_TRY(hipMemcpyAsync(d_blob, seal_blob + o0, (size_t)bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->mx[RZ_H_OFF], so.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(rm.h_off, so.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));                    // the staging vector is pageable host memory
-    if ((rc = run_router_set(c, n, d_blob, c->mx[RZ_H_OFF].as<const uint64_t>(), bytes, nullptr, nullptr, nullptr, nullptr, s, fp_mask,
-                             c->mx[RZS_DIAG].as<uint32_t>())) != ZKV_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out_rep, c->mx[RZS_DIAG], 4 * n, hipMemcpyDeviceToHost, s));
+    if ((rc = run_router_set(c, n, d_blob, rm.h_off, bytes, nullptr, nullptr, nullptr, nullptr, s, fp_mask, rm.s_diag)) != ZKV_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out_rep, rm.s_diag, 4 * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return ZKV_OK;
 }

@@ -283,7 +283,8 @@ def fam_mixed(z, real_proofs, verify_corpus):
 
 def fam_sp1_gateway_keyed(z, real_proofs, verify_corpus):
     """The built-in Groth16 route and a keyed route (a trapdoor key of tests/gateway_keys_model.py) in one batch: corpus statuses on the
-    first (no route instead of a selector mismatch), the model's on the second."""
+    first (no route instead of a selector mismatch), the model's on the second; then the eth_call entry points on the same rows as
+    calldata."""
     key = gk.Key(0xD3A1)
     gw = z.Sp1Gateway(True, groth16_keys=[(key.words, key.hash)])
     gw.set_aggregate_check(True)
@@ -302,6 +303,14 @@ def fam_sp1_gateway_keyed(z, real_proofs, verify_corpus):
     d_vk, d_pv, d_p, d_off = up(b''.join(x[0] for x in rows)), up(b''.join(x[1] for x in rows)), up(b''.join(x[2] for x in rows)), up(off)
     d_st, d_rv = outs(n)
     gw.verify_batch_dev(n, d_vk.data_ptr(), d_pv.data_ptr(), 96, d_p.data_ptr(), d_off.data_ptr(), int(off[-1]), d_st.data_ptr(), d_rv.data_ptr(), stream())
+    assert done(d_st)[0].tolist() == want
+    calls = [gw.encode_verify_proof_call(*x[:3]) for x in rows]
+    rev, _, st = gw.eth_call_batch(calls)
+    assert st.tolist() == want and rev.tolist() == [int(w != 0) for w in want]
+    off = np.zeros(n + 1, dtype=np.uint64); off[1:] = np.cumsum([len(c) for c in calls])
+    d_cd, d_off = up(b''.join(calls)), up(off)
+    d_st, d_rv = outs(n)
+    gw.eth_call_batch_dev(n, d_cd.data_ptr(), d_off.data_ptr(), int(off[-1]), d_st.data_ptr(), d_rv.data_ptr(), stream())
     assert done(d_st)[0].tolist() == want
     return [gw]
 
@@ -339,6 +348,30 @@ def fam_risc0_router_keyed(z, real_proofs, verify_corpus):
     d_st, d_rv = outs(n)
     rt.eth_call_batch_dev(n, d_cd.data_ptr(), d_off.data_ptr(), int(off[-1]), d_st.data_ptr(), d_rv.data_ptr(), 0, stream())
     assert done(d_st)[0].tolist() == want
+    return [rt]
+
+
+def fam_risc0_router_set(z, real_proofs, verify_corpus):
+    """A router with a set route on the first seals of tests/golden/risc0_router_set_cases.json -- Groth16 seals of every route, set seals
+    whose root seals the keyed routes verify, malformed ones -- through verify_batch and verify_ragged_dev: the fixture's statuses (those
+    of tests/risc0_router_set_model.py), and root jobs were run, so their rows are held too."""
+    rs = load('risc0_router_set_cases.json')
+    rt = z.RiscZeroSetRouter(H(rs['set_id']), [(H(rs['builtin']['control_root']), H(rs['builtin']['bn254_control_id']))],
+                             [(H(k['vk_words']), H(k['control_root']), H(k['bn254_control_id'])) for k in rs['keyed']])
+    rt.set_aggregate_check(True)
+    for x in rs['submitted_roots']:
+        assert rt.submit_root(H(x['root']), H(x['seal']))[0] == 0
+    cases = rs['cases'][:48]
+    n, want = len(cases), [c['status'] for c in cases]
+    seals, ids, jds = [H(c['seal']) for c in cases], [H(c['image_id']) for c in cases], [H(c['journal_digest']) for c in cases]
+    assert {0, 1, 4, 8} <= set(want)
+    st, _ = rt.verify_batch(seals, ids, jds)
+    assert st.tolist() == want and rt.set_last_counts()[2] >= 1
+    off = np.zeros(n + 1, dtype=np.uint64); off[1:] = np.cumsum([len(s) for s in seals])
+    d_s, d_off, d_a, d_b = up(b''.join(seals)), up(off), up(b''.join(ids)), up(b''.join(jds))
+    d_st, d_rv = outs(n)
+    rt.verify_ragged_dev(n, d_s.data_ptr(), d_off.data_ptr(), int(off[-1]), d_a.data_ptr(), d_b.data_ptr(), d_st.data_ptr(), d_rv.data_ptr(), stream())
+    assert done(d_st)[0].tolist() == want and rt.set_last_counts()[2] >= 1
     return [rt]
 
 
@@ -425,7 +458,7 @@ def fam_sp1_gt_tables_refused(z, real_proofs, verify_corpus):
 
 FAMILIES = {f.__name__[4:]: f for f in (fam_risc0, fam_risc0_set, fam_sp1, fam_sp1_plonk, fam_plonk_key, fam_groth16_short_key, fam_groth16_long_key,
                                          fam_groth16_key_set, fam_plonk_key_set, fam_mixed, fam_sp1_gateway_keyed, fam_risc0_router_keyed,
-                                         fam_set_inclusion, fam_bn254_precompiles, fam_risc0_sharded, fam_sp1_gt_tables, fam_sp1_gt_tables_refused)}
+                                         fam_risc0_router_set, fam_set_inclusion, fam_bn254_precompiles, fam_risc0_sharded, fam_sp1_gt_tables, fam_sp1_gt_tables_refused)}
 
 
 def cycle(z, name, real_proofs, verify_corpus):
