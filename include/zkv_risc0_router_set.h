@@ -38,7 +38,8 @@
  *   - OUT OF SCOPE, answered ZKV_ERR_WRONG_CTX: zkv_risc0_router_verify_batch_dev (a fixed stride of 260 bytes cannot hold a set
  *     seal), zkv_risc0_router_verify_call_batch and _verify_call_batch_dev (the per-seal method row) and the calldata entry points
  *     of zkv_risc0_router_wire.h (zkv_risc0_router_eth_call_batch, _eth_call_batch_dev, and zkv_risc0_router_last_call_counts, which
- *     describes them).  On a router without a set route nothing changes.
+ *     describes them).  On a router without a set route nothing changes.  Calldata and the per-seal method row for seals of any
+ *     length, on every router, are the entry points of zkv_risc0_router_set_wire.h (new names: the ones above keep refusing).
  * Device scratch on top of zkv_risc0_router.h's: per seal of a chunk 69 bytes (claim record, root, slot, job tables, answer) and 24
  * bytes of table (2 slots per seal, three words each); per root job 333 bytes.
  */

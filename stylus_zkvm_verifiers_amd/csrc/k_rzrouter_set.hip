@@ -1,13 +1,14 @@
 // RISC Zero router, set route (include/zkv_risc0_router_set.h; the header arithmetic and the identity pair:
 // zkv_rzrouter_set.h).  A set-inclusion seal arrives at the router in its on-chain form, is taken apart here, and its root seal goes
 // back into the router's own partition as a 260-byte job row.  Parity unpinned.
-//   k_rzset_front    one seal per lane: a seal with the set selector is parsed (rzs_parse); malformed bodies and the library limits (a
-//                    path past SETINCL_MAX_DEPTH, a root seal that begins with the set selector) are answered, the others leave a claim
-//                    record.  Seals of other selectors are not touched: the router's partition (k_rzrouter_count ...) reads them where
-//                    they lie
+//   k_rzset_front    one seal per lane, found by rzs_span (a pair of offsets, or the record of decoded calldata): a seal with the set
+//                    selector is parsed (rzs_parse); malformed bodies and the library limits (a path past SETINCL_MAX_DEPTH, a root
+//                    seal that begins with the set selector) are answered, the others leave a claim record.  Seals of other selectors
+//                    are not touched: the router's partition (k_rzrouter_count ...) reads them where they lie
 //   k_rzset_ident    one claim per wavefront: the claim's root seal finds its slot in an open-addressed table (fingerprint, then bytes)
 //                    and lowers the slot's representative; the slot is section 16's root index
-//   k_rzset_hash     one claim per lane: claim digest, leaf and path walk from the blob, the stored-root lookup of an empty root seal
+//   k_rzset_hash     one claim per lane: claim digest (derived or given, per row where the batch has a method row), leaf and path walk
+//                    from the blob, the stored-root lookup of an empty root seal
 //   (k_setincl_group of k_setincl.hip: representatives and stragglers take job slots)
 //   k_rzset_jobs     one job per lane: the root seal copied to a 260-byte row, its true length, ID and sha256(ID || root) beside it
 //   (the rows run through run_router as a batch of their own)
@@ -23,15 +24,31 @@ constexpr int RZS_HASH_BLOCK = 64;      // hash, jobs: one wavefront per workgro
 
 __device__ __forceinline__ void rzs_put_be32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
 
+// Seal i of the chunk as (start, length) from a.seals, the only place that knows offsets from records (k_rzset_front is its only caller:
+// every later kernel takes absolute positions from RzsRec).  false: the set stage never reads the seal and it is no set seal -- offsets
+// that run backwards or past seal_bytes (the partition answers a short seal), a request that is not a canonical call, a method byte
+// above ZKV_METHOD_VERIFY_INTEGRITY (the partition answers bad calldata).
+__device__ __forceinline__ bool rzs_span(const RzsArgs& a, uint32_t i, uint64_t* start, uint64_t* len) {
+    if (a.method && a.method[i] > 1) return false;
+    if (!a.seal_off) {
+        const RzsSpan sp = a.span[i];
+        *start = sp.at; *len = sp.len;
+        return a.wire_len[i] != 0xFFFFFFFFu;
+    }
+    const uint64_t s = a.seal_off[i], e = a.seal_off[i + 1];
+    *start = s; *len = e - s;
+    return s <= e && e <= a.seal_bytes;
+}
+
 __global__ __launch_bounds__(RZS_BLOCK) void k_rzset_front(SetinclChunk c, RzsArgs a) {
     const uint32_t i = blockIdx.x * RZS_BLOCK + threadIdx.x;
     bool set = false;
     if (i < c.n) {
-        const uint64_t s = a.seal_off[i], e = a.seal_off[i + 1];
+        uint64_t s, len;
         uint32_t job = RZS_JOB_NOT_SET;
-        if (s <= e && e <= a.seal_bytes) {                           // (else: never read; the partition answers it as a short seal)
+        if (rzs_span(a, i, &s, &len)) {
             const uint8_t* p = a.seals + s;
-            const RzsSeal r = rzs_parse(p, e - s, !((uintptr_t)p & 3u), a.set_sel);
+            const RzsSeal r = rzs_parse(p, len, !((uintptr_t)p & 3u), a.set_sel);
             if (r.kind != RZS_NOT_SET) {
                 set = true;
                 job = SETINCL_DONE;
@@ -131,7 +148,7 @@ __global__ __launch_bounds__(RZS_HASH_BLOCK) void k_rzset_hash(SetinclChunk c, R
     if (i < c.n && c.claim_job[i] == SETINCL_PENDING) {
         const RzsRec me = a.rec[i];
         uint32_t h[8], root[8];
-        if (c.in_b) risc0_claim_digest(k, c.in_a + 32 * (size_t)i, c.in_b + 32 * (size_t)i, h);
+        if (!rzs_claim_given(a.method, c.in_b != nullptr, i)) risc0_claim_digest(k, c.in_a + 32 * (size_t)i, c.in_b + 32 * (size_t)i, h);
         else {
 #pragma unroll 1
             for (int j = 0; j < 8; j++) h[j] = load_be32(c.in_a + 32 * (size_t)i + 4 * j);

@@ -31,6 +31,7 @@
 #include "../../include/zkv_risc0_router.h"
 #include "../../include/zkv_risc0_router_wire.h"
 #include "../../include/zkv_risc0_router_set.h"
+#include "../../include/zkv_risc0_router_set_wire.h"
 #include "zkv_host_abi.h"
 #include "zkv_host_vk.h"
 #include "zkv_internal.h"
@@ -43,6 +44,7 @@
 #include "zkv_rzrouter_prep.h"
 #include "zkv_wire_rzrouter.h"
 #include "zkv_rzrouter_set.h"
+#include "zkv_wire_rzset.h"
 #include <sys/random.h>
 
 using namespace zkv;
@@ -108,11 +110,12 @@ struct SetGroupMem {
 };
 // RISC Zero router (run_router): per-instance totals, the compact second inputs, instance and method rows, every group slot's key, the
 // keyed routes' constants; h_*: the host calls' staging (a calldata batch is decoded into h_a, h_b, h_method); w_*: a calldata batch's
-// decoded slots, true lengths and call kinds; s_*, grp: the set route -- claim records, root-seal table, root indices, answers, section 16.
+// decoded slots, true lengths and call kinds, and on a router with a set route every request's whole-seal record and the arena of the
+// uint8[] requests; s_*, grp: the set route -- claim records, root-seal table, root indices, answers, section 16.
 struct RouterMem : DemuxMem {
     DevBuf<uint32_t> itot, inst, skey; DevBuf<uint8_t> b, kind; DevBuf<RzrRoute> routes;
     DevBuf<uint8_t> h_seals, h_a, h_b, h_st, h_rv, h_method; DevBuf<uint64_t> h_off;
-    DevBuf<uint8_t> w_seals, w_ck; DevBuf<uint32_t> w_len;
+    DevBuf<uint8_t> w_seals, w_ck, w_arena; DevBuf<uint32_t> w_len; DevBuf<RzsSpan> w_span;
     DevBuf<RzsRec> s_rec; DevBuf<uint32_t> s_owner, s_ridx, s_diag; DevBuf<uint8_t> s_ans; SetGroupMem grp;
 };
 // Key sets, Groth16 and PLONK (set_partition .. set_agg_plan): per-block counts, per-key totals, block offsets, every proof's position,
@@ -2354,7 +2357,8 @@ ZKV_EXPORT int zkv_risc0_router_verify_batch_dev(zkv_ctx* c, size_t n, const uin
 }
 // host buffers: in_b == nullptr selects verify_integrity; method: the per-seal method row (in_b is then set), or nullptr
 static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64_t* d_seal_off, uint64_t seal_bytes, const uint8_t* d_a, const uint8_t* d_b,
-                          uint8_t* d_status, uint8_t* d_recv, hipStream_t s, uint32_t fp_mask, uint32_t* d_diag);
+                          uint8_t* d_status, uint8_t* d_recv, hipStream_t s, uint32_t fp_mask, uint32_t* d_diag, const uint8_t* d_method = nullptr,
+                          const RzWireArgs* wire = nullptr, const RzsSpan* d_span = nullptr);
 static int router_host_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, const uint64_t* seal_off, const uint8_t* in_a, const uint8_t* in_b,
                              uint8_t* status, uint8_t* recv, const uint8_t* method = nullptr) {
     if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES || !offsets_ok(seal_off, n)) return ZKV_ERR_INVALID_ARG;
@@ -2371,7 +2375,8 @@ static int router_host_batch(zkv_ctx* c, size_t n, const uint8_t* seal_blob, con
     HIP_TRY(hipMemcpyAsync(rm.h_a, in_a, 32 * n, hipMemcpyHostToDevice, s));
     if (in_b) HIP_TRY(hipMemcpyAsync(rm.h_b, in_b, 32 * n, hipMemcpyHostToDevice, s));
     if (method) HIP_TRY(hipMemcpyAsync(rm.h_method, method, n, hipMemcpyHostToDevice, s));
-    if (c->rz_set) rc = run_router_set(c, n, rm.h_seals, rm.h_off, sbytes, rm.h_a, in_b ? rm.h_b : nullptr, rm.h_st, rm.h_rv, s, 0xFFFFFFFFu, nullptr);
+    if (c->rz_set) rc = run_router_set(c, n, rm.h_seals, rm.h_off, sbytes, rm.h_a, in_b ? rm.h_b : nullptr, rm.h_st, rm.h_rv, s, 0xFFFFFFFFu, nullptr,
+                                       method ? rm.h_method : nullptr);
     else rc = run_router(c, n, rm.h_seals, rm.h_off, sbytes, rm.h_a, in_b ? rm.h_b : nullptr, rm.h_st, rm.h_rv, s, method ? rm.h_method : nullptr);
     if (rc != ZKV_OK) return rc;
     return return_to_host(rm.h_st, rm.h_rv, n, status, recv, s);
@@ -4635,8 +4640,12 @@ ZKV_EXPORT int zkv_risc0_router_set_last_counts(zkv_ctx* c, uint64_t out[4]) {
 // run through run_router as a batch of 260-byte rows with true lengths.  Two synchronisations for a call of one chunk that has root
 // jobs: the direct seals' route counts (with the job count), the jobs' route counts.
 // d_diag (diagnostic): stop behind the identity kernel of the one chunk and write every claim's representative.
+// d_method: the per-seal method row (d_b is then set), or nullptr.  wire, d_span (decoded calldata, zkv_wire_rzset.h; d_seal_off is then
+// nullptr): the partition takes the decoder's fixed-stride slots with their true lengths, the set stage every request's record, a
+// distance from d_seals.  Chunk bases apply to the records as they do to the offsets.
 static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64_t* d_seal_off, uint64_t seal_bytes, const uint8_t* d_a, const uint8_t* d_b,
-                          uint8_t* d_status, uint8_t* d_recv, hipStream_t s, uint32_t fp_mask, uint32_t* d_diag) {
+                          uint8_t* d_status, uint8_t* d_recv, hipStream_t s, uint32_t fp_mask, uint32_t* d_diag, const uint8_t* d_method,
+                          const RzWireArgs* wire, const RzsSpan* d_span) {
     int rc;
     const size_t cap = n < SETINCL_CHUNK ? n : SETINCL_CHUNK, R = c->gw_sel.size();
     size_t table = 64;
@@ -4652,7 +4661,7 @@ static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const ui
     if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
     HIP_TRY(hipMemsetAsync(g.cnt, 0, 16, s));
     uint32_t seen[4] = {0, 0, 0, 0};
-    uint64_t jobs = 0;
+    uint64_t jobs = 0, direct_bad = 0;
     std::vector<uint64_t> direct;
     for (size_t base = 0; base < n; base += cap) {
         const size_t mc = n - base < cap ? n - base : cap;
@@ -4666,7 +4675,9 @@ static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const ui
         ch.status = d_status ? d_status + base : nullptr; ch.recv = d_recv ? d_recv + 4 * base : nullptr;
         RzsArgs a;
         memset(&a, 0, sizeof a);
-        a.seals = d_seals; a.seal_off = d_seal_off + base; a.seal_bytes = seal_bytes;
+        a.seals = d_seals; a.seal_off = d_seal_off ? d_seal_off + base : nullptr; a.seal_bytes = seal_bytes;
+        if (wire) { a.span = d_span + base; a.wire_len = wire->seal_len + base; }
+        a.method = d_method ? d_method + base : nullptr;
         a.set_sel = be32_of(c->si_set_sel); a.table = (uint32_t)table; a.fp_mask = fp_mask;
         a.rec = rm.s_rec; a.owner = rm.s_owner; a.root_idx = rm.s_ridx; a.ans = rm.s_ans;
         HIP_TRY(hipMemsetAsync(a.owner, 0xFF, 4 * table, s));
@@ -4683,9 +4694,10 @@ static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const ui
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(seen, g.cnt, sizeof seen, hipMemcpyDeviceToHost, s));
         if (base == 0) {
-            rc = run_router(c, n, d_seals, d_seal_off, seal_bytes, d_a, d_b, d_status, d_recv, s);
+            if (wire) rc = run_router(c, n, wire->seals, nullptr, 0, d_a, d_b, d_status, d_recv, s, d_method, wire->seal_len);
+            else rc = run_router(c, n, d_seals, d_seal_off, seal_bytes, d_a, d_b, d_status, d_recv, s, d_method);
             if (rc != ZKV_OK) { (void)hipStreamSynchronize(s); return rc; }      // (the copy into `seen` may still be in flight)
-            direct = c->rz_counts;
+            direct = c->rz_counts; direct_bad = c->rz_bad;                       // (the root jobs' partitions write both again)
         } else HIP_TRY(hipStreamSynchronize(s));
         const uint32_t nj = seen[0];
         if (nj > mc) return ZKV_ERR_HIP;
@@ -4707,7 +4719,7 @@ static int run_router_set(zkv_ctx* c, size_t n, const uint8_t* d_seals, const ui
     // the counts of the call: the Groth16 routes' are the caller's direct seals (not the root jobs); the set seals were seals of an
     // unknown selector to the partition
     if (direct.size() != R + 2 || direct[R] < seen[2]) return ZKV_ERR_HIP;
-    c->rz_counts = direct;
+    c->rz_counts = direct; c->rz_bad = direct_bad;
     for (size_t r = 0; r < R; r++) c->rzs_counts[r] = direct[r];
     c->rzs_counts[R] = seen[2]; c->rzs_counts[R + 1] = direct[R] - seen[2]; c->rzs_counts[R + 2] = direct[R + 1];
     c->rzs_last[0] = seen[2]; c->rzs_last[1] = seen[3]; c->rzs_last[2] = jobs; c->rzs_last[3] = seen[1];
@@ -4752,5 +4764,111 @@ ZKV_EXPORT int zkv_diag_rzset_groups(zkv_ctx* c, size_t n, const uint8_t* seal_b
     if ((rc = run_router_set(c, n, d_blob, rm.h_off, bytes, nullptr, nullptr, nullptr, nullptr, s, fp_mask, rm.s_diag)) != ZKV_OK) return rc;
     HIP_TRY(hipMemcpyAsync(out_rep, rm.s_diag, 4 * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return ZKV_OK;
+}
+
+// ------------------------------------------------------------------ RISC Zero router with a set route: per-seal methods and eth_call batches
+// (zkv_risc0_router_set_wire.h; parity unpinned).  The entry points of zkv_risc0_router_wire.h for seals of any
+// length, valid on every router.  Without a set route they are the ragged twins of those calls: the decoded-input call is run_router on
+// offsets with a method row, the calldata call is run_router_wire as it is.  With one, k_wire_rzset writes k_wire_rzrouter's slots for
+// the partition and, beside them, every request's whole-seal record for the set stage (run_router_set).
+ZKV_EXPORT int zkv_risc0_router_verify_call_ragged_dev(zkv_ctx* c, size_t n, const uint8_t* d_method, const uint8_t* d_seal_blob, const uint64_t* d_seal_off,
+                                                       uint64_t blob_bytes, const uint8_t* d_in_a, const uint8_t* d_in_b, uint8_t* d_status, uint8_t* d_recv,
+                                                       void* stream) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_seal_off || !d_in_a || !d_in_b || !d_status || (blob_bytes && !d_seal_blob))) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->rz_set) return run_router_set(c, n, d_seal_blob, d_seal_off, blob_bytes, d_in_a, d_in_b, d_status, d_recv, s, 0xFFFFFFFFu, nullptr, d_method);
+    return run_router(c, n, d_seal_blob, d_seal_off, blob_bytes, d_in_a, d_in_b, d_status, d_recv, s, d_method);
+}
+ZKV_EXPORT int zkv_risc0_router_verify_call_ragged(zkv_ctx* c, size_t n, const uint8_t* method, const uint8_t* seal_blob, const uint64_t* seal_off,
+                                                   const uint8_t* in_a, const uint8_t* in_b, uint8_t* status, uint8_t* recv) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!seal_blob || !seal_off || !in_a || !in_b || !status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    return router_host_batch(c, n, seal_blob, seal_off, in_a, in_b, status, recv, method);
+}
+// Calldata and its n + 1 offsets on the device, a router with a set route.  The decode is enqueued in front of the first count, so the
+// call synchronises where run_router_set does.  One base address for the records: the lower of the blob and the arena, so that every
+// start is a plain non-negative distance (as run_gateway_wire).
+static int run_router_set_wire(zkv_ctx* c, size_t n, const uint8_t* d_cd, const uint64_t* d_off, uint64_t cd_bytes, uint8_t* d_status, uint8_t* d_recv,
+                               uint8_t* d_ck, hipStream_t s) {
+    int rc;
+    RouterMem& rm = c->m_rz;
+    if ((rc = grow_all(rm.w_seals, (size_t)ZKV_SEAL_BYTES * n + 8, rm.w_len, 4 * n, rm.h_a, 32 * n, rm.h_b, 32 * n, rm.h_method, n, rm.w_span, sizeof(RzsSpan) * n,
+                       rm.w_arena, (size_t)rzsw_arena_bytes(cd_bytes))) != ZKV_OK) return rc;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    RzSetWireArgs w;
+    memset(&w, 0, sizeof w);
+    w.w.n = n; w.w.cd = d_cd; w.w.off = d_off; w.w.cd_bytes = cd_bytes;
+    for (int k = 0; k < RZW_KINDS; k++) w.w.sel_be[k] = be32_of(router_call_selector(k));
+    w.w.seals = rm.w_seals; w.w.seal_len = rm.w_len; w.w.in_a = rm.h_a; w.w.in_b = rm.h_b; w.w.method = rm.h_method;
+    w.w.call_kind = d_ck;
+    w.set_sel = be32_of(c->si_set_sel); w.arena = rm.w_arena; w.span = rm.w_span;
+    const uintptr_t pc = (uintptr_t)d_cd, pa = (uintptr_t)w.arena, base = pc < pa ? pc : pa;
+    w.cd_delta = pc - base; w.arena_delta = pa - base;
+    (void)hipEventRecord(c->ev_wire[0], s);
+    launch_wire_rzset(w, s);
+    (void)hipEventRecord(c->ev_wire[1], s);
+    c->wire_timed = true;
+    HIP_TRY(hipGetLastError());
+    return run_router_set(c, n, (const uint8_t*)base, nullptr, 0, w.w.in_a, w.w.in_b, d_status, d_recv, s, 0xFFFFFFFFu, nullptr, w.w.method, &w.w, w.span);
+}
+ZKV_EXPORT int zkv_risc0_router_eth_call_ragged_dev(zkv_ctx* c, size_t n, const uint8_t* d_calldata, const uint64_t* d_calldata_off, uint64_t calldata_bytes,
+                                                    uint8_t* d_status, uint8_t* d_recv, uint8_t* d_call_kind, void* stream) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_calldata || !d_calldata_off || !d_status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->rz_set) return run_router_set_wire(c, n, d_calldata, d_calldata_off, calldata_bytes, d_status, d_recv, d_call_kind, s);
+    return run_router_wire(c, n, d_calldata, d_calldata_off, calldata_bytes, d_status, d_recv, d_call_kind, s);
+}
+ZKV_EXPORT int zkv_risc0_router_eth_call_ragged(zkv_ctx* c, size_t n, const uint8_t* blob, const uint64_t* off, uint8_t* reverted, uint8_t* returndata,
+                                                uint32_t* returndata_len, uint8_t* status) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (n && (!blob || !off || !reverted || !returndata || !returndata_len)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u / ZKV_SEAL_BYTES || !offsets_ok(off, n)) return ZKV_ERR_INVALID_ARG;
+    std::vector<uint8_t> st(n), rv(4 * n), ck(n);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        int rc = ctx_device_init(c);
+        if (rc != ZKV_OK) return rc;
+        RouterMem& rm = c->m_rz;
+        if ((rc = grow_all(rm.h_st, n, rm.h_rv, 4 * n, rm.w_ck, n)) != ZKV_OK) return rc;
+        hipStream_t s = c->stream;
+        if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+        std::vector<uint64_t> rel;
+        uint64_t bytes = 0;
+        if ((rc = stage_ragged(rm.h_seals, rm.h_off, blob, off, n, &rel, s, &bytes)) != ZKV_OK) return rc;
+        if (c->rz_set) rc = run_router_set_wire(c, n, rm.h_seals, rm.h_off, bytes, rm.h_st, rm.h_rv, rm.w_ck, s);
+        else rc = run_router_wire(c, n, rm.h_seals, rm.h_off, bytes, rm.h_st, rm.h_rv, rm.w_ck, s);
+        if (rc != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(ck.data(), rm.w_ck, n, hipMemcpyDeviceToHost, s));
+        if ((rc = return_to_host(rm.h_st, rm.h_rv, n, st.data(), rv.data(), s)) != ZKV_OK) return rc;
+    }
+    for (size_t i = 0; i < n; i++) {
+        const int rc = zkv_risc0_router_eth_call_returndata(c, st[i], rv.data() + 4 * i, ck[i], returndata + i * ZKV_RETURNDATA_STRIDE, &returndata_len[i], &reverted[i]);
+        if (rc != ZKV_OK) return rc;
+        if (status) status[i] = st[i];
+    }
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_risc0_router_last_ragged_call_counts(zkv_ctx* c, uint64_t* out) {
+    if (!c || c->vm != ZKV_VM_RISC0_ROUTER) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const std::vector<uint64_t>& v = c->rz_set ? c->rzs_counts : c->rz_counts;
+    for (size_t r = 0; r < v.size(); r++) out[r] = v[r];
+    out[v.size()] = c->rz_bad;
     return ZKV_OK;
 }

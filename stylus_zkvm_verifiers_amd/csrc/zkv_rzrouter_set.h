@@ -48,6 +48,15 @@ ZKV_HD RzsSeal rzs_parse(const uint8_t* seal, uint64_t len, bool al, uint32_t se
     return r;
 }
 
+// The seal of row i given as a record instead of a pair of offsets (decoded calldata: zkv_wire_rzset.h): `len` bytes from `at`, a
+// distance from RzsArgs::seals.  A request that is not a canonical call has {0, 0}.
+struct RzsSpan { uint64_t at; uint32_t len, pad; };
+
+// The claim digest of row i of a batch: true = in_a holds it (verifyIntegrity), false = it is ReceiptClaim::ok(in_a, in_b) (verify).
+// method: the per-row method bytes (ZKV_METHOD_*; rows with other bytes are no set seals) or nullptr: one method for the batch, verify
+// iff the batch has second inputs.
+ZKV_HD bool rzs_claim_given(const uint8_t* method, bool have_in_b, size_t i) { return method ? method[i] == 1 : !have_in_b; }
+
 // Root-seal identity.  The fingerprint of (length, first min(length, 260) bytes) only picks where a claim starts probing the table; two
 // root seals are one group iff rzs_equal says so.  Any alignment.  The fingerprint is the XOR of every word mixed with its position, so
 // that the lanes of a wavefront can each take words and combine them in any order (k_rzset_ident); the host walks the words in turn.
@@ -90,6 +99,9 @@ struct RzsRec { uint64_t path_at, root_at; uint32_t depth, root_len; };
 // and, summed over the call's chunks, [1] stored-root lookups, [2] set seals, [3] distinct root seals (slots taken).
 struct RzsArgs {
     const uint8_t* seals; const uint64_t* seal_off; uint64_t seal_bytes;       // the call's blob; the chunk's n + 1 offsets
+    const RzsSpan* span; const uint32_t* wire_len;                             // decoded calldata (seal_off == nullptr): the chunk's records and true
+                                                                               // lengths, 0xFFFFFFFF = not a canonical call; read by rzs_span alone
+    const uint8_t* method;                                                     // the chunk's method row, or nullptr (rzs_claim_given)
     uint32_t set_sel, table, fp_mask, pad;                                     // table: a power of two >= 2 n; fp_mask: ~0 (diagnostic: less)
     RzsRec* rec; uint32_t* owner; uint32_t* root_idx; uint8_t* ans;            // per seal; per slot: the claim that took it; per seal: the answer of a
                                                                                // claim that is SETINCL_DONE (written to status by the scatter)

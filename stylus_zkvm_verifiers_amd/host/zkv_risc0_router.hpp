@@ -1,7 +1,7 @@
 // C++ host wrapper of the RISC Zero verifier router (include/zkv_risc0_router.h): `IRiscZeroVerifier::verify` / `verify_integrity` with
 // the verifier chosen per seal by its first 4 bytes, as RISC Zero's on-chain RiscZeroVerifierRouter does.  Library/runtime failures throw
 // std::runtime_error; statuses (ZKV_STATUS_*, ZKV_STATUS_ROUTE_NOT_FOUND) are never exceptions.  Parity unpinned: the reference holds no
-// router.
+// router.  RiscZeroSetRouter is the router with a set route (include/zkv_risc0_router_set.h, zkv_risc0_router_set_wire.h).
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/zkv_risc0_router.h"
+#include "../../include/zkv_risc0_router_set_wire.h"
 
 namespace zkv {
 
@@ -29,18 +30,8 @@ public:
 
     // Route order: the built-in-key routes, then the keyed routes; every selector is derived
     RiscZeroRouter(const std::vector<RiscZeroBuiltinRoute>& builtin, const std::vector<RiscZeroKeyedRoute>& keyed, int device = 0) {
-        std::vector<uint8_t> roots, ids, kroots, kids; std::vector<const uint8_t*> keys;
-        for (const auto& r : builtin) {
-            if (r.control_root.size() != 32 || r.bn254_control_id.size() != 32) throw std::invalid_argument("RiscZeroRouter: control parameters must be 32 bytes");
-            roots.insert(roots.end(), r.control_root.begin(), r.control_root.end()); ids.insert(ids.end(), r.bn254_control_id.begin(), r.bn254_control_id.end());
-        }
-        for (const auto& r : keyed) {
-            if (r.vk_words.size() != ZKV_RISC0_KEY_BYTES) throw std::invalid_argument("RiscZeroRouter: a keyed route takes a key with n_ic = 6");
-            if (r.control_root.size() != 32 || r.bn254_control_id.size() != 32) throw std::invalid_argument("RiscZeroRouter: control parameters must be 32 bytes");
-            keys.push_back(r.vk_words.data());
-            kroots.insert(kroots.end(), r.control_root.begin(), r.control_root.end()); kids.insert(kids.end(), r.bn254_control_id.begin(), r.bn254_control_id.end());
-        }
-        ctx_ = zkv_risc0_router_create(builtin.size(), roots.data(), ids.data(), keyed.size(), keys.data(), kroots.data(), kids.data(), device);
+        const Packed p(builtin, keyed);
+        ctx_ = zkv_risc0_router_create(builtin.size(), p.roots.data(), p.ids.data(), keyed.size(), p.keys.data(), p.kroots.data(), p.kids.data(), device);
         if (!ctx_) throw std::invalid_argument("zkv_risc0_router_create rejected the routes");
     }
     RiscZeroRouter(RiscZeroRouter&& o) noexcept : ctx_(o.ctx_) { o.ctx_ = nullptr; }
@@ -117,8 +108,85 @@ public:
     }
     zkv_ctx* handle() const { return ctx_; }
 
-private:
+protected:
+    // the creators' argument rows
+    struct Packed {
+        std::vector<uint8_t> roots, ids, kroots, kids; std::vector<const uint8_t*> keys;
+        Packed(const std::vector<RiscZeroBuiltinRoute>& builtin, const std::vector<RiscZeroKeyedRoute>& keyed) {
+            for (const auto& r : builtin) {
+                if (r.control_root.size() != 32 || r.bn254_control_id.size() != 32) throw std::invalid_argument("RiscZeroRouter: control parameters must be 32 bytes");
+                roots.insert(roots.end(), r.control_root.begin(), r.control_root.end()); ids.insert(ids.end(), r.bn254_control_id.begin(), r.bn254_control_id.end());
+            }
+            for (const auto& r : keyed) {
+                if (r.vk_words.size() != ZKV_RISC0_KEY_BYTES) throw std::invalid_argument("RiscZeroRouter: a keyed route takes a key with n_ic = 6");
+                if (r.control_root.size() != 32 || r.bn254_control_id.size() != 32) throw std::invalid_argument("RiscZeroRouter: control parameters must be 32 bytes");
+                keys.push_back(r.vk_words.data());
+                kroots.insert(kroots.end(), r.control_root.begin(), r.control_root.end()); kids.insert(kids.end(), r.bn254_control_id.begin(), r.bn254_control_id.end());
+            }
+        }
+    };
+    explicit RiscZeroRouter(zkv_ctx* adopted) : ctx_(adopted) {}
     zkv_ctx* ctx_ = nullptr;
+};
+
+// The router plus the RiscZeroSetVerifier of one set-builder image id, registered under its own selector with the router itself as its
+// inner verifier: the last route.  verify / verify_integrity / verify_batch take set-inclusion seals beside Groth16 seals;
+// verify_batch_dev (a fixed stride cannot hold a set seal) fails on such a router: use verify_ragged_dev.
+class RiscZeroSetRouter : public RiscZeroRouter {
+public:
+    RiscZeroSetRouter(const uint8_t set_builder_image_id[32], const std::vector<RiscZeroBuiltinRoute>& builtin, const std::vector<RiscZeroKeyedRoute>& keyed,
+                      int device = 0) : RiscZeroRouter(create(set_builder_image_id, builtin, keyed, device)) {}
+
+    std::vector<uint8_t> set_selector() const {
+        std::vector<uint8_t> out(4);
+        const int rc = zkv_risc0_router_set_selector(ctx_, out.data());
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_risc0_router_set_selector failed with ZKV error " + std::to_string(rc));
+        return out;
+    }
+    // status of the router's verify(seal, ID, sha256(ID || root)); the root is remembered when that is ZKV_STATUS_OK
+    uint8_t submit_root(const uint8_t root[32], const std::vector<uint8_t>& seal, uint8_t recv[4] = nullptr) {
+        uint8_t st = 0;
+        const int rc = zkv_risc0_router_set_submit_root(ctx_, root, seal.data(), seal.size(), &st, recv);
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_risc0_router_set_submit_root failed with ZKV error " + std::to_string(rc));
+        return st;
+    }
+    // Device-resident seals of any length: the blob and its n + 1 offsets; d_journal_digests = nullptr: verify_integrity
+    void verify_ragged_dev(size_t n, const uint8_t* d_seal_blob, const uint64_t* d_seal_off, uint64_t blob_bytes, const uint8_t* d_image_ids,
+                           const uint8_t* d_journal_digests, uint8_t* d_status, uint8_t* d_recv = nullptr, void* stream = nullptr) const {
+        const int rc = zkv_risc0_router_verify_ragged_dev(ctx_, n, d_seal_blob, d_seal_off, blob_bytes, d_image_ids, d_journal_digests, d_status, d_recv, stream);
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_risc0_router_verify_ragged_dev failed with ZKV error " + std::to_string(rc));
+    }
+    // A method per seal (ZKV_METHOD_*; empty: all verify) over ragged host buffers; in_b is not read for verifyIntegrity rows
+    void verify_call_batch(const std::vector<uint8_t>& method, const std::vector<uint8_t>& seal_blob, const std::vector<uint64_t>& seal_off,
+                           const std::vector<uint8_t>& in_a, const std::vector<uint8_t>& in_b, std::vector<uint8_t>& status, std::vector<uint8_t>& recv) const {
+        const size_t n = seal_off.empty() ? 0 : seal_off.size() - 1;
+        if (in_a.size() != 32 * n || in_b.size() != 32 * n || (!method.empty() && method.size() != n)) throw std::invalid_argument("RiscZeroSetRouter::verify_call_batch: buffer sizes");
+        status.assign(n, 0); recv.assign(4 * n, 0);
+        const uint8_t zero = 0;
+        const int rc = zkv_risc0_router_verify_call_ragged(ctx_, n, method.empty() ? nullptr : method.data(), seal_blob.empty() ? &zero : seal_blob.data(),
+                                                           seal_off.data(), in_a.data(), in_b.data(), status.data(), recv.data());
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_risc0_router_verify_call_ragged failed with ZKV error " + std::to_string(rc));
+    }
+    // eth_call requests in either calldata form, both methods: reverted[i], return / revert data i at returndata[i * ZKV_RETURNDATA_STRIDE ..)
+    // with returndata_len[i] bytes, status[i]
+    void eth_call_batch(const std::vector<uint8_t>& calldata_blob, const std::vector<uint64_t>& calldata_off, std::vector<uint8_t>& reverted,
+                        std::vector<uint8_t>& returndata, std::vector<uint32_t>& returndata_len, std::vector<uint8_t>& status) const {
+        const size_t n = calldata_off.empty() ? 0 : calldata_off.size() - 1;
+        reverted.assign(n, 0); returndata.assign(n * ZKV_RETURNDATA_STRIDE, 0); returndata_len.assign(n, 0); status.assign(n, 0);
+        const uint8_t zero = 0;
+        const int rc = zkv_risc0_router_eth_call_ragged(ctx_, n, calldata_blob.empty() ? &zero : calldata_blob.data(), calldata_off.data(), reverted.data(),
+                                                        returndata.data(), returndata_len.data(), status.data());
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_risc0_router_eth_call_ragged failed with ZKV error " + std::to_string(rc));
+    }
+
+private:
+    static zkv_ctx* create(const uint8_t set_id[32], const std::vector<RiscZeroBuiltinRoute>& builtin, const std::vector<RiscZeroKeyedRoute>& keyed, int device) {
+        const Packed p(builtin, keyed);
+        zkv_ctx* c = zkv_risc0_router_create_with_set(builtin.size(), p.roots.data(), p.ids.data(), keyed.size(), p.keys.data(), p.kroots.data(), p.kids.data(),
+                                                      set_id, device);
+        if (!c) throw std::invalid_argument("zkv_risc0_router_create_with_set rejected the routes");
+        return c;
+    }
 };
 
 }  // namespace zkv

@@ -62,8 +62,10 @@ def abi_encode_seal(path, root_seal):
 
 class RiscZeroSetRouter(RiscZeroRouter):
     """RiscZeroRouter(routes, keyed) plus the set route of `set_builder_image_id`: the last route, at most MAX_ROUTES routes in all.
-    verify / verify_integrity / verify_batch / verify_integrity_batch take set-inclusion seals beside Groth16 seals; the fixed-stride,
-    per-seal-method and eth_call entry points are out of scope on such a router (ZKV_ERR_WRONG_CTX)."""
+    verify / verify_integrity / verify_batch / verify_integrity_batch take set-inclusion seals beside Groth16 seals, and so do
+    verify_call_batch / verify_call_ragged_dev / eth_call_batch / eth_call_batch_dev, which go through the entry points of
+    include/zkv_risc0_router_set_wire.h (risc0_router_set_wire.py); only the fixed-stride calls verify_batch_dev and
+    verify_call_batch_dev are out of scope on such a router (ZKV_ERR_WRONG_CTX)."""
 
     def __init__(self, set_builder_image_id, routes=(), keyed=(), device=0):
         set_id = bytes(set_builder_image_id)
@@ -111,6 +113,29 @@ class RiscZeroSetRouter(RiscZeroRouter):
 
     def verify_ragged_dev(self, n, d_seal_blob, d_seal_off, blob_bytes, d_image_ids, d_journal_digests, d_status, d_recv=0, stream=0):
         verify_ragged_dev(self._h, n, d_seal_blob, d_seal_off, blob_bytes, d_image_ids, d_journal_digests, d_status, d_recv, stream)
+
+    # ---- a method per seal, and eth_call batches: RiscZeroRouter's methods and return shapes on seals of any length
+    def verify_call_batch(self, methods, seals, in_a, in_b):
+        from . import risc0_router_set_wire as w
+        return w.verify_call_ragged(self._h, methods, seals, in_a, in_b)
+
+    def verify_call_ragged_dev(self, n, d_method, d_seal_blob, d_seal_off, blob_bytes, d_in_a, d_in_b, d_status, d_recv=0, stream=0):
+        """verify_ragged_dev with n method bytes on the device (0: all verify); d_in_b is always a row of n x 32 bytes."""
+        from . import risc0_router_set_wire as w
+        w.verify_call_ragged_dev(self._h, n, d_method, d_seal_blob, d_seal_off, blob_bytes, d_in_a, d_in_b, d_status, d_recv, stream)
+
+    def eth_call_batch(self, calls):
+        from . import risc0_router_set_wire as w
+        return w.eth_call_ragged(self._h, calls)
+
+    def eth_call_batch_dev(self, n, d_calldata, d_calldata_off, calldata_bytes, d_status, d_recv=0, d_call_kind=0, stream=0):
+        from . import risc0_router_set_wire as w
+        w.eth_call_ragged_dev(self._h, n, d_calldata, d_calldata_off, calldata_bytes, d_status, d_recv, d_call_kind, stream)
+
+    def last_call_counts(self):
+        """last_route_counts (the set route under its own index) with one more column: bad calldata."""
+        from . import risc0_router_set_wire as w
+        return w.last_ragged_call_counts(self._h, self._L.zkv_risc0_router_route_count(self._h))
 
     def submit_root(self, root, seal):
         """(status, received selector) of the router's verify(seal, ID, sha256(ID || root)); the root is remembered when that is OK."""
