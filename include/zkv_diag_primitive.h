@@ -30,6 +30,7 @@ extern "C" {
  *     op 5  a b (Fr) x (raw 256-bit) (24) -> fr_mul(a,b) fr_add(a,b) fr_sub(a,b) fr_inv(a) fr_from_raw_reduce(x) (40)
  *     op 6  k (raw, 8) -> glv_split: |k1| (5 words) neg1 |k2| (5 words) neg2 (12)
  *     op 7  P (Jacobian x y z) Q (affine x y) T (Jacobian) (64) -> g1j_dbl(P) g1j_add_affine(P,Q) g1j_add(P,T) (72)
+ *     op 8  a b (Fp2, 32) -> f2_is_zero(a) f2_eq(a,b), one 0 / 1 word each (2)
  *   mapping 1, one case per lane pair (ZKV_PAIRED: the even lane holds c0, the odd lane c1):
  *     op 0  a b (Fp2, 32) -> f2_mul(a,b) f2_sqr(a) f2_mul_xi(a) f2_add(a,b) f2_sub(a,b) (80)
  *     op 1  n c k_even[8] k_odd[8] x_even[8][9] x_odd[8][9] (162) -> l9_lincomb of the first n (1..8; otherwise zeros) terms with
@@ -39,10 +40,18 @@ extern "C" {
  *           f12m_frob(a,1) (a,2) (a,3) f12m_mul_by_034(a; c0,c3,c4) f12m_mul_by_134(a; c3,c4) f12l9_mul(a,b) f12l9_mul(a,conj b),
  *           with a and the results in LDS slots (LRef; L9Ref for f12l9_*) and the S operand of f12l9_mul in the input row
  *     op 4  a (cyclotomic Fp12, 96) -> f12m_cyclo_sqr(a) f12l9_cyclo_sqr(a) (192)
+ *     ops 5-7, the accept predicates: every verdict is two 0 / 1 words, what the even lane returned and then what the odd lane returned
+ *     (the verify kernels store the status from the even lane alone)
+ *     op 5  a b (Fp2, 32) -> f2_is_zero(a) f2_eq(a,b) (4)
+ *     op 6  f t (Fp12, 192) -> f12m_is_one(f) with f in an LDS slot (LRef), f12m_is_one(f) with f read as a global row (SoaRW),
+ *           f12m_eq_conj(f, t) with f in the resident-limb accumulator (L9Ref) and t a global row (SoaRW) (6)
+ *     op 7  T (X Y Z, Fp2) bx by (Fp2) (80) -> miller_point_closes(T; bx, by) with T in an LDS slot (2)
  *   mapping 2 (one case per 16 lanes, S = 1) and mapping 3 (one case per wavefront, S = 4), zkv_tower_wide.h:
  *     op 0  a b c0 c3 c4 as for mapping 1 op 3 (240) -> eight Fp12 (768): w12_mul(a,b) w12_mul(a,conj b) w12_sqr(a)
  *           w12_mul_sparse(a; c0,c3,c4) w12_mul_sparse(a; 1,c3,c4) w12_frob(a,1) (a,2) (a,3)
- *     op 1  a (cyclotomic Fp12, 96) -> w12_cyclo_sqr(a) (96) */
+ *     op 1  a (cyclotomic Fp12, 96) -> w12_cyclo_sqr(a) (96)
+ *     op 2  f (Fp12, 96) -> f12m_is_one(f) with f in the group's accumulator slot as k_finalexp_w lays it out, one 0 / 1 word per lane of
+ *           the group in lane order (16 for mapping 2, 64 for mapping 3); word 0 is the lane that stores the status */
 int zkv_diag_primitive(int device, int mapping, int op, size_t n, const uint32_t* in, uint32_t* out);
 
 #ifdef __cplusplus

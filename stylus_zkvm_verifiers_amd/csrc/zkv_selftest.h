@@ -16,15 +16,15 @@ namespace zkv {
 
 // words per case of (mapping, op): in, out; false for an unknown pair
 inline bool selftest_io(int mapping, int op, int* in_w, int* out_w) {
-    static const int LANE[8][2] = {{24, 128}, {24, 16}, {16, 16}, {8, 8}, {32, 64}, {24, 40}, {8, 12}, {64, 72}};
-    static const int PAIR[5][2] = {{32, 80}, {162, 18}, {36, 18}, {240, 11 * 96}, {96, 2 * 96}};
-    static const int WIDE[2][2] = {{240, 8 * 96}, {96, 96}};
+    static const int LANE[9][2] = {{24, 128}, {24, 16}, {16, 16}, {8, 8}, {32, 64}, {24, 40}, {8, 12}, {64, 72}, {32, 2}};
+    static const int PAIR[8][2] = {{32, 80}, {162, 18}, {36, 18}, {240, 11 * 96}, {96, 2 * 96}, {32, 4}, {192, 6}, {80, 2}};
+    static const int WIDE[3][2] = {{240, 8 * 96}, {96, 96}, {96, 16}};          // op 2: one word per lane of the group, 16 S
     const int* w = nullptr;
-    if (mapping == 0 && op >= 0 && op < 8) w = LANE[op];
-    else if (mapping == 1 && op >= 0 && op < 5) w = PAIR[op];
-    else if ((mapping == 2 || mapping == 3) && op >= 0 && op < 2) w = WIDE[op];
+    if (mapping == 0 && op >= 0 && op < 9) w = LANE[op];
+    else if (mapping == 1 && op >= 0 && op < 8) w = PAIR[op];
+    else if ((mapping == 2 || mapping == 3) && op >= 0 && op < 3) w = WIDE[op];
     if (!w) return false;
-    *in_w = w[0]; *out_w = w[1];
+    *in_w = w[0]; *out_w = (mapping == 3 && op == 2) ? 4 * w[1] : w[1];
     return true;
 }
 // cases one wavefront holds in each mapping (the host pads a batch to whole wavefronts with zero operands)
@@ -101,6 +101,11 @@ ZKV_HD void selftest_lane(int op, const uint32_t* in, uint32_t* out) {
     case 7: {                // in P (Jacobian), Q (affine), R (Jacobian); out g1j_dbl(P), g1j_add_affine(P, Q), g1j_add(P, R)
         const G1J p = st_ldj(in), r = st_ldj(in + 40);
         st_stj(out, g1j_dbl(p)); st_stj(out + 24, g1j_add_affine(p, st_ld(in + 24), st_ld(in + 32))); st_stj(out + 48, g1j_add(p, r));
+        break;
+    }
+    case 8: {                // in a b (Fp2); out f2_is_zero(a), f2_eq(a, b) as 0 / 1 words
+        const Fp2 a = st_ld2(in), b = st_ld2(in + 16);
+        out[0] = f2_is_zero(a) ? 1u : 0u; out[1] = f2_eq(a, b) ? 1u : 0u;
         break;
     }
     default: break;
@@ -180,12 +185,50 @@ ZKV_HD void selftest_pair(int op, const uint32_t* in, uint32_t* out, uint32_t* l
         f12m_copy(acc, ga); f12l9_cyclo_sqr(acc); f12m_copy(m_ref(out + 96 + 8 * par, 1, 16), acc);
         break;
     }
+    // The accept predicates.  Every lane writes the verdict IT returns (even lane's word, then the odd lane's): the kernels store the
+    // status from one lane only, so both words must hold the combined verdict of the pair.
+    case 5: {                // in a b (Fp2); out f2_is_zero(a) (even, odd), f2_eq(a, b) (even, odd)
+        const Fp2 a = st_ldh(in, par), b = st_ldh(in + 16, par);
+        out[par] = f2_is_zero(a) ? 1u : 0u; out[2 + par] = f2_eq(a, b) ? 1u : 0u;
+        break;
+    }
+    case 6: {                // in f t (Fp12); out f12m_is_one(f) from an LDS slot, from a global row, f12m_eq_conj(f as the accumulator, t)
+        const LRef A = l_ref(lds);
+        const L9Ref acc = l9_ref(lds + 144 * 64);
+        const MRef gf = m_ref((uint32_t*)in + 8 * par, 1, 16);
+        SoaRW F; F.p = (uint32_t*)in; F.stride = 1; F.off = 32u * par;             // the rows fe_slot hands ISONE and EQCONJ
+        SoaRW T; T.p = (uint32_t*)in + 96; T.stride = 1; T.off = 32u * par;
+        f12m_copy(A, gf);
+        out[par] = f12m_is_one(A) ? 1u : 0u;
+        out[2 + par] = f12m_is_one(F) ? 1u : 0u;
+        f12m_copy(acc, gf);
+        out[4 + par] = f12m_eq_conj(acc, T) ? 1u : 0u;
+        break;
+    }
+    case 7: {                // in T (X Y Z, Fp2) bx by (Fp2); out miller_point_closes(T; bx, by), T in an LDS slot as k_miller2 holds it
+        const LRef tm = l_ref(lds + 48 * 64);
+        for (int k = 0; k < 3; k++) m_st_f2(tm, k, st_ldh(in + 16 * k, par));
+        const Fp2 bx = st_ldh(in + 48, par), by = st_ldh(in + 64, par);
+        out[par] = miller_point_closes(tm, bx, by) ? 1u : 0u;
+        break;
+    }
     default: break;
     }
 }
 
 // words of group memory per case of the wide mappings: slots a, b, d and the slices' rows
 constexpr int ST_WIDE_SLOT = 3 * 96 + W_RED_WORDS;
+// This lane's index in its 16 S-lane group (lane 0 is the one that stores the status in k_finalexp_w / k_finalexp_w64).  On the device
+// from the lane counter, as zkv_parity (blocks are whole wavefronts and groups are aligned): pairs 6 and 7, which shadow pairs 0 and 1,
+// have indices of their own.  The host emulation has no threads for those two pairs; its index follows from the coefficient and slice.
+template <int S> ZKV_HD int st_group_lane(WL w, uint32_t par) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)w; (void)par;
+    return (int)(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & (uint32_t)(16 * S - 1));
+#else
+    return 16 * w.s + 2 * w.q + (int)par;
+#endif
+}
 // one case, one lane of its 16 S-lane group.  g: the group's ST_WIDE_SLOT words (LDS on the device); w: this lane's coefficient and slice.
 template <int S> ZKV_HD void selftest_wide(int op, const uint32_t* in, uint32_t* out, uint32_t* g, WL w) {
     const uint32_t par = zkv_parity();
@@ -208,6 +251,15 @@ template <int S> ZKV_HD void selftest_wide(int op, const uint32_t* in, uint32_t*
     }
     case 1: {                // in a (cyclotomic Fp12); out w12_cyclo_sqr(a)
         w12_copy(D, ga, q); w12_cyclo_sqr<S>(D, w, red); put(0);
+        break;
+    }
+    case 2: {                // in f (Fp12); out f12m_is_one(acc) as THIS lane returns it, acc laid out as finalexp_w_body's accumulator
+        w12_copy(A, ga, q);
+        const int lane = st_group_lane<S>(w, par);
+        out[lane] = f12m_is_one(A) ? 1u : 0u;
+#if !defined(__HIP_DEVICE_COMPILE__)
+        if (q < 2) out[lane + 12] = out[lane];          // the host emulation has no shadow pairs: their words repeat pairs 0 and 1
+#endif
         break;
     }
     default: break;

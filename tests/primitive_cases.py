@@ -26,7 +26,8 @@ WP = [0, 2, 4, 1, 3, 5]          # slot index -> power of w
 # (mapping, op) -> (in words, out words): include/zkv.h
 IO = {(0, 0): (24, 128), (0, 1): (24, 16), (0, 2): (16, 16), (0, 3): (8, 8), (0, 4): (32, 64), (0, 5): (24, 40), (0, 6): (8, 12), (0, 7): (64, 72),
       (1, 0): (32, 80), (1, 1): (162, 18), (1, 2): (36, 18), (1, 3): (240, 11 * 96), (1, 4): (96, 192),
-      (2, 0): (240, 768), (2, 1): (96, 96), (3, 0): (240, 768), (3, 1): (96, 96)}
+      (2, 0): (240, 768), (2, 1): (96, 96), (3, 0): (240, 768), (3, 1): (96, 96),
+      (0, 8): (32, 2), (1, 5): (32, 4), (1, 6): (192, 6), (1, 7): (80, 2), (2, 2): (96, 16), (3, 2): (96, 64)}      # the accept predicates
 PER_WAVE = {0: 64, 1: 32, 2: 4, 3: 1}
 
 
@@ -61,6 +62,7 @@ def edge_fp4(): return edge_fp2() + [2 * P, 2 * P + 1, 3 * P, 3 * P + 1, 4 * P -
 def lane_cases(op, n, rng):
     e2, e4 = edge_fp2(), edge_fp4()
     if op == 0:
+        e2 = e2 + [1 << (32 * i) for i in range(8)] + [P ^ (1 << (32 * i)) for i in range(8)]      # one limb away from 0 and from p (fp_is_zero, fp_eq)
         edges = [[a, b, c] for a in e2 for b in (0, P, 2 * P - 1, a, (a + P) % (2 * P)) for c in (0, 2 * P - 1)]
         rnd = gen_stream(lambda: [rng.choice(e2) if rng.random() < 0.2 else rng.randrange(2 * P) for _ in range(3)])
         cs = place_edges(edges, rnd, n)
@@ -505,6 +507,383 @@ def check_wide_f12(ins, outs):
             assert _f12_out(wo, k) == want[k], (idx, nm)
 
 
+# ---------------------------------------------------------------- the accept predicates (0 / 1 words, one per lane)
+# f2_is_zero / f2_eq (mapping 0 op 8, mapping 1 op 5), f12m_is_one and f12m_eq_conj (mapping 1 op 6), miller_point_closes (mapping 1 op 7),
+# f12m_is_one on the wide accumulator (mappings 2 and 3, op 2).  A verdict is a conjunction over Fp components, so the reference lists
+# the components that MISS: none means true, exactly one is a "one component off" case, and its position is what the coverage
+# conditions of predicate_profile count.  Inputs are raw Montgomery integers below 2p; a true input is tried in every mix of x and x + p.
+PREDICATE_OPS = {(0, 8), (1, 5), (1, 6), (1, 7), (2, 2), (3, 2)}
+ONE_M = RM % P                                          # 1 in Montgomery form
+ODD_AT = {0: (0, 63), 1: (0, 15, 31), 2: (0, 3), 3: (0,)}       # where the odd case of a run sits in its wavefront
+G2C = m.f2pow(m.XI, (P ** 3 - 1) // 3)                  # psi^3 on the twist: (x, y) -> (conj(x) G2C, conj(y) G3C)
+G3C = m.f2pow(m.XI, (P ** 3 - 1) // 2)
+
+
+def truth_plan(n, per_wave, odd_at):
+    """(holds a true input?, zone) per case.  The first half of the wavefronts alternates true and false case by case (zones 'a', 'b': the
+    phase flips from one wavefront to the next, so false cases meet even and odd places); then runs of per_wave - 1 true cases with
+    one false (zone 's'), and the reverse, the odd one at odd_at; a last partial wavefront alternates.  One case per wavefront
+    (per_wave = 1) has no neighbours: T F F T, so that both kinds still meet even and odd indices."""
+    if per_wave == 1:
+        return [(k % 4 in (0, 3), 'ab'[(k // 4) % 2]) for k in range(n)]
+    waves = n // per_wave
+    runs = waves // 4
+    alt = waves - 2 * runs
+    plan = []
+    for w in range(waves):
+        for k in range(per_wave):
+            if w < alt:
+                plan.append(((k + w) % 2 == 0, 'a' if w < (alt + 1) // 2 else 'b'))
+            else:
+                r = w - alt
+                plan.append(((k == odd_at[r % len(odd_at)]) != (r < runs), 's'))
+    for k in range(n - len(plan)):
+        plan.append((k % 2 == 0, 'ab'[(k // 2) % 2]))
+    return plan
+
+
+def _mont(v): return v * RM % P
+
+
+def _reps(vals, rng, j):
+    """the j-th representative mix of canonical components: all canonical, all shifted by p, then seeded random mixes"""
+    if j == 0:
+        return list(vals)
+    if j == 1:
+        return [v + P for v in vals]
+    return [v + P if rng.random() < 0.5 else v for v in vals]
+
+
+def _near(r):
+    """the raw value r moved by one, and with the low or the high bit of one limb flipped; only values below 2p (the contract)"""
+    out = [r + 1, r - 1] + [r ^ (1 << (32 * i + b)) for i in range(8) for b in (0, 31)]
+    return [v for v in dict.fromkeys(out) if 0 <= v < 2 * P]
+
+
+def _one_off(tgt, positions, rng, unit=None):
+    """[(k, v)]: v replaces component k of the canonical vector tgt and is NOT congruent to it: the neighbours (_near) of both
+    representatives and, where `unit` is given, the other field's unit.  +-1 and a flip in limb 7, then the unit, come first (so that
+    even the shortest case list has a value that differs in the top limb alone); the positions
+    are interleaved in rotating order, so that a short prefix already covers all of them."""
+    per = []
+    for k in positions:
+        c = tgt[k]
+        first = [c + 1, c ^ (1 << 224), c + P - 1, (c + P) ^ (1 << 224)]
+        if k % 2:
+            first = first[2:] + first[:2]
+        first += ([unit(k)] if unit else []) + [c + P + 1, c - 1]
+        rest = [v for r in (c, c + P) for v in _near(r)]
+        rng.shuffle(rest)
+        vs = [v for v in dict.fromkeys(first + rest) if 0 <= v < 2 * P]
+        assert all((v - c) % P for v in vs)
+        per.append([(k, v) for v in vs])
+    out = []
+    for r in range(max(len(x) for x in per)):
+        for i in range(len(per)):
+            x = per[(i + r) % len(per)]
+            if r < len(x):
+                out.append(x[r])
+    return out
+
+
+def _assign(parities, entries):
+    """one entry (key, payload) per slot, the slot's parity given: among the next unused entries the first whose key (the altered
+    position) has not met this parity yet, so that every position meets even and odd places early; the list is cycled"""
+    pending, seen, out = [], {}, []
+    for par in parities:
+        if not pending:
+            pending = list(entries)
+        pick = next((i for i, (key, _) in enumerate(pending[:24]) if key is not None and par not in seen.get(key, ())), 0)
+        key, payload = pending.pop(pick)
+        seen.setdefault(key, set()).add(par)
+        out.append(payload)
+    return out
+
+
+def _fpw(vals):
+    w = []
+    for v in vals:
+        w += words(v)
+    return w
+
+
+def _cycle(xs):
+    while True:
+        for x in xs:
+            yield x
+
+
+def _fill(plan, true_of, false_entries, zoned=False):
+    """cases by plan: true_of(j, zone) makes the j-th true case; false_entries(zone) -> [(key, payload)] are dealt to the false places
+    (zone by zone where the zones take different lists)"""
+    out = [None] * len(plan)
+    for zone in ('a', 'b', 's') if zoned else ('abs',):
+        idx = [i for i, (t, z) in enumerate(plan) if z in zone and not t]
+        for i, c in zip(idx, _assign([i % 2 for i in idx], false_entries(zone))):
+            out[i] = c
+    j = 0
+    for i, (t, z) in enumerate(plan):
+        if t:
+            out[i] = true_of(j, z)
+            j += 1
+    return out
+
+
+# ---- f2_is_zero(a), f2_eq(a, b): a0 a1 b0 b1
+def f2_pred_cases(n, rng, mapping):
+    plan = truth_plan(n, PER_WAVE[mapping], ODD_AT[mapping])
+    nz = lambda: rng.randrange(1, P)
+
+    def true_of(j, zone):                       # in a run: both verdicts true; elsewhere also eq alone and is_zero alone
+        kind = 0 if zone == 's' else j % 4
+        if kind == 1:
+            a = [nz(), nz()]
+            return _fpw(_reps(a, rng, j // 4) + _reps(a, rng, 2))
+        if kind == 2:
+            return _fpw(_reps([0, 0], rng, j // 4) + [rng.randrange(1, 2 * P), rng.randrange(2 * P)])
+        return _fpw(_reps([0, 0, 0, 0], rng, j // 4 if zone != 's' else j))
+
+    ent = []
+    for k, v in _one_off([0, 0], (0, 1), rng, unit=lambda k: ONE_M):           # is_zero misses in component k alone; b is anything
+        a = _reps([0, 0], rng, 2)
+        a[k] = v
+        ent.append((('z', k), _fpw(a + [rng.randrange(1, 2 * P), rng.randrange(1, 2 * P)])))
+    eqs = []
+    for t in range(2):                                                           # eq misses in component k alone, a != 0
+        tgt = [nz(), nz()]
+        for j, (k, v) in enumerate(_one_off(tgt, (0, 1), rng)):
+            x, y = _reps(tgt, rng, 2), _reps(tgt, rng, 2)
+            y[k] = v
+            eqs.append((('e', k), _fpw(x + y if (j + t) % 2 else y + x)))
+    ent = [e for pair in zip(ent, eqs) for e in pair] + eqs[len(ent):]
+    a = [nz(), nz()]
+    shapes = [a + [a[0], P - a[1]], a + [a[1], a[0]], a + [P - a[0], P - a[1]], [0, P] + a]
+    ent[8:8] = [(None, _fpw(x)) for x in shapes]
+    return _fill(plan, true_of, lambda zone: ent)
+
+
+# ---- Fp12: twelve raw components in slot order (g0 g1 g2 h0 h1 h2, c0 then c1)
+def _one_tgt(): return [ONE_M] + [0] * 11
+def _f12_raw(t): return [_mont(c) for s in f12_to_slots(t) for c in s]
+def _conj_raw(raw): return [x % P for x in raw[:6]] + [-x % P for x in raw[6:]]
+
+
+def is_one_false_entries(rng):
+    """[(position or None, twelve components)]: 1 with one component off; then -1, 1 in another coefficient, 0"""
+    tgt = _one_tgt()
+    ent = []
+    for k, v in _one_off(tgt, range(12), rng, unit=lambda k: 0 if k == 0 else ONE_M):
+        x = _reps(tgt, rng, 2)
+        x[k] = v
+        ent.append((k, x))
+    shapes = [[P - ONE_M] + [0] * 11, [2 * P - ONE_M] + [P] * 11, [0] * 12, [P] * 12]
+    for k in range(1, 12):
+        x = _reps([0] * 12, rng, 2)
+        x[k] = ONE_M + (P if k % 2 else 0)
+        shapes.append(x)
+    ent[24:24] = [(None, x) for x in shapes]
+    return ent
+
+
+def _conj_pool():
+    r = random.Random(0xC0)
+    cyc = cyclotomic_pool()
+    return [_f12_raw(cyc[0]), _f12_raw([r.randrange(P) for _ in range(12)]), _f12_raw(m.f12mul(cyc[1], cyc[2])), _f12_raw([r.randrange(P) for _ in range(12)])]
+
+
+def eq_conj_false_entries(rng):
+    """[(position or None, f, t)]: t = conj(f) with one component off, for cyclotomic and generic f; then t = f, an h coefficient
+    (Fp2) of conj(f) with its sign restored, g negated instead of h"""
+    pool = _conj_pool()
+    lists = [_one_off(_conj_raw(f), range(12), rng) for f in pool]
+    ent = []
+    for j in range(max(len(x) for x in lists)):
+        f, lst = pool[j % len(pool)], lists[j % len(pool)]
+        if j < len(lst):
+            k, v = lst[j]
+            t = _reps(_conj_raw(f), rng, 2)
+            t[k] = v
+            ent.append((k, _reps(f, rng, 2) + t))
+    shapes = []
+    for f in pool[:2]:
+        shapes.append(_reps(f, rng, 2) + _reps(f, rng, 2))                                   # t = f, h != 0
+        for c in (3, 4, 5):
+            t = _conj_raw(f)
+            t[2 * c:2 * c + 2] = f[2 * c:2 * c + 2]
+            shapes.append(_reps(f, rng, 2) + _reps(t, rng, 2))
+        shapes.append(_reps(f, rng, 2) + _reps([-x % P for x in f[:6]] + f[6:], rng, 2))
+    ent[24:24] = [(None, x) for x in shapes]
+    return ent
+
+
+def pair_f12_pred_cases(n, rng):
+    """f t.  Zone 'a': f = 1 in every mix against f one component off (t = conj(f) throughout: eq_conj stays true); zone 'b': generic and
+    cyclotomic f with t = conj(f) against t one component off (is_one stays false); runs: all three verdicts true against all three false."""
+    plan = truth_plan(n, 32, ODD_AT[1])
+    pool = _conj_pool()
+
+    def true_of(j, zone):
+        if zone == 'b':
+            f = pool[j % len(pool)]
+            if j % 5 == 4:                      # h = 0 mod p: t = f is conj(f) as well
+                f = f[:6] + [0] * 6
+                return _fpw(_reps(f, rng, 2) + _reps(f, rng, 2))
+            return _fpw(_reps(f, rng, j // len(pool)) + _reps(_conj_raw(f), rng, 2 if j % 3 else (j // len(pool) + 1) % 2))
+        jj = j // 2 if zone == 'a' else j
+        mixes = [(0, 0), (1, 1), (0, 1), (1, 0)]
+        mf, mt = mixes[jj] if jj < 4 else (2, 2)
+        return _fpw(_reps(_one_tgt(), rng, mf) + _reps(_one_tgt(), rng, mt))
+
+    ones, conjs = is_one_false_entries(rng), eq_conj_false_entries(rng)
+
+    def false_entries(zone):
+        if zone == 'a':
+            return [(k, _fpw(f + _reps(_conj_raw(f), rng, 2))) for k, f in ones]
+        if zone == 'b':
+            return [(k, _fpw(x)) for k, x in conjs]
+        out = []
+        for j, (k, f) in enumerate(ones):       # runs: f is not 1 AND t is conj(f) with one component off
+            tgt = _conj_raw(f)
+            t = _reps(tgt, rng, 2)
+            t[j % 12] = _near(tgt[j % 12] + (P if j % 2 else 0))[(j // 12) % 4]
+            out.append((k, _fpw(f + t)))
+        return out
+    return _fill(plan, true_of, false_entries, zoned=True)
+
+
+def wide_is_one_cases(n, rng, mapping):
+    plan = truth_plan(n, PER_WAVE[mapping], ODD_AT[mapping])
+    ent = [(k, _fpw(f)) for k, f in is_one_false_entries(rng)]
+    return _fill(plan, lambda j, zone: _fpw(_reps(_one_tgt(), rng, j)), lambda zone: ent)
+
+
+# ---- miller_point_closes: X Y Z bx by (Fp2 each)
+def closing_xy(bx, by, z):
+    """value domain: the X, Y with (X, Y, z) = -psi^3((bx, by)) in the loop's coordinates (x = X / Z, y = Y / Z)"""
+    return m.f2mul(m.f2mul(m.f2conj(bx), G2C), z), m.f2neg(m.f2mul(m.f2mul(m.f2conj(by), G3C), z))
+
+
+def _closing_raw(bx, by, z):
+    x, y = closing_xy(bx, by, z)
+    return [_mont(c) for c in x + y + z + bx + by]
+
+
+def closes_cases(n, rng):
+    plan = truth_plan(n, 32, ODD_AT[1])
+    f2r = lambda: (rng.randrange(P), rng.randrange(1, P))
+    zs = [(1, 0), (0, 1), (P - 1, 0), (0, P - 1), (2, 0)]
+
+    def true_of(j, zone):
+        z = zs[j % 8] if j % 8 < len(zs) else f2r()
+        return _fpw(_reps(_closing_raw(f2r(), f2r(), z), rng, j // 8 if j % 8 == 7 else 2))
+
+    bases = [_closing_raw(f2r(), f2r(), z) for z in (f2r(), (1, 0), f2r(), (0, 5))]
+    lists = [_one_off(b, range(4), rng) for b in bases]
+    ent = []
+    for j in range(max(len(x) for x in lists)):
+        lst = lists[j % len(bases)]
+        if j < len(lst):
+            k, v = lst[j]
+            x = _reps(bases[j % len(bases)], rng, 2)
+            x[k] = v
+            ent.append((k, _fpw(x)))
+    shapes = []
+    for j in range(6):
+        bx, by, z = f2r(), f2r(), f2r()
+        good = _closing_raw(bx, by, z)
+        shapes.append(_reps(_closing_raw(bx, by, (0, 0)), rng, j))                           # T = (0, 0, 0): closes but for Z = 0 (or p)
+        shapes.append(good[:4] + _reps([0, 0], rng, j) + good[6:])                          # Z alone replaced by 0 (or p)
+        x, y = closing_xy(bx, by, z)
+        shapes.append(_reps([_mont(c) for c in x + m.f2neg(y) + z + bx + by], rng, 2))       # Y = +conj(by) g3 Z
+        shapes.append(_reps(good[:6] + [_mont(c) for c in m.f2conj(bx) + by], rng, 2))       # bx, then by, handed over conjugated
+        shapes.append(_reps(good[:6] + [_mont(c) for c in bx + m.f2conj(by)], rng, 2))
+        for k in (4, 5):                                                                     # Z one off: X and Y both miss
+            w = _reps(good, rng, 2)
+            w[k] = _near(good[k] + (P if j % 2 else 0))[j % 3]
+            shapes.append(w)
+    for j, x in enumerate(shapes):
+        ent.insert(8 + 3 * j, (None, _fpw(x)))
+    return _fill(plan, true_of, lambda zone: ent)
+
+
+def predicate_cases(mapping, op, n, rng):
+    if (mapping, op) in ((0, 8), (1, 5)):
+        return f2_pred_cases(n, rng, mapping)
+    if (mapping, op) == (1, 6):
+        return pair_f12_pred_cases(n, rng)
+    if (mapping, op) == (1, 7):
+        return closes_cases(n, rng)
+    return wide_is_one_cases(n, rng, mapping)
+
+
+def predicate_reference(mapping, op, wi):
+    """[(verdict, components that miss, holds?, lanes that return it)] of one case, from Python integers mod p"""
+    c = [_fp_of(wi, k) for k in range(len(wi) // 8)]
+    if (mapping, op) in ((0, 8), (1, 5)):
+        lanes = 1 if mapping == 0 else 2
+        z = [k for k in (0, 1) if c[k] % P]
+        e = [k for k in (0, 1) if (c[k] - c[2 + k]) % P]
+        return [('is_zero', z, not z, lanes), ('eq', e, not e, lanes)]
+    if (mapping, op) == (1, 6) or op == 2:
+        one = [k for k in range(12) if (c[k] - _one_tgt()[k]) % P]
+        if op == 2:
+            return [('is_one', one, not one, 16 if mapping == 2 else 64)]
+        cj = [k for k in range(12) if ((c[k] - c[12 + k]) if k < 6 else (c[k] + c[12 + k])) % P]
+        return [('is_one', one, not one, 2), ('is_one', one, not one, 2), ('eq_conj', cj, not cj, 2)]
+    v = [x * RI % P for x in c]
+    z = (v[4], v[5])
+    x, y = closing_xy((v[6], v[7]), (v[8], v[9]), z)
+    miss = [k for k in range(4) if v[k] != (x + y)[k]]
+    return [('closes', miss if z != (0, 0) else [], z != (0, 0) and not miss, 2)]
+
+
+def predicate_profile(mapping, op, ins):
+    """(expected words of every case, {(verdict, position): parities of the case indices at which that component alone misses})"""
+    want, cover = [], {}
+    for idx, wi in enumerate(as_array(ins, mapping, op)):
+        row = []
+        for name, miss, holds, lanes in predicate_reference(mapping, op, [int(x) for x in wi]):
+            row += [1 if holds else 0] * lanes
+            if len(miss) == 1:
+                cover.setdefault((name, miss[0]), set()).add(idx % 2)
+        want.append(row)
+    return want, cover
+
+
+PREDICATE_POSITIONS = {(0, 8): [('is_zero', 0), ('is_zero', 1), ('eq', 0), ('eq', 1)], (1, 7): [('closes', k) for k in range(4)],
+                       (1, 6): [(v, k) for v in ('is_one', 'eq_conj') for k in range(12)], (2, 2): [('is_one', k) for k in range(12)]}
+PREDICATE_POSITIONS[(1, 5)] = PREDICATE_POSITIONS[(0, 8)]
+PREDICATE_POSITIONS[(3, 2)] = PREDICATE_POSITIONS[(2, 2)]
+
+
+def assert_predicate_cases_bite(mapping, op, ins):
+    """on the reference alone: a quarter of the expected words are 1 and a quarter 0, and the one-component-off cases reach every
+    position at an even and at an odd case index (the two lane pairs of a DPP quad, the two halves of a row of groups)"""
+    want, cover = predicate_profile(mapping, op, ins)
+    flat = [b for row in want for b in row]
+    assert 4 * sum(flat) >= len(flat) and 4 * (len(flat) - sum(flat)) >= len(flat), (sum(flat), len(flat))
+    for key in PREDICATE_POSITIONS[(mapping, op)]:
+        assert cover.get(key) == {0, 1}, (key, cover.get(key))
+
+
+def check_predicates(mapping, op, ins, outs):
+    want, _ = predicate_profile(mapping, op, ins)
+    bad = []
+    for idx, (wi, wo, ww) in enumerate(zip(ins, outs, want)):
+        k = 0
+        for name, miss, holds, lanes in predicate_reference(mapping, op, wi):
+            got = list(wo[k:k + lanes])
+            if len(set(got)) != 1:
+                bad.append((idx, name, 'the lanes of the case disagree', got[:16], 'misses', miss))
+            elif got[0] != (1 if holds else 0):
+                bad.append((idx, name, 'every lane returned %d, the reference is %d' % (got[0], 1 if holds else 0), 'misses', miss))
+            k += lanes
+        assert k == len(wo) == len(ww)
+        if list(wo) != ww and not bad:
+            bad.append((idx, 'words', list(wo)[:16], ww[:16]))
+    assert not bad, 'op %d: %d failing verdicts, first %s' % (op, len(bad), bad[:4])
+
+
 # ---------------------------------------------------------------- runners
 def as_array(cases, mapping, op):
     iw = IO[(mapping, op)][0]
@@ -550,6 +929,8 @@ def run_host(mapping, op, ins):
 
 def cases_for(mapping, op, n, seed):
     rng = random.Random(seed * 1000 + mapping * 10 + op)
+    if (mapping, op) in PREDICATE_OPS:
+        return predicate_cases(mapping, op, n, rng)
     if mapping == 0:
         return lane_cases(op, n, rng)
     if mapping == 1:
@@ -560,6 +941,8 @@ def cases_for(mapping, op, n, seed):
 def check(mapping, op, ins, outs):
     ins = [list(map(int, r)) for r in as_array(ins, mapping, op)]
     outs = [list(map(int, r)) for r in outs]
+    if (mapping, op) in PREDICATE_OPS:
+        return check_predicates(mapping, op, ins, outs)
     if mapping == 0:
         return check_lane(op, ins, outs)
     if mapping == 1:

@@ -79,7 +79,7 @@ def test_lane_g1_jacobian_ops(lib):
 
 def test_small_batches_are_padded(lib):
     """1 and 31 cases (the rest of the wavefront, pair block or group runs on zero operands and is discarded)"""
-    for mapping, op in ((0, 1), (0, 7), (1, 0), (1, 3), (2, 1), (3, 1)):
+    for mapping, op in ((0, 1), (0, 7), (1, 0), (1, 3), (2, 1), (3, 1), (0, 8), (1, 5), (1, 6), (1, 7), (2, 2), (3, 2)):
         for n in (1, 31) if mapping < 2 else (1, 5):
             run(lib, mapping, op, n, seed=n)
 
@@ -120,3 +120,36 @@ def test_wide_one_wavefront_fp12_routines(lib):
 
 def test_wide_one_wavefront_cyclotomic_squaring(lib):
     run(lib, 3, 1, 9)
+
+
+# ---------------------------------------------------------------- the accept predicates, one 0 / 1 word per lane
+def run_predicates(lib, mapping, op, n):
+    """The cases must be able to tell a right predicate from a subtly wrong one (checked on the reference alone, before anything is
+    compared); then every lane of a case must return the reference's verdict -- the lane that stores the status in the verify kernels
+    (word 0 of each verdict) holds its partner's half only through the DPP exchange, which the host build does not run."""
+    pc.assert_predicate_cases_bite(mapping, op, pc.cases_for(mapping, op, n, 7))
+    run(lib, mapping, op, n)
+
+
+def test_lane_fp2_is_zero_and_eq(lib):
+    run_predicates(lib, 0, 8, 64 * 8 + 1)
+
+
+def test_pair_fp2_is_zero_and_eq_in_both_lanes(lib):
+    run_predicates(lib, 1, 5, 32 * 12 + 1)
+
+
+def test_pair_fp12_is_one_and_eq_conj_in_both_lanes(lib):
+    run_predicates(lib, 1, 6, 32 * 12 + 1)
+
+
+def test_pair_miller_point_closes_in_both_lanes(lib):
+    run_predicates(lib, 1, 7, 32 * 12 + 1)
+
+
+def test_wide_sixteen_lanes_is_one_in_every_lane(lib):
+    run_predicates(lib, 2, 2, 4 * 24 + 1)
+
+
+def test_wide_one_wavefront_is_one_in_every_lane(lib):
+    run_predicates(lib, 3, 2, 48 + 1)

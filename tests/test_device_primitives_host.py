@@ -10,15 +10,20 @@ import pytest
 import primitive_cases as pc
 
 
-@pytest.mark.parametrize('op,n', [(0, 600), (1, 600), (2, 300), (3, 300), (4, 600), (5, 300), (6, 300), (7, 200)])
+@pytest.mark.parametrize('op,n', [(0, 600), (1, 600), (2, 300), (3, 300), (4, 600), (5, 300), (6, 300), (7, 200), (8, 64 * 8 + 1)])
 def test_lane_ops_on_the_host_build(op, n):
     ins = pc.cases_for(0, op, n, 7)
+    if (0, op) in pc.PREDICATE_OPS:
+        pc.assert_predicate_cases_bite(0, op, ins)
     pc.check(0, op, ins, pc.run_host(0, op, ins))
 
 
-@pytest.mark.parametrize('mapping,op,n', [(1, 0, 200), (1, 1, 600), (1, 2, 300), (1, 3, 9), (1, 4, 9), (2, 0, 9), (2, 1, 9), (3, 0, 5), (3, 1, 5)])
+@pytest.mark.parametrize('mapping,op,n', [(1, 0, 200), (1, 1, 600), (1, 2, 300), (1, 3, 9), (1, 4, 9), (2, 0, 9), (2, 1, 9), (3, 0, 5), (3, 1, 5),
+                                          (1, 5, 32 * 12 + 1), (1, 6, 32 * 12 + 1), (1, 7, 32 * 12 + 1), (2, 2, 4 * 24 + 1), (3, 2, 48 + 1)])
 def test_pair_and_wide_ops_on_the_host_build(mapping, op, n):
     ins = pc.cases_for(mapping, op, n, 7)
+    if (mapping, op) in pc.PREDICATE_OPS:
+        pc.assert_predicate_cases_bite(mapping, op, ins)
     pc.check(mapping, op, ins, pc.run_host(mapping, op, ins))
 
 
@@ -35,6 +40,50 @@ def test_references_agree_with_spec_model():
     assert m.f12mul(c, pc.f12_conj(c)) == m.F12_ONE           # cyclotomic: the conjugate is the inverse
     lam = m.g1_mul((1, 2), pc.GLV_LAMBDA)                       # the GLV endomorphism: lambda (x, y) = (beta x, y), beta^3 = 1
     assert lam[1] == 2 and lam[0] != 1 and pow(lam[0], 3, m.P) == 1
+
+
+def test_predicate_references_agree_with_spec_model(g2_membership_points):
+    """The `closes` reference against spec_model's own Frobenius on the twist: T = -psi^3(B) closes for the G2 generator and for subgroup
+    points of the fixture, under any Z; for a twist point outside the subgroup the point the loop's 88 steps arrive at,
+    [6u+2]B + psi(B) - psi^2(B) (formed with the group law; the line formulas are not replayed), does not.  For a subgroup point that
+    sum IS -psi^3(B).  And is_one / eq_conj on the value-domain 1 and on a cyclotomic element and its inverse."""
+    import random
+    import spec_model as m
+    rng = random.Random(11)
+    H = lambda h: int(h, 16)
+    pts = []
+    for c in g2_membership_points:
+        xi, xr, yi, yr = (H(h) for h in c['point'])             # EIP-197 order
+        pt = ((xr, xi), (yr, yi))
+        if m.g2_on_curve(pt):
+            pts.append((pt, c['in_subgroup']))
+    inside = [m.G2_GEN] + [p for p, ok in pts if ok][:2]
+    outside = next(p for p, ok in pts if not ok)
+    assert len(inside) == 3 and all(m.g2_in_subgroup(p) for p in inside) and not m.g2_in_subgroup(outside)
+    psi = m.g2_frobenius
+
+    def loop_end(b): return m.g2_add(m.g2_add(m.g2_mul(b, m.ATE_LOOP), psi(b)), m.g2_neg(psi(psi(b))))
+
+    def verdict(t, b, z):
+        raw = [pc._mont(c) for c in m.f2mul(t[0], z) + m.f2mul(t[1], z) + z + b[0] + b[1]]
+        (name, miss, holds, lanes), = pc.predicate_reference(1, 7, pc._fpw(raw))
+        return holds
+    for b in inside:
+        t = m.g2_neg(psi(psi(psi(b))))
+        assert loop_end(b) == t
+        for z in ((1, 0), (rng.randrange(pc.P), rng.randrange(pc.P))):
+            assert verdict(t, b, z)
+            assert not verdict(m.g2_neg(t), b, z) and not verdict(t, m.g2_neg(b), z)
+    t = loop_end(outside)
+    assert t is not None and not verdict(t, outside, (1, 0)) and not verdict(t, outside, (rng.randrange(pc.P), rng.randrange(pc.P)))
+    cyc = pc.cyclotomic_pool()[1]
+    inv = m.f12pow(cyc, m.P ** 12 - 2)
+    one = pc.predicate_reference(1, 6, pc._fpw(pc._f12_raw(m.F12_ONE) + pc._f12_raw(m.F12_ONE)))
+    assert [r[2] for r in one] == [True, True, True]
+    rows = pc.predicate_reference(1, 6, pc._fpw(pc._f12_raw(cyc) + pc._f12_raw(inv)))
+    assert [r[2] for r in rows] == [False, False, True] and m.f12mul(cyc, inv) == m.F12_ONE
+    rows = pc.predicate_reference(1, 6, pc._fpw(pc._f12_raw(cyc) + pc._f12_raw(cyc)))
+    assert not rows[2][2] and rows[2][1] == list(range(6, 12))
 
 
 def test_header_declares_exactly_the_harness_symbols():
@@ -59,7 +108,7 @@ def test_diag_primitive_argument_checks():
     L = diag_primitive.lib()
     buf = np.zeros(4096, dtype=np.uint32)
     p = buf.ctypes.data_as(C.POINTER(C.c_uint32))
-    for mapping, op, n in ((0, 8, 1), (0, -1, 1), (1, 5, 1), (2, 2, 1), (3, 2, 1), (4, 0, 1), (-1, 0, 1), (0, 0, 0), (1, 3, 0), (0, 0, diag_primitive.MAX_CASES + 1)):
+    for mapping, op, n in ((0, 9, 1), (0, -1, 1), (1, 8, 1), (2, 3, 1), (3, 3, 1), (4, 0, 1), (-1, 0, 1), (0, 0, 0), (1, 3, 0), (0, 0, diag_primitive.MAX_CASES + 1)):
         assert L.zkv_diag_primitive(0, mapping, op, n, p, p) == _lib.ERR_INVALID_ARG, (mapping, op, n)
     assert L.zkv_diag_primitive(0, 0, 0, 1, None, p) == _lib.ERR_INVALID_ARG
     for dev in (-1, 99):                       # no such device (on a machine without a GPU every index is one)
