@@ -1,7 +1,7 @@
 /*
  * zkv_diag_primitive.h -- known-answer harness of the arithmetic primitives.  TEST ONLY: no verification path uses it.
  *
- * Runs operands the caller chooses through the library's own field, tower and G1 code on the device, in the mappings the verify
+ * Runs operands the caller chooses through the library's own field, tower, G1 and G2 code on the device, in the mappings the verify
  * kernels use (one value per lane, one case per lane pair, one per 16 lanes, one per wavefront), and returns the raw result words, so
  * that a test can check a primitive at the edges of its contract.  Companion of zkv.h (same library, same ZKV_OK / ZKV_ERR_* codes);
  * the case bodies are stylus_zkvm_verifiers_amd/csrc/zkv_selftest.h.
@@ -31,6 +31,12 @@ extern "C" {
  *     op 6  k (raw, 8) -> glv_split: |k1| (5 words) neg1 |k2| (5 words) neg2 (12)
  *     op 7  P (Jacobian x y z) Q (affine x y) T (Jacobian) (64) -> g1j_dbl(P) g1j_add_affine(P,Q) g1j_add(P,T) (72)
  *     op 8  a b (Fp2, 32) -> f2_is_zero(a) f2_eq(a,b), one 0 / 1 word each (2)
+ *     op 9  P (Jacobian x y z over Fp2, 48) Q (affine x y, 32) R (Jacobian, 48) (128) -> g2j_dbl(P) g2j_add_affine(P,Q) g2j_add(P,R)
+ *           g2j_psi(P) g2_mul_u(Q), 48 Jacobian words each, then g2j_eq(P,R) g2_on_twist(Q) g2_in_subgroup(Q), one 0 / 1 word each, and
+ *           five zero words (248).  Infinity is z = 0 (mod p).
+ *     op 10 T (homogeneous X Y Z, 48) Q Q2 (affine, 32 each) (112) -> line_dbl(T) and line_add(T,Q), each as T' l0 l1 l3 (96),
+ *           g2_frob_affine(Q) g2_frob2_affine(Q) (x y, 32 each), aff_dbl(Q) and aff_add(Q,Q2), each as the new point x y and the
+ *           line nl c as line_to_table lays it out (64) (384)
  *   mapping 1, one case per lane pair (ZKV_PAIRED: the even lane holds c0, the odd lane c1):
  *     op 0  a b (Fp2, 32) -> f2_mul(a,b) f2_sqr(a) f2_mul_xi(a) f2_add(a,b) f2_sub(a,b) (80)
  *     op 1  n c k_even[8] k_odd[8] x_even[8][9] x_odd[8][9] (162) -> l9_lincomb of the first n (1..8; otherwise zeros) terms with
@@ -46,12 +52,32 @@ extern "C" {
  *     op 6  f t (Fp12, 192) -> f12m_is_one(f) with f in an LDS slot (LRef), f12m_is_one(f) with f read as a global row (SoaRW),
  *           f12m_eq_conj(f, t) with f in the resident-limb accumulator (L9Ref) and t a global row (SoaRW) (6)
  *     op 7  T (X Y Z, Fp2) bx by (Fp2) (80) -> miller_point_closes(T; bx, by) with T in an LDS slot (2)
+ *     op 8  T (X Y Z, 48) Q (x y, 32) xs ys (Fp, 8 each) f (Fp12, 96) (192) -> the G2 steps as miller_loop_p runs them, T in the LDS slot
+ *           of k_miller2, Q re-read through a SoaRef row for every chord, f in an LDS slot; every step starts from the input T (816):
+ *           words   0  the tangent step as T' (read back from the slot) l0 l1 l3 (96)
+ *           words  96  the chord steps of kinds 1 2 3 4 -- with Q, -Q, psi(Q), -psi^2(Q) -- likewise (4 x 96)
+ *           words 480  f after the variable-line product with the tangent's line: f2_mul_fp(l1, xs) f2_mul_fp(l3, ys), then
+ *                      f12m_mul_by_034_body (96)
+ *           words 576  T after tangent, chord(Q), tangent (48)
+ *           words 624  g2m_line_dbl(T) and words 720 g2m_line_add(T, Q), the wrappers of miller_loop_m, as T' l0 l1 l3 (2 x 96): the
+ *                      same words as at 0 and at 96
+ *     op 9  Q (x y, 32) -> g2_on_twist(Q) g2_in_subgroup(Q), two 0 / 1 words each as for ops 5-7 (4)
  *   mapping 2 (one case per 16 lanes, S = 1) and mapping 3 (one case per wavefront, S = 4), zkv_tower_wide.h:
  *     op 0  a b c0 c3 c4 as for mapping 1 op 3 (240) -> eight Fp12 (768): w12_mul(a,b) w12_mul(a,conj b) w12_sqr(a)
  *           w12_mul_sparse(a; c0,c3,c4) w12_mul_sparse(a; 1,c3,c4) w12_frob(a,1) (a,2) (a,3)
  *     op 1  a (cyclotomic Fp12, 96) -> w12_cyclo_sqr(a) (96)
  *     op 2  f (Fp12, 96) -> f12m_is_one(f) with f in the group's accumulator slot as k_finalexp_w lays it out, one 0 / 1 word per lane of
- *           the group in lane order (16 for mapping 2, 64 for mapping 3); word 0 is the lane that stores the status */
+ *           the group in lane order (16 for mapping 2, 64 for mapping 3); word 0 is the lane that stores the status
+ *     op 3  T (48) Q (32) xs ys (8 each) f (Fp12, 96) L0 L1 (LineAffC: nl c, 32 each) lxs lys cxs cys (Fp, 8 each) (288) -> the line steps
+ *           and line products of miller_loop_w, the group's memory laid out as in k_wide.hip (f, T, 13 scratch Fp2, the slices' rows);
+ *           G = 8 pairs (mapping 2) or 32 pairs (mapping 3), STEP = 48 + 48 G, 2 STEP + 528 in all (1392 words for mapping 2, 3696 for mapping 3):
+ *           words 0             w_line_dbl(T): T' read from the slot (48), then l0 l1 l3 as EACH pair of the group returned them, 48
+ *                               words per pair in pair order (pair = lane / 2; pairs 6 and 7 of every 16 lanes are the shadow pairs)
+ *           words STEP          w_line_add(T, Q), likewise
+ *           words 2 STEP        f after var_line_mul_w with the tangent's line (96)
+ *           words 2 STEP + 96   f after fixed_lines_mul_w with (do_l, do_c) = (1, 1), (1, 0), (0, 1) (3 x 96)
+ *           words 2 STEP + 384  f after f12m_inv_w (96)
+ *           words 2 STEP + 480  T after w_line_dbl, w_line_add(Q), w_line_dbl (48) */
 int zkv_diag_primitive(int device, int mapping, int op, size_t n, const uint32_t* in, uint32_t* out);
 
 #ifdef __cplusplus

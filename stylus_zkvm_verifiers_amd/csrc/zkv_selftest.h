@@ -8,7 +8,7 @@
 //   mapping 2  one case per 16 lanes (zkv_tower_wide.h, S = 1), mapping 3  one case per wavefront (S = 4), slots laid out as in k_wide.hip.
 // The bodies are ZKV_HD so that the host emulations (tests/host_sim) run the same code on the same cases.
 // Words: every Fp / Fr is eight little-endian 32-bit words (a Montgomery-domain integer, not necessarily reduced); an Fp2 is c0 then c1;
-// an Fp12 is six Fp2 in slot order g0 g1 g2 h0 h1 h2 (powers 0 2 4 1 3 5 of w), 96 words.  Layouts per op: include/zkv.h.
+// an Fp12 is six Fp2 in slot order g0 g1 g2 h0 h1 h2 (powers 0 2 4 1 3 5 of w), 96 words.  Layouts per op: include/zkv_diag_primitive.h.
 #pragma once
 #include <stdint.h>
 
@@ -16,15 +16,17 @@ namespace zkv {
 
 // words per case of (mapping, op): in, out; false for an unknown pair
 inline bool selftest_io(int mapping, int op, int* in_w, int* out_w) {
-    static const int LANE[9][2] = {{24, 128}, {24, 16}, {16, 16}, {8, 8}, {32, 64}, {24, 40}, {8, 12}, {64, 72}, {32, 2}};
-    static const int PAIR[8][2] = {{32, 80}, {162, 18}, {36, 18}, {240, 11 * 96}, {96, 2 * 96}, {32, 4}, {192, 6}, {80, 2}};
-    static const int WIDE[3][2] = {{240, 8 * 96}, {96, 96}, {96, 16}};          // op 2: one word per lane of the group, 16 S
+    static const int LANE[11][2] = {{24, 128}, {24, 16}, {16, 16}, {8, 8}, {32, 64}, {24, 40}, {8, 12}, {64, 72}, {32, 2}, {128, 248}, {112, 384}};
+    static const int PAIR[10][2] = {{32, 80}, {162, 18}, {36, 18}, {240, 11 * 96}, {96, 2 * 96}, {32, 4}, {192, 6}, {80, 2}, {192, 816}, {32, 4}};
+    static const int WIDE[4][2] = {{240, 8 * 96}, {96, 96}, {96, 16}, {288, 0}};     // op 2: one word per lane of the group, 16 S; op 3: below
     const int* w = nullptr;
-    if (mapping == 0 && op >= 0 && op < 9) w = LANE[op];
-    else if (mapping == 1 && op >= 0 && op < 8) w = PAIR[op];
-    else if ((mapping == 2 || mapping == 3) && op >= 0 && op < 3) w = WIDE[op];
+    if (mapping == 0 && op >= 0 && op < 11) w = LANE[op];
+    else if (mapping == 1 && op >= 0 && op < 10) w = PAIR[op];
+    else if ((mapping == 2 || mapping == 3) && op >= 0 && op < 4) w = WIDE[op];
     if (!w) return false;
     *in_w = w[0]; *out_w = (mapping == 3 && op == 2) ? 4 * w[1] : w[1];
+    // wide op 3: two line steps of T' (48) and three coefficients (48) per pair of the group (8 S pairs), five Fp12, the chain's T
+    if (mapping >= 2 && op == 3) *out_w = 2 * (48 + 48 * 8 * (mapping == 3 ? 4 : 1)) + 5 * 96 + 48;
     return true;
 }
 // cases one wavefront holds in each mapping (the host pads a batch to whole wavefronts with zero operands)
@@ -52,6 +54,8 @@ ZKV_HD void st_stj(uint32_t* w, const G1J& p) { st_st(w, p.x); st_st(w + 8, p.y)
 ZKV_HD G1J st_ldj(const uint32_t* w) { G1J p; p.x = st_ld(w); p.y = st_ld(w + 8); p.z = st_ld(w + 16); return p; }
 ZKV_HD Fp2 st_ld2(const uint32_t* w) { Fp2 r; r.c0 = st_ld(w); r.c1 = st_ld(w + 8); return r; }
 ZKV_HD void st_st2(uint32_t* w, const Fp2& a) { st_st(w, a.c0); st_st(w + 8, a.c1); }
+ZKV_HD G2J st_ldj2(const uint32_t* w) { G2J p; p.x = st_ld2(w); p.y = st_ld2(w + 16); p.z = st_ld2(w + 32); return p; }
+ZKV_HD void st_stj2(uint32_t* w, const G2J& p) { st_st2(w, p.x); st_st2(w + 16, p.y); st_st2(w + 32, p.z); }
 
 // one case, one lane
 ZKV_HD void selftest_lane(int op, const uint32_t* in, uint32_t* out) {
@@ -106,6 +110,37 @@ ZKV_HD void selftest_lane(int op, const uint32_t* in, uint32_t* out) {
     case 8: {                // in a b (Fp2); out f2_is_zero(a), f2_eq(a, b) as 0 / 1 words
         const Fp2 a = st_ld2(in), b = st_ld2(in + 16);
         out[0] = f2_is_zero(a) ? 1u : 0u; out[1] = f2_eq(a, b) ? 1u : 0u;
+        break;
+    }
+    case 9: {                // in P (Jacobian x y z, Fp2) Q (affine) R (Jacobian); out g2j_dbl(P) g2j_add_affine(P, Q) g2j_add(P, R) g2j_psi(P) g2_mul_u(Q),
+                             // then g2j_eq(P, R), g2_on_twist(Q), g2_in_subgroup(Q) as 0 / 1 words and five zero words
+        const G2J p = st_ldj2(in), r = st_ldj2(in + 80);
+        const Fp2 qx = st_ld2(in + 48), qy = st_ld2(in + 64);
+        st_stj2(out, g2j_dbl(p)); st_stj2(out + 48, g2j_add_affine(p, qx, qy)); st_stj2(out + 96, g2j_add(p, r)); st_stj2(out + 144, g2j_psi(p));
+        st_stj2(out + 192, g2_mul_u(qx, qy));
+        for (int k = 240; k < 248; k++) out[k] = 0;
+        out[240] = g2j_eq(p, r) ? 1u : 0u; out[241] = g2_on_twist(qx, qy) ? 1u : 0u; out[242] = g2_in_subgroup(qx, qy) ? 1u : 0u;
+        break;
+    }
+    case 10: {               // in T (homogeneous X Y Z, Fp2) Q Q2 (affine); out line_dbl(T), line_add(T, Q) as (T', l0, l1, l3), g2_frob_affine(Q),
+                             // g2_frob2_affine(Q), aff_dbl(Q), aff_add(Q, Q2) as (T', nl, c) with the line passed through line_to_table
+        const Fp2 qx = st_ld2(in + 48), qy = st_ld2(in + 64), q2x = st_ld2(in + 80), q2y = st_ld2(in + 96);
+        Fp2 l0, l1, l3;
+        G2H T; T.x = st_ld2(in); T.y = st_ld2(in + 16); T.z = st_ld2(in + 32);
+        line_dbl(T, l0, l1, l3);
+        st_st2(out, T.x); st_st2(out + 16, T.y); st_st2(out + 32, T.z); st_st2(out + 48, l0); st_st2(out + 64, l1); st_st2(out + 80, l3);
+        T.x = st_ld2(in); T.y = st_ld2(in + 16); T.z = st_ld2(in + 32);
+        line_add(T, qx, qy, l0, l1, l3);
+        st_st2(out + 96, T.x); st_st2(out + 112, T.y); st_st2(out + 128, T.z); st_st2(out + 144, l0); st_st2(out + 160, l1); st_st2(out + 176, l3);
+        Fp2 x, y;
+        g2_frob_affine(x, y, qx, qy); st_st2(out + 192, x); st_st2(out + 208, y);
+        g2_frob2_affine(x, y, qx, qy); st_st2(out + 224, x); st_st2(out + 240, y);
+        for (int k = 0; k < 2; k++) {
+            G2A A; A.x = qx; A.y = qy;
+            const LineAffC L = line_to_table(k == 0 ? aff_dbl(A) : aff_add(A, q2x, q2y));
+            uint32_t* o = out + 256 + 64 * k;
+            st_st2(o, A.x); st_st2(o + 16, A.y); st_st(o + 32, L.nl.c0); st_st(o + 40, L.nl.c1); st_st(o + 48, L.c.c0); st_st(o + 56, L.c.c1);
+        }
         break;
     }
     default: break;
@@ -212,12 +247,56 @@ ZKV_HD void selftest_pair(int op, const uint32_t* in, uint32_t* out, uint32_t* l
         out[par] = miller_point_closes(tm, bx, by) ? 1u : 0u;
         break;
     }
+    // The G2 steps of the Miller loop as miller_loop_p runs them: T in the LDS slot k_miller2 keeps it in, B re-read through a SoaRef row
+    // for every chord, the scalings of A' through another, f in an LDS slot.  Every step starts from the input T.
+    case 8: {                // in T (X Y Z) Q (x y) xs ys (Fp) f (Fp12); out the results listed in include/zkv_diag_primitive.h
+        const LRef fm = l_ref(lds), tm = l_ref(lds + 48 * 64);
+        SoaRef bsrc; bsrc.p = in + 48; bsrc.stride = 1; bsrc.off = 32u * par;
+        SoaRef norm; norm.p = in + 80; norm.stride = 1; norm.off = 0;
+        auto load_t = [&]() { for (int k = 0; k < 3; k++) m_st_f2(tm, k, st_ldh(in + 16 * k, par)); };
+        auto step = [&](int kind, Fp2& l0, Fp2& l1, Fp2& l3) {          // the body of `if (do_t)` in miller_loop_p
+            G2H T; T.x = m_ld_f2(tm, 0); T.y = m_ld_f2(tm, 1); T.z = m_ld_f2(tm, 2);
+            if (kind == 0) line_dbl(T, l0, l1, l3);
+            else {
+                Fp2 qx, qy; qx.h = bsrc.fp(0); qy.h = bsrc.fp(16);
+                if (kind == 2) qy = f2_neg(qy);
+                else if (kind == 3) { Fp2 x, y; g2_frob_affine(x, y, qx, qy); qx = x; qy = y; }
+                else if (kind == 4) { Fp2 x, y; g2_frob2_affine(x, y, qx, qy); qx = x; qy = f2_neg(y); }
+                line_add(T, qx, qy, l0, l1, l3);
+            }
+            m_st_f2(tm, 0, T.x); m_st_f2(tm, 1, T.y); m_st_f2(tm, 2, T.z);
+        };
+        auto put = [&](uint32_t* o, const Fp2& l0, const Fp2& l1, const Fp2& l3) {
+            for (int k = 0; k < 3; k++) st_st(o + 16 * k + 8 * par, m_ld_f2(tm, k).h);
+            st_st(o + 48 + 8 * par, l0.h); st_st(o + 64 + 8 * par, l1.h); st_st(o + 80 + 8 * par, l3.h);
+        };
+        Fp2 l0, l1, l3, t0, t1, t3;
+        load_t(); step(0, t0, t1, t3); put(out, t0, t1, t3);
+        for (int kind = 1; kind <= 4; kind++) { load_t(); step(kind, l0, l1, l3); put(out + 96 * kind, l0, l1, l3); }
+        f12m_copy(fm, m_ref((uint32_t*)in + 96 + 8 * par, 1, 16));
+        {
+            const Fp2 c3 = f2_mul_fp(t1, norm.fp(0)), c4 = f2_mul_fp(t3, norm.fp(8));
+            f12m_mul_by_034_body(fm, t0, c3, c4);
+        }
+        f12m_copy(m_ref(out + 480 + 8 * par, 1, 16), fm);
+        load_t(); step(0, l0, l1, l3); step(1, l0, l1, l3); step(0, l0, l1, l3);
+        for (int k = 0; k < 3; k++) st_st(out + 576 + 16 * k + 8 * par, m_ld_f2(tm, k).h);
+        load_t(); g2m_line_dbl(tm, &l0, &l1, &l3); put(out + 624, l0, l1, l3);          // the wrappers of miller_loop_m
+        const Fp2 qx = st_ldh(in + 48, par), qy = st_ldh(in + 64, par);
+        load_t(); g2m_line_add(tm, &qx, &qy, &l0, &l1, &l3); put(out + 720, l0, l1, l3);
+        break;
+    }
+    case 9: {                // in Q (x y); out g2_on_twist(Q) (even, odd), g2_in_subgroup(Q) (even, odd), as k_g2chk2 forms them
+        const Fp2 qx = st_ldh(in, par), qy = st_ldh(in + 16, par);
+        out[par] = g2_on_twist(qx, qy) ? 1u : 0u; out[2 + par] = g2_in_subgroup(qx, qy) ? 1u : 0u;
+        break;
+    }
     default: break;
     }
 }
 
-// words of group memory per case of the wide mappings: slots a, b, d and the slices' rows
-constexpr int ST_WIDE_SLOT = 3 * 96 + W_RED_WORDS;
+// words of group memory per case of the wide mappings: slots a, b, d and the slices' rows, or k_wide.hip's f, T, 13 scratch Fp2 and rows
+constexpr int ST_WIDE_SLOT = 96 + 48 + 13 * 16 + W_RED_WORDS;
 // This lane's index in its 16 S-lane group (lane 0 is the one that stores the status in k_finalexp_w / k_finalexp_w64).  On the device
 // from the lane counter, as zkv_parity (blocks are whole wavefronts and groups are aligned): pairs 6 and 7, which shadow pairs 0 and 1,
 // have indices of their own.  The host emulation has no threads for those two pairs; its index follows from the coefficient and slice.
@@ -260,6 +339,42 @@ template <int S> ZKV_HD void selftest_wide(int op, const uint32_t* in, uint32_t*
 #if !defined(__HIP_DEVICE_COMPILE__)
         if (q < 2) out[lane + 12] = out[lane];          // the host emulation has no shadow pairs: their words repeat pairs 0 and 1
 #endif
+        break;
+    }
+    // The line steps and line products of miller_loop_w and the inversion of final_exp_is_one_w, the group's memory laid out as in
+    // k_wide.hip: f, T (3 Fp2), the 13 scratch Fp2 `sc`, the slices' rows.  Every step starts from the input T, every product from f.
+    case 3: {                // in T Q xs ys f L0 L1 lxs lys cxs cys; out the results listed in include/zkv_diag_primitive.h
+        const MRef fm = A, tm = m_ref(base + 96, 1, 16), sc = m_ref(base + 144, 1, 16), rd = m_ref(base + 352, 1, 16);
+        const MRef gf = m_ref((uint32_t*)in + 96 + 8 * par, 1, 16);
+        const Fp2 qx = st_ldh(in + 48, par), qy = st_ldh(in + 64, par);
+        G1Norm n; n.axs = st_ld(in + 80); n.ays = st_ld(in + 88); n.lxs = st_ld(in + 256); n.lys = st_ld(in + 264); n.cxs = st_ld(in + 272); n.cys = st_ld(in + 280);
+        LineAffC L[2];
+        for (int k = 0; k < 2; k++) {
+            L[k].nl.c0 = st_ld(in + 192 + 32 * k); L[k].nl.c1 = st_ld(in + 200 + 32 * k); L[k].c.c0 = st_ld(in + 208 + 32 * k); L[k].c.c1 = st_ld(in + 216 + 32 * k);
+        }
+        const int pi = st_group_lane<S>(w, par) >> 1;          // this pair's place among the 8 S pairs of the group
+        constexpr int STEP = 48 + 48 * 8 * S;
+        auto load_t = [&]() { wide_sync(); for (int k = 0; k < 3; k++) m_st_f2(tm, k, st_ldh(in + 16 * k, par)); wide_fence(); };
+        auto put_t = [&](uint32_t* o) { for (int k = 0; k < 3; k++) st_st(o + 16 * k + 8 * par, m_ld_f2(tm, k).h); };
+        auto put_l = [&](uint32_t* o, const Fp2& l0, const Fp2& l1, const Fp2& l3) {          // this pair's OWN copy of the coefficients
+            uint32_t* c = o + 48 + 48 * pi + 8 * par;
+            st_st(c, l0.h); st_st(c + 16, l1.h); st_st(c + 32, l3.h);
+#if !defined(__HIP_DEVICE_COMPILE__)
+            if (q < 2) { st_st(c + 48 * 6, l0.h); st_st(c + 48 * 6 + 16, l1.h); st_st(c + 48 * 6 + 32, l3.h); }      // no shadow pairs on the host: theirs repeat pairs 0 and 1
+#endif
+        };
+        auto put_f = [&](uint32_t* o) { w12_copy(m_ref(o + 8 * par, 1, 16), fm, q); };
+        Fp2 l0, l1, l3, t0, t1, t3;
+        load_t(); w_line_dbl(tm, sc, &t0, &t1, &t3, q); put_t(out); put_l(out, t0, t1, t3);
+        load_t(); w_line_add(tm, sc, &qx, &qy, &l0, &l1, &l3, q); put_t(out + STEP); put_l(out + STEP, l0, l1, l3);
+        uint32_t* of = out + 2 * STEP;
+        w12_copy(fm, gf, q); var_line_mul_w<S>(fm, sc, t0, t1, t3, n.axs, n.ays, w, rd); put_f(of);
+        for (int k = 0; k < 3; k++) {               // (do_l, do_c) = (1, 1) (1, 0) (0, 1)
+            w12_copy(fm, gf, q); fixed_lines_mul_w<S>(fm, sc, L[0], L[1], n, k != 2, k != 1, w, rd); put_f(of + 96 * (1 + k));
+        }
+        w12_copy(fm, gf, q); f12m_inv_w(fm); put_f(of + 4 * 96);
+        load_t(); w_line_dbl(tm, sc, &l0, &l1, &l3, q); w_line_add(tm, sc, &qx, &qy, &l0, &l1, &l3, q); w_line_dbl(tm, sc, &l0, &l1, &l3, q);
+        put_t(of + 5 * 96);
         break;
     }
     default: break;

@@ -13,3 +13,7 @@ extern "C" int hs_selftest(int mapping, int op, size_t n, const uint32_t* in, ui
     for (size_t i = 0; i < n; i++) selftest_lane(op, in + i * (size_t)iw, out + i * (size_t)ow);
     return 0;
 }
+// the (in, out) words per case of (mapping, op) as selftest_io states them; -1 for a pair this build does not run
+extern "C" int hs_selftest_io(int mapping, int op, int* in_w, int* out_w) {
+    return (mapping != 0 || !selftest_io(mapping, op, in_w, out_w)) ? -1 : 0;
+}

@@ -1,7 +1,8 @@
 // Host build of the known-answer harness (stylus_zkvm_verifiers_amd/csrc/zkv_selftest.h), lane pairs and wide groups: the same case
 // bodies k_selftest_pair.hip runs, every lane played by a thread.  The DPP exchange inside a pair is a shared slot and a two-thread
 // barrier; the lockstep of a wide group (every load of a routine before its stores) and the work-group fence are a rendezvous of the
-// group's threads (12 S: pairs 6 and 7 of the device only shadow pairs 0 and 1).  TEST ONLY.
+// group's threads (12 S: pairs 6 and 7 of the device only shadow pairs 0 and 1; where an op returns one word group per pair, theirs
+// repeat those of pairs 0 and 1).  TEST ONLY.
 #define ZKV_PAIRED 1
 #include <atomic>
 #include <stddef.h>
@@ -74,4 +75,8 @@ extern "C" int hs_selftest(int mapping, int op, size_t n, const uint32_t* in, ui
     }
     for (auto& t : ts) t.join();
     return 0;
+}
+// the (in, out) words per case of (mapping, op) as selftest_io states them; -1 for a pair this build does not run
+extern "C" int hs_selftest_io(int mapping, int op, int* in_w, int* out_w) {
+    return (mapping < 1 || !selftest_io(mapping, op, in_w, out_w)) ? -1 : 0;
 }

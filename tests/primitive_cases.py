@@ -2,7 +2,7 @@
 stylus_zkvm_verifiers_amd/csrc/zkv_selftest.h).  Shared by the GPU test (tests/test_device_primitives_gpu.py) and its CPU counterpart
 (tests/test_device_primitives_host.py), which runs the same cases through host builds of the same header (tests/host_sim).
 
-Operands are Montgomery-domain integers (R = 2^261 for Fp and Fr); expectations come from Python integers and, for Fp12 and G1, from
+Operands are Montgomery-domain integers (R = 2^261 for Fp and Fr); expectations come from Python integers and, for Fp12, G1 and G2, from
 oracle/spec_model.py.  Every generator puts its edge operands first (lane 0, both lanes of the first pair, the first group), again at the
 end of the first wavefront and the start of the second (lanes 63 / 64, across a pair / group boundary), and fills the rest at random."""
 import ctypes as C
@@ -23,11 +23,13 @@ RIR = pow(RM, -1, RR)            # Fr
 M29 = (1 << 29) - 1
 WP = [0, 2, 4, 1, 3, 5]          # slot index -> power of w
 
-# (mapping, op) -> (in words, out words): include/zkv.h
+# (mapping, op) -> (in words, out words): include/zkv_diag_primitive.h
 IO = {(0, 0): (24, 128), (0, 1): (24, 16), (0, 2): (16, 16), (0, 3): (8, 8), (0, 4): (32, 64), (0, 5): (24, 40), (0, 6): (8, 12), (0, 7): (64, 72),
       (1, 0): (32, 80), (1, 1): (162, 18), (1, 2): (36, 18), (1, 3): (240, 11 * 96), (1, 4): (96, 192),
       (2, 0): (240, 768), (2, 1): (96, 96), (3, 0): (240, 768), (3, 1): (96, 96),
-      (0, 8): (32, 2), (1, 5): (32, 4), (1, 6): (192, 6), (1, 7): (80, 2), (2, 2): (96, 16), (3, 2): (96, 64)}      # the accept predicates
+      (0, 8): (32, 2), (1, 5): (32, 4), (1, 6): (192, 6), (1, 7): (80, 2), (2, 2): (96, 16), (3, 2): (96, 64),      # the accept predicates
+      (0, 9): (128, 248), (0, 10): (112, 384), (1, 8): (192, 816), (1, 9): (32, 4),                                # G2 and the line steps
+      (2, 3): (288, 2 * (48 + 48 * 8) + 5 * 96 + 48), (3, 3): (288, 2 * (48 + 48 * 32) + 5 * 96 + 48)}
 PER_WAVE = {0: 64, 1: 32, 2: 4, 3: 1}
 
 
@@ -884,6 +886,521 @@ def check_predicates(mapping, op, ins, outs):
     assert not bad, 'op %d: %d failing verdicts, first %s' % (op, len(bad), bad[:4])
 
 
+# ---------------------------------------------------------------- G2: Jacobian group ops, membership, Miller line steps
+# mapping 0 op 9 (group ops), op 10 (line steps, one value per lane); mapping 1 op 8 (the steps as miller_loop_p runs them), op 9
+# (g2_on_twist / g2_in_subgroup in both lanes); mappings 2, 3 op 3 (w_line_dbl, w_line_add and the wide line products).
+# The Jacobian ops are compared as group elements with spec_model's affine group law (which never uses the curve constant: a point off
+# the twist lies on y^2 = x^3 + b' for its own b', and P, Q, R of one case are multiples of one point); the line steps with the formulas
+# of zkv_curve.h restated over spec_model's f2* helpers (line_dbl_ref, line_add_ref, aff_*_ref -- checked on their own against the
+# group law in test_line_references_agree_with_spec_model).
+#
+# Shares, asserted on the reference alone (assert_g2_cases_bite).  The category of case k of wavefront w is c = (k + w) % 4, so every
+# category meets even and odd case indices and the first and the last case of a wavefront.  (place_edges is not used here: it puts a
+# list of edges at the start of the batch and across the FIRST wavefront boundary only, while these conditions ask for both values of a
+# verdict at the first and last case of wavefronts and at both parities, i.e. for edge and regular cases side by side in EVERY wavefront,
+# group and pair block.)
+#   membership   c = 0 subgroup, 1 off the twist, 2 on the twist outside the subgroup, 3 psi image of a subgroup point / outside / off the
+#                twist, in turn: on_twist 2/3 ones, 1/3 zeros; in_subgroup 1/3 ones, 1/3 zeros (the verdict of a point off the twist is
+#                not defined: raw_g2_valid never asks for it)
+#   g2j_eq       1 for (k / 2 + w) even: half ones
+#   line steps   c = 0, 2 regular (Z' != 0 in all three), 1: T = (0 : Y : 0) or Z = 0 (Z' = 0 after the tangent, the chord and the chain),
+#                3: T = Q, T = -Q (chord only), Y = 0 (tangent and chain), 2 T = Q (chain only) in turn: zeros 5/16, 3/8, 3/8
+G2_OPS = {(0, 9), (0, 10), (1, 8), (1, 9), (2, 3), (3, 3)}
+INV2 = pow(2, -1, P)
+B3 = m.f2smul(m.B2, 3)
+GOLDEN = os.path.join(HERE, 'golden')
+
+
+def f2sqr(a): return m.f2mul(a, a)
+def f2dbl(a): return m.f2add(a, a)
+def f2tpl(a): return m.f2smul(a, 3)
+def f2half(a): return m.f2smul(a, INV2)
+def f2inv0(a): return (0, 0) if a == (0, 0) else m.f2inv(a)          # f2_inv(0) = 0
+
+
+def line_dbl_ref(T):
+    """zkv_curve.h line_dbl: (T', l0, l1, l3), homogeneous projective T"""
+    X, Y, Z = T
+    a = f2half(m.f2mul(X, Y)); b = f2sqr(Y); c = f2sqr(Z)
+    e = m.f2mul(B3, c); f = f2tpl(e); g = f2half(m.f2add(b, f))
+    h = m.f2sub(f2sqr(m.f2add(Y, Z)), m.f2add(b, c)); j = f2sqr(X); e2 = f2sqr(e)
+    T2 = (m.f2mul(a, m.f2sub(b, f)), m.f2sub(f2sqr(g), f2tpl(e2)), m.f2mul(b, h))
+    return T2, m.f2neg(h), f2tpl(j), m.f2sub(e, b)
+
+
+def line_add_ref(T, Q):
+    """zkv_curve.h line_add"""
+    X, Y, Z = T
+    qx, qy = Q
+    theta = m.f2sub(Y, m.f2mul(qy, Z)); lam = m.f2sub(X, m.f2mul(qx, Z))
+    c = f2sqr(theta); d = f2sqr(lam); e = m.f2mul(lam, d); f = m.f2mul(Z, c); g = m.f2mul(X, d)
+    h = m.f2sub(m.f2add(e, f), f2dbl(g))
+    T2 = (m.f2mul(lam, h), m.f2sub(m.f2mul(theta, m.f2sub(g, h)), m.f2mul(e, Y)), m.f2mul(Z, e))
+    return T2, lam, m.f2neg(theta), m.f2sub(m.f2mul(theta, qx), m.f2mul(lam, qy))
+
+
+def aff_dbl_ref(T):
+    """zkv_curve.h aff_dbl: ((x3, y3), nl, c)"""
+    x, y = T
+    lam = m.f2mul(f2tpl(f2sqr(x)), f2inv0(f2dbl(y)))
+    x3 = m.f2sub(f2sqr(lam), f2dbl(x))
+    return (x3, m.f2sub(m.f2mul(lam, m.f2sub(x, x3)), y)), m.f2neg(lam), m.f2sub(m.f2mul(lam, x), y)
+
+
+def aff_add_ref(T, Q):
+    x, y = T
+    lam = m.f2mul(m.f2sub(Q[1], y), f2inv0(m.f2sub(Q[0], x)))
+    x3 = m.f2sub(m.f2sub(f2sqr(lam), x), Q[0])
+    return (x3, m.f2sub(m.f2mul(lam, m.f2sub(x, x3)), y)), m.f2neg(lam), m.f2sub(m.f2mul(lam, x), y)
+
+
+def psi2(pt): return m.g2_frobenius(m.g2_frobenius(pt))
+
+
+def step_q(Q, kind):
+    """the chord operand of step kind 1..4 of ZKV_MILLER_STEP_KIND: Q, -Q, psi(Q), -psi^2(Q)"""
+    return [None, Q, m.g2_neg(Q), m.g2_frobenius(Q), m.g2_neg(psi2(Q))][kind]
+
+
+def chain_ref(T, Q):
+    """T after tangent, chord(Q), tangent"""
+    T = line_dbl_ref(T)[0]
+    T = line_add_ref(T, Q)[0]
+    return line_dbl_ref(T)[0]
+
+
+def proj_to_aff(T):
+    if T[2] == (0, 0):
+        return None
+    zi = m.f2inv(T[2])
+    return (m.f2mul(T[0], zi), m.f2mul(T[1], zi))
+
+
+_G2_POOLS = None
+_IN_SUB = {}
+OUT_MEMBERSHIP, OUT_KATS = [], []      # the twist points outside the subgroup by fixture: g2_membership_points, precompile_kats['g2_subgroup']
+
+
+def outside_walk():
+    """the points outside the subgroup in the order the line cases use them: a small-order point of precompile_kats, a point of
+    g2_membership_points, and so on in turn -- the shortest case list (49 cases, about a dozen such Q) holds some of both"""
+    g2_pools()
+    k = max(len(OUT_KATS), len(OUT_MEMBERSHIP))
+    return [pool[i % len(pool)] for i in range(k) for pool in (OUT_KATS, OUT_MEMBERSHIP)]
+
+
+def g2_pools():
+    """(subgroup points, twist points outside the subgroup) -- the generator and multiples, and the points of tests/golden"""
+    global _G2_POOLS
+    if _G2_POOLS is None:
+        import json
+        r = random.Random(0x62)
+        sub = [m.G2_GEN, m.g2_mul(m.G2_GEN, 2), m.g2_neg(m.G2_GEN)] + [m.g2_mul(m.G2_GEN, r.randrange(1, RR)) for _ in range(5)]
+        out = []
+        H = lambda h: int(h, 16)
+        pts = json.load(open(os.path.join(GOLDEN, 'g2_membership_points.json')))['points']
+        n_membership = len(pts)
+        pts += [c for c in json.load(open(os.path.join(GOLDEN, 'precompile_kats.json')))['g2_subgroup'] if c.get('on_twist', True)]
+        for k, c in enumerate(pts):
+            xi, xr, yi, yr = (H(h) for h in c['point'])             # EIP-197 order
+            pt = ((xr, xi), (yr, yi))
+            if max(xi, xr, yi, yr) < P and m.g2_on_curve(pt) and pt not in sub and pt not in out:
+                (sub if c['in_subgroup'] else out).append(pt)
+                if not c['in_subgroup']:
+                    (OUT_MEMBERSHIP if k < n_membership else OUT_KATS).append(pt)
+        for pt in sub:
+            _IN_SUB[pt] = _IN_SUB[m.g2_frobenius(pt)] = True
+        for pt in out:
+            _IN_SUB[pt] = False
+        assert len(sub) >= 12 and len(OUT_MEMBERSHIP) >= 20 and len(OUT_KATS) >= 4
+        _G2_POOLS = (sub, out)
+    return _G2_POOLS
+
+
+def in_subgroup_ref(pt):
+    if pt not in _IN_SUB:
+        _IN_SUB[pt] = m.g2_in_subgroup(pt)
+    return _IN_SUB[pt]
+
+
+def _f2r(rng): return (rng.randrange(P), rng.randrange(P))
+def _f2nz(rng): return (rng.randrange(1, P), rng.randrange(1, P))
+def _f2w(c, rng): return words(_mont_rep(c[0], rng)) + words(_mont_rep(c[1], rng))
+def _f2_of(w, k): return (_fp_of(w, 2 * k) * RI % P, _fp_of(w, 2 * k + 1) * RI % P)
+
+
+def category(idx, n, per_wave):
+    """(category 0..3, wavefront, place in it) of case idx: (k + w) % 4; a closing partial wavefront starts with category 1; one case
+    per wavefront: the phase moves on every four, so that a category meets even and odd indices"""
+    w, k = divmod(idx, per_wave)
+    if per_wave == 1:
+        return (w + w // 4) % 4, w, 0
+    if w == n // per_wave:
+        return (1, 2, 0, 3)[k % 4], w, k
+    return (k + w) % 4, w, k
+
+
+OFF_TWIST = [((0, 0), (0, 0)), ((0, 0), (1, 0)), ((1, 0), (0, 0)), ((1, 0), (1, 0)), ((P - 1, 0), (0, 1)), ((0, 1), (P - 1, P - 1)), ((P - 1, P - 1), (1, 1)),
+             ((0, P - 1), (0, 0)), ((2, 0), (0, 3))]
+
+
+def membership_point(c, j, rng):
+    """the j-th point of category c (see the shares above)"""
+    sub, out = g2_pools()
+    if c == 0:
+        return sub[j % len(sub)]
+    if c == 2 or (c == 3 and j % 3 == 1):
+        return out[(j if c == 2 else j // 3 + 7) % len(out)]
+    if c == 3 and j % 3 == 0:
+        return m.g2_frobenius(sub[(j // 3) % len(sub)])
+    if c == 3:
+        j = 3 * (j // 3) + 1 + (j // 3) % 2               # off the twist: a twist point with a coordinate altered, or random
+    if j % 3 == 0:
+        return OFF_TWIST[(j // 3) % len(OFF_TWIST)]
+    x, y = rng.choice(sub + out)
+    if j % 3 == 1:                                      # a twist point with one coordinate one off, conjugated or swapped
+        return [(x, m.f2add(y, (1, 0))), (m.f2add(x, (0, 1)), y), (m.f2conj(x), y), (y, x)][(j // 3) % 4]
+    return (_f2r(rng), _f2r(rng))
+
+
+def _jac2(pt, rng):
+    """affine Fp2 point (or None) -> Jacobian words with a random z; infinity has z = 0 (either representative) and any x, y"""
+    if pt is None:
+        return _f2w(_f2nz(rng), rng) + _f2w(_f2nz(rng), rng) + words(rng.choice([0, P])) + words(rng.choice([0, P]))
+    z = rng.choice([(1, 0), (0, 1), _f2nz(rng), _f2nz(rng)])
+    z2 = f2sqr(z)
+    return _f2w(m.f2mul(pt[0], z2), rng) + _f2w(m.f2mul(pt[1], m.f2mul(z2, z)), rng) + _f2w(z, rng)
+
+
+def g2_group_cases(n, rng):
+    """P Q R: Q by category; P a multiple of Q (Q itself, -Q, infinity, 2Q, others); R equal to P in another representative where
+    g2j_eq is to hold, else -P, another multiple or infinity -- so that the branches for infinity, equal and opposite points are taken
+    by neighbours of regular cases"""
+    cnt = [0] * 4
+    out = []
+    for idx in range(n):
+        c, w, k = category(idx, n, 64)
+        j = cnt[c]
+        cnt[c] += 1
+        q = membership_point(c, j, rng)
+        mults = [1, -1, 0, 2, rng.randrange(3, 40), rng.randrange(3, 40), 1, -1][(j + w) % 8 if n > 8 else idx % 8]
+        mul = lambda kk: None if kk == 0 else (m.g2_mul(q, kk) if kk > 0 else m.g2_neg(m.g2_mul(q, -kk)))
+        p = mul(mults)
+        if (k // 2 + w) % 2 == 0:
+            r = p
+        else:
+            r = [m.g2_neg(p), mul(mults + 1), None, mul(-2)][j % 4]
+            if r == p:
+                r = mul(5) if p is None else None
+        out.append(_jac2(p, rng) + _f2w(q[0], rng) + _f2w(q[1], rng) + _jac2(r, rng))
+    return out
+
+
+def membership_cases(n, rng):
+    cnt = [0] * 4
+    out = []
+    for idx in range(n):
+        c = category(idx, n, 32)[0]
+        q = membership_point(c, cnt[c], rng)
+        cnt[c] += 1
+        out.append(_f2w(q[0], rng) + _f2w(q[1], rng))
+    return out
+
+
+def _jac2_to_aff(w):
+    x, y, z = (_f2_of(w, k) for k in range(3))
+    if z == (0, 0):
+        return None
+    zi = m.f2inv(z)
+    zi2 = f2sqr(zi)
+    return (m.f2mul(x, zi2), m.f2mul(y, m.f2mul(zi2, zi)))
+
+
+def g2_group_reference(wi):
+    """the expected group elements and verdicts of one case of mapping 0 op 9"""
+    p, q, r = _jac2_to_aff(wi[0:48]), (_f2_of(wi, 3), _f2_of(wi, 4)), _jac2_to_aff(wi[80:128])
+    on = m.g2_on_curve(q)
+    return {'dbl': m.g2_add(p, p), 'add_affine': m.g2_add(p, q), 'add': m.g2_add(p, r), 'psi': None if p is None else m.g2_frobenius(p),
+            'mul_u': m.g2_mul(q, m.U), 'eq': p == r, 'on_twist': on, 'in_subgroup': in_subgroup_ref(q) if on else None}
+
+
+def membership_reference(wi):
+    q = (_f2_of(wi, 0), _f2_of(wi, 1))
+    on = m.g2_on_curve(q)
+    return {'on_twist': on, 'in_subgroup': in_subgroup_ref(q) if on else None}
+
+
+def _below_2p(w, what):
+    vals = [_fp_of(w, k) for k in range(len(w) // 8)]
+    assert all(v < 2 * P for v in vals), (what, 'not below 2p', [hex(v) for v in vals if v >= 2 * P][:2])
+
+
+def check_g2_group(ins, outs):
+    bad = []
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        try:
+            want = g2_group_reference(wi)
+            _below_2p(wo[:240], 'g2')
+            for k, nm in enumerate(['dbl', 'add_affine', 'add', 'psi', 'mul_u']):
+                assert _jac2_to_aff(wo[48 * k:48 * k + 48]) == want[nm], ('g2j_' + nm, 'infinity expected' if want[nm] is None else '')
+            assert wo[240] == int(want['eq']), ('g2j_eq', wo[240])
+            assert wo[241] == int(want['on_twist']), ('g2_on_twist', wo[241])
+            assert wo[242] in (0, 1) and (want['in_subgroup'] is None or wo[242] == int(want['in_subgroup'])), ('g2_in_subgroup', wo[242])
+            assert list(wo[243:248]) == [0] * 5
+        except AssertionError as e:
+            bad.append((idx, str(e)))
+    assert not bad, 'g2 group ops: %d failing cases, first %s' % (len(bad), bad[:3])
+
+
+def check_membership(ins, outs):
+    bad = []
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        want = membership_reference(wi)
+        if wo[0] != wo[1] or wo[2] != wo[3]:
+            bad.append((idx, 'the lanes of the pair disagree', list(wo)))
+        elif wo[0] != int(want['on_twist']) or wo[2] not in (0, 1) or (want['in_subgroup'] is not None and wo[2] != int(want['in_subgroup'])):
+            bad.append((idx, list(wo), want))
+    assert not bad, 'membership: %d failing cases, first %s' % (len(bad), bad[:3])
+
+
+# ---- line steps: T (X Y Z) Q (x y), value domain
+LINE_EDGE = [0, 1, P - 1]
+
+
+def line_values(n, rng, per_wave):
+    """[(T, Q, Q2)] by category (see the shares above).  Regular cases: T a random projective scaling of a multiple of Q, Q in the
+    subgroup, outside it (tests/golden, in the order of outside_walk: small-order and membership points in turn) or a psi image; coordinates 0, 1, p - 1 and a Q with a zero component; generic field elements
+    and small distinct primes (no two of theta, lambda, qx, qy, X, Y, Z equal: a wrong operand pick of a wide round changes a product,
+    and with the primes each product of a round is a small value of its own) and one family in which two of them DO coincide
+    (qx = qy, X = Y, Y = Z), where a swapped pick of just those two would go unseen."""
+    sub, out = g2_pools()
+    walk = outside_walk()
+    HALF = (RR + 1) // 2
+    cnt = [0] * 4
+    used = [0]                                  # outside points handed out so far, over all categories
+    res = []
+
+    def outside():
+        used[0] += 1
+        return walk[(used[0] - 1) % len(walk)]
+
+    def scaled(t):
+        s = rng.choice([(1, 0), _f2nz(rng), _f2nz(rng)])
+        return (m.f2mul(t[0], s), m.f2mul(t[1], s), s)
+
+    for idx in range(n):
+        c = category(idx, n, per_wave)[0]
+        j = cnt[c]
+        cnt[c] += 1
+        q = sub[(j // 3) % len(sub)] if j % 3 == 0 else outside() if j % 3 == 1 and c != 2 else m.g2_frobenius(sub[(j // 3 + 3) % len(sub)])
+        if c == 0:
+            while True:                         # a multiple of THIS Q that keeps clear of the exceptional cases (some multiplier below 30 does,
+                for _ in range(60):             # whatever the order of Q; else the next outside point)
+                    t = m.g2_mul(q, rng.randrange(2, 30))
+                    if t is not None and t[0] != q[0] and proj_to_aff(chain_ref(t + ((1, 0),), q)) is not None:
+                        break
+                else:
+                    q = outside()
+                    continue
+                break
+            T = scaled(t)
+        elif c == 2:
+            if j % 3 == 0:
+                e = lambda: (rng.choice(LINE_EDGE), rng.choice(LINE_EDGE))
+                T = (e(), e(), rng.choice([(1, 0), (0, 1), (P - 1, P - 1), (1, P - 1)]))
+                q = [((0, 0), _f2nz(rng)), (_f2nz(rng), (0, 0)), (e(), e()), ((0, rng.randrange(1, P)), (rng.randrange(1, P), 0))][(j // 3) % 4]
+            elif j % 3 == 1:
+                T, q = (_f2nz(rng), _f2nz(rng), _f2nz(rng)), (_f2nz(rng), _f2nz(rng))
+                f = (j // 3) % 3
+                if f == 0: q = (q[0], q[0])
+                elif f == 1: T = (T[0], T[0], T[2])
+                else: T = (T[0], T[1], T[1])
+            elif j % 2:
+                T, q = (_f2nz(rng), _f2nz(rng), _f2nz(rng)), (_f2nz(rng), _f2nz(rng))
+            else:                               # X Y Z qx qy: five distinct small primes, each times 1, i or 1 + i, in any order: every one of
+                while True:                     # the 10 / 13 products is a small value no other product equals
+                    v = [m.f2smul(rng.choice([(1, 0), (0, 1), (1, 1)]), k) for k in rng.sample([2, 3, 5, 7, 11, 13, 17, 19, 23], 5)]
+                    T, q = (v[0], v[1], v[2]), (v[3], v[4])
+                    if len(set(v + [m.f2sub(v[1], m.f2mul(v[4], v[2])), m.f2sub(v[0], m.f2mul(v[3], v[2]))])) == 7:
+                        break
+        elif c == 1:
+            T = ((0, 0), rng.choice([(1, 0), _f2nz(rng)]), (0, 0)) if j % 2 == 0 else (_f2r(rng), _f2r(rng), (0, 0))
+        else:
+            f = j % 4
+            if f == 0: T = scaled(q)
+            elif f == 1: T = scaled(m.g2_neg(q))
+            elif f == 2: T = (_f2nz(rng), (0, 0), _f2nz(rng))
+            else:
+                q = sub[j % len(sub)]
+                T = scaled(m.g2_mul(q, HALF))
+        q2 = q if j % 5 == 0 else (m.g2_neg(q) if j % 5 == 1 else rng.choice(sub + out))
+        res.append((T, q, q2))
+    return res
+
+
+def _pt_words(vals, rng):
+    w = []
+    for c in vals:
+        w += _f2w(c, rng)
+    return w
+
+
+def _f12_rand_words(rng, j):
+    a = _f12_special([3, 3, 2, 0, 3, 1][j % 6], rng)
+    return f12_words(_mont_words_of(a, rng, rng.random() < 0.5))
+
+
+def line_cases(mapping, n, rng):
+    out = []
+    for j, (T, q, q2) in enumerate(line_values(n, rng, PER_WAVE[mapping])):
+        w = _pt_words(T, rng) + _pt_words(q, rng)
+        if mapping == 0:
+            w += _pt_words(q2, rng)
+        else:
+            w += words(_mont_rep(rng.randrange(P), rng)) + words(_mont_rep(rng.randrange(P), rng)) + _f12_rand_words(rng, j)
+        if mapping >= 2:
+            for _ in range(4):
+                w += _f2w(_f2r(rng), rng)
+            for _ in range(4):
+                w += words(_mont_rep(rng.choice([0, 1, rng.randrange(P), rng.randrange(P)]), rng))
+        out.append(w)
+    return out
+
+
+def line_reference(wi):
+    """T, Q of a case (both start at word 0 in every mapping) -> the tangent and the four chords as (T', l0, l1, l3), the chain's T"""
+    T = tuple(_f2_of(wi, k) for k in range(3))
+    Q = (_f2_of(wi, 3), _f2_of(wi, 4))
+    return T, Q, [line_dbl_ref(T)] + [line_add_ref(T, step_q(Q, kind)) for kind in (1, 2, 3, 4)], chain_ref(T, Q)
+
+
+def assert_line_cases_hold_golden_points(ins, mapping, op):
+    """on the inputs alone: some Q is a small-order point of precompile_kats['g2_subgroup'], some Q a point of g2_membership_points outside
+    the subgroup, some Q a subgroup point"""
+    sub, _ = g2_pools()
+    qs = {(_f2_of(wi, 3), _f2_of(wi, 4)) for wi in ([int(x) for x in r] for r in as_array(ins, mapping, op))}
+    assert qs & set(OUT_KATS) and qs & set(OUT_MEMBERSHIP) and qs & set(sub), (len(qs & set(OUT_KATS)), len(qs & set(OUT_MEMBERSHIP)))
+
+
+def line_verdicts(wi):
+    T, Q, steps, chain = line_reference(wi)
+    return {'tangent Z = 0': steps[0][0][2] == (0, 0), 'chord Z = 0': steps[1][0][2] == (0, 0), 'chain Z = 0': chain[2] == (0, 0)}
+
+
+def _f2s_match(w, want, what):
+    """w: 16 words per expected Fp2: below 2p and congruent (either representative of 0 is 0)"""
+    _below_2p(w, what)
+    for k, c in enumerate(want):
+        assert _f2_of(w, k) == c, (what, 'Fp2 %d' % k, 'want 0' if c == (0, 0) else '')
+
+
+def _step_words(step): return list(step[0]) + list(step[1:])
+
+
+def _f12_match(w, want, what):
+    assert _f12_out(w, 0) == want, what
+
+
+def _var_line_ref(f, step, xs, ys): return m.f12mul(f, line_f12(step[1], m.f2smul(step[2], xs), m.f2smul(step[3], ys)))
+
+
+def check_lane_lines(ins, outs):
+    bad = []
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        try:
+            T, Q, steps, _ = line_reference(wi)
+            Q2 = (_f2_of(wi, 5), _f2_of(wi, 6))
+            _f2s_match(wo[0:96], _step_words(steps[0]), 'line_dbl')
+            _f2s_match(wo[96:192], _step_words(steps[1]), 'line_add')
+            _f2s_match(wo[192:224], m.g2_frobenius(Q), 'g2_frob_affine')
+            _f2s_match(wo[224:256], psi2(Q), 'g2_frob2_affine')
+            for k, (pt, nl, c) in enumerate([aff_dbl_ref(Q), aff_add_ref(Q, Q2)]):
+                _f2s_match(wo[256 + 64 * k:320 + 64 * k], [pt[0], pt[1], nl, c], ['aff_dbl', 'aff_add'][k])
+        except AssertionError as e:
+            bad.append((idx, str(e)))
+    assert not bad, 'lane line steps: %d failing cases, first %s' % (len(bad), bad[:3])
+
+
+def check_pair_lines(ins, outs):
+    bad = []
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        try:
+            T, Q, steps, chain = line_reference(wi)
+            xs, ys = _fp_of(wi, 10) * RI % P, _fp_of(wi, 11) * RI % P
+            f = f12_from_words(wi[96:192])[1]
+            for k in range(5):
+                _f2s_match(wo[96 * k:96 * k + 96], _step_words(steps[k]), ['tangent', 'chord Q', 'chord -Q', 'chord psi(Q)', 'chord -psi^2(Q)'][k])
+            _f12_match(wo[480:576], _var_line_ref(f, steps[0], xs, ys), 'variable-line product')
+            _f2s_match(wo[576:624], chain, 'tangent, chord, tangent')
+            assert list(wo[624:720]) == list(wo[0:96]), 'g2m_line_dbl differs from the step of miller_loop_p'
+            assert list(wo[720:816]) == list(wo[96:192]), 'g2m_line_add differs from the step of miller_loop_p'
+        except AssertionError as e:
+            bad.append((idx, str(e)))
+    assert not bad, 'pair line steps: %d failing cases, first %s' % (len(bad), bad[:3])
+
+
+def check_wide_lines(ins, outs, S):
+    bad = []
+    step_w = 48 + 48 * 8 * S
+    for idx, (wi, wo) in enumerate(zip(ins, outs)):
+        try:
+            T, Q, steps, chain = line_reference(wi)
+            xs, ys = _fp_of(wi, 10) * RI % P, _fp_of(wi, 11) * RI % P
+            f = f12_from_words(wi[96:192])[1]
+            L = [_f2_of(wi, 12 + k) for k in range(4)]
+            ks = [_fp_of(wi, 32 + k) * RI % P for k in range(4)]
+            for k, nm in enumerate(['w_line_dbl', 'w_line_add']):
+                o = wo[step_w * k:step_w * (k + 1)]
+                _f2s_match(o[0:48], steps[k][0], nm + ' T')
+                for pr in range(8 * S):
+                    _f2s_match(o[48 + 48 * pr:96 + 48 * pr], steps[k][1:], '%s, the copy of pair %d' % (nm, pr))
+                    assert list(o[48 + 48 * pr:96 + 48 * pr]) == list(o[48:96]), (nm, 'pair %d holds other words than pair 0' % pr)
+            o = wo[2 * step_w:]
+            _f12_match(o[0:96], _var_line_ref(f, steps[0], xs, ys), 'var_line_mul_w')
+            ll = line_f12((1, 0), m.f2smul(L[0], ks[0]), m.f2smul(L[1], ks[1]))
+            lc = line_f12((1, 0), m.f2smul(L[2], ks[2]), m.f2smul(L[3], ks[3]))
+            _f12_match(o[96:192], m.f12mul(m.f12mul(f, ll), lc), 'fixed_lines_mul_w(1, 1)')
+            _f12_match(o[192:288], m.f12mul(f, ll), 'fixed_lines_mul_w(1, 0)')
+            _f12_match(o[288:384], m.f12mul(f, lc), 'fixed_lines_mul_w(0, 1)')
+            inv = _f12_out(o[384:480], 0)
+            assert (m.f12mul(inv, f) == m.F12_ONE) if any(f) else not any(inv), 'f12m_inv_w'
+            _f2s_match(o[480:528], chain, 'tangent, chord, tangent')
+        except AssertionError as e:
+            bad.append((idx, str(e)))
+    assert not bad, 'wide line steps: %d failing cases, first %s' % (len(bad), bad[:3])
+
+
+def g2_verdicts(mapping, op, ins):
+    """per case {verdict name: bool, or None where the reference leaves it open}: the 0 / 1 outputs, and Z' = 0 of the line steps"""
+    rows = []
+    for wi in as_array(ins, mapping, op):
+        wi = [int(x) for x in wi]
+        if (mapping, op) == (0, 9):
+            r = g2_group_reference(wi)
+            rows.append({k: r[k] for k in ('eq', 'on_twist', 'in_subgroup')})
+        elif (mapping, op) == (1, 9):
+            rows.append(membership_reference(wi))
+        else:
+            rows.append(line_verdicts(wi))
+    return rows
+
+
+def assert_g2_cases_bite(mapping, op, ins):
+    """on the reference alone: every verdict is 1 in at least a quarter of the cases and 0 in at least a quarter, takes both values at
+    even and at odd case indices, and at the first and at the last case of a wavefront"""
+    rows = g2_verdicts(mapping, op, ins)
+    if (mapping, op) in ((0, 10), (1, 8), (2, 3), (3, 3)):
+        assert_line_cases_hold_golden_points(ins, mapping, op)
+    n, pw = len(rows), PER_WAVE[mapping]
+    for name in rows[0]:
+        bits = [r[name] for r in rows]
+        ones, zeros = sum(1 for b in bits if b is True), sum(1 for b in bits if b is False)
+        assert 4 * ones >= n and 4 * zeros >= n, (name, ones, zeros, n)
+        assert {(b, i % 2) for i, b in enumerate(bits) if b is not None} == {(False, 0), (False, 1), (True, 0), (True, 1)}, name
+        full = n // pw * pw
+        assert {bits[i] for i in range(0, full, pw)} >= {False, True} and {bits[i] for i in range(pw - 1, full, pw)} >= {False, True}, name
+
+
 # ---------------------------------------------------------------- runners
 def as_array(cases, mapping, op):
     iw = IO[(mapping, op)][0]
@@ -916,6 +1433,7 @@ def host_lib(paired):
             subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-pthread', '-Wno-unknown-pragmas', '-o', lib, src])
         L = C.CDLL(lib)
         L.hs_selftest.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.hs_selftest_io.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         _HOST[name] = L
     return _HOST[name]
 
@@ -931,6 +1449,8 @@ def cases_for(mapping, op, n, seed):
     rng = random.Random(seed * 1000 + mapping * 10 + op)
     if (mapping, op) in PREDICATE_OPS:
         return predicate_cases(mapping, op, n, rng)
+    if (mapping, op) in G2_OPS:
+        return g2_group_cases(n, rng) if (mapping, op) == (0, 9) else membership_cases(n, rng) if (mapping, op) == (1, 9) else line_cases(mapping, n, rng)
     if mapping == 0:
         return lane_cases(op, n, rng)
     if mapping == 1:
@@ -943,6 +1463,9 @@ def check(mapping, op, ins, outs):
     outs = [list(map(int, r)) for r in outs]
     if (mapping, op) in PREDICATE_OPS:
         return check_predicates(mapping, op, ins, outs)
+    if (mapping, op) in G2_OPS:
+        return {(0, 9): check_g2_group, (0, 10): check_lane_lines, (1, 8): check_pair_lines, (1, 9): check_membership,
+                (2, 3): lambda i, o: check_wide_lines(i, o, 1), (3, 3): lambda i, o: check_wide_lines(i, o, 4)}[(mapping, op)](ins, outs)
     if mapping == 0:
         return check_lane(op, ins, outs)
     if mapping == 1:

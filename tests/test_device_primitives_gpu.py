@@ -1,4 +1,4 @@
-"""Known-answer tests of the field, tower and G1 primitives ON THE DEVICE (zkv_diag_primitive): the code the verify kernels run -- carry
+"""Known-answer tests of the field, tower, G1 and G2 primitives ON THE DEVICE (zkv_diag_primitive): the code the verify kernels run -- carry
 builtins, the non-inlined f2_mul_ni / l9_mul_ni leaves, the DPP exchange inside a lane pair, Fp12 values in LDS, the wide routines with
 several cases per wavefront -- at the edges of each primitive's contract, against Python integers and oracle/spec_model.py.  Where the
 host build of the same harness (tests/host_sim/host_sim_selftest*.cpp) can be compiled, the device words must also be bit-identical to
@@ -79,7 +79,8 @@ def test_lane_g1_jacobian_ops(lib):
 
 def test_small_batches_are_padded(lib):
     """1 and 31 cases (the rest of the wavefront, pair block or group runs on zero operands and is discarded)"""
-    for mapping, op in ((0, 1), (0, 7), (1, 0), (1, 3), (2, 1), (3, 1), (0, 8), (1, 5), (1, 6), (1, 7), (2, 2), (3, 2)):
+    for mapping, op in ((0, 1), (0, 7), (1, 0), (1, 3), (2, 1), (3, 1), (0, 8), (1, 5), (1, 6), (1, 7), (2, 2), (3, 2),
+                        (0, 9), (0, 10), (1, 8), (1, 9), (2, 3), (3, 3)):
         for n in (1, 31) if mapping < 2 else (1, 5):
             run(lib, mapping, op, n, seed=n)
 
@@ -153,3 +154,35 @@ def test_wide_sixteen_lanes_is_one_in_every_lane(lib):
 
 def test_wide_one_wavefront_is_one_in_every_lane(lib):
     run_predicates(lib, 3, 2, 48 + 1)
+
+
+# ---------------------------------------------------------------- G2: Jacobian group ops, membership, Miller line steps
+def run_g2(lib, mapping, op, n):
+    """The cases must show every 0 / 1 output, and Z' = 0 of the line steps, in both values often enough and in every place (on the
+    reference alone); then the device words against the Python reference and, bit for bit, against the host build."""
+    pc.assert_g2_cases_bite(mapping, op, pc.cases_for(mapping, op, n, 7))
+    run(lib, mapping, op, n)
+
+
+def test_lane_g2_jacobian_ops_and_membership(lib):
+    run_g2(lib, 0, 9, 64 * 16 + 1)
+
+
+def test_lane_line_steps_frobenius_and_table_lines(lib):
+    run_g2(lib, 0, 10, 64 * 16 + 1)
+
+
+def test_pair_line_steps_as_the_miller_loop_runs_them(lib):
+    run_g2(lib, 1, 8, 32 * 12 + 1)
+
+
+def test_pair_g2_membership_in_both_lanes(lib):
+    run_g2(lib, 1, 9, 32 * 6 + 1)              # every point of the pools; the host build's lane threads are the slow part
+
+
+def test_wide_sixteen_lanes_line_steps_and_line_products(lib):
+    run_g2(lib, 2, 3, 4 * 24 + 1)
+
+
+def test_wide_one_wavefront_line_steps_and_line_products(lib):
+    run_g2(lib, 3, 3, 48 + 1)
