@@ -21,7 +21,11 @@ extern "C" {
  * ZKV_ERR_INVALID_ARG for an unknown (mapping, op), n = 0 or n > 65,536, or a NULL buffer (checked before anything is launched);
  * ZKV_ERR_NO_DEVICE without a gfx950 device.  Words are little-endian uint32; an Fp or Fr is 8 words holding a Montgomery-domain
  * integer (R = 2^261 for both fields; inputs need not be reduced), an Fp2 is c0 then c1 (16 words), an Fp12 six Fp2 in slot order
- * g0 g1 g2 h0 h1 h2 = powers 0 2 4 1 3 5 of w (96 words).  in: n x IN words, out: n x OUT words; per op (IN -> OUT):
+ * g0 g1 g2 h0 h1 h2 = powers 0 2 4 1 3 5 of w (96 words).  "Need not be reduced" holds for the Fp and Fp2 ops (mapping 0 ops 0-4, mapping 1
+ * op 0: words up to 4p - 1, or any 256-bit word, as tests/primitive_cases.py tries them); the Fp12 routines, the cyclotomic squarings, the
+ * line steps, the predicates and the G1 / G2 ops run routines whose contract is "reduced values, below 2p": every Fp word of their
+ * operands must be below 2p -- ANY such word, 2p - 1 in all of them at once included -- and every Fp word they return is below 2p.
+ * in: n x IN words, out: n x OUT words; per op (IN -> OUT):
  *   mapping 0, one value per lane:
  *     op 0  a b c (24) -> fp_add(a,b) fp_sub(a,b) fp_neg(a) fp_dbl(a) fp_half(a), fp_add_x2 -> (a+b, c+a), fp_sub_x2 -> (a-b, c-a),
  *           fp_add_n<3>([a b c], [b c a]), fp_sub_n<3>(same), then fp_is_zero(a), fp_eq(a,b) and six zero words (128)

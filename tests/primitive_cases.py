@@ -1401,6 +1401,264 @@ def assert_g2_cases_bite(mapping, op, ins):
         assert {bits[i] for i in range(0, full, pw)} >= {False, True} and {bits[i] for i in range(pw - 1, full, pw)} >= {False, True}, name
 
 
+# ---------------------------------------------------------------- raw operands at the bounds of the contract
+# The Fp12 routines, the cyclotomic squarings, the line steps and the Jacobian ops take "reduced values (below 2p)".  The generators above
+# hand them v R mod p (sometimes + p): random-looking words.  These hand them the RAW integers at which a lazy sum inside a fused body
+# is largest: 2p - 1 in every place ("hot"), 0 ("cold") where a difference is to be most negative, every 29-bit limb or every 32-bit
+# word full.  The references read their expectation off the input words (f12_from_words, _f2_of, _jac_to_aff), so check() is unchanged.
+#   Fp12 products      (1, 3) (2, 0) (3, 0): every Fp of a, b, c0, c3, c4 is free
+#   cyclotomic squares (1, 4) (2, 1) (3, 1): the value must be cyclotomic; each coefficient is x or x + p
+#   line steps         (0, 10) (1, 8) (2, 3) (3, 3): the formulas are algebraic, every Fp is free
+#   Jacobian ops       (0, 7) (0, 9): P, Q, R stay multiples of one point (the reference is the affine group law); z's raw word is free
+# A batch is place_edges(bound cases, cases_for(...)): the bound cases first, again across the first wavefront boundary where the list
+# fits into a wavefront (a longer list crosses the boundaries by itself), value-domain cases in the rest, so that hot lanes run beside
+# ordinary ones.  A new fused body adds the pattern that drives ITS largest column to the structured lists below, and to the
+# independent restatement of them in assert_bound_cases_bite.
+BOUND_OPS = {(1, 3): 'f12', (2, 0): 'f12', (3, 0): 'f12', (1, 4): 'cyclo', (2, 1): 'cyclo', (3, 1): 'cyclo',
+             (0, 10): 'line', (1, 8): 'line', (2, 3): 'line', (3, 3): 'line', (0, 7): 'g1', (0, 9): 'g2'}
+HOT, COLD = 2 * P - 1, 0
+ALL29 = val9([M29] * 8 + [(HOT >> 232) - 1])                 # all eight low 29-bit limbs full, the top limb one below that of 2p - 1
+ALL32 = unwords([0xffffffff] * 7 + [(HOT >> 224) - 1])      # all seven low 32-bit words full, likewise
+BOUND_EDGES = [HOT, 2 * P - 2, P + 1, P, P - 1, 1, 0, ALL29, ALL32]
+assert all(0 <= v < 2 * P for v in BOUND_EDGES) and len(BOUND_EDGES) % 2 == 1
+LINE_SETTINGS = [[HOT] * 6, [COLD] * 6, [HOT, COLD] * 3, [COLD, HOT] * 3, [ALL29] * 6, [P] * 6]       # c0 c3 c4 of the Fp12 ops
+LINE_NFP = {0: 14, 1: 24, 2: 36, 3: 36}                     # T 0-5, Q 6-9, then Q2 10-13 (mapping 0) or xs ys 10 11, f 12-23, L0 L1 24-31, lxs lys cxs cys 32-35
+
+
+def _bound_row(vals):
+    assert all(0 <= v < 2 * P for v in vals), 'a bound case holds a word that is not below 2p'
+    return _fpw(vals)
+
+
+def _edge_mix(rng, k): return [rng.choice(BOUND_EDGES) for _ in range(k)]
+
+
+def f12_patterns():
+    """(patterns over the twelve Fp of an Fp12 that are no slot patterns, slot patterns); position 2 slot + component, slots g0 g1 g2 h0 h1 h2"""
+    flat = [[e] * 12 for e in BOUND_EDGES]
+    flat += [[HOT, COLD] * 6, [COLD, HOT] * 6]              # c0 against c1: a0 b0 - a1 b1 most positive, most negative
+    flat += [[HOT] * 6 + [COLD] * 6, [COLD] * 6 + [HOT] * 6]                               # g against h
+    slot = []
+    for s in range(6):
+        slot.append([HOT if k // 2 == s else COLD for k in range(12)])
+        slot.append([COLD if k // 2 == s else HOT for k in range(12)])
+    return flat, slot
+
+
+def f12_bound_cases(rng, mixes=4):
+    """a b c0 c3 c4: every ordered pair of the non-slot patterns (13 x 13: with an odd count the index 13 i + j gives every pattern of
+    a and of b both parities), every slot pattern against uniform hot and uniform cold in both orders, seeded mixes of the edge values.
+    The line operands cycle through LINE_SETTINGS, the phase moving on after every round (so that a setting meets both parities)."""
+    flat, slot = f12_patterns()
+    assert len(flat) % 2 == 1
+    ab = [(a, b) for a in flat for b in flat]
+    for s in slot:
+        for u in ([HOT] * 12, [COLD] * 12):
+            ab += [(s, u), (u, s)]
+    ab += [(_edge_mix(rng, 12), _edge_mix(rng, 12)) for _ in range(mixes)]
+    return [_bound_row(a + b + LINE_SETTINGS[(k + k // 6) % 6]) for k, (a, b) in enumerate(ab)]
+
+
+def cyclo_shifts():
+    """which of the twelve coefficients hold x + p: none, all, c0, c1, g, h, each slot"""
+    masks = [[False] * 12, [True] * 12, [k % 2 == 0 for k in range(12)], [k % 2 == 1 for k in range(12)], [k < 6 for k in range(12)], [k >= 6 for k in range(12)]]
+    return masks + [[k // 2 == s for k in range(12)] for s in range(6)]
+
+
+def cyclo_bound_cases(rng=None):
+    """every element of cyclotomic_pool() and 1, in every shift of cyclo_shifts(); shift by shift, so that with five elements a
+    coefficient meets both representatives at both parities"""
+    elems = [_f12_raw(c) for c in cyclotomic_pool()] + [_f12_raw(m.F12_ONE)]
+    assert len(elems) % 2 == 1
+    return [_bound_row([x + P if s else x for x, s in zip(e, mask)]) for mask in cyclo_shifts() for e in elems]
+
+
+def line_patterns(mapping):
+    """structured rows over every Fp of the op's operands (LINE_NFP)"""
+    n = LINE_NFP[mapping]
+    T, Q = range(0, 6), range(6, 14 if mapping == 0 else 10)
+    f, scal = range(12, 24), [10, 11] + list(range(24, n))          # f; xs ys and, wide, L0 L1 lxs lys cxs cys
+    rows = [[e] * n for e in BOUND_EDGES]
+    rows += [[HOT if k % 2 == 0 else COLD for k in range(n)], [COLD if k % 2 == 0 else HOT for k in range(n)]]
+    for t, q in ((HOT, COLD), (COLD, HOT)):
+        rows.append([t if k in T else q if k in Q else ALL29 for k in range(n)])
+    if mapping:                                 # f against the operands that scale and form the lines (T and Q full, or the lines are 0)
+        for a, b in ((HOT, COLD), (COLD, HOT)):
+            rows.append([a if k in f else b if k in scal else ALL29 for k in range(n)])
+    return rows
+
+
+def line_bound_cases(mapping, rng, mixes=6):
+    """the structured rows, seeded mixes, and the structured rows again from an odd index (every row meets both parities)"""
+    rows = line_patterns(mapping)
+    out = rows + [_edge_mix(rng, LINE_NFP[mapping]) for _ in range(mixes)]
+    if len(out) % 2 == 0:
+        out.append(_edge_mix(rng, LINE_NFP[mapping]))
+    return [_bound_row(r) for r in out + rows]
+
+
+def _z_plan(k, shift=0):
+    """(index into BOUND_EDGES, component of an Fp2 z) of case k: the edges in turn, the component changing every two rounds -- nine edges,
+    so case 9 q + j has the parity of q + j and every (edge, component) meets both"""
+    return (k + shift) % len(BOUND_EDGES), ((k // len(BOUND_EDGES)) // 2) % 2
+
+
+def _jac_raw_z(pt, zraw):
+    """_jac with z's raw Montgomery word given and x, y in the x + p representative; z = 0 (mod p) is infinity, for which x = y = 1"""
+    z = zraw * RI % P
+    if pt is None or z == 0:
+        assert z == 0
+        return words(ONE_M + P) + words(ONE_M + P) + words(zraw)
+    return words(_mont(pt[0] * z * z % P) + P) + words(_mont(pt[1] * z * z * z % P) + P) + words(zraw)
+
+
+def g1_bound_cases(rng, n=72):
+    """the points of g1_cases (decoded from its rows); z of P and of T at each edge value.  A point at infinity keeps z = 0 or p."""
+    out = []
+    for k, w in enumerate(g1_cases(n, rng)):
+        p, t = _jac_to_aff(w[0:24]), _jac_to_aff(w[40:64])
+        zp, zt = BOUND_EDGES[_z_plan(k)[0]], BOUND_EDGES[_z_plan(k, 4)[0]]
+        zp = zp if p is not None else (P if k % 2 else 0)
+        zt = zt if t is not None else (0 if k % 2 else P)
+        q = [_fp_of(w, 3) % P + P, _fp_of(w, 4) % P + P]
+        out.append(_bound_row([unwords(x) for x in _chunks(_jac_raw_z(p, zp) + _fpw(q) + _jac_raw_z(t, zt))]))
+    return out
+
+
+def _chunks(w): return [w[8 * k:8 * k + 8] for k in range(len(w) // 8)]
+
+
+def _jac2_raw_z(pt, zraw):
+    """_jac2 with both raw words of z given and x, y in the x + p representative; z = 0 (mod p) in both components is infinity"""
+    z = (zraw[0] * RI % P, zraw[1] * RI % P)
+    if pt is None or z == (0, 0):
+        assert z == (0, 0)
+        return [ONE_M + P, P, ONE_M + P, P, zraw[0], zraw[1]]
+    z2 = f2sqr(z)
+    x, y = m.f2mul(pt[0], z2), m.f2mul(pt[1], m.f2mul(z2, z))
+    return [_mont(c) + P for c in x + y] + list(zraw)
+
+
+def g2_bound_cases(rng, n=72):
+    """the points of g2_group_cases (decoded from its rows); each component of z of P and of R at each edge value, the other component
+    a random nonzero value, or (every third round) the same edge.  A point at infinity keeps z = 0 or p in both components."""
+    out = []
+    for k, w in enumerate(g2_group_cases(n, rng)):
+        row = []
+        for pt, shift, flip in ((_jac2_to_aff(w[0:48]), 0, 0), (_jac2_to_aff(w[80:128]), 4, 1)):
+            j, comp = _z_plan(k, shift)
+            comp ^= flip
+            if pt is None:
+                z = [P if (k + flip) % 2 else 0, 0 if (k // 2) % 2 else P]
+            else:
+                z = [_mont(rng.randrange(1, P)) + (P if k % 2 else 0)] * 2
+                z[comp] = BOUND_EDGES[j]
+                if (k // len(BOUND_EDGES)) % 3 == 2 and BOUND_EDGES[j] % P:
+                    z[1 - comp] = BOUND_EDGES[j]
+            row.append(_jac2_raw_z(pt, z))
+        q = [_fp_of(w, 6 + c) % P + P for c in range(4)]
+        out.append(_bound_row(row[0] + q + row[1]))
+    return out
+
+
+def bound_batch_size(mapping, nb):
+    """64 3 + 1 lanes, 32 7 + 1 lane pairs; wide groups: whole blocks of four wavefronts that hold the nb bound cases and at least one
+    block of other cases, and one case more (a last partial block)"""
+    if mapping < 2:
+        return (64 * 3 + 1, 32 * 7 + 1)[mapping]
+    block = 4 * PER_WAVE[mapping]
+    return -(-(nb + block) // block) * block + 1
+
+
+def bound_cases_for(mapping, op, seed=7):
+    """the batch of (mapping, op): its bound cases, placed by place_edges among the value-domain cases of cases_for"""
+    rng = random.Random(0xB0D + seed * 1000 + mapping * 10 + op)
+    kind = BOUND_OPS[(mapping, op)]
+    bounds = {'f12': lambda: f12_bound_cases(rng), 'cyclo': lambda: cyclo_bound_cases(rng), 'line': lambda: line_bound_cases(mapping, rng),
+              'g1': lambda: g1_bound_cases(rng), 'g2': lambda: g2_bound_cases(rng)}[kind]()
+    n = bound_batch_size(mapping, len(bounds))
+    assert len(bounds) < n
+    return place_edges(bounds, iter(cases_for(mapping, op, n, seed)), n, PER_WAVE[mapping])
+
+
+def all_hot_case(mapping, op):
+    """one case with every operand word at 2p - 1"""
+    return [_bound_row([HOT] * (IO[(mapping, op)][0] // 8))]
+
+
+def assert_bound_cases_bite(mapping, op, ins):
+    """On the inputs alone, before anything is compared.  Every operand word is below 2p; every free Fp position holds each of 2p - 1,
+    p, 0 and ALL29 at an even and at an odd case index (the two lane pairs of a DPP quad, the two halves of a row of groups); the
+    all-hot case and every structured pattern are there, both halves of each complementary pair among them.  The patterns are
+    restated here by position, NOT taken from the generators: a pattern dropped from a generator makes this fail."""
+    kind = BOUND_OPS[(mapping, op)]
+    rows = [[_fp_of(r, k) for k in range(len(r) // 8)] for r in ([int(x) for x in row] for row in as_array(ins, mapping, op))]
+    assert all(v < 2 * P for r in rows for v in r), 'an operand word is not below 2p'
+    hot, p, all29, all32 = 2 * P - 1, P, sum(M29 << (29 * i) for i in range(8)) + ((((2 * P - 1) >> 232) - 1) << 232), \
+        (1 << 224) - 1 + ((((2 * P - 1) >> 224) - 1) << 224)
+    edges = [hot, hot - 1, p + 1, p, p - 1, 1, 0, all29, all32]
+
+    def both_parities(positions, values):
+        for k in positions:
+            for v in values:
+                seen = {i % 2 for i, r in enumerate(rows) if r[k] == v}
+                assert seen == {0, 1}, ('Fp position %d holds %s at case parities %s only' % (k, hex(v), sorted(seen)))
+
+    def holds(name, want, lo=0):
+        assert any(r[lo:lo + len(want)] == want for r in rows), 'no case with the pattern: ' + name
+
+    if kind == 'f12':
+        both_parities(range(30), (hot, p, 0, all29))
+        holds('every operand uniform 2p - 1', [hot] * 30)
+        flat = [('uniform ' + hex(e), [e] * 12) for e in edges]
+        flat += [('c0 hot, c1 cold', [hot, 0] * 6), ('c1 hot, c0 cold', [0, hot] * 6), ('g hot, h cold', [hot] * 6 + [0] * 6), ('h hot, g cold', [0] * 6 + [hot] * 6)]
+        pairs = {(tuple(r[0:12]), tuple(r[12:24])) for r in rows}
+        for na, a in flat:
+            for nb, b in flat:
+                assert (tuple(a), tuple(b)) in pairs, 'no case with a: %s and b: %s' % (na, nb)
+        for s in range(6):
+            for x, y, nm in ((hot, 0, 'hot'), (0, hot, 'cold')):
+                pat = tuple(x if k // 2 == s else y for k in range(12))
+                for u in ((hot,) * 12, (0,) * 12):
+                    assert (pat, u) in pairs and (u, pat) in pairs, 'slot %d alone %s is not tried against uniform %s in both orders' % (s, nm, hex(u[0]))
+        for nm, c in (('hot', [hot] * 6), ('cold', [0] * 6), ('hot / cold', [hot, 0] * 3), ('cold / hot', [0, hot] * 3), ('ALL29', [all29] * 6), ('p', [p] * 6)):
+            holds('line operands ' + nm, c, 24)
+    elif kind == 'cyclo':
+        masks = {tuple(v >= P for v in r) for r in rows}
+        for k in range(12):
+            seen = {(r[k] >= P, i % 2) for i, r in enumerate(rows)}
+            assert seen == {(False, 0), (False, 1), (True, 0), (True, 1)}, ('coefficient %d' % k, sorted(seen))
+        want = [('none', lambda k: False), ('all', lambda k: True), ('c0', lambda k: k % 2 == 0), ('c1', lambda k: k % 2 == 1), ('g', lambda k: k < 6), ('h', lambda k: k >= 6)]
+        want += [('slot %d' % s, lambda k, s=s: k // 2 == s) for s in range(6)]
+        for nm, f in want:
+            assert tuple(f(k) for k in range(12)) in masks, 'no case shifted by p in: ' + nm
+        one = [RM % P] + [0] * 11
+        for nm, f in want:                      # 1 = (R mod p, 0, ...) in every shift: raw p in every coefficient but the first
+            holds('1 shifted in ' + nm, [x + P if f(k) else x for k, x in enumerate(one)])
+    elif kind == 'line':
+        n = len(rows[0])
+        both_parities(range(n), (hot, p, 0, all29))
+        for e in edges:
+            holds('uniform ' + hex(e), [e] * n)
+        holds('hot / cold alternating', [hot if k % 2 == 0 else 0 for k in range(n)])
+        holds('cold / hot alternating', [0 if k % 2 == 0 else hot for k in range(n)])
+        nq = 8 if mapping == 0 else 4
+        holds('T hot, Q cold', [hot] * 6 + [0] * nq)
+        holds('T cold, Q hot', [0] * 6 + [hot] * nq)
+        if mapping:
+            assert any(r[12:24] == [hot] * 12 and set(r[10:12] + r[24:]) == {0} and 0 not in r[:10] for r in rows), 'no case with f hot, the line operands cold'
+            assert any(r[12:24] == [0] * 12 and set(r[10:12] + r[24:]) == {hot} and 0 not in r[:10] for r in rows), 'no case with f cold, the line operands hot'
+    else:
+        zs = {'g1': (2, 7), 'g2': (4, 5, 14, 15)}[kind]
+        both_parities(zs, (hot, p, 0, all29))
+        for k in zs:
+            for e in edges:
+                assert any(r[k] == e for r in rows), 'z (Fp position %d) never holds %s' % (k, hex(e))
+        assert any(all(v >= P for k, v in enumerate(r) if k not in zs) for r in rows), 'no case with every coordinate in the x + p representative'
+        if kind == 'g2':
+            assert any(r[4] == r[5] == hot for r in rows) and any(r[14] == r[15] == hot for r in rows), 'no z with both components 2p - 1'
+
+
 # ---------------------------------------------------------------- runners
 def as_array(cases, mapping, op):
     iw = IO[(mapping, op)][0]

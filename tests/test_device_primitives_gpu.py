@@ -33,7 +33,11 @@ def _host_available(paired):
 
 def run(lib, mapping, op, n, same_as_host=None, seed=7):
     """one call with all n cases of the op; checks the results, and the first `same_as_host` (default all) against the host build"""
-    ins = pc.cases_for(mapping, op, n, seed)
+    return run_cases(lib, mapping, op, pc.cases_for(mapping, op, n, seed), same_as_host)
+
+
+def run_cases(lib, mapping, op, ins, same_as_host=None):
+    n = len(ins)
     out = pc.run_device(lib, mapping, op, ins)
     pc.check(mapping, op, ins, out)
     if _host_available(mapping != 0):
@@ -83,6 +87,8 @@ def test_small_batches_are_padded(lib):
                         (0, 9), (0, 10), (1, 8), (1, 9), (2, 3), (3, 3)):
         for n in (1, 31) if mapping < 2 else (1, 5):
             run(lib, mapping, op, n, seed=n)
+    for mapping, op in ((1, 3), (2, 0), (3, 0), (1, 8)):         # a lone case with every word at 2p - 1 beside the zero padding
+        run_cases(lib, mapping, op, pc.all_hot_case(mapping, op))
 
 
 # ---------------------------------------------------------------- lane pairs (k_selftest_pair)
@@ -186,3 +192,62 @@ def test_wide_sixteen_lanes_line_steps_and_line_products(lib):
 
 def test_wide_one_wavefront_line_steps_and_line_products(lib):
     run_g2(lib, 3, 3, 48 + 1)
+
+
+# ---------------------------------------------------------------- raw operands at the bounds of the contract
+def run_bounds(lib, mapping, op, same_as_host=None):
+    """Raw Montgomery words at which the lazy sums of a fused body are largest -- 2p - 1 in every place, hot against cold halves, full
+    29-bit limbs -- where the tests above hand the same routines v R mod p, a random-looking word.  The batch must hold every structured
+    pattern, and each extreme value in every operand position at both case parities (on the inputs alone); then the device words
+    against the Python reference, below 2p, and bit for bit against the host build."""
+    ins = pc.bound_cases_for(mapping, op)
+    pc.assert_bound_cases_bite(mapping, op, ins)
+    run_cases(lib, mapping, op, ins, same_as_host)
+
+
+def test_pair_fp12_routines_at_raw_operand_bounds(lib):
+    run_bounds(lib, 1, 3)
+
+
+def test_pair_cyclotomic_squarings_at_raw_operand_bounds(lib):
+    run_bounds(lib, 1, 4)
+
+
+def test_wide_sixteen_lanes_fp12_routines_at_raw_operand_bounds(lib):
+    run_bounds(lib, 2, 0)
+
+
+def test_wide_sixteen_lanes_cyclotomic_squaring_at_raw_operand_bounds(lib):
+    run_bounds(lib, 2, 1)
+
+
+def test_wide_one_wavefront_fp12_routines_at_raw_operand_bounds(lib):
+    run_bounds(lib, 3, 0)
+
+
+def test_wide_one_wavefront_cyclotomic_squaring_at_raw_operand_bounds(lib):
+    run_bounds(lib, 3, 1)
+
+
+def test_lane_line_steps_at_raw_operand_bounds(lib):
+    run_bounds(lib, 0, 10)
+
+
+def test_pair_line_steps_at_raw_operand_bounds(lib):
+    run_bounds(lib, 1, 8)
+
+
+def test_wide_sixteen_lanes_line_steps_at_raw_operand_bounds(lib):
+    run_bounds(lib, 2, 3)
+
+
+def test_wide_one_wavefront_line_steps_at_raw_operand_bounds(lib):
+    run_bounds(lib, 3, 3)
+
+
+def test_lane_g1_jacobian_ops_at_raw_z_bounds(lib):
+    run_bounds(lib, 0, 7)
+
+
+def test_lane_g2_jacobian_ops_at_raw_z_bounds(lib):
+    run_bounds(lib, 0, 9)

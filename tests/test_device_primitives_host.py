@@ -33,6 +33,34 @@ def test_pair_and_wide_ops_on_the_host_build(mapping, op, n):
     pc.check(mapping, op, ins, pc.run_host(mapping, op, ins))
 
 
+@pytest.mark.parametrize('mapping,op', sorted(pc.BOUND_OPS))
+def test_raw_operand_bounds_on_the_host_build(mapping, op):
+    """raw operands at the bounds of the contract (2p - 1 everywhere, hot against cold, full limbs): the generators, the condition on
+    the inputs alone, and the references, before any GPU time is spent"""
+    ins = pc.bound_cases_for(mapping, op)
+    pc.assert_bound_cases_bite(mapping, op, ins)
+    pc.check(mapping, op, ins, pc.run_host(mapping, op, ins))
+
+
+def test_bound_condition_bites():
+    """assert_bound_cases_bite fails when one structured pattern is taken out of a batch (each case that holds it replaced by a
+    value-domain case)"""
+    for mapping, op, drop in ((1, 3, lambda r: r[0:12] == [pc.HOT, pc.COLD] * 6 and r[12:24] == [pc.ALL32] * 12),
+                              (1, 3, lambda r: r[0:12] == [pc.COLD] * 12 and r[12:24] == [pc.COLD] * 10 + [pc.HOT] * 2),
+                              (1, 4, lambda r: all(v >= pc.P for v in r[6:12]) and all(v < pc.P for v in r[0:6])),
+                              (1, 8, lambda r: r[12:24] == [pc.HOT] * 12 and r[10:12] == [pc.COLD] * 2),
+                              (0, 10, lambda r: r == [pc.ALL32] * 14),
+                              (0, 7, lambda r: r[2] == pc.ALL29),
+                              (0, 9, lambda r: r[15] == 2 * pc.P - 2)):
+        ins = pc.bound_cases_for(mapping, op)
+        pc.assert_bound_cases_bite(mapping, op, ins)
+        plain = pc.cases_for(mapping, op, 1, 3)[0]
+        cut = [plain if drop([pc._fp_of(w, k) for k in range(len(w) // 8)]) else w for w in ins]
+        assert cut != ins
+        with pytest.raises(AssertionError):
+            pc.assert_bound_cases_bite(mapping, op, cut)
+
+
 def test_references_agree_with_spec_model():
     """the shortcuts of the references: the linear Frobenius against f12pow(a, p^k), the slot <-> w-basis conversion round trip"""
     import random
