@@ -31,7 +31,7 @@ def _hipcc():
 
 
 def _deps_mtime():
-    files = glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(HERE, '..', 'include', f) for f in ('zkv.h', 'zkv_groth16_set.h', 'zkv_sp1_gateway.h', 'zkv_sp1_gateway_wire.h', 'zkv_sp1_gateway_keys.h', 'zkv_plonk_keys.h', 'zkv_plonk_set.h', 'zkv_plonk_set_agg.h', 'zkv_diag_primitive.h', 'zkv_diag_prep.h', 'zkv_diag_gt.h', 'zkv_risc0_set_inclusion.h', 'zkv_risc0_router.h', 'zkv_risc0_router_wire.h', 'zkv_risc0_router_set.h', 'zkv_risc0_router_set_wire.h')]
+    files = glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(HERE, '..', 'include', f) for f in ('zkv.h', 'zkv_groth16_set.h', 'zkv_sp1_gateway.h', 'zkv_sp1_gateway_wire.h', 'zkv_sp1_gateway_keys.h', 'zkv_plonk_keys.h', 'zkv_plonk_set.h', 'zkv_plonk_set_agg.h', 'zkv_diag_primitive.h', 'zkv_diag_line_steps.h', 'zkv_diag_prep.h', 'zkv_diag_gt.h', 'zkv_risc0_set_inclusion.h', 'zkv_risc0_router.h', 'zkv_risc0_router_wire.h', 'zkv_risc0_router_set.h', 'zkv_risc0_router_set_wire.h')]
     return max(os.path.getmtime(f) for f in files)
 
 

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(PAIR_BLOCK, 2) void k_miller2(size_t n, const VkTab
     // words behind mconst (miller_start_value, zkv_verify.h: the final exponentiation of what the loop then delivers is that of loop value
     // times constant), and the loop's value goes straight to ws.f; without them the loop starts from 1 and closes with the product.
     const uint32_t* start = mconst ? mconst + 96 : nullptr;
-    if (!miller_loop_p(vk, flags, norm, bsrc, fm, tm, true, start)) {
+    if (!miller_loop_p<true>(vk, flags, norm, bsrc, fm, tm, true, start)) {     // <true>: line steps as column sums (zkv_line_sums.h)
         if (!par) { ws.g2bad[i] = 1; status[i] = ST_VERIFICATION_FAILED; }
         return;
     }

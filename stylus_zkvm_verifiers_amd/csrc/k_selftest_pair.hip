@@ -14,6 +14,12 @@ __global__ __launch_bounds__(64) void k_selftest_pair(int op, int in_w, int out_
     const size_t i = (size_t)blockIdx.x * 32 + (threadIdx.x >> 1);
     selftest_pair(op, in + i * (size_t)in_w, out + i * (size_t)out_w, lds + threadIdx.x);
 }
+// the line steps of k_miller2 as column sums (selftest_line_sums), one case per lane pair; f and T in the columns k_selftest_pair gives them
+__global__ __launch_bounds__(64) void k_selftest_line_sums(const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+    __shared__ uint32_t lds[(48 + 24) * 64];
+    const size_t i = (size_t)blockIdx.x * 32 + (threadIdx.x >> 1);
+    selftest_line_sums(in + i * (size_t)ST_LINE_SUMS_IN, out + i * (size_t)ST_LINE_SUMS_OUT, lds + threadIdx.x);
+}
 // one case per 16 S lanes, the group's slots as in k_wide.hip (pair q = (lane >> 1) & 7, pairs 6 and 7 shadow 0 and 1; slice = lane bits 4-5)
 template <int S>
 __device__ __forceinline__ void selftest_wide_body(int op, int in_w, int out_w, const uint32_t* in, uint32_t* out, uint32_t* lds) {
@@ -41,6 +47,9 @@ void launch_selftest_pair(int mapping, int op, unsigned waves, const uint32_t* i
     if (mapping == 1) hipLaunchKernelGGL(k_selftest_pair, dim3(waves), dim3(64), 0, s, op, iw, ow, in, out);
     else if (mapping == 2) hipLaunchKernelGGL(k_selftest_wide_s1, dim3(waves), dim3(64), 0, s, op, iw, ow, in, out);
     else hipLaunchKernelGGL(k_selftest_wide_s4, dim3(waves), dim3(64), 0, s, op, iw, ow, in, out);
+}
+void launch_selftest_line_sums(unsigned waves, const uint32_t* in, uint32_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_selftest_line_sums, dim3(waves), dim3(64), 0, s, in, out);
 }
 
 }  // namespace zkv

@@ -25,6 +25,7 @@
 #include "../../include/zkv_plonk_set.h"
 #include "../../include/zkv_plonk_set_agg.h"
 #include "../../include/zkv_diag_primitive.h"
+#include "../../include/zkv_diag_line_steps.h"
 #include "../../include/zkv_diag_prep.h"
 #include "../../include/zkv_diag_gt.h"
 #include "../../include/zkv_risc0_set_inclusion.h"
@@ -3871,6 +3872,27 @@ ZKV_EXPORT int zkv_diag_primitive(int device, int mapping, int op, size_t n, con
         else launch_selftest_pair(mapping, op, (unsigned)waves, d_in, d_out, nullptr);
         ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
              hipMemcpy(out, d_out, n * (size_t)ow * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); return ZKV_ERR_HIP; }
+    return ZKV_OK;
+}
+
+// The line steps of k_miller2 as column sums (zkv_diag_line_steps.h; selftest_line_sums): checked and padded like zkv_diag_primitive.
+static_assert(ZKV_DIAG_LINE_STEPS_IN == 192 && ZKV_DIAG_LINE_STEPS_OUT == 624, "zkv_diag_line_steps.h documents the rows of selftest_line_sums");
+ZKV_EXPORT int zkv_diag_line_steps(int device, size_t n, const uint32_t* in, uint32_t* out) {
+    if (n == 0 || n > ZKV_DIAG_PRIMITIVE_MAX_CASES || !in || !out) return ZKV_ERR_INVALID_ARG;
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { (void)hipGetLastError(); return ZKV_ERR_NO_DEVICE; }
+    if (device < 0 || device >= nd || !device_is_gfx950(device)) return ZKV_ERR_NO_DEVICE;
+    HIP_TRY(hipSetDevice(device));
+    const size_t iw = ZKV_DIAG_LINE_STEPS_IN, ow = ZKV_DIAG_LINE_STEPS_OUT, waves = (n + 31) / 32, padded = waves * 32;
+    DevBuf<uint32_t> d_in, d_out;
+    if (d_in.alloc(padded * iw * 4) || d_out.alloc(padded * ow * 4)) return ZKV_ERR_OOM;
+    bool ok = hipMemset(d_in, 0, padded * iw * 4) == hipSuccess && hipMemcpy(d_in, in, n * iw * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        launch_selftest_line_sums((unsigned)waves, d_in, d_out, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(out, d_out, n * ow * 4, hipMemcpyDeviceToHost) == hipSuccess;
     }
     if (!ok) { (void)hipGetLastError(); return ZKV_ERR_HIP; }
     return ZKV_OK;

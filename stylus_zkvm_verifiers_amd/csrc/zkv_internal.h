@@ -333,6 +333,7 @@ void launch_diag_issue(int kind, unsigned blocks, uint32_t iters, uint32_t* out,
 // known-answer harness of the primitives (k_selftest.hip: mapping 0; k_selftest_pair.hip: mappings 1-3; zkv_selftest.h)
 void launch_selftest_lane(int op, unsigned waves, const uint32_t* in, uint32_t* out, hipStream_t s);
 void launch_selftest_pair(int mapping, int op, unsigned waves, const uint32_t* in, uint32_t* out, hipStream_t s);
+void launch_selftest_line_sums(unsigned waves, const uint32_t* in, uint32_t* out, hipStream_t s);
 
 // aggregate check (k_agg.hip, k_pair.hip; zkv_agg.h)
 struct AggTables; struct AggSeed;

@@ -295,6 +295,43 @@ ZKV_HD void selftest_pair(int op, const uint32_t* in, uint32_t* out, uint32_t* l
     }
 }
 
+// The G2 steps of k_miller2 as fused column sums (zkv_line_sums.h; zkv_diag_line_steps, include/zkv_diag_line_steps.h): the input row of
+// op 8 above, T in the LDS slot of k_miller2, B and the scalings re-read through their SoaRef rows, every step starting from the input T.
+// out: the tangent step and the chord steps of kinds 1 2 3 4 as T' l0 c3 c4 (5 x 96), f after the variable-line product with the tangent's
+// line (96), T after tangent, chord(Q), tangent (48).
+constexpr int ST_LINE_SUMS_IN = 192, ST_LINE_SUMS_OUT = 624;
+ZKV_HD void selftest_line_sums(const uint32_t* in, uint32_t* out, uint32_t* lds) {
+    const uint32_t par = zkv_parity();
+    const LRef fm = l_ref(lds), tm = l_ref(lds + 48 * 64);
+    SoaRef bsrc; bsrc.p = in + 48; bsrc.stride = 1; bsrc.off = 32u * par;
+    SoaRef norm; norm.p = in + 80; norm.stride = 1; norm.off = 0;
+    const auto scale = [&](int k) { return norm.fp(8 * k); };
+    auto load_t = [&]() { for (int k = 0; k < 3; k++) m_st_f2(tm, k, st_ldh(in + 16 * k, par)); };
+    auto step = [&](int kind, Fp2& l0, Fp2& c3, Fp2& c4) {          // the body of `if (do_t)` in miller_loop_p<true>
+        if (kind == 0) line_dbl_sums(tm, l0, c3, c4, scale);
+        else {
+            Fp2 qx, qy; qx.h = bsrc.fp(0); qy.h = bsrc.fp(16);
+            if (kind == 2) qy = f2_neg(qy);
+            else if (kind == 3) { Fp2 x, y; g2_frob_affine(x, y, qx, qy); qx = x; qy = y; }
+            else if (kind == 4) { Fp2 x, y; g2_frob2_affine(x, y, qx, qy); qx = x; qy = f2_neg(y); }
+            line_add_sums(tm, qx, qy, l0, c3, c4, scale);
+        }
+    };
+    auto put = [&](uint32_t* o, const Fp2& l0, const Fp2& c3, const Fp2& c4) {
+        for (int k = 0; k < 3; k++) st_st(o + 16 * k + 8 * par, m_ld_f2(tm, k).h);
+        st_st(o + 48 + 8 * par, l0.h); st_st(o + 64 + 8 * par, c3.h); st_st(o + 80 + 8 * par, c4.h);
+    };
+    Fp2 l0, c3, c4, t0, t3, t4;
+    load_t(); step(0, t0, t3, t4); put(out, t0, t3, t4);
+#pragma unroll 1
+    for (int kind = 1; kind <= 4; kind++) { load_t(); step(kind, l0, c3, c4); put(out + 96 * kind, l0, c3, c4); }
+    f12m_copy(fm, m_ref((uint32_t*)in + 96 + 8 * par, 1, 16));
+    f12m_mul_by_034_body(fm, t0, t3, t4);
+    f12m_copy(m_ref(out + 480 + 8 * par, 1, 16), fm);
+    load_t(); step(0, l0, c3, c4); step(1, l0, c3, c4); step(0, l0, c3, c4);
+    for (int k = 0; k < 3; k++) st_st(out + 576 + 16 * k + 8 * par, m_ld_f2(tm, k).h);
+}
+
 // words of group memory per case of the wide mappings: slots a, b, d and the slices' rows, or k_wide.hip's f, T, 13 scratch Fp2 and rows
 constexpr int ST_WIDE_SLOT = 96 + 48 + 13 * 16 + W_RED_WORDS;
 // This lane's index in its 16 S-lane group (lane 0 is the one that stores the status in k_finalexp_w / k_finalexp_w64).  On the device

@@ -11,6 +11,7 @@
 // The functions are __host__ __device__ so tests/host_sim can run the identical code on the CPU.
 #pragma once
 #include "zkv_tower_mem.h"
+#include "zkv_line_sums.h"
 #include "zkv_sha256.h"
 #include "zkv_gt.h"
 
@@ -363,7 +364,9 @@ struct SoaRef {                         // word k of this proof's (this lane's) 
 // (Z3 = 2 Y^3 Z, Z3 = Z lambda^3), so such a point ends with Z = 0 and is rejected, while a point of G2 (prime order r, larger than
 // every partial scalar) never meets one and ends with Z != 0.  With check_b the point is stepped for A = infinity too (the precompile
 // validates B whether or not the pair contributes); only the line products are skipped then.
-template <class RF, class RT>
+// LINE_SUMS: the tangent and chord steps as fused column sums (zkv_line_sums.h) instead of line_dbl / line_add: the same field elements.
+// Only k_miller2 asks for them (in the other kernels that inline this loop the register report does not stay as it is).
+template <bool LINE_SUMS = false, class RF, class RT>
 ZKV_HD bool miller_loop_p(const VkTables* vkp, uint32_t flags, SoaRef norm, SoaRef bsrc, RF fm, RT tm, bool check_b = false, const uint32_t* start = nullptr) {
     const uint8_t KIND[ZKV_MILLER_STEPS] = ZKV_MILLER_STEP_KIND;
     const bool with_fixed = vkp != nullptr;
@@ -386,7 +389,21 @@ ZKV_HD bool miller_loop_p(const VkTables* vkp, uint32_t flags, SoaRef norm, SoaR
         asm volatile("" : "+v"(norm.off), "+v"(bsrc.off));
 #endif
         if (kind == 0 && li != 0) { ZKV_MARK("begin sqr"); f12m_sqr_body(fm); ZKV_MARK("end sqr"); }
-        if (do_t) {
+        if (LINE_SUMS && do_t) {
+            // the line steps hand over the scaled coefficients c3 = l1 xs, c4 = l3 ys, so the product follows at once
+            Fp2 l0, c3, c4;
+            const auto scale = [&](int k) { return norm.fp(8 * k); };
+            if (kind == 0) { ZKV_MARK("begin linedbl"); line_dbl_sums(tm, l0, c3, c4, scale); ZKV_MARK("end linedbl"); }
+            else {
+                Fp2 qx, qy; qx.h = bsrc.fp(0); qy.h = bsrc.fp(16);
+                if (kind == 2) qy = f2_neg(qy);
+                else if (kind == 3) { Fp2 x, y; g2_frob_affine(x, y, qx, qy); qx = x; qy = y; }
+                else if (kind == 4) { Fp2 x, y; g2_frob2_affine(x, y, qx, qy); qx = x; qy = f2_neg(y); }
+                ZKV_MARK("begin lineadd"); line_add_sums(tm, qx, qy, l0, c3, c4, scale); ZKV_MARK("end lineadd");
+            }
+            if (do_ab) { ZKV_MARK("begin mul034"); f12m_mul_by_034_body(fm, l0, c3, c4); ZKV_MARK("end mul034"); }
+        }
+        if (!LINE_SUMS && do_t) {
             Fp2 l0, l1, l3;
             G2H T; T.x = m_ld_f2(tm, 0); T.y = m_ld_f2(tm, 1); T.z = m_ld_f2(tm, 2);
             if (kind == 0) { ZKV_MARK("begin linedbl"); line_dbl(T, l0, l1, l3); ZKV_MARK("end linedbl"); }

@@ -53,13 +53,30 @@ def instrs(lines, a, b):
             yield l.strip()
 
 
+def callee(lines, at):
+    """The function an `s_swappc_b64 s[30:31], s[N:N+1]` at line `at` calls: the symbol of the nearest `s_add_u32 sN, sN, SYM@rel32@lo`
+    above it.  The address of a leaf that a body calls several times is formed once and kept in its register pair, so the register names
+    the callee, not the last symbol seen (which charged every later call of the tangent step to fp_mul, 81 multiply-adds short for each
+    f2_mul_lane)."""
+    m = re.search(r'(?:s\[(\d+):\d+\]|(vcc))\s*$', lines[at].strip())
+    if not m:
+        return None
+    lo = 'vcc_lo' if m.group(2) else 's' + m.group(1)
+    pat = re.compile(r's_add_u32\s+%s,\s*%s,\s*(_ZN\w+)@rel32@lo' % (lo, lo))
+    for k in range(at - 1, max(at - 60000, -1), -1):
+        f = pat.search(lines[k])
+        if f:
+            return f.group(1)
+    return None
+
+
 def walk(lines, start, labels, funcs, memo, stop_mark=None, end=None):
     """Instruction stream from line `start` along the executed path: unconditional branches are followed, conditional ones fall
     through (the marked bodies are straight-line code; their only conditional branches skip lane-masked sections; s_cbranch_execnz is
     followed), calls add the
     callee.  Stops at `stop_mark` (a '; ZKVMARK end X' comment) or at line `end`."""
     h, mn_h = collections.Counter(), collections.Counter()
-    pending, i, steps = None, start, 0
+    i, steps = start, 0
     while True:
         if end is not None and i >= end:
             break
@@ -74,10 +91,8 @@ def walk(lines, start, labels, funcs, memo, stop_mark=None, end=None):
         ins = l.strip()
         mn = ins.split()[0]
         h[classify(mn)] += 1; mn_h[mn] += 1
-        m = re.search(r'(_ZN\w+)@rel32@lo', ins)
-        if m:
-            pending = m.group(1)
-        if mn == 's_swappc_b64' and pending:
+        pending = callee(lines, i - 1) if mn == 's_swappc_b64' else None
+        if pending:
             if pending not in memo:
                 fa, fb = funcs[pending]
                 memo[pending] = walk(lines, fa, labels, funcs, memo, end=fb)
