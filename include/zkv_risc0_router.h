@@ -34,8 +34,12 @@
  *
  * Context-wide calls: zkv_ctx_destroy, _synchronize, _reserve, _set_lanes_per_proof and _last_stage_ms forward to both groups (the
  * built-in routes are one verifier set, the keyed routes one key set) and keep their meaning; zkv_ctx_last_stage_ms sums the groups
- * that ran in the most recent call.  zkv_ctx_vm returns ZKV_VM_RISC0_ROUTER.  zkv_ctx_set_aggregate_check returns ZKV_OK and reaches
- * the built-in group only: the keyed group keeps the per-proof path (no aggregate check and no GT tables for it).  A router is
+ * that ran in the most recent call.  zkv_ctx_vm returns ZKV_VM_RISC0_ROUTER.  zkv_ctx_set_aggregate_check reaches both groups: the
+ * built-in group with seed32 itself, the keyed group under the key sets' rules (zkv_groth16_set.h) with a secret of its own,
+ * SHA-256(seed32 | 255), or drawn from the operating system -- only with the automatic mapping, from ZKV_AGG_MIN seals on the keyed
+ * routes in one call, for routes whose key is valid with alpha and beta finite; a sub-batch holds seals of one route only, a failed
+ * sub-batch is verified again seal by seal, and statuses and received selectors are those of the per-proof path, byte for byte.
+ * zkv_ctx_aggregate_counters sums the two groups.  No GT tables for the keyed group.  A router is
  * single-device: zkv_ctx_create_sharded refuses it, and every batch entry point of another kind returns ZKV_ERR_WRONG_CTX on it.
  *
  * Device scratch of a batch call, on top of the two groups' own workspaces: 349 bytes per seal (compact 260-byte record, the two

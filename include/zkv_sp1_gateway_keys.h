@@ -17,8 +17,12 @@
  * pinned SP1 statuses.  PARITY UNPINNED for every other key: three-way agreement (spec model, C oracle, device) only.
  *
  * Context-wide calls: zkv_ctx_reserve, _synchronize, _set_lanes_per_proof and _last_stage_ms forward to the keyed routes as to any
- * route.  zkv_ctx_set_aggregate_check returns ZKV_OK and the keyed routes keep the per-proof path (no aggregate check and no GT tables
- * for them; a sharded gateway does not exist).
+ * route.  zkv_ctx_set_aggregate_check reaches the keyed routes too: together they take the check under the key sets' rules
+ * (zkv_groth16_set.h) -- only with the automatic mapping, from ZKV_AGG_MIN proofs on the keyed routes in one call, for routes whose key
+ * is valid with alpha and beta finite; a sub-batch holds proofs of one route only, a failed sub-batch is verified again proof by proof,
+ * and statuses and received selectors are those of the per-proof path, byte for byte.  Their secret is their own: SHA-256(seed32 | 255),
+ * the derivation of the routes' secrets under an index no route has, or 32 bytes from the operating system (re-drawn as for any
+ * context).  zkv_ctx_aggregate_counters includes their sub-batches in its sums.  No GT tables for them; a sharded gateway does not exist.
  *
  * Device memory per keyed route: one VkTables (2,644,456 bytes, most of it the unused short-key rows of the struct) and two signals' 8-bit
  * window rows of 524,288 bytes each -- 3,693,032 bytes; the workspace of the keyed routes is one, shared, and sized by their proofs in flight.

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(GW_BLOCK) void k_gateway_place(GatewayArgs a) {
         demux_answer(i, c == GW_COL_SHORT ? 4 : c == GW_COL_BAD ? 6 : 8, sel, a.pos, a.status, a.recv);
         return;
     }
-    const uint32_t slot = demux_slot<GW_COLS>(c, mine, wc, a.start, a.cnt);
+    const uint32_t slot = demux_slot<GW_COLS>(c, mine, wc, a.start, a.agg, a.astart, a.cnt);
     a.pos[i] = slot;
     a.idx[slot] = (uint32_t)i;
     uint64_t at, len;
@@ -120,12 +120,18 @@ __global__ __launch_bounds__(GW_BLOCK) void k_gateway_gather(GatewayArgs a) {
     if (i >= a.n) return;
     const uint32_t slot = a.pos[i];
     if (slot == GW_NONE) return;
-    // route of the slot: the last route starting at or before it (an empty route starts where the next one does)
-    uint32_t r = 0;
+    // a slot of the keyed group: the group-relative 260-byte row, in either of its regions.  Otherwise the route of the slot: the last
+    // route starting at or before it (an empty route starts where the next one does; a keyed route's start lies inside the group)
+    uint32_t rec = 260;
+    uint32_t* dst;
+    if (slot - a.g0 < a.gm) dst = (uint32_t*)(a.c_proofs + a.gb0 + (uint64_t)(slot - a.g0) * 260);
+    else {
+        uint32_t r = 0;
 #pragma unroll
-    for (int k = 1; k < GW_MAX_ROUTES; k++) if ((uint32_t)k < a.n_routes && a.start[k] <= slot) r = (uint32_t)k;
-    const uint32_t rec = a.rec[r];
-    uint32_t* dst = (uint32_t*)(a.c_proofs + a.base[r] + (uint64_t)(slot - a.start[r]) * rec);
+        for (int k = 1; k < GW_MAX_ROUTES; k++) if ((uint32_t)k < a.n_routes && a.start[k] <= slot) r = (uint32_t)k;
+        rec = a.rec[r];
+        dst = (uint32_t*)(a.c_proofs + a.base[r] + (uint64_t)(slot - a.start[r]) * rec);
+    }
     uint64_t at, len;
     gw_span(a, i, &at, &len);
     demux_copy_record(dst, a.proofs + at, len, rec, lane);

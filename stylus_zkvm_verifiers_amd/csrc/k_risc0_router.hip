@@ -89,7 +89,7 @@ __global__ __launch_bounds__(RZR_BLOCK) void k_rzrouter_place(RzrArgs a) {
         demux_answer(i, bad ? 6 : c == RZR_COL_SHORT ? 4 : 8, sel, a.pos, a.status, a.recv);
         return;
     }
-    const uint32_t slot = demux_slot<RZR_COLS>(c, mine, wc, a.start, a.cnt);
+    const uint32_t slot = demux_slot<RZR_COLS>(c, mine, wc, a.start, a.agg, a.astart, a.cnt);
     a.pos[i] = slot;
     a.idx[slot] = (uint32_t)i;
     uint64_t at, len;

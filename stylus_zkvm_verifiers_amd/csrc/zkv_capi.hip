@@ -1882,26 +1882,79 @@ static int gset_proof_stages(zkv_ctx* g, const GsetChunk& ch, int lanes, bool ti
     HIP_TRY(hipGetLastError());
     return ZKV_OK;
 }
-// The keyed group of a router (DESIGN.md sections 12d, 17): the M padded slots the demultiplexer has filled, verified in one pass for all
-// keys of the key set g -- prep(ch) fills and launches the caller's PREP record for the chunk, then the key sets' stages, chunk by chunk
-// as run_gset runs them (no tail split, no aggregate check).  idx, skey, st: the group's slot tables (index 0 = its first slot).  The
-// set's own buffers (its keys, staged signals, workspace) are read after groth16_ready, which may have made them: a PREP record takes
-// them from the chunk it is handed (keyed_prep_chunk), never from g before the call.  g->mu is held by the caller.
+// The keyed group of a router (DESIGN.md sections 12d, 12f, 17): the M padded slots the demultiplexer has filled, verified in one pass for
+// all keys of the key set g -- prep(ch) fills and launches the caller's PREP record for the chunk, then the key sets' stages, chunk by
+// chunk as run_gset runs them (no tail split).  idx, skey, st: the group's slot tables (index 0 = its first slot).  The set's own buffers
+// (its keys, staged signals, workspace) are read after groth16_ready, which may have made them: a PREP record takes them from the chunk it
+// is handed (keyed_prep_chunk), never from g before the call.  g->mu is held by the caller.
+// The aggregate check on the group (zkv_ctx_set_aggregate_check on the front end, under the key sets' rules): keyed_group_begin decides
+// whether the call takes it -- before the slots are laid out, the device has seen the count kernel only -- and names the capable keys
+// for route_layout_agg; run_keyed_group then runs the set's aggregate sequence over the aggregate region [0, ka.R) with the caller's PREP
+// (chunks ending on multiples of the unit), and the per-proof chunks from ka.R on.
 static int groth16_ready(zkv_ctx* c, size_t n, size_t* chunk);
+static bool gset_agg_tables(zkv_ctx* c);
+struct GsetAggChunk { size_t base, m, n2, off; uint64_t slots; int lanes; };       // (set_agg_plan)
+static int set_agg_plan(zkv_ctx* c, const uint64_t* beg, const uint64_t* end, const uint32_t* rep, uint32_t n_regions, uint64_t R, size_t capa,
+                        uint32_t sub, std::vector<GsetAggChunk>* plan, hipStream_t s);
 template <class Prep>
-static int run_keyed_group(zkv_ctx* g, size_t M, int lanes, const uint32_t* idx, const uint32_t* skey, uint8_t* st, hipStream_t s, Prep prep) {
-    if (!M) return ZKV_OK;
+static void enqueue_gset_agg(zkv_ctx* c, const GsetChunk& ch, const GsetAggChunk& g, const uint32_t* skey, const uint32_t* d_amap, uint32_t sub,
+                             hipStream_t s, bool timed, Prep prep);
+struct KeyedAgg {
+    const uint8_t* capable = nullptr;               // per key of the group: can take the check (null: this call does not)
+    uint32_t sub = 0;                               // proofs per sub-batch of this call
+    uint64_t R = 0;                                 // the aggregate region the layout gave: group slots [0, R), key k from astart[k]
+    uint64_t astart[ROUTE_MAX_COLS + 1] = {};
+};
+// tot: the K keyed columns' totals, `placed` their sum.  *lanes: the mapping of the per-proof slots, as route_layout_agg takes it.
+static int keyed_group_begin(zkv_ctx* g, const uint32_t* tot, size_t K, size_t placed, hipStream_t s, KeyedAgg* ka, int* lanes) {
+    *ka = KeyedAgg();
+    *lanes = miller_lanes(g, placed);
+    if (!placed) return ZKV_OK;
     size_t cap = 0;
-    int rc = groth16_ready(g, M, &cap);
+    int rc = groth16_ready(g, placed, &cap);
     if (rc != ZKV_OK) return rc;
     if ((rc = order_after_previous(g, s)) != ZKV_OK) return rc;
-    for (size_t base = 0; base < M; base += cap) {
-        const size_t m = M - base < cap ? M - base : cap;
+    if (!(g->agg_on && g->lanes == 0 && placed >= agg_min() && gset_agg_tables(g) && agg_wanted(g))) return ZKV_OK;
+    // the workspace for any layout of these proofs (at most 31 pad slots per key) and, now that the tables have made agg_key_ok, the
+    // aggregate buffers beside it: nothing grows once the slots are laid out
+    if ((rc = groth16_ready(g, placed + 31 * K, &cap)) != ZKV_OK) return rc;
+    const uint32_t unit = gset_agg_unit(g->agg_sub);
+    if (g->agg_cap < g->ws.cap || cap < unit) return ZKV_OK;                     // (the aggregate buffers could not be allocated)
+    size_t rest = 0;
+    for (size_t k = 0; k < K; k++) rest += g->gs_agg_ok[k] ? tot[k] % unit : tot[k];
+    ka->capable = g->gs_agg_ok.data(); ka->sub = g->agg_sub;
+    *lanes = miller_lanes(g, rest);
+    return ZKV_OK;
+}
+template <class Prep>
+static int run_keyed_group(zkv_ctx* g, size_t M, int lanes, const KeyedAgg& ka, const uint32_t* idx, const uint32_t* skey, uint8_t* st, hipStream_t s, Prep prep) {
+    if (!M) return ZKV_OK;
+    size_t cap = 0;
+    int rc = groth16_ready(g, M, &cap);            // (with the check engaged keyed_group_begin has sized the buffers already: nothing grows here)
+    if (rc != ZKV_OK) return rc;
+    auto chunk = [&](size_t base, size_t m) {
         GsetChunk ch;
         memset(&ch, 0, sizeof ch);
         ch.m = m; ch.slot0 = base; ch.idx = idx; ch.skey = skey;
         ch.keys = g->d_gs_key; ch.rows = g->d_gs_rows; ch.win = g->d_gs_win;
         ch.sig = g->d_lsig; ch.sig_cap = lsig_stride(g); ch.status = st + base;
+        return ch;
+    };
+    const size_t R = (size_t)ka.R;
+    if (R) {
+        // one region per key, the keys back to back, as run_gset passes them
+        const uint32_t unit = gset_agg_unit(ka.sub);
+        std::vector<GsetAggChunk> plan;
+        if ((rc = set_agg_plan(g, ka.astart, ka.astart + 1, nullptr, (uint32_t)g->gs_nic.size(), R, cap / unit * unit, ka.sub, &plan, s)) != ZKV_OK) return rc;
+        for (const GsetAggChunk& a : plan) {
+            const GsetChunk ch = chunk(a.base, a.m);
+            enqueue_gset_agg(g, ch, a, skey + a.base, g->m_ks.amap, ka.sub, s, M == R && a.base + a.m >= R, [&] { prep(ch); });
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    for (size_t base = R; base < M; base += cap) {
+        const size_t m = M - base < cap ? M - base : cap;
+        const GsetChunk ch = chunk(base, m);
         if ((rc = gset_proof_stages(g, ch, lanes, base + cap >= M, s, [&] { prep(ch); })) != ZKV_OK) return rc;
     }
     return mark_done(g, s);
@@ -2037,7 +2090,9 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
                        const GwWireArgs* recs = nullptr) {
     int rc;
     const size_t blocks = (n + 255) / 256, R = c->gw_route.size(), K = c->gw_nkeys, key0 = c->gw_key0;
-    // slots: one per routed proof, and up to 31 pad slots behind every keyed route (its successor starts on a wavefront of the Miller mapping)
+    // slots: one per routed proof, and up to 31 pad slots behind every keyed route (its successor starts on a wavefront of the Miller
+    // mapping).  With the aggregate check on the keyed group the bound is the same: the aggregate region pads nothing, and every route's
+    // per-proof part is padded as the whole route was (zkv_gset_layout.h route_layout_agg).
     const size_t ns = n + 32 * K;
     GatewayMem& gm = c->m_gw;                                     // (the compact records are sized behind the count)
     if ((rc = grow_all(gm.cnt, 4 * GW_COLS * blocks, gm.totals, 4 * GW_COLS, gm.pos, 4 * n, gm.idx, 4 * ns, gm.len, 4 * ns, gm.a, 32 * ns,
@@ -2067,9 +2122,18 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
     for (size_t k = 0; k < K; k++) placed += tot[key0 + k];
     std::unique_lock<std::mutex> glk;
     if (K) glk = std::unique_lock<std::mutex>(c->gw_group->mu);
+    // whether the group takes the aggregate check is decided here, before the layout: the layout then has two regions (route_layout_agg)
+    KeyedAgg ka;
+    int glanes = 0;
+    if (K && (rc = keyed_group_begin(c->gw_group, tot + key0, K, placed, s, &ka, &glanes)) != ZKV_OK) return rc;
     RouteLayout L;
-    route_layout(tot, (uint32_t)R, (uint32_t)key0, (uint32_t)K, a.rec, K ? miller_lanes(c->gw_group, placed) : 0, K && c->gw_group->lanes != 0, &L);
+    RouteAggLayout A;
+    route_layout_agg(tot, (uint32_t)R, (uint32_t)key0, (uint32_t)K, a.rec, glanes, K && c->gw_group->lanes != 0, ka.capable, ka.sub, &L, &A);
+    ka.R = A.R;
+    for (size_t k = 0; k <= K; k++) ka.astart[k] = A.astart[k];
     for (size_t r = 0; r < R; r++) { a.start[r] = L.start[r]; a.base[r] = L.base[r]; }
+    for (size_t k = 0; k < K; k++) { a.agg[key0 + k] = A.agg[k]; a.astart[key0 + k] = (uint32_t)(L.g0 + A.astart[k]); }
+    a.g0 = (uint32_t)L.g0; a.gm = (uint32_t)L.m; a.gb0 = L.b0;
     if (routed + tot[GW_COL_NOT_FOUND] + tot[GW_COL_SHORT] + tot[GW_COL_BAD] != n || L.slots > ns) return ZKV_ERR_HIP;
     if ((rc = gm.recs.grow((size_t)L.bytes + 8)) != ZKV_OK) return rc;
     a.c_proofs = gm.recs;
@@ -2093,9 +2157,10 @@ static int run_gateway(zkv_ctx* c, size_t n, const uint8_t* d_vkeys, const uint8
         pc.idx = a.idx + G0; pc.skey = gm.skey;
         pc.recs = a.c_proofs + L.b0; pc.len = a.c_len + G0; pc.vkeys = a.c_a + 32 * G0; pc.pvoff = a.c_pvoff + G0; pc.pvlen = a.c_pvlen + G0; pc.pv = d_pv;
         pc.n_keys = (uint32_t)K;
-        for (size_t k = 0; k < K; k++) pc.start[k] = (uint32_t)L.gstart[k];
+        for (size_t k = 0; k < K; k++) { pc.start[k] = (uint32_t)L.gstart[k]; pc.astart[k] = (uint32_t)A.astart[k]; }
+        pc.agg_r = (uint32_t)A.R;
         pc.status = st + G0; pc.recv = (uint32_t*)(rv + 4 * G0);
-        if ((rc = run_keyed_group(g, (size_t)L.m, L.lanes, pc.idx, pc.skey, pc.status, s, [&](const GsetChunk& ch) {
+        if ((rc = run_keyed_group(g, (size_t)L.m, L.lanes, ka, pc.idx, pc.skey, pc.status, s, [&](const GsetChunk& ch) {
                 keyed_prep_chunk(&pc, ch);
                 launch_gwset_prep(pc, g->ws, s); })) != ZKV_OK) return rc;
     }
@@ -2268,7 +2333,8 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
                       uint8_t* d_status, uint8_t* d_recv, hipStream_t s, const uint8_t* d_method = nullptr, const uint32_t* d_wire_len = nullptr) {
     int rc;
     const size_t blocks = (n + 255) / 256, R = c->gw_sel.size(), NB = c->rz_nb, K = R - NB;
-    // slots: one per routed seal, and up to 31 pad slots behind every keyed route (its successor starts on a wavefront of the Miller mapping)
+    // slots: one per routed seal, and up to 31 pad slots behind every keyed route (its successor starts on a wavefront of the Miller mapping);
+    // the same bound with the aggregate check on the keyed group (run_gateway)
     const size_t ns = n + 32 * K;
     RouterMem& rm = c->m_rz;
     if ((rc = grow_all(rm.cnt, 4 * GW_COLS * blocks, rm.totals, 4 * GW_COLS, rm.itot, 4 * (RZR_BAD_WORD + 1), rm.pos, 4 * n, rm.idx, 4 * ns,
@@ -2306,10 +2372,16 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
     if (K) glk = std::unique_lock<std::mutex>(c->gw_group->mu);
     uint32_t rec[RZR_COL_KEYED0 + RZR_MAX_KEYED];
     for (uint32_t& v : rec) v = ZKV_SEAL_BYTES;
+    KeyedAgg ka;                                                   // (the aggregate check on the keyed group: decided before the layout, as run_gateway does)
+    int glanes = 0;
+    if (K && (rc = keyed_group_begin(c->gw_group, tot + RZR_COL_KEYED0, K, placed, s, &ka, &glanes)) != ZKV_OK) return rc;
     RouteLayout L;
-    route_layout(tot, (uint32_t)(RZR_COL_KEYED0 + K), RZR_COL_KEYED0, (uint32_t)K, rec, K ? miller_lanes(c->gw_group, placed) : 0,
-                 K && c->gw_group->lanes != 0, &L);
+    RouteAggLayout A;
+    route_layout_agg(tot, (uint32_t)(RZR_COL_KEYED0 + K), RZR_COL_KEYED0, (uint32_t)K, rec, glanes, K && c->gw_group->lanes != 0, ka.capable, ka.sub, &L, &A);
+    ka.R = A.R;
+    for (size_t k = 0; k <= K; k++) ka.astart[k] = A.astart[k];
     for (size_t q = 0; q < RZR_COL_KEYED0 + K; q++) a.start[q] = L.start[q];
+    for (size_t k = 0; k < K; k++) { a.agg[RZR_COL_KEYED0 + k] = A.agg[k]; a.astart[RZR_COL_KEYED0 + k] = (uint32_t)(L.g0 + A.astart[k]); }
     uint64_t isum = 0;
     for (size_t r = 0; r < NB; r++) isum += itot[r];
     const uint32_t n_bad = itot[RZR_BAD_WORD];                     // in the short column
@@ -2327,10 +2399,11 @@ static int run_router(zkv_ctx* c, size_t n, const uint8_t* d_seals, const uint64
         pc.recs = a.c_seals + L.b0; pc.len = a.c_len + G0; pc.in_a = a.c_a + 32 * G0; pc.in_b = a.in_b ? a.c_b + 32 * G0 : nullptr;
         pc.kind = a.c_kind ? a.c_kind + G0 : nullptr;
         pc.n_keys = (uint32_t)K;
-        for (size_t k = 0; k < K; k++) pc.start[k] = (uint32_t)L.gstart[k];
+        for (size_t k = 0; k < K; k++) { pc.start[k] = (uint32_t)L.gstart[k]; pc.astart[k] = (uint32_t)A.astart[k]; }
+        pc.agg_r = (uint32_t)A.R;
         pc.routes = rm.routes;
         pc.status = st + G0; pc.recv = (uint32_t*)(rv + 4 * G0);
-        if ((rc = run_keyed_group(g, (size_t)L.m, L.lanes, pc.idx, pc.skey, pc.status, s, [&](const GsetChunk& ch) {
+        if ((rc = run_keyed_group(g, (size_t)L.m, L.lanes, ka, pc.idx, pc.skey, pc.status, s, [&](const GsetChunk& ch) {
                 keyed_prep_chunk(&pc, ch);
                 launch_rzrouter_prep(pc, c->consts, g->ws, s); })) != ZKV_OK) return rc;
     }
@@ -3353,7 +3426,7 @@ static int set_slot_buffers(zkv_ctx* c, size_t M, GsetPart* p, hipStream_t s) {
 // The aggregate chunks of the aggregate region [0, R), `capa` slots each, and their pseudo-proof maps (zkv_gset_layout.h
 // gset_agg_chunk_plan, whose regions the caller passes on): chunk g's map is in gs_amap from word g.off -- psl (sub-batch -> pseudo slot, n2
 // words), then the key of every pseudo slot (slots words) -- and all of gs_amap goes to m_ks.amap in one copy.
-struct GsetAggChunk { size_t base, m, n2, off; uint64_t slots; int lanes; };
+// (GsetAggChunk: declared with run_keyed_group, which plans the keyed group of a router the same way)
 static int set_agg_plan(zkv_ctx* c, const uint64_t* beg, const uint64_t* end, const uint32_t* rep, uint32_t n_regions, uint64_t R, size_t capa,
                         uint32_t sub, std::vector<GsetAggChunk>* plan, hipStream_t s) {
     c->gs_amap.clear();
@@ -3390,18 +3463,20 @@ static GsetChunk gset_chunk_of(const zkv_ctx* c, const GsetPart& p, const uint8_
     ch.sig = c->d_lsig; ch.sig_cap = lsig_stride(c); ch.status = c->d_st_all + base;
     return ch;
 }
-// The aggregate check of one chunk of a set's aggregate region (zkv_agg.h; k_gset_agg.hip): PREP, the coefficients and r A', r C, the
+// The aggregate check of one chunk of a set's aggregate region (zkv_agg.h; k_gset_agg.hip): PREP (`prep` launches it: the set's own
+// k_gset_prep, or the PREP kernel of a router's keyed group, as in gset_proof_stages), the coefficients and r A', r C, the
 // Miller loop of the variable pair, one pseudo-proof per sub-batch with its key's gamma / delta lines and ML(alpha, beta), the product of the
 // proofs' Miller values into it, its final exponentiation, the verdicts, and the per-proof kernels once more over the proofs of the
 // sub-batches that failed (in place: k_gset_agg_mark).
+template <class Prep>
 static void enqueue_gset_agg(zkv_ctx* c, const GsetChunk& ch, const GsetAggChunk& g, const uint32_t* skey, const uint32_t* d_amap, uint32_t sub,
-                             hipStream_t s, bool timed) {
+                             hipStream_t s, bool timed, Prep prep) {
     const size_t m = ch.m;
     const uint32_t sub64 = sub < 64 ? sub : 64, grp = agg_group(sub64);
     const uint32_t* psl = d_amap + g.off;
     const uint32_t* skey2 = psl + g.n2;
     if (timed) (void)hipEventRecord(c->ev[0], s);
-    launch_gset_prep(ch, c->ws, s);
+    prep();
     if (timed) (void)hipEventRecord(c->ev[1], s);
     agg_next_coefficients(c);
     launch_agg_g1(m, c->d_gs_tab, nullptr, c->ws, c->d_agg, c->agg_seed, true, s);      // (reads no key: the set's tables have n_var = 0)
@@ -3470,8 +3545,8 @@ static int run_gset(zkv_ctx* c, size_t n, const uint32_t* d_key, const uint8_t* 
         std::vector<GsetAggChunk> plan;
         if ((rc = set_agg_plan(c, c->gs_map.data(), c->gs_map.data() + 1, nullptr, K, R, cap / unit * unit, sub, &plan, s)) != ZKV_OK) return rc;
         for (const GsetAggChunk& g : plan) {
-            enqueue_gset_agg(c, gset_chunk_of(c, p, d_proofs, d_signals, g.base, g.m), g, p.skey + g.base, c->m_ks.amap, sub, s,
-                             M == R && g.base + g.m >= R);
+            const GsetChunk ch = gset_chunk_of(c, p, d_proofs, d_signals, g.base, g.m);
+            enqueue_gset_agg(c, ch, g, p.skey + g.base, c->m_ks.amap, sub, s, M == R && g.base + g.m >= R, [&] { launch_gset_prep(ch, c->ws, s); });
             HIP_TRY(hipGetLastError());
         }
     }
@@ -4016,6 +4091,20 @@ ZKV_EXPORT int zkv_diag_gt_product(zkv_ctx* c, size_t n, const uint32_t* scalars
     for (size_t i = 0; i < n; i++) for (size_t k = 0; k < GT_ENTRY_WORDS; k++) out[i * GT_ENTRY_WORDS + k] = res[k * n + i];
     return ZKV_OK;
 }
+// The keyed group of a gateway or router (gw_group, a Groth16 key set): its secret is derived from the front end's seed as the routes'
+// are -- SHA-256(seed | index), with index 255, which no route has -- or drawn from the operating system (seed = nullptr).
+constexpr uint8_t AGG_GROUP_SEED_INDEX = 255;
+ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t* seed32);
+static int set_group_aggregate_check(zkv_ctx* group, int enable, const uint8_t* seed) {
+    if (!enable || !seed) return zkv_ctx_set_aggregate_check(group, enable, nullptr);
+    uint8_t buf[33], sk[32];
+    memcpy(buf, seed, 32); buf[32] = AGG_GROUP_SEED_INDEX;
+    host::sha256_host(buf, 33, sk);
+    const int rc = zkv_ctx_set_aggregate_check(group, enable, sk);
+    { volatile uint8_t* w = sk; for (int i = 0; i < 32; i++) w[i] = 0; }
+    { volatile uint8_t* w = buf; for (int i = 0; i < 33; i++) w[i] = 0; }
+    return rc;
+}
 // Aggregate check on / off (zkv_agg.h).  seed32 = nullptr draws the 32 secret bytes from the operating system.
 ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t* seed32) {
     if (!c || (enable != 0 && enable != 1 && enable != 16 && enable != 32 && enable != 64 && enable != 128 && enable != 256)) return ZKV_ERR_INVALID_ARG;
@@ -4037,17 +4126,22 @@ ZKV_EXPORT int zkv_ctx_set_aggregate_check(zkv_ctx* c, int enable, const uint8_t
     if (c->vm == ZKV_VM_MIXED || c->vm == ZKV_VM_SP1_GATEWAY) {
         const size_t nk = c->vm == ZKV_VM_MIXED ? 2 : c->gw_route.size();
         for (size_t k = 0; k < nk; k++) {
-            if (c->vm == ZKV_VM_SP1_GATEWAY && !c->gw_route[k]) continue;      // a keyed route: its group keeps the per-proof path
+            if (c->vm == ZKV_VM_SP1_GATEWAY && !c->gw_route[k]) continue;      // a keyed route: its group follows the loop
             uint8_t sk[32];
             if (enable && seed32) { uint8_t buf[33]; memcpy(buf, seed, 32); buf[32] = (uint8_t)k; host::sha256_host(buf, 33, sk); }
             const int rc = zkv_ctx_set_aggregate_check(c->vm == ZKV_VM_MIXED ? c->kid[k] : c->gw_route[k], enable, enable && seed32 ? sk : nullptr);
             { volatile uint8_t* w = sk; for (int i = 0; i < 32; i++) w[i] = 0; }
             if (rc != ZKV_OK) return rc;
         }
+        if (c->vm == ZKV_VM_SP1_GATEWAY && c->gw_group) {   // the keyed group: a secret of its own, under an index no route has
+            const int rc = set_group_aggregate_check(c->gw_group, enable, seed32 ? seed : nullptr);
+            if (rc != ZKV_OK) return rc;
+        }
         return ZKV_OK;
     }
-    if (c->vm == ZKV_VM_RISC0_ROUTER) {                  // the built-in group only: the keyed group keeps the per-proof path
-        const int rc = c->kid[0] ? zkv_ctx_set_aggregate_check(c->kid[0], enable, enable && seed32 ? seed : nullptr) : ZKV_OK;
+    if (c->vm == ZKV_VM_RISC0_ROUTER) {                  // the built-in group with the seed itself, the keyed group with one derived from it
+        int rc = c->kid[0] ? zkv_ctx_set_aggregate_check(c->kid[0], enable, enable && seed32 ? seed : nullptr) : ZKV_OK;
+        if (rc == ZKV_OK && c->gw_group) rc = set_group_aggregate_check(c->gw_group, enable, seed32 ? seed : nullptr);
         { volatile uint8_t* w = seed; for (int i = 0; i < 32; i++) w[i] = 0; }
         return rc;
     }
@@ -4084,9 +4178,24 @@ ZKV_EXPORT int zkv_ctx_aggregate_counters(zkv_ctx* c, uint64_t out[2]) {
             if (rc != ZKV_OK) return rc;
             out[0] += o[0]; out[1] += o[1];
         }
+        if (!is_sharded(c) && c->vm == ZKV_VM_SP1_GATEWAY && c->gw_group) {      // the keyed group's
+            uint64_t o[2];
+            const int rc = zkv_ctx_aggregate_counters(c->gw_group, o);
+            if (rc != ZKV_OK) return rc;
+            out[0] += o[0]; out[1] += o[1];
+        }
         return ZKV_OK;
     }
-    if (c->vm == ZKV_VM_RISC0_ROUTER) return c->kid[0] ? zkv_ctx_aggregate_counters(c->kid[0], out) : ZKV_OK;
+    if (c->vm == ZKV_VM_RISC0_ROUTER) {                  // the built-in group's and the keyed group's
+        for (zkv_ctx* k : {c->kid[0], c->gw_group}) {
+            if (!k) continue;
+            uint64_t o[2];
+            const int rc = zkv_ctx_aggregate_counters(k, o);
+            if (rc != ZKV_OK) return rc;
+            out[0] += o[0]; out[1] += o[1];
+        }
+        return ZKV_OK;
+    }
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->dev_ready || !c->d_agg_cnt) return ZKV_OK;
     HIP_TRY(hipSetDevice(c->device));

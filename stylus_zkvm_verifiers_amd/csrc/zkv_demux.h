@@ -34,15 +34,19 @@ __device__ __forceinline__ void demux_block_counts(const uint32_t (&wc)[COLS][WA
     }
 }
 
-// The place kernel's slot of an item of routed column c: the column's first slot, the items of the column in earlier workgroups (cnt
-// after the scan, COLS columns per block) and the item's rank in this one -- a stable partition.
+// The place kernel's slot of an item of routed column c, a stable partition: its rank among the column's items in caller order -- the
+// items of the column in earlier workgroups (cnt after the scan, COLS columns per block) and before it in this one -- from the column's
+// first slot.  A column may have two regions (the aggregate check on a keyed group, zkv_gset_layout.h gset_agg_slot): the first agg[c]
+// items go to astart[c] .., the others to start[c] ..; agg[c] = 0: one region from start[c].
 template <int COLS, int ROUTED, int WAVES>
-__device__ __forceinline__ uint32_t demux_slot(int c, uint64_t mine, const uint32_t (&wc)[ROUTED][WAVES], const uint32_t* start, const uint32_t* cnt) {
+__device__ __forceinline__ uint32_t demux_slot(int c, uint64_t mine, const uint32_t (&wc)[ROUTED][WAVES], const uint32_t* start, const uint32_t* agg,
+                                               const uint32_t* astart, const uint32_t* cnt) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
     uint32_t r = (uint32_t)__popcll(mine & below);
     for (uint32_t w = 0; w < wave; w++) r += wc[c][w];
-    return start[c] + cnt[(size_t)blockIdx.x * COLS + c] + r;
+    r += cnt[(size_t)blockIdx.x * COLS + c];
+    return r < agg[c] ? astart[c] + r : start[c] + (r - agg[c]);
 }
 
 // An item no verifier is asked about: answered here, no slot.  recv may be null.

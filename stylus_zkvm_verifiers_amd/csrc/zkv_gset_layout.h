@@ -122,6 +122,64 @@ inline uint64_t gset_agg_slot(uint32_t k, uint32_t rank, const uint32_t* agg, co
     return rank < agg[k] ? astart[k] + rank : pstart[k] + (rank - agg[k]);
 }
 
+// Selector routers with the aggregate check on their keyed group: route_layout with the keyed block laid out by
+// gset_agg_choose over the keyed columns' totals.  capable[k]: keyed route k can take the check (null: the check does not engage);
+// `lanes`: the mapping the items of the per-proof region would take.  The block [g0, g0 + m) is then two regions: the aggregate region
+// [g0, g0 + R), every capable key's first floor(tot / A) * A items back to back, no pad slots, and behind it the per-proof region, the
+// rests by gset_choose.  R and every agg[k] are multiples of A = gset_agg_unit(sub) >= 64, so every 64-slot block and every sub-batch of
+// the aggregate region lies inside one key.  Records stay rows of rec[key0] bytes: group slot j at b0 + rec[key0] * j.  The columns
+// before and after the block are route_layout's.  In L, a keyed column's start, base and gstart are those of its per-proof part
+// (gstart[k] = pstart[k] >= R); the live runs: the aggregate region is one run, which the first non-empty per-proof part continues
+// (it starts at slot R), so there are never more runs than non-empty columns.  With R = 0 -- no capable key holds A items -- L is
+// route_layout's result bit for bit, and pstart = gstart.
+// Slot bound: the aggregate region pads nothing and gset_choose pads every key's rest to at most 32 slots, so the call takes at most
+// n + 31 * n_keyed slots, as without the check.
+struct RouteAggLayout {
+    uint64_t R;                                     // slots of the aggregate region (0: one region, the check does not engage)
+    uint32_t agg[ROUTE_MAX_COLS], rest[ROUTE_MAX_COLS];        // keyed route k: items in the aggregate region, and the others
+    uint64_t astart[ROUTE_MAX_COLS + 1], pstart[ROUTE_MAX_COLS + 1];      // their first group slots (gset_agg_choose; index 0 = slot g0)
+};
+inline void route_layout_agg(const uint32_t* tot, uint32_t n_cols, uint32_t key0, uint32_t n_keyed, const uint32_t* rec, int lanes, int fixed,
+                             const uint8_t* capable, uint32_t sub, RouteLayout* L, RouteAggLayout* A) {
+    const uint32_t unit = gset_agg_unit(sub);
+    A->R = 0;
+    for (uint32_t k = 0; k < ROUTE_MAX_COLS; k++) { A->agg[k] = 0; A->rest[k] = k < n_keyed ? tot[key0 + k] : 0; }
+    for (uint32_t k = 0; k <= ROUTE_MAX_COLS; k++) A->astart[k] = A->pstart[k] = 0;
+    uint64_t r = 0;
+    if (capable) for (uint32_t k = 0; k < n_keyed; k++) if (capable[k]) r += tot[key0 + k] / unit * unit;
+    if (!r) {
+        route_layout(tot, n_cols, key0, n_keyed, rec, lanes, fixed, L);
+        for (uint32_t k = 0; k <= n_keyed; k++) A->pstart[k] = L->gstart[k];
+        return;
+    }
+    uint64_t slots = 0, bytes = 0;
+    L->g0 = L->b0 = L->m = 0; L->lanes = 0; L->n_runs = 0;
+    for (uint32_t k = 0; k <= ROUTE_MAX_COLS; k++) L->gstart[k] = 0;
+    auto run = [L](uint64_t at, uint64_t n) {
+        if (!n) return;
+        if (L->n_runs && L->run_at[L->n_runs - 1] + L->run_n[L->n_runs - 1] == at) L->run_n[L->n_runs - 1] += n;
+        else { L->run_at[L->n_runs] = at; L->run_n[L->n_runs] = n; L->n_runs++; }
+    };
+    for (uint32_t c = 0; c < n_cols; c++) {
+        if (c == key0) {
+            L->lanes = gset_agg_choose(tot + key0, capable, n_keyed, sub, lanes, fixed, A->agg, A->astart, A->rest, A->pstart, &A->R, &L->m);
+            for (uint32_t k = 0; k <= n_keyed; k++) L->gstart[k] = A->pstart[k];
+            L->g0 = slots; L->b0 = bytes;
+            run(L->g0, A->R);
+        }
+        if (c >= key0 && c < key0 + n_keyed) {
+            L->start[c] = (uint32_t)(L->g0 + L->gstart[c - key0]); L->base[c] = L->b0 + (uint64_t)rec[key0] * L->gstart[c - key0];
+            if (c + 1 == key0 + n_keyed) { slots = L->g0 + L->m; bytes = L->b0 + (uint64_t)rec[key0] * L->m; }
+            run(L->start[c], A->rest[c - key0]);
+        } else {
+            L->start[c] = (uint32_t)slots; L->base[c] = bytes;
+            slots += tot[c]; bytes += (uint64_t)tot[c] * rec[c];
+            run(L->start[c], tot[c]);
+        }
+    }
+    L->slots = slots; L->bytes = bytes;
+}
+
 // Aggregate check on a PLONK key set (zkv_plonk_set_agg.h).  A PLONK key gives the pairing check nothing but its two
 // G2 points, so a sub-batch may hold proofs of any keys of one SRS class (keys with the same [1]_2 | [tau]_2 bytes): cls[k] is key k's class,
 // capable[c] whether class c's points passed the set-up validation.  Key groups stay on 64-slot boundaries (PREP wavefronts stay

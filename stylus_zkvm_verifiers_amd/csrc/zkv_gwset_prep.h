@@ -57,16 +57,27 @@ ZKV_HD uint32_t gwset_key_of_slot(const uint32_t* start, uint32_t n_keys, uint32
     for (uint32_t q = 1; q < n_keys; q++) if (start[q] <= j) k = q;
     return k;
 }
+// With the aggregate check on the group (zkv_gset_layout.h route_layout_agg) the group has two regions, each with one start per key:
+// group slots below agg_r are the aggregate region (astart), the others the per-proof region (start).  The region is taken from
+// wave_slot, the first slot of the lane's 64-slot PREP block: agg_r and every chunk's first slot are multiples of 64, so a block lies in
+// one region and the choice between the two start rows stays wave-uniform.  agg_r = 0: gwset_key_of_slot over start.
+ZKV_HD uint32_t gwset_key_of_slot2(const uint32_t* astart, const uint32_t* start, uint32_t n_keys, uint32_t agg_r, uint32_t wave_slot, uint32_t j) {
+    return gwset_key_of_slot(wave_slot < agg_r ? astart : start, n_keys, j);
+}
 
 #if defined(__HIPCC__)
 // The PREP kernel of a keyed group (k_gwset_prep, k_rzrouter_prep), one slot per lane: everything around the unit's slot function.
 // Records are 260-byte rows from a 4-byte aligned base (the caller's own allocation; every record before the group's is a multiple of 4
 // bytes), so the 64 rows of a wavefront are 16,640 contiguous bytes: copied to LDS with coalesced dword loads, every lane then reads its
 // own 65 words (row stride 65 dwords: conflict-free), as k_prep_sp1 stages fixed-stride seals.  The address test is wave-uniform; a base
-// that fails it is read byte by byte.  Then the key of the slot (skey, for k_gset_msm / k_gset_miller), and for a live slot
+// that fails it is read byte by byte.  Then the key of the slot (skey, for k_gset_msm / k_gset_miller; two regions when the group takes
+// the aggregate check: gwset_key_of_slot2), and for a live slot
 // slot_fn(chunk, key, slot, record, r) -- the unit's checks, filling a Slot with NSIG signals --, the signals staged as GsetChunk::sig, the
 // points where k_gset_msm reads them, flags, status and the (zero) received selector.  Chunk: GwsetChunk or RzrChunk (zkv_internal.h);
 // lds: ZKV_BLOCK * 65 words of the kernel's.
+// A chunk of the aggregate region is left as k_gset_prep leaves one for k_agg_g1 and the k_gset_agg_* kernels: rows and flags of the live
+// slots, g2bad cleared, the signals staged (below r, or the slot is off), every slot's key; a slot the front checks fail is switched off
+// (flags 0) and keeps the status written here, which k_gset_agg_mark leaves alone.
 template <int NSIG, class Slot, class Chunk, class F>
 __device__ __forceinline__ void gwset_prep_lane(const Chunk& c, const Workspace& ws, uint32_t* lds, F slot_fn) {
     const size_t b0 = (size_t)blockIdx.x * ZKV_BLOCK;
@@ -83,7 +94,7 @@ __device__ __forceinline__ void gwset_prep_lane(const Chunk& c, const Workspace&
     const size_t j = b0 + threadIdx.x;
     if (j >= c.m) return;
     const size_t slot = c.slot0 + j;
-    const uint32_t k = gwset_key_of_slot(c.start, c.n_keys, (uint32_t)slot);
+    const uint32_t k = gwset_key_of_slot2(c.astart, c.start, c.n_keys, c.agg_r, (uint32_t)(c.slot0 + b0), (uint32_t)slot);
     c.skey[slot] = k;
     const uint32_t i = c.idx[slot];
     uint32_t flags = 0;

@@ -185,6 +185,11 @@ struct GatewayArgs {
     uint32_t sel[GW_MAX_ROUTES];                                               // route selectors, big-endian words (kernel arguments: SGPRs)
     uint32_t rec[GW_MAX_ROUTES];                                               // record bytes per route: ZKV_SEAL_BYTES or ZKV_PLONK_PROOF_BYTES
     uint32_t start[GW_MAX_ROUTES]; uint64_t base[GW_MAX_ROUTES];               // (place, gather) first slot and record byte offset of each route
+    // (place) aggregate check on the keyed group (zkv_gset_layout.h route_layout_agg): the first agg[r] proofs of route r, in caller order,
+    // go to slots astart[r] .., the others to start[r] .. (base[r] is that part's); agg[r] = 0: one region.  (gather) the keyed group is
+    // slots [g0, g0 + gm), its 260-byte rows from byte gb0, whichever region a slot lies in; gm = 0: no keyed route
+    uint32_t agg[GW_MAX_ROUTES], astart[GW_MAX_ROUTES];
+    uint32_t g0, gm; uint64_t gb0;
     uint32_t* cnt; uint32_t* totals;                                           // GW_COLS per block (exclusive scan in place), GW_COLS totals
     uint32_t* pos; uint32_t* idx;                                              // pos[i] = slot (GW_NONE: answered in place); idx[slot] = i
     uint8_t* c_proofs; uint32_t* c_len; uint8_t* c_a; uint64_t* c_pvoff; uint32_t* c_pvlen;    // compact records
@@ -231,12 +236,14 @@ int read_gset_wait_faults(unsigned long long* out);     // k_gset_miller_w64d's 
 // group, the gateway's routes with caller keys as one key set.  Every per-slot table is the group's (index 0 = its first slot): the
 // demultiplexer's compact outputs -- caller index (GW_NONE: pad slot), 260-byte records, true lengths, program vkeys, (offset, length)
 // of the public values in `pv` -- and the outputs: the slot's key (skey, read by k_gset_msm and k_gset_miller), the signals staged as
-// GsetChunk::sig, the status and the (zero) received selector.  start[k]: first group slot of key k (zkv_gset_layout.h).
+// GsetChunk::sig, the status and the (zero) received selector.  start[k]: first group slot of key k (zkv_gset_layout.h).  A chunk may be
+// one of the aggregate region: the k_gset_agg_* kernels then follow it as they follow k_gset_prep.
 struct GwsetChunk {
     size_t m, slot0;
     const uint32_t* idx; uint32_t* skey;
     const uint8_t* recs; const uint32_t* len; const uint8_t* vkeys; const uint64_t* pvoff; const uint32_t* pvlen; const uint8_t* pv;
     uint32_t n_keys; uint32_t start[GW_MAX_ROUTES];
+    uint32_t agg_r, astart[GW_MAX_ROUTES];           // aggregate region: group slots [0, agg_r), key k from astart[k]; start[] is then the per-proof region's
     const GsetKey* keys;
     uint32_t* sig; size_t sig_cap;
     uint8_t* status; uint32_t* recv;
@@ -257,6 +264,8 @@ struct RzrArgs {
     uint32_t n_builtin, n_keyed;
     uint32_t sel[32];                                                          // route selectors, big-endian words (kernel arguments: SGPRs)
     uint32_t start[9];                                                         // (place) first slot of the built-in group and of every keyed route
+    uint32_t agg[9], astart[9];                                                // (place) aggregate check on the keyed group, as GatewayArgs: the first
+                                                                               // agg[c] seals of column c go to slots astart[c] .., the others to start[c] ..
     uint32_t* cnt; uint32_t* totals;                                           // GW_COLS per block (exclusive scan in place), GW_COLS totals
     uint32_t* inst_tot;                                                        // seals per built-in route, then (word RZR_BAD_WORD) the bad-calldata
                                                                                // seals, which the short column counts too (zeroed by the host)
@@ -275,6 +284,7 @@ struct RzrChunk {
     const uint8_t* recs; const uint32_t* len; const uint8_t* in_a; const uint8_t* in_b;     // in_b == nullptr: verify_integrity
     const uint8_t* kind;                                                                    // per-slot ZKV_METHOD_*, or nullptr: in_b decides
     uint32_t n_keys; uint32_t start[GW_MAX_ROUTES];
+    uint32_t agg_r, astart[GW_MAX_ROUTES];           // as GwsetChunk
     const GsetKey* keys; const RzrRoute* routes;
     uint32_t* sig; size_t sig_cap;
     uint8_t* status; uint32_t* recv;

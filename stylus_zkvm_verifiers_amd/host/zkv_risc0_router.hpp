@@ -101,7 +101,8 @@ public:
         out.resize((size_t)n);
         return out;
     }
-    // Opt-in aggregate check on the built-in routes (zkv_ctx_set_aggregate_check): sub_batch 0 = automatic size, 16 ... 256 fixed.
+    // Opt-in aggregate check on the built-in routes and, under the key sets' rules, on the keyed routes (zkv_ctx_set_aggregate_check):
+    // sub_batch 0 = automatic size, 16 ... 256 fixed.
     void set_aggregate_check(bool enable, const uint8_t* seed32 = nullptr, int sub_batch = 0) {
         const int rc = zkv_ctx_set_aggregate_check(ctx_, enable ? (sub_batch ? sub_batch : 1) : 0, seed32);
         if (rc != ZKV_OK) throw std::invalid_argument("zkv_ctx_set_aggregate_check failed with ZKV error " + std::to_string(rc));

@@ -225,10 +225,12 @@ class RiscZeroRouter:
         _lib.check(self._L.zkv_ctx_reserve(self._h, n), 'zkv_ctx_reserve')
 
     def set_aggregate_check(self, enable=True, seed=None, sub_batch=None):
-        """Opt-in aggregate check on the built-in routes (include/zkv.h); the keyed routes keep the per-proof path."""
+        """Opt-in aggregate check (include/zkv.h) on the built-in routes and, under the key sets' rules, on the keyed routes (a call with at
+        least ZKV_AGG_MIN seals on them, the automatic mapping, keys with alpha and beta finite); statuses stay the per-proof ones."""
         _set_aggregate_check(self._L, self._h, enable, seed, sub_batch)
 
     def aggregate_counters(self):
+        """(sub-batches checked in aggregate, sub-batches that failed), summed over the built-in and the keyed group."""
         return _aggregate_counters(self._L, self._h)
 
     def synchronize(self):

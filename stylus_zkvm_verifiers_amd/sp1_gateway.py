@@ -185,11 +185,13 @@ class Sp1Gateway:
         _lib.check(self._L.zkv_ctx_reserve(self._h, n), 'zkv_ctx_reserve')
 
     def set_aggregate_check(self, enable=True, seed=None, sub_batch=None):
-        """Opt-in aggregate check on every route (include/zkv.h), each route with its own secret; statuses stay the per-proof ones."""
+        """Opt-in aggregate check on every route (include/zkv.h), each route with its own secret; statuses stay the per-proof ones.  The
+        routes with caller keys take it together, under the key sets' rules (a call with at least ZKV_AGG_MIN proofs on them, the automatic
+        mapping, keys with alpha and beta finite), with one secret of their own."""
         _set_aggregate_check(self._L, self._h, enable, seed, sub_batch)
 
     def aggregate_counters(self):
-        """(sub-batches checked in aggregate, sub-batches that failed), summed over the routes."""
+        """(sub-batches checked in aggregate, sub-batches that failed), summed over the routes, the group of keyed routes included."""
         return _aggregate_counters(self._L, self._h)
 
     def synchronize(self):

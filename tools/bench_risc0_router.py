@@ -1,6 +1,7 @@
 """Throughput of the RISC Zero verifier router (include/zkv_risc0_router.h).
 
     python tools/bench_risc0_router.py [--cases one,four] [--log2n 16] [--steps 3] [--out FILE]
+    python tools/bench_risc0_router.py --aggregate [--log2n-aggregate 18] [--steps 3] [--out FILE]
 
 One JSON line per case (appended to --out, default profiles/risc0_router_bench.jsonl); device-resident batches (torch tensors), best of
 --steps timed calls after a warm-up call, every status checked.
@@ -10,6 +11,11 @@ One JSON line per case (appended to --out, default profiles/risc0_router_bench.j
          (i) zkv_groth16_set_verify_batch_dev on the same proofs with host-prepared signals and key indices -- the nearest existing
              path; it does no selector or digest work -- and
          (ii) four one-route routers on the pre-sorted quarters, summed
+  --aggregate   the aggregate check on the keyed group (default --out profiles/keyed_group_aggregate_bench.jsonl):
+         four keyed routes, 2^log2n-aggregate shuffled seals, check off then on (automatic size) in one process, all seals valid and
+         with one seal in 64 damaged (four fifths refused before the pairing, a fifth at it); beside it the same keys and proofs through
+         zkv_groth16_set_verify_batch_dev off and on, whose ratio is the yardstick.  Damaged batches are a loss at 2^18, as on sets
+         (DESIGN.md section 11a): the second pass costs a kernel latency per stage that this size cannot hide.
 Seals: one proof per key re-randomised into 4,096 distinct ones (synth.make_batch / make_groth16_batch), tiled.  Not bench.py.
 """
 import argparse
@@ -75,8 +81,9 @@ class RouterCall:
         return int((self.st.cpu().numpy() == 0).sum())
 
 
-def trapdoor_pool(seed):
-    """(key words, control root, control id, selector, POOL x 260 seals, image id, journal digest, the five signals) of a fresh trapdoor key."""
+def trapdoor_pool(seed, mutate_every=1 << 30):
+    """(key, POOL x 260 seals, image id, journal digest, the five signals) of a fresh trapdoor key; every mutate_every-th seal has C off the
+    curve or B outside the subgroup."""
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import risc0_router_model as rm
     key = rm.Key(seed)
@@ -84,7 +91,7 @@ def trapdoor_pool(seed):
     iid = bytes(rng.randrange(256) for _ in range(32)); jd = bytes(rng.randrange(256) for _ in range(32))
     sig = key.route.verifier.signals(m.receipt_claim_ok_digest(iid, jd))
     base = key.prove(iid, jd)[4:]
-    p, _, _, _ = synth.make_groth16_batch(key.words, 'risc0', base, sig, POOL, seed=seed, mutate_every=1 << 30)
+    p, _, _, _ = synth.make_groth16_batch(key.words, 'risc0', base, sig, POOL, seed=seed, mutate_every=mutate_every, classes=('c_off_curve', 'b_out_of_subgroup'))
     seals = np.concatenate([np.tile(np.frombuffer(key.selector, np.uint8), (POOL, 1)), p], axis=1)
     return key, seals, np.frombuffer(iid, np.uint8), np.frombuffer(jd, np.uint8), np.frombuffer(b''.join(m.be32(s) for s in sig), np.uint8)
 
@@ -168,15 +175,63 @@ def case_four(a):
                 router_stage_ms=stage, route_counts=counts, all_accepted=ok)
 
 
+def case_aggregate(a, damaged):
+    import torch
+    n = 1 << a.log2n_aggregate
+    per = n // 4
+    pools = [trapdoor_pool(0x17D10 + k, 64 if damaged else 1 << 30) for k in range(4)]
+    S = np.concatenate([np.tile(p[1], (per // POOL, 1)) for p in pools])
+    I = np.concatenate([np.tile(p[2], (per, 1)) for p in pools])
+    J = np.concatenate([np.tile(p[3], (per, 1)) for p in pools])
+    G = np.concatenate([np.tile(p[4], (per, 1)) for p in pools])
+    K = np.repeat(np.arange(4, dtype=np.uint32), per)
+    bad = n // 64 if damaged else 0
+    if damaged:                                                   # a fifth of the damaged seals fail at the pairing instead: a valid seal, other inputs
+        at = np.arange(63, n, 64)[::5]
+        S[at] = S[at - 1]
+        J[at, 31] ^= 1
+        G[at, 3 * 32 + 31] ^= 1                                   # (the key set takes signals: any other claim digest half)
+    perm = np.random.default_rng(0x17D2).permutation(n)
+    call = RouterCall(zkv.RiscZeroRouter(keyed=[p[0].triple() for p in pools]), S[perm], I[perm], J[perm])
+    t_off = timed(call, a.steps)
+    acc_off, stage_off = call.accepted(), [round(x, 3) for x in call.rt.last_stage_ms()]
+    call.rt.set_aggregate_check(True)
+    t_on = timed(call, a.steps)
+    acc_on, stage_on = call.accepted(), [round(x, 3) for x in call.rt.last_stage_ms()]
+    counters = [int(x) for x in call.rt.aggregate_counters()]
+    call.rt.close()
+    gs = zkv.Groth16VerifierSet([(p[0].words, 6, zkv.errors.VM_RISC0) for p in pools])
+    d = [up(K[perm]), up(S[perm][:, 4:]), up(G[perm])]
+    ver = status_buffer(n)
+    s = torch.cuda.current_stream().cuda_stream
+    gs.reserve(n)
+    run = lambda: gs.verify_batch_dev(n, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), ver.data_ptr(), s)
+    g_off = timed(run, a.steps)
+    gacc_off, gstage_off = int((ver.cpu().numpy() == 1).sum()), [round(x, 3) for x in gs.last_stage_ms()]
+    gs.set_aggregate_check(True)
+    g_on = timed(run, a.steps)
+    gacc_on, gstage_on = int((ver.cpu().numpy() == 1).sum()), [round(x, 3) for x in gs.last_stage_ms()]
+    gs.close()
+    ratio, gratio = min(t_on) / min(t_off), min(g_on) / min(g_off)
+    return dict(case='aggregate_four_keyed_routes', front_end='risc0_router', n=n, damaged_one_in=64 if damaged else 0, off_ms=min(t_off), on_ms=min(t_on),
+                ratio=round(ratio, 4), key_set_off_ms=min(g_off), key_set_on_ms=min(g_on), key_set_ratio=round(gratio, 4), gap=round(ratio / gratio, 4),
+                off_all_ms=t_off, on_all_ms=t_on, key_set_off_all_ms=g_off, key_set_on_all_ms=g_on, stage_off_ms=stage_off, stage_on_ms=stage_on,
+                key_set_stage_off_ms=gstage_off, key_set_stage_on_ms=gstage_on, aggregate_counters=counters,
+                all_accepted=acc_off == acc_on == gacc_off == gacc_on == n - bad and counters[0] > 0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--cases', default='one,four')
     ap.add_argument('--log2n', type=int, default=16)
     ap.add_argument('--steps', type=int, default=3)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'risc0_router_bench.jsonl'))
+    ap.add_argument('--aggregate', action='store_true')
+    ap.add_argument('--log2n-aggregate', type=int, default=18)
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, 'profiles', 'keyed_group_aggregate_bench.jsonl' if a.aggregate else 'risc0_router_bench.jsonl')
     fns = dict(one=case_one, four=case_four)
-    rows = [fns[c](a) for c in a.cases.split(',')]
+    rows = [case_aggregate(a, False), case_aggregate(a, True)] if a.aggregate else [fns[c](a) for c in a.cases.split(',')]
     with open(a.out, 'a') as f:
         for r in rows:
             print(json.dumps(r), flush=True)

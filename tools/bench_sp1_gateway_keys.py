@@ -1,6 +1,7 @@
 """Throughput of the SP1 gateway's Groth16 routes with caller-supplied keys (include/zkv_sp1_gateway_keys.h).
 
     python tools/bench_sp1_gateway_keys.py [--cases one,four,guard] [--log2n 18] [--log2n-guard 20] [--steps 3] [--keyed 1] [--out FILE]
+    python tools/bench_sp1_gateway_keys.py --aggregate [--log2n 18] [--steps 3] [--out FILE]
 
 One JSON line per case (appended to --out, default profiles/sp1_gateway_keys_bench.jsonl); device-resident batches (torch tensors), best of
 --steps timed calls after a warm-up call, every status checked.
@@ -11,6 +12,11 @@ One JSON line per case (appended to --out, default profiles/sp1_gateway_keys_ben
   guard  2^log2n-guard proofs, all for the built-in route, on a gateway that has the built-in route and (--keyed 1) two keyed routes none
          of whose proofs appear; --keyed 0 builds the plain gateway (the only one a library without this header has; set ZKV_LIB_PATH to
          measure another build of the library)
+  --aggregate   the aggregate check on the keyed group (default --out profiles/keyed_group_aggregate_bench.jsonl):
+         four keyed routes, 2^log2n shuffled proofs, check off then on (automatic size) in one process, all proofs valid and with one
+         proof in 64 damaged (four fifths refused before the pairing, a fifth at it); beside it the same keys and proofs through
+         zkv_groth16_set_verify_batch_dev off and on, whose ratio is the yardstick.  Damaged batches are a loss at 2^18, as on sets
+         (DESIGN.md section 11a): the second pass costs a kernel latency per stage that this size cannot hide.
 Proofs: one proof per key re-randomised into 4,096 distinct ones (synth.make_batch / make_groth16_batch), tiled.  Not bench.py.
 """
 import argparse
@@ -41,8 +47,9 @@ def real_pool():
     return seals, np.frombuffer(H(g['vkey']), np.uint8), np.frombuffer(H(g['public_values']), np.uint8)
 
 
-def trapdoor_pool(seed, pv_len):
-    """(key words, verifier hash, POOL x 260 proofs, program vkey, public values) of a fresh trapdoor key."""
+def trapdoor_pool(seed, pv_len, mutate_every=1 << 30):
+    """(key words, verifier hash, POOL x 260 proofs, program vkey, public values) of a fresh trapdoor key; every mutate_every-th proof
+    has C off the curve or B outside the subgroup."""
     rng = random.Random(seed)
     vk, td = m.trapdoor_vk(rng, 3)
     vkey = int(rng.randrange(m.R)).to_bytes(32, 'big')
@@ -50,7 +57,7 @@ def trapdoor_pool(seed, pv_len):
     sig = [int.from_bytes(vkey, 'big'), m.sp1_hash_public_values(pv)]
     words = m.vk_to_words(vk)
     base = m.proof_to_words(*m.trapdoor_prove(rng, td, sig, 'sp1'))
-    p, _, _, _ = synth.make_groth16_batch(words, 'sp1', base, sig, POOL, seed=seed, mutate_every=1 << 30)
+    p, _, _, _ = synth.make_groth16_batch(words, 'sp1', base, sig, POOL, seed=seed, mutate_every=mutate_every, classes=('c_off_curve', 'b_out_of_subgroup'))
     vh = hashlib.sha256(b'bench keyed route %d' % seed).digest()
     seals = np.concatenate([np.tile(np.frombuffer(vh[:4], np.uint8), (POOL, 1)), p], axis=1)
     return words, vh, seals, np.frombuffer(vkey, np.uint8), np.frombuffer(pv, np.uint8)
@@ -144,6 +151,53 @@ def case_guard(a):
     return row
 
 
+def case_aggregate(a, damaged):
+    import torch
+    n = 1 << a.log2n
+    per = n // 4
+    pools = [trapdoor_pool(0x12D10 + k, 96, 64 if damaged else 1 << 30) for k in range(4)]
+    S = np.concatenate([np.tile(p[2], (per // POOL, 1)) for p in pools])
+    V = np.concatenate([np.tile(p[3], (per, 1)) for p in pools])
+    W = np.concatenate([np.tile(p[4], (per, 1)) for p in pools])
+    K = np.repeat(np.arange(4, dtype=np.uint32), per)
+    sig = [np.frombuffer(bytes(p[3]) + m.be32(m.sp1_hash_public_values(bytes(p[4]))), np.uint8) for p in pools]
+    G = np.concatenate([np.tile(g, (per, 1)) for g in sig])
+    bad = n // 64 if damaged else 0
+    if damaged:                                                   # a fifth of the damaged proofs fail at the pairing instead: a valid proof, other public values
+        at = np.arange(63, n, 64)[::5]
+        S[at] = S[at - 1]
+        W[at, 95] ^= 1
+        G[at, 63] ^= 1                                            # (the key set takes signals: any other hash)
+    perm = np.random.default_rng(0x12D2).permutation(n)
+    call = Call(zkv.Sp1Gateway(False, groth16_keys=[(p[0], p[1]) for p in pools]), S[perm], V[perm], W[perm])
+    t_off = timed(call, a.steps)
+    acc_off, stage_off = call.accepted(), [round(x, 3) for x in call.gw.last_stage_ms()]
+    call.gw.set_aggregate_check(True)
+    t_on = timed(call, a.steps)
+    acc_on, stage_on = call.accepted(), [round(x, 3) for x in call.gw.last_stage_ms()]
+    counters = [int(x) for x in call.gw.aggregate_counters()]
+    call.gw.close()
+    gs = zkv.Groth16VerifierSet([(p[0], 3, zkv.errors.VM_SP1) for p in pools])
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x).reshape(-1)).to(torch.device('cuda', 0))
+    d = [up(K[perm]), up(S[perm][:, 4:]), up(G[perm])]
+    ver = torch.full((n,), 255, dtype=torch.uint8, device=torch.device('cuda', 0))
+    s = torch.cuda.current_stream().cuda_stream
+    gs.reserve(n)
+    run = lambda: gs.verify_batch_dev(n, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), ver.data_ptr(), s)
+    g_off = timed(run, a.steps)
+    gacc_off, gstage_off = int((ver.cpu().numpy() == 1).sum()), [round(x, 3) for x in gs.last_stage_ms()]
+    gs.set_aggregate_check(True)
+    g_on = timed(run, a.steps)
+    gacc_on, gstage_on = int((ver.cpu().numpy() == 1).sum()), [round(x, 3) for x in gs.last_stage_ms()]
+    gs.close()
+    ratio, gratio = min(t_on) / min(t_off), min(g_on) / min(g_off)
+    return dict(case='aggregate_four_keyed_routes', front_end='sp1_gateway', n=n, damaged_one_in=64 if damaged else 0, off_ms=min(t_off), on_ms=min(t_on),
+                ratio=round(ratio, 4), key_set_off_ms=min(g_off), key_set_on_ms=min(g_on), key_set_ratio=round(gratio, 4), gap=round(ratio / gratio, 4),
+                off_all_ms=t_off, on_all_ms=t_on, key_set_off_all_ms=g_off, key_set_on_all_ms=g_on, stage_off_ms=stage_off, stage_on_ms=stage_on,
+                key_set_stage_off_ms=gstage_off, key_set_stage_on_ms=gstage_on, aggregate_counters=counters,
+                all_accepted=acc_off == acc_on == gacc_off == gacc_on == n - bad and counters[0] > 0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--cases', default='one,four,guard')
@@ -151,10 +205,12 @@ def main():
     ap.add_argument('--log2n-guard', type=int, default=20)
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--keyed', type=int, default=1)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sp1_gateway_keys_bench.jsonl'))
+    ap.add_argument('--aggregate', action='store_true')
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, 'profiles', 'keyed_group_aggregate_bench.jsonl' if a.aggregate else 'sp1_gateway_keys_bench.jsonl')
     fns = dict(one=case_one, four=case_four, guard=case_guard)
-    rows = [fns[c](a) for c in a.cases.split(',')]
+    rows = [case_aggregate(a, False), case_aggregate(a, True)] if a.aggregate else [fns[c](a) for c in a.cases.split(',')]
     with open(a.out, 'a') as f:
         for r in rows:
             print(json.dumps(r), flush=True)
