@@ -11,6 +11,7 @@ from .sp1 import Sp1Verifier, Sp1PlonkVerifier
 from .bn254 import Bn254Precompiles
 from .groth16 import Groth16Verifier
 from .groth16_set import Groth16VerifierSet
+from .groth16_set_wire import Groth16DeployedSet
 from .mixed import MixedVerifier
 from .sp1_gateway import Sp1Gateway
 from .risc0_router import RiscZeroRouter
@@ -20,7 +21,7 @@ from .plonk_set import PlonkVerifierSet
 from . import wire
 from .sharded import shard, shard_count, shard_devices, shard_peer_access
 
-__all__ = ['host_register', 'host_unregister', 'RiscZeroVerifier', 'RiscZeroVerifierSet', 'RiscZeroSetInclusionVerifier', 'Sp1Verifier', 'Sp1PlonkVerifier', 'Bn254Precompiles', 'Groth16Verifier', 'Groth16VerifierSet', 'MixedVerifier', 'Sp1Gateway', 'RiscZeroRouter', 'RiscZeroSetRouter', 'PlonkVerifier', 'PlonkVerifierSet', 'VerifierError', 'errors', 'wire', 'device_count', 'shard', 'shard_count', 'shard_devices', 'shard_peer_access']
+__all__ = ['host_register', 'host_unregister', 'RiscZeroVerifier', 'RiscZeroVerifierSet', 'RiscZeroSetInclusionVerifier', 'Sp1Verifier', 'Sp1PlonkVerifier', 'Bn254Precompiles', 'Groth16Verifier', 'Groth16VerifierSet', 'Groth16DeployedSet', 'MixedVerifier', 'Sp1Gateway', 'RiscZeroRouter', 'RiscZeroSetRouter', 'PlonkVerifier', 'PlonkVerifierSet', 'VerifierError', 'errors', 'wire', 'device_count', 'shard', 'shard_count', 'shard_devices', 'shard_peer_access']
 
 
 def device_count():

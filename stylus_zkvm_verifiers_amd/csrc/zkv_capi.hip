@@ -2,6 +2,7 @@
 // Host code here only marshals bytes, runs the once-per-context SHA-256 chain (initialize) and enqueues
 // kernels; every field/curve/pairing operation runs in the HIP kernels.  No CPU fallback exists.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <condition_variable>
 #include <functional>
 #include <memory>
@@ -18,6 +19,7 @@
 
 #include "../../include/zkv.h"
 #include "../../include/zkv_groth16_set.h"
+#include "../../include/zkv_groth16_set_wire.h"
 #include "../../include/zkv_sp1_gateway.h"
 #include "../../include/zkv_sp1_gateway_wire.h"
 #include "../../include/zkv_sp1_gateway_keys.h"
@@ -46,6 +48,7 @@
 #include "zkv_wire_rzrouter.h"
 #include "zkv_rzrouter_set.h"
 #include "zkv_wire_rzset.h"
+#include "zkv_wire_gset.h"
 #include <sys/random.h>
 
 using namespace zkv;
@@ -128,6 +131,13 @@ struct SetInclMem : SetGroupMem { DevBuf<uint8_t> h_a, h_b, h_paths, h_seals, h_
 struct HostBatchMem { DevBuf<uint8_t> seals, in_a, in_b, pv; DevBuf<uint64_t> off, pv_off; };
 // Host-buffer calls on a key set: the caller's keys, proofs and signal / public-input rows, the verdicts; the vk_x call's points.
 struct KeySetHostMem { DevBuf<uint32_t> key; DevBuf<uint8_t> proofs, rows, verdicts, vk_x; };
+// eth_call batches on a deployed key set (run_gset_wire): the sorted address table; the rows the decoder writes -- the set's ordinary
+// inputs (key, proofs, signal rows), the key each address resolved to, decode verdict and in-field byte --, the verdicts of the pipeline
+// and the four totals; h_*: the host call's staging.
+struct GsetWireMem {
+    DevBuf<GswEntry> tab; DevBuf<uint32_t> key, rkey; DevBuf<uint8_t> proofs, rows, verdict, ge_r, verified; DevBuf<unsigned long long> cnt;
+    DevBuf<uint8_t> h_to, h_cd, h_st; DevBuf<uint64_t> h_cdoff;
+};
 // Grows each buffer to the byte count behind it, in the order given; the first failure ends it.
 static int grow_all() { return ZKV_OK; }
 template <class T, class... Rest> static int grow_all(DevBuf<T>& buf, size_t bytes, Rest&&... rest) {
@@ -162,7 +172,7 @@ struct CtxDevice : ChunkMem, AggMem {
     DevBuf<> d_blob, d_pv, d_cd[2], d_st_all, d_rv_all;
     // the families' staging: host-buffer batches, key-set host calls; demultiplexing, routing, key-set and set-inclusion buffers
     HostBatchMem m_host; KeySetHostMem m_kshost;
-    MixedMem m_mixed; GatewayMem m_gw; RouterMem m_rz; KeySetMem m_ks; SetInclMem m_si;
+    MixedMem m_mixed; GatewayMem m_gw; RouterMem m_rz; KeySetMem m_ks; SetInclMem m_si; GsetWireMem m_gsw;
     DevEvent ev_fork, ev_join;                                 // small chunks: the G2 subgroup check runs beside the MSM (stream `side`)
     DevEvent ev_copied[2], ev_decoded[2];                      // wire layer: H2D of calldata chunk k+1 overlaps the kernels of chunk k
     DevEvent ev[6], ev_wire[2];
@@ -195,6 +205,10 @@ struct zkv_ctx : CtxDevice {
     // aggregate check on a set: which keys can take it (d_agg_tab then holds one AggTables per key), and per call the two-region layout
     // (zkv_gset_layout.h: gset_agg_choose) and every aggregate chunk's pseudo-proof slots (run_gset)
     std::vector<uint8_t> gs_agg_ok; std::vector<uint32_t> gs_agg_n, gs_rest, gs_nsb, gs_amap; std::vector<uint64_t> gs_map, gs_pst;
+    // A set of deployed contracts (zkv_groth16_set_wire.h; gsw_tab empty: not one): the address table, ascending, and per key the contract
+    // form; the two gnark error selectors, ProofInvalid() and PublicInputNotInField()
+    std::vector<GswEntry> gsw_tab; std::vector<uint8_t> gsw_form;
+    uint8_t gsw_err[2][4] = {{0}};
     float gt_build_ms = 0;
     size_t last_chunk_n = 0;                                 // proofs of the most recent chunk (zkv_diag_prep.h reads their rows back)
     // ZKV_VM_SP1_PLONK and ZKV_VM_PLONK (zkv_plonk_keys.h): parsed verifying key, the SRS's two G2 points (reference word order) and
@@ -3612,6 +3626,156 @@ ZKV_EXPORT int zkv_groth16_set_vk_x_batch(zkv_ctx* c, size_t n, const uint32_t* 
     HIP_TRY(hipMemcpyAsync(out, hb.vk_x, 64 * n, hipMemcpyDeviceToHost, c->stream));
     if ((rc = mark_done(c, c->stream)) != ZKV_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return ZKV_OK;
+}
+
+// ------------------------------------------------------------------ Groth16 key sets of deployed contracts: eth_call batches
+// (zkv_groth16_set_wire.h; parity unpinned).  k_gset_wire_decode turns every request into a row of the set's
+// ordinary inputs, run_gset runs on those rows as it runs on a caller's, and k_gset_wire_return merges its verdicts with the decoder's.
+static bool gsw_signature(int form, size_t n_sig, char out[96]) {
+    if ((form != ZKV_G16_FORM_SNARKJS && form != ZKV_G16_FORM_GNARK) || n_sig < 1 || n_sig >= ZKV_GROTH16_MAX_IC) return false;
+    snprintf(out, 96, form == ZKV_G16_FORM_SNARKJS ? "verifyProof(uint256[2],uint256[2][2],uint256[2],uint256[%zu])" : "verifyProof(uint256[8],uint256[%zu])", n_sig);
+    return true;
+}
+ZKV_EXPORT int zkv_groth16_set_call_selector(int form, size_t n_signals, uint8_t out[4]) {
+    char sig[96];
+    if (!out || !gsw_signature(form, n_signals, sig)) return ZKV_ERR_INVALID_ARG;
+    host::fn_selector(sig, out);
+    return ZKV_OK;
+}
+static bool is_deployed_set(const zkv_ctx* c) { return c && c->vm == ZKV_VM_GROTH16_SET && !c->gsw_tab.empty(); }
+ZKV_EXPORT zkv_ctx* zkv_groth16_set_create_deployed(size_t n_keys, const uint8_t* const* vk_words, const size_t* n_ic, const int* vm_type,
+                                                    const uint8_t* addresses, const uint8_t* form, int device) {
+    if (!addresses || !form) return nullptr;
+    zkv_ctx* c = zkv_groth16_set_create(n_keys, vk_words, n_ic, vm_type, device);
+    if (!c) return nullptr;
+    try {
+        c->gsw_tab.resize(n_keys);
+        c->gsw_form.assign(form, form + n_keys);
+    } catch (const std::bad_alloc&) { delete c; return nullptr; }
+    bool ok = true;
+    for (size_t k = 0; k < n_keys && ok; k++) {
+        GswEntry& e = c->gsw_tab[k];
+        for (int j = 0; j < 5; j++) e.addr[j] = be32_of(addresses + 20 * k + 4 * j);
+        e.key = (uint32_t)k; e.sel_be = 0; e.n_sig = GSW_NONE;           // (n_ic = 1: no method)
+        ok = form[k] == ZKV_G16_FORM_SNARKJS || form[k] == ZKV_G16_FORM_GNARK;
+        uint8_t sel[4];
+        if (ok && n_ic[k] > 1) {
+            (void)zkv_groth16_set_call_selector(form[k], n_ic[k] - 1, sel);
+            e.sel_be = be32_of(sel); e.n_sig = (uint32_t)(n_ic[k] - 1);
+        }
+    }
+    std::sort(c->gsw_tab.begin(), c->gsw_tab.end(), [](const GswEntry& a, const GswEntry& b) { return gsw_addr_cmp(a.addr, b.addr) < 0; });
+    for (size_t k = 1; k < n_keys && ok; k++) ok = gsw_addr_cmp(c->gsw_tab[k - 1].addr, c->gsw_tab[k].addr) != 0;
+    if (!ok) { delete c; return nullptr; }
+    host::fn_selector("ProofInvalid()", c->gsw_err[0]);
+    host::fn_selector("PublicInputNotInField()", c->gsw_err[1]);
+    return c;
+}
+ZKV_EXPORT int zkv_groth16_set_eth_call_returndata(const zkv_ctx* c, uint32_t key, uint8_t status, uint8_t out[ZKV_RETURNDATA_STRIDE], uint32_t* out_len,
+                                                   uint8_t* reverted) {
+    if (!is_deployed_set(c)) return ZKV_ERR_WRONG_CTX;
+    if (!out || !out_len || !reverted) return ZKV_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (status == ZKV_STATUS_NO_CONTRACT) { *reverted = 0; return ZKV_OK; }             // an address without code: success, no data
+    if (status == ZKV_STATUS_BAD_CALLDATA) { *reverted = 1; return ZKV_OK; }            // the contract's dispatcher reverts with no data
+    if ((status != ZKV_STATUS_OK && status != ZKV_STATUS_VERIFICATION_FAILED && status != ZKV_STATUS_INPUT_NOT_IN_FIELD) || key >= c->gsw_form.size())
+        return ZKV_ERR_INVALID_ARG;
+    if (c->gsw_form[key] == ZKV_G16_FORM_SNARKJS) {                                     // returns (bool), whatever went wrong
+        *reverted = 0; *out_len = 32;
+        memset(out, 0, 32);
+        out[31] = status == ZKV_STATUS_OK ? 1 : 0;
+        return ZKV_OK;
+    }
+    *reverted = status == ZKV_STATUS_OK ? 0 : 1;
+    if (status != ZKV_STATUS_OK) { memcpy(out, c->gsw_err[status == ZKV_STATUS_INPUT_NOT_IN_FIELD ? 1 : 0], 4); *out_len = 4; }
+    return ZKV_OK;
+}
+// Addresses, calldata and its n + 1 offsets on the device (c->mu held).  The decode is enqueued in front of the partition, so the call
+// synchronises where run_gset does; d_key: the resolved keys go there (the host call passes its own row).
+static int run_gset_wire(zkv_ctx* c, size_t n, const uint8_t* d_to, const uint8_t* d_cd, const uint64_t* d_off, uint64_t cd_bytes, uint8_t* d_status,
+                         uint32_t* d_key, hipStream_t s) {
+    size_t cap = 0;
+    int rc = groth16_ready(c, n, &cap);
+    if (rc != ZKV_OK) return rc;
+    GsetWireMem& gm = c->m_gsw;
+    const size_t stride = (size_t)32 * (c->g_n_ic - 1);
+    if ((rc = grow_all(gm.key, 4 * n, gm.rkey, d_key ? 0 : 4 * n, gm.proofs, 256 * n, gm.rows, stride * n + 8, gm.verdict, n, gm.ge_r, n, gm.verified, n,
+                       gm.cnt, 4 * sizeof(unsigned long long))) != ZKV_OK) return rc;
+    if (!gm.tab) {                                               // once per device set-up: the table is the context's own, sorted at creation
+        if ((rc = gm.tab.alloc(sizeof(GswEntry) * c->gsw_tab.size())) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpy(gm.tab, c->gsw_tab.data(), sizeof(GswEntry) * c->gsw_tab.size(), hipMemcpyHostToDevice));
+    }
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    HIP_TRY(hipMemsetAsync(gm.cnt, 0, 4 * sizeof(unsigned long long), s));
+    GswArgs w;
+    memset(&w, 0, sizeof w);
+    w.n = n; w.to = d_to; w.cd = d_cd; w.off = d_off; w.cd_bytes = cd_bytes;
+    w.tab = gm.tab; w.n_tab = (uint32_t)c->gsw_tab.size();
+    w.key = gm.key; w.rkey = d_key ? d_key : (uint32_t*)gm.rkey; w.proofs = gm.proofs; w.rows = gm.rows; w.sig_stride = (uint32_t)stride;
+    w.verdict = gm.verdict; w.ge_r = gm.ge_r;
+    (void)hipEventRecord(c->ev_wire[0], s);
+    launch_gset_wire_decode(w, s);
+    (void)hipEventRecord(c->ev_wire[1], s);
+    c->wire_timed = true;
+    HIP_TRY(hipGetLastError());
+    if ((rc = run_gset(c, n, gm.key, gm.proofs, gm.rows, gm.verified, s)) != ZKV_OK) return rc;
+    launch_gset_wire_return(n, gm.verdict, gm.ge_r, gm.verified, d_status, gm.cnt, s);
+    HIP_TRY(hipGetLastError());
+    return mark_done(c, s);
+}
+ZKV_EXPORT int zkv_groth16_set_eth_call_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_to, const uint8_t* d_calldata, const uint64_t* d_calldata_off,
+                                                  uint64_t calldata_bytes, uint8_t* d_status, uint32_t* d_key, void* stream) {
+    if (!is_deployed_set(c)) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_to || !d_calldata || !d_calldata_off || !d_status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_device_init(c);
+    if (rc != ZKV_OK) return rc;
+    return run_gset_wire(c, n, d_to, d_calldata, d_calldata_off, calldata_bytes, d_status, d_key, stream ? (hipStream_t)stream : c->stream);
+}
+ZKV_EXPORT int zkv_groth16_set_eth_call_batch(zkv_ctx* c, size_t n, const uint8_t* to, const uint8_t* blob, const uint64_t* off, uint8_t* reverted,
+                                              uint8_t* returndata, uint32_t* returndata_len, uint8_t* status) {
+    if (!is_deployed_set(c)) return ZKV_ERR_WRONG_CTX;
+    if (n && (!to || !blob || !off || !reverted || !returndata || !returndata_len)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u) return ZKV_ERR_INVALID_ARG;
+    std::vector<uint8_t> st(n);
+    std::vector<uint32_t> key(n);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        int rc = ctx_device_init(c);
+        if (rc != ZKV_OK) return rc;
+        const uint64_t bytes = off[n];                           // the blob; a request may still run backwards or past it
+        GsetWireMem& gm = c->m_gsw;
+        if ((rc = grow_all(gm.h_to, 20 * n, gm.h_cd, (size_t)bytes + 8, gm.h_cdoff, 8 * (n + 1), gm.h_st, n, gm.rkey, 4 * n)) != ZKV_OK) return rc;
+        hipStream_t s = c->stream;
+        if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(gm.h_to, to, 20 * n, hipMemcpyHostToDevice, s));
+        if (bytes) HIP_TRY(hipMemcpyAsync(gm.h_cd, blob, (size_t)bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(gm.h_cdoff, off, 8 * (n + 1), hipMemcpyHostToDevice, s));
+        if ((rc = run_gset_wire(c, n, gm.h_to, gm.h_cd, gm.h_cdoff, bytes, gm.h_st, gm.rkey, s)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(st.data(), gm.h_st, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(key.data(), gm.rkey, 4 * n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (size_t i = 0; i < n; i++) {
+        const int rc = zkv_groth16_set_eth_call_returndata(c, key[i], st[i], returndata + i * ZKV_RETURNDATA_STRIDE, &returndata_len[i], &reverted[i]);
+        if (rc != ZKV_OK) return rc;
+        if (status) status[i] = st[i];
+    }
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_groth16_set_last_call_counts(zkv_ctx* c, uint64_t out[4]) {
+    if (!is_deployed_set(c)) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    memset(out, 0, 4 * sizeof(uint64_t));
+    if (!c->dev_ready || !c->m_gsw.cnt || !c->has_done) return ZKV_OK;       // no eth_call batch has run
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(c->ev_done));
+    HIP_TRY(hipMemcpy(out, c->m_gsw.cnt, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return ZKV_OK;
 }
 

@@ -232,6 +232,13 @@ void launch_gset_return(size_t n, const uint32_t* pos, const uint8_t* status, ui
 // Miller loops with the key of each wavefront's first slot (k_gset_pair.hip): lanes 2 / 16 / 64 / 128 as zkv_ctx_set_lanes_per_proof
 void launch_gset_miller(int lanes, size_t m, const uint32_t* skey, const GsetKey* keys, const Workspace& ws, uint8_t* status, hipStream_t s);
 int read_gset_wait_faults(unsigned long long* out);     // k_gset_miller_w64d's counterpart of read_wait_faults
+// eth_call calldata of a set of deployed contracts (k_gset_wire.hip; zkv_wire_gset.h has the decode rule and GswArgs): one request per
+// lane into the set's ordinary inputs, then, behind the set's pipeline, one lane per request for the status byte and the four totals
+// (counts: placed, no contract, bad calldata, signal not in field -- added to, so zeroed by the host).
+struct GswArgs;
+void launch_gset_wire_decode(const GswArgs& a, hipStream_t s);
+void launch_gset_wire_return(size_t n, const uint8_t* verdict, const uint8_t* ge_r, const uint8_t* verified, uint8_t* status,
+                             unsigned long long* counts, hipStream_t s);
 // SP1 gateway, keyed Groth16 routes (k_gateway_keys.hip; include/zkv_sp1_gateway_keys.h): PREP of slots [slot0, slot0 + m) of the keyed
 // group, the gateway's routes with caller keys as one key set.  Every per-slot table is the group's (index 0 = its first slot): the
 // demultiplexer's compact outputs -- caller index (GW_NONE: pad slot), 260-byte records, true lengths, program vkeys, (offset, length)

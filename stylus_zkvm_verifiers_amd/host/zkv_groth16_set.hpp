@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/zkv_groth16_set.h"
+#include "../../include/zkv_groth16_set_wire.h"
 
 namespace zkv {
 
@@ -60,8 +61,86 @@ public:
     }
     zkv_ctx* handle() const { return ctx_; }
 
-private:
+protected:
+    explicit Groth16VerifierSet(zkv_ctx* adopted) : ctx_(adopted) {}
     zkv_ctx* ctx_ = nullptr;
+};
+
+// A key set whose keys are deployed verifier contracts (include/zkv_groth16_set_wire.h; parity unpinned: the reference holds no generic
+// contract shell): Groth16VerifierSet plus eth_call batches of raw `verifyProof` calldata, each request addressed to a contract.
+struct Groth16Contract {
+    Groth16Key key;
+    uint8_t address[20];
+    int form;                     // ZKV_G16_FORM_SNARKJS / ZKV_G16_FORM_GNARK
+};
+
+struct EthCallResults {
+    std::vector<uint8_t> reverted, status;
+    std::vector<std::vector<uint8_t>> returndata;
+};
+
+class Groth16DeployedSet : public Groth16VerifierSet {
+public:
+    explicit Groth16DeployedSet(const std::vector<Groth16Contract>& contracts, int device = 0) : Groth16VerifierSet(create(contracts, device)) {}
+
+    // the 4-byte selector of a form's verifyProof with n_signals public signals
+    static std::vector<uint8_t> selector(int form, size_t n_signals) {
+        std::vector<uint8_t> out(4);
+        if (zkv_groth16_set_call_selector(form, n_signals, out.data()) != ZKV_OK) throw std::invalid_argument("Groth16DeployedSet::selector: form or signal count");
+        return out;
+    }
+    // canonical calldata of verifyProof: selector, the 256 proof bytes (the precompiles' word order), the 32-byte signals
+    static std::vector<uint8_t> encode_call(int form, const std::vector<uint8_t>& proof_words, const std::vector<uint8_t>& signals) {
+        if (proof_words.size() != 256 || signals.size() % 32) throw std::invalid_argument("Groth16DeployedSet::encode_call: a proof is 256 bytes and a signal 32");
+        std::vector<uint8_t> out = selector(form, signals.size() / 32);
+        out.insert(out.end(), proof_words.begin(), proof_words.end());
+        out.insert(out.end(), signals.begin(), signals.end());
+        return out;
+    }
+    // request i: calls[i] to the contract at to[20 i ..]
+    EthCallResults eth_call_batch(const std::vector<uint8_t>& to, const std::vector<std::vector<uint8_t>>& calls) const {
+        const size_t n = calls.size();
+        if (to.size() != 20 * n) throw std::invalid_argument("Groth16DeployedSet::eth_call_batch: one 20-byte address per request");
+        std::vector<uint64_t> off(n + 1, 0);
+        std::vector<uint8_t> blob;
+        for (size_t i = 0; i < n; i++) { blob.insert(blob.end(), calls[i].begin(), calls[i].end()); off[i + 1] = blob.size(); }
+        blob.push_back(0);
+        EthCallResults r;
+        r.reverted.assign(n ? n : 1, 0); r.status.assign(n ? n : 1, 0);
+        std::vector<uint8_t> data((n ? n : 1) * ZKV_RETURNDATA_STRIDE);
+        std::vector<uint32_t> len(n ? n : 1, 0);
+        const int rc = zkv_groth16_set_eth_call_batch(ctx_, n, to.data(), blob.data(), off.data(), r.reverted.data(), data.data(), len.data(), r.status.data());
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_groth16_set_eth_call_batch failed with ZKV error " + std::to_string(rc));
+        r.reverted.resize(n); r.status.resize(n);
+        for (size_t i = 0; i < n; i++) r.returndata.emplace_back(data.begin() + i * ZKV_RETURNDATA_STRIDE, data.begin() + i * ZKV_RETURNDATA_STRIDE + len[i]);
+        return r;
+    }
+    // every buffer in device memory, enqueued on `stream` (nullptr: the context's); d_key may be nullptr
+    void eth_call_batch_dev(size_t n, const uint8_t* d_to, const uint8_t* d_calldata, const uint64_t* d_calldata_off, uint64_t calldata_bytes, uint8_t* d_status,
+                            uint32_t* d_key = nullptr, void* stream = nullptr) const {
+        const int rc = zkv_groth16_set_eth_call_batch_dev(ctx_, n, d_to, d_calldata, d_calldata_off, calldata_bytes, d_status, d_key, stream);
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_groth16_set_eth_call_batch_dev failed with ZKV error " + std::to_string(rc));
+    }
+    // {placed, no contract, bad calldata, signal not in field} of the most recent eth_call batch
+    std::vector<uint64_t> last_call_counts() const {
+        uint64_t v[4] = {0, 0, 0, 0};
+        const int rc = zkv_groth16_set_last_call_counts(ctx_, v);
+        if (rc != ZKV_OK) throw std::runtime_error("zkv_groth16_set_last_call_counts failed with ZKV error " + std::to_string(rc));
+        return {v[0], v[1], v[2], v[3]};
+    }
+
+private:
+    static zkv_ctx* create(const std::vector<Groth16Contract>& contracts, int device) {
+        std::vector<const uint8_t*> w; std::vector<size_t> n; std::vector<int> vm; std::vector<uint8_t> addr, form;
+        for (const auto& c : contracts) {
+            if (c.key.words.size() != 448 + 64 * c.key.n_ic) throw std::invalid_argument("Groth16DeployedSet: key must be 448 + 64 n_ic bytes");
+            w.push_back(c.key.words.data()); n.push_back(c.key.n_ic); vm.push_back(c.key.vm_type);
+            addr.insert(addr.end(), c.address, c.address + 20); form.push_back((uint8_t)c.form);
+        }
+        zkv_ctx* ctx = zkv_groth16_set_create_deployed(contracts.size(), w.data(), n.data(), vm.data(), addr.data(), form.data(), device);
+        if (!ctx) throw std::invalid_argument("zkv_groth16_set_create_deployed rejected the contracts");
+        return ctx;
+    }
 };
 
 }  // namespace zkv
