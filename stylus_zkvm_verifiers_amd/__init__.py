@@ -18,10 +18,11 @@ from .risc0_router import RiscZeroRouter
 from .risc0_router_set import RiscZeroSetRouter
 from .plonk_keys import PlonkVerifier
 from .plonk_set import PlonkVerifierSet
+from .plonk_set_wire import PlonkDeployedSet
 from . import wire
 from .sharded import shard, shard_count, shard_devices, shard_peer_access
 
-__all__ = ['host_register', 'host_unregister', 'RiscZeroVerifier', 'RiscZeroVerifierSet', 'RiscZeroSetInclusionVerifier', 'Sp1Verifier', 'Sp1PlonkVerifier', 'Bn254Precompiles', 'Groth16Verifier', 'Groth16VerifierSet', 'Groth16DeployedSet', 'MixedVerifier', 'Sp1Gateway', 'RiscZeroRouter', 'RiscZeroSetRouter', 'PlonkVerifier', 'PlonkVerifierSet', 'VerifierError', 'errors', 'wire', 'device_count', 'shard', 'shard_count', 'shard_devices', 'shard_peer_access']
+__all__ = ['host_register', 'host_unregister', 'RiscZeroVerifier', 'RiscZeroVerifierSet', 'RiscZeroSetInclusionVerifier', 'Sp1Verifier', 'Sp1PlonkVerifier', 'Bn254Precompiles', 'Groth16Verifier', 'Groth16VerifierSet', 'Groth16DeployedSet', 'MixedVerifier', 'Sp1Gateway', 'RiscZeroRouter', 'RiscZeroSetRouter', 'PlonkVerifier', 'PlonkVerifierSet', 'PlonkDeployedSet', 'VerifierError', 'errors', 'wire', 'device_count', 'shard', 'shard_count', 'shard_devices', 'shard_peer_access']
 
 
 def device_count():

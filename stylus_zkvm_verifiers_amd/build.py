@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 BUILD = os.path.join(CSRC, 'build')
 LIB = os.path.join(HERE, 'libzkv_mi355x.so')
-UNITS = ['k_setup', 'k_gt', 'k_prep', 'k_msm', 'k_pair', 'k_wide', 'k_precompile', 'k_wire', 'k_mixed', 'k_diag', 'k_plonk', 'k_plonk_keys', 'k_plonk_set', 'k_pset_agg', 'k_agg', 'k_gset', 'k_gset_pair', 'k_gset_agg', 'k_gset_agg_pair', 'k_gset_wire', 'k_gateway', 'k_gateway_keys', 'k_risc0_router', 'k_setincl', 'k_rzrouter_set', 'k_wire_rzset', 'k_selftest', 'k_selftest_pair', 'zkv_capi']
+UNITS = ['k_setup', 'k_gt', 'k_prep', 'k_msm', 'k_pair', 'k_wide', 'k_precompile', 'k_wire', 'k_mixed', 'k_diag', 'k_plonk', 'k_plonk_keys', 'k_plonk_set', 'k_pset_agg', 'k_pset_wire', 'k_agg', 'k_gset', 'k_gset_pair', 'k_gset_agg', 'k_gset_agg_pair', 'k_gset_wire', 'k_gateway', 'k_gateway_keys', 'k_risc0_router', 'k_setincl', 'k_rzrouter_set', 'k_wire_rzset', 'k_selftest', 'k_selftest_pair', 'zkv_capi']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden', '-DZKV_FP_MUL_NOINLINE',
          '-Rpass-analysis=kernel-resource-usage']
 UNIT_FLAGS = {}          # per-unit extra flags (none at present)
@@ -31,7 +31,7 @@ def _hipcc():
 
 
 def _deps_mtime():
-    files = glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(HERE, '..', 'include', f) for f in ('zkv.h', 'zkv_groth16_set.h', 'zkv_groth16_set_wire.h', 'zkv_sp1_gateway.h', 'zkv_sp1_gateway_wire.h', 'zkv_sp1_gateway_keys.h', 'zkv_plonk_keys.h', 'zkv_plonk_set.h', 'zkv_plonk_set_agg.h', 'zkv_diag_primitive.h', 'zkv_diag_line_steps.h', 'zkv_diag_prep.h', 'zkv_diag_gt.h', 'zkv_risc0_set_inclusion.h', 'zkv_risc0_router.h', 'zkv_risc0_router_wire.h', 'zkv_risc0_router_set.h', 'zkv_risc0_router_set_wire.h')]
+    files = glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(HERE, '..', 'include', f) for f in ('zkv.h', 'zkv_groth16_set.h', 'zkv_groth16_set_wire.h', 'zkv_sp1_gateway.h', 'zkv_sp1_gateway_wire.h', 'zkv_sp1_gateway_keys.h', 'zkv_plonk_keys.h', 'zkv_plonk_set.h', 'zkv_plonk_set_agg.h', 'zkv_plonk_set_wire.h', 'zkv_diag_primitive.h', 'zkv_diag_line_steps.h', 'zkv_diag_prep.h', 'zkv_diag_gt.h', 'zkv_risc0_set_inclusion.h', 'zkv_risc0_router.h', 'zkv_risc0_router_wire.h', 'zkv_risc0_router_set.h', 'zkv_risc0_router_set_wire.h')]
     return max(os.path.getmtime(f) for f in files)
 
 

@@ -26,6 +26,7 @@
 #include "../../include/zkv_plonk_keys.h"
 #include "../../include/zkv_plonk_set.h"
 #include "../../include/zkv_plonk_set_agg.h"
+#include "../../include/zkv_plonk_set_wire.h"
 #include "../../include/zkv_diag_primitive.h"
 #include "../../include/zkv_diag_line_steps.h"
 #include "../../include/zkv_diag_prep.h"
@@ -49,6 +50,7 @@
 #include "zkv_rzrouter_set.h"
 #include "zkv_wire_rzset.h"
 #include "zkv_wire_gset.h"
+#include "zkv_wire_pset.h"
 #include <sys/random.h>
 
 using namespace zkv;
@@ -138,6 +140,13 @@ struct GsetWireMem {
     DevBuf<GswEntry> tab; DevBuf<uint32_t> key, rkey; DevBuf<uint8_t> proofs, rows, verdict, ge_r, verified; DevBuf<unsigned long long> cnt;
     DevBuf<uint8_t> h_to, h_cd, h_st; DevBuf<uint64_t> h_cdoff;
 };
+// eth_call batches on a deployed PLONK set (run_pset_wire): the sorted address table; the rows the decoder writes -- the set's ordinary
+// inputs (key, proofs, input rows), the key each address resolved to, decode verdict, reason, point count and point byte --, the verdicts
+// of the pipeline and the eight totals; h_*: the host call's staging.
+struct PsetWireMem {
+    DevBuf<PswEntry> tab; DevBuf<uint32_t> key, rkey; DevBuf<uint8_t> proofs, rows, verdict, reason, npt, ec, verified; DevBuf<unsigned long long> cnt;
+    DevBuf<uint8_t> h_to, h_cd, h_st, h_rs; DevBuf<uint64_t> h_cdoff;
+};
 // Grows each buffer to the byte count behind it, in the order given; the first failure ends it.
 static int grow_all() { return ZKV_OK; }
 template <class T, class... Rest> static int grow_all(DevBuf<T>& buf, size_t bytes, Rest&&... rest) {
@@ -172,7 +181,7 @@ struct CtxDevice : ChunkMem, AggMem {
     DevBuf<> d_blob, d_pv, d_cd[2], d_st_all, d_rv_all;
     // the families' staging: host-buffer batches, key-set host calls; demultiplexing, routing, key-set and set-inclusion buffers
     HostBatchMem m_host; KeySetHostMem m_kshost;
-    MixedMem m_mixed; GatewayMem m_gw; RouterMem m_rz; KeySetMem m_ks; SetInclMem m_si; GsetWireMem m_gsw;
+    MixedMem m_mixed; GatewayMem m_gw; RouterMem m_rz; KeySetMem m_ks; SetInclMem m_si; GsetWireMem m_gsw; PsetWireMem m_psw;
     DevEvent ev_fork, ev_join;                                 // small chunks: the G2 subgroup check runs beside the MSM (stream `side`)
     DevEvent ev_copied[2], ev_decoded[2];                      // wire layer: H2D of calldata chunk k+1 overlaps the kernels of chunk k
     DevEvent ev[6], ev_wire[2];
@@ -222,6 +231,8 @@ struct zkv_ctx : CtxDevice {
     // aggregate check on a PLONK set (zkv_plonk_set_agg.h): every key's SRS class and each class's first key (formed at creation), which
     // classes can take the check (read back the first time a call wants it), and per call every class's region (pset_agg_choose)
     std::vector<uint32_t> ps_class, ps_cls_rep; std::vector<uint8_t> ps_cls_ok; std::vector<uint64_t> ps_cbeg, ps_cend;
+    // A PLONK set of deployed contracts (zkv_plonk_set_wire.h; psw_tab empty: not one): the address table, ascending
+    std::vector<PswEntry> psw_tab;
     // Aggregate check (zkv_agg.h, zkv_ctx_set_aggregate_check): the switch and its policy state (the buffers: AggMem, CtxDevice)
     bool agg_on = false;
     uint32_t agg_sub = 32;                                     // proofs per sub-batch: 16, 32, 64, 128 or 256
@@ -4022,6 +4033,147 @@ ZKV_EXPORT int zkv_plonk_set_verify_batch(zkv_ctx* c, size_t n, const uint32_t* 
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return mark_done(c, c->stream);
+}
+
+// ------------------------------------------------------------------ PLONK key sets of deployed contracts: eth_call batches
+// (zkv_plonk_set_wire.h; parity unpinned).  k_pset_wire_decode turns every request into a row of the set's ordinary
+// inputs, k_pset_wire_points takes the key from a request with a point the precompiles refuse, run_pset runs on those rows as it runs on
+// a caller's, and k_pset_wire_return merges its verdicts with the classification.
+static const uint8_t* psw_selector() {
+    static const struct Sel { uint8_t b[2][4]; Sel() { host::fn_selector("Verify(bytes,uint256[])", b[0]); host::fn_selector("Error(string)", b[1]); } } s;
+    return &s.b[0][0];
+}
+ZKV_EXPORT int zkv_plonk_set_call_selector(uint8_t out[4]) {
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    memcpy(out, psw_selector(), 4);
+    return ZKV_OK;
+}
+static bool is_deployed_pset(const zkv_ctx* c) { return c && c->vm == ZKV_VM_PLONK_SET && !c->psw_tab.empty(); }
+ZKV_EXPORT zkv_ctx* zkv_plonk_set_create_deployed(size_t n_keys, const uint8_t* const* vk_bytes, const size_t* vk_len, const uint8_t* addresses, int device) {
+    if (!addresses) return nullptr;
+    zkv_ctx* c = zkv_plonk_set_create(n_keys, vk_bytes, vk_len, device);
+    if (!c) return nullptr;
+    try { c->psw_tab.resize(n_keys); } catch (const std::bad_alloc&) { delete c; return nullptr; }
+    for (size_t k = 0; k < n_keys; k++) {
+        PswEntry& e = c->psw_tab[k];
+        for (int j = 0; j < 5; j++) e.addr[j] = be32_of(addresses + 20 * k + 4 * j);
+        e.key = (uint32_t)k; e.nb = c->ps_raw[k].nb_public; e.n_c = c->ps_raw[k].n_c;
+    }
+    std::sort(c->psw_tab.begin(), c->psw_tab.end(), [](const PswEntry& a, const PswEntry& b) { return gsw_addr_cmp(a.addr, b.addr) < 0; });
+    for (size_t k = 1; k < n_keys; k++)
+        if (gsw_addr_cmp(c->psw_tab[k - 1].addr, c->psw_tab[k].addr) == 0) { delete c; return nullptr; }
+    return c;
+}
+ZKV_EXPORT int zkv_plonk_set_eth_call_returndata(uint8_t status, uint8_t reason, uint8_t out[ZKV_PLONK_RETURNDATA_STRIDE], uint32_t* out_len, uint8_t* reverted) {
+    if (!out || !out_len || !reverted) return ZKV_ERR_INVALID_ARG;
+    static const char* const MSG[6] = {"", "wrong number of public inputs", "inputs are bigger than r", "wrong proof size", "openings bigger than r",
+                                       "error ec operation"};
+    *out_len = 0;
+    if (reason == ZKV_PLONK_REVERT_NONE) {
+        if (status == ZKV_STATUS_NO_CONTRACT) { *reverted = 0; return ZKV_OK; }         // an address without code: success, no data
+        if (status == ZKV_STATUS_BAD_CALLDATA) { *reverted = 1; return ZKV_OK; }        // the contract's dispatcher or ABI decoder reverts with no data
+        if (status != ZKV_STATUS_OK && status != ZKV_STATUS_VERIFICATION_FAILED) return ZKV_ERR_INVALID_ARG;
+        *reverted = 0; *out_len = 32;                                                   // returns (bool)
+        memset(out, 0, 32);
+        out[31] = status == ZKV_STATUS_OK ? 1 : 0;
+        return ZKV_OK;
+    }
+    if (reason > ZKV_PLONK_REVERT_EC_OPERATION ||
+        status != (reason == ZKV_PLONK_REVERT_INPUT_RANGE ? ZKV_STATUS_INPUT_NOT_IN_FIELD : ZKV_STATUS_INVALID_PROOF_DATA)) return ZKV_ERR_INVALID_ARG;
+    const size_t len = strlen(MSG[reason]);                                             // Error(string): selector, offset 0x20, length, the message padded to 32
+    memset(out, 0, 100);
+    memcpy(out, psw_selector() + 4, 4);
+    out[35] = 0x20; out[67] = (uint8_t)len;
+    memcpy(out + 68, MSG[reason], len);
+    *reverted = 1; *out_len = 100;
+    return ZKV_OK;
+}
+// Addresses, calldata and its n + 1 offsets on the device (c->mu held, device set up and ordered after the previous call).  Decode and
+// point test are enqueued in front of the partition, so the call synchronises where run_pset does; d_key: the resolved keys go there.
+static int run_pset_wire(zkv_ctx* c, size_t n, const uint8_t* d_to, const uint8_t* d_cd, const uint64_t* d_off, uint64_t cd_bytes, uint8_t* d_status,
+                         uint8_t* d_reason, uint32_t* d_key, hipStream_t s) {
+    int rc;
+    PsetWireMem& pm = c->m_psw;
+    const size_t ps = pset_proof_stride(c), is = pset_input_stride(c);
+    if ((rc = grow_all(pm.key, 4 * n, pm.rkey, d_key ? 0 : 4 * n, pm.proofs, ps * n, pm.rows, is * n + 8, pm.verdict, n, pm.reason, n, pm.npt, n, pm.ec, n,
+                       pm.verified, n, pm.cnt, 8 * sizeof(unsigned long long))) != ZKV_OK) return rc;
+    if (!pm.tab) {                                               // once per device set-up: the table is the context's own, sorted at creation
+        if ((rc = pm.tab.alloc(sizeof(PswEntry) * c->psw_tab.size())) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpy(pm.tab, c->psw_tab.data(), sizeof(PswEntry) * c->psw_tab.size(), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemsetAsync(pm.cnt, 0, 8 * sizeof(unsigned long long), s));
+    PswArgs w;
+    memset(&w, 0, sizeof w);
+    w.n = n; w.to = d_to; w.cd = d_cd; w.off = d_off; w.cd_bytes = cd_bytes;
+    w.tab = pm.tab; w.n_tab = (uint32_t)c->psw_tab.size(); w.sel_be = be32_of(psw_selector());
+    w.key = pm.key; w.rkey = d_key ? d_key : (uint32_t*)pm.rkey; w.proofs = pm.proofs; w.proof_stride = (uint32_t)ps; w.rows = pm.rows; w.input_stride = (uint32_t)is;
+    w.verdict = pm.verdict; w.reason = pm.reason; w.npt = pm.npt; w.ec = pm.ec;
+    (void)hipEventRecord(c->ev_wire[0], s);
+    launch_pset_wire_decode(w, s);
+    launch_pset_wire_points(w, s);
+    (void)hipEventRecord(c->ev_wire[1], s);
+    c->wire_timed = true;
+    HIP_TRY(hipGetLastError());
+    if ((rc = run_pset(c, n, pm.key, pm.proofs, is ? (const uint8_t*)pm.rows : nullptr, pm.verified, s)) != ZKV_OK) return rc;
+    launch_pset_wire_return(n, pm.verdict, pm.reason, pm.ec, pm.verified, d_status, d_reason, pm.cnt, s);
+    HIP_TRY(hipGetLastError());
+    return mark_done(c, s);
+}
+ZKV_EXPORT int zkv_plonk_set_eth_call_batch_dev(zkv_ctx* c, size_t n, const uint8_t* d_to, const uint8_t* d_calldata, const uint64_t* d_calldata_off,
+                                                uint64_t calldata_bytes, uint8_t* d_status, uint8_t* d_reason, uint32_t* d_key, void* stream) {
+    if (!is_deployed_pset(c)) return ZKV_ERR_WRONG_CTX;
+    if (n && (!d_to || !d_calldata || !d_calldata_off || !d_status)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_ready(c, n);
+    if (rc != ZKV_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+    return run_pset_wire(c, n, d_to, d_calldata, d_calldata_off, calldata_bytes, d_status, d_reason, d_key, s);
+}
+ZKV_EXPORT int zkv_plonk_set_eth_call_batch(zkv_ctx* c, size_t n, const uint8_t* to, const uint8_t* blob, const uint64_t* off, uint8_t* reverted,
+                                            uint8_t* returndata, uint32_t* returndata_len, uint8_t* status, uint8_t* reason) {
+    if (!is_deployed_pset(c)) return ZKV_ERR_WRONG_CTX;
+    if (n && (!to || !blob || !off || !reverted || !returndata || !returndata_len)) return ZKV_ERR_INVALID_ARG;
+    if (!n) return ZKV_OK;
+    if (n > 0xFFFFFFF0u) return ZKV_ERR_INVALID_ARG;
+    std::vector<uint8_t> st(n), rs(n);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        int rc = ctx_ready(c, n);
+        if (rc != ZKV_OK) return rc;
+        const uint64_t bytes = off[n];                           // the blob; a request may still run backwards or past it
+        PsetWireMem& pm = c->m_psw;
+        if ((rc = grow_all(pm.h_to, 20 * n, pm.h_cd, (size_t)bytes + 8, pm.h_cdoff, 8 * (n + 1), pm.h_st, n, pm.h_rs, n)) != ZKV_OK) return rc;
+        hipStream_t s = c->stream;
+        if ((rc = order_after_previous(c, s)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(pm.h_to, to, 20 * n, hipMemcpyHostToDevice, s));
+        if (bytes) HIP_TRY(hipMemcpyAsync(pm.h_cd, blob, (size_t)bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(pm.h_cdoff, off, 8 * (n + 1), hipMemcpyHostToDevice, s));
+        if ((rc = run_pset_wire(c, n, pm.h_to, pm.h_cd, pm.h_cdoff, bytes, pm.h_st, pm.h_rs, nullptr, s)) != ZKV_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(st.data(), pm.h_st, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(rs.data(), pm.h_rs, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (size_t i = 0; i < n; i++) {
+        const int rc = zkv_plonk_set_eth_call_returndata(st[i], rs[i], returndata + i * ZKV_PLONK_RETURNDATA_STRIDE, &returndata_len[i], &reverted[i]);
+        if (rc != ZKV_OK) return rc;
+        if (status) status[i] = st[i];
+        if (reason) reason[i] = rs[i];
+    }
+    return ZKV_OK;
+}
+ZKV_EXPORT int zkv_plonk_set_last_call_counts(zkv_ctx* c, uint64_t out[8]) {
+    if (!is_deployed_pset(c)) return ZKV_ERR_WRONG_CTX;
+    if (!out) return ZKV_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    memset(out, 0, 8 * sizeof(uint64_t));
+    if (!c->dev_ready || !c->m_psw.cnt || !c->has_done) return ZKV_OK;       // no eth_call batch has run
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(c->ev_done));
+    HIP_TRY(hipMemcpy(out, c->m_psw.cnt, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return ZKV_OK;
 }
 
 // ------------------------------------------------------------------ Groth16 core pieces

@@ -239,6 +239,15 @@ struct GswArgs;
 void launch_gset_wire_decode(const GswArgs& a, hipStream_t s);
 void launch_gset_wire_return(size_t n, const uint8_t* verdict, const uint8_t* ge_r, const uint8_t* verified, uint8_t* status,
                              unsigned long long* counts, hipStream_t s);
+// eth_call calldata of a set of deployed PLONK contracts (k_pset_wire.hip; zkv_wire_pset.h has the rules and PswArgs): one request per
+// lane into the PLONK set's ordinary inputs, the curve test of the copied proofs' points, then, behind the set's pipeline, one lane per
+// request for status and reason (may be null) and the eight totals (counts: placed, no contract, bad calldata, reasons 1 .. 5 -- added
+// to, so zeroed by the host).
+struct PswArgs;
+void launch_pset_wire_decode(const PswArgs& a, hipStream_t s);
+void launch_pset_wire_points(const PswArgs& a, hipStream_t s);
+void launch_pset_wire_return(size_t n, const uint8_t* verdict, const uint8_t* reason_in, const uint8_t* ec, const uint8_t* verified, uint8_t* status,
+                             uint8_t* reason, unsigned long long* counts, hipStream_t s);
 // SP1 gateway, keyed Groth16 routes (k_gateway_keys.hip; include/zkv_sp1_gateway_keys.h): PREP of slots [slot0, slot0 + m) of the keyed
 // group, the gateway's routes with caller keys as one key set.  Every per-slot table is the group's (index 0 = its first slot): the
 // demultiplexer's compact outputs -- caller index (GW_NONE: pad slot), 260-byte records, true lengths, program vkeys, (offset, length)

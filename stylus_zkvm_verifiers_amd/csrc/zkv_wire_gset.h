@@ -21,8 +21,10 @@ ZKV_HD int gsw_addr_cmp(const uint32_t a[5], const uint32_t b[5]) {
     for (int k = 0; k < 5; k++) if (a[k] != b[k]) return a[k] < b[k] ? -1 : 1;
     return 0;
 }
-// Index of the entry with address `to` (20 bytes, any alignment) among tab[0 .. n), GSW_NONE when there is none.
-ZKV_HD uint32_t gsw_find(const GswEntry* tab, uint32_t n, const uint8_t* to) {
+// Index of the entry with address `to` (20 bytes, any alignment) among tab[0 .. n), GSW_NONE when there is none.  Entry: GswEntry, or
+// the entry of another kind of deployed set (zkv_wire_pset.h) -- anything with addr[5].
+template <class Entry>
+ZKV_HD uint32_t gsw_find(const Entry* tab, uint32_t n, const uint8_t* to) {
     uint32_t a[5];
     for (int k = 0; k < 5; k++) a[k] = load_be32(to + 4 * k);
     uint32_t lo = 0, hi = n;                              // the entry, if any, is in [lo, hi)
